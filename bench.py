@@ -41,6 +41,9 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 HBM_PEAK_MEASURED_GBS = 6300.0   # what a streaming read of K5's access pattern (46 KB runs from ~6 000 waves) reaches on this part: tools/ubench/stream46k, docs/history.md section 6
 TRAFFIC_FILES = [os.path.join(ROOT, "profiles", f) for f in ("r06_traffic.json", "r05_traffic.json", "r04_traffic.json")]   # the newest committed PMC summary that exists
+DUMP_BYTES = 64 << 20           # --dump-outputs: at most this many bytes in all
+DUMP_WHOLE_BYTES = 1 << 20      # arrays up to this size are always written whole
+DUMP_SEED = 20261015            # the row sample of larger arrays when everything does not fit
 
 
 def parse_args():
@@ -91,7 +94,15 @@ def parse_args():
     ap.add_argument("--cpu-threads", type=int, default=0, help="oracle threads for cpu_baseline (0 = all host cores)")
     ap.add_argument("--cpu-sample-genomes", type=int, default=100, help="at least this many contigs in the CPU sample reference ...")
     ap.add_argument("--cpu-sample-bases", type=float, default=1.0e9, help="... and at least this many bases (filled up with further contigs of the bench reference)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (mapping records, EM abundances, log-likelihoods, posteriors, best "
+                         "mapping per read) as DIR/<name>.npy in float64, at most 64 MB in all (dump_outputs); default config only, rank 0")
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != 1:
+        ap.error("--dump-outputs covers the default config only")
+    return args
 
 
 def build_reference(ctx, args, shape):
@@ -110,6 +121,34 @@ def build_reference(ctx, args, shape):
     desc = (f"community (SURVEY D1): {ng} microbial genomes in {sp} species / {ge} genera, lognormal lengths, 0.1-5 % strain divergence + block indels, "
             f"{human} human-like contigs ({int(3.1e9 * min(args.scale, 1.0))} bp, 45 % library repeats, 1 % N), contigs shuffled")
     return ref, genome.astype(np.int32), ng + 1, desc
+
+
+def step_outputs(off, rec, f, lls, post, best):
+    """what one step of the timed path hands its caller, as named 1-D float64 arrays (copies: `rec` is a view of a reused buffer)"""
+    out = {"mapping_offsets": off}
+    for name in rec.dtype.names:
+        out["mapping_" + name] = rec[name]
+    out.update(em_abundance=f, em_loglik=lls, em_posterior=post, em_best_mapping=best)
+    return {n: np.array(a, dtype=np.float64) for n, a in out.items()}
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy.  When they do not fit DUMP_BYTES together, every array larger than DUMP_WHOLE_BYTES
+    is cut to the same fraction of its rows, drawn by a generator seeded with DUMP_SEED (the same rows for the same length on every run);
+    the row numbers go beside it as DIR/<name>.rows.npy"""
+    os.makedirs(outdir, exist_ok=True)
+    budget = DUMP_BYTES - 2 * 4096 * len(arrays)                   # (room for the .npy headers)
+    big = {n for n, a in arrays.items() if a.nbytes > DUMP_WHOLE_BYTES}
+    small_bytes = sum(a.nbytes for n, a in arrays.items() if n not in big)
+    big_bytes = sum(arrays[n].nbytes for n in big)
+    frac = 1.0 if small_bytes + big_bytes <= budget else (budget - small_bytes) / (2 * big_bytes)   # (row numbers: as many bytes as the rows)
+    for n, a in arrays.items():
+        if n in big and frac < 1.0:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, int(a.size * frac), replace=False))
+            np.save(os.path.join(outdir, n + ".rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(outdir, n + ".npy"), a)
+    return frac
 
 
 def default_steps(args):
@@ -170,8 +209,9 @@ def main():
         for c in ctxs:
             c.synchronize()
 
-    def run_shape(shape, steps, warmup):
-        """setup (untimed) + warm-up + `steps` timed steps on one reference shape; returns everything the report needs"""
+    def run_shape(shape, steps, warmup, keep_outputs=False):
+        """setup (untimed) + warm-up + `steps` timed steps on one reference shape; returns everything the report needs (with keep_outputs,
+        also what the last timed step returned: step_outputs)"""
         t0 = time.time()
         ref, contig_taxon, n_taxa, desc = build_reference(ctx, args, shape)
         ctx.synchronize()
@@ -210,6 +250,7 @@ def main():
         hold_lock = [bool(args.hold_lock_to_the_end)]
         em_turn = {"next": 0, "cv": threading.Condition()}
         em_wall = [0.0, 0]                                            # seconds inside em.run, iterations
+        last = {"ticket": None}                                      # keep_outputs: the ticket of the last timed step, then its results
 
         def step(wi, serialise=True, ticket=0):
             """serialise: True (default) — one lock around the mapping section of a step, released when its last big kernel (K5) is
@@ -267,6 +308,8 @@ def main():
             post, best = em.posteriors(f)
             em.close()
             tt.append(time.perf_counter())
+            if ticket == last["ticket"]:
+                last["out"] = (off, rec, f, lls, post, best)
             if os.environ.get("MM_BENCH_STEP_LOG"):                  # per step: worker, batch, host sections and the device's stage times (which step of the timed region is long, and where)
                 print(f"STEPLOG ticket {ticket} worker {wi} batch {ticket % B}: start {tt[0] * 1e3:.1f} map_batch {(tt[1] - tt[0]) * 1e3:.1f} mapq+fetch {(tt[2] - tt[1]) * 1e3:.1f} "
                       f"em {(tt[3] - tt[2]) * 1e3:.1f} post {(tt[4] - tt[3]) * 1e3:.1f} end {tt[4] * 1e3:.1f} | device ms: K1 {st['ms_minimizer']:.1f} K2 {st['ms_sketch']:.1f} K3 {st['ms_probe_gather']:.1f} "
@@ -304,9 +347,15 @@ def main():
         barrier()
         t0 = time.perf_counter()
         if os.environ.get("MM_ALLOC_TRACE"): print(f"MM_ALLOC_TRACE (bench) timed region starts at {time.time() * 1e3:.1f} ms", file=sys.stderr, flush=True)
+        if keep_outputs:
+            last["ticket"] = step_base[0] + steps - 1
         run_steps(steps, sched)
         barrier()
         dt = time.perf_counter() - t0
+        outputs = None
+        if keep_outputs:                                            # copied before any further step reuses the worker's record buffer
+            outputs = step_outputs(*last.pop("out"))
+            last["ticket"] = None
         if os.environ.get("MM_ALLOC_TRACE"): print(f"MM_ALLOC_TRACE (bench) timed region ends at {time.time() * 1e3:.1f} ms", file=sys.stderr, flush=True)
         if os.environ.get("MM_BENCH_RANK_LOG"):                       # tools/scale_check.sh: what every rank saw
             nr, rk = ctx.comm_info()
@@ -360,7 +409,7 @@ def main():
             bases_all = bases_timed
         return dict(ref=ref, idx=idx, reads=reads, reads_w=batches, truth=truth, contig_taxon=contig_taxon, info=info, desc=desc, t_ref=t_ref, t_index=t_index, free=free,
                     agg=agg, st=st, st_clean=st_clean, same_batch=same, dt=dt, steps=steps, bases_all=bases_all, value=bases_all / dt / 1e9, ms_step=dt / steps * 1e3, step_ms=step_ms,
-                    n_batches=B, freq_threshold=idx.freq_threshold, reference_bp=int(ref.total_bases))
+                    n_batches=B, freq_threshold=idx.freq_threshold, reference_bp=int(ref.total_bases), outputs=outputs)
 
     if args.config == 5 and args.scale == 1.0:
         args.scale = 11.2                                          # SURVEY D1, DB-refseq-scale: 140 000 genomes, ~300 Gbp
@@ -383,7 +432,11 @@ def main():
             dist.destroy_process_group()
         return
 
-    R = run_shape(args.shape, args.steps, args.warmup)
+    R = run_shape(args.shape, args.steps, args.warmup, keep_outputs=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        frac = dump_outputs(args.dump_outputs, R.pop("outputs"))
+        print(f"--dump-outputs: the last timed step's results in {args.dump_outputs}" + ("" if frac == 1.0 else f" (arrays over {DUMP_WHOLE_BYTES >> 20} MB: "
+              f"a seeded sample of {frac:.3f} of their rows)"), file=sys.stderr, flush=True)
 
     out = None
     if rank == 0:

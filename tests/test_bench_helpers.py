@@ -43,3 +43,55 @@ def test_bench_arguments_parse():
     finally:
         sys.argv = argv
     assert a.shape == "community" and a.reads == 100_000 and a.read_len == 10_000 and a.window == 8
+
+
+def _parse(*extra):
+    import sys
+    import bench
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1"] + list(extra)
+        return bench.parse_args()
+    finally:
+        sys.argv = argv
+
+
+def test_bench_steps_and_dump_arguments():
+    import pytest
+    a = _parse("--steps", "5", "--warmup", "0", "--dump-outputs", "d")
+    assert a.steps == 5 and a.warmup == 0 and a.dump_outputs == "d"
+    for bad in (("--steps", "0"), ("--config", "3", "--dump-outputs", "d")):
+        with pytest.raises(SystemExit):
+            _parse(*bad)
+
+
+def test_step_outputs_and_dump_within_budget(tmp_path, monkeypatch):
+    """what a step returns, as float64 arrays; all of it when it fits, else the same seeded rows of the large arrays, under the budget"""
+    import bench
+    from metamaps_amd import capi
+    rng = np.random.default_rng(1)
+    rec = np.zeros(5000, dtype=capi.RECORD_DTYPE)
+    rec["ref_contig"] = rng.integers(0, 2**31 - 1, len(rec)); rec["mapq"] = rng.random(len(rec))
+    off = np.linspace(0, len(rec), 1001).astype(np.int64)
+    out = bench.step_outputs(off, rec, rng.random(30), rng.random(7), rng.random(len(rec)), rng.integers(0, len(rec), 1000))
+    assert all(a.dtype == np.float64 and a.ndim == 1 for a in out.values())
+    assert np.array_equal(out["mapping_ref_contig"], rec["ref_contig"]) and np.array_equal(out["mapping_offsets"], off)
+
+    assert bench.dump_outputs(str(tmp_path / "all"), out) == 1.0
+    for n, a in out.items():
+        assert np.array_equal(np.load(str(tmp_path / "all" / (n + ".npy"))), a)
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 120_000)              # a budget the records do not fit: scaled down
+    monkeypatch.setattr(bench, "DUMP_WHOLE_BYTES", 1_000)
+    d1, d2 = tmp_path / "s1", tmp_path / "s2"
+    frac = bench.dump_outputs(str(d1), out)
+    assert 0.0 < frac < 1.0 and bench.dump_outputs(str(d2), out) == frac
+    assert sum(p.stat().st_size for p in d1.iterdir()) <= 120_000
+    for n, a in out.items():
+        got = np.load(str(d1 / (n + ".npy")))
+        assert np.array_equal(got, np.load(str(d2 / (n + ".npy"))))
+        if a.nbytes > 1_000:
+            rows = np.load(str(d1 / (n + ".rows.npy"))).astype(np.int64)
+            assert np.array_equal(got, a[rows]) and len(rows) == int(a.size * frac)
+        else:
+            assert np.array_equal(got, a) and not (d1 / (n + ".rows.npy")).exists()

@@ -1,10 +1,11 @@
 """Pins the oracle (oracle/) against everything the reference itself offers for this path:
-  * the real reference murmur header compiled in place (oracle/_ref, only where /root/reference exists),
+  * the real reference murmur header: its answers pinned in tests/golden/ref_golden.json, and compiled in place (oracle/_ref) where built,
   * the reference's example outputs (tests/golden/example/*, a real miniSeq+H run of the reference),
   * Boost.Math's own answers for the binomial calls (tests/golden/binom_golden.json, via scipy),
   * the known answers the survey recorded from the reference.
 CPU only."""
 import ctypes as C
+import hashlib
 import json
 import math
 import os
@@ -26,17 +27,31 @@ def test_murmur_known_answers(oracle_lib):
         assert oracle_lib.kmer_hash(s, 16) == v
 
 
-def test_murmur_against_real_reference_header(oracle_lib):
-    import orc
-    if not os.path.exists(orc.REF_LIB):
-        pytest.skip("oracle/_ref not built (no /root/reference on this box)")
-    ref = C.CDLL(orc.REF_LIB)
-    ref.ref_kmer_hash.restype = C.c_uint32
+def murmur_cases():
     rnd = random.Random(9)
+    cases = []
     for _ in range(20000):
         k = rnd.randint(1, 80)
-        s = bytes(rnd.choice(b"ACGTNacgtRYKM") for _ in range(k))
-        assert oracle_lib.kmer_hash(s, k) == ref.ref_kmer_hash(s, k)
+        cases.append((bytes(rnd.choice(b"ACGTNacgtRYKM") for _ in range(k)), k))
+    return cases
+
+
+def murmur_digest(values) -> str:
+    return hashlib.sha256(np.asarray(values, dtype="<u4").tobytes()).hexdigest()[:24]
+
+
+def test_murmur_against_real_reference_header(oracle_lib):
+    """against the reference header's answers, pinned in tests/golden/ref_golden.json (tests/golden/make_ref_golden.py); where
+    oracle/_ref is built, against the header compiled in place as well"""
+    import orc
+    cases = murmur_cases()
+    got = [oracle_lib.kmer_hash(s, k) for s, k in cases]
+    if os.path.exists(orc.REF_LIB):
+        ref = C.CDLL(orc.REF_LIB)
+        ref.ref_kmer_hash.restype = C.c_uint32
+        for (s, k), g in zip(cases, got):
+            assert g == ref.ref_kmer_hash(s, k), (s, k)
+    assert murmur_digest(got) == json.load(open(os.path.join(HERE, "golden", "ref_golden.json")))["murmur"]
 
 
 def test_minimizer_known_answer(oracle_lib):

@@ -5,9 +5,16 @@ reference's meta/util.h split() and overlap() against the host's and the oracle'
 every sequence the path ever sees (winSketch.hpp:245-252, computeMap.hpp:123-134, mapWrap.h:107-114) from "restated" into
 "pinned by reference code run here".
 
-CPU only.  oracle/_ref/ is built by __graft_entry__.build() wherever /root/reference exists; elsewhere these tests skip."""
+What the reference's code answered on every input below is pinned in tests/golden/ref_golden.json (sha256 digests, written by
+tests/golden/make_ref_golden.py from oracle/_ref/ref_host), so that these tests need nothing outside the repository.  Where
+oracle/_ref/ is built (__graft_entry__.build() builds it wherever the reference tree exists) the live reference is run as well and
+must still give the pinned answers.
+
+CPU only."""
 import ctypes as C
 import gzip
+import hashlib
+import json
 import os
 import random
 import subprocess
@@ -17,15 +24,29 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 REF = os.path.join(ROOT, "oracle", "_ref", "ref_host")
+GOLDEN = os.path.join(HERE, "golden", "ref_golden.json")
+
+
+class Ref:
+    """the reference's answers: the pinned digests, and the live oracle/_ref/ref_host where it is built (None elsewhere)"""
+    def __init__(self, exe):
+        self.exe = exe
+        self.golden = json.load(open(GOLDEN))
 
 
 @pytest.fixture(scope="module")
 def ref():
-    if os.path.isdir("/root/reference/src"):
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True, timeout=600)
-    if not os.path.exists(REF):
-        pytest.skip("oracle/_ref/ref_host is not built (no reference tree on this machine)")
-    return REF
+    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True, timeout=600)   # (a no-op without the reference tree)
+    return Ref(REF if os.path.exists(REF) else None)
+
+
+def digest(data: bytes) -> str:
+    return hashlib.sha256(data).hexdigest()[:24]
+
+
+def kseq_digest(lines, code) -> str:
+    """one digest over the records of a read loop and the code that ended it (the output format of `ref_host kseq`)"""
+    return digest(("".join(l + "\n" for l in lines) + "END %d\n" % code).encode("latin-1"))
 
 
 @pytest.fixture(scope="module")
@@ -42,10 +63,10 @@ def host_util(tmp_path_factory):
     return e
 
 
-def _kseq(ref, path):
+def _kseq(exe, path):
     """records of the real kseq_read loop (or None where the reference itself crashes, e.g. an empty first record: kseq.h:189
     writes through a buffer it never allocated)"""
-    r = subprocess.run([ref, "kseq", path], capture_output=True, timeout=120)
+    r = subprocess.run([exe, "kseq", path], capture_output=True, timeout=120)
     if r.returncode != 0:
         return None
     lines = r.stdout.decode("latin-1").splitlines()
@@ -73,17 +94,21 @@ def _host_reader(exe, path):
     return seq, blocks_ok
 
 
-def _check(ref, oracle_lib, exe, path):
-    k = _kseq(ref, path)
-    if k is None:
+def _check(ref, oracle_lib, exe, path, key):
+    """the oracle's and the host's readers against what the reference's reader gave on this input (pinned under `key`);
+    False where the reference crashes on it"""
+    pin = ref.golden["kseq"][key]
+    if ref.exe is not None:
+        k = _kseq(ref.exe, path)
+        assert (k and [kseq_digest(*k), len(k[0])]) == (pin or None), (key, "the live reference no longer gives the pinned answer")
+    if pin is None:
         return False
-    want, code = k
+    want, n_want = pin
     got_o, code_o = _oracle_reader(oracle_lib, path)
-    assert got_o == want, (path, "oracle reader", len(got_o), len(want))
-    assert code_o == code
+    assert kseq_digest(got_o, code_o) == want, (key, "oracle reader", len(got_o), n_want)
     got_h, blocks_ok = _host_reader(exe, path)
-    assert got_h == want, (path, "host reader", len(got_h), len(want))
-    assert blocks_ok in (None, True), (path, "block parser differs from the sequential parse")
+    assert got_h == got_o, (key, "host reader", len(got_h), n_want)
+    assert blocks_ok in (None, True), (key, "block parser differs from the sequential parse")
     return True
 
 
@@ -135,64 +160,84 @@ def test_readers_equal_real_kseq(ref, oracle_lib, host_reader, tmp_path, layout)
     p = str(tmp_path / "in.fq")
     with open(p, "wb") as f:
         f.write(LAYOUTS[layout].encode("latin-1"))
-    assert _check(ref, oracle_lib, host_reader, p), "the reference's reader crashed on a curated layout"
+    assert _check(ref, oracle_lib, host_reader, p, layout), "the reference's reader crashed on a curated layout"
     with open(p, "rb") as f, gzip.open(p + ".gz", "wb") as g:    # the same bytes through zlib (winSketch.hpp:245-248 opens everything with gzopen)
         g.write(f.read())
-    assert _check(ref, oracle_lib, host_reader, p + ".gz")
+    assert _check(ref, oracle_lib, host_reader, p + ".gz", layout + ".gz")
     if layout == "no_newline_before_next_record":               # the quirk is observable: kseq.h:200 eats the '@' that follows the qualities
-        assert [l.split()[0] for l in _kseq(ref, p)[0]] == ["r0", "r2"]
+        assert [l.split()[0] for l in _oracle_reader(oracle_lib, p)[0]] == ["r0", "r2"]   # (the oracle's records are the reference's: _check)
+
+
+def soup(seed):
+    """the file of byte soup number `seed`"""
+    rng = random.Random(seed)
+    kind = seed % 4
+    if kind == 0:     # pure soup
+        alpha = "@>+\n\n\r \tACGTacgtnN!~I5" + ("\x80" if seed % 8 == 0 else "")
+        body = "".join(rng.choice(alpha) for _ in range(rng.choice([30, 300, 5000, 20000])))
+    else:             # records with random damage
+        parts = []
+        for i in range(rng.randrange(1, 25)):
+            n = rng.choice([1, 5, 60, 200, 1500, 4096, 6000])
+            sq = _seq(rng, n, "ACGTacgtN")
+            ql = n + rng.choice([0, 0, 0, 0, 1, -1, 5, -5]) if kind == 3 else n
+            qu = _seq(rng, max(ql, 0), "I5?~!@>+" if kind >= 2 else "I5?~!")
+            if rng.random() < 0.3:
+                parts.append(f">f{i} c\n" + "\n".join(sq[j:j + 70] for j in range(0, n, 70)) + "\n")
+            else:
+                nl = "" if (kind == 3 and rng.random() < 0.2) else "\n"
+                wrap = rng.random() < 0.2 and n > 10
+                sl = sq[:n // 2] + "\n" + sq[n // 2:] if wrap else sq
+                parts.append(f"@q{i}{rng.choice(['', ' c', chr(9) + 'c'])}\n{sl}\n+{rng.choice(['', 'x'])}\n{qu}{nl}")
+        body = "".join(parts)
+        if kind == 3 and rng.random() < 0.5:
+            body = body[:rng.randrange(len(body) // 2, len(body))]
+    return "@first\nACGT\n+\nIIII\n" + body
+
+
+SOUP_SEEDS = range(500)
 
 
 def test_readers_equal_real_kseq_on_byte_soup(ref, oracle_lib, host_reader, tmp_path):
     """random files over an alphabet of everything kseq treats specially: 500 seeds, 30 bytes to 20 kb (kseq's buffer is 4096 bytes)"""
     crashed = 0
-    for seed in range(500):
-        rng = random.Random(seed)
-        kind = seed % 4
-        if kind == 0:     # pure soup
-            alpha = "@>+\n\n\r \tACGTacgtnN!~I5" + ("\x80" if seed % 8 == 0 else "")
-            body = "".join(rng.choice(alpha) for _ in range(rng.choice([30, 300, 5000, 20000])))
-        else:             # records with random damage
-            parts = []
-            for i in range(rng.randrange(1, 25)):
-                n = rng.choice([1, 5, 60, 200, 1500, 4096, 6000])
-                sq = _seq(rng, n, "ACGTacgtN")
-                ql = n + rng.choice([0, 0, 0, 0, 1, -1, 5, -5]) if kind == 3 else n
-                qu = _seq(rng, max(ql, 0), "I5?~!@>+" if kind >= 2 else "I5?~!")
-                if rng.random() < 0.3:
-                    parts.append(f">f{i} c\n" + "\n".join(sq[j:j + 70] for j in range(0, n, 70)) + "\n")
-                else:
-                    nl = "" if (kind == 3 and rng.random() < 0.2) else "\n"
-                    wrap = rng.random() < 0.2 and n > 10
-                    sl = sq[:n // 2] + "\n" + sq[n // 2:] if wrap else sq
-                    parts.append(f"@q{i}{rng.choice(['', ' c', chr(9) + 'c'])}\n{sl}\n+{rng.choice(['', 'x'])}\n{qu}{nl}")
-            body = "".join(parts)
-            if kind == 3 and rng.random() < 0.5:
-                body = body[:rng.randrange(len(body) // 2, len(body))]
-        body = "@first\nACGT\n+\nIIII\n" + body
+    for seed in SOUP_SEEDS:
+        body = soup(seed)
         p = str(tmp_path / f"s{seed}.fq")
         with open(p, "wb") as f:
             f.write(body.encode("latin-1"))
-        crashed += not _check(ref, oracle_lib, host_reader, p)
+        crashed += not _check(ref, oracle_lib, host_reader, p, f"soup{seed}")
         os.unlink(p)
     assert crashed <= 25, crashed                                # (the reference's reader crashes on a few soups; those cases prove nothing)
 
 
-def test_split_equals_reference_util_h(ref, host_util):
+SPLIT_DELIMS = (" ", ";", "=", "|", "\t", "ab", "  ")
+
+
+def split_lines():
     rng = random.Random(3)
     lines = ["", " ", "a", "a b", "a  b", " a b ", "x;y;;z;", "k=v", "=", "1 C1=100;C2=200", "a||b|", "|", "tab\there", "ab" * 50]
     for _ in range(300):
         lines.append("".join(rng.choice("ab ;=|\t") for _ in range(rng.randrange(0, 30))))
+    return lines
+
+
+def test_split_equals_reference_util_h(ref, host_util):
+    lines = split_lines()
     data = ("\n".join(lines) + "\n").encode()
-    for delim in (" ", ";", "=", "|", "\t", "ab", "  "):
-        want = subprocess.run([ref, "split", delim], input=data, capture_output=True, check=True, timeout=60).stdout
+    for delim in SPLIT_DELIMS:
+        want = ref.golden["split"][delim]
+        if ref.exe is not None:
+            live = subprocess.run([ref.exe, "split", delim], input=data, capture_output=True, check=True, timeout=60).stdout
+            assert len(live.splitlines()) == len(lines)
+            assert digest(live) == want, (delim, "the live reference no longer gives the pinned answer")
         for who in ("host", "oracle"):
             got = subprocess.run([host_util, who, "split", delim], input=data, capture_output=True, check=True, timeout=60).stdout
-            assert got == want, (who, delim)
-        assert len(want.splitlines()) == len(lines)
+            assert len(got.splitlines()) == len(lines), (who, delim)
+            assert digest(got) == want, (who, delim)
 
 
-def test_overlap_equals_reference_util_h(ref, host_util):
+def overlap_cases():
     """util.h overlap() over the domain classify reaches (fEM.h:757-773: a 1000-base window clipped to the contig against a read's
     mapping clipped to the contig) and over random interval pairs; the reference asserts left < right for both intervals, so
     one-base intervals (a contig of 1000 k + 1 bases has a one-base last window: the reference aborts there) are left out"""
@@ -212,9 +257,18 @@ def test_overlap_equals_reference_util_h(ref, host_util):
     for _ in range(3000):
         a, c = rng.randrange(0, 5000), rng.randrange(0, 5000)
         cases.append((a, a + rng.randrange(1, 3000), c, c + rng.randrange(1, 3000)))
+    return cases
+
+
+def test_overlap_equals_reference_util_h(ref, host_util):
+    cases = overlap_cases()
     data = "".join("%d %d %d %d\n" % t for t in cases).encode()
-    want = subprocess.run([ref, "overlap"], input=data, capture_output=True, check=True, timeout=60).stdout
-    assert len(want.splitlines()) == len(cases)
+    want = ref.golden["overlap"]
+    if ref.exe is not None:
+        live = subprocess.run([ref.exe, "overlap"], input=data, capture_output=True, check=True, timeout=60).stdout
+        assert len(live.splitlines()) == len(cases)
+        assert digest(live) == want, "the live reference no longer gives the pinned answer"
     for who in ("host", "oracle"):
         got = subprocess.run([host_util, who, "overlap"], input=data, capture_output=True, check=True, timeout=60).stdout
-        assert got == want, who
+        assert len(got.splitlines()) == len(cases), who
+        assert digest(got) == want, who
