@@ -75,6 +75,12 @@ int mm_seqset_add(mm_seqset* s, const char* ascii, int64_t len);   /* host stagi
 /* same, without the copy: the caller keeps `ascii` valid and unchanged until mm_seqset_upload has returned (a parser that
  * fills one arena per batch hands its records over this way) */
 int mm_seqset_add_view(mm_seqset* s, const char* ascii, int64_t len);
+/* BAM's packed form of a read: n_bases 4-bit codes of "=ACMGRSVTWYHKDBN", two per byte, the first in the high nibble (the `seq` field of a
+ * BAM record, (n_bases + 1) / 2 bytes).  reverse != 0: the codes are the reverse complement of the read (BAM flag 0x10), which is stored
+ * turned back — as `samtools fastq` writes it.  The set then holds what mm_seqset_add of that read in ASCII would give, byte for byte (codes
+ * other than A/C/G/T become exception runs of their letter).  A view, like mm_seqset_add_view: `nt16` stays valid until mm_seqset_upload
+ * has returned, which packs the codes on the device.  One set holds either ASCII or 4-bit sequences: adding the other kind is MM_ERR_STATE. */
+int mm_seqset_add_nt16(mm_seqset* s, const uint8_t* nt16, int64_t n_bases, int reverse);
 int mm_seqset_upload(mm_seqset* s);                                /* pack + copy to HBM; set is then frozen.  Packs into the CONTEXT's pinned
                                                                     * staging buffer: two uploads of sets of one context must not overlap (the one-thread-
                                                                     * per-context rule above applies to this entry point too) */

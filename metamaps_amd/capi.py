@@ -109,6 +109,7 @@ def lib() -> C.CDLL:
             "mm_seqset_destroy": (None, [vp]),
             "mm_seqset_add": (C.c_int, [vp, C.c_char_p, i64]),
             "mm_seqset_add_view": (C.c_int, [vp, C.c_char_p, i64]),
+            "mm_seqset_add_nt16": (C.c_int, [vp, C.c_char_p, i64, C.c_int]),
             "mm_seqset_save": (C.c_int, [vp, C.c_char_p]),
             "mm_seqset_load": (C.c_int, [vp, C.c_char_p, P(vp)]),
             "mm_seqset_upload": (C.c_int, [vp]),
@@ -231,6 +232,17 @@ class Context:
                 q = q.encode()
             q = bytes(q)
             self.check(lib().mm_seqset_add(h, q, len(q)))
+        self.check(lib().mm_seqset_upload(h))
+        return s
+
+    def seqset_nt16(self, records) -> "SeqSet":
+        """a set of BAM-packed reads: records are (4-bit code bytes, bases, reverse) as a BAM record stores them"""
+        h = C.c_void_p()
+        self.check(lib().mm_seqset_create(self.h, C.byref(h)))
+        s = SeqSet(self, h)
+        keep = [bytes(b) for b, _, _ in records]                   # alive until the upload has returned
+        for b, (_, n, rev) in zip(keep, records):
+            self.check(lib().mm_seqset_add_nt16(h, b, n, 1 if rev else 0))
         self.check(lib().mm_seqset_upload(h))
         return s
 

@@ -5,7 +5,7 @@
 // exclusively through the C ABI in include/metamaps_hip.h.  Host work here is what stays host work in the
 // reference too: argument parsing, FASTA/FASTQ(.gz) reading, text formatting, taxonomy bookkeeping.
 //
-//   metamaps mapDirectly [--all] -r DB.fa -q reads.fq -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
+//   metamaps mapDirectly [--all] -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
 //   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N]
 //
@@ -27,12 +27,18 @@
 // device index itself (IDX.N.mmidx, mm_index_save: the arrays as they lie in HBM) and mapAgainstIndex loads it without running a
 // kernel — the persistent index of SURVEY N2; which of the two is faster is a question of file bandwidth against build time.
 //
+// Query files (-q) may be FASTA/FASTQ(.gz) or BAM, recognised by content, per file of a comma list (host/bam_reader.hpp).  A BAM gives the
+// files its `samtools fastq -n` conversion gives: secondary and supplementary records skipped, 0x10 records turned back to the read as
+// sequenced, qualities, tags and paired-end flags ignored.  Its 4-bit codes are packed on the device (mm_seqset_add_nt16); the host only
+// inflates the BGZF blocks (in parallel) and cuts the records.  The reference (-r) stays FASTA/FASTQ.
+//
 // Not provided: classifyU (disabled upstream).
 
 #include "../mm_env.hpp"
 #include "../cpu_budget.hpp"
 #include "../../../include/metamaps_hip.h"
 #include "seq_reader.hpp"
+#include "bam_reader.hpp"
 #include "host_util.hpp"
 #include "id_set.hpp"
 #include "fast_format.hpp"
@@ -143,6 +149,7 @@ uint64_t file_size(const std::string& f) {                       // commonFunc.h
 struct Batch {
   std::vector<std::string> names; std::vector<int> lens; std::vector<size_t> off;
   std::vector<const char*> view;                                 // per read: where the sequence lies in a mapped query file, or nullptr (then arena + off)
+  bool nt16 = false; std::vector<uint8_t> rev;                   // a batch of a BAM file: the arena holds 4-bit codes (mm_seqset_add_nt16), rev per read
   char* arena = nullptr; size_t cap = 0, used = 0;
   size_t seq = 0, file = 0;
   ~Batch() { free(arena); }
@@ -162,7 +169,14 @@ struct Batch {
     names.push_back(f.name); lens.push_back((int)f.length());
     if (f.view) put_view(f.view); else put(f.seq);
   }
-  void reset() { names.clear(); lens.clear(); off.clear(); view.clear(); used = 0; }
+  void put_nt16(const bam::Record& r) {                          // a BAM record's codes as they are, or (MM_BAM_HOST_DECODE) decoded to ASCII here
+    const size_t nb = nt16 ? ((size_t)r.l_seq + 1) / 2 : (size_t)r.l_seq;
+    reserve(used + nb + 1);
+    if (nt16) { memcpy(arena + used, r.seq, nb); rev.push_back(r.reverse() ? 1 : 0); }
+    else bam::nt16_to_ascii(r.seq, (size_t)r.l_seq, r.reverse(), arena + used);
+    names.push_back(r.name); lens.push_back((int)r.l_seq); off.push_back(used); view.push_back(nullptr); used += nb;
+  }
+  void reset() { names.clear(); lens.clear(); off.clear(); view.clear(); rev.clear(); nt16 = false; used = 0; }
   int64_t bases() const { int64_t b = 0; for (int L : lens) b += L; return b; }
   void absorb(Batch& o) {                                        // o's reads behind this batch's (the block parser's small batches joined up to the batch limits)
     const size_t base = used;
@@ -499,6 +513,32 @@ struct MapRun {
       return !gave_up;
     };
     for (size_t fi = 0; fi < queries.size(); ++fi) {
+      if (bam::is_bam_file(queries[fi])) {                       // BAM (by content): records -> batches of 4-bit codes, packed on the device
+        const bool host_decode = getenv("MM_BAM_HOST_DECODE") != nullptr;
+        const unsigned P = (unsigned)std::max<unsigned>(1, std::min<unsigned>(32, mm::cpu_budget() / 2));
+        const auto b_t0 = std::chrono::steady_clock::now();
+        try {
+          bam::Reader br(queries[fi], P, (1LL << 29) - 1);
+          bam::Record r;
+          bool more = true;
+          while (more) {
+            std::unique_ptr<Batch> b = fresh();
+            b->nt16 = !host_decode;
+            int64_t bases = 0;
+            while ((int64_t)b->names.size() < BATCH_READS && bases < BATCH_BASES) {
+              if (!(more = br.next(r))) break;
+              if (b->names.empty()) b->reserve((size_t)std::min<int64_t>(BATCH_BASES, r.l_seq * BATCH_READS) + ((size_t)64 << 20));
+              bases += r.l_seq;
+              b->put_nt16(r);
+            }
+            if (b->names.empty()) { std::lock_guard<std::mutex> lk(reader.m); reader.spare.push_back(std::move(b)); break; }
+            enqueue(std::move(b), fi);
+          }
+        } catch (const bam::Error& e) { die(std::string("Error reading BAM: ") + e.what()); }
+        pc.add("R BAM reader (inflate + parse, without waiting for a queue slot)", std::chrono::duration<double>(std::chrono::steady_clock::now() - b_t0).count());
+        std::lock_guard<std::mutex> lk(reader.m); reader.file_end.push_back(seq); reader.cv.notify_all();
+        continue;
+      }
       mapped.emplace_back();
       MappedFile& mf = mapped.back();
       if (getenv("MM_CLI_NO_MMAP") || !mf.open(queries[fi])) {   // gzip, pipes, ...: the sequential reader
@@ -921,7 +961,8 @@ struct MapRun {
 
   mm_seqset* upload_batch(mm_ctx* ctx, const Batch& bt) {
     mm_seqset* reads; ck(ctx, mm_seqset_create(ctx, &reads), "seqset");
-    for (size_t r = 0; r < bt.names.size(); ++r) ck(ctx, mm_seqset_add_view(reads, bt.seq_of(r), (int64_t)bt.lens[r]), "add read");
+    if (bt.nt16) for (size_t r = 0; r < bt.names.size(); ++r) ck(ctx, mm_seqset_add_nt16(reads, (const uint8_t*)bt.seq_of(r), (int64_t)bt.lens[r], bt.rev[r]), "add read");
+    else for (size_t r = 0; r < bt.names.size(); ++r) ck(ctx, mm_seqset_add_view(reads, bt.seq_of(r), (int64_t)bt.lens[r]), "add read");
     ck(ctx, mm_seqset_upload(reads), "upload reads");
     return reads;
   }

@@ -13,6 +13,7 @@
 
 namespace mm {
 void seqset_upload(mm_seqset* s);
+void seqset_upload_nt16(mm_seqset* s);
 void seqset_save(mm_seqset* s, const char* path);
 void seqset_load(mm_seqset* s, const char* path);
 void seqset_fetch(mm_seqset* s, int64_t i, char* out, int64_t cap);
@@ -145,6 +146,8 @@ int mm_seqset_add(mm_seqset* s, const char* ascii, int64_t len) {
   if (!s || (!ascii && len > 0) || len < 0) return MM_ERR_ARG;
   return guarded(s->ctx, [&] {
     MM_REQUIRE(!s->frozen, MM_ERR_STATE, "sequence set already uploaded");
+    MM_REQUIRE(s->staged_kind != 2, MM_ERR_STATE, "this sequence set holds 4-bit codes (mm_seqset_add_nt16): ASCII cannot join it");
+    s->staged_kind = 1;
     s->owned.emplace_back(ascii ? ascii : "", (size_t)len);
     s->staged.emplace_back(s->owned.back().data(), (size_t)len);
   });
@@ -153,12 +156,24 @@ int mm_seqset_add_view(mm_seqset* s, const char* ascii, int64_t len) {
   if (!s || (!ascii && len > 0) || len < 0) return MM_ERR_ARG;
   return guarded(s->ctx, [&] {
     MM_REQUIRE(!s->frozen, MM_ERR_STATE, "sequence set already uploaded");
+    MM_REQUIRE(s->staged_kind != 2, MM_ERR_STATE, "this sequence set holds 4-bit codes (mm_seqset_add_nt16): ASCII cannot join it");
+    s->staged_kind = 1;
     s->staged.emplace_back(ascii, (size_t)len);
+  });
+}
+int mm_seqset_add_nt16(mm_seqset* s, const uint8_t* nt16, int64_t n_bases, int reverse) {
+  if (!s || (!nt16 && n_bases > 0) || n_bases < 0) return MM_ERR_ARG;
+  return guarded(s->ctx, [&] {
+    MM_REQUIRE(!s->frozen, MM_ERR_STATE, "sequence set already uploaded");
+    MM_REQUIRE(s->staged_kind != 1, MM_ERR_STATE, "this sequence set holds ASCII sequences: 4-bit codes (mm_seqset_add_nt16) cannot join it");
+    s->staged_kind = 2;
+    s->staged.emplace_back((const char*)nt16, (size_t)n_bases);
+    s->staged_rev.push_back(reverse ? 1 : 0);
   });
 }
 int mm_seqset_upload(mm_seqset* s) {
   if (!s) return MM_ERR_ARG;
-  return guarded(s->ctx, [&] { MM_HIP(hipSetDevice(s->ctx->device)); mm::seqset_upload(s); });
+  return guarded(s->ctx, [&] { MM_HIP(hipSetDevice(s->ctx->device)); if (s->staged_kind == 2) mm::seqset_upload_nt16(s); else mm::seqset_upload(s); });
 }
 int mm_seqset_save(mm_seqset* s, const char* path) {
   if (!s || !path) return MM_ERR_ARG;

@@ -645,6 +645,9 @@ struct mm_seqset {
   // host staging (until upload)
   std::deque<std::string> owned;                                // copies made by mm_seqset_add (stable addresses)
   std::vector<std::pair<const char*, size_t>> staged;           // what upload packs: views into `owned` or into caller memory (mm_seqset_add_view)
+                                                                // or, for a set of BAM's 4-bit codes (mm_seqset_add_nt16), (codes, bases)
+  std::vector<uint8_t> staged_rev;                              // nt16 only: 1 = the record is the reverse complement of the read
+  int staged_kind = 0;                                          // 0 nothing staged yet, 1 ASCII, 2 nt16: one set holds one kind
   // host-side metadata (always valid after upload / synthesis)
   std::vector<int32_t> len;            // per sequence
   std::vector<uint64_t> base;          // [n+1] first base of sequence i in the packed stream (multiple of 16)

@@ -195,6 +195,167 @@ void seqset_upload(mm_seqset* s) {
   s->frozen = true;
 }
 
+// ---- device packing of BAM's 4-bit codes (mm_seqset_add_nt16) --------------------------------------------------------------------------
+// The records' code bytes go up as they are (0.5 B per base; every record's bytes start on an 8-byte boundary of the staging) and three
+// kernels plus the scan of mm_scan.hpp write what seqset_upload writes from the same reads in ASCII.  One thread per 16-base output word
+// decodes its bases (a record flagged reverse is read back to front and complemented: the complement of a 4-bit code is its bit reversal),
+// packs A/C/G/T and counts the exception runs that START in its word; the scan turns the counts into run indexes; a second pass over the
+// words writes the starts, bytes and ends of the runs (the run that ends at a base is the last one started at or before it: runs do not
+// nest), a third the lengths.  A run is a maximal stretch of one byte other than A/C/G/T inside one sequence, as the host packer joins them.
+namespace {
+constexpr uint64_t NT16_ASCII_LO = 0x565352474d43413dull, NT16_ASCII_HI = 0x4e42444b48595754ull;   // "=ACMGRSVT", "WYHKDBN" little endian
+
+struct Nt16View {
+  const uint8_t* codes; const uint64_t* boff; const uint64_t* base; const int32_t* len; const uint8_t* rev; int64_t n;
+};
+
+// 4-bit code -> exception byte (0 for A/C/G/T, whose 2-bit code is the position of their single set bit)
+__device__ __forceinline__ uint32_t nt16_exc(uint32_t c) {
+  if (c && !(c & (c - 1))) return 0;
+  return (uint32_t)(((c < 8 ? NT16_ASCII_LO : NT16_ASCII_HI) >> (8 * (c & 7))) & 255);
+}
+// code of base j of sequence i as sequenced
+__device__ __forceinline__ uint32_t nt16_code(const uint8_t* p, int64_t L, bool rev, int64_t j) {
+  const int64_t q = rev ? L - 1 - j : j;
+  uint32_t c = (p[q >> 1] >> ((q & 1) ? 0 : 4)) & 15u;
+  if (rev) c = ((c & 1u) << 3) | ((c & 2u) << 1) | ((c & 4u) >> 1) | ((c & 8u) >> 3);
+  return c;
+}
+// the sequence whose words hold word w: the last i with base[i] <= 16 w (sequences of length 0 own no words)
+__device__ __forceinline__ int64_t nt16_seq_of(const uint64_t* base, int64_t n, uint64_t g) {
+  int64_t lo = 0, hi = n;                                        // base[lo] <= g < base[hi]
+  while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (base[mid] <= g) lo = mid; else hi = mid; }
+  return lo;
+}
+// the 16 codes of word w, 4 bits each (pad positions 0): one aligned 8-byte load for a full forward word, base by base otherwise
+__device__ __forceinline__ uint64_t nt16_word_codes(const Nt16View& V, int64_t i, int64_t j0, int64_t L) {
+  const uint8_t* p = V.codes + V.boff[i];
+  const bool rev = V.rev[i] != 0;
+  uint64_t out = 0;
+  if (!rev && j0 + 16 <= L) {
+    const uint64_t v = *(const uint64_t*)(p + (j0 >> 1));      // byte b holds bases 2b (high nibble) and 2b + 1
+#pragma unroll
+    for (int t = 0; t < 16; ++t) out |= ((v >> (8 * (t >> 1) + ((t & 1) ? 0 : 4))) & 15ull) << (4 * t);
+    return out;
+  }
+  const int m = (int)(L - j0 < 16 ? L - j0 : 16);
+  for (int t = 0; t < m; ++t) out |= (uint64_t)nt16_code(p, L, rev, j0 + t) << (4 * t);
+  return out;
+}
+
+__global__ void __launch_bounds__(256) nt16_pack_kernel(Nt16View V, int64_t nwords, uint32_t* __restrict__ packed, uint32_t* __restrict__ nstart) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= nwords) return;
+  const uint64_t g = (uint64_t)w << 4;
+  const int64_t i = nt16_seq_of(V.base, V.n, g);
+  const int64_t L = V.len[i], j0 = (int64_t)(g - V.base[i]);
+  const uint64_t codes = nt16_word_codes(V, i, j0, L);
+  uint32_t prev = j0 > 0 ? nt16_exc(nt16_code(V.codes + V.boff[i], L, V.rev[i] != 0, j0 - 1)) : 0u;
+  uint32_t wv = 0, starts = 0;
+  const int m = (int)(L - j0 < 16 ? L - j0 : 16);
+  for (int t = 0; t < m; ++t) {
+    const uint32_t c = (uint32_t)(codes >> (4 * t)) & 15u, e = nt16_exc(c);
+    if (!e) wv |= (uint32_t)(__builtin_ctz(c)) << (2 * t);
+    starts += (e != 0 && e != prev);
+    prev = e;
+  }
+  packed[w] = wv;
+  nstart[w] = starts;
+}
+
+__global__ void __launch_bounds__(256) nt16_runs_kernel(Nt16View V, int64_t nwords, const uint64_t* __restrict__ first_run, uint64_t* __restrict__ exc_start,
+                                                        uint8_t* __restrict__ exc_byte, uint64_t* __restrict__ exc_end) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= nwords) return;
+  const uint64_t g = (uint64_t)w << 4;
+  const int64_t i = nt16_seq_of(V.base, V.n, g);
+  const int64_t L = V.len[i], j0 = (int64_t)(g - V.base[i]);
+  const uint64_t codes = nt16_word_codes(V, i, j0, L);
+  const uint8_t* p = V.codes + V.boff[i];
+  const bool rev = V.rev[i] != 0;
+  const int m = (int)(L - j0 < 16 ? L - j0 : 16);
+  uint32_t prev = j0 > 0 ? nt16_exc(nt16_code(p, L, rev, j0 - 1)) : 0u;
+  const uint32_t after = j0 + m < L ? nt16_exc(nt16_code(p, L, rev, j0 + m)) : 0u;   // the base behind the word, if the sequence goes on
+  uint64_t k = first_run[w];                                     // index of the next run to start
+  for (int t = 0; t < m; ++t) {
+    const uint32_t e = nt16_exc((uint32_t)(codes >> (4 * t)) & 15u);
+    if (!e) { prev = 0; continue; }
+    if (e != prev) { exc_start[k] = g + (uint64_t)t; exc_byte[k] = (uint8_t)e; ++k; }
+    const uint32_t nx = t + 1 < m ? nt16_exc((uint32_t)(codes >> (4 * (t + 1))) & 15u) : after;
+    if (nx != e) exc_end[k - 1] = g + (uint64_t)t + 1;
+    prev = e;
+  }
+}
+
+__global__ void __launch_bounds__(256) nt16_run_len_kernel(const uint64_t* __restrict__ exc_start, const uint64_t* __restrict__ exc_end, int64_t n_runs,
+                                                           uint32_t* __restrict__ exc_len) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n_runs) exc_len[r] = (uint32_t)(exc_end[r] - exc_start[r]);
+}
+}  // namespace
+
+void seqset_upload_nt16(mm_seqset* s) {
+  MM_REQUIRE(!s->frozen, MM_ERR_STATE, "sequence set already uploaded");
+  hipStream_t st = s->ctx->stream;
+  const size_t n = s->staged.size();
+  s->len.resize(n);
+  s->base.assign(n + 1, 0);
+  s->total_bases = 0;
+  std::vector<uint64_t> boff(n + 1, 0);
+  for (size_t i = 0; i < n; ++i) {
+    MM_REQUIRE((int64_t)s->staged[i].second <= MAX_SEQ_LEN, MM_ERR_LIMIT, "sequence longer than 2^29-1 bases");
+    s->len[i] = (int32_t)s->staged[i].second;
+    s->base[i + 1] = s->base[i] + (((uint64_t)s->len[i] + 15) & ~15ull);
+    boff[i + 1] = boff[i] + ((((uint64_t)s->len[i] + 1) / 2 + 7) & ~7ull);
+    s->total_bases += s->len[i];
+  }
+  const size_t nwords = (size_t)(s->base[n] >> 4), nbytes = (size_t)boff[n];
+  s->d_base.alloc(n + 1); s->d_base.upload(s->base.data(), n + 1, st);
+  s->d_len.alloc(std::max<size_t>(n, 1)); s->d_len.upload(s->len.data(), n, st);
+  s->packed.alloc(nwords + 1);
+  MM_HIP(hipMemsetAsync(s->packed.p + nwords, 0, sizeof(uint32_t), st));   // the pad word every set ends on
+  s->n_exc = 0;
+  if (nwords) {
+    // the code bytes, back to back in the context's pinned staging (copied by the pack helpers for large batches)
+    uint8_t* const stage = (uint8_t*)s->ctx->pinned_up_at_least(nbytes);
+    const size_t nthr = (size_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)std::max(1u, mm::cpu_budget() / 2), 32, (uint64_t)(nbytes >> 23) + 1, (uint64_t)n}));
+    auto copy = [&](size_t t) {
+      for (size_t i = n * t / nthr; i < n * (t + 1) / nthr; ++i) memcpy(stage + boff[i], s->staged[i].first, ((size_t)s->len[i] + 1) / 2);
+    };
+    if (nthr > 1) { if (!s->ctx->pack_pool) s->ctx->pack_pool = std::make_unique<TaskPool>(31); s->ctx->pack_pool->run(nthr, copy); }
+    else copy(0);
+    DBuf<uint8_t> d_codes(nbytes);
+    d_codes.upload(stage, nbytes, st);
+    DBuf<uint64_t> d_boff(n);
+    d_boff.upload(boff.data(), n, st);
+    DBuf<uint8_t> d_rev(n);
+    d_rev.upload(s->staged_rev.data(), n, st);
+    const Nt16View V{d_codes.p, d_boff.p, s->d_base.p, s->d_len.p, d_rev.p, (int64_t)n};
+    DBuf<uint32_t> nstart(nwords);
+    DBuf<uint64_t> first_run(nwords + 1), tmp;
+    const unsigned grid = (unsigned)ceil_div((int64_t)nwords, 256);
+    nt16_pack_kernel<<<dim3(grid), dim3(256), 0, st>>>(V, (int64_t)nwords, s->packed.p, nstart.p);
+    MM_KERNEL_CHECK();
+    exclusive_scan_u32_u64(nstart.p, (int64_t)nwords, first_run.p, tmp, st);
+    uint64_t runs = 0;
+    MM_HIP(hipMemcpyAsync(&runs, first_run.p + nwords, sizeof runs, hipMemcpyDeviceToHost, st));
+    MM_HIP(mm::stream_sync(st));
+    if (runs) {
+      s->exc_start.alloc((size_t)runs); s->exc_len.alloc((size_t)runs); s->exc_byte.alloc((size_t)runs);
+      DBuf<uint64_t> exc_end((size_t)runs);
+      nt16_runs_kernel<<<dim3(grid), dim3(256), 0, st>>>(V, (int64_t)nwords, first_run.p, s->exc_start.p, s->exc_byte.p, exc_end.p);
+      MM_KERNEL_CHECK();
+      nt16_run_len_kernel<<<dim3((unsigned)ceil_div((int64_t)runs, 256)), dim3(256), 0, st>>>(s->exc_start.p, exc_end.p, (int64_t)runs, s->exc_len.p);
+      MM_KERNEL_CHECK();
+      s->n_exc = (int64_t)runs;
+    }
+    MM_HIP(mm::stream_sync(st));                                 // (the staging and the temporaries are released behind the kernels)
+  }
+  MM_HIP(mm::stream_sync(st));
+  s->staged.clear(); s->staged.shrink_to_fit(); s->staged_rev.clear(); s->staged_rev.shrink_to_fit();
+  s->frozen = true;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Persistent packed form (what `metamaps index` writes instead of the reference's Boost archives of the sketch,
 // mapWrap.h:358-405): the 2-bit stream, the exception runs and the lengths.  The device index is rebuilt from it in
