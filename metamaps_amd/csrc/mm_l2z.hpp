@@ -1010,7 +1010,13 @@ l2z_kernel(IndexView I, const int32_t* __restrict__ cand, const int32_t* __restr
     zb_first = zb;
   }
   while (any_pass) {
-    if (++n_pass > (s >> 6) + 4) break;                            // (cannot happen: every pass moves the band by its width in one direction)
+    // (cannot happen: every pass moves the band by its width in one direction.  Should it, the sweep is unfinished: the candidate goes to l2_kernel,
+    //  as one too large for the masks does; MM_L2Z_FORCE_HANDBACK sends every candidate that gets here that way)
+    if (++n_pass > (s >> 6) + 4 || (dbg_flags & 0x1000)) {
+      release_slot();
+      if (lane == 0) { L2Result z{}; out[c] = z; big_list[atomicAdd(big_n, 1u)] = (int32_t)c; }
+      return;
+    }
     if (!masks_ready) { pass_low(); ++n_low; }
     masks_ready = false;
     if (dbg_stop == 6) { release_slot(); return; }
@@ -1050,16 +1056,48 @@ l2z_kernel(IndexView I, const int32_t* __restrict__ cand, const int32_t* __restr
     } else { stage = 1; j0 = -1; bk = 0; }
     lap(2);
     if (dbg_stop == 4) { release_slot(); return; }
+    // blocks from `from` on whose bound reaches thr, as two ballots over the bounds (lane l: blocks l and l + 64; blocks from nblk on have none)
+    auto passing_from = [&](int from, int thr, uint64_t& p0, uint64_t& p1) {
+      const int u0 = (int)ub2L[lane_b] - 1, u1 = (int)ub2L[lane_b + 64] - 1;   // (lane_b: see above)
+      p0 = __ballot(u0 >= thr && lane_b >= from);
+      p1 = __ballot(u1 >= thr && lane_b + 64 >= from);
+    };
+    auto first_of = [&](uint64_t p0, uint64_t p1) -> int { return p0 ? __builtin_ctzll(p0) : (p1 ? 64 + __builtin_ctzll(p1) : 1 << 20); };
     for (;;) {
       // the next block whose bound reaches max(best so far, amin); everything else is provably below the maximum.
-      // stage 0: from j0 to the first failing block behind bkmax; stage 1: all other blocks in index order.
+      // stage 0: from j0 to the first failing block behind bkmax; stage 1: all other blocks in index order, [j0, done_hi) left out.
+      // 10 kb class: two ballots over the bounds instead of the walk one block at a time with an LDS read per block (the same block comes out;
+      // K5 11.4 -> 10.0 ms on the bench batch).  The long-read classes keep the walk: there the ballots measured slower on config 3 (182 -> 191-209 ms of K5).
       bool found = false;
-      for (;;) {
-        if (stage == 1 && bk == j0) bk = done_hi;
-        if (bk >= nblk) { if (stage == 0) { done_hi = nblk; stage = 1; bk = 0; continue; } break; }
-        if (ub_of(bk) >= max(best, amin)) { found = true; break; }
-        if (stage == 0 && bk >= bkmax) { done_hi = bk + 1; stage = 1; bk = 0; continue; }
-        ++bk;
+      if (NWQ == 2 && !(dbg_flags & 0x2000)) {                  // (MM_L2Z_WALK_SEARCH: the walk in this class too, for the test that holds the two against each other)
+        const int thr = max(best, amin);
+        uint64_t p0, p1;
+        if (stage == 0) {
+          passing_from(bk, thr, p0, p1);
+          const int f = first_of(p0, p1), g = max(bk, bkmax);     // first passing block; the first block at which a failure ends stage 0
+          if (g < f && g < nblk) { done_hi = g + 1; stage = 1; bk = 0; }
+          else if (f < nblk) { bk = f; found = true; }
+          else { done_hi = nblk; stage = 1; bk = 0; }
+        }
+        if (stage == 1 && !found) {
+          passing_from(bk, thr, p0, p1);
+          if (bk <= j0) {                                          // (the blocks stage 0 covered)
+            const uint64_t k0 = (j0 > 0 ? (j0 >= 64 ? ~0ull : (1ull << j0) - 1ull) : 0ull) | (done_hi >= 64 ? 0ull : ~0ull << done_hi);
+            const int j1 = j0 - 64, d1 = done_hi - 64;
+            const uint64_t k1 = (j1 > 0 ? (j1 >= 64 ? ~0ull : (1ull << j1) - 1ull) : 0ull) | (d1 <= 0 ? ~0ull : (d1 >= 64 ? 0ull : ~0ull << d1));
+            p0 &= k0; p1 &= k1;
+          }
+          const int f = first_of(p0, p1);
+          if (f < nblk) { bk = f; found = true; }
+        }
+      } else {
+        for (;;) {
+          if (stage == 1 && bk == j0) bk = done_hi;
+          if (bk >= nblk) { if (stage == 0) { done_hi = nblk; stage = 1; bk = 0; continue; } break; }
+          if (ub_of(bk) >= max(best, amin)) { found = true; break; }
+          if (stage == 0 && bk >= bkmax) { done_hi = bk + 1; stage = 1; bk = 0; continue; }
+          ++bk;
+        }
       }
       if (!found) break;
       const int nb = bk * bspan;

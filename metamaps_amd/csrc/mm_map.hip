@@ -2015,8 +2015,8 @@ void map_batch(mm_ctx* ctx, const mm_index* I, const mm_seqset* reads, const mm_
     MM_REQUIRE(lds_wide <= 160 * 1024, MM_ERR_LIMIT, "L2 window state does not fit LDS");
     auto set_lds = [&](const void* fn, size_t bytes) { if (bytes > 64 * 1024) MM_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)); };
     DBuf<unsigned long long> counters(16); counters.zero(st);
-    if (getenv("MM_L2_STOP") || getenv("MM_L2_PHASES") || getenv("MM_FORCE_AMB_REDO") || getenv("MM_L2Z_DBG")) {
-      const char* ds = getenv("MM_L2_STOP"); unsigned long long v = (unsigned long long)((ds ? atoi(ds) & 0xff : 0) | (getenv("MM_L2_PHASES") ? 0x100 : 0) | (getenv("MM_FORCE_AMB_REDO") ? 0x200 : 0) | (getenv("MM_L2Z_DBG") ? (atoi(getenv("MM_L2Z_DBG")) == 2 ? 0xc00 : 0x400) : 0)); MM_HIP(hipMemcpyAsync(counters.p + 11, &v, sizeof v, hipMemcpyHostToDevice, st)); MM_HIP(mm::stream_sync(st)); }   // timing aid: leave the kernel after phase n (results are then meaningless)
+    if (getenv("MM_L2_STOP") || getenv("MM_L2_PHASES") || getenv("MM_FORCE_AMB_REDO") || getenv("MM_L2Z_DBG") || getenv("MM_L2Z_FORCE_HANDBACK") || getenv("MM_L2Z_WALK_SEARCH")) {
+      const char* ds = getenv("MM_L2_STOP"); unsigned long long v = (unsigned long long)((ds ? atoi(ds) & 0xff : 0) | (getenv("MM_L2_PHASES") ? 0x100 : 0) | (getenv("MM_FORCE_AMB_REDO") ? 0x200 : 0) | (getenv("MM_L2Z_DBG") ? (atoi(getenv("MM_L2Z_DBG")) == 2 ? 0xc00 : 0x400) : 0) | (getenv("MM_L2Z_FORCE_HANDBACK") ? 0x1000 : 0) | (getenv("MM_L2Z_WALK_SEARCH") ? 0x2000 : 0)); MM_HIP(hipMemcpyAsync(counters.p + 11, &v, sizeof v, hipMemcpyHostToDevice, st)); MM_HIP(mm::stream_sync(st)); }   // timing aid: leave the kernel after phase n (results are then meaningless)
     DBuf<int32_t> ovf((size_t)ncand);
     DBuf<unsigned int> ovf_n(1); ovf_n.zero(st);
     DBuf<uint8_t> amb_used;
@@ -2290,13 +2290,17 @@ void map_batch(mm_ctx* ctx, const mm_index* I, const mm_seqset* reads, const mm_
         MM_KERNEL_CHECK();
       }
       hl("K5 uploads + launches");
-      if (M->at_stage) M->at_stage(M->at_stage_user, 2);          // mm_map_batch_phased, stage 2: the last big kernel is enqueued
+      // mm_map_batch_phased, stage 2: the last big kernel is enqueued.  (Here, before the wait below for the hand-back counters, so that the next step's
+      // minimizer can fill the CUs the zone kernels leave as they drain; the rare big-list launch behind the wait is not waited for.)
+      if (M->at_stage) M->at_stage(M->at_stage_user, 2);
       // candidates the skip kernels hand back (reads shorter than w+k): the literal full slide
       int64_t n_fallback = 0;
-      auto run_fallback = [&](uint8_t* amb_ptr) {
-        unsigned int h_ovf = 0;
-        MM_HIP(hipMemcpyAsync(&h_ovf, ovf_n.p, sizeof h_ovf, hipMemcpyDeviceToHost, st));
-        MM_HIP(mm::stream_sync(st));                        // also keeps the host lists alive until the uploads are done
+      // read_ovf: ovf_n has not been read since the last launch that may add to it; otherwise h_ovf already holds it
+      auto run_fallback = [&](uint8_t* amb_ptr, bool read_ovf, unsigned int h_ovf) {
+        if (read_ovf) {
+          MM_HIP(hipMemcpyAsync(&h_ovf, ovf_n.p, sizeof h_ovf, hipMemcpyDeviceToHost, st));
+          MM_HIP(mm::stream_sync(st));                      // also keeps the host lists alive until the uploads are done
+        }
         if (!h_ovf) return;
         const size_t lds = l2_lds_bytes<uint16_t>(smax, false, 1, 8);
         set_lds((const void*)l2_kernel<false, uint16_t, 1, 8>, lds);
@@ -2307,10 +2311,14 @@ void map_batch(mm_ctx* ctx, const mm_index* I, const mm_seqset* reads, const mm_
         n_fallback += h_ovf;
       };
       int64_t n_big = 0;
+      unsigned int h_ovf0 = 0;
       if (v2) {                                                    // what the zone kernels handed back for its size: one wave per candidate, masks for 32 768 entries (beyond: every window)
         unsigned int h_big = 0;
+        // both counters behind one wait: l2_kernel on the big list adds nothing to ovf_n (the zone kernels hand reads shorter than w + k to ovf before
+        // they look at a candidate's size), so the fall-back below needs no second read of it
         MM_HIP(hipMemcpyAsync(&h_big, big_n.p, sizeof h_big, hipMemcpyDeviceToHost, st));
-        MM_HIP(mm::stream_sync(st));
+        MM_HIP(hipMemcpyAsync(&h_ovf0, ovf_n.p, sizeof h_ovf0, hipMemcpyDeviceToHost, st));
+        MM_HIP(mm::stream_sync(st));                        // also keeps the host lists alive until the uploads are done
         if (h_big) {
           const int smW = std::max(std::max(smA, smB), smD);
           const size_t lds = l2_lds_bytes<uint16_t>(smW, true, 1, 8);
@@ -2321,7 +2329,7 @@ void map_batch(mm_ctx* ctx, const mm_index* I, const mm_seqset* reads, const mm_
           n_big = h_big;
         }
       }
-      run_fallback(amb_used_p);
+      run_fallback(amb_used_p, !v2, h_ovf0);
       int64_t n_redo = 0;
       if (!lazy_reads.empty()) {                                 // votes that read an unresolved strand: resolve those reads, redo their candidates
         std::vector<uint8_t> used = amb_used.to_host(st, (size_t)n);
@@ -2345,7 +2353,7 @@ void map_batch(mm_ctx* ctx, const mm_index* I, const mm_seqset* reads, const mm_
             l2_kernel<true, uint16_t, 1, 8><<<dim3((unsigned)redo.size()), dim3(64), lds, st>>>(IV, M->cand.p, M->cand_read.p, M->sk_hash.p, M->sk_strand.p,
                 M->mz.off.p, M->sk_n.p, M->d_read_len.p, M->accept_min.p, P.k, P.w, smR, M->l2.p, counters.p, nullptr, nullptr, d_redo.p, ovf.p, ovf_n.p, nullptr, nullptr, masks_for(redo.size()), slot_flags_p, (int)slots_of(redo.size()));
             MM_KERNEL_CHECK();
-            run_fallback(nullptr);
+            run_fallback(nullptr, true, 0);
           }
           MM_HIP(mm::stream_sync(st));
           n_redo += (int64_t)redo.size();
