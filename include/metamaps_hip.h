@@ -38,7 +38,8 @@ typedef enum {
   MM_ERR_STATE = -4,      /* call sequence violated                               */
   MM_ERR_LIMIT = -5,      /* documented capacity limit exceeded       */
   MM_ERR_NUMERIC = -6,    /* reference would abort here (e.g. likelihood sum 0, mapWrap.h:298) */
-  MM_ERR_COMM = -7        /* RCCL error                                           */
+  MM_ERR_COMM = -7,       /* RCCL error                                           */
+  MM_ERR_DATA = -8        /* input data is corrupt (mm_bgzf_inflate: a block's status says which) */
 } mm_status;
 
 typedef struct mm_ctx mm_ctx;          /* a device + streams + scratch allocator                  */
@@ -81,6 +82,14 @@ int mm_seqset_add_view(mm_seqset* s, const char* ascii, int64_t len);
  * other than A/C/G/T become exception runs of their letter).  A view, like mm_seqset_add_view: `nt16` stays valid until mm_seqset_upload
  * has returned, which packs the codes on the device.  One set holds either ASCII or 4-bit sequences: adding the other kind is MM_ERR_STATE. */
 int mm_seqset_add_nt16(mm_seqset* s, const uint8_t* nt16, int64_t n_bases, int reverse);
+/* Inflate n BGZF blocks (whole gzip members with the BC field: header + deflate + CRC32 + ISIZE) on the context's device, from host memory
+ * into host memory.  Block i is comp[comp_off[i], comp_off[i] + comp_len[i]) (comp_bytes bytes in `comp`); its ISIZE inflated bytes go to
+ * out[out_off[i], out_off[i] + ISIZE) (out_cap bytes in `out`); no other byte of `out` is written, nor the bytes of a block that fails.
+ * status[i] (may be NULL): 0 ok, 1 deflate stream invalid, 2 length != ISIZE (or ISIZE > 65536), 3 CRC32 mismatch, 4 malformed gzip
+ * header (shorter than 26 bytes, or the extra field runs into the trailer).  Returns MM_OK if every block is ok, MM_ERR_ARG for bad
+ * arguments (a block outside `comp`, or a readable ISIZE that does not fit `out` at its offset), MM_ERR_DATA if any block is bad. */
+int mm_bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const int64_t* comp_off, const int32_t* comp_len, int32_t n,
+                    uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status);
 int mm_seqset_upload(mm_seqset* s);                                /* pack + copy to HBM; set is then frozen.  Packs into the CONTEXT's pinned
                                                                     * staging buffer: two uploads of sets of one context must not overlap (the one-thread-
                                                                     * per-context rule above applies to this entry point too) */

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmetamaps_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "metamaps_hip.h")
 
 COMM_ID_BYTES = 128
+MM_ERR_DATA = -8
 
 
 class MMError(RuntimeError):
@@ -110,6 +111,7 @@ def lib() -> C.CDLL:
             "mm_seqset_add": (C.c_int, [vp, C.c_char_p, i64]),
             "mm_seqset_add_view": (C.c_int, [vp, C.c_char_p, i64]),
             "mm_seqset_add_nt16": (C.c_int, [vp, C.c_char_p, i64, C.c_int]),
+            "mm_bgzf_inflate": (C.c_int, [vp, C.c_char_p, i64, vp, vp, C.c_int32, vp, i64, vp, vp]),
             "mm_seqset_save": (C.c_int, [vp, C.c_char_p]),
             "mm_seqset_load": (C.c_int, [vp, C.c_char_p, P(vp)]),
             "mm_seqset_upload": (C.c_int, [vp]),
@@ -245,6 +247,35 @@ class Context:
             self.check(lib().mm_seqset_add_nt16(h, b, n, 1 if rev else 0))
         self.check(lib().mm_seqset_upload(h))
         return s
+
+    def bgzf_inflate(self, blocks, out_off=None, out_cap=None):
+        """BGZF blocks (bytes each, whole members) inflated on the device in one call (mm_bgzf_inflate).  Returns (out, status): `out` a
+        bytearray of out_cap bytes (default: the blocks' ISIZEs back to back), status one int32 per block (0 ok, 1 deflate stream invalid,
+        2 length != ISIZE, 3 CRC32 mismatch, 4 malformed header).  MM_ERR_DATA (a corrupt block) is not raised: the statuses say which."""
+        blocks = [bytes(b) for b in blocks]
+        n = len(blocks)
+        comp = b"".join(blocks)
+        comp_len = np.array([len(b) for b in blocks], dtype=np.int32)
+        comp_off = np.zeros(n, dtype=np.int64)
+        if n:
+            comp_off[1:] = np.cumsum(comp_len[:-1], dtype=np.int64)
+        if out_off is None:
+            isz = np.array([int.from_bytes(b[-4:], "little") if len(b) >= 26 and int.from_bytes(b[-4:], "little") <= 65536 else 0 for b in blocks],
+                           dtype=np.int64)
+            out_off = np.zeros(n, dtype=np.int64)
+            if n:
+                out_off[1:] = np.cumsum(isz[:-1])
+            if out_cap is None:
+                out_cap = int(isz.sum())
+        out_off = np.ascontiguousarray(out_off, dtype=np.int64)
+        out = bytearray(out_cap or 0)
+        obuf = (C.c_uint8 * max(1, len(out))).from_buffer(out) if out else None
+        status = np.zeros(n, dtype=np.int32)
+        st = lib().mm_bgzf_inflate(self.h, comp, len(comp), comp_off.ctypes.data, comp_len.ctypes.data, n,
+                                   C.cast(obuf, C.c_void_p) if obuf is not None else None, len(out), out_off.ctypes.data, status.ctypes.data)
+        if st not in (0, MM_ERR_DATA):
+            self.check(st)
+        return out, status
 
     def load_seqset(self, path: str) -> "SeqSet":
         h = C.c_void_p()

@@ -1,5 +1,5 @@
-// Unaligned (or aligned) BAM as a query file for the `metamaps` host program: the BGZF block walk, parallel raw inflate of the blocks and the
-// record parse.  Host only, no device dependencies: tests/test_bam_reader.cpp checks it on the CPU against a BAM writer in Python.
+// Unaligned (or aligned) BAM as a query file for the `metamaps` host program: the BGZF block walk (also of bgzip-compressed FASTA/FASTQ),
+// parallel raw inflate of the blocks (or a caller's segment inflater: the CLI's inflates on the device) and the record parse.  Host only, no device dependencies: tests/test_bam_reader.cpp checks it on the CPU against a BAM writer in Python.
 //
 // What a record becomes is what `samtools fastq -n` writes for it: secondary (0x100) and supplementary (0x800) records are skipped, a record
 // with 0x10 is the reverse complement of the read as sequenced (the complement of a 4-bit code is its bit reversal: A<->T, C<->G, M<->K, R<->Y,
@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <cstring>
 #include <iostream>
+#include <functional>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -65,6 +66,23 @@ inline void bgzf_inflate(const uint8_t* p, size_t bs, uint8_t* out, size_t isize
   if ((uint32_t)crc32(0L, out, (uInt)isize) != rd32(p + bs - 8)) throw Error("corrupt BGZF block at byte " + std::to_string(at) + " (CRC mismatch)");
 }
 
+// the message bgzf_inflate throws for a block at file offset `at`, from a block status of a device inflate (mm_bgzf_inflate: 1 deflate
+// stream invalid, 2 length != ISIZE — both "inflate failed" for zlib —, 3 CRC32 mismatch, 4 malformed header)
+inline std::string bgzf_status_message(int status, size_t at) {
+  const std::string m = "corrupt BGZF block at byte " + std::to_string(at);
+  return status == 3 ? m + " (CRC mismatch)" : status == 4 ? m : m + " (inflate failed)";
+}
+
+// a file that starts with a BGZF block (BAM, or text written by bgzip)
+inline bool is_bgzf_file(const std::string& path) {
+  const int fd = ::open(path.c_str(), O_RDONLY);
+  if (fd < 0) return false;
+  uint8_t b[1024];
+  const ssize_t n = pread(fd, b, sizeof b, 0);
+  ::close(fd);
+  return n >= 18 && bgzf_block_size(b, (size_t)n) >= 26;
+}
+
 // a file is BAM if it starts with a BGZF block whose inflated data starts with "BAM\1"; anything else (FASTA, FASTQ, plain gzip) is not
 inline bool is_bam_file(const std::string& path) {
   const int fd = ::open(path.c_str(), O_RDONLY);
@@ -90,14 +108,20 @@ struct Record {
   bool reverse() const { return flag & 0x10; }
 };
 
-// Sequential record reader over a memory-mapped BAM.  The blocks are inflated a segment (up to SEG_BLOCKS blocks, ~64 MiB of data) at a
-// time, the blocks of a segment in parallel on a TaskPool of `threads` participants (1: all on the calling thread); a record that spans
-// two segments is carried over whole.  Errors throw bam::Error with a message; a missing EOF marker is a warning on stderr, as in samtools.
-class Reader {
+// One block of a segment to inflate: bs bytes at file offset `off`, its isize inflated bytes go to dst + out.
+struct SegBlock { size_t off, bs, isize, out; };
+// Inflates the n blocks of a segment (consecutive in the file mapped at `file`) into dst, or throws bam::Error with bgzf_inflate's message
+// for the first bad block.  With none given, zlib on the host (on a TaskPool); the CLI passes one that inflates on the device.
+using SegmentInflater = std::function<void(const uint8_t* file, const SegBlock* blk, size_t n, uint8_t* dst)>;
+
+// The inflated bytes of a memory-mapped BGZF file, a segment (up to SEG_BLOCKS blocks, ~64 MiB of data) at a time.  Without an inflater the
+// blocks of a segment are inflated in parallel on a TaskPool of `threads` participants (1: all on the calling thread).  A missing EOF marker
+// is a warning on stderr, as in samtools, where `warn_eof` is set.
+class BgzfStream {
  public:
   static constexpr size_t SEG_BLOCKS = 1024;
-  Reader(const std::string& path, unsigned threads, int64_t max_len, bool skip_filtered = true)
-      : path_(path), max_len_(max_len), skip_filtered_(skip_filtered) {
+  BgzfStream(const std::string& path, unsigned threads, SegmentInflater inflater = nullptr, bool warn_eof = true)
+      : path_(path), inflater_(std::move(inflater)), warn_eof_(warn_eof) {
     const int fd = ::open(path.c_str(), O_RDONLY);
     if (fd < 0) throw Error("Cannot open " + path);
     struct stat st;
@@ -110,10 +134,73 @@ class Reader {
       data_ = (const uint8_t*)p;
     }
     ::close(fd);
-    if (threads > 1) pool_ = std::make_unique<TaskPool>(threads - 1);
+    if (threads > 1 && !inflater_) pool_ = std::make_unique<TaskPool>(threads - 1);
+  }
+  ~BgzfStream() { if (data_) munmap((void*)data_, size_); }
+  BgzfStream(const BgzfStream&) = delete;
+  BgzfStream& operator=(const BgzfStream&) = delete;
+  const uint8_t* data() const { return data_; }
+  size_t size() const { return size_; }
+  bool at_end() const { return foff_ >= size_; }
+  size_t blocks() const { return nblocks_; }
+  bool eof_marker() const { return eof_seen_; }
+
+  // the next segment's inflated bytes into buf from `at` on (buf grows as needed); returns their number
+  size_t inflate_segment(std::vector<uint8_t>& buf, size_t at) {
+    std::vector<SegBlock> seg;
+    size_t total = 0;
+    while (foff_ < size_ && seg.size() < SEG_BLOCKS) {
+      const size_t bs = bgzf_block_size(data_ + foff_, size_ - foff_);
+      if (!bs) {
+        if (size_ - foff_ < 18) throw Error(path_ + ": truncated BGZF block at byte " + std::to_string(foff_));
+        throw Error(path_ + ": bad magic: no BGZF block at byte " + std::to_string(foff_));
+      }
+      if (bs < 26 || foff_ + bs > size_) throw Error(path_ + ": truncated BGZF block at byte " + std::to_string(foff_));
+      const size_t isize = rd32(data_ + foff_ + bs - 4);
+      if (isize > 65536) throw Error(path_ + ": corrupt BGZF block at byte " + std::to_string(foff_) + " (ISIZE " + std::to_string(isize) + ")");
+      seg.push_back(SegBlock{foff_, bs, isize, at + total});
+      total += isize;
+      foff_ += bs;
+      ++nblocks_;
+      if (foff_ == size_) {                                      // the last block: BGZF's EOF marker is an empty block of exactly 28 bytes
+        eof_seen_ = isize == 0 && bs == 28;
+        if (!eof_seen_ && warn_eof_) std::cerr << "[W::bgzf_read_block] EOF marker is absent. The input " << path_ << " is probably truncated" << std::endl;
+      }
+    }
+    if (buf.size() < at + total) buf.resize(at + total + (at + total) / 4);
+    if (inflater_) { if (!seg.empty()) inflater_(data_, seg.data(), seg.size(), buf.data()); }
+    else {
+      auto one = [&](size_t t) { const SegBlock& b = seg[t]; bgzf_inflate(data_ + b.off, b.bs, buf.data() + b.out, b.isize, b.off); };
+      if (pool_ && seg.size() > 1) {
+        const size_t W = pool_->width();
+        pool_->run(W, [&](size_t p) { for (size_t t = p; t < seg.size(); t += W) one(t); });
+      } else for (size_t t = 0; t < seg.size(); ++t) one(t);
+    }
+    if (!seg.empty()) {                                          // the compressed pages of the segment are not needed again
+      const uintptr_t a = (uintptr_t)(data_ + seg[0].off) & ~(uintptr_t)4095, b = (uintptr_t)(data_ + foff_) & ~(uintptr_t)4095;
+      if (b > a) madvise((void*)a, (size_t)(b - a), MADV_DONTNEED);
+    }
+    return total;
+  }
+
+ private:
+  std::string path_;
+  SegmentInflater inflater_;
+  bool warn_eof_;
+  const uint8_t* data_ = nullptr; size_t size_ = 0, foff_ = 0, nblocks_ = 0;
+  bool eof_seen_ = false;
+  std::unique_ptr<TaskPool> pool_;
+};
+
+// Sequential record reader over a BAM: the inflated bytes come a segment at a time from a BgzfStream (`inflater` as there); a record that
+// spans two segments is carried over whole.  Errors throw bam::Error with a message; a missing EOF marker is a warning on stderr.
+class Reader {
+ public:
+  static constexpr size_t SEG_BLOCKS = BgzfStream::SEG_BLOCKS;
+  Reader(const std::string& path, unsigned threads, int64_t max_len, bool skip_filtered = true, SegmentInflater inflater = nullptr)
+      : path_(path), max_len_(max_len), skip_filtered_(skip_filtered), z_(path, threads, std::move(inflater)) {
     read_header();
   }
-  ~Reader() { if (data_) munmap((void*)data_, size_); }
   Reader(const Reader&) = delete;
   Reader& operator=(const Reader&) = delete;
 
@@ -146,56 +233,22 @@ class Reader {
       return true;
     }
   }
-  size_t blocks() const { return nblocks_; }
-  bool eof_marker() const { return eof_seen_; }
+  size_t blocks() const { return z_.blocks(); }
+  bool eof_marker() const { return z_.eof_marker(); }
 
  private:
   const uint8_t* at() const { return buf_.data() + pos_; }
   // at least n inflated bytes from pos_ on in buf_, inflating further segments as needed; false if the file ends first
   bool need(size_t n) {
     while (end_ - pos_ < n) {
-      if (foff_ >= size_) return false;
+      if (z_.at_end()) return false;
       if (pos_) { memmove(buf_.data(), buf_.data() + pos_, end_ - pos_); end_ -= pos_; pos_ = 0; }
-      inflate_segment();
+      end_ += z_.inflate_segment(buf_, end_);
     }
     return true;
   }
-  void inflate_segment() {
-    struct Blk { size_t off, bs, isize, out; };
-    std::vector<Blk> seg;
-    size_t total = 0;
-    while (foff_ < size_ && seg.size() < SEG_BLOCKS) {
-      const size_t bs = bgzf_block_size(data_ + foff_, size_ - foff_);
-      if (!bs) {
-        if (size_ - foff_ < 18) throw Error(path_ + ": truncated BGZF block at byte " + std::to_string(foff_));
-        throw Error(path_ + ": bad magic: no BGZF block at byte " + std::to_string(foff_));
-      }
-      if (bs < 26 || foff_ + bs > size_) throw Error(path_ + ": truncated BGZF block at byte " + std::to_string(foff_));
-      const size_t isize = rd32(data_ + foff_ + bs - 4);
-      if (isize > 65536) throw Error(path_ + ": corrupt BGZF block at byte " + std::to_string(foff_) + " (ISIZE " + std::to_string(isize) + ")");
-      seg.push_back(Blk{foff_, bs, isize, end_ + total});
-      total += isize;
-      foff_ += bs;
-      ++nblocks_;
-      if (foff_ == size_) {                                      // the last block: BGZF's EOF marker is an empty block of exactly 28 bytes
-        eof_seen_ = isize == 0 && bs == 28;
-        if (!eof_seen_) std::cerr << "[W::bgzf_read_block] EOF marker is absent. The input " << path_ << " is probably truncated" << std::endl;
-      }
-    }
-    if (buf_.size() < end_ + total) buf_.resize(end_ + total + (end_ + total) / 4);
-    auto one = [&](size_t t) { const Blk& b = seg[t]; bgzf_inflate(data_ + b.off, b.bs, buf_.data() + b.out, b.isize, b.off); };
-    if (pool_ && seg.size() > 1) {
-      const size_t W = pool_->width();
-      pool_->run(W, [&](size_t p) { for (size_t t = p; t < seg.size(); t += W) one(t); });
-    } else for (size_t t = 0; t < seg.size(); ++t) one(t);
-    if (!seg.empty()) {                                          // the compressed pages of the segment are not needed again
-      const uintptr_t a = (uintptr_t)(data_ + seg[0].off) & ~(uintptr_t)4095, b = (uintptr_t)(data_ + foff_) & ~(uintptr_t)4095;
-      if (b > a) madvise((void*)a, (size_t)(b - a), MADV_DONTNEED);
-    }
-    end_ += total;
-  }
   void read_header() {
-    if (size_ == 0 || !bgzf_block_size(data_, size_)) throw Error(path_ + ": bad magic: not a BGZF file");
+    if (z_.size() == 0 || !bgzf_block_size(z_.data(), z_.size())) throw Error(path_ + ": bad magic: not a BGZF file");
     if (!need(8) || memcmp(at(), "BAM\1", 4) != 0) throw Error(path_ + ": bad magic: not a BAM file");
     const int32_t l_text = (int32_t)rd32(at() + 4);
     if (l_text < 0) throw Error(path_ + ": corrupt BAM header");
@@ -216,10 +269,8 @@ class Reader {
   std::string path_;
   int64_t max_len_;
   bool skip_filtered_;
-  const uint8_t* data_ = nullptr; size_t size_ = 0, foff_ = 0, nblocks_ = 0;
-  bool eof_seen_ = false;
+  BgzfStream z_;
   std::vector<uint8_t> buf_; size_t pos_ = 0, end_ = 0;          // inflated bytes [pos_, end_) of buf_ not parsed yet
-  std::unique_ptr<TaskPool> pool_;
 };
 
 }  // namespace bam

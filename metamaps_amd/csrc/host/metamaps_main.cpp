@@ -29,8 +29,9 @@
 //
 // Query files (-q) may be FASTA/FASTQ(.gz) or BAM, recognised by content, per file of a comma list (host/bam_reader.hpp).  A BAM gives the
 // files its `samtools fastq -n` conversion gives: secondary and supplementary records skipped, 0x10 records turned back to the read as
-// sequenced, qualities, tags and paired-end flags ignored.  Its 4-bit codes are packed on the device (mm_seqset_add_nt16); the host only
-// inflates the BGZF blocks (in parallel) and cuts the records.  The reference (-r) stays FASTA/FASTQ.
+// sequenced, qualities, tags and paired-end flags ignored.  Its 4-bit codes are packed on the device (mm_seqset_add_nt16).  The BGZF blocks
+// of FASTA/FASTQ written by bgzip (and of a BAM with MM_BAM_DEVICE_INFLATE=1) are inflated on the device a segment at a time
+// (mm_bgzf_inflate); the host walks the block headers, cuts the records and parses the text.  Plain gzip keeps zlib's sequential reader.  The reference (-r) stays FASTA/FASTQ(.gz).
 //
 // Not provided: classifyU (disabled upstream).
 
@@ -512,13 +513,31 @@ struct MapRun {
       }
       return !gave_up;
     };
+    // bgzip text is inflated on the device a segment at a time (mm_bgzf_inflate), on a context of the reader's own on the first device;
+    // MM_BGZF_HOST_INFLATE=1: through zlib's sequential gz reader instead.  BAM stays on the host's TaskPool unless MM_BAM_DEVICE_INFLATE=1:
+    // on 16 CPUs the kernel (1.7 GB/s on BAM) is slower than zlib on 8 threads, though it takes a third of the host CPU.
+    const bool host_inflate = getenv("MM_BGZF_HOST_INFLATE") != nullptr;
+    const bool bam_device = !host_inflate && getenv("MM_BAM_DEVICE_INFLATE") != nullptr;
+    mm_ctx* zctx = nullptr;
+    struct ZctxGuard { mm_ctx*& c; ~ZctxGuard() { if (c) mm_ctx_destroy(c); } } zguard{zctx};
+    std::vector<int64_t> z_coff, z_ooff; std::vector<int32_t> z_clen, z_st;
+    bam::SegmentInflater device_inflate;
+    if (!host_inflate) device_inflate = [&](const uint8_t* file, const bam::SegBlock* b, size_t n, uint8_t* dst) {
+      if (!zctx && mm_ctx_create(devs[0].phys, &zctx) != MM_OK) die("cannot create the reader's inflate context");
+      z_coff.resize(n); z_clen.resize(n); z_ooff.resize(n); z_st.assign(n, 0);
+      for (size_t i = 0; i < n; ++i) { z_coff[i] = (int64_t)(b[i].off - b[0].off); z_clen[i] = (int32_t)b[i].bs; z_ooff[i] = (int64_t)(b[i].out - b[0].out); }
+      const int64_t comp = (int64_t)(b[n - 1].off + b[n - 1].bs - b[0].off), out = (int64_t)(b[n - 1].out + b[n - 1].isize - b[0].out);
+      const int rc = mm_bgzf_inflate(zctx, file + b[0].off, comp, z_coff.data(), z_clen.data(), (int32_t)n, dst + b[0].out, out, z_ooff.data(), z_st.data());
+      if (rc == MM_ERR_DATA) for (size_t i = 0; i < n; ++i) if (z_st[i] != 0) throw bam::Error(bam::bgzf_status_message(z_st[i], b[i].off));
+      if (rc != MM_OK) die(std::string("device inflate failed: ") + mm_last_error(zctx));
+    };
     for (size_t fi = 0; fi < queries.size(); ++fi) {
       if (bam::is_bam_file(queries[fi])) {                       // BAM (by content): records -> batches of 4-bit codes, packed on the device
         const bool host_decode = getenv("MM_BAM_HOST_DECODE") != nullptr;
         const unsigned P = (unsigned)std::max<unsigned>(1, std::min<unsigned>(32, mm::cpu_budget() / 2));
         const auto b_t0 = std::chrono::steady_clock::now();
         try {
-          bam::Reader br(queries[fi], P, (1LL << 29) - 1);
+          bam::Reader br(queries[fi], P, (1LL << 29) - 1, true, bam_device ? device_inflate : nullptr);
           bam::Record r;
           bool more = true;
           while (more) {
@@ -536,6 +555,20 @@ struct MapRun {
           }
         } catch (const bam::Error& e) { die(std::string("Error reading BAM: ") + e.what()); }
         pc.add("R BAM reader (inflate + parse, without waiting for a queue slot)", std::chrono::duration<double>(std::chrono::steady_clock::now() - b_t0).count());
+        std::lock_guard<std::mutex> lk(reader.m); reader.file_end.push_back(seq); reader.cv.notify_all();
+        continue;
+      }
+      if (!host_inflate && bam::is_bgzf_file(queries[fi])) {     // bgzip FASTA/FASTQ: the sequential record parse over device-inflated segments
+        const auto z_t0 = std::chrono::steady_clock::now();
+        try {
+          bam::BgzfStream z(queries[fi], 1, device_inflate, false);
+          SeqFile f([&](std::vector<unsigned char>& buf) -> size_t {
+            while (!z.at_end()) if (const size_t n = z.inflate_segment(buf, 0)) return n;
+            return 0;
+          });
+          parse_into(f, (size_t)-1, [&](std::unique_ptr<Batch> b) { enqueue(std::move(b), fi); });
+        } catch (const bam::Error& e) { die(std::string("Error reading ") + queries[fi] + ": " + e.what()); }
+        pc.add("R bgzip reader (inflate + parse, without waiting for a queue slot)", std::chrono::duration<double>(std::chrono::steady_clock::now() - z_t0).count());
         std::lock_guard<std::mutex> lk(reader.m); reader.file_end.push_back(seq); reader.cv.notify_all();
         continue;
       }

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <functional>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -21,15 +22,24 @@ namespace {
 [[noreturn]] inline void seq_reader_die(const std::string& m) { std::cerr << m << std::endl; std::cout.flush(); fflush(nullptr); _exit(1); }   // (_exit: other threads may be inside the HIP runtime, metamaps_main.cpp die())
 
 // FASTA/FASTQ(.gz) records with kseq's observable behaviour (common/kseq.h:170-207)
-// Two sources: a (gz) file read through zlib in 1 MiB pieces, or a byte range of a memory-mapped plain file (MemView: the parallel
+// Three sources: a (gz) file read through zlib in 1 MiB pieces, a caller's `fill` (the inflated segments of a bgzip file: the record parse
+// is the zlib source's, byte for byte, only where the bytes come from differs), or a byte range of a memory-mapped plain file (MemView: the parallel
 // block parser below).  In memory mode `rec_start` is the file offset of the header character of the record just returned, `tell`
 // the offset of the first byte the next call will look at, and a record whose sequence sits on one line of a 4-line FASTQ record
 // is returned as a view into the mapping (view != nullptr, seq empty) instead of a copy.
 class SeqFile {
   struct Buf { const unsigned char* p; const unsigned char* data() const { return p; } } buf_{nullptr};
   gzFile fp_ = nullptr; std::vector<unsigned char> own_; size_t beg_ = 0, end_ = 0; bool eof_ = false; int pending_ = 0; size_t pending_pos_ = 0; bool mem_ = false;
+  std::function<size_t(std::vector<unsigned char>&)> fill_;     // the next bytes into the vector (resized as it likes), their number; 0 at the end
   int get() {
-    if (beg_ >= end_) { if (eof_) return -1; int n = gzread(fp_, own_.data(), (unsigned)own_.size()); if (n <= 0) { eof_ = true; return -1; } beg_ = 0; end_ = (size_t)n; }
+    if (beg_ >= end_) {
+      if (eof_) return -1;
+      size_t n = 0;
+      if (fill_) { n = fill_(own_); buf_.p = own_.data(); }
+      else { const int r = gzread(fp_, own_.data(), (unsigned)own_.size()); n = r > 0 ? (size_t)r : 0; }
+      if (n == 0) { eof_ = true; return -1; }
+      beg_ = 0; end_ = n;
+    }
     return buf_.p[beg_++];
   }
  public:
@@ -37,6 +47,7 @@ class SeqFile {
   const char* view = nullptr; size_t view_len = 0;               // memory mode: the sequence where it lies in the file
   size_t rec_start = 0;
   explicit SeqFile(const std::string& path) : own_(1 << 20) { fp_ = gzopen(path.c_str(), "r"); if (!fp_) seq_reader_die("Cannot open " + path); buf_.p = own_.data(); }
+  explicit SeqFile(std::function<size_t(std::vector<unsigned char>&)> fill) : own_(1), fill_(std::move(fill)) { buf_.p = own_.data(); }
   SeqFile(const unsigned char* data, size_t begin, size_t size) : beg_(begin), end_(size), eof_(true), mem_(true) { buf_.p = data; }   // memory mode: parses from `begin` on
   ~SeqFile() { if (fp_) gzclose(fp_); }
   SeqFile(const SeqFile&) = delete;

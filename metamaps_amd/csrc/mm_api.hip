@@ -14,6 +14,8 @@
 namespace mm {
 void seqset_upload(mm_seqset* s);
 void seqset_upload_nt16(mm_seqset* s);
+int64_t bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const int64_t* comp_off, const int32_t* comp_len, int32_t n,
+                     uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status);
 void seqset_save(mm_seqset* s, const char* path);
 void seqset_load(mm_seqset* s, const char* path);
 void seqset_fetch(mm_seqset* s, int64_t i, char* out, int64_t cap);
@@ -170,6 +172,15 @@ int mm_seqset_add_nt16(mm_seqset* s, const uint8_t* nt16, int64_t n_bases, int r
     s->staged.emplace_back((const char*)nt16, (size_t)n_bases);
     s->staged_rev.push_back(reverse ? 1 : 0);
   });
+}
+int mm_bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const int64_t* comp_off, const int32_t* comp_len, int32_t n,
+                    uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status) {
+  if (!ctx || n < 0 || comp_bytes < 0 || out_cap < 0 || (n > 0 && (!comp || !comp_off || !comp_len || !out_off)) || (!out && out_cap > 0)) return MM_ERR_ARG;
+  int64_t bad = 0;
+  const int rc = guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); bad = mm::bgzf_inflate(ctx, comp, comp_bytes, comp_off, comp_len, n, out, out_cap, out_off, status); });
+  if (rc != MM_OK) return rc;
+  if (bad) { ctx->err = "mm_bgzf_inflate: " + std::to_string(bad) + " corrupt BGZF block(s)"; return MM_ERR_DATA; }
+  return MM_OK;
 }
 int mm_seqset_upload(mm_seqset* s) {
   if (!s) return MM_ERR_ARG;

@@ -34,6 +34,8 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_CLI_REF_GROUP_BASES", "2^30", "test", "bases per upload group of the reference (small groups: the concat path on small inputs)"},
     {"MM_CLI_REF_SEQUENTIAL", "unset", "test", "reference through the sequential kseq-style reader instead of the block parser"},
     {"MM_BAM_HOST_DECODE", "unset", "test", "BAM query files decoded to ASCII on the host and uploaded like FASTQ (cross-check of the device nt16 packer)"},
+    {"MM_BGZF_HOST_INFLATE", "unset", "test", "BGZF query files (BAM, bgzip FASTA/FASTQ) inflated by zlib on the host, never on the device (cross-check of mm_bgzf_inflate)"},
+    {"MM_BAM_DEVICE_INFLATE", "unset", "tuning", "BAM query files inflated on the device (mm_bgzf_inflate) instead of by zlib on the host's threads: a third of the host CPU, slower on 16 CPUs (DESIGN.md §1)"},
     {"MM_CLI_NO_MMAP", "unset", "test", "query and reference files through the sequential reader (what .gz and pipes always take)"},
     {"MM_CLI_NO_PREWARM", "unset", "test", "worker contexts come up with their first batch instead of beside the index build"},
     {"MM_SF_GRID", "the device's CU count", "debug", "resident workgroups of the streaming seed filter (measurement aid: how K3 scales with the CUs at work)"},

@@ -1,5 +1,7 @@
-"""The CLI on the same reads as FASTQ and as unaligned BAM: wall time, host CPU time and identical output files, the BAM reader's inflate rate
-(tests/test_bam_reader.cpp, `rate` mode) and, with --rocprof, the device pack kernels' time under `rocprofv3 --kernel-trace --stats`.
+"""The CLI on the same reads as page-cached FASTQ, as unaligned BAM and as bgzip-compressed FASTQ, the BGZF forms each with device inflate
+(mm_bgzf_inflate) and with host inflate (MM_BGZF_HOST_INFLATE=1: zlib on a TaskPool for BAM, zlib's sequential gzread for bgzip text): wall
+time, host CPU time and identical output files, the BAM reader's host inflate rate (tests/test_bam_reader.cpp, `rate` mode) and, with
+--rocprof, the device pack and inflate kernels' time under `rocprofv3 --kernel-trace --stats` (one run per BGZF form).
 
   python tools/bam_cli_bench.py --out DIR [--batches 2] [--reads 100000] [--read-len 10000] [--cpus 16] [--rocprof]
 
@@ -37,6 +39,11 @@ def _deflate(chunk: bytes) -> bytes:
     return bw.bgzf_block(chunk, level=1)
 
 
+def _deflate6(chunk: bytes) -> bytes:                             # (bgzip's default level)
+    import bam_writer as bw
+    return bw.bgzf_block(chunk, level=6)
+
+
 def _records(buf, ln, names, rng):
     import struct
     out, at = [], 0
@@ -60,13 +67,14 @@ def make_inputs(d, batches, n_reads, read_len, cpus):
     from metamaps_amd import capi, synth
     import bam_writer as bw
     db = synth.make_db(os.path.join(d, "db"), n_genomes=40, genome_len=1_000_000, seed=7)
-    fq, bam = os.path.join(d, "reads.fq"), os.path.join(d, "reads.bam")
+    fq, bam, fqz = os.path.join(d, "reads.fq"), os.path.join(d, "reads.bam"), os.path.join(d, "reads.fq.gz")
     ctx = capi.Context(0)
     ref = ctx.seqset([s.tobytes() for s in db.contig_seqs])
     rng = np.random.default_rng(5)
     bases = 0
     with open(fq, "wb", buffering=1 << 24) as f, open(bam, "wb") as g, mp.Pool(cpus) as pool:
         pend = bw.header_bytes(refs=())
+        bam_inflated = len(pend)
         for b in range(batches):
             rb, _t = ctx.synth_reads(ref, seed=1000 + 97 * b, n_reads=n_reads, read_len=read_len, read_len_min=0, frac_random=0.05, n_abundant=100,
                                      sub_rate=0.04, ins_rate=0.03, del_rate=0.05)
@@ -77,7 +85,9 @@ def make_inputs(d, batches, n_reads, read_len, cpus):
                 f.write(b"@" + names[r] + b"\n"); f.write(mv[at:at + L]); f.write(b"\n+\n"); f.write(qual[:L]); f.write(b"\n")
                 at += L
             bases += int(ln.sum())
-            pend += _records(buf, ln, names, rng)
+            recs = _records(buf, ln, names, rng)
+            bam_inflated += len(recs)
+            pend += recs
             cut = len(pend) // 65280 * 65280
             for blk in pool.imap(_deflate, [pend[i:i + 65280] for i in range(0, cut, 65280)], chunksize=64):
                 g.write(blk)
@@ -87,7 +97,15 @@ def make_inputs(d, batches, n_reads, read_len, cpus):
             g.write(blk)
         g.write(bw.EOF_BLOCK)
     ref.close(); ctx.close()
-    return db, fq, bam, bases
+    with open(fq, "rb") as f, open(fqz, "wb") as g, mp.Pool(cpus) as pool:   # what `bgzip reads.fq` writes
+        while True:
+            piece = f.read(65280 * 1024)
+            if not piece:
+                break
+            for blk in pool.imap(_deflate6, [piece[i:i + 65280] for i in range(0, len(piece), 65280)], chunksize=16):
+                g.write(blk)
+        g.write(bw.EOF_BLOCK)
+    return db, fq, bam, fqz, bases, bam_inflated
 
 
 def run_cli(cmd, cpus, env_extra=None):
@@ -130,36 +148,47 @@ def main():
     os.makedirs(a.out, exist_ok=True)
     res = {"cpus": a.cpus}
     t0 = time.time()
-    db, fq, bam, bases = make_inputs(a.out, a.batches, a.reads, a.read_len, a.cpus)
-    res.update(bases=bases, fastq_bytes=os.path.getsize(fq), bam_bytes=os.path.getsize(bam), inputs_s=round(time.time() - t0, 1))
+    db, fq, bam, fqz, bases, bam_inflated = make_inputs(a.out, a.batches, a.reads, a.read_len, a.cpus)
+    res.update(bases=bases, fastq_bytes=os.path.getsize(fq), bam_bytes=os.path.getsize(bam), bam_inflated_bytes=bam_inflated,
+               fastq_gz_bytes=os.path.getsize(fqz), inputs_s=round(time.time() - t0, 1))
     rate_exe = os.path.join(a.out, "bam_rate")
     subprocess.run(["g++", "-O3", "-std=c++17", "-pthread", "-o", rate_exe, os.path.join(ROOT, "tests", "test_bam_reader.cpp"), "-lz"], check=True)
     for t in sorted({1, max(1, a.cpus // 2), a.cpus}):
         p = subprocess.run(["taskset", "-c", f"0-{a.cpus - 1}", rate_exe, "rate", bam, str(t)], capture_output=True, text=True, timeout=900, check=True)
         res[f"reader_rate_threads{t}"] = p.stdout.strip()
-    pf, pb = os.path.join(a.out, "fq", "out"), os.path.join(a.out, "bam", "out")
-    os.makedirs(os.path.dirname(pf), exist_ok=True); os.makedirs(os.path.dirname(pb), exist_ok=True)
+    host = {"MM_BGZF_HOST_INFLATE": "1"}
+    dev = {"MM_BAM_DEVICE_INFLATE": "1"}
+    forms = {"fastq": (fq, None), "bam_device": (bam, dev), "bam_host": (bam, host), "fqgz_device": (fqz, None), "fqgz_host": (fqz, host)}
+    outs = {k: os.path.join(a.out, k, "out") for k in forms}
+    for k in outs:
+        os.makedirs(os.path.dirname(outs[k]), exist_ok=True)
     base = ["mapDirectly", "--all", "-r", db.fasta, "--then-classify", db.dir]
-    for rep in range(2):                                           # alternating, twice: the second pair has warm page caches for both
-        res[f"fastq_{rep}"] = run_cli([CLI] + base + ["-q", fq, "-o", pf], a.cpus)
-        res[f"bam_{rep}"] = run_cli([CLI] + base + ["-q", bam, "-o", pb], a.cpus)
-    res["outputs_identical"] = same_outputs(pb, pf, [(bam, fq), (pb, pf)])
+    for rep in range(2):                                           # alternating, twice: the second round has warm page caches for every form
+        for k, (q, env) in forms.items():
+            res[f"{k}_{rep}"] = run_cli([CLI] + base + ["-q", q, "-o", outs[k]], a.cpus, env)
+    res["outputs_identical"] = {k: same_outputs(outs[k], outs["fastq"], [(forms[k][0], fq), (outs[k], outs["fastq"])]) for k in forms if k != "fastq"}
     if a.rocprof:
-        d = a.prof_dir or os.path.join(a.out, "prof")
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "run", "--", CLI] + base + ["-q", bam, "-o", pb + "_prof"]
-        # (MM_CLI_FULL_TEARDOWN: the CLI leaves through exit() instead of _exit(), so the profiler's exit handlers write their files)
-        subprocess.run(cmd, capture_output=True, text=True, timeout=1800, check=True, env=dict(os.environ, MM_CPU_BUDGET=str(a.cpus), MM_CLI_FULL_TEARDOWN="1"))
         import csv
         import glob
-        kern = {}
-        for fcsv in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
-            for row in csv.DictReader(open(fcsv)):
-                if "nt16" in row["Name"] or "scan_" in row["Name"]:
-                    name = re.search(r"(\w+)(<[^(]*>)?\(", row["Name"]).group(1)   # (names carry namespaces, "(anonymous namespace)" among them)
-                    kern[name] = {"calls": int(row["Calls"]), "total_ms": float(row["TotalDurationNs"]) / 1e6}
-        res["kernels"] = kern
-        nt16_ms = sum(v["total_ms"] for k, v in kern.items() if "nt16" in k)
-        res["nt16_kernels_ms_per_gbase"] = round(nt16_ms / (bases / 1e9), 3) if bases else None
+        res["kernels"] = {}
+        for k, q, inflated in (("bam_device", bam, bam_inflated), ("fqgz_device", fqz, res["fastq_bytes"])):
+            d = os.path.join(a.prof_dir or os.path.join(a.out, "prof"), k)
+            cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "run", "--", CLI] + base + ["-q", q, "-o", outs[k] + "_prof"]
+            # (MM_CLI_FULL_TEARDOWN: the CLI leaves through exit() instead of _exit(), so the profiler's exit handlers write their files)
+            subprocess.run(cmd, capture_output=True, text=True, timeout=1800, check=True, env=dict(os.environ, MM_CPU_BUDGET=str(a.cpus), MM_CLI_FULL_TEARDOWN="1", **dev))
+            kern = {}
+            for fcsv in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
+                for row in csv.DictReader(open(fcsv)):
+                    if "nt16" in row["Name"] or "scan_" in row["Name"] or "bgzf" in row["Name"]:
+                        name = re.search(r"(\w+)(<[^(]*>)?\(", row["Name"]).group(1)   # (names carry namespaces, "(anonymous namespace)" among them)
+                        kern[name] = {"calls": int(row["Calls"]), "total_ms": float(row["TotalDurationNs"]) / 1e6}
+            res["kernels"][k] = kern
+            inf_ms = sum(v["total_ms"] for n, v in kern.items() if "bgzf" in n)
+            res[f"{k}_inflate_kernel_GBps"] = round(inflated / 1e9 / (inf_ms / 1e3), 2) if inf_ms else None
+            res[f"{k}_inflate_kernel_ms"] = round(inf_ms, 2)
+            if k == "bam_device":
+                nt16_ms = sum(v["total_ms"] for n, v in kern.items() if "nt16" in n)
+                res["nt16_kernels_ms_per_gbase"] = round(nt16_ms / (bases / 1e9), 3) if bases else None
     print(json.dumps(res))
 
 
