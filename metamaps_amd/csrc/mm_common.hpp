@@ -228,9 +228,9 @@ struct DevAlloc {
     static const bool use_slabs = getenv("MM_NO_SLABS") == nullptr;
     if (use_slabs && !eager && !in_build && want >= SLAB_FROM_BYTES) {
       const auto ts0 = std::chrono::steady_clock::now();
-      if (void* q = slab_piece(device, ask)) { *got = SlabSet::granules(ask); if (trace) fprintf(stderr, "MM_ALLOC_TRACE slab piece %zu bytes %.3f ms at %.1f ms\n", *got,
+      if (void* q = slab_piece(device, ask)) { *got = SlabSet::granules(ask); if (trace) { fprintf(stderr, "MM_ALLOC_TRACE slab piece %zu bytes %.3f ms at %.1f ms\n", *got,
                                                                                                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts0).count(),
-                                                                                               std::chrono::duration<double, std::milli>(std::chrono::system_clock::now().time_since_epoch()).count()); return q; }
+                                                                                               std::chrono::duration<double, std::milli>(std::chrono::system_clock::now().time_since_epoch()).count()); } return q; }
     }
     const auto t0 = std::chrono::steady_clock::now();
     hipError_t e = refuse ? hipErrorOutOfMemory : dev_malloc(&p, ask);
@@ -582,7 +582,6 @@ struct mm_ctx {
   void* comm = nullptr;          // ncclComm_t
   bool comm_shared = false;      // the communicator belongs to another context of this device (mm_comm_share)
   int comm_rank = 0, comm_size = 1;
-  bool em_split = false;         // the resident EM kernel once failed to get its grid onto the device: one launch per phase from then on (mm_post.hip)
   // per-(k, pi) cache of the host statistics thresholds (pure functions of the sketch size), mm_stats.hpp
   std::shared_ptr<void> lut_cache;
   int lut_k = 0; float lut_pi = 0;

@@ -15,11 +15,10 @@ struct mm_em {
   // device-resident loop (mm_em_run): taxa with mappings on this rank, their partial sums, loop control, log-likelihood trace
   mm::DBuf<int32_t> present; int32_t n_present = -1;
   // the per-taxon sums in fixed shape: items of <= 512 consecutive entries of one taxon (one wavefront each), the items of present taxon p
-  // are [pt_item[p], pt_item[p + 1]); the resident kernel's grid, its per-workgroup log-likelihood partials and its barrier words
+  // are [pt_item[p], pt_item[p + 1]); the grid of the P1 / P2 launches and its per-workgroup log-likelihood partials
   mm::DBuf<int32_t> pt_item; mm::DBuf<int64_t> item_lo, item_hi; int32_t n_items = 0, n_wg = 0;
-  mm::DBuf<double> item_sum, wg_ll; mm::DBuf<unsigned> bar;
+  mm::DBuf<double> item_sum, wg_ll;
   mm::DBuf<int32_t> eread;                                // read of every mapping
-  mm::DBuf<int64_t> span;                                 // per read (sorted by mapping count, longest first): first and behind-last mapping
   mm::DBuf<int64_t> pos; mm::DBuf<double> post_sorted;   // pos[i]: place of entry i in taxon-sorted order (inverse of perm); the loop keeps its posteriors there
   mm::DBuf<double> local_partial, ll_trace, f_run;   // f_run: the loop's own frequencies (mm_em_iterate / mm_em_posteriors in between do not disturb mm_em_continue)
   mm::DBuf<long long> ctrl;

@@ -104,16 +104,10 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_HF_DBG", "0", "debug", "two-pass filter leaves after phase n WITHOUT RESULTS"},
     {"MM_SF_PROF", "unset", "debug", "cycle counts per phase of the streaming seed filter on stderr"},
     // ---- library: EM and exchange (mm_post.hip, mm_api.hip)
-    {"MM_EM_FORCE_COLLECTIVE", "unset", "test", "a one-rank communicator keeps P1-P3' | ncclAllReduce | finalize instead of the plain loop (how one GPU drives the multi-rank path)"},
-    {"MM_EM_RESIDENT", "unset", "tuning", "EM as one resident kernel with grid barriers instead of one launch per phase (measured: slower, DESIGN.md section 4)"},
-    {"MM_EM_SPLIT", "unset", "test", "with MM_EM_RESIDENT: the phases as launches all the same (cross-check); 2: P2 and P3 in one launch (measured slower than a launch per phase)"},
-    {"MM_EM_GRID", "256 (128 resident)", "tuning", "workgroups of the EM kernels"},
-    {"MM_EM_BARRIER_TICKS", "2 s", "test", "time-out of the resident kernel's grid barrier before it hands the run to the launch path"},
+    {"MM_EM_FORCE_COLLECTIVE", "unset", "test", "a one-rank communicator keeps P1-P3' | ncclAllReduce | finalize instead of P1-P3 alone (how one GPU drives the multi-rank path)"},
+    {"MM_EM_GRID", "by size", "tuning", "workgroups of the EM kernels; by default enough for about 160 reads and 448 mappings each, 256 at least, one per read at most; when set: at most 1024 and one per 256 reads"},
     {"MM_CLI_FORMAT_PART", "10000", "test", "mapping records per formatter thread of a batch (the text of a batch is formatted in up to eight parts and joined)"},
     {"MM_CLI_CLASSIFY_FROM_FILE", "unset", "test", "mapDirectly --then-classify reads PREFIX back and tokenises it (as `classify` does) instead of taking the lines it has just formatted from memory"},
-    {"MM_EM_ORDER", "file", "debug", "\"count\": reads by mapping count for the thread-per-read E step (measurement aid)"},
-    {"MM_EM_DBG", "0", "debug", "E-step variants of the round-4 measurements (tools/em_latency.py)"},
-    {"MM_EM_PROF", "unset", "debug", "phase clocks of the resident EM kernel on stderr"},
     {"MM_GATHER_SELF_SEND", "unset", "test", "mm_mapping_gather sends the owner's own parts through ncclSend / ncclRecv too (one-GPU test of the exchange)"},
   };
   *n = sizeof T / sizeof T[0];

@@ -185,7 +185,7 @@ void em_create(mm_ctx* ctx, int64_t n_reads, const int64_t* read_off, const int3
   E->post.alloc((size_t)std::max<int64_t>(ne, 1));
   E->ll_read.alloc((size_t)std::max<int64_t>(n_reads, 1));
   E->f.alloc((size_t)n_taxa);
-  E->partial.alloc((size_t)n_taxa + 2);
+  E->partial.alloc((size_t)n_taxa + 1);
   E->block_sum.alloc((size_t)ceil_div(std::max<int64_t>(n_reads, 1), 256));
   MM_HIP(mm::stream_sync(st));
 }
@@ -279,7 +279,7 @@ void em_create_from_mapping(mm_ctx* ctx, const mm_mapping* M, const int32_t* con
   MM_KERNEL_CHECK();
   E->ll_read.alloc((size_t)std::max<int64_t>(n_reads, 1));
   E->f.alloc((size_t)n_taxa);
-  E->partial.alloc((size_t)n_taxa + 2);
+  E->partial.alloc((size_t)n_taxa + 1);
   E->block_sum.alloc((size_t)ceil_div(std::max<int64_t>(n_reads, 1), 256));
   MM_HIP(mm::stream_sync(st));
 }
@@ -324,28 +324,24 @@ void em_iterate_allreduce(mm_em* E, const double* f, double* f_next, double* ll)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The whole EM loop on the device (meta::doEM's while loop, fEM.h:501-661), round 4: ONE resident kernel per run.
+// The whole EM loop on the device (meta::doEM's while loop, fEM.h:501-661): one launch per phase, the host reads the control word
+// once per group of iterations.
 //
 // An iteration has three phases with a dependency between each:
-//   P1  E step, thread per read (fEM.h:350-361, :578): post[i] = l_i / sum l, log-likelihood partial per workgroup
+//   P1  E step (fEM.h:350-361, :578): post[i] = l_i / sum l, log-likelihood partial per workgroup
 //   P2  per-taxon sums of the posteriors in a FIXED SHAPE: the entries of a taxon (read order, `perm`) are cut into items of <= 512,
 //       an item is summed by one wavefront (lane l takes l, l + 64, ...; butterfly), the items of a taxon are added in order.  The
 //       shape depends on the number of entries only, so exactly tied taxa stay exactly tied (getBestMapping's first-maximum rule,
 //       fEM.h:217-232, sees the same ties as the reference's sequential sums)
 //   P3  one workgroup: item sums -> per-taxon sums, their total, f = sum / total (fEM.h:606-615), log-likelihood, stop rule (:624-639)
-// Round 3 ran them as five launches + a copy per iteration (136 us per iteration, 4.3 ms of a 48 ms bench step for a 5 MB problem).
-// Now the grid (<= 128 workgroups, all resident) loops over the iterations itself; the phases are separated by grid barriers (agent-scope
-// release / acquire around one atomic counter; the workgroup that arrives last at the second barrier runs P3 before it releases the
-// others).  With several ranks an iteration is kernel A = P1 | barrier | P2 | last arriver: P3' (local sums), the ncclAllReduce, and
-// kernel B = normalise + stop rule on the all-reduced sums (every rank decides on identical values, so the collectives stay matched).
-// A barrier that is not released within 2 s (a grid that cannot become resident: many contexts of one device inside their EM loops at
-// once) raises the abort flag; the host then finishes the run with the same phases as separate launches (MM_EM_SPLIT=1 forces that
-// path: bit-identical results, same shapes).
+// An iteration is em_p1_kernel | em_p2_kernel | em_p3_kernel on the context's stream.  With several ranks it is P1 | P2 | P3' (local sums),
+// the ncclAllReduce, and em_finalize_kernel = normalise + stop rule on the all-reduced sums (every rank decides on identical values, so the
+// collectives stay matched).  Round 3 ran five launches + a copy per iteration; the forms measured since (one resident kernel with grid
+// barriers, P2 and P3 in one launch) were slower and are gone: DESIGN.md section 4.
 // ctrl[0] = iterations done, ctrl[1] = stopped (1: the stop rule fired, 2: the caller's iteration limit), ctrl[2] = bits of the
-// previous log-likelihood, ctrl[3] = first iteration of the current log-likelihood trace, ctrl[4] = a barrier timed out.
+// previous log-likelihood, ctrl[3] = first iteration of the current log-likelihood trace.
 // ---------------------------------------------------------------------------------------------------
 struct EmLoop {
-  const longlong2* span;                                          // per read (file order; MM_EM_ORDER=count: by mapping count): [first, behind-last) mapping
   const int64_t* read_off; const int32_t* eread;                  // [n_reads + 1]; read of every mapping
   const int32_t* taxon; const double* mapq; const double* inv_nloc;
   int64_t n_reads;
@@ -355,28 +351,19 @@ struct EmLoop {
   double* item_sum; double* wg_ll;
   double* f; double* local_partial; int32_t n_taxa;
   long long* ctrl; double* ll_trace; int ll_cap; long long it_limit;
-  unsigned* bar;                                                  // [0] arrivals, [1] released generation
-  long long barrier_ticks;                                        // a barrier not released within this many ticks of the 100 MHz wall clock gives up (ctrl[4])
-  int dbg;                                                        // MM_EM_DBG (timing aid, results then meaningless): 1 = P1 without its scattered stores, 2 = without the f gather
 };
 constexpr int EM_ITEM = 512;
-constexpr int EM_BAR_GROUP = 16;                                  // workgroups per first-level barrier counter
-constexpr long long EM_BARRIER_TICKS = 200000000LL;               // 2 s of the 100 MHz wall clock (MM_EM_BARRIER_TICKS: test hook)
 
-// P1.  A thread walks its reads; the mappings of a read are taken EIGHT at a time with every load of the eight issued before the first is used
-// (clamped indices instead of branches), so a read of up to eight mappings — 98 % of them at ~4 per read — costs two dependent memory round
-// trips; longer reads loop over such chunks twice (sum, then posteriors).  A wave takes as many rounds as its LONGEST read, so the reads
-// are visited in the order of their mapping counts (`span`: the reads' [first, behind-last) mapping pairs sorted by count, longest first,
-// made once per problem): lanes of a wave then hold reads of equal length.  (Round 4 measured the first form of this phase — four at a time,
-// file order, two passes from five mappings on — at 38 of an iteration's 53 us: per wave the maximum over 64 lanes of ~6 rounds of two dependent
-// loads.)  The likelihoods are added in mapping order, as the reference adds them (fEM.h:353-358).  The posterior goes straight to its place
-// in the taxon-sorted array P2 reads (pos[i]): P2 then streams instead of gathering through perm[].
-__device__ inline double em_p1_reads(const EmLoop& a, int64_t q0, int64_t q1) {   // thread-per-read form over reads [q0, q1) of `span`; returns the thread's log-likelihood share
+// P1, thread per read.  A thread walks its reads; the mappings of a read are taken EIGHT at a time with every load of the eight issued before
+// the first is used (clamped indices instead of branches), so a read of up to eight mappings — 98 % of them at ~4 per read — costs two dependent
+// memory round trips; longer reads loop over such chunks twice (sum, then posteriors).  The likelihoods are added in mapping order, as the
+// reference adds them (fEM.h:353-358).  The posterior goes straight to its place in the taxon-sorted array P2 reads (pos[i]): P2 then streams
+// instead of gathering through perm[].
+__device__ inline double em_p1_reads(const EmLoop& a, int64_t r0, int64_t r1) {   // over reads [r0, r1); returns the thread's log-likelihood share
   const int tid = threadIdx.x;
   double ll = 0;
-  for (int64_t q = q0 + tid; q < q1; q += 256) {
-    int64_t lo, hi;
-    if (a.span) { const longlong2 sp = a.span[q]; lo = sp.x; hi = sp.y; } else { lo = a.read_off[q]; hi = a.read_off[q + 1]; }
+  for (int64_t r = r0 + tid; r < r1; r += 256) {
+    const int64_t lo = a.read_off[r], hi = a.read_off[r + 1];
     if (hi <= lo) continue;
     const int64_t last = hi - 1;
     double sum = 0, l8[8]; int64_t p8[8];
@@ -385,13 +372,13 @@ __device__ inline double em_p1_reads(const EmLoop& a, int64_t q0, int64_t q1) { 
 #pragma unroll
       for (int u = 0; u < 8; ++u) { const int64_t i = c + u < last ? c + u : last; t8[u] = a.taxon[i]; w8[u] = a.inv_nloc[i]; q8[u] = a.mapq[i]; p8[u] = a.pos[i]; }
 #pragma unroll
-      for (int u = 0; u < 8; ++u) f8[u] = a.dbg == 2 ? 1e-4 : a.f[t8[u]];
+      for (int u = 0; u < 8; ++u) f8[u] = a.f[t8[u]];
 #pragma unroll
       for (int u = 0; u < 8; ++u) { l8[u] = f8[u] * w8[u] * q8[u]; if (c + u < hi) sum += l8[u]; }   // fEM.h:353
     }
     if (hi - lo <= 8) {                                            // the usual read: everything is still in registers
 #pragma unroll
-      for (int u = 0; u < 8; ++u) if (lo + u < hi && a.dbg != 1) a.post_sorted[p8[u]] = l8[u] / sum;              // :361
+      for (int u = 0; u < 8; ++u) if (lo + u < hi) a.post_sorted[p8[u]] = l8[u] / sum;              // :361
     } else {
       for (int64_t c = lo; c < hi; c += 8) {
         int t8[8]; double w8[8], q8[8], f8[8]; int64_t q_pos[8];
@@ -400,7 +387,7 @@ __device__ inline double em_p1_reads(const EmLoop& a, int64_t q0, int64_t q1) { 
 #pragma unroll
         for (int u = 0; u < 8; ++u) f8[u] = a.f[t8[u]];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) if (c + u < hi && a.dbg != 1) a.post_sorted[q_pos[u]] = (f8[u] * w8[u] * q8[u]) / sum;
+        for (int u = 0; u < 8; ++u) if (c + u < hi) a.post_sorted[q_pos[u]] = (f8[u] * w8[u] * q8[u]) / sum;
       }
     }
     ll += log(sum);                                                // :578
@@ -422,7 +409,7 @@ __device__ inline void em_p1(const EmLoop& a, int wg, int n_wg, double* sh, doub
   double ll = 0;
   const int64_t E0 = R1 > R0 ? a.read_off[R0] : 0, E1 = R1 > R0 ? a.read_off[R1] : 0;
   const int nE = (int)min(E1 - E0, (int64_t)EM_LBUF + 1), nR = (int)(R1 - R0);
-  if (a.dbg == 3 || E1 - E0 > EM_LBUF || nR > EM_RBUF) ll = em_p1_reads(a, R0, R1);
+  if (E1 - E0 > EM_LBUF || nR > EM_RBUF) ll = em_p1_reads(a, R0, R1);
   else if (nR > 0) {
     for (int e0 = 0; e0 < nE; e0 += 4 * 256) {                   // four coalesced mappings per thread in flight
       int t4[4]; double w4[4], q4[4], f4[4];
@@ -527,119 +514,17 @@ __device__ inline void em_p3(const EmLoop& a, int n_wg, double* sh) {
   if (tid == 0) em_stop_rule(a.ctrl, ll, a.ll_trace, a.ll_cap, a.it_limit);
 }
 
-// grid barrier pieces (thread 0 of every workgroup talks; agent-scope fences publish / fetch the other workgroups' plain stores: the
-// XCDs' L2s are not coherent with each other, docs/history.md K5 scratch slots)
-// bar[0]: groups that have arrived, bar[1]: released generation, bar[16 * (1 + g)]: arrivals of group g (EM_BAR_GROUP workgroups, a
-// 64-byte line each).  Two levels because 128 agent-scope atomics on ONE word are served one after the other: ~13 us per barrier,
-// more than the phases between them.
-__device__ inline bool grid_arrive_is_last(unsigned* bar, unsigned epoch, unsigned n_wg, int* s_flag) {
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    const unsigned g = blockIdx.x / EM_BAR_GROUP, n_groups = (n_wg + EM_BAR_GROUP - 1) / EM_BAR_GROUP;
-    const unsigned g_size = min((unsigned)EM_BAR_GROUP, n_wg - g * EM_BAR_GROUP);
-    int last = 0;
-    if (__hip_atomic_fetch_add(&bar[16 * (1 + g)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 == epoch * g_size) {
-      __threadfence();
-      last = __hip_atomic_fetch_add(&bar[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 == epoch * n_groups;
-    }
-    if (last) __threadfence();
-    *s_flag = last;
-  }
-  __syncthreads();
-  return *s_flag != 0;
-}
-__device__ inline void grid_release(unsigned* bar, unsigned epoch) {
-  __syncthreads();
-  if (threadIdx.x == 0) { __threadfence(); __hip_atomic_store(&bar[1], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-}
-__device__ inline bool grid_wait(unsigned* bar, unsigned epoch, long long* ctrl, int* s_flag, long long ticks) {   // false: timed out / aborted
-  if (threadIdx.x == 0) {
-    const long long t0 = (long long)wall_clock64();
-    int ok = 1;
-    while (__hip_atomic_load(&bar[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < epoch) {
-      __builtin_amdgcn_s_sleep(1);
-      if ((long long)wall_clock64() - t0 > (ticks < 0 ? -ticks : ticks) || __hip_atomic_load(&ctrl[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-        __hip_atomic_store(&ctrl[4], 1LL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = 0; break;
-      }
-    }
-    __threadfence();
-    *s_flag = ok;
-  }
-  __syncthreads();
-  return *s_flag != 0;
-}
-
-// ONE_ITERATION = false: the whole run of one rank.  true: kernel A of a multi-rank iteration (P1 | P2 | local sums), leaves after it.
-template <bool ONE_ITERATION>
-__global__ void __launch_bounds__(256) em_loop_kernel(EmLoop a) {
-  __shared__ double sh[256], lbuf[EM_LBUF], rsum[EM_RBUF];
-  __shared__ int s_flag;
-  const int wg = blockIdx.x, n_wg = gridDim.x;
-  if (__hip_atomic_load(&a.ctrl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;   // (iterations enqueued past the stop are no-ops)
-  unsigned epoch = 0;
-  const bool prof = a.barrier_ticks < 0 && wg == 0 && threadIdx.x == 0;   // MM_EM_PROF: workgroup 0's wall-clock ticks per phase into ctrl[5..7]
-  long long t_prev = prof ? (long long)wall_clock64() : 0;
-  auto tick = [&](int slot) { if (prof) { const long long t = (long long)wall_clock64(); a.ctrl[slot] += t - t_prev; t_prev = t; } };
-  for (;;) {
-    em_p1(a, wg, n_wg, sh, lbuf, rsum);
-    tick(5);
-    ++epoch;
-    if (grid_arrive_is_last(a.bar, epoch, n_wg, &s_flag)) grid_release(a.bar, epoch);
-    else if (!grid_wait(a.bar, epoch, a.ctrl, &s_flag, a.barrier_ticks)) {
-      if (ONE_ITERATION && threadIdx.x == 0) a.local_partial[a.n_taxa + 1] = 1.0;   // all-reduced: every rank learns that this iteration did not happen
-      return;
-    }
-    tick(6);                                                       // (barrier 1)
-    em_p2(a, wg, n_wg);
-    tick(7);
-    ++epoch;
-    if (grid_arrive_is_last(a.bar, epoch, n_wg, &s_flag)) {
-      em_p3<ONE_ITERATION>(a, n_wg, sh);
-      if (ONE_ITERATION) return;
-      grid_release(a.bar, epoch);
-    } else {
-      if (ONE_ITERATION) return;
-      if (!grid_wait(a.bar, epoch, a.ctrl, &s_flag, a.barrier_ticks)) return;
-    }
-    if (__hip_atomic_load(&a.ctrl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-  }
-}
-// the same phases as separate launches (no barrier inside): the path after a barrier time-out, and MM_EM_SPLIT=1
+// one launch per phase; once the loop has stopped every kernel leaves at once (iterations enqueued past the stop are no-ops)
 __global__ void __launch_bounds__(256) em_p1_kernel(EmLoop a) { __shared__ double sh[256], lbuf[EM_LBUF], rsum[EM_RBUF]; if (a.ctrl[1]) return; em_p1(a, blockIdx.x, gridDim.x, sh, lbuf, rsum); }
 __global__ void __launch_bounds__(256) em_p2_kernel(EmLoop a) { if (a.ctrl[1]) return; em_p2(a, blockIdx.x, gridDim.x); }
 template <bool LOCAL>
 __global__ void __launch_bounds__(256) em_p3_kernel(EmLoop a, int n_wg) { __shared__ double sh[256]; if (a.ctrl[1]) return; em_p3<LOCAL>(a, n_wg, sh); }
-// P2 and P3 in one launch (round 6, MM_EM_SPLIT=2): the workgroup that finishes its items last runs P3 — the hand-over of the resident kernel's second barrier
-// (arrive, agent-scope release / acquire) without anybody waiting, so it needs no co-residency.  An iteration is then two launches (with several ranks: kernel A',
-// this one, the all-reduce and kernel B) instead of three (five).  bar[2]: workgroups done with P2; the last one puts it back to zero.
-// NOT the default: it measured slower than the launch it saves (see em_run).
-template <bool LOCAL>
-__global__ void __launch_bounds__(256) em_p23_kernel(EmLoop a) {
-  __shared__ double sh[256];
-  __shared__ int s_last;
-  if (a.ctrl[1]) return;
-  em_p2(a, blockIdx.x, gridDim.x);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    const int last = __hip_atomic_fetch_add(&a.bar[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 == gridDim.x;
-    if (last) { __threadfence(); __hip_atomic_store(&a.bar[2], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    s_last = last;
-  }
-  __syncthreads();
-  if (s_last) em_p3<LOCAL>(a, (int)gridDim.x, sh);
-}
-// kernel B of a multi-rank iteration: normalise the all-reduced sums (fEM.h:606-615; fixed-shape sum over the taxa, the same on every
+// the last kernel of a multi-rank iteration: normalise the all-reduced sums (fEM.h:606-615; fixed-shape sum over the taxa, the same on every
 // rank), log-likelihood trace, stop rule (:624-639)
 __global__ void __launch_bounds__(256) em_finalize_kernel(const double* __restrict__ partial, int32_t n_taxa, double* __restrict__ f, long long* __restrict__ ctrl,
                                                           double* __restrict__ ll_trace, int ll_cap, long long it_limit) {
   if (ctrl[1]) return;
   __shared__ double sh[256];
-  if (partial[n_taxa + 1] > 0) {                                   // some rank's kernel A gave up at its barrier: nothing is applied, every rank repeats the iteration phase by phase
-    if (threadIdx.x == 0) { ctrl[4] = 1; ctrl[1] = 3; }
-    return;
-  }
   const double sum = wg_sum256(n_taxa, sh, [&](int t) { return partial[t]; });
   for (int t = threadIdx.x; t < n_taxa; t += 256) f[t] = partial[t] / sum;
   if (threadIdx.x == 0) em_stop_rule(ctrl, partial[n_taxa], ll_trace, ll_cap, it_limit);
@@ -654,12 +539,12 @@ __global__ void em_pos_kernel(const int64_t* __restrict__ perm, int64_t ne, int6
   if (j < ne) pos[perm[j]] = j;
 }
 static int em_grid(int64_t n_reads, int64_t n_entries) {         // (fixed per problem: the log-likelihood partials are summed in the grid's shape)
-  if (!getenv("MM_EM_GRID") && !getenv("MM_EM_RESIDENT")) {        // launches: as many blocks as keep a block within P1's LDS buffers (a little under EM_RBUF reads and EM_LBUF mappings on average), 256 at least
+  const char* e = getenv("MM_EM_GRID");
+  if (!e) {                                                        // as many blocks as keep a block within P1's LDS buffers (a little under EM_RBUF reads and EM_LBUF mappings on average), 256 at least
     const int64_t want = std::max<int64_t>({(int64_t)256, ceil_div(std::max<int64_t>(n_reads, 1), EM_RBUF * 5 / 6), ceil_div(std::max<int64_t>(n_entries, 1), EM_LBUF * 7 / 8)});
     return (int)std::max<int64_t>(1, std::min<int64_t>({want, (int64_t)1 << 20, std::max<int64_t>(n_reads, 1)}));
   }
-  const char* e = getenv("MM_EM_GRID");                           // default: 256 workgroups as launches (33 us per iteration against 38 at 128), 128 for the resident kernel (all must be resident together)
-  const int cap = std::min(std::max(e ? atoi(e) : (getenv("MM_EM_RESIDENT") ? 128 : 256), 1), 1024);
+  const int cap = std::min(std::max(atoi(e), 1), 1024);
   return (int)std::max<int64_t>(1, std::min<int64_t>(cap, ceil_div(std::max<int64_t>(n_reads, 1), 256)));
 }
 
@@ -689,34 +574,19 @@ int em_run(mm_em* E, const double* f0, int max_iter, double* f_out, double* ll_t
     E->item_lo.alloc(std::max<size_t>(ilo.size(), 1)); E->item_lo.upload(ilo.data(), ilo.size(), st);
     E->item_hi.alloc(std::max<size_t>(ihi.size(), 1)); E->item_hi.upload(ihi.data(), ihi.size(), st);
     E->item_sum.alloc(std::max<size_t>(ilo.size(), 1));
-    if (getenv("MM_EM_ORDER") && !strcmp(getenv("MM_EM_ORDER"), "count")) {   // measurement aid: the thread-per-read form (MM_EM_DBG=3) with the reads by mapping count, longest first
-      std::vector<int64_t> ro = E->read_off.to_host(st, (size_t)E->n_reads + 1);
-      std::vector<int64_t> sp(2 * (size_t)std::max<int64_t>(E->n_reads, 1), 0);
-      int64_t cmax = 0; for (int64_t r = 0; r < E->n_reads; ++r) cmax = std::max(cmax, ro[(size_t)r + 1] - ro[(size_t)r]);
-      const int64_t NB = std::min<int64_t>(cmax, 255) + 1;       // (counts beyond 255 share the first bucket: order among them does not matter for what this is for)
-      std::vector<int64_t> start((size_t)NB + 1, 0);
-      const bool by_count = getenv("MM_EM_ORDER") && !strcmp(getenv("MM_EM_ORDER"), "count");   // default: file order (one bucket)
-      auto bucket = [&](int64_t c) { return by_count ? NB - 1 - std::min<int64_t>(c, NB - 1) : (int64_t)0; };
-      for (int64_t r = 0; r < E->n_reads; ++r) start[(size_t)bucket(ro[(size_t)r + 1] - ro[(size_t)r]) + 1]++;
-      for (int64_t b2 = 0; b2 < NB; ++b2) start[(size_t)b2 + 1] += start[(size_t)b2];
-      for (int64_t r = 0; r < E->n_reads; ++r) { const int64_t k2 = start[(size_t)bucket(ro[(size_t)r + 1] - ro[(size_t)r])]++; sp[2 * (size_t)k2] = ro[(size_t)r]; sp[2 * (size_t)k2 + 1] = ro[(size_t)r + 1]; }
-      E->span.alloc(sp.size()); E->span.upload(sp.data(), sp.size(), st);
-      MM_HIP(mm::stream_sync(st));                          // (sp is the upload's source)
-    }
     E->pos.alloc((size_t)std::max<int64_t>(E->n_entries, 1)); E->post_sorted.alloc((size_t)std::max<int64_t>(E->n_entries, 1));
     MM_REQUIRE(E->n_reads < (1LL << 31), MM_ERR_LIMIT, "EM problem beyond 2^31 reads");
     E->eread.alloc((size_t)std::max<int64_t>(E->n_entries, 1));
     if (E->n_reads > 0) { em_eread_kernel<<<dim3((unsigned)ceil_div(E->n_reads, 256)), dim3(256), 0, st>>>(E->read_off.p, E->n_reads, E->eread.p); MM_KERNEL_CHECK(); }
     if (E->n_entries > 0) { em_pos_kernel<<<dim3((unsigned)ceil_div(E->n_entries, 256)), dim3(256), 0, st>>>(E->perm.p, E->n_entries, E->pos.p); MM_KERNEL_CHECK(); }
     E->wg_ll.alloc((size_t)E->n_wg);
-    E->local_partial.alloc((size_t)T + 2);
+    E->local_partial.alloc((size_t)T + 1);
     E->ll_trace.alloc((size_t)cap);
     E->f_run.alloc((size_t)T);
-    E->ctrl.alloc(8);
-    E->bar.alloc(16 * (size_t)(1 + ceil_div(E->n_wg, EM_BAR_GROUP)));
+    E->ctrl.alloc(4);
     MM_HIP(mm::stream_sync(st));
   }
-  long long h_ctrl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long long h_ctrl[4] = {0, 0, 0, 0};
   if (f0) {
     E->f_run.upload(f0, (size_t)T, st);
     E->local_partial.zero(st);
@@ -725,83 +595,40 @@ int em_run(mm_em* E, const double* f0, int max_iter, double* f_out, double* ll_t
     MM_HIP(hipMemcpyAsync(h_ctrl, E->ctrl.p, sizeof h_ctrl, hipMemcpyDeviceToHost, st));
     MM_HIP(mm::stream_sync(st));
     if (h_ctrl[1] == 2) h_ctrl[1] = 0;
-    h_ctrl[3] = h_ctrl[0]; h_ctrl[4] = 0;
+    h_ctrl[3] = h_ctrl[0];
     MM_HIP(hipMemcpyAsync(E->ctrl.p, h_ctrl, sizeof h_ctrl, hipMemcpyHostToDevice, st));
     MM_HIP(mm::stream_sync(st));
   }
   const long long it0 = h_ctrl[0], it_limit = it0 + max_iter;
-  EmLoop a{(const longlong2*)(E->span.n ? E->span.p : nullptr), E->read_off.p, E->eread.p, E->taxon.p, E->mapq.p, E->inv_nloc.p, E->n_reads, E->post_sorted.p, E->pos.p, E->item_lo.p, E->item_hi.p, E->n_items,
-           E->present.p, E->pt_item.p, E->n_present, E->item_sum.p, E->wg_ll.p, E->f_run.p, E->local_partial.p, T, E->ctrl.p, E->ll_trace.p, cap, it_limit, E->bar.p,
-           (getenv("MM_EM_PROF") ? -1 : 1) * (getenv("MM_EM_BARRIER_TICKS") ? atoll(getenv("MM_EM_BARRIER_TICKS")) : EM_BARRIER_TICKS),
-           getenv("MM_EM_DBG") ? atoi(getenv("MM_EM_DBG")) : 0};
+  EmLoop a{E->read_off.p, E->eread.p, E->taxon.p, E->mapq.p, E->inv_nloc.p, E->n_reads, E->post_sorted.p, E->pos.p, E->item_lo.p, E->item_hi.p, E->n_items,
+           E->present.p, E->pt_item.p, E->n_present, E->item_sum.p, E->wg_ll.p, E->f_run.p, E->local_partial.p, T, E->ctrl.p, E->ll_trace.p, cap, it_limit};
   const dim3 grid((unsigned)E->n_wg), blk(256);
-  // One launch per phase is the default: measured against the resident kernel (MM_EM_RESIDENT=1, same phases behind grid barriers, bit-identical)
-  // it is the faster form on an idle GPU (35 against 44 us per iteration, tools/em_latency.py) and no slower beside another context's kernels
-  // (bench: 1.9 against 2.2 ms of EM per step) — the barriers' L2 write-back / invalidate and the wait for the slowest workgroup cost more
-  // than three launches on one stream do.
-  const bool force_split = getenv("MM_EM_RESIDENT") == nullptr || getenv("MM_EM_SPLIT") != nullptr;
-  bool split = force_split || ctx->em_split;
-  // MM_EM_SPLIT=2: P2 and P3 in one launch (em_p23_kernel).  Measured in round 6 (tools/em_latency.py, idle GPU): 48.4 us per iteration against 34.7 with a launch
-  // per phase — 256 agent-scope releases (an L2 write-back each) and the arrival counter cost more than the launch they save.  Kept as the record of that.
-  const bool three_launches = !(getenv("MM_EM_SPLIT") && atoi(getenv("MM_EM_SPLIT")) == 2);
-  if (force_split) E->bar.zero(st);                              // (bar[2]: em_p23_kernel's arrival count)
-  // a communicator of ONE rank has nothing to exchange: the run is the resident kernel, as without a communicator (MM_EM_FORCE_COLLECTIVE=1
-  // keeps kernel A | ncclAllReduce | kernel B also then: how the tests drive the collective path on a one-GPU box)
+  // a communicator of ONE rank has nothing to exchange: the run is the plain loop, as without a communicator (MM_EM_FORCE_COLLECTIVE=1
+  // keeps P3' | ncclAllReduce | finalize also then: how the tests drive the collective path on a one-GPU box)
   const bool collective = ctx->comm && (ctx->comm_size > 1 || getenv("MM_EM_FORCE_COLLECTIVE") != nullptr);
-  auto fetch_ctrl = [&] {
-    MM_HIP(hipMemcpyAsync(h_ctrl, E->ctrl.p, sizeof h_ctrl, hipMemcpyDeviceToHost, st));
-    MM_HIP(mm::stream_sync(st));
-    if (h_ctrl[4]) {                                             // a grid barrier timed out: the state is that of the last completed iteration (P1 / P2 only write scratch)
-      if (!ctx->em_split) fprintf(stderr, "libmetamaps_hip: the resident EM kernel could not get its %d workgroups onto device %d together; "
-                                          "this context goes on with one launch per phase\n", E->n_wg, ctx->device);
-      ctx->em_split = split = true;
-      h_ctrl[4] = 0;
-      if (h_ctrl[1] == 3) h_ctrl[1] = 0;                         // (several ranks: the all-reduced abort mark stopped the rest of the enqueued group on every rank)
-      MM_HIP(hipMemcpyAsync(E->ctrl.p, h_ctrl, sizeof h_ctrl, hipMemcpyHostToDevice, st));
-      MM_HIP(hipMemsetAsync(E->local_partial.p + T + 1, 0, sizeof(double), st));
-      MM_HIP(mm::stream_sync(st));
-    }
-  };
   // iterations are enqueued in groups with one read of the control word behind each; iterations behind the stop are no-ops (every kernel leaves at once, the
   // collective still runs: the ranks' sequences must match).  The reference's runs take 20-40 iterations: a first group of 24, then eights — two host round
   // trips for a run of 29 instead of four (round 5; each is a copy, a wait and, under a small CPU budget, a sleep: mm::stream_sync).
   int group_no = 0;
   while (!h_ctrl[1] && h_ctrl[0] < it_limit) {
     const int GROUP = group_no++ == 0 ? 24 : 8;
-    if (!collective && !split) {                                 // one rank: the whole run is one launch
-      E->bar.zero(st);
-      em_loop_kernel<false><<<grid, blk, 0, st>>>(a);
+    const int g_n = (int)std::min<long long>(GROUP, it_limit - h_ctrl[0]);   // (the same on every rank: h_ctrl holds all-reduced decisions)
+    for (int g = 0; g < g_n; ++g) {
+      em_p1_kernel<<<grid, blk, 0, st>>>(a); MM_KERNEL_CHECK();
+      em_p2_kernel<<<grid, blk, 0, st>>>(a); MM_KERNEL_CHECK();
+      if (collective) em_p3_kernel<true><<<dim3(1), blk, 0, st>>>(a, E->n_wg); else em_p3_kernel<false><<<dim3(1), blk, 0, st>>>(a, E->n_wg);
       MM_KERNEL_CHECK();
-    } else {
-      const int g_n = (int)std::min<long long>(GROUP, it_limit - h_ctrl[0]);   // (the same on every rank: h_ctrl holds all-reduced decisions)
-      for (int g = 0; g < g_n; ++g) {
-        if (!split) {
-          E->bar.zero(st);
-          em_loop_kernel<true><<<grid, blk, 0, st>>>(a);
-          MM_KERNEL_CHECK();
-        } else if (three_launches) {
-          em_p1_kernel<<<grid, blk, 0, st>>>(a); MM_KERNEL_CHECK();
-          em_p2_kernel<<<grid, blk, 0, st>>>(a); MM_KERNEL_CHECK();
-          if (collective) em_p3_kernel<true><<<dim3(1), blk, 0, st>>>(a, E->n_wg); else em_p3_kernel<false><<<dim3(1), blk, 0, st>>>(a, E->n_wg);
-          MM_KERNEL_CHECK();
-        } else {
-          em_p1_kernel<<<grid, blk, 0, st>>>(a); MM_KERNEL_CHECK();
-          if (collective) em_p23_kernel<true><<<grid, blk, 0, st>>>(a); else em_p23_kernel<false><<<grid, blk, 0, st>>>(a);
-          MM_KERNEL_CHECK();
-        }
-        if (collective) {                                        // fEM.h:583-600, across GPUs instead of OpenMP threads
-          ncclResult_t rc = ncclAllReduce(E->local_partial.p, E->partial.p, (size_t)T + 2, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, st);
-          MM_REQUIRE(rc == ncclSuccess, MM_ERR_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(rc));
-          em_finalize_kernel<<<dim3(1), blk, 0, st>>>(E->partial.p, T, E->f_run.p, E->ctrl.p, E->ll_trace.p, cap, it_limit);
-          MM_KERNEL_CHECK();
-        }
+      if (collective) {                                          // fEM.h:583-600, across GPUs instead of OpenMP threads
+        ncclResult_t rc = ncclAllReduce(E->local_partial.p, E->partial.p, (size_t)T + 1, ncclDouble, ncclSum, (ncclComm_t)ctx->comm, st);
+        MM_REQUIRE(rc == ncclSuccess, MM_ERR_COMM, std::string("ncclAllReduce: ") + ncclGetErrorString(rc));
+        em_finalize_kernel<<<dim3(1), blk, 0, st>>>(E->partial.p, T, E->f_run.p, E->ctrl.p, E->ll_trace.p, cap, it_limit);
+        MM_KERNEL_CHECK();
       }
     }
-    fetch_ctrl();
+    MM_HIP(hipMemcpyAsync(h_ctrl, E->ctrl.p, sizeof h_ctrl, hipMemcpyDeviceToHost, st));
+    MM_HIP(mm::stream_sync(st));
   }
   const int n_iter = (int)(h_ctrl[0] - it0);
-  if (getenv("MM_EM_PROF") && n_iter > 0)                        // ticks of the 100 MHz clock, workgroup 0: P1 | barrier 1 | P2 — the rest of an iteration is barrier 2 + P3
-    fprintf(stderr, "MM_EM_PROF %d iterations: P1 %.1f us, barrier 1 %.1f us, P2 %.1f us per iteration\n", n_iter, h_ctrl[5] / 100.0 / n_iter, h_ctrl[6] / 100.0 / n_iter, h_ctrl[7] / 100.0 / n_iter);
   if (stopped) *stopped = h_ctrl[1] == 1;
   if (f_out) E->f_run.download(f_out, (size_t)T, st);
   if (ll_trace && ll_cap > 0 && n_iter > 0) E->ll_trace.download(ll_trace, (size_t)std::min(std::min(n_iter, ll_cap), cap), st);

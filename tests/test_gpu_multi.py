@@ -93,8 +93,8 @@ def test_replicated_chunks_over_devices(small_run):
 
 
 def test_classify_through_rccl_one_rank(small_run):
-    """`classify --gpus 1` with MM_EM_FORCE_COLLECTIVE=1: the EM loop goes through ncclCommInitRank / kernel A | ncclAllReduce | kernel B (one rank)
-    and writes the oracle's files; without the switch the one-rank communicator takes the resident kernel: the same files"""
+    """`classify --gpus 1` with MM_EM_FORCE_COLLECTIVE=1: the EM loop goes through ncclCommInitRank / P1 | P2 | P3' | ncclAllReduce | finalize
+    (one rank) and writes the oracle's files; without the switch the one-rank communicator runs the plain loop: the same files"""
     o1, _, _ = _gpu_map(small_run, "cls", [])
     for env in (dict(os.environ, MM_EM_FORCE_COLLECTIVE="1"), dict(os.environ)):
         p = subprocess.run([CLI, "classify", "--DB", small_run["db"].dir, "--mappings", o1, "--minreads", "3", "--gpus", "1"], capture_output=True, timeout=900, env=env)
@@ -192,22 +192,23 @@ def _em_problem(seed, n_reads, n_taxa, sigma=2.0, tied=True):
 
 
 @pytest.mark.parametrize("n_reads,n_taxa", [(60_000, 700), (900, 40), (3, 5)])
-def test_em_resident_kernel_equals_its_phases_as_launches(n_reads, n_taxa, monkeypatch):
-    """the whole EM run as ONE resident kernel (MM_EM_RESIDENT=1: grid barriers between E step, per-taxon sums and normalisation + stop rule) gives, bit for bit,
-    what the same phases give as separate launches (the default since the two were measured against each other), also when a barrier gives up mid-run (MM_EM_BARRIER_TICKS=1: the run goes on
-    phase by phase from the last completed iteration); other grid sizes (another summation shape of the log-likelihood) agree to 1e-12; with a
-    one-rank communicator (kernel A | ncclAllReduce | kernel B per iteration) as well; exactly tied taxa stay exactly tied in every form"""
+def test_em_loop_is_invariant_to_grid_and_collective_form(n_reads, n_taxa, monkeypatch):
+    """the EM loop (one launch per phase: E step, per-taxon sums, normalisation + stop rule) agrees with itself across grid sizes (another summation
+    shape of the log-likelihood) to 1e-12; grids 1 and 7 put far more reads into a workgroup than P1's LDS buffers hold (60 000 reads over 7
+    workgroups: ~8 600 per block against EM_RBUF = 192), so they run P1's thread-per-read form against the LDS form of the other grids; with a
+    one-rank communicator (P3' | ncclAllReduce | finalize per iteration) as well, and without the switch that communicator gives the plain run bit
+    for bit; exactly tied taxa stay exactly tied in every form"""
     from metamaps_amd import capi, emhost
     off, taxon, mapq, inv, T = _em_problem(7 + n_reads, n_reads, n_taxa)
     f0 = np.full(T, 1.0 / T)
 
     def run(env, comm=False):
-        for kk in ("MM_EM_SPLIT", "MM_EM_RESIDENT", "MM_EM_GRID", "MM_EM_BARRIER_TICKS", "MM_EM_FORCE_COLLECTIVE"):
+        for kk in ("MM_EM_GRID", "MM_EM_FORCE_COLLECTIVE"):
             monkeypatch.delenv(kk, raising=False)
         for kk, v in env.items():
             monkeypatch.setenv(kk, v)
         if comm:
-            monkeypatch.setenv("MM_EM_FORCE_COLLECTIVE", "1")     # (a one-rank communicator alone takes the resident kernel: nothing to exchange)
+            monkeypatch.setenv("MM_EM_FORCE_COLLECTIVE", "1")     # (a one-rank communicator alone runs the plain loop: nothing to exchange)
         ctx = capi.Context(0)
         if comm:
             ctx.comm_init(capi.Context.comm_unique_id(), 0, 1)
@@ -220,33 +221,22 @@ def test_em_resident_kernel_equals_its_phases_as_launches(n_reads, n_taxa, monke
         assert stopped and np.array_equal(np.concatenate([lls5, llsc]), lls) and np.array_equal(fc, f)
         return f, lls, best
 
-    G = {"MM_EM_GRID": "96"}                                      # (the two forms default to different grids; the log-likelihood is summed in the grid's shape)
-    f_a, ll_a, best_a = run({"MM_EM_RESIDENT": "1", **G})
+    f_a, ll_a, _ = run({"MM_EM_GRID": "96"})
     assert len(ll_a) >= 3 and abs(f_a.sum() - 1) < 1e-12
     if T > 4:
         assert f_a[1] == f_a[2] and f_a[1] > 0                    # the twins
-    f_b, ll_b, best_b = run(G)                                    # the default form: one launch per phase
-    assert np.array_equal(f_a, f_b) and np.array_equal(ll_a, ll_b) and np.array_equal(best_a, best_b)
-    f_3, ll_3, best_3 = run({"MM_EM_SPLIT": "2", **G})            # P1 | P2 + P3 (the workgroup that finishes its items last runs P3: measured slower, kept as the record)
-    assert np.array_equal(f_a, f_3) and np.array_equal(ll_a, ll_3) and np.array_equal(best_a, best_3)
-    f_c, ll_c, best_c = run({"MM_EM_RESIDENT": "1", "MM_EM_BARRIER_TICKS": "1", **G})
-    assert np.array_equal(f_a, f_c) and np.array_equal(ll_a, ll_c)
     f_0, ll_0, _ = run({})                                        # the default grid
     assert len(ll_0) == len(ll_a) and np.allclose(ll_0, ll_a, rtol=1e-12, atol=0) and np.allclose(f_0, f_a, rtol=1e-10, atol=1e-300)
-    f_d, ll_d, _ = run({"MM_EM_DBG": "3"})                        # P1 thread-per-read (the form blocks too large for the LDS buffers take): another summation order of ll only
-    monkeypatch.delenv("MM_EM_DBG", raising=False)
-    assert len(ll_d) == len(ll_a) and np.allclose(ll_d, ll_a, rtol=1e-12, atol=0) and np.allclose(f_d, f_a, rtol=1e-10, atol=1e-300)
     for grid in ("1", "7", "256"):
-        f_g, ll_g, _ = run({"MM_EM_GRID": grid} if grid == "7" else {"MM_EM_GRID": grid, "MM_EM_RESIDENT": "1"})
+        f_g, ll_g, _ = run({"MM_EM_GRID": grid})
         assert len(ll_g) == len(ll_a) and np.allclose(ll_g, ll_a, rtol=1e-12, atol=0) and np.allclose(f_g, f_a, rtol=1e-10, atol=1e-300)
         if T > 4:
             assert f_g[1] == f_g[2]
-    for env in ({}, {"MM_EM_SPLIT": "2"}, {"MM_EM_RESIDENT": "1"}, {"MM_EM_RESIDENT": "1", "MM_EM_BARRIER_TICKS": "1"}):
-        f_m, ll_m, _ = run(env, comm=True)
-        assert len(ll_m) == len(ll_a) and np.allclose(ll_m, ll_a, rtol=1e-12, atol=0) and np.allclose(f_m, f_a, rtol=1e-10, atol=1e-300)
-        if T > 4:
-            assert f_m[1] == f_m[2]
-    monkeypatch.delenv("MM_EM_FORCE_COLLECTIVE", raising=False); monkeypatch.delenv("MM_EM_RESIDENT", raising=False); monkeypatch.delenv("MM_EM_BARRIER_TICKS", raising=False)
+    f_m, ll_m, _ = run({}, comm=True)
+    assert len(ll_m) == len(ll_a) and np.allclose(ll_m, ll_a, rtol=1e-12, atol=0) and np.allclose(f_m, f_a, rtol=1e-10, atol=1e-300)
+    if T > 4:
+        assert f_m[1] == f_m[2]
+    monkeypatch.delenv("MM_EM_FORCE_COLLECTIVE", raising=False)
     ctx = capi.Context(0)                                         # a one-rank communicator without the switch: no collective, bit for bit the plain run
     ctx.comm_init(capi.Context.comm_unique_id(), 0, 1)
     e = ctx.em(off, taxon, mapq, inv, T)
