@@ -22,6 +22,11 @@ Multi-GPU: one process per GPU (torch.distributed launch), index replicated, eve
 `--reads` reads (weak scaling: per-GPU work fixed; the default) or — `--scaling strong`, BASELINE configs[2] — its contiguous shard of
 ONE batch of `--reads` reads that every rank generates; EM sufficient statistics all-reduced over RCCL (also at N = 1: the same
 code path at every N).  Timing: barrier + synchronize on both sides of exactly K steps, MAX over ranks; rank 0 prints one JSON line.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.  Everything
+else it can measure runs with --full only: the stage times and roofline of a step that owns the GPU (two more steps), one batch mapped
+again and again (config.one_batch_repeated), --measure-free-overlap, the CPU baseline and the CLI on a sample of the workload
+(cpu_baseline, e2e_cli), the other reference shape (config.other_shape) and the CLI at full size (e2e_cli_full, e2e_cli_stream).
 """
 from __future__ import annotations
 
@@ -77,19 +82,21 @@ def parse_args():
                     "duration then includes the time it shares the CUs (K1 issues VALU instructions in 99 percent of its cycles: the two do not complement each other)")
     ap.add_argument("--hold-lock-to-the-end", action="store_true", help="release the mapping lock when mm_map_batch returns instead of when its last big kernel is enqueued")
     ap.add_argument("--free-overlap", action="store_true", help="(the default since round 3; kept for old command lines) do not serialise the mapping sections of the workers")
-    ap.add_argument("--measure-free-overlap", action="store_true", help="after the timed region, six more steps with nothing serialised, reported in config.free_overlap")
+    ap.add_argument("--full", action="store_true", help="after the headline, every side measurement (the module docstring lists them; the --no-* options leave parts "
+                    "out).  Off by default: a plain run sets up, warms up, times its steps and prints the line")
+    ap.add_argument("--measure-free-overlap", action="store_true", help="(--full) after the timed region, six more steps with nothing serialised, reported in config.free_overlap")
     ap.add_argument("--config", type=int, choices=(1, 3, 4, 5), default=1, help="BASELINE.json configs[N] as far as one GPU carries it: 1 (default, the configuration `value` is "
                     "quoted on) 100k x 10 kb ONT reads vs the resident index; 3: mixed 1-50 kb PacBio reads vs the index split by the --maxmemory chunk rule into resident "
                     "chunk indexes; 4: 10 kb reads vs chunk indexes that are built, mapped and dropped in turn (the multi-pass streaming of an index larger than HBM)")
     ap.add_argument("--distinct-batches", type=int, default=24, help="read batches generated up front (seeds 1000 + rank + 97 i); step s maps batch s mod this")
     ap.add_argument("--chunk-gib", type=float, default=0.0, help="--maxmemory of configs 3 / 4 in GiB (default 70 -> 4 chunks for config 3, 25 -> 11 chunks for config 4)")
     ap.add_argument("--batches-per-pass", type=int, default=4, help="config 4: read batches mapped against every chunk index of a pass (the index builds of a pass are inside the timed region)")
-    ap.add_argument("--no-e2e-full", action="store_true", help="skip e2e_cli_full (the drop-in CLI on the whole 26.8 GB DB.fa written to local disk: ~2 minutes)")
-    ap.add_argument("--no-e2e-stream", action="store_true", help="skip e2e_cli_stream (the CLI on --e2e-stream-batches batches in one FASTQ; inside e2e_cli_full)")
+    ap.add_argument("--no-e2e-full", action="store_true", help="(--full) skip e2e_cli_full (the drop-in CLI on the whole 26.8 GB DB.fa written to local disk: ~2 minutes)")
+    ap.add_argument("--no-e2e-stream", action="store_true", help="(--full) skip e2e_cli_stream (the CLI on --e2e-stream-batches batches in one FASTQ; inside e2e_cli_full)")
     ap.add_argument("--e2e-stream-batches", type=int, default=10)
     ap.add_argument("--e2e-dir", default=os.environ.get("MM_BENCH_E2E_DIR", ""), help="directory for the files of e2e_cli_full (default: a temporary directory)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-shape", action="store_true", help="skip the second reference shape (config.other_shape)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip cpu_baseline and e2e_cli")
+    ap.add_argument("--no-other-shape", action="store_true", help="(--full) skip the second reference shape (config.other_shape)")
     ap.add_argument("--cpu-sample-reads", type=int, default=20000)
     ap.add_argument("--cpu-threads", type=int, default=0, help="oracle threads for cpu_baseline (0 = all host cores)")
     ap.add_argument("--cpu-sample-genomes", type=int, default=100, help="at least this many contigs in the CPU sample reference ...")
@@ -102,6 +109,8 @@ def parse_args():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.config != 1:
         ap.error("--dump-outputs covers the default config only")
+    if args.measure_free_overlap and not args.full:
+        ap.error("--measure-free-overlap is a side measurement: it needs --full")
     return args
 
 
@@ -371,8 +380,8 @@ def main():
         if len(gaps) <= 64:
             step_ms["all"] = [round(float(g), 1) for g in gaps]
         # stage times of a step whose kernels all own the GPU (the timed region lets the next step's K1 queue behind K5): two more steps, untimed
-        st_clean = st
-        if W > 1 and not hold_lock[0]:                               # (one lock, held to the end of the mapping section)
+        st_clean = st if args.full else None
+        if args.full and W > 1 and not hold_lock[0]:                 # (one lock, held to the end of the mapping section)
             keep = dict(agg); keep["done_t"] = list(agg["done_t"])
             hold_lock[0] = True; run_steps(2, True); hold_lock[0] = False
             st_clean = agg["stats"]
@@ -380,7 +389,7 @@ def main():
         # beside the headline: the same number of steps ... six steps that map ONE batch again and again (what rounds 1 and 2 timed): the
         # distance between the two is what the batch-to-batch variation of the workload costs (other genomes, other candidate counts)
         same = None
-        if world == 1 and B > 1 and shape == args.shape:
+        if args.full and world == 1 and B > 1 and shape == args.shape:
             keep = dict(agg); keep["done_t"] = list(agg["done_t"]); agg["bases"] = 0
             saved = list(batches)
             batches[:] = [saved[0]] * len(saved)
@@ -441,10 +450,6 @@ def main():
     out = None
     if rank == 0:
         agg, st, info = R["agg"], R["st"], R["info"]
-        roof = roofline_block(args, R)
-        roof["peak_measured"] = HBM_PEAK_MEASURED_GBS
-        roof["peak_measured_source"] = "tools/ubench/stream46k (round 3): 6.3 TB/s for this access pattern; frac stays algorithmic bytes / the nominal 8 TB/s"
-        roof["frac_of_measured_peak"] = roof["achieved"] / HBM_PEAK_MEASURED_GBS if roof.get("achieved") else None
         len_txt = f"{args.read_len}" if not args.read_len_min else f"{args.read_len_min}-{args.read_len}"
         out_workload = (f"{args.reads} synthetic {len_txt} bp {'PacBio' if args.pacbio else 'ONT'}-error reads {'per GPU' if args.scaling == 'weak' else f'in all, sharded over {world} GPU(s)'} vs synthetic miniSeq+H-shaped index "
                         f"({R['desc']}; {R['reference_bp'] / 1e9:.2f} Gbp), k=16 w={w}, --all")
@@ -469,15 +474,20 @@ def main():
                 "per_step": {kk: st[kk] for kk in ("n_reads_long_enough", "n_reads_mapped", "n_mappings", "sum_sketch", "sum_hits",
                                                    "n_candidates", "sum_l2_stream_entries", "sum_l2_evals", "n_ambiguous_sketch_reads",
                                                    "sum_hits_kept", "n_l2_rebuilds", "n_l2_wide_redo")},
-                "stage_ms": {kk: round(R["st_clean"][kk], 3) for kk in st if kk.startswith("ms_")},
-                "stage_ms_note": "stage times of a step run after the timed region with the mapping lock held to the end of the step; in the timed region the next step's K1 "
-                                 "queues behind K5 (config.parallelism), which shows up in that step's ms_minimizer / ms_total: stage_ms_timed_region",
                 "stage_ms_timed_region": {kk: round(st[kk], 3) for kk in st if kk.startswith("ms_")},
                 "host_wall_ms": {kk: round(v, 3) for kk, v in agg.get("host_ms", {}).items()},
             },
-            "roofline": roof,
         }
-        if not args.no_cpu_baseline and world == 1:              # (the contract asks for it at N=1 only)
+        if args.full:                                             # from the steps run_shape adds behind the timed region (st_clean)
+            out["config"]["stage_ms"] = {kk: round(R["st_clean"][kk], 3) for kk in st if kk.startswith("ms_")}
+            out["config"]["stage_ms_note"] = ("stage times of a step run after the timed region with the mapping lock held to the end of the step; in the timed region the next step's K1 "
+                                              "queues behind K5 (config.parallelism), which shows up in that step's ms_minimizer / ms_total: stage_ms_timed_region")
+            roof = roofline_block(args, R)
+            roof["peak_measured"] = HBM_PEAK_MEASURED_GBS
+            roof["peak_measured_source"] = "tools/ubench/stream46k (round 3): 6.3 TB/s for this access pattern; frac stays algorithmic bytes / the nominal 8 TB/s"
+            roof["frac_of_measured_peak"] = roof["achieved"] / HBM_PEAK_MEASURED_GBS if roof.get("achieved") else None
+            out["roofline"] = roof
+        if args.full and not args.no_cpu_baseline and world == 1:    # (the contract asks for it at N=1 only)
             # the CLI of the e2e_cli leg is another process on this device: what this one holds in reserve goes back first (the contexts'
             # cached blocks, which since round 4 are pieces of the ~100 GB of pooled index-build buffers: with those kept the device had
             # 0.6 GiB left and the CLI's index build failed for lack of memory)
@@ -490,7 +500,7 @@ def main():
                 tail = (" | stderr: " + tail.decode(errors="replace")[-400:]) if isinstance(tail, (bytes, bytearray)) and tail else ""
                 out["cpu_baseline"] = {"value": None, "unit": "Gbp/s", "cores": 1, "kind": "port", "sample": f"failed: {e}{tail}"}
     # the other reference shape, beside the headline (one GPU only: it costs a second index build)
-    if world == 1 and not args.no_other_shape:
+    if args.full and world == 1 and not args.no_other_shape:
         for rd in R["reads_w"]:
             rd.close()
         for kk in ("idx", "ref"):
@@ -514,7 +524,7 @@ def main():
     R["idx"].close(); R["ref"].close()
     for c in ctxs:
         c.close()
-    if rank == 0 and world == 1 and not args.no_e2e_full and (args.scale == 1.0 or os.environ.get("MM_BENCH_E2E_ANY_SCALE")) and args.shape == "community" and not args.read_len_min:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e_full and (args.scale == 1.0 or os.environ.get("MM_BENCH_E2E_ANY_SCALE")) and args.shape == "community" and not args.read_len_min:
         try:
             out["e2e_cli_full"] = e2e_cli_full(args, k, w, 1000 + rank)
             out["e2e_cli_stream"] = out["e2e_cli_full"].pop("e2e_cli_stream", None)

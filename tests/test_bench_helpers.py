@@ -65,6 +65,15 @@ def test_bench_steps_and_dump_arguments():
             _parse(*bad)
 
 
+def test_bench_side_measurements_need_full():
+    """a plain run measures the headline alone: --full is off by default, and a side measurement asked for without it is refused"""
+    import pytest
+    assert not _parse().full and _parse("--full").full
+    assert _parse("--full", "--measure-free-overlap").measure_free_overlap
+    with pytest.raises(SystemExit):
+        _parse("--measure-free-overlap")
+
+
 def test_step_outputs_and_dump_within_budget(tmp_path, monkeypatch):
     """what a step returns, as float64 arrays; all of it when it fits, else the same seeded rows of the large arrays, under the budget"""
     import bench

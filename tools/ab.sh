@@ -13,7 +13,7 @@ for v in "$@"; do
     env:*) kv=${v#env:}; export "$kv"; AB_LAST_ENV=${kv%%=*} ;;          # the in-tree build under an environment switch, e.g. env:MM_L2_ONE_STREAM=1
     *) export MM_LIB_PATH=$PWD/_ab/$v/libmetamaps_hip.so ;;
   esac
-  python bench.py $F 2>/dev/null | python -c "
+  python bench.py --full $F 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); k=d['roofline']['kernels']
 print('$v', round(d['value'],2), 'Gbp/s', round(d['ms_per_step'],2), 'ms/step | alone / timed:', ' '.join(f\"{n} {k[n]['ms_alone']:.2f}/{k[n]['ms_timed_region']:.2f}\" for n in k), '| index build', d['config']['index_build_s'], 's | stage', d['config']['stage_ms'])"
