@@ -28,7 +28,7 @@ extern "C" {
 #define MM_ABI_VERSION 6   /* 3: mm_seqset_slice/concat, mm_map_batch_reusing, mm_em_continue, mm_synth_community_species;
                             * 4: mm_sketch_batch, mm_ctx_release_cached, mm_index_dup_neighbours;
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
-                            * 6: mm_index_save, mm_index_load */
+                            * 6: mm_index_save, mm_index_load; mm_em_bootstrap (an addition to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -344,6 +344,15 @@ int mm_em_run(mm_em* em, const double* f0, int max_iter, double* f_out, double* 
 int mm_em_continue(mm_em* em, int max_iter, double* f_out, double* ll_trace, int ll_cap, int* n_iter, int* stopped);
 /* final posteriors p_i for the current f (fEM.h:684-707) and the index of the best mapping per read (fEM.h:217) */
 int mm_em_posteriors(mm_em* em, const double* f, double* post /* [n_entries] */, int64_t* best /* [n_reads] */);
+/* Read-level Poisson bootstrap of the EM (not in the reference): replicates rep0 .. rep0+n_rep-1 of `em`, each the weighted EM
+ * started from f_start with weights w(r,i) = boot_weight(seed, r, i), or weights[(r-rep0)*n_reads + i] if weights != NULL.
+ * f_out [n_rep*n_taxa] (replicate-major), ll_out [n_rep], n_iter [n_rep], stopped [n_rep] (1: stop rule, 0: max_iter reached).
+ * Read i is the i-th read WITH a mapping (reads without one are not resampled), so n_reads above counts those reads.  The stop rule is
+ * mm_em_run's, per replicate; a replicate that has stopped is frozen.  Results do not depend on how the replicates are split over calls
+ * or devices.  The communicator of the context is never used.  MM_ERR_LIMIT when the per-replicate buffers (n_entries*n_rep*8 bytes of
+ * posteriors and n_taxa*n_rep*8 of frequencies) exceed the device, MM_ERR_NOMEM when they do not fit its free memory: the caller tiles. */
+int mm_em_bootstrap(mm_em* em, const double* f_start, int32_t rep0, int32_t n_rep, uint64_t seed, const uint8_t* weights,
+                    int max_iter, double* f_out, double* ll_out, int32_t* n_iter, int32_t* stopped);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------------------------- */
 #define MM_COMM_ID_BYTES 128

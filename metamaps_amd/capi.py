@@ -172,6 +172,7 @@ def lib() -> C.CDLL:
             "mm_em_posteriors": (C.c_int, [vp, vp, vp, vp]),
             "mm_em_run": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, P(C.c_int)]),
             "mm_em_continue": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, P(C.c_int), P(C.c_int)]),
+            "mm_em_bootstrap": (C.c_int, [vp, vp, i32, i32, u64, vp, C.c_int, vp, vp, vp, vp]),
             "mm_comm_unique_id": (C.c_int, [C.c_char_p]),
             "mm_comm_init": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
             "mm_comm_allreduce_f64": (C.c_int, [vp, vp, i64]),
@@ -374,7 +375,7 @@ class Context:
         inv_nloc = np.ascontiguousarray(inv_nloc, dtype=np.float64)
         h = C.c_void_p()
         self.check(lib().mm_em_create(self.h, len(read_off) - 1, _ptr(read_off), _ptr(taxon), _ptr(mapq), _ptr(inv_nloc), n_taxa, C.byref(h)))
-        return EM(self, h, n_taxa, len(read_off) - 1, len(taxon))
+        return EM(self, h, n_taxa, len(read_off) - 1, len(taxon), n_mapped=int(np.count_nonzero(np.diff(read_off))))
 
     def em_from_mapping(self, mapping: "Mapping", contig_taxon, contig_len, n_taxa: int) -> "EM":
         """the EM problem of `classify` built on the device from the mapping's records (after add_qualities)"""
@@ -630,8 +631,9 @@ class Mapping:
 
 
 class EM:
-    def __init__(self, ctx: Context, h, n_taxa: int, n_reads: int, n_entries: int):
+    def __init__(self, ctx: Context, h, n_taxa: int, n_reads: int, n_entries: int, n_mapped: int | None = None):
         self.ctx, self.h, self.n_taxa, self.n_reads, self.n_entries = ctx, h, n_taxa, n_reads, n_entries
+        self.n_mapped = n_mapped                                   # reads with at least one mapping (the bootstrap's reads), where known
 
     def iterate(self, f: np.ndarray):
         f = np.ascontiguousarray(f, dtype=np.float64)
@@ -663,6 +665,26 @@ class EM:
         n, stopped = C.c_int(), C.c_int()
         self.ctx.check(lib().mm_em_continue(self.h, max_iter, _ptr(f), _ptr(ll), len(ll), C.byref(n), C.byref(stopped)))
         return f, ll[:min(n.value, len(ll))], bool(stopped.value)
+
+    def bootstrap(self, f_start: np.ndarray, n_rep: int, seed: int, rep0: int = 0, weights=None, max_iter: int = 10_000):
+        """read-level Poisson bootstrap: replicates rep0 .. rep0 + n_rep - 1 of the weighted EM from f_start (mm_em_bootstrap).
+        weights: optional uint8 [n_rep, n_mapped] instead of the generated ones.  Returns (f [n_rep, n_taxa], ll [n_rep],
+        n_iter [n_rep], stopped [n_rep] bool)."""
+        f_start = np.ascontiguousarray(f_start, dtype=np.float64)
+        if f_start.shape != (self.n_taxa,):
+            raise ValueError(f"f_start must have {self.n_taxa} values")
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.uint8)
+            if weights.ndim != 2 or weights.shape[0] != n_rep or (self.n_mapped is not None and weights.shape[1] != self.n_mapped):
+                raise ValueError(f"weights must be uint8 [n_rep, n_mapped] = [{n_rep}, {self.n_mapped}]")
+        n = max(int(n_rep), 0)
+        f = np.empty((n, self.n_taxa), dtype=np.float64)           # (empty: a refused call touches none of it)
+        ll = np.zeros(n, dtype=np.float64)
+        it = np.zeros(n, dtype=np.int32)
+        stopped = np.zeros(n, dtype=np.int32)
+        self.ctx.check(lib().mm_em_bootstrap(self.h, _ptr(f_start), int(rep0), int(n_rep), int(seed) & (2**64 - 1), _ptr(weights), int(max_iter),
+                                             _ptr(f), _ptr(ll), _ptr(it), _ptr(stopped)))
+        return f, ll, it, stopped.astype(bool)
 
     def taxon_counts(self) -> np.ndarray:
         c = np.zeros(self.n_taxa, dtype=np.int64)

@@ -7,7 +7,7 @@
 //
 //   metamaps mapDirectly [--all] -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
-//   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N]
+//   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]]
 //
 // --gpus N uses devices 0..N-1 of the node, one context per device on its own host thread (where the reference has -t N worker
 // threads, computeMap.hpp:104-176 / fEM.h:1229): mapping shards the read batches (index replicated) or the index chunks
@@ -119,6 +119,28 @@ Options parse(int argc, char** argv) {
     o.v[key] = argv[++i];
   }
   return o;
+}
+
+// --bootstrap B [--bootstrap-seed S] (classify, mapDirectly --then-classify; not in the reference): B read-level Poisson bootstrap replicates of
+// the EM after the point estimate, PREFIX.EM.WIMP.bootstrap beside the WIMP.  B = 0: off (nothing changes, no file appears).
+struct BootOpts { int B = 0; uint64_t seed = 1; };
+BootOpts boot_options(const Options& o) {
+  BootOpts b;
+  auto digits = [](const std::string& v) { return !v.empty() && v.size() <= 20 && v.find_first_not_of("0123456789") == std::string::npos; };
+  if (o.v.count("bootstrap")) {
+    const std::string& v = o.v.at("bootstrap");
+    if (!digits(v) || v.size() > 6 || std::stoul(v) < 2 || std::stoul(v) > 100000) die("--bootstrap takes an integer from 2 to 100000, not '" + v + "'");
+    b.B = (int)std::stoul(v);
+  }
+  if (o.v.count("bootstrap-seed")) {
+    const std::string& v = o.v.at("bootstrap-seed");
+    errno = 0;
+    const unsigned long long x = digits(v) ? strtoull(v.c_str(), nullptr, 10) : 0;
+    if (!digits(v) || errno == ERANGE) die("--bootstrap-seed takes an unsigned 64-bit integer, not '" + v + "'");
+    if (!b.B) die("--bootstrap-seed needs --bootstrap B");
+    b.seed = (uint64_t)x;
+  }
+  return b;
 }
 
 uint64_t file_size(const std::string& f) {                       // commonFunc.hpp:211-231
@@ -325,7 +347,7 @@ struct KeptLines {                                               // the mapping 
   std::vector<Part> parts; const std::vector<std::string>* cname = nullptr;
 };
 int classify_one(const std::vector<Dev>& devs, EmReduce reduce, const std::string& mapped, const std::string& db, size_t minReadsU,
-                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept = nullptr);
+                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept = nullptr, BootOpts boot = BootOpts());
 
 // One run of mapDirectly / index / mapAgainstIndex.  The state every stage shares lives in the object; the stages are its methods, in the order run()
 // calls them: parameters -> devices -> reference (parsed, packed, uploaded) or stored index -> chunk plan -> placement of the chunk indexes
@@ -1250,7 +1272,7 @@ struct MapRun {
       const bool last = fi + 1 == prefixes.size();
       KeptLines kl; kl.cname = &cname;
       if (keep_lines && fi < kept.size()) for (const auto& d : kept[fi]) kl.parts.push_back(KeptLines::Part{d->text.data(), d->meta.data(), d->meta.size(), d->off.data(), d->lens.size()});
-      classify_one(devs, reduce, prefixes[fi], o.v.at("then-classify"), minReadsU, last ? leave : std::function<void()>(), nullptr, keep_lines ? &kl : nullptr);
+      classify_one(devs, reduce, prefixes[fi], o.v.at("then-classify"), minReadsU, last ? leave : std::function<void()>(), nullptr, keep_lines ? &kl : nullptr, boot_options(o));
       if (keep_lines && fi < kept.size()) kept[fi].clear();
       for (auto& d : devs) mm_comm_destroy(d.ctx);
       pc.lap("9 classify");
@@ -1337,26 +1359,49 @@ std::string extract_taxon(const std::string& contig) {
   die("Could not extract taxon ID from contig identifier '" + contig + "' - did you use the MetMaps build scripts to construct your database?");
 }
 
+// The EMFrequency column of the WIMP (fEM.h:52-215): the frequencies go up the taxonomy (a sum above 1 is cut to 1 on the way), and per
+// level every taxon with a frequency or with reads (the level's keys, in order) gets its frequency over the level's sum.  The bootstrap
+// file puts every replicate through the same steps.  `up_memo` (optional) keeps the upward paths of the taxa between calls.
+struct WimpLevel { std::set<std::string> keys; std::map<std::string, double> emF; };
+using UpMemo = std::map<std::string, std::map<std::string, std::string>>;
+std::map<std::string, WimpLevel> wimp_em_frequencies(const Taxonomy& T, const std::map<std::string, double>& freq, const std::map<std::string, size_t>& reads,
+                                                     UpMemo* up_memo = nullptr) {
+  static const std::set<std::string> levels{"species", "genus", "family", "order", "phylum", "superkingdom"};
+  auto upward = [&](const std::string& id) {
+    if (up_memo) { auto it = up_memo->find(id); if (it != up_memo->end()) return it->second; }
+    auto up = T.upward_by_ranks(id, levels); up["definedGenomes"] = id;
+    if (up_memo) (*up_memo)[id] = up;
+    return up;
+  };
+  std::map<std::string, WimpLevel> W;
+  std::map<std::string, std::map<std::string, double>> fL;
+  for (auto& kv : freq) for (auto& u : upward(kv.first)) { fL[u.first][u.second] += kv.second; W[u.first].keys.insert(u.second); if (fL[u.first][u.second] > 1) fL[u.first][u.second] = 1; }
+  for (auto& kv : reads) for (auto& u : upward(kv.first)) W[u.first].keys.insert(u.second);
+  for (auto& lv : W) {
+    const std::string& L = lv.first; double sumF = 0;
+    for (auto& t : lv.second.keys) { double f = fL[L].count(t) ? fL[L][t] : 0; sumF += f; fL[L][t] = f; }
+    for (auto& t : lv.second.keys) lv.second.emF[t] = fL[L][t] / sumF;
+  }
+  return W;
+}
+
 void write_wimp(const std::string& fn, const Taxonomy& T, const std::map<std::string, double>& freq, const std::map<std::string, size_t>& reads,
                 size_t nTotal, size_t nUnmapped, size_t nTooShort) {   // fEM.h:52-215
   const std::set<std::string> levels{"species", "genus", "family", "order", "phylum", "superkingdom"};
-  std::map<std::string, std::set<std::string>> keys;
+  std::map<std::string, WimpLevel> W = wimp_em_frequencies(T, freq, reads);
   std::map<std::string, std::map<std::string, double>> fL; std::map<std::string, std::map<std::string, size_t>> rL;
-  for (auto& kv : freq) { auto up = T.upward_by_ranks(kv.first, levels); up["definedGenomes"] = kv.first;
-    for (auto& u : up) { fL[u.first][u.second] += kv.second; keys[u.first].insert(u.second); if (fL[u.first][u.second] > 1) fL[u.first][u.second] = 1; } }
   for (auto& kv : reads) { auto up = T.upward_by_ranks(kv.first, levels); up["definedGenomes"] = kv.first;
-    for (auto& u : up) { rL[u.first][u.second] += kv.second; keys[u.first].insert(u.second); } }
+    for (auto& u : up) rL[u.first][u.second] += kv.second; }
   const long long nMappable = (long long)nTotal - (long long)nTooShort, nMapped = nMappable - (long long)nUnmapped;
   std::ofstream o(fn);
   o << "AnalysisLevel\ttaxonID\tName\tAbsolute\tEMFrequency\tPotFrequency\n";
-  for (auto& lv : keys) {
-    const std::string& L = lv.first; std::map<std::string, double> emF; double sumF = 0;
-    for (auto& t : lv.second) { double f = fL[L].count(t) ? fL[L][t] : 0; size_t r = rL[L].count(t) ? rL[L][t] : 0; sumF += f; fL[L][t] = f; rL[L][t] = r; }
-    for (auto& t : lv.second) { fL[L][t] /= sumF; emF[t] = fL[L][t]; }
+  for (auto& lv : W) {
+    const std::string& L = lv.first; std::map<std::string, double>& emF = lv.second.emF;
+    for (auto& t : lv.second.keys) { size_t r = rL[L].count(t) ? rL[L][t] : 0; rL[L][t] = r; fL[L][t] = emF[t]; }
     const double propMapped = (double)nMapped / nMappable; double propNot = (double)nUnmapped / nMappable;
-    for (auto& t : lv.second) fL[L][t] *= propMapped;
+    for (auto& t : lv.second.keys) fL[L][t] *= propMapped;
     double emUnm = 0; size_t nUnmUndef = nUnmapped;
-    for (auto& t : lv.second) {
+    for (auto& t : lv.second.keys) {
       if (t != "Undefined") o << L << "\t" << t << "\t" << T.T.at(t).sci << "\t" << rL[L][t] << "\t" << emF[t] << "\t" << fL[L][t] << "\n";
       else { nUnmUndef += rL[L][t]; emUnm += emF[t]; propNot += fL[L][t]; }
     }
@@ -1670,6 +1715,8 @@ struct ClassifyRun {
   std::vector<int> contig_tx; std::vector<long long> contig_len_ti;   // per contig: taxon index; length per taxonInfo (-1: not listed)
   std::vector<int32_t> taxon; std::vector<double> mapq, inv;          // per mapping
   std::vector<double> f, post; std::vector<int64_t> best;
+  BootOpts boot;                                                  // --bootstrap: the replicates' frequencies of the present taxa, [replicate][boot_pres]
+  std::vector<int32_t> boot_pres; std::vector<double> boot_f;
 
   ClassifyRun(const std::vector<Dev>& devs_, EmReduce reduce_, const std::string& mapped_, const std::string& db_, size_t minReadsU_, const std::function<void()>& leave_now_,
               const std::function<void()>& need_devices_) : devs(devs_), reduce(reduce_), mapped(mapped_), db(db_), minReadsU(minReadsU_), leave_now(leave_now_), need_devices(need_devices_) {}
@@ -1834,6 +1881,93 @@ struct ClassifyRun {
     if (need_devices) need_devices();
     run_em_sharded(devs, reduce, off, taxon, mapq, inv, NT, f, post, best);
   }
+  // --bootstrap B: replicates 0..B-1 of the weighted EM (mm_em_bootstrap), started from the point estimate, dealt to the devices in contiguous
+  // ranges; every device holds the whole EM problem and tiles its range to its free memory.  The result depends on neither.
+  void bootstrap() {
+    if (boot.B <= 0) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t NT = taxa.size(), G = devs.size(), B = (size_t)boot.B;
+    { std::vector<char> has(NT, 0); for (int32_t t : taxon) has[(size_t)t] = 1; for (size_t t = 0; t < NT; ++t) if (has[t]) boot_pres.push_back((int32_t)t); }
+    const size_t NP = boot_pres.size();
+    boot_f.assign(B * NP, 0.0);
+    const int MAX_ITER = 10000;
+    std::atomic<long long> at_cap{0}; std::atomic<int> it_min{INT_MAX}, it_max{0};
+    on_each(G, [&](size_t d) {
+      const size_t lo = B * d / G, hi = B * (d + 1) / G;
+      if (hi <= lo) return;
+      mm_ctx* ctx = devs[d].ctx;
+      mm_em* em; ck(ctx, mm_em_create(ctx, (int64_t)NRD, off.data(), taxon.data(), mapq.data(), inv.data(), (int32_t)NT, &em), "bootstrap");
+      uint64_t tot = 0, fr = 0;
+      ck(ctx, mm_ctx_device_info(ctx, nullptr, 0, nullptr, &tot, &fr), "device info");
+      // per replicate on the device: posteriors (8 B per mapping), frequencies and sums (8 B per taxon, ~3x), a little per read block; half of
+      // the free memory (the logical devices of one GPU share it); on the host the call's f_out (8 B per taxon) within 1 GiB
+      const double per_rep = 8.0 * ((double)taxon.size() + 3.0 * (double)NT + (double)NRD / 64.0) + 1024.0;
+      const size_t by_dev = (size_t)std::max(1.0, (double)fr / (2.0 * G) / per_rep), by_host = std::max<size_t>(1, ((size_t)1 << 30) / (8 * std::max<size_t>(NT, 1)));
+      const size_t tile = std::max<size_t>(1, std::min({hi - lo, by_dev, by_host}));
+      std::vector<double> fo(tile * NT), llo(tile); std::vector<int32_t> nit(tile), stp(tile);
+      for (size_t r0 = lo; r0 < hi; r0 += tile) {
+        const size_t n = std::min(tile, hi - r0);
+        ck(ctx, mm_em_bootstrap(em, f.data(), (int32_t)r0, (int32_t)n, boot.seed, nullptr, MAX_ITER, fo.data(), llo.data(), nit.data(), stp.data()), "bootstrap");
+        for (size_t k = 0; k < n; ++k) {
+          for (size_t j = 0; j < NP; ++j) boot_f[(r0 + k) * NP + j] = fo[k * NT + (size_t)boot_pres[j]];
+          if (!stp[k]) ++at_cap;
+          int v = it_min.load(); while (nit[k] < v && !it_min.compare_exchange_weak(v, nit[k])) {}
+          v = it_max.load(); while (nit[k] > v && !it_max.compare_exchange_weak(v, nit[k])) {}
+        }
+      }
+      mm_em_destroy(em);
+    });
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::cout << "Bootstrap: " << B << " replicates, seed " << boot.seed << ", " << it_min.load() << "-" << it_max.load() << " EM iterations per replicate, "
+              << secs << " s on " << G << " device(s)" << std::endl;
+    if (at_cap) std::cerr << "Warning: " << at_cap.load() << " of " << B << " bootstrap replicates reached " << MAX_ITER << " EM iterations without meeting the stop rule." << std::endl;
+  }
+  // PREFIX.EM.WIMP.bootstrap: the WIMP's rows without the -3 count rows, its EMFrequency text, and over the replicates (each through cleanF with
+  // the point estimate's best-mapping tallies, then the WIMP's upward sums and per-level normalisation) mean, SD (B - 1), 2.5 % and 97.5 %
+  // quantiles (linear between order statistics)
+  void write_bootstrap(const std::string& fn, const Taxonomy& T, const std::map<std::string, double>& fmap, const std::map<std::string, size_t>& readsPer) {
+    const size_t B = (size_t)boot.B, NP = boot_pres.size();
+    UpMemo memo;
+    const std::map<std::string, WimpLevel> W0 = wimp_em_frequencies(T, fmap, readsPer, &memo);
+    struct Row { const std::string* L; std::string t; double em; std::vector<double> v; };
+    std::vector<Row> rows;
+    for (auto& lv : W0) {
+      double emUnm = 0;
+      for (auto& t : lv.second.keys) { if (t != "Undefined") rows.push_back(Row{&lv.first, t, lv.second.emF.at(t), {}}); else emUnm += lv.second.emF.at(t); }
+      rows.push_back(Row{&lv.first, "0", emUnm, {}});
+    }
+    for (auto& R : rows) R.v.reserve(B);
+    const double minF = 0.9 * (1.0 / (double)st.at("ReadsMapped"));
+    for (size_t b = 0; b < B; ++b) {
+      std::map<std::string, double> fm;                            // cleanF (fEM.h:1135-1163) of the replicate (taxa without a mapping: 0, dropped)
+      for (size_t j = 0; j < NP; ++j) { const std::string& id = taxa[(size_t)boot_pres[j]]; const double v = boot_f[b * NP + j]; if (!(v < minF) || readsPer.count(id)) fm[id] = v; }
+      double s = 0; for (auto& e : fm) s += e.second; for (auto& e : fm) e.second /= s;
+      const std::map<std::string, WimpLevel> Wb = wimp_em_frequencies(T, fm, readsPer, &memo);
+      for (auto& R : rows) {
+        auto lv = Wb.find(*R.L);
+        double v = 0;
+        if (lv != Wb.end()) {
+          if (R.t == "0") { auto u = lv->second.emF.find("Undefined"); if (u != lv->second.emF.end()) v = u->second; }
+          else { auto e = lv->second.emF.find(R.t); if (e != lv->second.emF.end()) v = e->second; }
+        }
+        R.v.push_back(v);
+      }
+    }
+    std::ofstream o(fn);
+    o << "AnalysisLevel\ttaxonID\tName\tEMFrequency\tBootstrapMean\tBootstrapSD\tLower95\tUpper95\n";
+    auto quantile = [](const std::vector<double>& x, double q) {   // numpy's default (linear)
+      const double h = q * (double)(x.size() - 1); const size_t k = (size_t)std::floor(h);
+      return k + 1 < x.size() ? x[k] + (h - (double)k) * (x[k + 1] - x[k]) : x[k];
+    };
+    char num[128];
+    for (auto& R : rows) {
+      double mean = 0; for (double v : R.v) mean += v; mean /= (double)B;
+      double ss = 0; for (double v : R.v) ss += (v - mean) * (v - mean);
+      std::vector<double> x = R.v; std::sort(x.begin(), x.end());
+      snprintf(num, sizeof num, "\t%.6g\t%.6g\t%.6g\t%.6g\n", mean, std::sqrt(ss / (double)(B - 1)), quantile(x, 0.025), quantile(x, 0.975));
+      o << *R.L << "\t" << R.t << "\t" << (R.t == "0" ? std::string("Unclassified") : T.T.at(R.t).sci) << "\t" << R.em << num;
+    }
+  }
   void write_outputs() {
     Taxonomy& T = *tax;
     std::cout << "Outputting mappings with adjusted alignment qualities." << std::endl;
@@ -1936,6 +2070,7 @@ struct ClassifyRun {
     pc.lap("c5 output files");
     write_wimp(mapped + ".EM.WIMP", T, fmap, readsPer, nTotal, nUnmapped, nTooShort);
     pc.lap("c6 WIMP");
+    if (boot.B > 0) { write_bootstrap(mapped + ".EM.WIMP.bootstrap", T, fmap, readsPer); pc.lap("c6b WIMP bootstrap"); }
     side_files.join();
     if (!unknown_written)
       std::cerr << "Warning: " << db << "/contigNstats_windowSize_1000.txt not found - " << mapped << ".EM.evidenceUnknownSpecies is not written." << std::endl;
@@ -1974,15 +2109,18 @@ struct ClassifyRun {
     pc.lap("c3 per-mapping fields");
     em();
     pc.lap("c4 EM");
+    bootstrap();
+    pc.lap("c4b EM bootstrap");
     write_outputs();
     return 0;
   }
 };
 
 int classify_one(const std::vector<Dev>& devs, EmReduce reduce, const std::string& mapped, const std::string& db, size_t minReadsU,
-                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept) {
+                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept, BootOpts boot) {
   ClassifyRun run(devs, reduce, mapped, db, minReadsU, leave_now, need_devices);
   run.kept = kept;
+  run.boot = boot;
   return run.run();
 }
 
@@ -1997,6 +2135,8 @@ int main(int argc, char** argv) {
   const std::string mode = argv[1];
   if (mm::env_strict()) { const std::string bad = mm::env_unknown(); if (!bad.empty()) die("unknown MM_* environment switch(es): " + bad + " (MM_STRICT_ENV is set; see INTEGRATION.md)"); }
   Options o = parse(argc, argv);
+  const BootOpts boot = boot_options(o);                          // (validated before any work)
+  if (boot.B && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--bootstrap needs classify or mapDirectly --then-classify");
   if (mode == "mapDirectly" || mode == "index" || mode == "mapAgainstIndex") return map_mode(o, mode);
   if (mode == "classify") {
     if (!o.v.count("DB")) die("Provide path to DB.");
@@ -2025,8 +2165,8 @@ int main(int argc, char** argv) {
     const size_t minReadsU = o.v.count("minreads") ? std::stoull(o.v.at("minreads")) : 10000;   // parseCmdArgs.hpp:462-471
     const std::vector<std::string> files = split(o.v.at("mappings"), ",");
     for (size_t fi = 0; fi < files.size(); ++fi) {
-      if (fi + 1 == files.size()) classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, [&] { since("mappings file done"); }, need_devices);
-      else classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, nullptr, need_devices);
+      if (fi + 1 == files.size()) classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, [&] { since("mappings file done"); }, need_devices, nullptr, boot);
+      else classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, nullptr, need_devices, nullptr, boot);
       need_devices();
       for (auto& d : devs) mm_comm_destroy(d.ctx);
       since("mappings file done");

@@ -856,6 +856,11 @@ int mm_em_posteriors(mm_em* em, const double* f, double* post, int64_t* best) {
   if (!em || !f) return MM_ERR_ARG;
   return guarded(em->ctx, [&] { MM_HIP(hipSetDevice(em->ctx->device)); mm::em_posteriors(em, f, post, best); });
 }
+int mm_em_bootstrap(mm_em* em, const double* f_start, int32_t rep0, int32_t n_rep, uint64_t seed, const uint8_t* weights,
+                    int max_iter, double* f_out, double* ll_out, int32_t* n_iter, int32_t* stopped) {
+  if (!em || !f_start || n_rep <= 0 || rep0 < 0 || (int64_t)rep0 + n_rep - 1 > INT32_MAX || max_iter <= 0 || !f_out || !ll_out || !n_iter || !stopped) return MM_ERR_ARG;
+  return guarded(em->ctx, [&] { MM_HIP(hipSetDevice(em->ctx->device)); mm::boot_run(em, f_start, rep0, n_rep, seed, weights, max_iter, f_out, ll_out, n_iter, stopped); });
+}
 
 // ---- communicator -------------------------------------------------------------------------------------
 int mm_comm_unique_id(char id[MM_COMM_ID_BYTES]) {

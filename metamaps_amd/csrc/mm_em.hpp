@@ -22,6 +22,8 @@ struct mm_em {
   mm::DBuf<int64_t> pos; mm::DBuf<double> post_sorted;   // pos[i]: place of entry i in taxon-sorted order (inverse of perm); the loop keeps its posteriors there
   mm::DBuf<double> local_partial, ll_trace, f_run;   // f_run: the loop's own frequencies (mm_em_iterate / mm_em_posteriors in between do not disturb mm_em_continue)
   mm::DBuf<long long> ctrl;
+  // the bootstrap (mm_em_bootstrap, mm_boot.hip): index of every read among the reads with at least one mapping (-1: none), their number
+  mm::DBuf<int32_t> mread; int64_t n_mapped = -1;
 };
 
 namespace mm {
@@ -31,7 +33,10 @@ void em_create_from_mapping(mm_ctx* ctx, const ::mm_mapping* M, const int32_t* c
                             int32_t n_taxa, mm_em* E);
 void em_iterate(mm_em* E, const double* f, double* f_partial, double* ll_partial);
 void em_iterate_allreduce(mm_em* E, const double* f, double* f_next, double* ll);
+void em_prepare(mm_em* E);
 int em_run(mm_em* E, const double* f0, int max_iter, double* f_out, double* ll_trace, int ll_cap, bool* stopped);
+int boot_run(mm_em* E, const double* f_start, int32_t rep0, int32_t n_rep, uint64_t seed, const uint8_t* weights, int max_iter,
+             double* f_out, double* ll_out, int32_t* n_iter, int32_t* stopped);
 void em_posteriors(mm_em* E, const double* f, double* post, int64_t* best);
 void comm_unique_id(char* id);
 void comm_init(mm_ctx* ctx, const char* id, int rank, int nranks);

@@ -548,6 +548,43 @@ static int em_grid(int64_t n_reads, int64_t n_entries) {         // (fixed per p
   return (int)std::max<int64_t>(1, std::min<int64_t>(cap, ceil_div(std::max<int64_t>(n_reads, 1), 256)));
 }
 
+// The set-up both device-resident loops share (em_run, and the bootstrap's boot_run in mm_boot.hip), built on the first call on E: the taxa
+// with mappings on this rank, the items of the per-taxon sums, the grid, pos[] and eread[]
+void em_prepare(mm_em* E) {
+  if (E->n_present >= 0) return;
+  hipStream_t st = E->ctx->stream;
+  const int32_t T = E->n_taxa;
+  const int cap = 1024;
+  std::vector<int64_t> ts = E->tstart.to_host(st, (size_t)T + 1);
+  std::vector<int32_t> pr, pti(1, 0);
+  std::vector<int64_t> ilo, ihi;
+  for (int32_t t = 0; t < T; ++t) {
+    if (ts[(size_t)t + 1] == ts[(size_t)t]) continue;
+    pr.push_back(t);
+    for (int64_t j = ts[(size_t)t]; j < ts[(size_t)t + 1]; j += EM_ITEM) { ilo.push_back(j); ihi.push_back(std::min(j + EM_ITEM, ts[(size_t)t + 1])); }
+    MM_REQUIRE(ilo.size() < (size_t)INT32_MAX, MM_ERR_LIMIT, "EM problem beyond 2^31 sum items");
+    pti.push_back((int32_t)ilo.size());
+  }
+  E->n_present = (int32_t)pr.size(); E->n_items = (int32_t)ilo.size();
+  E->n_wg = em_grid(E->n_reads, E->n_entries);
+  E->present.alloc(std::max<size_t>(pr.size(), 1)); E->present.upload(pr.data(), pr.size(), st);
+  E->pt_item.alloc(pti.size()); E->pt_item.upload(pti.data(), pti.size(), st);
+  E->item_lo.alloc(std::max<size_t>(ilo.size(), 1)); E->item_lo.upload(ilo.data(), ilo.size(), st);
+  E->item_hi.alloc(std::max<size_t>(ihi.size(), 1)); E->item_hi.upload(ihi.data(), ihi.size(), st);
+  E->item_sum.alloc(std::max<size_t>(ilo.size(), 1));
+  E->pos.alloc((size_t)std::max<int64_t>(E->n_entries, 1)); E->post_sorted.alloc((size_t)std::max<int64_t>(E->n_entries, 1));
+  MM_REQUIRE(E->n_reads < (1LL << 31), MM_ERR_LIMIT, "EM problem beyond 2^31 reads");
+  E->eread.alloc((size_t)std::max<int64_t>(E->n_entries, 1));
+  if (E->n_reads > 0) { em_eread_kernel<<<dim3((unsigned)ceil_div(E->n_reads, 256)), dim3(256), 0, st>>>(E->read_off.p, E->n_reads, E->eread.p); MM_KERNEL_CHECK(); }
+  if (E->n_entries > 0) { em_pos_kernel<<<dim3((unsigned)ceil_div(E->n_entries, 256)), dim3(256), 0, st>>>(E->perm.p, E->n_entries, E->pos.p); MM_KERNEL_CHECK(); }
+  E->wg_ll.alloc((size_t)E->n_wg);
+  E->local_partial.alloc((size_t)T + 1);
+  E->ll_trace.alloc((size_t)cap);
+  E->f_run.alloc((size_t)T);
+  E->ctrl.alloc(4);
+  MM_HIP(mm::stream_sync(st));
+}
+
 // f0 == nullptr continues the loop where the previous call on E left it (same f, iteration count and previous log-likelihood):
 // mm_em_continue.  Returns the iterations done by this call; *stopped = the stop rule has fired.
 int em_run(mm_em* E, const double* f0, int max_iter, double* f_out, double* ll_trace, int ll_cap, bool* stopped) {
@@ -557,34 +594,7 @@ int em_run(mm_em* E, const double* f0, int max_iter, double* f_out, double* ll_t
   const int cap = 1024;
   if (E->n_present < 0) {                                        // first run: taxa with mappings on this rank, the items of the per-taxon sums
     MM_REQUIRE(f0 != nullptr, MM_ERR_STATE, "mm_em_continue before mm_em_run");
-    std::vector<int64_t> ts = E->tstart.to_host(st, (size_t)T + 1);
-    std::vector<int32_t> pr, pti(1, 0);
-    std::vector<int64_t> ilo, ihi;
-    for (int32_t t = 0; t < T; ++t) {
-      if (ts[(size_t)t + 1] == ts[(size_t)t]) continue;
-      pr.push_back(t);
-      for (int64_t j = ts[(size_t)t]; j < ts[(size_t)t + 1]; j += EM_ITEM) { ilo.push_back(j); ihi.push_back(std::min(j + EM_ITEM, ts[(size_t)t + 1])); }
-      MM_REQUIRE(ilo.size() < (size_t)INT32_MAX, MM_ERR_LIMIT, "EM problem beyond 2^31 sum items");
-      pti.push_back((int32_t)ilo.size());
-    }
-    E->n_present = (int32_t)pr.size(); E->n_items = (int32_t)ilo.size();
-    E->n_wg = em_grid(E->n_reads, E->n_entries);
-    E->present.alloc(std::max<size_t>(pr.size(), 1)); E->present.upload(pr.data(), pr.size(), st);
-    E->pt_item.alloc(pti.size()); E->pt_item.upload(pti.data(), pti.size(), st);
-    E->item_lo.alloc(std::max<size_t>(ilo.size(), 1)); E->item_lo.upload(ilo.data(), ilo.size(), st);
-    E->item_hi.alloc(std::max<size_t>(ihi.size(), 1)); E->item_hi.upload(ihi.data(), ihi.size(), st);
-    E->item_sum.alloc(std::max<size_t>(ilo.size(), 1));
-    E->pos.alloc((size_t)std::max<int64_t>(E->n_entries, 1)); E->post_sorted.alloc((size_t)std::max<int64_t>(E->n_entries, 1));
-    MM_REQUIRE(E->n_reads < (1LL << 31), MM_ERR_LIMIT, "EM problem beyond 2^31 reads");
-    E->eread.alloc((size_t)std::max<int64_t>(E->n_entries, 1));
-    if (E->n_reads > 0) { em_eread_kernel<<<dim3((unsigned)ceil_div(E->n_reads, 256)), dim3(256), 0, st>>>(E->read_off.p, E->n_reads, E->eread.p); MM_KERNEL_CHECK(); }
-    if (E->n_entries > 0) { em_pos_kernel<<<dim3((unsigned)ceil_div(E->n_entries, 256)), dim3(256), 0, st>>>(E->perm.p, E->n_entries, E->pos.p); MM_KERNEL_CHECK(); }
-    E->wg_ll.alloc((size_t)E->n_wg);
-    E->local_partial.alloc((size_t)T + 1);
-    E->ll_trace.alloc((size_t)cap);
-    E->f_run.alloc((size_t)T);
-    E->ctrl.alloc(4);
-    MM_HIP(mm::stream_sync(st));
+    em_prepare(E);
   }
   long long h_ctrl[4] = {0, 0, 0, 0};
   if (f0) {
