@@ -28,7 +28,7 @@ extern "C" {
 #define MM_ABI_VERSION 6   /* 3: mm_seqset_slice/concat, mm_map_batch_reusing, mm_em_continue, mm_synth_community_species;
                             * 4: mm_sketch_batch, mm_ctx_release_cached, mm_index_dup_neighbours;
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
-                            * 6: mm_index_save, mm_index_load; mm_em_bootstrap (an addition to 6) */
+                            * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_* (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -39,7 +39,7 @@ typedef enum {
   MM_ERR_LIMIT = -5,      /* documented capacity limit exceeded       */
   MM_ERR_NUMERIC = -6,    /* reference would abort here (e.g. likelihood sum 0, mapWrap.h:298) */
   MM_ERR_COMM = -7,       /* RCCL error                                           */
-  MM_ERR_DATA = -8        /* input data is corrupt (mm_bgzf_inflate: a block's status says which) */
+  MM_ERR_DATA = -8        /* input data is corrupt (mm_bgzf_inflate: a block's status says which; mm_gzip_feed: the message names the offset) */
 } mm_status;
 
 typedef struct mm_ctx mm_ctx;          /* a device + streams + scratch allocator                  */
@@ -47,6 +47,7 @@ typedef struct mm_seqset mm_seqset;    /* sequences resident in HBM as packed 2-
 typedef struct mm_index mm_index;      /* reference sketch of one index chunk, resident in HBM     */
 typedef struct mm_mapping mm_mapping;  /* mapping results of one read batch, resident in HBM      */
 typedef struct mm_em mm_em;            /* EM state (mappings x taxa) resident in HBM              */
+typedef struct mm_gzip mm_gzip;        /* a plain gzip stream being inflated on a context's device */
 
 /* ---- context -------------------------------------------------------------------------------- */
 int mm_abi_version(void);
@@ -90,6 +91,27 @@ int mm_seqset_add_nt16(mm_seqset* s, const uint8_t* nt16, int64_t n_bases, int r
  * arguments (a block outside `comp`, or a readable ISIZE that does not fit `out` at its offset), MM_ERR_DATA if any block is bad. */
 int mm_bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const int64_t* comp_off, const int32_t* comp_len, int32_t n,
                     uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status);
+/* Plain gzip (RFC 1952: any number of members, each one DEFLATE stream without a block index) inflated on the context's device, from host
+ * memory into host memory, a segment at a time ("Plain gzip on the device").  The compressed stream is cut into chunks of
+ * chunk_bytes (0: MM_GZIP_CHUNK_BYTES, else 256 KiB) and each chunk decoded speculatively from a block start it finds, then checked against its
+ * predecessor; segment_bytes (0: 128 MiB, at most 1 GiB) is how much compressed input one round takes.  Device memory of a stream: the round's
+ * chunk slots, kept within 4.5 GiB (a small chunk_bytes shortens the round instead), two segments of input and a round's output.
+ *   mm_gzip_open   a stream on ctx (ctx outlives it; the one-thread-per-context rule holds for the stream's calls too)
+ *   mm_gzip_feed   the next n compressed bytes (all are taken; last != 0: they end the file).  *avail (may be NULL): inflated bytes ready to
+ *                  read.  Output is produced once a segment's worth of input is buffered, and at the end.  Header fields (FEXTRA, FNAME,
+ *                  FCOMMENT, FHCRC) are parsed, concatenated members read through, each member's CRC32 and ISIZE checked, and bytes behind a
+ *                  member that do not start a gzip header are ignored (as zlib's gzread ignores them).  MM_ERR_DATA for a corrupt or
+ *                  truncated stream: mm_last_error names the compressed byte offset, and every later feed fails the same way.
+ *   mm_gzip_read   up to cap inflated bytes into out, *got of them
+ *   mm_gzip_stats  counts[5]: chunks, chunks whose speculation was accepted, chunks decoded again from their predecessor's end, chunks covered
+ *                  by their predecessor's decode (no block starts in them), members; seconds[4]: speculative kernel, sequential walk (with the
+ *                  decodes again), resolve + CRC, all of feed.  Either pointer may be NULL.
+ *   mm_gzip_close  frees the stream */
+int mm_gzip_open(mm_ctx* ctx, int64_t chunk_bytes, int64_t segment_bytes, mm_gzip** out);
+int mm_gzip_feed(mm_gzip* g, const uint8_t* comp, int64_t n, int last, int64_t* avail);
+int mm_gzip_read(mm_gzip* g, uint8_t* out, int64_t cap, int64_t* got);
+int mm_gzip_stats(const mm_gzip* g, int64_t* counts, double* seconds);
+void mm_gzip_close(mm_gzip* g);
 int mm_seqset_upload(mm_seqset* s);                                /* pack + copy to HBM; set is then frozen.  Packs into the CONTEXT's pinned
                                                                     * staging buffer: two uploads of sets of one context must not overlap (the one-thread-
                                                                     * per-context rule above applies to this entry point too) */

@@ -112,6 +112,11 @@ def lib() -> C.CDLL:
             "mm_seqset_add_view": (C.c_int, [vp, C.c_char_p, i64]),
             "mm_seqset_add_nt16": (C.c_int, [vp, C.c_char_p, i64, C.c_int]),
             "mm_bgzf_inflate": (C.c_int, [vp, C.c_char_p, i64, vp, vp, C.c_int32, vp, i64, vp, vp]),
+            "mm_gzip_open": (C.c_int, [vp, i64, i64, P(vp)]),
+            "mm_gzip_feed": (C.c_int, [vp, C.c_char_p, i64, C.c_int, P(i64)]),
+            "mm_gzip_read": (C.c_int, [vp, vp, i64, P(i64)]),
+            "mm_gzip_stats": (C.c_int, [vp, P(i64), P(f64)]),
+            "mm_gzip_close": (None, [vp]),
             "mm_seqset_save": (C.c_int, [vp, C.c_char_p]),
             "mm_seqset_load": (C.c_int, [vp, C.c_char_p, P(vp)]),
             "mm_seqset_upload": (C.c_int, [vp]),
@@ -277,6 +282,37 @@ class Context:
         if st not in (0, MM_ERR_DATA):
             self.check(st)
         return out, status
+
+    def gzip_inflate(self, comp, chunk_bytes: int = 0, segment_bytes: int = 0, pieces=None):
+        """A plain gzip stream (bytes) inflated on the device (mm_gzip_open / feed / read).  `pieces`: the byte counts it is fed in (the
+        rest goes in the last feed).  Returns (inflated bytes, stats): stats has chunks, accepted, redone, skipped, members and the seconds
+        spec, chain, resolve, total.  Corrupt data raises MMError(MM_ERR_DATA) whose message names the compressed byte offset."""
+        comp = bytes(comp)
+        h = C.c_void_p()
+        self.check(lib().mm_gzip_open(self.h, chunk_bytes, segment_bytes, C.byref(h)))
+        out = bytearray()
+        try:
+            cuts = list(pieces or [])
+            at, avail = 0, C.c_int64()
+            while True:
+                n = min(cuts.pop(0), len(comp) - at) if cuts else len(comp) - at
+                last = at + n >= len(comp)
+                self.check(lib().mm_gzip_feed(h, comp[at:at + n], n, 1 if last else 0, C.byref(avail)))
+                at += n
+                if avail.value:
+                    buf = bytearray(avail.value)
+                    got = C.c_int64()
+                    self.check(lib().mm_gzip_read(h, (C.c_uint8 * len(buf)).from_buffer(buf), len(buf), C.byref(got)))
+                    out += buf[:got.value]
+                if last:
+                    break
+            counts, secs = (C.c_int64 * 5)(), (C.c_double * 4)()
+            self.check(lib().mm_gzip_stats(h, counts, secs))
+        finally:
+            lib().mm_gzip_close(h)
+        stats = dict(zip(("chunks", "accepted", "redone", "skipped", "members"), list(counts)))
+        stats.update(zip(("spec_s", "chain_s", "resolve_s", "total_s"), list(secs)))
+        return bytes(out), stats
 
     def load_seqset(self, path: str) -> "SeqSet":
         h = C.c_void_p()

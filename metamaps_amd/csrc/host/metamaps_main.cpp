@@ -31,7 +31,9 @@
 // files its `samtools fastq -n` conversion gives: secondary and supplementary records skipped, 0x10 records turned back to the read as
 // sequenced, qualities, tags and paired-end flags ignored.  Its 4-bit codes are packed on the device (mm_seqset_add_nt16).  The BGZF blocks
 // of FASTA/FASTQ written by bgzip (and of a BAM with MM_BAM_DEVICE_INFLATE=1) are inflated on the device a segment at a time
-// (mm_bgzf_inflate); the host walks the block headers, cuts the records and parses the text.  Plain gzip keeps zlib's sequential reader.  The reference (-r) stays FASTA/FASTQ(.gz).
+// (mm_bgzf_inflate); the host walks the block headers, cuts the records and parses the text.  Plain gzip FASTA/FASTQ — queries and the reference
+// (-r DB.fa.gz) — is inflated on the device too, by speculative decoding of chunks of the one DEFLATE stream (mm_gzip_*); the
+// parse is the zlib reader's.  MM_GZIP_HOST_INFLATE=1 keeps zlib's sequential reader.  The reference (-r) stays FASTA/FASTQ(.gz).
 //
 // Not provided: classifyU (disabled upstream).
 
@@ -97,6 +99,46 @@ struct PhaseClock {
 // An error exit leaves through _exit: helper threads (the HIP runtime coming up beside the parse of `classify`, the worker contexts' prewarm, the
 // readers) may be inside the driver at this moment, and exit() would run static destructors and the runtime's atexit handlers under them.
 [[noreturn]] void die(const std::string& m) { std::cerr << m << std::endl; std::cout.flush(); fflush(nullptr); _exit(1); }
+
+// a plain gzip file (starts with 1f 8b, not BGZF): what the device gzip reader takes unless MM_GZIP_HOST_INFLATE is set
+bool is_plain_gzip_file(const std::string& path) {
+  const int fd = ::open(path.c_str(), O_RDONLY);
+  if (fd < 0) return false;
+  uint8_t b[2] = {0, 0};
+  const ssize_t n = pread(fd, b, 2, 0);
+  ::close(fd);
+  return n == 2 && b[0] == 0x1f && b[1] == 0x8b && !bam::is_bgzf_file(path);
+}
+
+// A plain gzip file inflated on the device (mm_gzip_*, DESIGN.md §1 "Plain gzip on the device"), read in 64 MiB pieces: the `fill` source of
+// a SeqFile, so the record parse is the zlib reader's byte for byte.  Corrupt data ends the program with the offset mm_last_error names.
+struct DeviceGzip {
+  mm_ctx* ctx; std::string path; FILE* f = nullptr; mm_gzip* g = nullptr;
+  std::vector<uint8_t> piece; int64_t avail = 0; bool fed_last = false;
+  DeviceGzip(mm_ctx* c, const std::string& p) : ctx(c), path(p), piece((size_t)64 << 20) {
+    f = fopen(p.c_str(), "rb");
+    if (!f) die("Cannot open " + p);
+    if (mm_gzip_open(ctx, 0, 0, &g) != MM_OK) die(std::string("cannot open a device gzip stream: ") + mm_last_error(ctx));
+  }
+  ~DeviceGzip() { if (g) mm_gzip_close(g); if (f) fclose(f); }
+  DeviceGzip(const DeviceGzip&) = delete;
+  size_t fill(std::vector<unsigned char>& buf) {
+    while (avail == 0 && !fed_last) {
+      const size_t n = fread(piece.data(), 1, piece.size(), f);
+      if (ferror(f)) die("Error reading " + path);
+      fed_last = n < piece.size() && feof(f);
+      const int rc = mm_gzip_feed(g, piece.data(), (int64_t)n, fed_last ? 1 : 0, &avail);
+      if (rc == MM_ERR_DATA) die("Error reading " + path + ": " + mm_last_error(ctx));
+      if (rc != MM_OK) die(std::string("device gzip inflate failed: ") + mm_last_error(ctx));
+    }
+    if (avail == 0) return 0;
+    buf.resize((size_t)std::min<int64_t>(avail, (int64_t)64 << 20));
+    int64_t got = 0;
+    if (mm_gzip_read(g, buf.data(), (int64_t)buf.size(), &got) != MM_OK) die(std::string("device gzip read failed: ") + mm_last_error(ctx));
+    avail -= got;
+    return (size_t)got;
+  }
+};
 // a helper thread that is joined on every way out of its scope (an exception that passes a joinable std::thread ends in std::terminate)
 struct JoinOnExit { std::thread& t; ~JoinOnExit() { if (t.joinable()) t.join(); } };
 void ck(mm_ctx* ctx, int st, const char* what) { if (st != MM_OK) die(std::string(what) + ": " + mm_last_error(ctx)); }
@@ -540,6 +582,7 @@ struct MapRun {
     // on 16 CPUs the kernel (1.7 GB/s on BAM) is slower than zlib on 8 threads, though it takes a third of the host CPU.
     const bool host_inflate = getenv("MM_BGZF_HOST_INFLATE") != nullptr;
     const bool bam_device = !host_inflate && getenv("MM_BAM_DEVICE_INFLATE") != nullptr;
+    const bool gzip_host = getenv("MM_GZIP_HOST_INFLATE") != nullptr;   // plain gzip through zlib's sequential reader instead of mm_gzip_*
     mm_ctx* zctx = nullptr;
     struct ZctxGuard { mm_ctx*& c; ~ZctxGuard() { if (c) mm_ctx_destroy(c); } } zguard{zctx};
     std::vector<int64_t> z_coff, z_ooff; std::vector<int32_t> z_clen, z_st;
@@ -591,6 +634,19 @@ struct MapRun {
           parse_into(f, (size_t)-1, [&](std::unique_ptr<Batch> b) { enqueue(std::move(b), fi); });
         } catch (const bam::Error& e) { die(std::string("Error reading ") + queries[fi] + ": " + e.what()); }
         pc.add("R bgzip reader (inflate + parse, without waiting for a queue slot)", std::chrono::duration<double>(std::chrono::steady_clock::now() - z_t0).count());
+        std::lock_guard<std::mutex> lk(reader.m); reader.file_end.push_back(seq); reader.cv.notify_all();
+        continue;
+      }
+      if (!gzip_host && is_plain_gzip_file(queries[fi])) {       // plain gzip FASTA/FASTQ: the sequential record parse over device-inflated segments
+        const auto g_t0 = std::chrono::steady_clock::now();
+        if (!zctx && mm_ctx_create(devs[0].phys, &zctx) != MM_OK) die("cannot create the reader's inflate context");
+        {
+          DeviceGzip z(zctx, queries[fi]);
+          SeqFile f([&](std::vector<unsigned char>& buf) -> size_t { return z.fill(buf); });
+          parse_into(f, (size_t)-1, [&](std::unique_ptr<Batch> b) { enqueue(std::move(b), fi); });
+        }
+        (void)mm_ctx_release_cached(zctx);                       // (the stream's slots, up to 4.5 GiB, back to the driver beside the mapping)
+        pc.add("R gzip reader (device inflate + parse, without waiting for a queue slot)", std::chrono::duration<double>(std::chrono::steady_clock::now() - g_t0).count());
         std::lock_guard<std::mutex> lk(reader.m); reader.file_end.push_back(seq); reader.cv.notify_all();
         continue;
       }
@@ -790,7 +846,24 @@ struct MapRun {
     } else {
       // gzip, pipes: a parser thread fills groups, the main thread packs and uploads each while the next one is parsed.  Host memory: two groups.
       std::mutex gm; std::condition_variable gcv; std::deque<std::unique_ptr<Group>> ready; bool parsed = false;
+      double t_gzip = -1;                                        // the device gzip reader's wall time (its phase line), -1 if zlib read the file
       std::thread parser([&]() {
+        if (!getenv("MM_GZIP_HOST_INFLATE") && is_plain_gzip_file(ref)) {   // plain gzip: inflated on the device, on a context of the parser's own
+          const auto g_t0 = std::chrono::steady_clock::now();
+          mm_ctx* gctx = nullptr;
+          if (mm_ctx_create(devs[0].phys, &gctx) != MM_OK) die("cannot create the reference reader's inflate context");
+          {
+            DeviceGzip z(gctx, ref);
+            SeqFile f([&](std::vector<unsigned char>& buf) -> size_t { return z.fill(buf); });
+            parse_groups(f, (size_t)-1, [&](std::unique_ptr<Group> g) {
+              std::unique_lock<std::mutex> lk(gm); gcv.wait(lk, [&] { return ready.size() < 2; }); ready.push_back(std::move(g)); gcv.notify_all();
+            });
+          }
+          mm_ctx_destroy(gctx);
+          std::lock_guard<std::mutex> lk(gm); parsed = true; gcv.notify_all();
+          t_gzip = std::chrono::duration<double>(std::chrono::steady_clock::now() - g_t0).count();
+          return;
+        }
         SeqFile f(ref);
         parse_groups(f, (size_t)-1, [&](std::unique_ptr<Group> g) {
           std::unique_lock<std::mutex> lk(gm); gcv.wait(lk, [&] { return ready.size() < 2; }); ready.push_back(std::move(g)); gcv.notify_all();
@@ -803,6 +876,7 @@ struct MapRun {
         consume(*g);
       }
       parser.join();
+      if (t_gzip >= 0) pc.add("1g reference gzip reader (device inflate + parse, inside 1)", t_gzip);
     }
     on_each(parts.size(), [&](size_t d) {
       if (parts[d].size() == 1) { refset[d] = parts[d][0]; return; }

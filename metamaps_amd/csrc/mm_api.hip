@@ -16,6 +16,12 @@ void seqset_upload(mm_seqset* s);
 void seqset_upload_nt16(mm_seqset* s);
 int64_t bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const int64_t* comp_off, const int32_t* comp_len, int32_t n,
                      uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status);
+mm_gzip* gzip_open(mm_ctx* ctx, int64_t chunk, int64_t segment);
+void gzip_close(mm_gzip* g);
+int gzip_feed(mm_gzip* g, const uint8_t* comp, int64_t n, bool last, int64_t* avail);
+int64_t gzip_read(mm_gzip* g, uint8_t* out, int64_t cap);
+void gzip_stats(const mm_gzip* g, int64_t* counts, double* seconds);
+mm_ctx* gzip_ctx(const mm_gzip* g);
 void seqset_save(mm_seqset* s, const char* path);
 void seqset_load(mm_seqset* s, const char* path);
 void seqset_fetch(mm_seqset* s, int64_t i, char* out, int64_t cap);
@@ -181,6 +187,33 @@ int mm_bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const 
   if (rc != MM_OK) return rc;
   if (bad) { ctx->err = "mm_bgzf_inflate: " + std::to_string(bad) + " corrupt BGZF block(s)"; return MM_ERR_DATA; }
   return MM_OK;
+}
+int mm_gzip_open(mm_ctx* ctx, int64_t chunk_bytes, int64_t segment_bytes, mm_gzip** out) {
+  if (!ctx || !out || chunk_bytes < 0 || segment_bytes < 0) return MM_ERR_ARG;
+  *out = nullptr;
+  return guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); *out = mm::gzip_open(ctx, chunk_bytes, segment_bytes); });
+}
+int mm_gzip_feed(mm_gzip* g, const uint8_t* comp, int64_t n, int last, int64_t* avail) {
+  if (!g || n < 0 || (n > 0 && !comp)) return MM_ERR_ARG;
+  int bad = 0;
+  const int rc = guarded(mm::gzip_ctx(g), [&] { MM_HIP(hipSetDevice(mm::gzip_ctx(g)->device)); bad = mm::gzip_feed(g, comp, n, last != 0, avail); });
+  if (rc != MM_OK) return rc;
+  return bad ? MM_ERR_DATA : MM_OK;
+}
+int mm_gzip_read(mm_gzip* g, uint8_t* out, int64_t cap, int64_t* got) {
+  if (!g || cap < 0 || (cap > 0 && !out) || !got) return MM_ERR_ARG;
+  *got = mm::gzip_read(g, out, cap);
+  return MM_OK;
+}
+int mm_gzip_stats(const mm_gzip* g, int64_t* counts, double* seconds) {
+  if (!g) return MM_ERR_ARG;
+  mm::gzip_stats(g, counts, seconds);
+  return MM_OK;
+}
+void mm_gzip_close(mm_gzip* g) {
+  if (!g) return;
+  mm_ctx* ctx = mm::gzip_ctx(g);
+  (void)guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); mm::gzip_close(g); });
 }
 int mm_seqset_upload(mm_seqset* s) {
   if (!s) return MM_ERR_ARG;

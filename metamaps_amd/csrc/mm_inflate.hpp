@@ -185,6 +185,8 @@ struct Bits {
   MMI_HD uint32_t take(uint32_t n) { const uint32_t v = peek(n); drop(n); return v; }
   MMI_HD bool overrun() const { return (uint64_t)pos * 8 - cnt > (uint64_t)len * 8; }
   MMI_HD void align() { drop(cnt & 7); }
+  MMI_HD uint64_t bitpos() const { return (uint64_t)pos * 8 - cnt; }   // the next bit to be taken
+  MMI_HD void seek(uint64_t bit) { pos = (uint32_t)(bit >> 3); buf = 0; cnt = 0; fill(); drop((uint32_t)(bit & 7)); }   // (forward only on the device)
 };
 
 // one symbol of h (needs >= 15 bits in the buffer); -1 for a code that is not in the set
@@ -210,8 +212,8 @@ struct Scratch {
   uint16_t rank[320];
 };
 
-template <class P>
-MMI_HD void copy_match(P& p, uint8_t* out, uint32_t at, uint32_t dist, uint32_t len) {
+template <class P, class T>
+MMI_HD void copy_match(P& p, T* out, uint32_t at, uint32_t dist, uint32_t len) {
   const uint32_t src = at - dist;
   if (dist >= len) { for (uint32_t i = p.lane(); i < len; i += P::W) out[at + i] = out[src + i]; }
   else for (uint32_t i = p.lane(); i < len; i += P::W) out[at + i] = out[src + i % dist];   // overlapping: the period repeats
@@ -220,6 +222,54 @@ MMI_HD void copy_match(P& p, uint8_t* out, uint32_t at, uint32_t dist, uint32_t 
 
 MMI_HD uint16_t rd16(const uint8_t* q) { return (uint16_t)(q[0] | (q[1] << 8)); }
 MMI_HD uint32_t rd32(const uint8_t* q) { return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24); }
+
+// The Huffman tables of a fixed (type 1) or dynamic (type 2) block whose three header bits `b` has just taken: S.lit and S.dist, the dynamic
+// header's code lengths read from `b`.  BAD_STREAM for anything RFC 1951 or zlib rejects.  (inflate_raw here and the plain gzip decoder of
+// mm_gzip.hpp share it.)
+template <class P>
+MMI_HD int32_t read_tables(P& p, Scratch& S, const Consts& K, Bits<P>& b, uint32_t type) {
+  int nlit = 288, ndist = 32;                                  // (fixed codes: the distance code has 32 symbols, 30 and 31 invalid, as in zlib)
+  if (type == 1) {
+    for (int s = (int)p.lane(); s < 320; s += P::W) S.lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5);
+    p.sync();
+  } else {                                                     // dynamic: the code-length code first (built into S.dist)
+    nlit = (int)b.take(5) + 257; ndist = (int)b.take(5) + 1;
+    const int ncl = (int)b.take(4) + 4;
+    if (nlit > 286 || ndist > 30) return BAD_STREAM;
+    for (int k = (int)p.lane(); k < 19; k += P::W) S.lens[k] = 0;
+    p.sync();
+    for (int i = 0; i < ncl; ++i) {
+      if (b.cnt < 3) b.fill();
+      const uint8_t v = (uint8_t)b.take(3);
+      if (p.lane() == 0) S.lens[K.clord[i]] = v;
+    }
+    p.sync();
+    if (b.overrun() || !build_huff(p, S.dist, S.lens, 19, false, S.rank)) return BAD_STREAM;
+    const int total = nlit + ndist;
+    int i = 0;
+    uint8_t prev = 0;
+    while (i < total) {
+      b.fill();
+      if (b.overrun()) return BAD_STREAM;
+      const int sym = decode_sym(b, S.dist);
+      if (sym < 0) return BAD_STREAM;
+      if (sym < 16) { if (p.lane() == 0) S.lens[i] = (uint8_t)sym; prev = (uint8_t)sym; ++i; continue; }
+      uint32_t rep; uint8_t v;
+      if (sym == 16) { if (i == 0) return BAD_STREAM; v = prev; rep = 3 + b.take(2); }
+      else if (sym == 17) { v = 0; rep = 3 + b.take(3); }
+      else { v = 0; rep = 11 + b.take(7); }
+      if (i + (int)rep > total) return BAD_STREAM;
+      for (uint32_t k = p.lane(); k < rep; k += P::W) S.lens[i + k] = v;
+      i += (int)rep; prev = v;
+    }
+    if (b.overrun()) return BAD_STREAM;
+    p.sync();
+    if (S.lens[256] == 0) return BAD_STREAM;                   // no end-of-block code
+  }
+  if (!build_huff(p, S.lit, S.lens, nlit, true, S.rank)) return BAD_STREAM;
+  if (!build_huff(p, S.dist, S.lens + nlit, ndist, true, S.rank)) return BAD_STREAM;
+  return OK;
+}
 
 // The deflate stream in[0, n) into out[0, isize): BAD_STREAM for anything RFC 1951 or zlib rejects (and for output beyond isize), BAD_LENGTH
 // if the stream ends before isize bytes.  Trailing bytes behind the final block are ignored, as zlib's inflate(Z_FINISH) ignores them.
@@ -245,46 +295,8 @@ MMI_HD int32_t inflate_raw(P& p, Scratch& S, const Consts& K, const uint8_t* in,
       continue;
     }
     if (type == 3) return BAD_STREAM;
-    int nlit = 288, ndist = 32;                                  // (fixed codes: the distance code has 32 symbols, 30 and 31 invalid, as in zlib)
-    if (type == 1) {
-      for (int s = (int)p.lane(); s < 320; s += P::W) S.lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : s < 288 ? 8 : 5);
-      p.sync();
-    } else {                                                     // dynamic: the code-length code first (built into S.dist)
-      nlit = (int)b.take(5) + 257; ndist = (int)b.take(5) + 1;
-      const int ncl = (int)b.take(4) + 4;
-      if (nlit > 286 || ndist > 30) return BAD_STREAM;
-      for (int k = (int)p.lane(); k < 19; k += P::W) S.lens[k] = 0;
-      p.sync();
-      for (int i = 0; i < ncl; ++i) {
-        if (b.cnt < 3) b.fill();
-        const uint8_t v = (uint8_t)b.take(3);
-        if (p.lane() == 0) S.lens[K.clord[i]] = v;
-      }
-      p.sync();
-      if (b.overrun() || !build_huff(p, S.dist, S.lens, 19, false, S.rank)) return BAD_STREAM;
-      const int total = nlit + ndist;
-      int i = 0;
-      uint8_t prev = 0;
-      while (i < total) {
-        b.fill();
-        if (b.overrun()) return BAD_STREAM;
-        const int sym = decode_sym(b, S.dist);
-        if (sym < 0) return BAD_STREAM;
-        if (sym < 16) { if (p.lane() == 0) S.lens[i] = (uint8_t)sym; prev = (uint8_t)sym; ++i; continue; }
-        uint32_t rep; uint8_t v;
-        if (sym == 16) { if (i == 0) return BAD_STREAM; v = prev; rep = 3 + b.take(2); }
-        else if (sym == 17) { v = 0; rep = 3 + b.take(3); }
-        else { v = 0; rep = 11 + b.take(7); }
-        if (i + (int)rep > total) return BAD_STREAM;
-        for (uint32_t k = p.lane(); k < rep; k += P::W) S.lens[i + k] = v;
-        i += (int)rep; prev = v;
-      }
-      if (b.overrun()) return BAD_STREAM;
-      p.sync();
-      if (S.lens[256] == 0) return BAD_STREAM;                   // no end-of-block code
-    }
-    if (!build_huff(p, S.lit, S.lens, nlit, true, S.rank)) return BAD_STREAM;
-    if (!build_huff(p, S.dist, S.lens + nlit, ndist, true, S.rank)) return BAD_STREAM;
+    const int32_t ts = read_tables(p, S, K, b, type);
+    if (ts != OK) return ts;
     for (;;) {
       b.fill();
       if (b.overrun()) return BAD_STREAM;
