@@ -91,6 +91,15 @@ int mm_seqset_add_nt16(mm_seqset* s, const uint8_t* nt16, int64_t n_bases, int r
  * arguments (a block outside `comp`, or a readable ISIZE that does not fit `out` at its offset), MM_ERR_DATA if any block is bad. */
 int mm_bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const int64_t* comp_off, const int32_t* comp_len, int32_t n,
                     uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status);
+/* Deflate in_bytes bytes of host memory into BGZF on the context's device: the input is cut into blocks of 65 280 bytes and each becomes one
+ * complete BGZF member (header with the BC subfield and BSIZE, one DEFLATE block with dynamic Huffman codes — stored where that would not be
+ * smaller —, CRC32, ISIZE; LZ77 over a 32 KiB window inside the block).  The members go back to back into out[0, *out_bytes); *n_blocks is
+ * their number.  The bytes are a function of the input alone (not of the device, the grid or the call that carries a block).  in_bytes == 0
+ * gives zero blocks and *out_bytes == 0.  The 28-byte BGZF end-of-file block is NOT appended: the caller writes it once when it closes the
+ * file.  MM_ERR_ARG for a null pointer or an out_cap below mm_bgzf_deflate_bound(in_bytes).  With MM_DEFLATE_HOST=1 in the environment the
+ * same container is written by zlib level 1 on the host's threads (other bytes, the same inflated text). */
+int64_t mm_bgzf_deflate_bound(int64_t in_bytes);   /* bytes `out` must hold for any input of that size */
+int mm_bgzf_deflate(mm_ctx* ctx, const uint8_t* in, int64_t in_bytes, uint8_t* out, int64_t out_cap, int64_t* out_bytes, int32_t* n_blocks);
 /* Plain gzip (RFC 1952: any number of members, each one DEFLATE stream without a block index) inflated on the context's device, from host
  * memory into host memory, a segment at a time ("Plain gzip on the device").  The compressed stream is cut into chunks of
  * chunk_bytes (0: MM_GZIP_CHUNK_BYTES, else 256 KiB) and each chunk decoded speculatively from a block start it finds, then checked against its

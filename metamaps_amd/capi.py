@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmetamaps_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "metamaps_hip.h")
 
 COMM_ID_BYTES = 128
+MM_ERR_ARG = -1
 MM_ERR_DATA = -8
 
 
@@ -112,6 +113,8 @@ def lib() -> C.CDLL:
             "mm_seqset_add_view": (C.c_int, [vp, C.c_char_p, i64]),
             "mm_seqset_add_nt16": (C.c_int, [vp, C.c_char_p, i64, C.c_int]),
             "mm_bgzf_inflate": (C.c_int, [vp, C.c_char_p, i64, vp, vp, C.c_int32, vp, i64, vp, vp]),
+            "mm_bgzf_deflate_bound": (i64, [i64]),
+            "mm_bgzf_deflate": (C.c_int, [vp, C.c_char_p, i64, vp, i64, P(i64), P(C.c_int32)]),
             "mm_gzip_open": (C.c_int, [vp, i64, i64, P(vp)]),
             "mm_gzip_feed": (C.c_int, [vp, C.c_char_p, i64, C.c_int, P(i64)]),
             "mm_gzip_read": (C.c_int, [vp, vp, i64, P(i64)]),
@@ -282,6 +285,17 @@ class Context:
         if st not in (0, MM_ERR_DATA):
             self.check(st)
         return out, status
+
+    def bgzf_deflate(self, data, out_cap=None):
+        """data (bytes) deflated into BGZF members of 65 280 input bytes each on the device (mm_bgzf_deflate).  Returns (members back to
+        back as bytes, number of members); the BGZF end-of-file block is not part of it.  out_cap: the capacity passed instead of
+        mm_bgzf_deflate_bound(len(data))."""
+        data = bytes(data)
+        cap = lib().mm_bgzf_deflate_bound(len(data)) if out_cap is None else out_cap
+        out = bytearray(max(cap, 1))
+        nbytes, nblocks = C.c_int64(-1), C.c_int32(-1)
+        self.check(lib().mm_bgzf_deflate(self.h, data, len(data), (C.c_uint8 * len(out)).from_buffer(out), cap, C.byref(nbytes), C.byref(nblocks)))
+        return bytes(out[:nbytes.value]), nblocks.value
 
     def gzip_inflate(self, comp, chunk_bytes: int = 0, segment_bytes: int = 0, pieces=None):
         """A plain gzip stream (bytes) inflated on the device (mm_gzip_open / feed / read).  `pieces`: the byte counts it is fed in (the

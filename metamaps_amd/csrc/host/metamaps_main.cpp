@@ -5,7 +5,7 @@
 // exclusively through the C ABI in include/metamaps_hip.h.  Host work here is what stays host work in the
 // reference too: argument parsing, FASTA/FASTQ(.gz) reading, text formatting, taxonomy bookkeeping.
 //
-//   metamaps mapDirectly [--all] -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
+//   metamaps mapDirectly [--all] [--compress-output] -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
 //   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]]
 //
@@ -34,6 +34,14 @@
 // (mm_bgzf_inflate); the host walks the block headers, cuts the records and parses the text.  Plain gzip FASTA/FASTQ — queries and the reference
 // (-r DB.fa.gz) — is inflated on the device too, by speculative decoding of chunks of the one DEFLATE stream (mm_gzip_*); the
 // parse is the zlib reader's.  MM_GZIP_HOST_INFLATE=1 keeps zlib's sequential reader.  The reference (-r) stays FASTA/FASTQ(.gz).
+//
+// --compress-output (mapDirectly, mapAgainstIndex; not in the reference): the mappings go to PREFIX.gz as BGZF, ending in BGZF's end-of-file
+// block, and no plain PREFIX is written (one left by an earlier run is removed); .meta, .meta.unmappedReadsLengths and .parameters are as ever.
+// The text of a batch is deflated on the device by the context that mapped it (mm_bgzf_deflate; MM_DEFLATE_HOST=1: zlib level 1 on the host)
+// and the writer concatenates the batches' members.  `classify --mappings PREFIX` takes PREFIX if it exists (inflated if it starts with a
+// BGZF block) and PREFIX.gz otherwise: the block headers are walked on the host, the blocks inflated on the device (mm_bgzf_inflate) into
+// the buffer the tokeniser works on; any bgzip'd mappings file is accepted.  A corrupt or truncated file ends the run with the compressed
+// offset of the bad block.  A plain gzip mappings file (no BGZF blocks) is refused with a message that says so.
 //
 // Not provided: classifyU (disabled upstream).
 
@@ -154,7 +162,7 @@ Options parse(int argc, char** argv) {
     if (a == "--stream-chunks") { o.stream = true; continue; }
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
-    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index") { o.v[a.substr(2)] = "1"; continue; }
+    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") { std::cout << "see the header of metamaps_main.cpp / the reference's README\n"; exit(0); }
     std::string key = alias.count(a) ? alias.at(a) : (a.rfind("--", 0) == 0 ? a.substr(2) : "");
     if (key.empty() || i + 1 >= argc) die("Unknown or incomplete option " + a);
@@ -422,9 +430,11 @@ struct MapRun {
   mm_map_params mp{};
   std::vector<int32_t> chunk_base;
   // what a worker hands to the writer: the finished text of one batch
-  struct Done { size_t file = 0; std::vector<std::string> names; std::vector<int> lens; std::vector<int64_t> off; std::string text; std::vector<LineMeta> meta; double t_mapq = 0, t_fetch = 0, t_format = 0; };
+  struct Done { size_t file = 0; std::vector<std::string> names; std::vector<int> lens; std::vector<int64_t> off; std::string text; std::string gz /* --compress-output: the text as BGZF members */; std::vector<LineMeta> meta; double t_mapq = 0, t_fetch = 0, t_format = 0; };
   // --then-classify: the batches of every query file as they were written, in order (text + the parsed fields of every line): what classify takes instead of the file
   const bool keep_lines = o.v.count("then-classify") && !getenv("MM_CLI_CLASSIFY_FROM_FILE");
+  // --compress-output: the mappings go to PREFIX.gz as BGZF; a batch's text is deflated by the context that mapped it, right behind its formatting
+  const bool compress = o.v.count("compress-output") != 0;
   std::vector<std::vector<std::unique_ptr<Done>>> kept;
   // the writer: batches in input order -> PREFIX, .meta.unmappedReadsLengths, .meta, .parameters of every query file (mapWrap.h:34-213)
   struct Writer {
@@ -1117,6 +1127,7 @@ struct MapRun {
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
     format_records(dn->names, dn->lens, dn->off, rec, cname, clen, k, dn->text, keep_lines ? &dn->meta : nullptr);
+    if (compress) deflate_text(ctx, *dn);
     const auto f3 = std::chrono::steady_clock::now();
     pc.add("7a mapping qualities + offsets", std::chrono::duration<double>(f1 - f0).count());
     pc.add("7b fetch records", std::chrono::duration<double>(f2 - f1).count());
@@ -1124,12 +1135,25 @@ struct MapRun {
     dn->t_mapq = std::chrono::duration<double>(f1 - f0).count(); dn->t_fetch = std::chrono::duration<double>(f2 - f1).count(); dn->t_format = std::chrono::duration<double>(f3 - f2).count();
     return dn;
   }
+  // the text of a batch as BGZF members (mm_bgzf_deflate: blocks of 65 280 bytes, each a member of its own, so the batches' members
+  // concatenate in output order); the text itself is kept only where --then-classify takes its lines from memory
+  void deflate_text(mm_ctx* ctx, Done& dn) {
+    const auto z0 = std::chrono::steady_clock::now();
+    dn.gz.resize((size_t)mm_bgzf_deflate_bound((int64_t)dn.text.size()));
+    int64_t nbytes = 0; int32_t nblocks = 0;
+    ck(ctx, mm_bgzf_deflate(ctx, (const uint8_t*)dn.text.data(), (int64_t)dn.text.size(), (uint8_t*)&dn.gz[0], (int64_t)dn.gz.size(), &nbytes, &nblocks), "deflate the mappings");
+    dn.gz.resize((size_t)nbytes);
+    if (!keep_lines) std::string().swap(dn.text);
+    pc.add("7d deflate", std::chrono::duration<double>(std::chrono::steady_clock::now() - z0).count());
+  }
   void write_all(const std::function<std::unique_ptr<Done>(size_t, size_t)>& next /* (file, seq): batch `seq` if it belongs to that file, nullptr once the file has ended */) {
     size_t seq = 0;
     for (size_t fi = 0; fi < queries.size(); ++fi) {
       const std::string& prefix = prefixes[fi];
-      std::ofstream out(prefix), unm(prefix + ".meta.unmappedReadsLengths");
-      if (!out.is_open()) die("Cannot open output file " + prefix);
+      if (compress) ::unlink(prefix.c_str());                    // (classify prefers a plain PREFIX: one left from an earlier run must not shadow PREFIX.gz)
+      const std::string out_name = compress ? prefix + ".gz" : prefix;
+      std::ofstream out(out_name, std::ios::binary), unm(prefix + ".meta.unmappedReadsLengths");
+      if (!out.is_open()) die("Cannot open output file " + out_name);
       size_t total = 0, tooShort = 0, mapped = 0, notMapped = 0; IdSet seen;   // (id_set.hpp: a std::set of 10^6 IDs bounded the mapping phase)
       for (;;) {
         std::unique_ptr<Done> d = next(fi, seq);
@@ -1146,10 +1170,14 @@ struct MapRun {
           if (!seen.insert(d->names[r])) die("Seems that read ID " + d->names[r] + " has already been processed");
           ++mapped;
         }
-        out << d->text;
+        if (compress) out.write(d->gz.data(), (std::streamsize)d->gz.size()); else out << d->text;
+        std::string().swap(d->gz);
         if (keep_lines) { if (kept.size() <= fi) kept.resize(fi + 1); d->names.clear(); d->names.shrink_to_fit(); kept[fi].push_back(std::move(d)); }
       }
       if (keep_lines && kept.size() <= fi) kept.resize(fi + 1);
+      if (compress) { static const unsigned char eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0}; out.write((const char*)eof, 28); }
+      out.close();
+      if (!out) die("Error writing " + out_name);
       std::ofstream meta(prefix + ".meta");                      // mapWrap.h:178-184
       meta << "TotalReads " << total << "\nReadsTooShort " << tooShort << "\nReadsMapped " << mapped << "\nReadsNotMapped " << notMapped << "\n";
       std::ofstream ps(prefix + ".parameters");                  // mapWrap.h:196-211
@@ -1799,9 +1827,52 @@ struct ClassifyRun {
   // fEM.h:1171-1214, :234-373), lines of one read are consecutive (mapWrap.h:128-149), contig IDs are interned.
   // Round 4: read and tokenised by several threads — pieces of the file that begin on a read boundary are parsed on their own and joined in
   // file order (read offsets shifted, contig IDs interned in the order a single pass would meet them): 4.2 M lines took 1.3 s on one thread.
+  // A BGZF mappings file (mapDirectly --compress-output, or any bgzip'd mappings file): the block headers are walked here, the blocks
+  // inflated on the device a segment of 1 024 at a time (mm_bgzf_inflate), straight into the buffer tokenise() works on.
+  void read_bgzf(const std::string& src) {
+    const int fd = ::open(src.c_str(), O_RDONLY);
+    struct stat stt;
+    if (fd < 0 || fstat(fd, &stt) != 0) die("Cannot open mappings file " + src);
+    const size_t FS = (size_t)stt.st_size;
+    const uint8_t* const F = (const uint8_t*)mmap(nullptr, FS, PROT_READ, MAP_PRIVATE, fd, 0);
+    ::close(fd);
+    if (F == MAP_FAILED) die("Cannot map mappings file " + src);
+    const std::string err = "Error reading mappings file " + src + ": ";
+    std::vector<int64_t> coff, ooff; std::vector<int32_t> clen;
+    size_t total = 0;
+    for (size_t at = 0; at < FS;) {
+      const size_t bs = bam::bgzf_block_size(F + at, FS - at);
+      if (!bs && FS - at >= 18) die(err + "bad magic: no BGZF block at byte " + std::to_string(at));
+      if (bs < 26 || at + bs > FS) die(err + "truncated BGZF block at byte " + std::to_string(at));
+      const size_t isize = bam::rd32(F + at + bs - 4);
+      if (isize > 65536) die(err + "corrupt BGZF block at byte " + std::to_string(at) + " (ISIZE " + std::to_string(isize) + ")");
+      coff.push_back((int64_t)at); clen.push_back((int32_t)bs); ooff.push_back((int64_t)total);
+      total += isize; at += bs;
+    }
+    if (coff.empty() || clen.back() != 28 || bam::rd32(F + FS - 4) != 0) std::cerr << "Warning: " << src << " does not end in the BGZF end-of-file block; it is probably truncated" << std::endl;
+    text.resize(total);
+    if (need_devices) need_devices();
+    mm_ctx* const ctx = devs[0].ctx;
+    const size_t SEG = 1024;
+    std::vector<int64_t> rc_off(SEG), ro_off(SEG); std::vector<int32_t> st(SEG);
+    for (size_t b0 = 0; b0 < coff.size(); b0 += SEG) {
+      const size_t n = std::min(SEG, coff.size() - b0), last = b0 + n - 1;
+      for (size_t i = 0; i < n; ++i) { rc_off[i] = coff[b0 + i] - coff[b0]; ro_off[i] = ooff[b0 + i] - ooff[b0]; }
+      const int64_t comp = coff[last] + clen[last] - coff[b0], out = (last + 1 < ooff.size() ? ooff[last + 1] : (int64_t)total) - ooff[b0];
+      const int rc = mm_bgzf_inflate(ctx, F + coff[b0], comp, rc_off.data(), clen.data() + b0, (int32_t)n, (uint8_t*)text.p + ooff[b0], out, ro_off.data(), st.data());
+      if (rc == MM_ERR_DATA) for (size_t i = 0; i < n; ++i) if (st[i] != 0) die(err + bam::bgzf_status_message(st[i], (size_t)coff[b0 + i]));
+      if (rc != MM_OK) die(std::string("device inflate of the mappings file failed: ") + mm_last_error(ctx));
+    }
+    munmap((void*)F, FS);
+  }
+  // `mapped` if it exists (plain text, or BGZF by content), else `mapped`.gz
   void read_file() {
+    struct stat probe;
+    const std::string src = stat(mapped.c_str(), &probe) == 0 ? mapped : stat((mapped + ".gz").c_str(), &probe) == 0 ? mapped + ".gz" : mapped;
+    if (bam::is_bgzf_file(src)) { read_bgzf(src); return; }
+    if (is_plain_gzip_file(src)) die("Mappings file " + src + " is plain gzip without BGZF blocks: recompress it with bgzip, or decompress it");
     {
-      const int fd = ::open(mapped.c_str(), O_RDONLY);
+      const int fd = ::open(src.c_str(), O_RDONLY);
       if (fd < 0) die("Cannot open mappings file " + mapped);
       struct stat stt; if (fstat(fd, &stt) != 0) die("Cannot open mappings file " + mapped);
       text.resize((size_t)stt.st_size);
@@ -2211,6 +2282,7 @@ int main(int argc, char** argv) {
   Options o = parse(argc, argv);
   const BootOpts boot = boot_options(o);                          // (validated before any work)
   if (boot.B && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--bootstrap needs classify or mapDirectly --then-classify");
+  if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
   if (mode == "mapDirectly" || mode == "index" || mode == "mapAgainstIndex") return map_mode(o, mode);
   if (mode == "classify") {
     if (!o.v.count("DB")) die("Provide path to DB.");

@@ -16,6 +16,8 @@ void seqset_upload(mm_seqset* s);
 void seqset_upload_nt16(mm_seqset* s);
 int64_t bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const int64_t* comp_off, const int32_t* comp_len, int32_t n,
                      uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status);
+void bgzf_deflate(mm_ctx* ctx, const uint8_t* in, int64_t in_bytes, uint8_t* out, int64_t out_cap, int64_t* out_bytes, int32_t* n_blocks);
+int64_t bgzf_deflate_bound(int64_t in_bytes);
 mm_gzip* gzip_open(mm_ctx* ctx, int64_t chunk, int64_t segment);
 void gzip_close(mm_gzip* g);
 int gzip_feed(mm_gzip* g, const uint8_t* comp, int64_t n, bool last, int64_t* avail);
@@ -187,6 +189,11 @@ int mm_bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const 
   if (rc != MM_OK) return rc;
   if (bad) { ctx->err = "mm_bgzf_inflate: " + std::to_string(bad) + " corrupt BGZF block(s)"; return MM_ERR_DATA; }
   return MM_OK;
+}
+int64_t mm_bgzf_deflate_bound(int64_t in_bytes) { return in_bytes < 0 ? 0 : mm::bgzf_deflate_bound(in_bytes); }
+int mm_bgzf_deflate(mm_ctx* ctx, const uint8_t* in, int64_t in_bytes, uint8_t* out, int64_t out_cap, int64_t* out_bytes, int32_t* n_blocks) {
+  if (!ctx || !out_bytes || !n_blocks || in_bytes < 0 || (in_bytes > 0 && (!in || !out))) return MM_ERR_ARG;
+  return guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); mm::bgzf_deflate(ctx, in, in_bytes, out, out_cap, out_bytes, n_blocks); });
 }
 int mm_gzip_open(mm_ctx* ctx, int64_t chunk_bytes, int64_t segment_bytes, mm_gzip** out) {
   if (!ctx || !out || chunk_bytes < 0 || segment_bytes < 0) return MM_ERR_ARG;

@@ -39,6 +39,7 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_CLI_NO_MMAP", "unset", "test", "plain query and reference files through the sequential reader instead of the memory-mapped block parser (what pipes and, with MM_GZIP_HOST_INFLATE, plain gzip take)"},
     {"MM_GZIP_HOST_INFLATE", "unset", "test", "plain gzip query and reference files inflated by zlib's sequential reader on the host, never on the device (cross-check of mm_gzip_*)"},
     {"MM_GZIP_CHUNK_BYTES", "262144", "test", "compressed bytes per speculatively decoded chunk of a plain gzip stream (mm_gzip_open with chunk_bytes 0): small values make small files run through many chunks"},
+    {"MM_DEFLATE_HOST", "unset", "test", "mm_bgzf_deflate (the mappings file of --compress-output) writes its BGZF members with zlib level 1 on the host's threads instead of the device kernel: the A/B partner and a fallback; other bytes, the same text"},
     {"MM_CLI_NO_PREWARM", "unset", "test", "worker contexts come up with their first batch instead of beside the index build"},
     {"MM_SF_GRID", "the device's CU count", "debug", "resident workgroups of the streaming seed filter (measurement aid: how K3 scales with the CUs at work)"},
     {"MM_CLI_LATE_READER", "unset", "debug", "the query reader starts when the index is built instead of beside the build (measurement aid)"},
