@@ -243,6 +243,50 @@ static void build_directory(mm_index* I, hipStream_t st) {
   MM_HIP(mm::stream_sync(st));                              // `off` is the upload source
 }
 
+// how far the flagged entries' same-hash neighbours are (mm_index.hpp); key_out: the sorted hashes
+static void index_dup_distances(mm_index* I, const uint32_t* key_out, int64_t N, unsigned nblk, hipStream_t st) {
+  const int64_t nb64 = (N + 63) >> 6;
+  if (const char* e = getenv("MM_DUP_SAT")) I->dup_sat = std::min(std::max(atoi(e), 1), 65535);
+  I->dup_bits.alloc((size_t)nb64); I->dup_rank.alloc((size_t)nb64 + 1);
+  DBuf<uint32_t> bcnt((size_t)nb64);
+  DBuf<uint64_t> scan_tmp4;
+  dup_bits_kernel<<<dim3((unsigned)std::min<int64_t>(ceil_div(nb64, 4), 1 << 20)), dim3(256), 0, st>>>(I->pos.p, N, I->dup_bits.p, bcnt.p);
+  MM_KERNEL_CHECK();
+  exclusive_scan_u32_u64(bcnt.p, nb64, I->dup_rank.p, scan_tmp4, st);
+  uint64_t nflag = 0;
+  MM_HIP(hipMemcpyAsync(&nflag, I->dup_rank.p + nb64, sizeof nflag, hipMemcpyDeviceToHost, st));
+  MM_HIP(mm::stream_sync(st));
+  I->dup_dist.alloc(std::max<size_t>((size_t)nflag, 1)); I->dup_dist.zero(st);
+  if (nflag) {
+    dup_pairs_kernel<true><<<dim3(nblk), dim3(256), 0, st>>>(key_out, I->occ.p, N, I->cstart.p, I->dir.p, I->dir_off.p, I->dir_shift, I->pos.p, nullptr,
+                                                             I->dup_bits.p, I->dup_rank.p, (uint16_t*)I->dup_dist.p, I->dup_sat);
+    MM_KERNEL_CHECK();
+  }
+}
+
+// sector-aligned occurrence lists (see padded_counts_kernel): occ[] is replaced by its padded form, occ16[] gets the bin codes
+static void index_pad_lists(mm_index* I, uint64_t U, DBuf<uint64_t>& pstart, hipStream_t st) {
+  DBuf<uint32_t> pc((size_t)U + 1); pc.zero(st);
+  padded_counts_kernel<<<dim3((unsigned)std::min<int64_t>(ceil_div((int64_t)U, 256), 1 << 20)), dim3(256), 0, st>>>(I->ustart.p, (int64_t)U, pc.p);
+  MM_KERNEL_CHECK();
+  DBuf<uint64_t> scan_tmp3;
+  exclusive_scan_u32_u64(pc.p, (int64_t)U, pstart.p, scan_tmp3, st);
+  uint64_t P = 0;
+  MM_HIP(hipMemcpyAsync(&P, pstart.p + U, sizeof P, hipMemcpyDeviceToHost, st));
+  MM_HIP(mm::stream_sync(st));
+  MM_REQUIRE(P < ((uint64_t)1 << 35), MM_ERR_LIMIT, "more than 2^35 padded occurrences in one index chunk (the seed filter keeps list starts / 8 in 32 bits)");
+  DBuf<uint64_t> padded((size_t)P + 2);
+  I->occ16.alloc((size_t)P + 16);
+  std::vector<uint64_t> h_cbase((size_t)I->n_contigs + 1, 0);
+  for (int64_t c = 0; c < I->n_contigs; ++c) h_cbase[(size_t)c + 1] = h_cbase[(size_t)c] + (uint64_t)I->contig_len[(size_t)c];
+  DBuf<uint64_t> d_cbase(h_cbase.size()); d_cbase.upload(h_cbase.data(), h_cbase.size(), st);
+  pad_lists_kernel<<<dim3((unsigned)std::min<int64_t>(ceil_div((int64_t)U * 8, 256), 1 << 20)), dim3(256), 0, st>>>(I->occ.p, I->ustart.p, pstart.p, (int64_t)U, d_cbase.p,
+                                                                                                             padded.p, I->occ16.p);
+  MM_KERNEL_CHECK();
+  MM_HIP(mm::stream_sync(st));
+  I->occ = std::move(padded);
+}
+
 void index_build(mm_ctx* ctx, const mm_seqset* contigs, int k, int w, mm_index* I) {
   hipStream_t st = ctx->stream;
   struct BuildClock {                                            // MM_HOST_TIMING=1: wall time of the build's sections (stderr; each lap drains the stream)
@@ -386,25 +430,7 @@ void index_build(mm_ctx* ctx, const mm_seqset* contigs, int k, int w, mm_index* 
   dup_pairs_kernel<false><<<dim3(nblk), dim3(256), 0, st>>>(key_out.p, I->occ.p, N, I->cstart.p, I->dir.p, I->dir_off.p, I->dir_shift, I->pos.p, ndup.p,
                                                             nullptr, nullptr, nullptr, 0);
   MM_KERNEL_CHECK();
-  {                                                              // ... and how far the flagged entries' same-hash neighbours are (mm_index.hpp)
-    const int64_t nb64 = (N + 63) >> 6;
-    if (const char* e = getenv("MM_DUP_SAT")) I->dup_sat = std::min(std::max(atoi(e), 1), 65535);
-    I->dup_bits.alloc((size_t)nb64); I->dup_rank.alloc((size_t)nb64 + 1);
-    DBuf<uint32_t> bcnt((size_t)nb64);
-    DBuf<uint64_t> scan_tmp4;
-    dup_bits_kernel<<<dim3((unsigned)std::min<int64_t>(ceil_div(nb64, 4), 1 << 20)), dim3(256), 0, st>>>(I->pos.p, N, I->dup_bits.p, bcnt.p);
-    MM_KERNEL_CHECK();
-    exclusive_scan_u32_u64(bcnt.p, nb64, I->dup_rank.p, scan_tmp4, st);
-    uint64_t nflag = 0;
-    MM_HIP(hipMemcpyAsync(&nflag, I->dup_rank.p + nb64, sizeof nflag, hipMemcpyDeviceToHost, st));
-    MM_HIP(mm::stream_sync(st));
-    I->dup_dist.alloc(std::max<size_t>((size_t)nflag, 1)); I->dup_dist.zero(st);
-    if (nflag) {
-      dup_pairs_kernel<true><<<dim3(nblk), dim3(256), 0, st>>>(key_out.p, I->occ.p, N, I->cstart.p, I->dir.p, I->dir_off.p, I->dir_shift, I->pos.p, nullptr,
-                                                               I->dup_bits.p, I->dup_rank.p, (uint16_t*)I->dup_dist.p, I->dup_sat);
-      MM_KERNEL_CHECK();
-    }
-  }
+  index_dup_distances(I, key_out.p, N, nblk, st);
   clk.lap("duplicate flags");
   // occurrence histogram (winSketch.hpp:456-459)
   const int64_t big_cap = 1 << 20;
@@ -423,27 +449,7 @@ void index_build(mm_ctx* ctx, const mm_seqset* contigs, int k, int w, mm_index* 
   // sector-aligned occurrence lists (see padded_counts_kernel)
   clk.lap("occurrence histogram");
   DBuf<uint64_t> pstart((size_t)U + 1);
-  {
-    DBuf<uint32_t> pc((size_t)U + 1); pc.zero(st);
-    padded_counts_kernel<<<dim3((unsigned)std::min<int64_t>(ceil_div((int64_t)U, 256), 1 << 20)), dim3(256), 0, st>>>(I->ustart.p, (int64_t)U, pc.p);
-    MM_KERNEL_CHECK();
-    DBuf<uint64_t> scan_tmp3;
-    exclusive_scan_u32_u64(pc.p, (int64_t)U, pstart.p, scan_tmp3, st);
-    uint64_t P = 0;
-    MM_HIP(hipMemcpyAsync(&P, pstart.p + U, sizeof P, hipMemcpyDeviceToHost, st));
-    MM_HIP(mm::stream_sync(st));
-    MM_REQUIRE(P < ((uint64_t)1 << 35), MM_ERR_LIMIT, "more than 2^35 padded occurrences in one index chunk (the seed filter keeps list starts / 8 in 32 bits)");
-    DBuf<uint64_t> padded((size_t)P + 2);
-    I->occ16.alloc((size_t)P + 16);
-    std::vector<uint64_t> h_cbase((size_t)I->n_contigs + 1, 0);
-    for (int64_t c = 0; c < I->n_contigs; ++c) h_cbase[(size_t)c + 1] = h_cbase[(size_t)c] + (uint64_t)I->contig_len[(size_t)c];
-    DBuf<uint64_t> d_cbase(h_cbase.size()); d_cbase.upload(h_cbase.data(), h_cbase.size(), st);
-    pad_lists_kernel<<<dim3((unsigned)std::min<int64_t>(ceil_div((int64_t)U * 8, 256), 1 << 20)), dim3(256), 0, st>>>(I->occ.p, I->ustart.p, pstart.p, (int64_t)U, d_cbase.p,
-                                                                                                               padded.p, I->occ16.p);
-    MM_KERNEL_CHECK();
-    MM_HIP(mm::stream_sync(st));
-    I->occ = std::move(padded);
-  }
+  index_pad_lists(I, U, pstart, st);
   clk.lap("padded lists + bin codes");
   // lookup table (load factor <= 0.55, any number of 4-slot buckets), then the CSR arrays are no longer needed
   I->tab_buckets = tab_buckets_for((int64_t)U);

@@ -5,10 +5,13 @@ set -e
 cd "$(dirname "$0")/../metamaps_amd/csrc"
 name=$1; flags=$2
 out=../../_ab/$name; mkdir -p $out/_build
-for f in mm_seq mm_index mm_map mm_post mm_synth mm_api; do
-  ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-result $flags -c $f.hip -o $out/_build/$f.o ) &
+srcs=$(make -pn 2>/dev/null | sed -n 's/^SRCS := //p')         # the library's translation units: the Makefile's list, not a copy of it
+[ -n "$srcs" ] || { echo "ab_build.sh: no SRCS in the Makefile" >&2; exit 1; }
+pids=""
+for f in $srcs; do
+  ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-result $flags -c $f -o $out/_build/${f%.hip}.o ) & pids="$pids $!"
 done
-wait
+for p in $pids; do wait $p; done                                # (a plain `wait` hides a failed compile)
 g++ -O3 -std=c++17 -fPIC -c host_pack.cpp -o $out/_build/host_pack.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libmetamaps_hip.so $out/_build/*.o -L/opt/rocm/lib -lrccl -lpthread -Wl,-rpath,/opt/rocm/lib
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libmetamaps_hip.so $out/_build/*.o -L/opt/rocm/lib -lrccl -lz -lpthread -Wl,-rpath,/opt/rocm/lib
 ls -la $out/libmetamaps_hip.so

@@ -1,7 +1,18 @@
-"""Longest functions of the host program (round-4 review item 8: no function above 200 lines in metamaps_amd/csrc/host/).  A function = a brace block whose
-opening line ends in ') {' or ') const {' (or carries a trailing comment behind that) at nesting depth <= 1 (top level, or directly inside a struct / namespace)."""
+"""Longest host functions of the CLI (metamaps_amd/csrc/host/) and of the library (metamaps_amd/csrc/*.hip): none above 200 lines (round-4 review item 8,
+round-6 item 8).  A function = a brace block whose opening line ends in ') {' or ') const {' (or carries a trailing comment behind that); methods of structs count.
+Device code is left out: a function whose declaration carries __global__ or __device__, on the opening line or on the earlier lines of a multi-line signature
+(back to the previous ';', '}' or blank line).  Kernels are judged by other means."""
 import glob, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def device_decl(lines, i):
+    while True:
+        if "__global__" in lines[i] or "__device__" in lines[i]:
+            return True
+        i -= 1
+        if i < 0 or not lines[i].strip() or lines[i].split("//")[0].rstrip().endswith((";", "}")):
+            return False
 
 
 def functions(path):
@@ -11,7 +22,7 @@ def functions(path):
         code = re.sub(r'"(?:[^"\\]|\\.)*"', '""', ln)
         code = re.sub(r"'(?:[^'\\]|\\.)'", "''", code).split("//")[0]
         opens, closes = code.count("{"), code.count("}")
-        if opens > closes and re.search(r"\)\s*(const\s*)?(noexcept\s*)?(->\s*[\w:<>]+\s*)?\{\s*$", code.rstrip()) and not re.match(r"\s*(if|for|while|switch|else|do)\b", code) and "[&" not in code and "[=" not in code and "[this" not in code:
+        if opens > closes and not device_decl(lines, i) and re.search(r"\)\s*(const\s*)?(noexcept\s*)?(->\s*[\w:<>]+\s*)?\{\s*$", code.rstrip()) and not re.match(r"\s*(if|for|while|switch|else|do)\b", code) and "[&" not in code and "[=" not in code and "[this" not in code:
             stack.append((depth, i, ln.strip()[:90]))
         depth += opens - closes
         while stack and depth <= stack[-1][0]:
@@ -21,10 +32,11 @@ def functions(path):
 
 
 if __name__ == "__main__":
-    allf = []
-    for f in glob.glob(os.path.join(ROOT, "metamaps_amd", "csrc", "host", "*")):
-        allf += functions(f)
-    allf.sort(reverse=True)
+    csrc = os.path.join(ROOT, "metamaps_amd", "csrc")
+    host = [fn for f in sorted(glob.glob(os.path.join(csrc, "host", "*"))) for fn in functions(f)]
+    lib = [fn for f in sorted(glob.glob(os.path.join(csrc, "*.hip"))) for fn in functions(f)]
+    allf = sorted(host + lib, reverse=True)
     for n, f, l, name in allf[:12]:
         print(f"{n:5d}  {f}:{l}  {name}")
+    print(f"functions: {len(host)} csrc/host {len(lib)} csrc/*.hip")
     sys.exit(1 if allf and allf[0][0] > 200 else 0)
