@@ -33,11 +33,15 @@ void seqset_concat(const mm_seqset* const* parts, int n_parts, mm_seqset* o);
 }
 
 namespace {
+// a context is bound to the calling thread for the duration of a call: its device (hipSetDevice is per thread), its
+// stream and its allocator.  Several contexts — one per GPU, or several on one GPU — may be driven from different threads.
+void bind(mm_ctx* ctx) {
+  if (ctx->device >= 0 && ctx->stream) (void)hipSetDevice(ctx->device);
+  mm::current_stream() = ctx->stream; mm::current_alloc() = &ctx->alloc;
+}
 template <typename F>
 int guarded(mm_ctx* ctx, F&& f) {
-  // a context is bound to the calling thread for the duration of the call: its device (hipSetDevice is per thread), its
-  // stream and its allocator.  Several contexts — one per GPU, or several on one GPU — may be driven from different threads.
-  if (ctx) { if (ctx->device >= 0 && ctx->stream) (void)hipSetDevice(ctx->device); mm::current_stream() = ctx->stream; mm::current_alloc() = &ctx->alloc; }
+  if (ctx) bind(ctx);
   try { f(); return MM_OK; }
   catch (const mm::Error& e) { if (ctx) ctx->err = e.what(); return e.status; }
   catch (const std::bad_alloc&) { if (ctx) ctx->err = "host allocation failed"; return MM_ERR_NOMEM; }
@@ -106,6 +110,7 @@ int mm_ctx_create(int device_id, mm_ctx** out) {
 }
 void mm_ctx_destroy(mm_ctx* ctx) {
   if (!ctx) return;
+  mm::alloc_unregister(&ctx->alloc);                               // first: from here on no other context's thread trims this cache, waits for this stream or finds its event (reclaim, mm_alloc.hpp)
   (void)hipSetDevice(ctx->device);
   (void)mm::stream_sync(ctx->stream);
   ctx->alloc.trim();
@@ -113,8 +118,7 @@ void mm_ctx_destroy(mm_ctx* ctx) {
   mm::comm_destroy(ctx);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->pinned_up) (void)hipHostFree(ctx->pinned_up);
-  if (ctx->l2_codes) mm::dev_free(ctx->l2_codes, ctx->l2_codes_bytes);
-  if (ctx->l2_masks) mm::dev_free(ctx->l2_masks, ctx->l2_masks_bytes);
+  ctx->l2_codes.release(); ctx->l2_masks.release();
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   if (ctx->aux_stream) { mm::stream_event_unregister(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
@@ -131,7 +135,7 @@ int mm_ctx_device_info(mm_ctx* ctx, char* name, size_t name_cap, int* cus, uint6
     if (name && name_cap) { snprintf(name, name_cap, "%s (%s)", p.name, p.gcnArchName); }
     if (cus) *cus = p.multiProcessorCount;
     size_t f = 0, t = 0;
-    MM_HIP(mm::dev_mem_info(&f, &t));                             // (capped by the test hook MM_DEVICE_BYTES_CAP, mm_common.hpp)
+    MM_HIP(mm::dev_mem_info(&f, &t));                             // (capped by the test hook MM_DEVICE_BYTES_CAP, mm_alloc.hpp)
     if (hbm_total) *hbm_total = t;
     if (hbm_free) *hbm_free = f;
   });
@@ -151,7 +155,7 @@ int mm_seqset_create(mm_ctx* ctx, mm_seqset** out) {
   if (!ctx || !out) return MM_ERR_ARG;
   return guarded(ctx, [&] { auto* s = new mm_seqset; s->ctx = ctx; *out = s; });
 }
-void mm_seqset_destroy(mm_seqset* s) { if (s) { (void)hipSetDevice(s->ctx->device); mm::current_stream() = s->ctx->stream; mm::current_alloc() = &s->ctx->alloc; delete s; } }
+void mm_seqset_destroy(mm_seqset* s) { if (s) { bind(s->ctx); delete s; } }
 int mm_seqset_add(mm_seqset* s, const char* ascii, int64_t len) {
   if (!s || (!ascii && len > 0) || len < 0) return MM_ERR_ARG;
   return guarded(s->ctx, [&] {
@@ -352,7 +356,7 @@ int mm_index_load(mm_ctx* ctx, const char* path, mm_index** out) {
     *out = I;
   });
 }
-void mm_index_destroy(mm_index* idx) { if (idx) { (void)hipSetDevice(idx->ctx->device); mm::current_stream() = idx->ctx->stream; mm::current_alloc() = &idx->ctx->alloc; delete idx; } }
+void mm_index_destroy(mm_index* idx) { if (idx) { bind(idx->ctx); delete idx; } }
 int mm_index_get_info(const mm_index* idx, mm_index_info* out) {
   if (!idx || !out) return MM_ERR_ARG;
   out->n_contigs = idx->n_contigs; out->n_entries = idx->N; out->n_unique_hashes = idx->U; out->n_dup_flagged = idx->n_dup;
@@ -498,7 +502,7 @@ int mm_map_batch_phased(mm_ctx* ctx, const mm_index* idx, const mm_seqset* reads
     *out = M;
   });
 }
-void mm_mapping_destroy(mm_mapping* m) { if (m) { (void)hipSetDevice(m->ctx->device); mm::current_stream() = m->ctx->stream; mm::current_alloc() = &m->ctx->alloc; delete m; } }
+void mm_mapping_destroy(mm_mapping* m) { if (m) { bind(m->ctx); delete m; } }
 int mm_mapping_release_intermediates(mm_mapping* m) {
   if (!m) return MM_ERR_ARG;
   return guarded(m->ctx, [&] {
@@ -870,7 +874,7 @@ int mm_em_sizes(const mm_em* em, int64_t* n_reads, int64_t* n_entries, int32_t* 
   if (n_taxa) *n_taxa = em->n_taxa;
   return MM_OK;
 }
-void mm_em_destroy(mm_em* em) { if (em) { (void)hipSetDevice(em->ctx->device); mm::current_stream() = em->ctx->stream; mm::current_alloc() = &em->ctx->alloc; delete em; } }
+void mm_em_destroy(mm_em* em) { if (em) { bind(em->ctx); delete em; } }
 int mm_em_iterate(mm_em* em, const double* f, double* f_partial, double* ll_partial) {
   if (!em || !f || !f_partial || !ll_partial) return MM_ERR_ARG;
   return guarded(em->ctx, [&] { MM_HIP(hipSetDevice(em->ctx->device)); mm::em_iterate(em, f, f_partial, ll_partial); });

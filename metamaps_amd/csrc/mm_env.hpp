@@ -51,16 +51,12 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_EM_SLICE", "1024", "test", "EM iterations per mm_em_run / mm_em_continue call of classify"},
     {"MM_CLI_TIMING", "unset", "debug", "phase laps of the CLI on stderr (bench.py's e2e legs parse them)"},
     {"MM_CLI_FORMAT_TRACE", "unset", "debug", "per-thread times of the text formatting of a batch on stderr"},
-    // ---- library: allocator (mm_common.hpp)
+    // ---- library: allocator (mm_alloc.hpp)
     {"MM_DEVICE_BYTES_CAP", "0 (off)", "test", "the library behaves as if every device had this many bytes: allocations beyond fail, mm_ctx_device_info reports it (placement tests)"},
     {"MM_INDEX_SCALE_MB", "8192", "test", "blocks from this size on are index-scale (pooled per device); a few MB exercise the pool on small inputs"},
     {"MM_NO_SLABS", "unset", "test", "worker buffers are not cut out of pooled index-scale blocks"},
     {"MM_NO_POOL_RESCUE", "unset", "test", "round-3 behaviour: a request the driver refuses hands the whole pool back instead of being served from it"},
-    {"MM_RETURN_INDEX_BLOCKS", "unset", "test", "index-scale blocks go back to the driver when released instead of into the device's pool"},
-    {"MM_INDEX_PRETRIM", "unset", "test", "a device-filling index build hands the pool back before it starts (round-4 mid-round behaviour)"},
-    {"MM_INDEX_NO_PRETRIM", "unset", "test", "... and does not even trim the context's own cache"},
     {"MM_ALLOC_TRACE", "unset", "debug", "every block that comes from the driver, with its cost, on stderr"},
-    {"MM_ALLOC_NO_MID_HEADROOM", "unset", "test", "device buffers of 256 KiB .. 64 MiB are asked for without the quarter of headroom that lets later, slightly larger batches reuse them (round 5 behaviour)"},
     {"MM_CTX_TRACE", "unset", "debug", "phases of mm_ctx_create (HIP initialisation, stream, allocator) on stderr"},
     {"MM_HOST_TIMING", "unset", "debug", "host-side sections of mm_map_batch and of the index build on stderr"},
     {"MM_PACK_SCALAR", "unset", "test", "mm_seqset_upload packs bases with the byte-table loop only (cross-check of the AVX2 path, host_pack.cpp)"},

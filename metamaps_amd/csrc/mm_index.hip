@@ -298,7 +298,7 @@ void index_build(mm_ctx* ctx, const mm_seqset* contigs, int k, int w, mm_index* 
       fprintf(stderr, "INFO, index build: %-28s %9.3f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count()); t = n;
     }
   } clk{st};
-  // Two allocation regimes (mm_common.hpp).  The index of a chunk of a --maxmemory run, one of many of its size: the cached blocks of
+  // Two allocation regimes (mm_alloc.hpp).  The index of a chunk of a --maxmemory run, one of many of its size: the cached blocks of
   // earlier work stay and serve this build (0.15 s per 13 GB chunk instead of 1-6 s through the driver), an allocation that fails for
   // lack of memory trims the caches itself.  An index that takes a good part of the device: memory goes back to the driver as the build
   // proceeds (DevAlloc::eager), nothing is left cached beside it.
@@ -308,9 +308,10 @@ void index_build(mm_ctx* ctx, const mm_seqset* contigs, int k, int w, mm_index* 
     if (dev_mem_info(&fr, &tot) == hipSuccess && (double)contigs->total_bases * 5.5 > (double)tot / 4) {
       // (until round 4's last session the device's pool went back to the driver here, before every device-filling build: with the chunk indexes of a
       // reference larger than the device built in turn that meant ~150 GB fresh from the driver per 15 Gbp chunk, cleared as it is handed out — 5.6 s of a
-      // 7.0 s build.  Now the pool stays: what the build asks for and the pool has is taken, what the driver cannot give is freed block by block.  MM_INDEX_PRETRIM=1: as before)
+      // 7.0 s build.  Now the pool stays: what the build asks for and the pool has is taken, what the driver cannot give is freed block by block.  MM_NO_POOL_RESCUE=1: as before)
       ctx->alloc.eager = true;
-      if (!getenv("MM_INDEX_NO_PRETRIM")) { ctx->alloc.trim(); if (getenv("MM_INDEX_PRETRIM") || getenv("MM_NO_POOL_RESCUE")) big_pool_trim(ctx->device); else big_pool_adopt_idle(ctx->device); }
+      ctx->alloc.trim();
+      if (alloc_env().rescue) big_pool_adopt_idle(ctx->device); else big_pool_trim(ctx->device);
     } }
   clk.lap("pool handling");
   I->ctx = ctx; I->k = k; I->w = w;

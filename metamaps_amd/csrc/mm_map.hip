@@ -849,15 +849,15 @@ struct MapRun {
   unsigned int* slot_flags_p() const { return sw.l2_no_slots ? nullptr : sk->slot_flags.p; }
   size_t max_slots(int nwq) const { return sw.l2_no_slots ? (size_t)1 << 40 : sw.l2_slots ? sw.l2_slots : (size_t)ctx->cus * (nwq == 2 ? 64 : 32); }
   size_t slots_of(size_t n_waves, int nwq = 8) const { return std::min((std::max<size_t>(n_waves, 1) + 7) / 8 * 8, max_slots(nwq)); }   // (a multiple of 8: one share per XCD)
-  uint8_t* masks_for(size_t n_waves, int nwq = 8) { return (uint8_t*)ctx->l2_masks_at_least(slots_of(n_waves, nwq) * l2_skip_bytes(nwq)); }
+  uint8_t* masks_for(size_t n_waves, int nwq = 8) { return (uint8_t*)ctx->l2_masks.at_least(ctx->alloc, slots_of(n_waves, nwq) * l2_skip_bytes(nwq)); }
   // per-entry code words of pass A: one slot range per wave of a launch (the launches of a batch run one after the other
   // on the stream, so they share the buffer); classes whose ranks do not fit 16 bits (C) search the sketch instead
   void* codes_for(size_t n_waves, int nwq) {
     if (sw.l2_no_codes) return nullptr;
-    return ctx->l2_codes_at_least(slots_of(n_waves, nwq) * (size_t)(64 * 64 * nwq) * (nwq == 2 ? sizeof(uint16_t) : sizeof(uint32_t)));
+    return ctx->l2_codes.at_least(ctx->alloc, slots_of(n_waves, nwq) * (size_t)(64 * 64 * nwq) * (nwq == 2 ? sizeof(uint16_t) : sizeof(uint32_t)));
   }
-  void* lists_for(size_t n_waves, int nwq) { return ctx->l2_codes_at_least(slots_of(n_waves, nwq) * l2z_list_bytes(nwq)); }
-  uint8_t* zmasks_for(size_t n_waves, int nwq) { return (uint8_t*)ctx->l2_masks_at_least(slots_of(n_waves, nwq) * l2z_mask_bytes(nwq)); }
+  void* lists_for(size_t n_waves, int nwq) { return ctx->l2_codes.at_least(ctx->alloc, slots_of(n_waves, nwq) * l2z_list_bytes(nwq)); }
+  uint8_t* zmasks_for(size_t n_waves, int nwq) { return (uint8_t*)ctx->l2_masks.at_least(ctx->alloc, slots_of(n_waves, nwq) * l2z_mask_bytes(nwq)); }
 
   // ---- K5/K6
   void l2() {

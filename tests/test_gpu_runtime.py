@@ -45,7 +45,7 @@ def test_same_results_with_and_without_pytorch_runtime(tmp_path):
 def test_cached_blocks_of_one_context_serve_another():
     """A context keeps the device blocks it frees (its allocator's cache) and gives them up when one of ITS allocations fails for lack of
     memory.  Worker contexts beside the context that built the indexes need that memory too: an allocation that fails now also trims the
-    caches of the other contexts of the device (mm_common.hpp: alloc_trim_others).  Context A fills three quarters of the free memory with
+    caches of the other contexts of the device (mm_alloc.hpp: alloc_trim_others).  Context A fills three quarters of the free memory with
     ~3 GiB sequence sets and closes them (all cached, nothing back at the driver); context B then allocates half of what was free."""
     from metamaps_amd import capi
     a, b = capi.Context(0), capi.Context(0)

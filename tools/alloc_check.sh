@@ -1,5 +1,5 @@
 #!/bin/bash
-# allocator regimes (mm_common.hpp): step times of the default bench (three runs: no step may stall), configs 3 and 4
+# allocator regimes (mm_alloc.hpp): step times of the default bench (three runs: no step may stall), configs 3 and 4
 cd $GRAFT_REPO_ROOT
 for i in ${RUNS:-1 2 3}; do timeout 900 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e-full --no-other-shape 2> /dev/null | python -c "
 import json,sys
