@@ -28,7 +28,7 @@ extern "C" {
 #define MM_ABI_VERSION 6   /* 3: mm_seqset_slice/concat, mm_map_batch_reusing, mm_em_continue, mm_synth_community_species;
                             * 4: mm_sketch_batch, mm_ctx_release_cached, mm_index_dup_neighbours;
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
-                            * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_* (additions to 6) */
+                            * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -48,6 +48,7 @@ typedef struct mm_index mm_index;      /* reference sketch of one index chunk, r
 typedef struct mm_mapping mm_mapping;  /* mapping results of one read batch, resident in HBM      */
 typedef struct mm_em mm_em;            /* EM state (mappings x taxa) resident in HBM              */
 typedef struct mm_gzip mm_gzip;        /* a plain gzip stream being inflated on a context's device */
+typedef struct mm_hpc_map mm_hpc_map;  /* compressed -> raw coordinates of a homopolymer-compressed set, resident in HBM */
 
 /* ---- context -------------------------------------------------------------------------------- */
 int mm_abi_version(void);
@@ -142,6 +143,26 @@ int mm_seqset_lengths(const mm_seqset* s, int32_t* len_out /* [count] */);
 int mm_seqset_fetch(mm_seqset* s, int64_t i, char* ascii_out, int64_t cap);
 /* sequences [first, first + count) one behind the other, no separators (lengths: mm_seqset_lengths); cap >= their total length */
 int mm_seqset_fetch_range(mm_seqset* s, int64_t first, int64_t count, char* ascii_out, int64_t cap);
+
+/* Homopolymer compression (mapDirectly --hpc; not in the reference).  hpc(S) replaces every maximal run of equal bytes
+ * of S — as the pipeline hashes it: upper-cased ASCII, IUPAC and N bytes kept — by one such byte ("NNNN" -> "N", "aAaA" -> "A", "NNRRNN" ->
+ * "NRN", empty stays empty).  mm_seqset_hpc compresses every sequence of an uploaded set on the device into a new set in the same layout
+ * (`raw` is left as it is and may be destroyed): every other entry point takes the result as it takes an uploaded set.  `map` (NULL: not
+ * wanted, e.g. for reads) receives the coordinate map back to raw positions, 0.133 bytes per raw base on the device:
+ *   raw(i, p)      0 <= p < clen: the raw position of the first base of the run that became base p of sequence i; p >= clen: rawlen + (p - clen)
+ *                  (the reference reports end = start + len - 1 without clamping, so positions past the end translate too); p < 0: p
+ *   rawlast(i, p)  the raw position of the last base of that run, the same rule beyond the end
+ * mm_hpc_map_to_raw evaluates both for n (sequence, compressed position) pairs given in host arrays (either output may not be NULL).
+ * mm_mapping_to_raw rewrites the records of `m` on the device, after mm_mapping_add_qualities: ref_start becomes raw(ref_contig, ref_start),
+ * and end_out[i] (host, cap >= number of records) receives rawlast(ref_contig, ref_start + read length - 1) of record i, with the lengths
+ * the mapping was made with (the compressed reads').  ref_contig indexes the set `ref_map` was made from: call it on the merged mapping
+ * (mm_mapping_concat / _gather / _from_parts), whose contig ids are those of the whole reference.  Call it once per mapping. */
+int mm_seqset_hpc(mm_ctx* ctx, const mm_seqset* raw, mm_seqset** out, mm_hpc_map** map);
+int mm_hpc_map_to_raw(mm_hpc_map* map, const int32_t* seq, const int64_t* pos, int64_t n, int64_t* first_out, int64_t* last_out);
+int mm_hpc_map_lengths(const mm_hpc_map* map, int32_t* raw_len /* [count], may be NULL */, int32_t* compressed_len /* [count], may be NULL */);
+int64_t mm_hpc_map_device_bytes(const mm_hpc_map* map);
+int mm_mapping_to_raw(mm_ctx* ctx, mm_mapping* m, const mm_hpc_map* ref_map, int64_t* end_out, int64_t cap);
+void mm_hpc_map_destroy(mm_hpc_map* map);
 
 /* Device-side synthetic inputs (bench.py; DESIGN.md "Synthetic workload").  The reference is a set of
  * genomes grouped in species (strains = substituted copies of a species root), generated straight into

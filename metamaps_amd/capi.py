@@ -130,6 +130,12 @@ def lib() -> C.CDLL:
             "mm_seqset_lengths": (C.c_int, [vp, vp]),
             "mm_seqset_fetch": (C.c_int, [vp, i64, C.c_char_p, i64]),
             "mm_seqset_fetch_range": (C.c_int, [vp, i64, i64, C.c_void_p, i64]),
+            "mm_seqset_hpc": (C.c_int, [vp, vp, P(vp), P(vp)]),
+            "mm_hpc_map_to_raw": (C.c_int, [vp, vp, vp, i64, vp, vp]),
+            "mm_hpc_map_lengths": (C.c_int, [vp, vp, vp]),
+            "mm_hpc_map_device_bytes": (i64, [vp]),
+            "mm_mapping_to_raw": (C.c_int, [vp, vp, vp, vp, i64]),
+            "mm_hpc_map_destroy": (None, [vp]),
             "mm_synth_reference": (C.c_int, [vp, P(SynthRefParams), P(vp)]),
             "mm_synth_reads": (C.c_int, [vp, vp, P(SynthReadParams), P(vp), vp]),
             "mm_synth_community": (C.c_int, [vp, P(SynthCommunityParams), P(vp), vp]),
@@ -497,6 +503,13 @@ class SeqSet:
     def save(self, path: str):
         self.ctx.check(lib().mm_seqset_save(self.h, path.encode()))
 
+    def hpc(self, want_map: bool = False):
+        """the homopolymer-compressed set (mm_seqset_hpc), compressed on the device; with want_map: (set, HpcMap back to raw coordinates)"""
+        h, m = C.c_void_p(), C.c_void_p()
+        self.ctx.check(lib().mm_seqset_hpc(self.ctx.h, self.h, C.byref(h), C.byref(m) if want_map else None))
+        out = SeqSet(self.ctx, h)
+        return (out, HpcMap(self.ctx, m, self.count)) if want_map else out
+
     def fetch(self, i: int, length: int) -> bytes:
         buf = C.create_string_buffer(length + 1)
         self.ctx.check(lib().mm_seqset_fetch(self.h, i, buf, length))
@@ -512,6 +525,37 @@ class SeqSet:
     def close(self):
         if self.h:
             lib().mm_seqset_destroy(self.h)
+            self.h = None
+
+
+class HpcMap:
+    """compressed -> raw coordinates of a homopolymer-compressed set (mm_hpc_map)"""
+    def __init__(self, ctx: Context, h, count: int):
+        self.ctx, self.h, self.count = ctx, h, count
+
+    def to_raw(self, seq, pos):
+        """(raw, rawlast) of the (sequence, compressed position) pairs (mm_hpc_map_to_raw)"""
+        seq = np.ascontiguousarray(seq, dtype=np.int32)
+        pos = np.ascontiguousarray(pos, dtype=np.int64)
+        first = np.zeros(len(seq), dtype=np.int64)
+        last = np.zeros(len(seq), dtype=np.int64)
+        self.ctx.check(lib().mm_hpc_map_to_raw(self.h, _ptr(seq), _ptr(pos), len(seq), _ptr(first), _ptr(last)))
+        return first, last
+
+    def lengths(self):
+        """(raw lengths, compressed lengths)"""
+        raw = np.zeros(self.count, dtype=np.int32)
+        comp = np.zeros(self.count, dtype=np.int32)
+        self.ctx.check(lib().mm_hpc_map_lengths(self.h, _ptr(raw), _ptr(comp)))
+        return raw, comp
+
+    @property
+    def device_bytes(self) -> int:
+        return int(lib().mm_hpc_map_device_bytes(self.h))
+
+    def close(self):
+        if self.h:
+            lib().mm_hpc_map_destroy(self.h)
             self.h = None
 
 
@@ -582,6 +626,15 @@ class Mapping:
 
     def add_qualities(self, k: int):
         self.ctx.check(lib().mm_mapping_add_qualities(self.ctx.h, self.h, None, k))
+
+    def to_raw(self, ref_map: "HpcMap") -> np.ndarray:
+        """records of a mapping made on compressed sequences -> raw reference coordinates (mm_mapping_to_raw, after add_qualities):
+        ref_start is rewritten on the device; returns the raw end of every record"""
+        off = np.empty(self.n_reads + 1, dtype=np.int64)
+        self.ctx.check(lib().mm_mapping_fetch(self.h, _ptr(off), None, 0))
+        end = np.zeros(int(off[-1]), dtype=np.int64)
+        self.ctx.check(lib().mm_mapping_to_raw(self.ctx.h, self.h, ref_map.h, _ptr(end), len(end)))
+        return end
 
     def release_intermediates(self):
         """frees everything but the records (minimizers, sketches, hits, candidates): what a chunk mapping keeps while the other chunks are mapped"""

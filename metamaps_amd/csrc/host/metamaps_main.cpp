@@ -43,6 +43,14 @@
 // the buffer the tokeniser works on; any bgzip'd mappings file is accepted.  A corrupt or truncated file ends the run with the compressed
 // offset of the bad block.  A plain gzip mappings file (no BGZF blocks) is refused with a message that says so.
 //
+// --hpc (mapDirectly; not in the reference; minimap2's -H): homopolymer-compressed mapping.  Every maximal run of equal bytes of the reference and
+// of the reads — as hashed: upper-cased, IUPAC and N kept — becomes one byte, on the device (mm_seqset_hpc): the reference once per device behind
+// its upload, every read batch on the context that maps it.  The pipeline then runs unchanged on the compressed sequences: -m, the len < w and
+// len < k skips, identities, sketch sizes and mapping qualities are in COMPRESSED space.  Lengths and coordinates are reported raw: fields 2, 4, 7
+// of a mapping line and .meta.unmappedReadsLengths carry raw lengths, field 8 the raw position of the first base of the run the compressed start
+// fell on, field 9 that of the last base of the run the compressed end fell on (mm_mapping_to_raw, on the device behind the mapping qualities).
+// -w is chosen from the raw reference size as ever; PREFIX.parameters gains the line "hpc 1".  index / mapAgainstIndex / classify refuse the flag.
+//
 // Not provided: classifyU (disabled upstream).
 
 #include "../mm_env.hpp"
@@ -162,8 +170,13 @@ Options parse(int argc, char** argv) {
     if (a == "--stream-chunks") { o.stream = true; continue; }
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
-    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output") { o.v[a.substr(2)] = "1"; continue; }
-    if (a == "-h" || a == "--help") { std::cout << "see the header of metamaps_main.cpp / the reference's README\n"; exit(0); }
+    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc") { o.v[a.substr(2)] = "1"; continue; }
+    if (a == "-h" || a == "--help") {
+      std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
+                   "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
+                   "         sketching; -m, identities and mapping qualities are in compressed space, reported lengths and coordinates are raw\n";
+      exit(0);
+    }
     std::string key = alias.count(a) ? alias.at(a) : (a.rfind("--", 0) == 0 ? a.substr(2) : "");
     if (key.empty() || i + 1 >= argc) die("Unknown or incomplete option " + a);
     o.v[key] = argv[++i];
@@ -297,7 +310,7 @@ struct FormatCache {
 // A mapping line as `classify` sees it once it has tokenised the file (fEM.h:234-275): where the line lies in the text, and the values of the fields it reads
 // — identity and mapping quality as the PRINTED text parses, not as the floats they were printed from.  `mapDirectly --then-classify` keeps these beside the
 // text it writes, so that classify in the same process neither reads the file back nor tokenises it.
-struct LineMeta { uint32_t beg, ls /* the blank before field 14, relative to beg */, n /* length without the newline */; int32_t contig /* index into the reference's contigs */, len, start; double ident, mapq; };
+struct LineMeta { uint32_t beg, ls /* the blank before field 14, relative to beg */, n /* length without the newline */; int32_t contig /* index into the reference's contigs */, len, start, stop /* field 9: start + len - 1, or its raw translation with --hpc */; double ident, mapq; };
 static double mapq_as_classify_reads_it(const char* p, size_t n) {
   double v;
   if (parse_g6_text(p, n, &v)) return v;
@@ -308,7 +321,7 @@ static double mapq_as_classify_reads_it(const char* p, size_t n) {
 }
 static void format_range(const std::vector<std::string>& names, const std::vector<int>& lens, const std::vector<int64_t>& off,
                          const std::vector<mm_map_record>& rec, const std::vector<std::string>& cname, const std::vector<int>& clen, int k, size_t r0, size_t r1, std::string& out,
-                         FormatCache& fc, std::vector<LineMeta>* meta) {
+                         FormatCache& fc, std::vector<LineMeta>* meta, const int64_t* raw_end /* --hpc: field 9 of every record; else nullptr */) {
   out.clear();
   if (meta) { meta->clear(); meta->reserve((size_t)(off[r1] - off[r0])); }
   out.reserve((size_t)(off[r1] - off[r0]) * 160);
@@ -339,13 +352,13 @@ static void format_range(const std::vector<std::string>& names, const std::vecto
       out += ' '; append_int(out, len); out += " 0 "; append_int(out, len - 1); out += ' '; out += x.strand == 1 ? '+' : '-'; out += ' ';
       out += cname[(size_t)x.ref_contig];
       out += ' '; append_int(out, clen[(size_t)x.ref_contig]);
-      out += ' '; append_int(out, x.ref_start); out += ' '; append_int(out, (long long)x.ref_start + len - 1);
+      out += ' '; append_int(out, x.ref_start); out += ' '; append_int(out, raw_end ? (long long)raw_end[(size_t)i] : (long long)x.ref_start + len - 1);
       out += ' '; out.append(P.ids, P.n_ids);
       out += ' '; append_int(out, x.shared); out += ' '; append_int(out, x.sketch);
       out += ' '; out.append(P.corr, P.n_corr);
       const size_t ls = out.size();
       out += ' '; append_g6(out, x.mapq);                          // :318-320
-      if (meta) meta->push_back(LineMeta{(uint32_t)line_beg, (uint32_t)(ls - line_beg), (uint32_t)(out.size() - line_beg), (int32_t)x.ref_contig, (int32_t)len, (int32_t)x.ref_start,
+      if (meta) meta->push_back(LineMeta{(uint32_t)line_beg, (uint32_t)(ls - line_beg), (uint32_t)(out.size() - line_beg), (int32_t)x.ref_contig, (int32_t)len, (int32_t)x.ref_start, (int32_t)(raw_end ? raw_end[(size_t)i] : (int64_t)x.ref_start + len - 1),
                                          P.ident, mapq_as_classify_reads_it(out.data() + ls + 1, out.size() - ls - 1)});
       out += '\n';
     }
@@ -353,12 +366,13 @@ static void format_range(const std::vector<std::string>& names, const std::vecto
 }
 // the mapping lines of a batch (mapWrap.h:300-323): ranges of reads formatted by a few threads, joined in read order
 void format_records(const std::vector<std::string>& names, const std::vector<int>& lens, const std::vector<int64_t>& off,
-                    const std::vector<mm_map_record>& rec, const std::vector<std::string>& cname, const std::vector<int>& clen, int k, std::string& out, std::vector<LineMeta>* meta) {
+                    const std::vector<mm_map_record>& rec, const std::vector<std::string>& cname, const std::vector<int>& clen, int k, std::string& out, std::vector<LineMeta>* meta,
+                    const int64_t* raw_end = nullptr) {
   const size_t n = names.size();
   static const size_t per_part = getenv("MM_CLI_FORMAT_PART") ? (size_t)std::max(1, atoi(getenv("MM_CLI_FORMAT_PART"))) : 10000;   // (tests: several parts for small batches too)
   const size_t T = std::max<size_t>(1, std::min<size_t>({(size_t)8, (size_t)std::max(per_part < 10000 ? 8u : 1u, mm::cpu_budget() / 4), rec.size() / per_part + 1}));   // (a quarter of the CPU budget per worker: four workers rarely format at the same moment)
   static thread_local std::vector<FormatCache> caches(8);          // (the calling thread's: a worker of mapDirectly formats batch after batch)
-  if (T == 1) { format_range(names, lens, off, rec, cname, clen, k, 0, n, out, caches[0], meta); return; }
+  if (T == 1) { format_range(names, lens, off, rec, cname, clen, k, 0, n, out, caches[0], meta, raw_end); return; }
   std::vector<size_t> cut(T + 1, n);
   cut[0] = 0;
   { size_t t = 1; for (size_t r = 0; r < n && t < T; ++r) if ((uint64_t)off[r] >= (uint64_t)rec.size() * t / T) cut[t++] = r; }
@@ -369,7 +383,7 @@ void format_records(const std::vector<std::string>& names, const std::vector<int
   std::vector<std::vector<LineMeta>>& metas = meta_store;        // (the CALLING thread's: the helpers below must not name the thread_local themselves)
   const auto q0 = std::chrono::steady_clock::now();
   std::vector<double> took(T, 0.0);
-  auto timed = [&](size_t t) { const auto a = std::chrono::steady_clock::now(); format_range(names, lens, off, rec, cname, clen, k, cut[t], cut[t + 1], part[t], fcs[t], meta ? &metas[t] : nullptr);
+  auto timed = [&](size_t t) { const auto a = std::chrono::steady_clock::now(); format_range(names, lens, off, rec, cname, clen, k, cut[t], cut[t + 1], part[t], fcs[t], meta ? &metas[t] : nullptr, raw_end);
                                took[t] = std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
   static thread_local TaskPool helpers(7);                         // (task_pool.hpp: the calling worker's own helpers, there from batch to batch)
   const auto q1 = q0;
@@ -412,6 +426,10 @@ struct MapRun {
   PhaseClock pc;
   std::vector<Dev> devs; size_t G = 0; mm_ctx* ctx0 = nullptr;
   std::vector<std::string> cname; std::vector<int> clen;
+  // --hpc: the sequences are homopolymer-compressed on the device (mm_seqset_hpc) and everything from the chunk plan to the mapping qualities sees the
+  // compressed ones: clen holds the compressed contig lengths, clen_raw what is printed; hpc_map[d] translates the records' coordinates on device d
+  const bool hpc = o.v.count("hpc") != 0;
+  std::vector<int> clen_raw; std::vector<mm_hpc_map*> hpc_map;
   struct Chunk { int first, count; std::string file; };
   std::vector<Chunk> chunks;
   // The packed reference (2 bits per base + exception runs, a quarter of the FASTA's size) lives on every device that builds indexes
@@ -430,7 +448,7 @@ struct MapRun {
   mm_map_params mp{};
   std::vector<int32_t> chunk_base;
   // what a worker hands to the writer: the finished text of one batch
-  struct Done { size_t file = 0; std::vector<std::string> names; std::vector<int> lens; std::vector<int64_t> off; std::string text; std::string gz /* --compress-output: the text as BGZF members */; std::vector<LineMeta> meta; double t_mapq = 0, t_fetch = 0, t_format = 0; };
+  struct Done { size_t file = 0; std::vector<std::string> names; std::vector<int> lens; std::vector<int> clens /* --hpc: the compressed lengths (lens stay raw) */; std::vector<int64_t> off; std::string text; std::string gz /* --compress-output: the text as BGZF members */; std::vector<LineMeta> meta; double t_mapq = 0, t_fetch = 0, t_format = 0; };
   // --then-classify: the batches of every query file as they were written, in order (text + the parsed fields of every line): what classify takes instead of the file
   const bool keep_lines = o.v.count("then-classify") && !getenv("MM_CLI_CLASSIFY_FROM_FILE");
   // --compress-output: the mappings go to PREFIX.gz as BGZF; a batch's text is deflated by the context that mapped it, right behind its formatting
@@ -464,6 +482,7 @@ struct MapRun {
   ~MapRun() { if (prewarm.joinable()) prewarm.join(); }
 
   void read_parameters() {
+    if (hpc && mode != "mapDirectly") die("--hpc belongs to mapDirectly: " + mode + " --hpc (stored indexes of compressed sequences) is not provided");
     if (!from_index && !o.v.count("reference")) die("Provide reference file (s)");
     if ((from_index || only_index) && !o.v.count("index")) die("Please provide index");
     if (!only_index && !o.v.count("query")) die("Provide query file (s)");
@@ -896,8 +915,26 @@ struct MapRun {
     });
     pc.lap("1 reference parse + pack + upload");
     pc.add("2 reference pack+upload (inside 1)", t_pack);
+    if (hpc) compress_reference();
     if (!only_index) { if (!getenv("MM_CLI_LATE_READER")) start_reader(); start_prewarm(); }   // (MM_CLI_LATE_READER: measurement aid — the reader starts when the index is built)
     query_free();                                                // the packed reference now lives on the device (0.25 B per base, for as long as chunks are cut out of it): what is left is what the indexes get
+  }
+
+  // --hpc: the reference of every device compressed where it lies, once, before the chunk plan; the raw packed set goes, the map stays
+  void compress_reference() {
+    hpc_map.assign(refset.size(), nullptr);
+    std::vector<int32_t> cl(cname.size());
+    on_each(refset.size(), [&](size_t d) {
+      if (!refset[d]) return;
+      mm_seqset* c = nullptr;
+      ck(devs[d].ctx, mm_seqset_hpc(devs[d].ctx, refset[d], &c, &hpc_map[d]), "homopolymer compression of the reference");
+      mm_seqset_destroy(refset[d]); refset[d] = c;
+      if (d == 0 && !cl.empty()) ck(devs[d].ctx, mm_seqset_lengths(c, cl.data()), "compressed contig lengths");
+    });
+    clen_raw = clen; ref_bases = 0;
+    for (size_t i = 0; i < clen.size(); ++i) { clen[i] = cl[i]; ref_bases += (uint64_t)cl[i]; }
+    std::cout << "INFO, --hpc: " << ref_bases << " reference bases after homopolymer compression, coordinate map of " << (mm_hpc_map_device_bytes(hpc_map[0]) >> 10) << " KiB per device\n";
+    pc.lap("2h reference homopolymer compression");
   }
 
   // ---- the chunk plan of --maxmemory (winSketch.hpp:274-329): on the index of the whole reference when that fits, on contig ranges otherwise
@@ -1103,7 +1140,17 @@ struct MapRun {
     if (bt.nt16) for (size_t r = 0; r < bt.names.size(); ++r) ck(ctx, mm_seqset_add_nt16(reads, (const uint8_t*)bt.seq_of(r), (int64_t)bt.lens[r], bt.rev[r]), "add read");
     else for (size_t r = 0; r < bt.names.size(); ++r) ck(ctx, mm_seqset_add_view(reads, bt.seq_of(r), (int64_t)bt.lens[r]), "add read");
     ck(ctx, mm_seqset_upload(reads), "upload reads");
+    if (hpc) {                                                     // compressed on the context that maps the batch, between upload and K1
+      mm_seqset* c = nullptr;
+      ck(ctx, mm_seqset_hpc(ctx, reads, &c, nullptr), "homopolymer compression of the reads");
+      mm_seqset_destroy(reads); reads = c;
+    }
     return reads;
+  }
+  std::vector<int> compressed_lengths(mm_ctx* ctx, const mm_seqset* reads) {   // --hpc: what -m, the skips and the mapping qualities count
+    std::vector<int> cl((size_t)mm_seqset_count(reads));
+    if (!cl.empty()) ck(ctx, mm_seqset_lengths(reads, cl.data()), "compressed read lengths");
+    return cl;
   }
   // one "PREFIX.N" per chunk in the reference (mapWrap.h:419-437); `sketch_of`: an earlier mapping of the same batch on this device,
   // whose minimizers and sketches are reused (they do not depend on the index)
@@ -1114,19 +1161,24 @@ struct MapRun {
     if (!o.all) ck(ctx, mm_mapping_keep_best(ctx, pm, k), "best mappings");
     return pm;
   }
-  std::unique_ptr<Done> finish_mapping(mm_ctx* ctx, mm_mapping* m, std::vector<std::string>&& names, std::vector<int>&& lens, size_t file) {   // mapping qualities + text; consumes m
+  std::unique_ptr<Done> finish_mapping(mm_ctx* ctx, size_t dev, mm_mapping* m, std::vector<std::string>&& names, std::vector<int>&& lens, std::vector<int>&& clens, size_t file) {   // mapping qualities + text; consumes m
     auto dn = std::make_unique<Done>();
-    dn->file = file; dn->names = std::move(names); dn->lens = std::move(lens);
+    dn->file = file; dn->names = std::move(names); dn->lens = std::move(lens); dn->clens = std::move(clens);
     const auto f0 = std::chrono::steady_clock::now();
     ck(ctx, mm_mapping_add_qualities(ctx, m, nullptr, k), "mapping qualities");
     dn->off.resize(dn->names.size() + 1);
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), nullptr, 0), "fetch");
+    std::vector<int64_t> raw_end;
+    if (hpc) {                                                     // the records' start -> raw coordinates on the device; field 9 comes back beside them
+      raw_end.resize((size_t)dn->off.back());
+      ck(ctx, mm_mapping_to_raw(ctx, m, hpc_map[dev], raw_end.data(), (int64_t)raw_end.size()), "raw coordinates");
+    }
     const auto f1 = std::chrono::steady_clock::now();
     std::vector<mm_map_record> rec((size_t)dn->off.back());
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), rec.data(), (int64_t)rec.size()), "fetch");
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
-    format_records(dn->names, dn->lens, dn->off, rec, cname, clen, k, dn->text, keep_lines ? &dn->meta : nullptr);
+    format_records(dn->names, dn->lens, dn->off, rec, cname, hpc ? clen_raw : clen, k, dn->text, keep_lines ? &dn->meta : nullptr, hpc ? raw_end.data() : nullptr);
     if (compress) deflate_text(ctx, *dn);
     const auto f3 = std::chrono::steady_clock::now();
     pc.add("7a mapping qualities + offsets", std::chrono::duration<double>(f1 - f0).count());
@@ -1162,8 +1214,8 @@ struct MapRun {
         ++seq;
         for (size_t r = 0; r < d->names.size(); ++r) {
           ++total;
-          const int len = d->lens[r];
-          if (len < w || len < k || len < minLen) { ++tooShort; continue; }
+          const int len = d->lens[r], mlen = d->clens.empty() ? len : d->clens[r];   // (--hpc: the skips count compressed bases, the file carries raw lengths)
+          if (mlen < w || mlen < k || mlen < minLen) { ++tooShort; continue; }
           // mapWrap.h:71-75 checks the IDs of mapping LINES against the reads already handled: a repeated ID only stops the run
           // when the repeat carries mappings; every handled read's ID is remembered (:154-157)
           if (d->off[r] == d->off[r + 1]) { ++notMapped; unm << len << "\t" << d->names[r] << "\n"; seen.insert(d->names[r]); continue; }
@@ -1184,6 +1236,7 @@ struct MapRun {
       ps << "kmerSize " << k << "\nwindowSize " << w << "\nminReadLength " << minLen << "\nalphabetSize " << 4 << "\nreferenceSize " << refSize
          << "\npercentageIdentity " << pi << "\np_value " << pval << "\nrefSequences [" << ref << "]\nquerySequences [" << queries[fi]
          << "]\noutFileName " << prefix << "\nreportAll " << o.all << "\nindex " << "" << "\nmaximumMemory " << maxMem << "\n";
+      if (hpc) ps << "hpc 1\n";
       std::cout << "INFO, [count of mapped reads, reads qualified for mapping, total input reads] = [" << mapped << ", " << total - tooShort << ", " << total << "]\n";
     }
   }
@@ -1208,6 +1261,7 @@ struct MapRun {
       while (std::unique_ptr<Batch> bt = reader.take()) {
         const auto t0 = std::chrono::steady_clock::now();
         mm_seqset* reads = upload_batch(ctx, *bt);
+        std::vector<int> clens; if (hpc) clens = compressed_lengths(ctx, reads);
         const auto t1 = std::chrono::steady_clock::now();
         std::vector<mm_mapping*> parts;
         map_slots[d].acquire();
@@ -1223,7 +1277,7 @@ struct MapRun {
         mm_seqset_destroy(reads);
         const auto t2 = std::chrono::steady_clock::now();
         const size_t seq = bt->seq;
-        auto dn = finish_mapping(ctx, m, std::move(bt->names), std::move(bt->lens), bt->file);
+        auto dn = finish_mapping(ctx, d, m, std::move(bt->names), std::move(bt->lens), std::move(clens), bt->file);
         const auto t3 = std::chrono::steady_clock::now();
         pc.add("5 reads pack+upload", std::chrono::duration<double>(t1 - t0).count());
         pc.add("6 map", std::chrono::duration<double>(t2 - t1a).count());
@@ -1250,7 +1304,7 @@ struct MapRun {
 
   void run_chunk_major() {
     // ---- sharded / streamed: every read batch is packed onto every device and stays there (2 bits per base) ...
-    struct Held { size_t file = 0; std::vector<std::string> names; std::vector<int> lens; std::vector<mm_seqset*> reads;
+    struct Held { size_t file = 0; std::vector<std::string> names; std::vector<int> lens, clens /* --hpc: compressed */; std::vector<mm_seqset*> reads;
                   std::vector<mm_mapping*> sk;                 // per device: the batch's minimizers + sketches (mm_sketch_batch), computed once for all chunks
                   std::vector<mm_mapping*> part;               // per chunk: the batch's records against that chunk, on the device that holds the chunk (c mod G)
                   std::vector<std::vector<int64_t>> poff; std::vector<std::vector<mm_map_record>> prec; };   // --host-gather: the same in host memory (rounds 1-3)
@@ -1268,6 +1322,7 @@ struct MapRun {
       h.file = bt->file; h.reads.assign(G, nullptr); h.sk.assign(G, nullptr); h.part.assign(NC, nullptr); h.poff.resize(NC); h.prec.resize(NC);
       on_each(G, [&](size_t d) { h.reads[d] = upload_batch(devs[d].ctx, *bt); });
       h.names = std::move(bt->names); h.lens = std::move(bt->lens);
+      if (hpc) h.clens = compressed_lengths(devs[0].ctx, h.reads[0]);
       reader.recycle(std::move(bt));
     }
     pc.lap("5 reads pack+upload");
@@ -1294,7 +1349,7 @@ struct MapRun {
           if (c % G != d) continue;
           for (auto& h : held) {
             if (!h.sk[d] && sk_budget[d]) {
-              uint64_t bases = 0; for (int L : h.lens) bases += (uint64_t)L;
+              uint64_t bases = 0; for (int L : (hpc ? h.clens : h.lens)) bases += (uint64_t)L;
               if (sk_used[d] + 3 * bases <= sk_budget[d]) { ck(devs[d].ctx, mm_sketch_batch(devs[d].ctx, h.reads[d], &mp, &h.sk[d]), "sketch"); sk_used[d] += 3 * bases; }
             }
             mm_mapping* pm = map_chunk(devs[d].ctx, devs[d].idx[c], h.reads[d], h.sk[d]);
@@ -1327,7 +1382,7 @@ struct MapRun {
           std::vector<mm_mapping*> mine; std::vector<int32_t> ids;
           for (size_t c = d; c < NC; c += G) { mine.push_back(h.part[c]); ids.push_back((int32_t)c); }
           mm_mapping* m = nullptr;
-          ck(ctx, mm_mapping_gather(ctx, (int)(b % G), (int64_t)h.names.size(), h.lens.data(), &mp, mine.data(), ids.data(), (int)mine.size(), (int)NC, chunk_rank.data(), chunk_base.data(), &m), "gather chunks");
+          ck(ctx, mm_mapping_gather(ctx, (int)(b % G), (int64_t)h.names.size(), (hpc ? h.clens : h.lens).data(), &mp, mine.data(), ids.data(), (int)mine.size(), (int)NC, chunk_rank.data(), chunk_base.data(), &m), "gather chunks");
           if (b % G == d) merged[b] = m;
           for (auto* pm : mine) mm_mapping_destroy(pm);
         }
@@ -1343,9 +1398,9 @@ struct MapRun {
         } else if (gather == Gather::Host) {
           std::vector<const int64_t*> op; std::vector<const mm_map_record*> rp;
           for (size_t c = 0; c < NC; ++c) { op.push_back(h.poff[c].data()); rp.push_back(h.prec[c].data()); }
-          ck(devs[d].ctx, mm_mapping_from_parts(devs[d].ctx, (int64_t)h.names.size(), h.lens.data(), &mp, (int)NC, op.data(), rp.data(), chunk_base.data(), &m), "merge chunks");
+          ck(devs[d].ctx, mm_mapping_from_parts(devs[d].ctx, (int64_t)h.names.size(), (hpc ? h.clens : h.lens).data(), &mp, (int)NC, op.data(), rp.data(), chunk_base.data(), &m), "merge chunks");
         }
-        results[b] = finish_mapping(devs[d].ctx, m, std::move(h.names), std::move(h.lens), h.file);
+        results[b] = finish_mapping(devs[d].ctx, d, m, std::move(h.names), std::move(h.lens), std::move(h.clens), h.file);
         std::vector<std::vector<int64_t>>().swap(h.poff); std::vector<std::vector<mm_map_record>>().swap(h.prec);
       }
     });
@@ -2236,7 +2291,7 @@ struct ClassifyRun {
         const LineMeta& m = P.meta[i];
         int& ci = intern[(size_t)m.contig];
         if (ci < 0) { ci = (int)contig_id.size(); contig_id.push_back((*kept->cname)[(size_t)m.contig]); contig_index.emplace(contig_id.back(), ci); }
-        lines[at + i] = MapLine{P.text + m.beg, m.ls, m.n, ci, (long long)m.len, (size_t)m.start, (size_t)((long long)m.start + m.len - 1), m.ident, m.mapq};
+        lines[at + i] = MapLine{P.text + m.beg, m.ls, m.n, ci, (long long)m.len, (size_t)m.start, (size_t)m.stop, m.ident, m.mapq};
       }
       at += P.n_lines;
     }
@@ -2285,6 +2340,7 @@ int main(int argc, char** argv) {
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
   if (mode == "mapDirectly" || mode == "index" || mode == "mapAgainstIndex") return map_mode(o, mode);
   if (mode == "classify") {
+    if (o.v.count("hpc")) die("--hpc belongs to mapDirectly: classify reads the raw coordinates a --hpc mapping reports and takes no such flag");
     if (!o.v.count("DB")) die("Provide path to DB.");
     if (!o.v.count("mappings")) die("Provide path to mappings.");
     const auto m0 = std::chrono::steady_clock::now();

@@ -6,6 +6,7 @@
 #include "mm_em.hpp"
 #include "mm_stats.hpp"
 #include "mm_synth.hpp"
+#include "mm_hpc.hpp"
 #include <chrono>
 #include <new>
 #include <rccl/rccl.h>
@@ -278,6 +279,35 @@ int mm_seqset_fetch_range(mm_seqset* s, int64_t first, int64_t count, char* asci
   if (!s || (!ascii_out && cap > 0)) return MM_ERR_ARG;
   return guarded(s->ctx, [&] { mm::seqset_fetch_range(s, first, count, ascii_out, cap); });
 }
+
+// ---- homopolymer compression (mm_hpc.hip) -------------------------------------------------------------
+int mm_seqset_hpc(mm_ctx* ctx, const mm_seqset* raw, mm_seqset** out, mm_hpc_map** map) {
+  if (!ctx || !raw || !out) return MM_ERR_ARG;
+  *out = nullptr; if (map) *map = nullptr;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<mm_seqset> S(new mm_seqset); S->ctx = ctx;
+    std::unique_ptr<mm_hpc_map> M(map ? new mm_hpc_map : nullptr);
+    mm::seqset_hpc(ctx, raw, S.get(), M.get());
+    *out = S.release(); if (map) *map = M.release();
+  });
+}
+int mm_hpc_map_to_raw(mm_hpc_map* map, const int32_t* seq, const int64_t* pos, int64_t n, int64_t* first_out, int64_t* last_out) {
+  if (!map || n < 0 || (n > 0 && (!seq || !pos || !first_out || !last_out))) return MM_ERR_ARG;
+  return guarded(map->ctx, [&] { MM_HIP(hipSetDevice(map->ctx->device)); mm::hpc_map_to_raw(map, seq, pos, n, first_out, last_out); });
+}
+int mm_hpc_map_lengths(const mm_hpc_map* map, int32_t* raw_len, int32_t* compressed_len) {
+  if (!map) return MM_ERR_ARG;
+  if (raw_len) memcpy(raw_len, map->rawlen.data(), map->rawlen.size() * sizeof(int32_t));
+  if (compressed_len) memcpy(compressed_len, map->clen.data(), map->clen.size() * sizeof(int32_t));
+  return MM_OK;
+}
+int64_t mm_hpc_map_device_bytes(const mm_hpc_map* map) { return map ? (int64_t)map->device_bytes() : 0; }
+int mm_mapping_to_raw(mm_ctx* ctx, mm_mapping* m, const mm_hpc_map* ref_map, int64_t* end_out, int64_t cap) {
+  if (!ctx || !m || !ref_map || cap < 0 || (!end_out && cap > 0)) return MM_ERR_ARG;
+  return guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); mm::mapping_to_raw(ctx, m, ref_map, end_out, cap); });
+}
+void mm_hpc_map_destroy(mm_hpc_map* map) { if (map) { bind(map->ctx); delete map; } }
 
 int mm_synth_reference(mm_ctx* ctx, const mm_synth_ref_params* p, mm_seqset** out) {
   if (!ctx || !p || !out) return MM_ERR_ARG;
