@@ -28,7 +28,8 @@ extern "C" {
 #define MM_ABI_VERSION 6   /* 3: mm_seqset_slice/concat, mm_map_batch_reusing, mm_em_continue, mm_synth_community_species;
                             * 4: mm_sketch_batch, mm_ctx_release_cached, mm_index_dup_neighbours;
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
-                            * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw (additions to 6) */
+                            * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
+                            *    mm_em_lca (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -405,6 +406,13 @@ int mm_em_posteriors(mm_em* em, const double* f, double* post /* [n_entries] */,
  * posteriors and n_taxa*n_rep*8 of frequencies) exceed the device, MM_ERR_NOMEM when they do not fit its free memory: the caller tiles. */
 int mm_em_bootstrap(mm_em* em, const double* f_start, int32_t rep0, int32_t n_rep, uint64_t seed, const uint8_t* weights,
                     int max_iter, double* f_out, double* ll_out, int32_t* n_iter, int32_t* stopped);
+/* Confidence-thresholded lowest-common-ancestor assignment of every read of `em` (not in the reference).
+ * Tree: n_nodes nodes, parent[v] < v for v > 0, parent[0] == 0 (the root); taxon_node[n_taxa]: the node of every taxon of `em`.
+ * Posteriors are those of mm_em_posteriors(em, f).  node_out[n_reads]: lca(r), or -1 for a read without entries; mass_out[n_reads]
+ * (may be NULL): mass(r, lca(r)), 0 for such a read; direct_out[n_nodes] (may be NULL): reads per assigned node.
+ * MM_ERR_ARG: threshold outside [0.51, 1], a parent[] that is not in that order, a taxon_node outside the tree. */
+int mm_em_lca(mm_em* em, const double* f, int32_t n_nodes, const int32_t* parent, const int32_t* taxon_node, double threshold,
+              int32_t* node_out, double* mass_out, int64_t* direct_out);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------------------------- */
 #define MM_COMM_ID_BYTES 128

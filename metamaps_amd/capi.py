@@ -187,6 +187,7 @@ def lib() -> C.CDLL:
             "mm_em_run": (C.c_int, [vp, vp, C.c_int, vp, vp, C.c_int, P(C.c_int)]),
             "mm_em_continue": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, P(C.c_int), P(C.c_int)]),
             "mm_em_bootstrap": (C.c_int, [vp, vp, i32, i32, u64, vp, C.c_int, vp, vp, vp, vp]),
+            "mm_em_lca": (C.c_int, [vp, vp, i32, vp, vp, f64, vp, vp, vp]),
             "mm_comm_unique_id": (C.c_int, [C.c_char_p]),
             "mm_comm_init": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
             "mm_comm_allreduce_f64": (C.c_int, [vp, vp, i64]),
@@ -800,6 +801,21 @@ class EM:
         best = np.zeros(self.n_reads, dtype=np.int64)
         self.ctx.check(lib().mm_em_posteriors(self.h, _ptr(f), _ptr(post), _ptr(best)))
         return post, best
+
+    def lca(self, f: np.ndarray, parent, taxon_node, threshold: float, want_mass: bool = True, want_direct: bool = True):
+        """confidence-thresholded LCA assignment of every read for the posteriors of f (mm_em_lca).  parent: the tree (parent[v] < v,
+        parent[0] == 0); taxon_node [n_taxa]: the node of every taxon.  Returns (node [n_reads] int32, -1 for a read without entries;
+        mass [n_reads] or None; direct [n_nodes] int64 or None)."""
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        taxon_node = np.ascontiguousarray(taxon_node, dtype=np.int32)
+        if f.shape != (self.n_taxa,) or taxon_node.shape != (self.n_taxa,):
+            raise ValueError(f"f and taxon_node must have {self.n_taxa} values")
+        node = np.full(self.n_reads, -2, dtype=np.int32)
+        mass = np.zeros(self.n_reads, dtype=np.float64) if want_mass else None
+        direct = np.zeros(len(parent), dtype=np.int64) if want_direct else None
+        self.ctx.check(lib().mm_em_lca(self.h, _ptr(f), len(parent), _ptr(parent), _ptr(taxon_node), float(threshold), _ptr(node), _ptr(mass), _ptr(direct)))
+        return node, mass, direct
 
     def close(self):
         if self.h:

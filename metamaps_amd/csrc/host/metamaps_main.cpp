@@ -7,7 +7,7 @@
 //
 //   metamaps mapDirectly [--all] [--compress-output] -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
-//   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]]
+//   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]] [--lca T]
 //
 // --gpus N uses devices 0..N-1 of the node, one context per device on its own host thread (where the reference has -t N worker
 // threads, computeMap.hpp:104-176 / fEM.h:1229): mapping shards the read batches (index replicated) or the index chunks
@@ -50,6 +50,11 @@
 // of a mapping line and .meta.unmappedReadsLengths carry raw lengths, field 8 the raw position of the first base of the run the compressed start
 // fell on, field 9 that of the last base of the run the compressed end fell on (mm_mapping_to_raw, on the device behind the mapping qualities).
 // -w is chosen from the raw reference size as ever; PREFIX.parameters gains the line "hpc 1".  index / mapAgainstIndex / classify refuse the flag.
+//
+// --lca T (classify, mapDirectly --then-classify; not in the reference; Kraken 2's --confidence): every read is also given to the deepest taxonomy
+// node whose subtree holds at least T (0.51 to 1) of its posterior mass, on the device behind the final posteriors (mm_em_lca, DESIGN.md §4 "LCA
+// assignment").  PREFIX.EM.reads2Taxon.lca (readID, taxonID, rank, mass) and PREFIX.EM.kreport (the six-column Kraken report) are added; every
+// other output is unchanged.
 //
 // Not provided: classifyU (disabled upstream).
 
@@ -174,7 +179,9 @@ Options parse(int argc, char** argv) {
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
-                   "         sketching; -m, identities and mapping qualities are in compressed space, reported lengths and coordinates are raw\n";
+                   "         sketching; -m, identities and mapping qualities are in compressed space, reported lengths and coordinates are raw\n"
+                   "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
+                   "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n";
       exit(0);
     }
     std::string key = alias.count(a) ? alias.at(a) : (a.rfind("--", 0) == 0 ? a.substr(2) : "");
@@ -204,6 +211,21 @@ BootOpts boot_options(const Options& o) {
     b.seed = (uint64_t)x;
   }
   return b;
+}
+
+// --lca T (classify, mapDirectly --then-classify; not in the reference): the confidence threshold of the LCA assignment, a decimal in [0.51, 1].
+// Off without the flag: nothing changes and no file appears.
+struct LcaOpts { bool on = false; double tau = 0; };
+LcaOpts lca_options(const Options& o) {
+  LcaOpts l;
+  if (!o.v.count("lca")) return l;
+  const std::string& v = o.v.at("lca");
+  const bool decimal = !v.empty() && v.size() <= 32 && v.find_first_not_of("0123456789.") == std::string::npos && v.find_first_of("0123456789") != std::string::npos &&
+                       std::count(v.begin(), v.end(), '.') <= 1;
+  const double x = decimal ? strtod(v.c_str(), nullptr) : 0;
+  if (!decimal || !(x >= 0.51 && x <= 1.0)) die("--lca takes a decimal threshold from 0.51 to 1, not '" + v + "'");
+  l.on = true; l.tau = x;
+  return l;
 }
 
 uint64_t file_size(const std::string& f) {                       // commonFunc.hpp:211-231
@@ -411,7 +433,8 @@ struct KeptLines {                                               // the mapping 
   std::vector<Part> parts; const std::vector<std::string>* cname = nullptr;
 };
 int classify_one(const std::vector<Dev>& devs, EmReduce reduce, const std::string& mapped, const std::string& db, size_t minReadsU,
-                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept = nullptr, BootOpts boot = BootOpts());
+                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept = nullptr, BootOpts boot = BootOpts(),
+                 LcaOpts lca = LcaOpts());
 
 // One run of mapDirectly / index / mapAgainstIndex.  The state every stage shares lives in the object; the stages are its methods, in the order run()
 // calls them: parameters -> devices -> reference (parsed, packed, uploaded) or stored index -> chunk plan -> placement of the chunk indexes
@@ -1429,7 +1452,7 @@ struct MapRun {
       const bool last = fi + 1 == prefixes.size();
       KeptLines kl; kl.cname = &cname;
       if (keep_lines && fi < kept.size()) for (const auto& d : kept[fi]) kl.parts.push_back(KeptLines::Part{d->text.data(), d->meta.data(), d->meta.size(), d->off.data(), d->lens.size()});
-      classify_one(devs, reduce, prefixes[fi], o.v.at("then-classify"), minReadsU, last ? leave : std::function<void()>(), nullptr, keep_lines ? &kl : nullptr, boot_options(o));
+      classify_one(devs, reduce, prefixes[fi], o.v.at("then-classify"), minReadsU, last ? leave : std::function<void()>(), nullptr, keep_lines ? &kl : nullptr, boot_options(o), lca_options(o));
       if (keep_lines && fi < kept.size()) kept[fi].clear();
       for (auto& d : devs) mm_comm_destroy(d.ctx);
       pc.lap("9 classify");
@@ -1759,6 +1782,63 @@ bool write_unknown_species(const std::string& fn, const std::string& db, const T
 //   Host  each rank's partial sums (mm_em_iterate) added on the host in rank order — what the all-reduce delivers —; several ranks
 //         may then share one device, which is how everything AROUND the collective is tested on a one-GPU box (--em-host-reduce)
 //   None  one rank, no communicator
+// --lca: the part of the taxonomy above the taxa of the mappings as mm_em_lca takes it — node 0 is taxon "1", parents before children (the nodes
+// sorted by depth, then ID) — and what the devices return: per read with a mapping its node and mass, per node the reads assigned to it
+struct LcaJob {
+  double tau = 0;
+  std::vector<std::string> id; std::vector<int32_t> parent, depth, taxon_node;
+  std::vector<int32_t> node; std::vector<double> mass; std::vector<int64_t> direct; std::mutex m;
+  LcaJob(const Taxonomy& T, const std::vector<std::string>& taxa, double tau_, size_t n_reads) : tau(tau_), node(n_reads, -1), mass(n_reads, 0.0) {
+    std::map<std::string, int32_t> dep{{"1", 0}};
+    std::function<int32_t(const std::string&)> depth_of = [&](const std::string& t) {
+      auto it = dep.find(t); if (it != dep.end()) return it->second;
+      auto n = T.T.find(t); if (n == T.T.end()) die("--lca: taxon ID " + t + " is not in the taxonomy");
+      if (n->second.parent == t) die("--lca: taxon ID " + t + " is its own parent in the taxonomy");
+      const int32_t d = depth_of(n->second.parent) + 1;
+      return dep[t] = d;
+    };
+    for (auto& t : taxa) depth_of(t);
+    std::vector<std::pair<int32_t, std::string>> order;
+    for (auto& kv : dep) order.emplace_back(kv.second, kv.first);
+    std::sort(order.begin(), order.end());
+    std::map<std::string, int32_t> index;
+    for (auto& e : order) { index[e.second] = (int32_t)id.size(); id.push_back(e.second); depth.push_back(e.first); }
+    parent.assign(id.size(), 0);
+    for (size_t v = 1; v < id.size(); ++v) parent[v] = index.at(T.T.at(id[v]).parent);
+    for (auto& t : taxa) taxon_node.push_back(index.at(t));
+    direct.assign(id.size(), 0);
+  }
+};
+
+// PREFIX.EM.kreport: Kraken's six-column report of the LCA assignments — percentage of all reads in the clade, clade reads, reads assigned to the node
+// itself, rank code, taxon ID, name indented by two blanks per depth.  First the unclassified reads (unmapped or too short) if there are any, then the
+// tree from taxon 1 depth first: clades without reads are left out, children by clade reads descending, then by taxon ID as text.
+void write_kreport(const std::string& fn, const Taxonomy& T, const LcaJob& J, size_t nTotal, size_t nUnclassified) {
+  static const std::map<std::string, const char*> code{{"superkingdom", "D"}, {"kingdom", "K"}, {"phylum", "P"}, {"class", "C"}, {"order", "O"}, {"family", "F"},
+                                                       {"genus", "G"}, {"species", "S"}};
+  const size_t N = J.id.size();
+  std::vector<int64_t> clade(J.direct);
+  std::vector<std::vector<int32_t>> kids(N);
+  for (size_t v = N - 1; v > 0; --v) { clade[(size_t)J.parent[v]] += clade[v]; kids[(size_t)J.parent[v]].push_back((int32_t)v); }
+  std::ofstream o(fn);
+  char num[96];
+  auto line = [&](int64_t c, int64_t d, const char* rank, const std::string& id, int depth, const std::string& name) {
+    snprintf(num, sizeof num, "%6.2f\t%lld\t%lld\t%s\t", 100.0 * (double)c / (double)nTotal, (long long)c, (long long)d, rank);
+    o << num << id << "\t" << std::string(2 * (size_t)depth, ' ') << name << "\n";
+  };
+  if (nUnclassified) line((int64_t)nUnclassified, (int64_t)nUnclassified, "U", "0", 0, "unclassified");
+  std::function<void(int32_t)> walk = [&](int32_t v) {
+    if (clade[(size_t)v] == 0) return;
+    const TaxNode& n = T.T.at(J.id[(size_t)v]);
+    auto c = code.find(n.rank);
+    line(clade[(size_t)v], J.direct[(size_t)v], v == 0 ? "R" : c != code.end() ? c->second : "-", J.id[(size_t)v], J.depth[(size_t)v], n.sci);
+    std::vector<int32_t>& k = kids[(size_t)v];
+    std::sort(k.begin(), k.end(), [&](int32_t a, int32_t b) { return clade[(size_t)a] != clade[(size_t)b] ? clade[(size_t)a] > clade[(size_t)b] : J.id[(size_t)a] < J.id[(size_t)b]; });
+    for (int32_t w : k) walk(w);
+  };
+  walk(0);
+}
+
 struct EmShard { size_t lo = 0, hi = 0, e0 = 0; std::vector<int64_t> soff; };   // reads [lo, hi); e0: first mapping of the shard; soff: shard-local offsets
 EmShard em_shard(const std::vector<int64_t>& off, size_t G, size_t d) {
   const size_t NR = off.size() - 1, base = NR / G, rem = NR % G;
@@ -1778,10 +1858,11 @@ void print_em_round(long long it, double ll, double ll_prev) {  // the per-round
   std::cout << "EM round " << it << std::endl << "\n\tLog likelihood: " << ll << std::endl;
   if (it > 0) std::cout << "\tImprovement: " << ll - ll_prev << "\n\tRelative   : " << ll / ll_prev << std::endl;
 }
-// f: start frequencies in, final frequencies out; post[mapping], best[read] (index into the whole mapping list) out
+// f: start frequencies in, final frequencies out; post[mapping], best[read] (index into the whole mapping list) out; lca (may be null): every
+// rank's reads assigned behind its posteriors, the ranks' direct counts added
 void run_em_sharded(const std::vector<Dev>& devs, EmReduce reduce, const std::vector<int64_t>& off, const std::vector<int32_t>& taxon,
                     const std::vector<double>& mapq, const std::vector<double>& inv, size_t NT, std::vector<double>& f,
-                    std::vector<double>& post, std::vector<int64_t>& best) {
+                    std::vector<double>& post, std::vector<int64_t>& best, LcaJob* lca = nullptr) {
   const size_t G = devs.size();
   if (reduce == EmReduce::None && G != 1) die("internal error: several EM ranks without a reduction");
   char comm_id[MM_COMM_ID_BYTES];
@@ -1836,6 +1917,12 @@ void run_em_sharded(const std::vector<Dev>& devs, EmReduce reduce, const std::ve
     std::vector<int64_t> bl(n);
     ck(ctx, mm_em_posteriors(em, fl.data(), post.data() + sh.e0, bl.data()), "posteriors");
     for (size_t i = 0; i < n; ++i) best[sh.lo + i] = bl[i] < 0 ? -1 : bl[i] + (int64_t)sh.e0;   // rank-local index -> index into the whole mapping list
+    if (lca) {
+      std::vector<int64_t> dl(lca->id.size());
+      ck(ctx, mm_em_lca(em, fl.data(), (int32_t)lca->id.size(), lca->parent.data(), lca->taxon_node.data(), lca->tau, lca->node.data() + sh.lo, lca->mass.data() + sh.lo, dl.data()), "lca");
+      std::lock_guard<std::mutex> lk(lca->m);
+      for (size_t v = 0; v < dl.size(); ++v) lca->direct[v] += dl[v];
+    }
     mm_em_destroy(em);
     bar.wait();                                                  // (every rank has read f_cur)
     if (d == 0) f = fl;
@@ -1874,6 +1961,7 @@ struct ClassifyRun {
   std::vector<double> f, post; std::vector<int64_t> best;
   BootOpts boot;                                                  // --bootstrap: the replicates' frequencies of the present taxa, [replicate][boot_pres]
   std::vector<int32_t> boot_pres; std::vector<double> boot_f;
+  LcaOpts lca; std::unique_ptr<LcaJob> lca_job;                   // --lca
 
   ClassifyRun(const std::vector<Dev>& devs_, EmReduce reduce_, const std::string& mapped_, const std::string& db_, size_t minReadsU_, const std::function<void()>& leave_now_,
               const std::function<void()>& need_devices_) : devs(devs_), reduce(reduce_), mapped(mapped_), db(db_), minReadsU(minReadsU_), leave_now(leave_now_), need_devices(need_devices_) {}
@@ -2079,7 +2167,21 @@ struct ClassifyRun {
     post.assign(taxon.size(), 0.0); best.assign(NR, 0);
     std::cout << "Starting EM..." << std::endl;
     if (need_devices) need_devices();
-    run_em_sharded(devs, reduce, off, taxon, mapq, inv, NT, f, post, best);
+    if (lca.on) lca_job = std::make_unique<LcaJob>(*tax, taxa, lca.tau, NR);
+    run_em_sharded(devs, reduce, off, taxon, mapq, inv, NT, f, post, best, lca_job.get());
+  }
+  // PREFIX.EM.reads2Taxon.lca: readID, taxon ID, rank and mass of the LCA assignment of every read with a mapping, in the order of reads2Taxon
+  void write_lca_reads(const std::string& fn) const {
+    const LcaJob& J = *lca_job;
+    std::string out; char num[48];
+    for (size_t r = 0; r < NRD; ++r) {
+      const MapLine& B = lines[(size_t)off[r]];
+      const std::string& id = J.id[(size_t)J.node[r]];
+      out.append(B.p, (size_t)((const char*)memchr(B.p, ' ', B.n) - B.p)); out += '\t'; out += id; out += '\t'; out += tax->T.at(id).rank;
+      snprintf(num, sizeof num, "\t%.6f\n", J.mass[r]); out += num;
+    }
+    std::ofstream o(fn);
+    o.write(out.data(), (std::streamsize)out.size());
   }
   // --bootstrap B: replicates 0..B-1 of the weighted EM (mm_em_bootstrap), started from the point estimate, dealt to the devices in contiguous
   // ranges; every device holds the whole EM problem and tiles its range to its free memory.  The result depends on neither.
@@ -2271,6 +2373,7 @@ struct ClassifyRun {
     write_wimp(mapped + ".EM.WIMP", T, fmap, readsPer, nTotal, nUnmapped, nTooShort);
     pc.lap("c6 WIMP");
     if (boot.B > 0) { write_bootstrap(mapped + ".EM.WIMP.bootstrap", T, fmap, readsPer); pc.lap("c6b WIMP bootstrap"); }
+    if (lca.on) { write_lca_reads(mapped + ".EM.reads2Taxon.lca"); write_kreport(mapped + ".EM.kreport", T, *lca_job, nTotal, nUnmapped + nTooShort); pc.lap("c6c LCA files"); }
     side_files.join();
     if (!unknown_written)
       std::cerr << "Warning: " << db << "/contigNstats_windowSize_1000.txt not found - " << mapped << ".EM.evidenceUnknownSpecies is not written." << std::endl;
@@ -2317,10 +2420,11 @@ struct ClassifyRun {
 };
 
 int classify_one(const std::vector<Dev>& devs, EmReduce reduce, const std::string& mapped, const std::string& db, size_t minReadsU,
-                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept, BootOpts boot) {
+                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept, BootOpts boot, LcaOpts lca) {
   ClassifyRun run(devs, reduce, mapped, db, minReadsU, leave_now, need_devices);
   run.kept = kept;
   run.boot = boot;
+  run.lca = lca;
   return run.run();
 }
 
@@ -2337,6 +2441,8 @@ int main(int argc, char** argv) {
   Options o = parse(argc, argv);
   const BootOpts boot = boot_options(o);                          // (validated before any work)
   if (boot.B && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--bootstrap needs classify or mapDirectly --then-classify");
+  const LcaOpts lca = lca_options(o);
+  if (lca.on && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--lca needs classify or mapDirectly --then-classify");
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
   if (mode == "mapDirectly" || mode == "index" || mode == "mapAgainstIndex") return map_mode(o, mode);
   if (mode == "classify") {
@@ -2367,8 +2473,8 @@ int main(int argc, char** argv) {
     const size_t minReadsU = o.v.count("minreads") ? std::stoull(o.v.at("minreads")) : 10000;   // parseCmdArgs.hpp:462-471
     const std::vector<std::string> files = split(o.v.at("mappings"), ",");
     for (size_t fi = 0; fi < files.size(); ++fi) {
-      if (fi + 1 == files.size()) classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, [&] { since("mappings file done"); }, need_devices, nullptr, boot);
-      else classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, nullptr, need_devices, nullptr, boot);
+      if (fi + 1 == files.size()) classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, [&] { since("mappings file done"); }, need_devices, nullptr, boot, lca);
+      else classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, nullptr, need_devices, nullptr, boot, lca);
       need_devices();
       for (auto& d : devs) mm_comm_destroy(d.ctx);
       since("mappings file done");

@@ -7,6 +7,7 @@
 #include "mm_stats.hpp"
 #include "mm_synth.hpp"
 #include "mm_hpc.hpp"
+#include "mm_lca.hpp"
 #include <chrono>
 #include <new>
 #include <rccl/rccl.h>
@@ -934,6 +935,11 @@ int mm_em_bootstrap(mm_em* em, const double* f_start, int32_t rep0, int32_t n_re
                     int max_iter, double* f_out, double* ll_out, int32_t* n_iter, int32_t* stopped) {
   if (!em || !f_start || n_rep <= 0 || rep0 < 0 || (int64_t)rep0 + n_rep - 1 > INT32_MAX || max_iter <= 0 || !f_out || !ll_out || !n_iter || !stopped) return MM_ERR_ARG;
   return guarded(em->ctx, [&] { MM_HIP(hipSetDevice(em->ctx->device)); mm::boot_run(em, f_start, rep0, n_rep, seed, weights, max_iter, f_out, ll_out, n_iter, stopped); });
+}
+int mm_em_lca(mm_em* em, const double* f, int32_t n_nodes, const int32_t* parent, const int32_t* taxon_node, double threshold,
+              int32_t* node_out, double* mass_out, int64_t* direct_out) {
+  if (!em || !f || !parent || !taxon_node || !node_out || n_nodes <= 0) return MM_ERR_ARG;
+  return guarded(em->ctx, [&] { MM_HIP(hipSetDevice(em->ctx->device)); mm::lca_run(em, f, n_nodes, parent, taxon_node, threshold, node_out, mass_out, direct_out); });
 }
 
 // ---- communicator -------------------------------------------------------------------------------------

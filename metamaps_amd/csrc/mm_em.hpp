@@ -37,6 +37,7 @@ void em_prepare(mm_em* E);
 int em_run(mm_em* E, const double* f0, int max_iter, double* f_out, double* ll_trace, int ll_cap, bool* stopped);
 int boot_run(mm_em* E, const double* f_start, int32_t rep0, int32_t n_rep, uint64_t seed, const uint8_t* weights, int max_iter,
              double* f_out, double* ll_out, int32_t* n_iter, int32_t* stopped);
+void em_estep(mm_em* E, const double* f);
 void em_posteriors(mm_em* E, const double* f, double* post, int64_t* best);
 void comm_unique_id(char* id);
 void comm_init(mm_ctx* ctx, const char* id, int rank, int nranks);

@@ -646,14 +646,19 @@ int em_run(mm_em* E, const double* f0, int max_iter, double* f_out, double* ll_t
   return n_iter;
 }
 
-void em_posteriors(mm_em* E, const double* f, double* post, int64_t* best) {
+// the E step alone (fEM.h:696-716), no sums: E->post = the posteriors of f, enqueued on the context's stream
+void em_estep(mm_em* E, const double* f) {
   hipStream_t st = E->ctx->stream;
-  E->f.upload(f, (size_t)E->n_taxa, st);                         // the E step alone (fEM.h:696-716): no sums
+  E->f.upload(f, (size_t)E->n_taxa, st);
   if (E->n_reads > 0) {
     em_estep_kernel<<<dim3((unsigned)ceil_div(E->n_reads, 128)), dim3(128), 0, st>>>(E->read_off.p, E->taxon.p, E->mapq.p, E->inv_nloc.p, E->f.p,
                                                                                  E->n_reads, E->post.p, E->ll_read.p);
     MM_KERNEL_CHECK();
   }
+}
+void em_posteriors(mm_em* E, const double* f, double* post, int64_t* best) {
+  hipStream_t st = E->ctx->stream;
+  em_estep(E, f);
   if (post) E->post.download(post, (size_t)E->n_entries, st);
   if (best && E->n_reads > 0) {
     DBuf<int64_t> b((size_t)E->n_reads);
