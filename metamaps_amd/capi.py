@@ -18,6 +18,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "metamaps_hip.h")
 
 COMM_ID_BYTES = 128
 MM_ERR_ARG = -1
+MM_ERR_LIMIT = -5
 MM_ERR_DATA = -8
 
 

@@ -64,30 +64,23 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_INDEX_PART_MAX", "2^31 - 2^24 entries", "test", "entries per partition of the hash sort (small values: the partitioned sort + merge on small inputs)"},
     {"MM_DUP_SAT", "65535", "test", "saturation value of the stored same-hash neighbour distances (small values: K5's scan fall-back)"},
     // ---- library: mapping (mm_map.hip, mm_seq.hip)
-    {"MM_SKETCH_BITONIC", "unset", "test", "K2 for sketches beyond the LDS radix sort: bitonic network instead of one segmented device sort"},
     {"MM_EAGER_TIEBREAK", "unset", "test", "resolve every duplicate-hash strand by the reference's std::sort order up front instead of only where a strand vote reads one"},
     {"MM_FORCE_AMB_REDO", "unset", "test", "every read with an unresolved strand goes through the redo path"},
     {"MM_NO_HIT_FILTER", "unset", "test", "K3 without the exact seed-hit pre-filter: every hit of every kept list reaches the sort (parity tests of the raw hit list)"},
     {"MM_NO_FUSED_FILTER", "unset", "test", "K3 as probe_kernel + two-pass hit_filter_kernel for every read (what reads that do not fit the fused kernel take)"},
-    {"MM_SF_ONESHOT", "unset", "test", "the fused seed filter as one read per workgroup instead of the resident streaming form"},
     {"MM_HF_STAGE_CAP", "auto", "test", "capacity of a read's survivor stage (tiny values: the overflow / re-filter path)"},
     {"MM_HF_WIDE_FROM", "13000", "tuning", "sketch size from which the two-pass filter counts in 32768 position slots instead of 8192"},
-    {"MM_HITS_BITONIC", "unset", "test", "K4 hit sort: bitonic / LDS radix per read only, never the segmented device sort"},
-    {"MM_SEGSORT_FROM", "auto", "tuning", "hits per read from which K4 uses the segmented device sort"},
+    {"MM_SEGSORT_MAX_KEYS", "2^32 - 1", "test", "keys per call of K4's segmented device sort (small values: the split on small inputs)"},
     {"MM_L1_SERIAL", "unset", "test", "K4's L1 merge loop as the literal one-thread-per-read loop (cross-check of the wavefront form)"},
     {"MM_L2_FULL", "unset", "test", "K5 evaluates every window (the literal slide) instead of the exact skip-ahead"},
-    {"MM_L2_NO_CODES", "unset", "test", "K5 classifies streamed entries again in every pass instead of parking their codes"},
-    {"MM_L2_NO_DENSE", "unset", "test", "no dense path for sketches >= 13000 hashes (they take the long-read classes of l2_kernel)"},
     {"MM_L2_DENSE_FROM", "13000", "tuning", "sketch size from which K5 runs as l2_codes_kernel + l2_dense_kernel"},
     {"MM_L2_DENSE_NO_STOP", "unset", "test", "dense path without its early stop (every window evaluated)"},
     {"MM_L2_NO_SMALL_GROUPS", "unset", "test", "groups of fewer than three candidates also run as four-wave workgroups (one launch instead of two)"},
     {"MM_L2_HOST_GROUPS", "unset", "test", "candidate groups formed on the host instead of by l2_group_kernel"},
     {"MM_L2_NO_GROUP_SORT", "unset", "test", "K5 workgroups in read order instead of the order of their candidates' positions"},
     {"MM_L2_GROUP_SORT_MIN", "2048", "tuning", "groups from which the launch order is sorted"},
-    {"MM_L2_XCD_ORDER", "unset", "tuning", "deal the position-sorted workgroup list out per XCD (measured: slower, DESIGN.md section 7)"},
     {"MM_L2_V1", "unset", "test", "K5's 10 kb class through l2_kernel (rank codes per entry) instead of the zone kernel l2z_kernel (mm_l2z.hpp): the cross-check and the A/B"},
     {"MM_L2_V1_LONG", "unset", "test", "the long-read classes (sketches of 3 073 .. 13 000 hashes) through l2_kernel, the 10 kb class through the zone kernel"},
-    {"MM_L2_SMALL_QLDS", "unset", "tuning", "zone kernel, two-wave workgroups (groups of one or two candidates): the sketch in LDS as in the four-wave workgroups instead of searched in global memory"},
     {"MM_L2_NO_FUSE", "unset", "test", "zone kernel without the band predicted from L1's seed-hit count: its masks always come from a second pass over the stream"},
     {"MM_L2_NO_RANGES", "unset", "test", "the zone kernel's waves search their candidates' index ranges themselves (until round 6) instead of taking them from l2_ranges_kernel (cross-check)"},
     {"MM_L2Z_FORCE_HANDBACK", "unset", "test", "the zone kernel hands every candidate that reaches its band loop to l2_kernel, as its pass-count guard does (the hand-back path against the default)"},
@@ -99,7 +92,6 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_L2_STOP", "0", "debug", "K5 leaves after phase n WITHOUT RESULTS (tools/l2_stop.py)"},
     {"MM_L2_PHASES", "unset", "debug", "K5 phase clocks into its counters (tools/l2_long_phases.py; the zone kernel has them in a build with -DL2Z_CLOCKS only)"},
     {"MM_MZ_DBG", "0", "debug", "K1 leaves after step n WITHOUT RESULTS (tools/stage_ms.py)"},
-    {"MM_SF_DBG", "0", "debug", "fused seed filter leaves after phase n WITHOUT RESULTS (tools/sf_dbg.py)"},
     {"MM_HF_DBG", "0", "debug", "two-pass filter leaves after phase n WITHOUT RESULTS"},
     {"MM_SF_PROF", "unset", "debug", "cycle counts per phase of the streaming seed filter on stderr"},
     // ---- library: EM and exchange (mm_post.hip, mm_api.hip)

@@ -1,32 +1,17 @@
 // K4 kernels — hit sort and L1 candidate scan (computeMap.hpp:346-386) — the K5 grouping / range kernels and the record compaction.
-// Included by mm_map.hip alone, behind mm_sketch.hpp (bitonic_sort_u64) and mm_l2.hpp.
+// Included by mm_map.hip alone, behind mm_l2.hpp.
 #pragma once
 #include <rocprim/rocprim.hpp>
 #include "mm_map.hpp"
 #include "mm_l2.hpp"
-#include "mm_sketch.hpp"
 
 namespace mm {
 
 // ---------------------------------------------------------------------------------------------------
 // K4a  sort the seed hits of each read by (contig, wpos)          computeMap.hpp:353
 // ---------------------------------------------------------------------------------------------------
-template <bool IN_LDS>
-__global__ void __launch_bounds__(256) sort_hits_kernel(uint64_t* __restrict__ hits, const uint64_t* __restrict__ read_hit_off,
-                                                        const int32_t* __restrict__ read_list, int npow2, uint64_t* __restrict__ gscratch) {
-  extern __shared__ __align__(16) uint64_t skeys[];
-  const int r = read_list[blockIdx.x];
-  const uint64_t o = read_hit_off[r];
-  const int n = (int)(read_hit_off[r + 1] - o);
-  uint64_t* a = IN_LDS ? skeys : gscratch + (size_t)blockIdx.x * npow2;
-  for (int i = threadIdx.x; i < npow2; i += 256) a[i] = i < n ? hits[o + i] : ~0ull;
-  __syncthreads();
-  bitonic_sort_u64(a, npow2);
-  for (int i = threadIdx.x; i < n; i += 256) hits[o + i] = a[i];
-}
-
-// The same with an LDS radix sort over the significant key bits (contig in the high word, position and strand below it):
-// fewer instructions than the bitonic network and no padding to a power of two.  256 * IPT >= hits of the longest read of the class.
+// Up to 4096 hits: an LDS radix sort over the significant key bits (contig in the high word, position and strand below it).
+// 256 * IPT >= hits of the longest read of the class.  Longer lists take the device's segmented radix sort (MapRun::sort_hits_segmented).
 template <int IPT>
 __global__ void __launch_bounds__(256) sort_hits_radix_kernel(uint64_t* __restrict__ hits, const uint64_t* __restrict__ read_hit_off,
                                                               const int32_t* __restrict__ read_list, int end_bit,
@@ -192,16 +177,11 @@ __global__ void __launch_bounds__(256) l2_group_keys_kernel(const int32_t* __res
   key[g] = (uint64_t)(uint32_t)cand[3 * (int64_t)c0] << 32 | (uint32_t)cand[3 * (int64_t)c0 + 1];
   val[g] = (uint64_t)(uint32_t)c0 << 32 | (uint32_t)gn[g];
 }
-// xcds = 1: the sorted order as it is (the default).  xcds = 8 (MM_L2_XCD_ORDER=1, a measurement switch): the sorted list dealt out so that XCD x — workgroup p
-// of a launch goes to XCD p mod 8, every XCD has its own L2 — works through the x-th eighth of it in order (sorted element i -> launch slot
-// (i mod n/8) * 8 + i / (n/8)), neighbours in position sharing an L2 and not only the Infinity Cache.  Measured: 15.5 ms against 15.2 for the plain
-// sorted order (16.0 unsorted) — eight fronts through the list leave each L2 a smaller share of the in-flight neighbours than one front does.
-__global__ void __launch_bounds__(256) l2_group_unpack_kernel(const uint64_t* __restrict__ val, int64_t n, int xcds, int32_t* __restrict__ g0, int32_t* __restrict__ gn) {
+// the sorted (first candidate, count) pairs back into the two group arrays
+__global__ void __launch_bounds__(256) l2_group_unpack_kernel(const uint64_t* __restrict__ val, int64_t n, int32_t* __restrict__ g0, int32_t* __restrict__ gn) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (g >= n) return;
-  const int64_t chunk = n / xcds;
-  const int64_t p = (xcds > 1 && g < chunk * xcds) ? (g % chunk) * xcds + g / chunk : g;
-  g0[p] = (int32_t)(val[g] >> 32); gn[p] = (int32_t)(uint32_t)val[g];
+  g0[g] = (int32_t)(val[g] >> 32); gn[g] = (int32_t)(uint32_t)val[g];
 }
 
 // The streamed range of every candidate (computeMap.hpp:466, :477) — first index entry at or beyond the candidate's start, first at or beyond its end + read length —

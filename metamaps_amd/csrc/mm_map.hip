@@ -32,21 +32,6 @@ namespace mm {
 // host orchestration
 // ---------------------------------------------------------------------------------------------------
 namespace {
-struct SizeClass { int npow2; std::vector<int32_t> reads; };
-
-// reads grouped by power-of-two capacity; entries beyond lds_cap elements use the global-memory variant
-std::vector<SizeClass> make_classes(const std::vector<int64_t>& count, int min_pow2) {
-  std::map<int, std::vector<int32_t>> m;
-  for (size_t r = 0; r < count.size(); ++r) {
-    if (count[r] <= 1) continue;                                // nothing to sort
-    m[std::max(min_pow2, pow2_at_least(count[r]))].push_back((int32_t)r);
-  }
-  std::vector<SizeClass> v;
-  for (auto& kv : m) v.push_back(SizeClass{kv.first, std::move(kv.second)});
-  return v;
-}
-constexpr int LDS_SORT_MAX = 16384;     // 128 KiB of 64-bit keys
-
 // MM_HOST_TIMING=1: wall time of the host sections between kernels (stderr)
 struct HostLap {
   const bool on = getenv("MM_HOST_TIMING") != nullptr; std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
@@ -121,7 +106,6 @@ struct MapSwitches {
   static int num(const char* e, int dflt) { return e ? atoi(e) : dflt; }
   static OptInt opt(const char* e) { return OptInt{e != nullptr, e ? atoi(e) : 0}; }
   // K2
-  const bool sketch_bitonic = on(getenv("MM_SKETCH_BITONIC"));   // reads beyond 16 384 minimizers through the bitonic network instead of the segmented device sort (cross-check)
   const bool eager_tiebreak = on(getenv("MM_EAGER_TIEBREAK"));   // tests that compare every sketch strand with the oracle
   // K3
   const bool use_filter = !is1(getenv("MM_NO_HIT_FILTER"));      // parity tests of the raw hit list
@@ -135,26 +119,21 @@ struct MapSwitches {
   const int hf_wide_from = hf_wide_env > 0 ? hf_wide_env : INT_MAX;
   const OptInt hf_stage_cap = opt(getenv("MM_HF_STAGE_CAP"));    // tests: a tiny capacity forces the re-filtering write path
   const int hf_dbg = num(getenv("MM_HF_DBG"), 0);
-  // default: the streaming form of the fused kernel (one resident workgroup per CU, look-ups of the next read under the LDS phases of this
-  // one); MM_SF_ONESHOT=1 / MM_SF_DBG: one workgroup per read, the form the phase timings of docs/history.md were taken on
-  const OptInt sf_dbg = opt(getenv("MM_SF_DBG"));
-  const bool sf_oneshot = on(getenv("MM_SF_ONESHOT")) || sf_dbg.set;
+  // the fused kernel streams: one resident workgroup per CU, look-ups of the next read under the LDS phases of this one
   const bool sf_prof = on(getenv("MM_SF_PROF"));                 // cycles per phase of the streaming kernel, printed per batch
   const OptInt sf_grid = opt(getenv("MM_SF_GRID"));              // (measurement aid: fewer resident workgroups = fewer CUs at work)
   // K4
-  const bool hits_bitonic = on(getenv("MM_HITS_BITONIC"));       // cross-check: the bitonic network for every read
-  // beyond 4096 hits the device's segmented radix sort is faster (50 kb reads: 7.9 -> 7.0 ms); below, the LDS network (10 kb: 2.2 vs 3.9 ms)
-  const int segsort_from = std::min(num(getenv("MM_SEGSORT_FROM"), 4096), LDS_SORT_MAX);
+  // beyond 4096 hits a read takes the device's segmented radix sort, at most max_keys - 1 keys per call (test hook, small values: the split on small inputs)
+  const OptInt segsort_max_env = opt(getenv("MM_SEGSORT_MAX_KEYS"));
+  const uint64_t segsort_max_keys = segsort_max_env.set ? (uint64_t)std::max(segsort_max_env.v, 1) : 0xffffffffull;
   const bool l1_serial = on(getenv("MM_L1_SERIAL"));             // cross-check switch: the one-thread-per-read loop
   const bool l2_no_fuse = on(getenv("MM_L2_NO_FUSE"));           // no band prediction from the L1 kernel
   // K5
   const bool l2_no_ranges = on(getenv("MM_L2_NO_RANGES"));       // the zone kernel's waves search their ranges themselves, as until round 6
   const bool l2_skip = !is1(getenv("MM_L2_FULL"));               // MM_L2_FULL=1, cross-check switch: evaluate every window
-  // sketches from this size on take the dense path (MM_L2_DENSE_FROM: experiments; MM_L2_NO_DENSE=1: the LDS classes / literal automaton,
-  // and sketches of >= 32768 hashes go to l2_giant_kernel, which has no "vote read an unresolved strand" feedback)
+  // sketches from this size on take the dense path (MM_L2_DENSE_FROM: experiments, tests)
   // (from ~58 kb reads on the streamed range of a candidate outgrows the 32 768-entry masks of the LDS classes' exact skip-ahead, which
   //  then evaluate every window with a rebuild per zone exit: 6 000 reads of 60-73 kb: 171 ms there, 83 ms here)
-  const bool use_dense = !on(getenv("MM_L2_NO_DENSE"));
   const int dense_from = num(getenv("MM_L2_DENSE_FROM"), 13000);
   const bool dense_no_stop = on(getenv("MM_L2_DENSE_NO_STOP"));
   const bool no_small_groups = on(getenv("MM_L2_NO_SMALL_GROUPS"));   // cross-check / timing switch
@@ -167,16 +146,13 @@ struct MapSwitches {
   const bool l2_no_slots = on(getenv("MM_L2_NO_SLOTS"));
   const OptInt l2_slots_env = opt(getenv("MM_L2_SLOTS"));
   const size_t l2_slots = l2_slots_env.set ? ((size_t)std::max(l2_slots_env.v, 1) + 7) / 8 * 8 : 0;
-  const bool l2_no_codes = on(getenv("MM_L2_NO_CODES"));         // cross-check switch
   // the zone kernels (mm_l2z.hpp, the default; MM_L2_V1=1: l2_kernel for every class): matched list + masks per slot
   const bool v2 = !on(getenv("MM_L2_V1"));
   const bool v2_long = v2 && !on(getenv("MM_L2_V1_LONG"));       // (MM_L2_V1_LONG=1: the long-read classes, sketches of 3 073 .. 13 000 hashes, through l2_kernel)
   const bool sort_groups = !on(getenv("MM_L2_NO_GROUP_SORT"));
   const OptInt group_sort_env = opt(getenv("MM_L2_GROUP_SORT_MIN"));   // (test hook: small batches take the sort too)
   const size_t group_sort_from = group_sort_env.set ? (size_t)std::max(group_sort_env.v, 1) : 2048;
-  const bool xcd_order = on(getenv("MM_L2_XCD_ORDER"));          // measurement switch of l2_group_unpack_kernel
   const bool one_stream = on(getenv("MM_L2_ONE_STREAM"));        // the two launches of the 10 kb class one behind the other as until round 5 (cross-check and A/B)
-  const bool small_qlds = on(getenv("MM_L2_SMALL_QLDS"));        // two-wave workgroups with the sketch in LDS
   // the debug word of the K5 kernels (counters[11])
   const OptInt l2_stop = opt(getenv("MM_L2_STOP"));              // timing aid: leave the kernel after phase n (results are then meaningless)
   const bool l2_phases = on(getenv("MM_L2_PHASES"));
@@ -248,8 +224,6 @@ struct MapRun {
   DBuf<unsigned int> ovf_n;
   DBuf<uint8_t> amb_used;
   uint8_t* amb_used_p = nullptr;
-  DBuf<int32_t> d_listG;
-  DBuf<uint32_t> giant_scratch;
   // K5, the skip classes only: released by l2_skip_classes where its block ended, in front of the compaction's allocations
   struct SkipClasses {
     DBuf<unsigned int> slot_flags;
@@ -270,7 +244,7 @@ struct MapRun {
 
   const std::vector<uint64_t>& hoff() const { return M->mz.h_off; }
   int min_mapped_len() const { return P.w + P.k + 1; }           // shorter reads are handed back by the skip kernels
-  bool dense_read(int64_t r, int sr) const { return sw.use_dense && sr >= sw.dense_from && sr < L2_SKETCH_LIMIT && M->read_len[(size_t)r] >= min_mapped_len(); }
+  bool dense_read(int64_t r, int sr) const { return sr >= sw.dense_from && sr < L2_SKETCH_LIMIT && M->read_len[(size_t)r] >= min_mapped_len(); }
   bool filtering() const { return sw.use_filter && n > 0; }
 
   void begin() {
@@ -363,26 +337,7 @@ struct MapRun {
       MM_HIP(mm::stream_sync(st));                          // RB.order is the source of the async upload
       hl("K2 sync (kernels)");
     }
-    std::vector<int64_t> cnt;                                     // longer lists (reads beyond ~73 kb)
-    if (any_big && !sw.sketch_bitonic) sketch_big_segmented();    // one segmented device sort (MM_SKETCH_BITONIC=1: the bitonic network below, cross-check)
-    else if (any_big) { cnt.assign((size_t)n, 0); for (int64_t r = 0; r < n; ++r) { const int64_t c = (int64_t)(hoff()[(size_t)r + 1] - hoff()[(size_t)r]); if (c > 16384) cnt[(size_t)r] = c; } }
-    for (auto& cls : make_classes(cnt, 256)) {
-      DBuf<int32_t> list(cls.reads.size());
-      list.upload(cls.reads.data(), cls.reads.size(), st);
-      if (cls.npow2 <= LDS_SORT_MAX) {
-        size_t lds = (size_t)cls.npow2 * 8;
-        set_lds((const void*)sketch_kernel<true>, lds);
-        sketch_kernel<true><<<dim3((unsigned)cls.reads.size()), dim3(256), lds, st>>>(M->mz.rec.p, M->mz.off.p, list.p, cls.npow2, nullptr,
-                                                                                     M->sk_hash.p, M->sk_strand.p, M->sk_n.p, M->amb.p);
-        MM_KERNEL_CHECK();
-      } else {
-        DBuf<uint64_t> scratch((size_t)cls.npow2 * cls.reads.size());
-        sketch_kernel<false><<<dim3((unsigned)cls.reads.size()), dim3(256), 0, st>>>(M->mz.rec.p, M->mz.off.p, list.p, cls.npow2, scratch.p,
-                                                                                    M->sk_hash.p, M->sk_strand.p, M->sk_n.p, M->amb.p);
-        MM_KERNEL_CHECK();
-      }
-      MM_HIP(mm::stream_sync(st));                          // cls.reads is the source of the async upload
-    }
+    if (any_big) sketch_big_segmented();                          // longer lists (reads beyond ~73 kb)
     T.end(t_sk);
   }
 
@@ -421,8 +376,8 @@ struct MapRun {
     if (M->at_stage) M->at_stage(M->at_stage_user, 1);
     h_amb = M->amb.to_host(st, (size_t)n);
     hl("post-K2 downloads");
-    // Reads whose sketch has >= 32768 hashes (~145 kb at w = 8) are beyond the LDS-resident window state of the K5 classes:
-    // their candidates go through l2_giant_kernel (state in global memory); counted for the caller's information only.
+    // Reads whose sketch has >= 32768 hashes (~145 kb at w = 8) are beyond the LDS-resident window state of the K5 classes
+    // whatever MM_L2_DENSE_FROM says: their candidates always take the dense path; counted for the caller's information only.
     int64_t giant = 0;
     for (int64_t r = 0; r < n; ++r) if (M->h_sk_n[(size_t)r] >= L2_SKETCH_LIMIT) ++giant;
     M->stats.n_reads_giant = giant;
@@ -434,11 +389,9 @@ struct MapRun {
   //      (slidingMap.hpp:247), so it is resolved here with the same library calls on the same input order.
   //      Entries whose strand depends on that are marked by K2 (bit 1 of the strand byte); the library sort is only run for
   //      reads whose strand vote actually read such an entry (found out by K6, amb_used[]), and those few candidates are
-  //      then redone.  Reads sorted by the bitonic kernel (> 16 384 minimizers) carry no marks and are resolved up front.
+  //      then redone.  MM_EAGER_TIEBREAK: every marked read is resolved up front.
   void tiebreak_lists() {
-    // (without the dense path sketches of >= 32768 hashes go to l2_giant_kernel, which has no feedback: resolved up front)
-    for (int64_t r = 0; r < n; ++r) if (h_amb[(size_t)r])
-      ((h_amb[(size_t)r] == 2 && !sw.eager_tiebreak && !(!sw.use_dense && M->h_sk_n[(size_t)r] >= L2_SKETCH_LIMIT)) ? lazy_reads : eager_reads).push_back(r);
+    for (int64_t r = 0; r < n; ++r) if (h_amb[(size_t)r]) (sw.eager_tiebreak ? eager_reads : lazy_reads).push_back(r);
     M->stats.n_ambiguous_sketch_reads = (int64_t)(eager_reads.size() + lazy_reads.size());
     hl("post-K2 amb lists");
     if (!eager_reads.empty()) amb_finish = start_tiebreak(eager_reads);
@@ -590,7 +543,7 @@ struct MapRun {
     M->stats.sum_hits_kept = total_hits;
     M->hits.alloc((size_t)std::max<int64_t>(total_hits, 1));
     if (total_hits > 0) {
-      if (sw.use_filter) launch_hit_filter<true>(M->read_hit_off.p, M->hits.p, sw.hits_bitonic ? 0 : 100, nullptr);
+      if (sw.use_filter) launch_hit_filter<true>(M->read_hit_off.p, M->hits.p, 100, nullptr);
       else {
         gather_hits_kernel<<<dim3((unsigned)n), dim3(256), 0, st>>>(IV, M->mz.off.p, M->sk_n.p, probe_cnt.p, probe_start.p, hit_off.p, M->hits.p);
         MM_KERNEL_CHECK();
@@ -625,22 +578,17 @@ struct MapRun {
     MM_HIP(mm::stream_sync(st));                            // h_stage_off is the source of the async upload
     hl("K3 stage_off loop + upload");
     if (!(sw.use_fused && n_fused > 0)) return;
-    const size_t lds1 = sizeof(SeedFilterLds), lds = sizeof(SeedFilterStreamLds);
-    MM_HIP(hipFuncSetAttribute((const void*)seed_filter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+    const size_t lds = sizeof(SeedFilterStreamLds);
     MM_HIP(hipFuncSetAttribute((const void*)seed_filter_stream_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     MM_HIP(hipFuncSetAttribute((const void*)seed_filter_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const bool oneshot = sw.sf_oneshot;
     DBuf<uint32_t> sf_ticket(1);
-    if (!oneshot) sf_ticket.zero(st);
+    sf_ticket.zero(st);
     DBuf<unsigned long long> sf_prof;
     if (sw.sf_prof) { sf_prof.alloc(16); sf_prof.zero(st); }
     int sf_grid = (int)std::min<int64_t>(n, std::max(ctx->cus, 1));
     if (sw.sf_grid.set) sf_grid = std::max(1, std::min(sf_grid, sw.sf_grid.v));
     const size_t t_sf = T.begin(&M->stats.ms_hit_filter);
-    if (oneshot)
-      seed_filter_kernel<<<dim3((unsigned)n), dim3(SF_THREADS), lds1, st>>>(IV, M->sk_hash.p, M->mz.off.p, M->sk_n.p, M->d_read_len.p, M->min_hits.p, surv.p,
-                                                                         stage.p, stage_off.p, need_old.p, raw_per_read.p, sw.sf_dbg.v);
-    else if (sf_prof.p)
+    if (sf_prof.p)
       seed_filter_stream_kernel<true><<<dim3((unsigned)sf_grid), dim3(SF_THREADS), lds, st>>>(IV, M->sk_hash.p, M->mz.off.p, M->sk_n.p, M->d_read_len.p, M->min_hits.p, surv.p, stage.p, stage_off.p,
                                                                          need_old.p, reinterpret_cast<const uint32_t*>(need_old.p), raw_per_read.p, (int)n, sf_ticket.p, sf_prof.p);
     else
@@ -648,7 +596,7 @@ struct MapRun {
                                                                          need_old.p, reinterpret_cast<const uint32_t*>(need_old.p), raw_per_read.p, (int)n, sf_ticket.p, nullptr);
     MM_KERNEL_CHECK();
     T.end(t_sf);
-    if (sf_prof.p && !oneshot) {
+    if (sf_prof.p) {
       auto h = sf_prof.to_host(st);
       const double tot = (double)std::accumulate(h.begin(), h.end(), 0ull);
       fprintf(stderr, "MM_SF_PROF share of cycles: zero+top %.3f | next head + resolve %.3f | scan %.3f | lists+count %.3f | window sums+alive+issue %.3f | phase 2 %.3f | survivors+end %.3f | total %.3g cycles over %d workgroups\n",
@@ -661,47 +609,13 @@ struct MapRun {
 
   int64_t hits_of(int64_t r) const { return (int64_t)(M->h_read_hit_off[(size_t)r + 1] - M->h_read_hit_off[(size_t)r]); }
 
-  // ---- K4a
+  // ---- K4a: up to 4096 hits per read the LDS radix sort, beyond that the device's segmented radix sort (50 kb reads: 7.9 -> 7.0 ms against a sort per read)
   void sort_hits() {
     if (total_hits > 0) {
       const size_t t_sh = T.begin(&M->stats.ms_sort_hits);
       hl("K4 hits alloc + emit launch");
-      std::vector<int64_t> hc;                                      // hit counts of the reads the LDS radix sort does not take
-      const bool seg_ok = total_hits < (int64_t)0xffffffffll && !sw.hits_bitonic;
-      std::vector<int32_t> seg_reads;                               // reads of every class handled by the segmented sort: one call for all
-      // up to 4096 hits per read: LDS radix sort, the reads grouped by the elements per thread they need
       int key_bits = 32; while (key_bits < 64 && ((int64_t)1 << (key_bits - 32)) < I->n_contigs) ++key_bits;
-      const bool use_radix = !sw.hits_bitonic;
-      bool any_left = !use_radix;
-      if (use_radix) any_left = sort_hits_radix(key_bits);
-      if (any_left) {                                              // the loops below only see the longer lists
-        hc.assign((size_t)n, 0);
-        for (int64_t r = 0; r < n; ++r) { const int64_t c = hits_of(r); if (!use_radix || c > 4096) hc[(size_t)r] = c; }
-      }
-      for (auto& cls : make_classes(hc, 256)) {
-        if (cls.npow2 > sw.segsort_from && seg_ok) { seg_reads.insert(seg_reads.end(), cls.reads.begin(), cls.reads.end()); continue; }
-        DBuf<int32_t> list(cls.reads.size());
-        list.upload(cls.reads.data(), cls.reads.size(), st);
-        if (cls.npow2 <= LDS_SORT_MAX) {
-          size_t lds = (size_t)cls.npow2 * 8;
-          set_lds((const void*)sort_hits_kernel<true>, lds);
-          sort_hits_kernel<true><<<dim3((unsigned)cls.reads.size()), dim3(256), lds, st>>>(M->hits.p, M->read_hit_off.p, list.p, cls.npow2, nullptr);
-          MM_KERNEL_CHECK();
-          MM_HIP(mm::stream_sync(st));
-        } else {
-          // (fallback) a few reads at a time through a global scratch buffer
-          const size_t per = (size_t)cls.npow2;
-          const size_t group = std::max<size_t>(1, std::min<size_t>(cls.reads.size(), ((size_t)1 << 28) / per));
-          DBuf<uint64_t> scratch(per * group);
-          for (size_t g0 = 0; g0 < cls.reads.size(); g0 += group) {
-            size_t g = std::min(group, cls.reads.size() - g0);
-            sort_hits_kernel<false><<<dim3((unsigned)g), dim3(256), 0, st>>>(M->hits.p, M->read_hit_off.p, list.p + g0, cls.npow2, scratch.p);
-            MM_KERNEL_CHECK();
-          }
-          MM_HIP(mm::stream_sync(st));
-        }
-      }
-      if (!seg_reads.empty()) sort_hits_segmented(seg_reads, key_bits);
+      if (sort_hits_radix(key_bits)) sort_hits_segmented(key_bits);
       T.end(t_sh);
     }
     hl("K4 launches + sync");
@@ -741,40 +655,53 @@ struct MapRun {
     return left_seen != 0;
   }
 
-  // large segments (reads beyond ~30 kb): the device's segmented radix sort over exactly these reads' ranges (the bitonic
-  // network through global memory took 0.5 s for a few hundred such reads).  When they are a minority of the batch their
-  // ranges are gathered into a compact buffer first, so that the scratch is twice their hits instead of a copy of all hits.
-  void sort_hits_segmented(std::vector<int32_t>& seg_reads, int key_bits) {
-    std::sort(seg_reads.begin(), seg_reads.end());
-    const size_t ns = seg_reads.size();
-    std::vector<uint64_t> hb(ns), he(ns), cb(ns), ce(ns);
-    uint64_t run = 0;
-    for (size_t i = 0; i < ns; ++i) {
-      const int32_t r = seg_reads[i];
-      hb[i] = M->h_read_hit_off[(size_t)r]; he[i] = M->h_read_hit_off[(size_t)r + 1];
-      cb[i] = run; run += he[i] - hb[i]; ce[i] = run;
+  // Reads of more than 4096 hits (beyond ~30 kb): the device's segmented radix sort over exactly these reads' ranges.  When they are a
+  // minority of the batch their ranges are gathered into a compact buffer first, so that the scratch is twice their hits instead of a
+  // copy of all hits.  The sort counts its keys in 32 bits: a batch with max_keys hits or more goes through it as consecutive runs of
+  // reads of fewer than max_keys hits each, every run through the compact buffer.
+  void sort_hits_segmented(int key_bits) {
+    const uint64_t max_keys = sw.segsort_max_keys;
+    std::vector<int32_t> seg_reads;                               // ascending
+    std::vector<uint64_t> hb, he, cb, ce;                         // per read: its range in hits[], and in the compact buffer of its run
+    std::vector<size_t> run_at{0};                                // first read of every run (+ end)
+    uint64_t in_run = 0, longest_run = 0;
+    for (int64_t r = 0; r < n; ++r) {
+      const uint64_t c = (uint64_t)hits_of(r);
+      if (c <= 4096) continue;
+      MM_REQUIRE(c < max_keys, MM_ERR_LIMIT, "one read has more seed hits than a segmented sort takes (2^32 - 1, or MM_SEGSORT_MAX_KEYS)");
+      if (in_run + c >= max_keys) { run_at.push_back(seg_reads.size()); in_run = 0; }
+      seg_reads.push_back((int32_t)r);
+      hb.push_back(M->h_read_hit_off[(size_t)r]); he.push_back(M->h_read_hit_off[(size_t)r + 1]);
+      cb.push_back(in_run); in_run += c; ce.push_back(in_run);
+      longest_run = std::max(longest_run, in_run);
     }
-    const bool compact = 2 * run <= (uint64_t)total_hits;
+    const size_t ns = seg_reads.size();
+    run_at.push_back(ns);
+    // one call over everything: in place where these reads are most of the batch
+    const bool compact = run_at.size() > 2 || 2 * longest_run <= (uint64_t)total_hits || (uint64_t)total_hits >= max_keys;
     DBuf<uint64_t> d_hb(ns), d_he(ns), d_cb(ns), d_ce(ns);
     d_hb.upload(hb.data(), ns, st); d_he.upload(he.data(), ns, st);
-    auto seg_sort = [&](uint64_t* in, uint64_t* out, uint64_t count, uint64_t* begins, uint64_t* ends) {
+    auto seg_sort = [&](uint64_t* in, uint64_t* out, uint64_t count, size_t nseg, uint64_t* begins, uint64_t* ends) {
       size_t tmp_bytes = 0;
-      MM_HIP(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, in, out, (unsigned int)count, (unsigned int)ns, begins, ends, 0, key_bits, st));
+      MM_HIP(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, in, out, (unsigned int)count, (unsigned int)nseg, begins, ends, 0, key_bits, st));
       DBuf<uint8_t> tmp(std::max<size_t>(tmp_bytes, 16));
-      MM_HIP(rocprim::segmented_radix_sort_keys((void*)tmp.p, tmp_bytes, in, out, (unsigned int)count, (unsigned int)ns, begins, ends, 0, key_bits, st));
+      MM_HIP(rocprim::segmented_radix_sort_keys((void*)tmp.p, tmp_bytes, in, out, (unsigned int)count, (unsigned int)nseg, begins, ends, 0, key_bits, st));
     };
     if (compact) {
       d_cb.upload(cb.data(), ns, st); d_ce.upload(ce.data(), ns, st);
-      DBuf<uint64_t> packed((size_t)run), sorted((size_t)run);
-      move_ranges_kernel<<<dim3((unsigned)ns), dim3(256), 0, st>>>(M->hits.p, d_hb.p, d_he.p, packed.p, d_cb.p);
-      MM_KERNEL_CHECK();
-      seg_sort(packed.p, sorted.p, run, d_cb.p, d_ce.p);
-      move_ranges_kernel<<<dim3((unsigned)ns), dim3(256), 0, st>>>(sorted.p, d_cb.p, d_ce.p, M->hits.p, d_hb.p);
-      MM_KERNEL_CHECK();
+      DBuf<uint64_t> packed((size_t)longest_run), sorted((size_t)longest_run);
+      for (size_t k = 0; k + 1 < run_at.size(); ++k) {             // (on one stream: a run's buffers are free again when the next run gathers into them)
+        const size_t i0 = run_at[k], nr = run_at[k + 1] - i0;
+        move_ranges_kernel<<<dim3((unsigned)nr), dim3(256), 0, st>>>(M->hits.p, d_hb.p + i0, d_he.p + i0, packed.p, d_cb.p + i0);
+        MM_KERNEL_CHECK();
+        seg_sort(packed.p, sorted.p, ce[i0 + nr - 1], nr, d_cb.p + i0, d_ce.p + i0);
+        move_ranges_kernel<<<dim3((unsigned)nr), dim3(256), 0, st>>>(sorted.p, d_cb.p + i0, d_ce.p + i0, M->hits.p, d_hb.p + i0);
+        MM_KERNEL_CHECK();
+      }
       MM_HIP(mm::stream_sync(st));
     } else {
       DBuf<uint64_t> sorted((size_t)total_hits);
-      seg_sort(M->hits.p, sorted.p, (uint64_t)total_hits, d_hb.p, d_he.p);
+      seg_sort(M->hits.p, sorted.p, (uint64_t)total_hits, ns, d_hb.p, d_he.p);
       move_ranges_kernel<<<dim3((unsigned)ns), dim3(256), 0, st>>>(sorted.p, d_hb.p, d_he.p, M->hits.p, d_hb.p);
       MM_KERNEL_CHECK();
       MM_HIP(mm::stream_sync(st));
@@ -853,7 +780,6 @@ struct MapRun {
   // per-entry code words of pass A: one slot range per wave of a launch (the launches of a batch run one after the other
   // on the stream, so they share the buffer); classes whose ranks do not fit 16 bits (C) search the sketch instead
   void* codes_for(size_t n_waves, int nwq) {
-    if (sw.l2_no_codes) return nullptr;
     return ctx->l2_codes.at_least(ctx->alloc, slots_of(n_waves, nwq) * (size_t)(64 * 64 * nwq) * (nwq == 2 ? sizeof(uint16_t) : sizeof(uint32_t)));
   }
   void* lists_for(size_t n_waves, int nwq) { return ctx->l2_codes.at_least(ctx->alloc, slots_of(n_waves, nwq) * l2z_list_bytes(nwq)); }
@@ -863,7 +789,7 @@ struct MapRun {
   void l2() {
     l2_setup();
     const size_t t_l2 = T.begin(&M->stats.ms_l2);
-    l2_giant();
+    l2_dense_beyond_limit();
     if (!sw.l2_skip) l2_full_slide(); else l2_skip_classes();
     l2_stats_kernel<<<dim3((unsigned)std::min<int64_t>(ceil_div(ncand, 256), 1024)), dim3(256), 0, st>>>(M->l2.p, ncand, counters.p);
     MM_KERNEL_CHECK();
@@ -887,13 +813,13 @@ struct MapRun {
     if (sw.dev_groups) {
       d_gA0.alloc((size_t)ncand); d_gAn.alloc((size_t)ncand); d_gS0.alloc((size_t)ncand); d_gSn.alloc((size_t)ncand);
       grp_ctr.zero(st);
-      l2_group_kernel<<<dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st>>>(M->cand_off.p, M->sk_n.p, M->d_read_len.p, n, min_mapped_len(), sw.use_dense ? sw.dense_from : INT_MAX,
+      l2_group_kernel<<<dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st>>>(M->cand_off.p, M->sk_n.p, M->d_read_len.p, n, min_mapped_len(), sw.dense_from,
                                                                             sw.no_small_groups ? 1 : 0, d_gA0.p, d_gAn.p, d_gS0.p, d_gSn.p, grp_ctr.p);
       MM_KERNEL_CHECK();
     }
     const size_t lds_wide = l2_lds_bytes<uint16_t>(M->smax, sw.l2_skip, 1, 8);
     // Sketches of >= 32768 hashes (L2_SKETCH_LIMIT): the rebuild's 1024-bucket histogram would be as coarse as the 64-rank pivot
-    // zone, and the window state of the full slide no longer fits LDS either -> l2_giant_kernel, state in global memory.
+    // zone, and the window state of the full slide no longer fits LDS either -> always the dense path, state in global memory.
     for (int64_t r = 0; r < n && M->stats.n_reads_giant > 0; ++r) {
       const int sr = M->h_sk_n[(size_t)r];
       if (sr < L2_SKETCH_LIMIT) continue;
@@ -949,19 +875,8 @@ struct MapRun {
     MM_HIP(mm::stream_sync(st));                          // host vectors above are upload sources; the buffers die with this scope
   }
 
-  // sketches of >= L2_SKETCH_LIMIT hashes: the dense path, or (MM_L2_NO_DENSE=1) l2_giant_kernel
-  void l2_giant() {
-    d_listG.alloc(listG.size());
-    if (!listG.empty() && sw.use_dense) l2_dense(listG, smG, amb_used_p);
-    else if (!listG.empty()) {
-      d_listG.upload(listG.data(), listG.size(), st);
-      const unsigned slots = (unsigned)std::min<size_t>(listG.size(), (size_t)ctx->cus * 8);
-      giant_scratch.alloc((size_t)slots * l2_giant_slot_words(smG));
-      l2_giant_kernel<<<dim3(slots), dim3(64), 0, st>>>(IV, M->cand.p, M->cand_read.p, M->sk_hash.p, M->sk_strand.p, M->mz.off.p, M->sk_n.p, M->d_read_len.p,
-                                                      M->accept_min.p, P.k, P.w, smG, M->l2.p, d_listG.p, (int)listG.size(), giant_scratch.p);
-      MM_KERNEL_CHECK();
-    }
-  }
+  // sketches of >= L2_SKETCH_LIMIT hashes
+  void l2_dense_beyond_limit() { l2_dense(listG, smG, amb_used_p); }
 
   // MM_L2_FULL=1: every window of every candidate below the giant class
   void l2_full_slide() {
@@ -1064,7 +979,7 @@ struct MapRun {
     MM_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key.p, key2.p, val.p, val2.p, ng, 12u, (unsigned)(32 + cbits), st));
     DBuf<uint8_t> tmp(std::max<size_t>(tmp_bytes, 1));
     MM_HIP(rocprim::radix_sort_pairs((void*)tmp.p, tmp_bytes, key.p, key2.p, val.p, val2.p, ng, 12u, (unsigned)(32 + cbits), st));
-    l2_group_unpack_kernel<<<dim3((unsigned)ceil_div((int64_t)ng, 256)), dim3(256), 0, st>>>(val2.p, (int64_t)ng, sw.xcd_order ? 8 : 1, g0.p, gn.p);
+    l2_group_unpack_kernel<<<dim3((unsigned)ceil_div((int64_t)ng, 256)), dim3(256), 0, st>>>(val2.p, (int64_t)ng, g0.p, gn.p);
     MM_KERNEL_CHECK();
   }
 
@@ -1093,9 +1008,8 @@ struct MapRun {
     if (sw.v2) {
       if (nA) launch_l2z<4, 2, true>(nA, st, smA, d_gA0.p, d_gAn.p, codes, masks, n_slots);
       // groups of one or two candidates: a two-wave workgroup with the sketch in LDS holds 20 KB for two waves (16 waves per CU); with the sketch left
-      // in global memory (the default; MM_L2_SMALL_QLDS=1: in LDS) it holds 10 KB and the CU its 24 waves
-      if (nS && sw.small_qlds) launch_l2z<2, 2, true>(nS, st_small, smA, d_gS0.p, d_gSn.p, codes, masks, n_slots);
-      else if (nS) launch_l2z<2, 2, false>(nS, st_small, smA, d_gS0.p, d_gSn.p, codes, masks, n_slots);
+      // in global memory it holds 10 KB and the CU its 24 waves
+      if (nS) launch_l2z<2, 2, false>(nS, st_small, smA, d_gS0.p, d_gSn.p, codes, masks, n_slots);
     } else {
       if (nA) launch_l2<true, uint8_t, 4, 2>(nA, st, smA, d_gA0.p, d_gAn.p, nullptr, amb_used_p, codes, masks, n_slots);
       if (nS) launch_l2<true, uint8_t, 2, 2>(nS, st_small, smA, d_gS0.p, d_gSn.p, nullptr, amb_used_p, codes, masks, n_slots);
@@ -1157,7 +1071,7 @@ struct MapRun {
     std::vector<int32_t> redo, redoL; int smR = 0, smRL = 0;   // redoL: reads of the dense path (long sketches) go through it again
     for (int64_t r : fix) {
       const int sr = M->h_sk_n[(size_t)r];
-      const bool dense_r = sw.use_dense && (sr >= L2_SKETCH_LIMIT || (sr >= sw.dense_from && M->read_len[(size_t)r] >= min_mapped_len()));
+      const bool dense_r = sr >= L2_SKETCH_LIMIT || (sr >= sw.dense_from && M->read_len[(size_t)r] >= min_mapped_len());
       (dense_r ? smRL : smR) = std::max(dense_r ? smRL : smR, sr);
       for (uint64_t c0 = M->h_cand_off[(size_t)r]; c0 < M->h_cand_off[(size_t)r + 1]; ++c0) (dense_r ? redoL : redo).push_back((int32_t)c0);
     }

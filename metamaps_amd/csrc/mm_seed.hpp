@@ -241,246 +241,21 @@ __global__ void __launch_bounds__(HitFilterCfg<SLOT_BITS>::THREADS) hit_filter_k
 // K3 + K3c fused for reads whose sketch and seed hits fit LDS (the 10 kb class): probe, count, filter in ONE launch.
 // hit_filter_kernel above reads every occurrence list twice (count pass, then the pass that tests each entry against the
 // surviving bins) and takes its list heads from arrays probe_kernel wrote to global memory.  Random requests, not bytes, are
-// what these kernels pay for (tools/ubench/randread), so here every list is requested ONCE: one workgroup of 1024 threads per
-// read keeps in LDS
-//     the list heads (first occurrence, count) of the sketch          phase 0: table lookups, 4 lanes per hash
-//     the 13-bit bin codes of every seed hit, 8 per 16-byte chunk      phase 1: one 16-byte load per lane, all lists of a lane
-//                                                                      group in flight together; bins counted as they arrive
+// what these kernels pay for (tools/ubench/randread), so here every list is requested ONCE: a workgroup of 1024 threads keeps
+// in LDS
+//     the list heads (first occurrence, count) of the sketch          phase 0: table look-ups, 4 lanes per hash
+//     the 13-bit bin codes of every seed hit, 8 per 16-byte piece      phase 1: one 16-byte load per piece, the pieces handed out
+//                                                                      to the lanes; bins counted as they arrive
 // and the second pass (phase 2) is bit tests over LDS; only survivors (a few per cent) touch occ[].  Results, staging and
 // overflow protocol are those of hit_filter_kernel<false>: survivors staged per read, surv_n[r] their number.  A read that does
-// not fit (sketch > SF_SMAX, more than SF_CHUNKS code chunks, a bin count that would not fit 16 bits, or a full stage) is
-// flagged in need_old[] and redone by probe_kernel + hit_filter_kernel, which skip every other read.
-// ---------------------------------------------------------------------------------------------------
-constexpr int SF_THREADS = 1024, SF_GROUPS = SF_THREADS / 4;
-constexpr int SF_LPG = 11;                                      // lists per lane group
-constexpr int SF_SMAX = SF_GROUPS * SF_LPG;                     // 2816 sketch hashes (reads up to ~12.5 kb at w = 8)
-constexpr int SF_CHUNKS = 6144;                                 // parked code chunks (8 codes, 16 bytes each): 49 152 seed hits incl. padding
-constexpr int SF_EXTRA = 1024;                                  // pieces of 32 entries beyond the first of a list (lists longer than 32 entries)
-struct SeedFilterLds {
-  uint32_t cnt16[HF_SLOTS / 2];                                 // two 16-bit bin counters per word
-  uint32_t good[HF_SLOTS / 32], alive[HF_SLOTS / 32];
-  uint32_t lstart8[SF_SMAX];                                   // first occurrence of every list / 8: lists start on 64-byte sectors = multiples of 8 entries (padded_counts_kernel), and an index of
-                                                                // more than 2^35 padded occurrences (275 GB of occ[] alone) does not fit a device — 11 KB of LDS that a minimizer workgroup of ANOTHER batch fits into beside this kernel
-  uint16_t lcnt[SF_SMAX];
-  uint16_t coff8[SF_SMAX + 8];                                  // first code chunk of every list (+ total)
-  uint32_t extra[SF_EXTRA];                                     // 32-entry pieces beyond a list's first: list << 11 | piece
-  uint32_t wsum[SF_THREADS / 64], wsum2[SF_THREADS / 64];
-  uint32_t cursor, fallback, total8, hraw, n_extra, tick[2], pad_[1];
-  ulonglong2 codes[SF_CHUNKS];
-};
-__global__ void __launch_bounds__(SF_THREADS) seed_filter_kernel(IndexView I, const uint32_t* __restrict__ sk_hash, const uint64_t* __restrict__ off,
-                                                                 const int32_t* __restrict__ sk_n, const int32_t* __restrict__ read_len,
-                                                                 const int32_t* __restrict__ min_hits, uint32_t* __restrict__ surv_n,
-                                                                 uint64_t* __restrict__ stage, const uint64_t* __restrict__ stage_off,
-                                                                 uint8_t* __restrict__ need_old, uint32_t* __restrict__ raw_hits, int dbg /* timing aid (MM_SF_DBG): leave after phase n */) {
-  extern __shared__ __align__(16) unsigned char sf_dyn[];
-  SeedFilterLds& L = *reinterpret_cast<SeedFilterLds*>(sf_dyn);
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int s = sk_n[r];
-  if (need_old[r]) return;                                       // not of this class (set by the host): the two-pass kernels take it
-  if (s <= 0) { if (tid == 0) { surv_n[r] = 0; raw_hits[r] = 0; } return; }
-  const uint64_t o = off[r];
-  const int grp = tid >> 2, sub = tid & 3, gshift = lane & ~3;
-  for (int i = tid; i < HF_SLOTS / 2; i += SF_THREADS) L.cnt16[i] = 0;
-  if (tid == 0) { L.cursor = 0; L.fallback = 0; }
-  __syncthreads();
-  // ---- phase 0: table lookups (probe_kernel's scheme: 4 lanes read the four 16-byte slots of the hash's home sector).  All hashes
-  // of a lane group are loaded first, then all home sectors requested, then resolved: two memory latencies for the whole sketch.
-  {
-    const ulonglong2* __restrict__ tab = reinterpret_cast<const ulonglong2*>(I.tab);
-    const uint64_t tslots = (uint64_t)I.tab_buckets << 2;
-    uint32_t hq[SF_LPG]; ulonglong2 vq[SF_LPG];
-#pragma unroll
-    for (int u = 0; u < SF_LPG; ++u) { const int i = grp + SF_GROUPS * u; hq[u] = i < s ? sk_hash[o + i] : 0u; }
-#pragma unroll
-    for (int u = 0; u < SF_LPG; ++u) vq[u] = tab[tab_slot(hq[u], I.tab_buckets) + sub];
-#pragma unroll
-    for (int u = 0; u < SF_LPG; ++u) {
-      const int i = grp + SF_GROUPS * u;
-      const uint32_t h = hq[u]; uint64_t slot = tab_slot(h, I.tab_buckets); ulonglong2 v = vq[u];
-      bool pending = i < s;
-      while (__any(pending)) {
-        const bool match = pending && v.x != 0 && (uint32_t)v.x == h, empty = pending && v.x == 0;
-        const uint32_t gm = (uint32_t)(__ballot(match) >> gshift) & 0xfu, ge = (uint32_t)(__ballot(empty) >> gshift) & 0xfu;
-        if (pending && (gm | ge)) {
-          if (match) {
-            const uint32_t cnt = (uint32_t)(v.x >> 32);
-            const bool keep = (uint64_t)cnt < (uint64_t)(int64_t)I.freq_threshold;   // computeMap.hpp:317
-            if (keep && cnt > 0xffffu) L.fallback = 1;              // (a list this long overflows the code area anyway)
-            L.lcnt[i] = keep ? (uint16_t)cnt : (uint16_t)0; L.lstart8[i] = keep ? (uint32_t)(v.y >> 3) : 0u;
-          } else if (!gm && sub == 0) { L.lcnt[i] = 0; L.lstart8[i] = 0u; }
-          pending = false;
-        }
-        if (pending) { slot = tab_next_sector(slot, tslots); v = tab[slot + sub]; }
-      }
-    }
-  }
-  __syncthreads();
-  if (dbg == 1) { if (tid == 0) { surv_n[r] = 0; raw_hits[r] = L.lcnt[0]; } return; }
-  // ---- code chunk offsets: exclusive scan of ceil(count / 8) over the lists (three lists per thread)
-  {
-    uint32_t c8[3], hr = 0, mine = 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { const int i = tid * 3 + j; const uint32_t c = i < s ? L.lcnt[i] : 0u; c8[j] = (c + 7) >> 3; mine += c8[j]; hr += c; }
-    const uint32_t inc = (uint32_t)wave_incl_scan((int)mine), inc2 = (uint32_t)wave_incl_scan((int)hr);
-    if (lane == 63) { L.wsum[wid] = inc; L.wsum2[wid] = inc2; }
-    __syncthreads();
-    uint32_t basew = 0, tot = 0, tot2 = 0;
-#pragma unroll
-    for (int q = 0; q < SF_THREADS / 64; ++q) { const uint32_t x = L.wsum[q]; if (q < wid) basew += x; tot += x; tot2 += L.wsum2[q]; }
-    uint32_t ex = basew + inc - mine;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { const int i = tid * 3 + j; if (i <= s) L.coff8[i] = (uint16_t)min(ex, 0xffffu); ex += c8[j]; }
-    if (tid == 0) { L.total8 = tot; L.hraw = tot2; L.n_extra = 0; if (tot > (uint32_t)SF_CHUNKS || tot2 > 65535u) L.fallback = 1; }
-  }
-  __syncthreads();
-  // 32-entry pieces beyond the first of a list get their own table, so that they are requested together, too
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int i = tid * 3 + j;
-    const uint32_t c = i < s ? (uint32_t)L.lcnt[i] : 0u;
-    if (c > 32) {
-      const uint32_t np = (c - 1) >> 5;                           // pieces 1 .. np
-      const uint32_t at = atomicAdd(&L.n_extra, np);
-      for (uint32_t p = 0; p < np; ++p) if (at + p < (uint32_t)SF_EXTRA) L.extra[at + p] = ((uint32_t)i << 11) | (p + 1);
-    }
-  }
-  __syncthreads();
-  if (L.n_extra > (uint32_t)SF_EXTRA) L.fallback = 1;             // (every thread writes the same value)
-  __syncthreads();
-  if (L.fallback) { if (tid == 0) { need_old[r] = 1; surv_n[r] = 0; raw_hits[r] = 0; } return; }
-  if (dbg == 2) { if (tid == 0) { surv_n[r] = 0; raw_hits[r] = L.hraw; } return; }
-  const uint32_t len = (uint32_t)max(read_len[r], 1);
-  const int nb = min((int)((len - 1) >> HF_BIN_SHIFT) + 2, HF_SLOTS);
-  int m = min_hits[r]; if (m < 1) m = 1;
-  // ---- phase 1: every list once.  A lane group owns lists grp, grp + 256, ...; the first 32 entries of all of them are requested
-  // before any is used (up to 11 x 16 bytes per lane in flight); the further pieces of long lists follow the same way.
-  {
-    auto code_of = [](const ulonglong2& v, int t) { return (uint32_t)((t < 4 ? v.x : v.y) >> (16 * (t & 3))) & 0xffffu; };
-    // a parked chunk: eight 16-bit slots, bin code in the low 13 bits; the 3 spare bits of the slots together hold the list the chunk
-    // belongs to (12 bits) and its number of valid entries - 1 (3 bits), so that the second pass needs no search
-    auto take = [&](uint32_t cc, uint32_t li, uint32_t chunk0, uint32_t j0, const ulonglong2& x) {   // lane `sub` holds entries j0 + 8 sub .. + 7 of list li (cc entries)
-      const uint32_t e0 = j0 + 8u * sub;
-      if (e0 >= cc) return;
-      const uint32_t nv = min(8u, cc - e0), meta = li | ((nv - 1u) << 12);
-      uint64_t w0 = 0, w1 = 0;
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const uint32_t code = code_of(x, t) & (uint32_t)(HF_SLOTS - 1);
-        if ((uint32_t)t < nv) atomicAdd(&L.cnt16[code >> 1], 1u << (16 * (code & 1)));
-        const uint64_t slot = code | (((meta >> (3 * t)) & 7u) << 13);
-        if (t < 4) w0 |= slot << (16 * t); else w1 |= slot << (16 * (t - 4));
-      }
-      L.codes[chunk0 + (e0 >> 3)] = make_ulonglong2(w0, w1);
-    };
-    {
-      uint32_t c[SF_LPG]; ulonglong2 v[SF_LPG];
-#pragma unroll
-      for (int u = 0; u < SF_LPG; ++u) {
-        const int i = grp + SF_GROUPS * u;
-        c[u] = i < s ? (uint32_t)L.lcnt[i] : 0u;
-        v[u] = make_ulonglong2(0, 0);
-        if (c[u]) v[u] = *reinterpret_cast<const ulonglong2*>(I.occ16 + ((uint64_t)L.lstart8[i] << 3) + min(8u * sub, (c[u] - 1) & ~7u));
-      }
-#pragma unroll
-      for (int u = 0; u < SF_LPG; ++u) { const int i = grp + SF_GROUPS * u; if (c[u]) take(c[u], (uint32_t)i, (uint32_t)L.coff8[i], 0u, v[u]); }
-    }
-    {
-      constexpr int EPG = SF_EXTRA / SF_GROUPS;                   // extra pieces per lane group
-      const uint32_t ne = L.n_extra;
-      uint32_t c[EPG], ch0[EPG], j0[EPG], li[EPG]; ulonglong2 v[EPG];
-#pragma unroll
-      for (int u = 0; u < EPG; ++u) {
-        const uint32_t k = (uint32_t)(grp + SF_GROUPS * u);
-        c[u] = 0; v[u] = make_ulonglong2(0, 0); ch0[u] = 0; j0[u] = 0; li[u] = 0;
-        if (k < ne) {
-          const uint32_t e = L.extra[k], i = e >> 11;
-          li[u] = i; c[u] = (uint32_t)L.lcnt[i]; ch0[u] = (uint32_t)L.coff8[i]; j0[u] = (e & 0x7ffu) << 5;
-          v[u] = *reinterpret_cast<const ulonglong2*>(I.occ16 + ((uint64_t)L.lstart8[i] << 3) + min(j0[u] + 8u * sub, (c[u] - 1) & ~7u));
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < EPG; ++u) if (c[u]) take(c[u], li[u], ch0[u], j0[u], v[u]);
-    }
-  }
-  __syncthreads();
-  if (dbg == 3) { if (tid == 0) { surv_n[r] = 0; raw_hits[r] = L.cnt16[0]; } return; }
-  {
-    // good[b]: the window of nb bins starting at b holds >= m hits (eight window starts per thread, one byte of the bit set);
-    // alive[b]: some good window contains b, i.e. good dilated by nb positions (hit_filter_kernel)
-    const uint16_t* cnt = reinterpret_cast<const uint16_t*>(L.cnt16);
-    const int b0 = tid * 8;
-    uint32_t sum = 0, bits = 0;
-    for (int i = 0; i < nb; ++i) sum += cnt[(b0 + i) & (HF_SLOTS - 1)];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      bits |= (sum >= (uint32_t)m ? 1u : 0u) << t;
-      sum += (uint32_t)cnt[(b0 + t + nb) & (HF_SLOTS - 1)] - (uint32_t)cnt[(b0 + t) & (HF_SLOTS - 1)];
-    }
-    reinterpret_cast<uint8_t*>(L.good)[tid] = (uint8_t)bits;
-  }
-  __syncthreads();
-  if (tid < HF_SLOTS / 32) {
-    uint32_t al = 0;
-    for (int j = 0; j < nb; ++j) {
-      const int wsh = j >> 5, bsh = j & 31;
-      const uint32_t g0 = L.good[(tid - wsh) & 255], g1 = L.good[(tid - wsh - 1) & 255];
-      al |= bsh ? (g0 << bsh) | (g1 >> (32 - bsh)) : g0;
-    }
-    L.alive[tid] = al;
-  }
-  __syncthreads();
-  if (dbg == 5) { if (tid == 0) { surv_n[r] = 0; raw_hits[r] = L.alive[0]; } return; }
-  // ---- phase 2: bit tests over the parked codes; a survivor is the occurrence (list start + position in the list)
-  const uint64_t stage_base = stage_off[r];
-  const uint32_t stage_cap = (uint32_t)(stage_off[r + 1] - stage_base);
-  uint64_t* const dst = stage + stage_base;
-  const uint32_t T8 = L.total8;
-  for (uint32_t q0 = 0; q0 < T8; q0 += SF_THREADS) {             // (wave-uniform trip count)
-    const uint32_t q = q0 + tid;
-    uint32_t mask = 0, meta = 0;
-    if (q < T8) {
-      const ulonglong2 x = L.codes[q];
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const uint32_t slot = (uint32_t)((t < 4 ? x.x : x.y) >> (16 * (t & 3))) & 0xffffu, code = slot & (uint32_t)(HF_SLOTS - 1);
-        meta |= (slot >> 13) << (3 * t);
-        mask |= ((L.alive[code >> 5] >> (code & 31)) & 1u) << t;
-      }
-      mask &= (2u << (meta >> 12 & 7u)) - 1u;                     // valid entries only
-    }
-    const int mine = __popc(mask);
-    const int incl = wave_incl_scan(mine);
-    const int total = __builtin_amdgcn_readlane(incl, 63);
-    if (total == 0) continue;
-    uint32_t base = 0;
-    if (lane == 63) base = atomicAdd(&L.cursor, (uint32_t)total);
-    base = (uint32_t)__builtin_amdgcn_readlane((int)base, 63);
-    uint32_t pos = base + (uint32_t)(incl - mine);
-    if (mask) {
-      const uint32_t li = meta & 0xfffu;
-      const uint64_t first = ((uint64_t)L.lstart8[li] << 3) + (uint64_t)(q - (uint32_t)L.coff8[li]) * 8u;
-      while (mask) {
-        const int t = __ffs(mask) - 1; mask &= mask - 1;
-        if (pos < stage_cap) dst[pos] = first + (uint32_t)t;
-        ++pos;
-      }
-    }
-  }
-  __syncthreads();
-  const uint32_t n_s = L.cursor;
-  if (dbg == 4) { if (tid == 0) { surv_n[r] = 0; raw_hits[r] = n_s; } return; }
-  if (n_s > stage_cap) { if (tid == 0) { need_old[r] = 1; surv_n[r] = 0; raw_hits[r] = 0; } return; }   // stage too small: the two-pass kernels redo the read
-  for (uint32_t j = tid; j < n_s; j += SF_THREADS) dst[j] = I.occ[dst[j]] & ~(uint64_t)(PW_DP | PW_DN);
-  if (tid == 0) { surv_n[r] = n_s; raw_hits[r] = L.hraw; }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// The same filter as a resident workgroup that streams through the reads (one workgroup per CU, reads handed out by a ticket
+// not fit (sketch > SF_SMAX, more than SF_CHUNKS code pieces, more than 65 535 seed hits, or a full stage) is flagged in
+// need_old[] and redone by probe_kernel + hit_filter_kernel, which skip every other read.
+//
+// The workgroup is resident and streams through the reads (one workgroup per CU, 158 KB of LDS; reads handed out by a ticket
 // counter) and overlaps itself: the table look-ups of read r + 1 are in flight — their answers wait in registers, 11 x 16 bytes per
-// lane, so the LDS layout is unchanged — while read r tests its parked codes against the surviving bins, writes its survivor slots
-// and fetches its survivors.  seed_filter_kernel above does a read's phases one after the other on a CU that holds one workgroup
-// (152 KB of LDS): VALU 40 %, LDS 19 %, waiting on memory 26 % of the cycles (profiles/r02_sq_counters.txt).
+// lane — while read r tests its parked codes against the surviving bins, writes its survivor slots and fetches its survivors.
+// (A read's phases one after the other, one workgroup per read: VALU 40 %, LDS 19 %, waiting on memory 26 % of the cycles,
+// profiles/r02_sq_counters.txt.)
 // What the form needs to work at all (each found in the ISA, docs/history.md section 4):
 //   * the barriers of the loop are LDS-only (s_waitcnt lgkmcnt(0) + s_barrier): nothing may drain the vector memory counter
 //     between the issue of the look-ups and their use;
@@ -490,8 +265,12 @@ __global__ void __launch_bounds__(SF_THREADS) seed_filter_kernel(IndexView I, co
 //     the loop they are spilled, and a reload from scratch is a vector memory operation;
 //   * look-ups that need a second probe (a full home sector) are re-issued together, after all eleven answers have been looked at:
 //     one more round trip per read instead of one per list of a lane group (2.4 ms of 15.6 in the first version).
-// Results are those of seed_filter_kernel read for read (tests: MM_SF_ONESHOT=1 runs the one-read-per-workgroup form).
+// Results are those of the two-pass kernels hit for hit (tests/test_gpu_parity.py).
 // ---------------------------------------------------------------------------------------------------
+constexpr int SF_THREADS = 1024, SF_GROUPS = SF_THREADS / 4;
+constexpr int SF_LPG = 11;                                      // lists per lane group
+constexpr int SF_SMAX = SF_GROUPS * SF_LPG;                     // 2816 sketch hashes (reads up to ~12.5 kb at w = 8)
+constexpr int SF_CHUNKS = 6144;                                 // parked code pieces (8 codes, 16 bytes each): 49 152 seed hits incl. padding
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // SF_STREAM_WAVES_PER_EU: the register budget of the streaming kernel.  4 (default) = all 512 registers of a SIMD's lane slot go to its four waves, 128
@@ -663,7 +442,7 @@ __global__ void __launch_bounds__(SF_THREADS) __attribute__((amdgpu_waves_per_eu
       }
       lds_barrier();
       lapp(1);
-      // ---- code chunk offsets (seed_filter_kernel)
+      // ---- code piece offsets
       {
         uint32_t c8[3], hr = 0, mine = 0;
 #pragma unroll
@@ -755,7 +534,7 @@ __global__ void __launch_bounds__(SF_THREADS) __attribute__((amdgpu_waves_per_eu
         issue_lookups();
         lapp(11);                                                  // (hashes arrived, look-ups issued)
         next_issued = true;
-        // ---- phase 2: bit tests over the parked codes (seed_filter_kernel, phase 2)
+        // ---- phase 2: bit tests over the parked codes
         uint64_t* const dst = stage + stage_base;
         uint16_t* const sv = reinterpret_cast<uint16_t*>(L.cnt);   // (2 x 8 256 slots: stage_cap = 1024 + 2 x sketch size <= 6 656, unless the test hook MM_HF_STAGE_CAP says otherwise)
         const uint32_t sv_cap = min(stage_cap, (uint32_t)(2 * (HF_SLOTS + HF_PAD_SLOTS)));

@@ -7,70 +7,10 @@
 namespace mm {
 
 // ---------------------------------------------------------------------------------------------------
-// workgroup bitonic sort of 64-bit keys (n a power of two), data in LDS or global memory
-// ---------------------------------------------------------------------------------------------------
-__device__ inline void bitonic_sort_u64(uint64_t* a, int n) {
-  for (int k = 2; k <= n; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < (n >> 1); t += blockDim.x) {
-        int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        int p = i | j;
-        uint64_t x = a[i], y = a[p];
-        bool up = (i & k) == 0;
-        if ((x > y) == up) { a[i] = y; a[p] = x; }
-      }
-      __syncthreads();
-    }
-  }
-}
-static inline int pow2_at_least(int64_t n) { int p = 1; while (p < n) p <<= 1; return p; }
-
-// ---------------------------------------------------------------------------------------------------
 // K2  sketch: one workgroup per read
 // ---------------------------------------------------------------------------------------------------
-template <bool IN_LDS>
-__global__ void __launch_bounds__(256) sketch_kernel(const Rec* __restrict__ rec, const uint64_t* __restrict__ off,
-                                                     const int32_t* __restrict__ read_list, int npow2, uint64_t* __restrict__ gscratch,
-                                                     uint32_t* __restrict__ sk_hash, uint8_t* __restrict__ sk_strand,
-                                                     int32_t* __restrict__ sk_n, uint8_t* __restrict__ amb) {
-  extern __shared__ __align__(16) uint64_t skeys[];
-  const int r = read_list[blockIdx.x];
-  const uint64_t o = off[r];
-  const int n = (int)(off[r + 1] - o);
-  uint64_t* a = IN_LDS ? skeys : gscratch + (size_t)blockIdx.x * npow2;
-  for (int i = threadIdx.x; i < npow2; i += 256) a[i] = i < n ? (((uint64_t)rec[o + i].hash << 32) | (uint32_t)i) : ~0ull;
-  __syncthreads();
-  bitonic_sort_u64(a, npow2);
-  __shared__ int s_amb;
-  if (threadIdx.x == 0) s_amb = 0;
-  __syncthreads();
-  uint64_t carry = 0;
-  for (int base = 0; base < n; base += 256) {
-    const int i = base + threadIdx.x;
-    bool first = false; uint32_t h = 0; uint32_t st = 0;
-    if (i < n) {
-      uint64_t key = a[i];
-      h = (uint32_t)(key >> 32);
-      st = rec[o + (uint32_t)key].pw & PW_STRAND;
-      if (i == 0) first = true;
-      else {
-        uint64_t pk = a[i - 1];
-        first = (uint32_t)(pk >> 32) != h;
-        if (!first && (rec[o + (uint32_t)pk].pw & PW_STRAND) != st) s_amb = 1;   // same hash, different strands
-      }
-    }
-    uint64_t tot;
-    uint64_t ex = block_excl_scan_u64(first ? 1 : 0, &tot);
-    if (first) { sk_hash[o + carry + ex] = h; sk_strand[o + carry + ex] = (uint8_t)st; }
-    carry += tot;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) { sk_n[r] = (int32_t)carry; amb[r] = (uint8_t)s_amb; }
-}
-
-// The same with an LDS radix sort (stable, so equal hashes stay in winnowing order exactly as with the 64-bit
-// (hash, index) keys of the bitonic version): ~4x fewer instructions than the bitonic network, which also pays for the
-// padding to a power of two.  IPT = elements per thread; 256 * IPT >= minimizers of the longest read of the class.
+// Up to 16 384 minimizers: an LDS radix sort by hash (stable, so equal hashes stay in winnowing order), then unique + strand.
+// IPT = elements per thread; 256 * IPT >= minimizers of the longest read of the class.
 template <int IPT>
 __global__ void __launch_bounds__(256) sketch_radix_kernel(const Rec* __restrict__ rec, const uint64_t* __restrict__ off,
                                                            const int32_t* __restrict__ read_list, uint32_t* __restrict__ sk_hash,
@@ -132,10 +72,8 @@ __global__ void __launch_bounds__(256) sketch_radix_kernel(const Rec* __restrict
 }
 
 // Sketches of more than 16 384 minimizers (reads beyond ~73 kb): (hash << 32 | winnowing index) keys of the listed reads back to back
-// in one buffer, one segmented device radix sort, then unique + strand per read from the sorted keys — what sketch_kernel does
-// with its bitonic network through global memory (48 ms per 4 000 reads of 75-140 kb) — plus sketch_radix_kernel's per-entry
-// ambiguity marks, so that these reads take the lazy strand tie-break too (the bitonic kernel flags the whole read and all its
-// minimizer records go to the host up front: a third of 4 000 such reads, 0.5 GB per batch).
+// in one buffer, one segmented device radix sort, then unique + strand per read from the sorted keys, with sketch_radix_kernel's
+// per-entry ambiguity marks, so that these reads take the lazy strand tie-break too.
 __global__ void __launch_bounds__(256) sketch_keys_kernel(const Rec* __restrict__ rec, const uint64_t* __restrict__ off, const int32_t* __restrict__ read_list,
                                                           const uint64_t* __restrict__ koff, uint64_t* __restrict__ keys) {
   const int r = read_list[blockIdx.x];

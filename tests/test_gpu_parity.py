@@ -444,27 +444,52 @@ def test_wide_slot_table_of_the_hit_filter_changes_no_result(ctx, monkeypatch):
     idx.close(); reads.close(); ref.close()
 
 
-def test_long_sketches_segmented_sort_equals_bitonic_network(ctx, monkeypatch):
-    """K2 for reads with more than 16 384 minimizers: segmented device radix sort + finish kernel against the bitonic network
-    (MM_SKETCH_BITONIC=1): identical sketches (hash, strand after the tie-break), sizes, ambiguity flags and records."""
-    ref = ctx.synth_reference(seed=55, n_species=8, strains_per_species=3, genome_len=600_000, strain_divergence=0.02, genus_divergence=0.08)
-    idx = ctx.index(ref, 16, 5)                                   # w = 5: a 60 kb read already has ~20 000 minimizers
-    reads, _ = ctx.synth_reads(ref, seed=59, n_reads=120, read_len=150_000, read_len_min=20_000, sub_rate=0.03, ins_rate=0.02, del_rate=0.03, frac_random=0.05, n_abundant=6)
+def test_long_sketches_segmented_sort_matches_oracle(ctx, oracle_lib, tmp_path, monkeypatch):
+    """K2 for reads with more than 16 384 minimizers (segmented device radix sort + finish kernel), in one batch with reads below that
+    (LDS radix sort; both write into the same arrays): sketch hashes and, with every duplicated-hash strand resolved, strands, sketch
+    sizes and records against the oracle, read by read."""
+    from metamaps_amd import synth
+    k, w = 16, 5                                                  # w = 5: a third of the positions are minimizers, 16 384 of them at ~49 kb
+    db = synth.make_db(str(tmp_path / "db"), n_genomes=4, genome_len=200_000, seed=23, contigs_per_genome=1)
+    rng = np.random.default_rng(29)
+    genomes = [c for c in db.contig_seqs if c.size >= 200_000]     # (not the six-base contig of the oddities)
+    reads = []
+    for L in (40_000, 44_000, 47_000, 52_000, 55_000, 58_000, 60_000, 62_000):
+        cs = genomes[len(reads) % len(genomes)]
+        st = int(rng.integers(0, cs.size - L + 1))
+        q = np.frombuffer(cs[st:st + L].tobytes().upper(), dtype=np.uint8).copy()
+        q[2000:2400] = synth.revcomp(q[1000:1400])                # an inverted repeat: the same hashes again on the other strand
+        if len(reads) % 2:
+            q = synth.revcomp(q)
+        reads.append(synth.mutate(rng, q, 0.03, 0.02, 0.03).tobytes())
     monkeypatch.setenv("MM_EAGER_TIEBREAK", "1")                  # every duplicated-hash strand resolved, so that whole sketches compare
-    res = {}
-    for mode in ("segmented", "bitonic"):
-        if mode == "bitonic": monkeypatch.setenv("MM_SKETCH_BITONIC", "1")
-        M = ctx.map_batch(idx, reads, 16, 5)
-        sk_off, sk_h, sk_s = M.debug_sketch()
-        off, rec = M.fetch()
-        res[mode] = (sk_off.copy(), sk_h.copy(), sk_s.copy(), off.copy(), rec.copy(), M.stats())
-        M.close()
-        monkeypatch.delenv("MM_SKETCH_BITONIC", raising=False)
-    for a, b in zip(res["segmented"][:5], res["bitonic"][:5]):
-        assert np.array_equal(a, b)
-    assert np.diff(res["segmented"][0]).max() > 16384 and res["segmented"][5]["n_mappings"] > 100
-    assert res["segmented"][5]["n_ambiguous_sketch_reads"] == res["bitonic"][5]["n_ambiguous_sketch_reads"]
-    idx.close(); reads.close(); ref.close()
+    names, contigs = _read_fasta(db.fasta)
+    S, R = ctx.seqset(contigs), ctx.seqset(reads)
+    idx = ctx.index(S, k, w)
+    oi = oracle_lib.index(db.fasta, k, w)
+    M = ctx.map_batch(idx, R, k, w, pi=80.0, min_read_len=1000)
+    st = M.stats()
+    mz_off = ctx.minimizers(R, k, w)[0]
+    sk_off, sk_h, sk_s = M.debug_sketch()
+    rec_off, rec = M.fetch()
+    n_mz = np.diff(mz_off)
+    print("minimizers per read", n_mz.tolist(), "ambiguous reads", st["n_ambiguous_sketch_reads"], "mappings", st["n_mappings"])
+    assert n_mz.max() > 16384 and n_mz.min() <= 16384            # both K2 forms ran
+    assert st["n_ambiguous_sketch_reads"] > 0
+    n_mapped = 0
+    for r, q in enumerate(reads):
+        o = oi.map_read(q, 80.0)
+        a, b = int(sk_off[r]), int(sk_off[r + 1])
+        assert b - a == len(o["sketch_hash"]), r
+        assert np.array_equal(sk_h[a:b], o["sketch_hash"]) and np.array_equal(sk_s[a:b], o["sketch_strand"]), r
+        m = o["map"]
+        rr = rec[int(rec_off[r]):int(rec_off[r + 1])]
+        assert len(rr) == len(m), r
+        assert np.array_equal(rr["ref_contig"], m[:, 0]) and np.array_equal(rr["ref_start"], m[:, 1]), r
+        assert np.array_equal(rr["shared"], m[:, 3]) and np.array_equal(rr["sketch"], m[:, 4]) and np.array_equal(rr["strand"], m[:, 5]), r
+        n_mapped += len(m) > 0
+    assert n_mapped >= 6
+    oi.close(); M.close(); idx.close(); R.close(); S.close()
 
 
 def test_hit_prefilter_keeps_candidates_identical(ctx, monkeypatch):
@@ -650,6 +675,64 @@ def test_l2_long_read_classes_equal_full_slide(ctx, monkeypatch, read_len, n_rea
         M.close()
         monkeypatch.delenv("MM_L2_DENSE_NO_STOP")
     idx.close(); reads.close(); ref.close()
+
+
+def test_hit_sort_split_into_several_segmented_calls(ctx, monkeypatch):
+    """K4 for reads of more than 4096 kept hits: the segmented device sort counts its keys in 32 bits, so a batch beyond that goes through it
+    as consecutive runs of reads (MM_SEGSORT_MAX_KEYS: the split on a small batch).  Sorted hits, candidates and records are those of the
+    one call; a single read with as many hits as a call takes is MM_ERR_LIMIT."""
+    from metamaps_amd import capi
+    ref = ctx.synth_reference(seed=15, n_species=12, strains_per_species=4, genome_len=600_000, strain_divergence=0.02, genus_divergence=0.08)
+    kw = dict(sub_rate=0.02, ins_rate=0.01, del_rate=0.02, frac_random=0.0, n_abundant=10)   # 95 % identity: 0.44 of a read's 16-mers are the reference's
+    long_set, _ = ctx.synth_reads(ref, seed=19, n_reads=8, read_len=60_000, **kw)           # ~13 000 hashes each, 6 000 or more of them seed hits per strain
+    short_set, _ = ctx.synth_reads(ref, seed=21, n_reads=24, read_len=3_000, **kw)
+    def host_reads(seqs):
+        buf, ln = seqs.fetch_range(0, seqs.count)
+        at = np.concatenate(([0], np.cumsum(ln)))
+        return [buf[at[i]:at[i + 1]].tobytes() for i in range(seqs.count)]
+
+    longs, shorts = host_reads(long_set), host_reads(short_set)
+    batch = []
+    for i, q in enumerate(longs):                                 # short, short, short, long, ...
+        batch += shorts[3 * i:3 * i + 3] + [q]
+    long_set.close(); short_set.close()
+    R = ctx.seqset(batch)
+    idx = ctx.index(ref, 16, 8)
+
+    def run():
+        M = ctx.map_batch(idx, R, 16, 8)
+        got = dict(hits=M.debug_hits(), cand=M.debug_candidates(), rec=M.fetch())
+        M.close()
+        return got
+
+    one = run()
+    per_read = np.diff(one["hits"][0])
+    seg = per_read[per_read > 4096]
+    print("kept hits per read:", per_read.tolist())
+    assert len(seg) >= 6 and (per_read <= 4096).sum() >= 20
+    max_keys = 2 * int(seg.max()) + 1                             # two of these reads fit one call, all of them do not
+    n_calls, in_run = 1, 0
+    for c in seg.tolist():
+        if in_run + c >= max_keys: n_calls += 1; in_run = 0
+        in_run += c
+    assert n_calls >= 3
+    monkeypatch.setenv("MM_SEGSORT_MAX_KEYS", str(max_keys))
+    split = run()
+    for x, y in zip(one["hits"], split["hits"]):
+        assert np.array_equal(x, y)
+    assert np.array_equal(one["cand"][0], split["cand"][0]) and np.array_equal(one["cand"][1], split["cand"][1])
+    assert np.array_equal(one["rec"][0], split["rec"][0]) and one["rec"][1].tobytes() == split["rec"][1].tobytes()
+    off, hc, hw = split["hits"]
+    key = hc.astype(np.int64) << 32 | hw.astype(np.int64)
+    for r in range(len(batch)):
+        assert np.all(np.diff(key[off[r]:off[r + 1]]) >= 0), r
+    assert len(one["rec"][1]) > 8
+    monkeypatch.setenv("MM_SEGSORT_MAX_KEYS", str(int(seg.max())))   # one read alone has as many
+    with pytest.raises(capi.MMError) as e:
+        run()
+    assert e.value.status == capi.MM_ERR_LIMIT
+    monkeypatch.delenv("MM_SEGSORT_MAX_KEYS")
+    idx.close(); R.close(); ref.close()
 
 
 def test_mixed_read_lengths_one_batch_equal_full_slide(ctx, monkeypatch):
@@ -867,9 +950,9 @@ def test_host_statistics_match_committed_golden():
             assert b.value < 80.0, (s, v)
 
 
-def test_streaming_seed_filter_equals_one_read_per_workgroup(ctx, dense, monkeypatch):
+def test_streaming_seed_filter_equals_two_pass_filter(ctx, dense, monkeypatch):
     """K3: the resident-workgroup form (default: reads handed out by a ticket, the next read's look-ups in flight under this read's
-    LDS phases) against the one-workgroup-per-read form (MM_SF_ONESHOT=1) and against the two-pass kernels (MM_NO_FUSED_FILTER=1), at
+    LDS phases) against the two-pass kernels (MM_NO_FUSED_FILTER=1, which test_mapping_at_bench_hit_density_matches_oracle holds against the oracle), at
     bench hit density: the filtered seed hits, hit for hit, the raw hit counts, candidates and records; with a batch smaller than
     the grid, with reads of other classes in between (skipped by this kernel) and with a stage too small for some reads (fallback)"""
     names, contigs = _read_fasta(dense["db"].fasta)
@@ -888,7 +971,7 @@ def test_streaming_seed_filter_equals_one_read_per_workgroup(ctx, dense, monkeyp
     for batch, cap in ((mixed, None), (reads[:7], None), (mixed, "40")):
         R = ctx.seqset(batch)
         got = {}
-        for mode, env in (("stream", {}), ("oneshot", {"MM_SF_ONESHOT": "1"}), ("twopass", {"MM_NO_FUSED_FILTER": "1"})):
+        for mode, env in (("stream", {}), ("twopass", {"MM_NO_FUSED_FILTER": "1"})):
             for k_, v_ in env.items():
                 monkeypatch.setenv(k_, v_)
             if cap:
@@ -900,7 +983,7 @@ def test_streaming_seed_filter_equals_one_read_per_workgroup(ctx, dense, monkeyp
                 monkeypatch.delenv(k_, raising=False)
         a = got["stream"]
         assert a["st"]["sum_hits"] > 100_000 and a["st"]["sum_hits_kept"] > 0
-        for other in ("oneshot", "twopass"):
+        for other in ("twopass",):
             b = got[other]
             assert a["st"]["sum_hits"] == b["st"]["sum_hits"] and a["st"]["sum_hits_kept"] == b["st"]["sum_hits_kept"], other
             for x, y in zip(a["hits"], b["hits"]):
