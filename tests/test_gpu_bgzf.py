@@ -2,6 +2,7 @@
 a batch with corrupt blocks among good ones gets every status right and leaves the bad blocks' output untouched; and the CLI writes the
 same files for bgzip FASTQ as for the plain FASTQ, and for BAM under device inflate as under host inflate (MM_BGZF_HOST_INFLATE=1), with
 the host path's error for a corrupt block.  Fixtures: tests/bgzf_corpus.py and tests/bam_writer.py."""
+import gzip
 import os
 import random
 import struct
@@ -107,6 +108,13 @@ def _bgzip(src, dst, block_bytes):
     return dst
 
 
+def _gzip(src, dst):
+    """what gzip writes for src: one DEFLATE stream, no BGZF blocks"""
+    with gzip.open(dst, "wb") as f:
+        f.write(open(src, "rb").read())
+    return dst
+
+
 def _fastq_records(path):
     out = []
     with open(path) as f:
@@ -135,7 +143,7 @@ def data(tmp_path_factory):
     bw.write_bam(str(d / "r1.bam"), recs, block_bytes=20000)
     return {"db": db, "dir": d, "r1": r1, "r2": r2, "fa": fa, "bam": str(d / "r1.bam"),
             "r1z": _bgzip(r1, str(d / "r1z.fq.gz"), 20000), "r2z": _bgzip(r2, str(d / "r2z.fq.gz"), 777),
-            "faz": _bgzip(fa, str(d / "r3z.fa.gz"), 333)}
+            "faz": _bgzip(fa, str(d / "r3z.fa.gz"), 333), "r1g": _gzip(r1, str(d / "r1g.fq.gz"))}
 
 
 def _map(args, env=None):
@@ -183,14 +191,14 @@ def test_cli_map_against_index_bgzip_equals_plain(data, tmp_path):
 
 @pytest.mark.parametrize("devices", [None, "0,0"])
 def test_cli_then_classify_mixed_list(data, tmp_path, devices):
-    """a comma list of bgzip FASTQ, BAM and plain FASTQ, mapped and classified in one process, writes the files of the all-plain list; and
-    the same list under host inflate writes them too"""
+    """a comma list of bgzip FASTQ, BAM, plain FASTA and plain gzip FASTQ — every kind of query file the reader knows, each ending its file for the
+    writer —, mapped and classified in one process, writes the files of the all-plain list; and the same list under host inflate writes them too"""
     db = data["db"]
     dev = ["--devices", devices, "--em-host-reduce"] if devices else []
     common = ["--then-classify", db.dir, "--minreads", "3"] + dev
-    plain = [data["r2"], data["r1"], data["fa"]]
-    mixed = [data["r2z"], data["bam"], data["fa"]]
-    outs = {k: [str(tmp_path / f"{k}_{i}") for i in range(3)] for k in ("plain", "dev", "host")}
+    plain = [data["r2"], data["r1"], data["fa"], data["r1"]]
+    mixed = [data["r2z"], data["bam"], data["fa"], data["r1g"]]
+    outs = {k: [str(tmp_path / f"{k}_{i}") for i in range(4)] for k in ("plain", "dev", "host")}
     _map(["mapDirectly", "--all", "-r", db.fasta, "-q", ",".join(plain), "-o", ",".join(outs["plain"])] + common)
     _map(["mapDirectly", "--all", "-r", db.fasta, "-q", ",".join(mixed), "-o", ",".join(outs["dev"])] + common, dict(DEV, MM_CLI_BATCH_READS="64"))
     _map(["mapDirectly", "--all", "-r", db.fasta, "-q", ",".join(mixed), "-o", ",".join(outs["host"])] + common, HOST)

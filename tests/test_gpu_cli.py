@@ -667,7 +667,7 @@ def test_cli_device_cap_decides_placement(tmp_path):
     rd = synth.make_reads(db, str(tmp_path / "r.fq"), n_reads=3000, read_len=6000, seed=3)
     ref_bases = n_genomes * 10_000_000
     base = ["mapDirectly", "--all", "-r", db.fasta, "-q", rd["path"], "--maxmemory-bytes", str(int(ref_bases * 3)), "--workers-per-gpu", "1"]
-    # the CLI's size model (index_bytes, metamaps_main.cpp): 22 GB for the whole 1 Gbp reference (at this size nearly every hash is a list of one,
+    # the CLI's size model (index_bytes, host/map_run.hpp): 22 GB for the whole 1 Gbp reference (at this size nearly every hash is a list of one,
     # padded to a 64-byte sector), ~4 GB for each of the ~6 chunks of --maxmemory: 25 GB together do not fit 0.8 x 20 GiB, two per device do
     cap = int(os.environ.get("MM_TEST_DEVICE_CAP", 20 << 30))
     env = dict(os.environ, MM_DEVICE_BYTES_CAP=str(cap))
