@@ -29,7 +29,7 @@ extern "C" {
                             * 4: mm_sketch_batch, mm_ctx_release_cached, mm_index_dup_neighbours;
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
-                            *    mm_em_lca (additions to 6) */
+                            *    mm_em_lca, mm_gene_overlap (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -413,6 +413,23 @@ int mm_em_bootstrap(mm_em* em, const double* f_start, int32_t rep0, int32_t n_re
  * MM_ERR_ARG: threshold outside [0.51, 1], a parent[] that is not in that order, a taxon_node outside the tree. */
 int mm_em_lca(mm_em* em, const double* f, int32_t n_nodes, const int32_t* parent, const int32_t* taxon_node, double threshold,
               int32_t* node_out, double* mass_out, int64_t* direct_out);
+
+/* ---- gene-level analysis (classify --genes; the reference's geneLevelAnalysis.pl) ---------------------- */
+/* Which annotated genes do mappings overlap.  Genes: those of contig c are [contig_gene_off[c], contig_gene_off[c+1]), sorted by Start within
+ * the contig, Start and Stop inclusive; gene_group[j] in [0, n_groups): genes of one group are pooled.  group_feat_off[n_groups+1] /
+ * group_feat: the feature ids (in [0, n_feats)) a group's protein carries.  Mapping (c, s, e) overlaps gene (Start, Stop) of contig c iff
+ * Start < e && s <= Stop.  group_reads[g]: overlaps of the group's genes (a mapping that overlaps two of them counts twice);
+ * group_median[g]: the element of 0-based rank (n-1)/2 of the identities of those overlaps in ascending order, NaN where group_reads is 0;
+ * feat_reads[f] (may be NULL): mappings that overlap at least one gene whose group carries f; maps_on_annotated (may be NULL): mappings on
+ * contigs with at least one gene.  Zero genes or zero mappings are valid.  MM_ERR_ARG: offsets that do not start at 0 and ascend, genes not
+ * sorted by Start within a contig, Stop < Start, a gene_group, feature id or map_contig out of range, map_stop < map_start, a negative or
+ * NaN identity.  MM_ERR_LIMIT: 2^32 mappings or more.  The device buffers are tiled to MM_GENE_PAIR_BUDGET pairs; no result depends on it. */
+int mm_gene_overlap(mm_ctx* ctx, int32_t n_contigs, const int64_t* contig_gene_off, const int32_t* gene_start, const int32_t* gene_stop,
+                    const int32_t* gene_group, int32_t n_groups,
+                    const int64_t* group_feat_off /* [n_groups+1] */, const int32_t* group_feat, int32_t n_feats,
+                    int64_t n_maps, const int32_t* map_contig, const int32_t* map_start, const int32_t* map_stop, const double* map_ident,
+                    int64_t* group_reads /* [n_groups] */, double* group_median /* [n_groups], NaN where group_reads is 0 */,
+                    int64_t* feat_reads /* [n_feats], may be NULL */, int64_t* maps_on_annotated /* may be NULL */);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------------------------- */
 #define MM_COMM_ID_BYTES 128

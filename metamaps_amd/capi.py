@@ -189,6 +189,7 @@ def lib() -> C.CDLL:
             "mm_em_continue": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, P(C.c_int), P(C.c_int)]),
             "mm_em_bootstrap": (C.c_int, [vp, vp, i32, i32, u64, vp, C.c_int, vp, vp, vp, vp]),
             "mm_em_lca": (C.c_int, [vp, vp, i32, vp, vp, f64, vp, vp, vp]),
+            "mm_gene_overlap": (C.c_int, [vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, P(i64)]),
             "mm_comm_unique_id": (C.c_int, [C.c_char_p]),
             "mm_comm_init": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
             "mm_comm_allreduce_f64": (C.c_int, [vp, vp, i64]),
@@ -444,6 +445,23 @@ class Context:
         nr, ne, nt = C.c_int64(), C.c_int64(), C.c_int32()
         self.check(lib().mm_em_sizes(h, C.byref(nr), C.byref(ne), C.byref(nt)))
         return EM(self, h, n_taxa, nr.value, ne.value)
+
+    def gene_overlap(self, contig_gene_off, gene_start, gene_stop, gene_group, n_groups: int, group_feat_off, group_feat, n_feats: int,
+                     map_contig, map_start, map_stop, map_ident, want_feats: bool = True, want_annotated: bool = True):
+        """which annotated genes the mappings overlap (mm_gene_overlap; classify --genes): genes of contig c are [contig_gene_off[c],
+        contig_gene_off[c+1]), sorted by Start.  Returns (group_reads[n_groups], group_median[n_groups] with NaN for groups without a read,
+        feat_reads[n_feats] or None, mappings on contigs with genes or None)."""
+        i4 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        i8 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+        off, gs, ge, gg, fo, ff = i8(contig_gene_off), i4(gene_start), i4(gene_stop), i4(gene_group), i8(group_feat_off), i4(group_feat)
+        mc, ms, me, mi = i4(map_contig), i4(map_start), i4(map_stop), np.ascontiguousarray(map_ident, dtype=np.float64)
+        reads, median = np.zeros(n_groups, dtype=np.int64), np.zeros(n_groups, dtype=np.float64)
+        feats = np.zeros(n_feats, dtype=np.int64) if want_feats else None
+        on = C.c_int64(-1)
+        self.check(lib().mm_gene_overlap(self.h, len(off) - 1, _ptr(off), _ptr(gs), _ptr(ge), _ptr(gg), n_groups, _ptr(fo), _ptr(ff), n_feats,
+                                         len(mc), _ptr(mc), _ptr(ms), _ptr(me), _ptr(mi), _ptr(reads), _ptr(median), _ptr(feats),
+                                         C.byref(on) if want_annotated else None))
+        return reads, median, feats, (on.value if want_annotated else None)
 
     # ---- communicator
     @staticmethod

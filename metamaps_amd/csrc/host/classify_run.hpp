@@ -4,6 +4,7 @@
 #include "bam_reader.hpp"
 #include "cli_device.hpp"
 #include "cli_switches.hpp"
+#include "gene_annot.hpp"
 #include "query_reader.hpp"
 #include "taxonomy.hpp"
 #include <fcntl.h>
@@ -159,6 +160,7 @@ struct ClassifyRun {
   BootOpts boot;                                                  // --bootstrap: the replicates' frequencies of the present taxa, [replicate][boot_pres]
   std::vector<int32_t> boot_pres; std::vector<double> boot_f;
   LcaOpts lca; std::unique_ptr<LcaJob> lca_job;                   // --lca
+  GeneOpts genes;                                                 // --genes
 
   ClassifyRun(const std::vector<Dev>& devs_, EmReduce reduce_, const std::string& mapped_, const std::string& db_, size_t minReadsU_, const std::function<void()>& leave_now_,
               const std::function<void()>& need_devices_, const CliSwitches& sw_)
@@ -381,6 +383,48 @@ struct ClassifyRun {
     std::ofstream o(fn);
     o.write(out.data(), (std::streamsize)out.size());
   }
+  // --genes: the best mappings of all reads against the annotated genes of their contigs, on the first device (mm_gene_overlap; medians do not merge
+  // across shards, and the job is small); PREFIX.EM.geneLevelAnalysis and PREFIX.EM.proteins.TYPE beside the WIMP
+  void gene_analysis() {
+    std::unordered_map<std::string, int> relevant;                // contigs with a best mapping, in the order of their first one
+    std::vector<int> rel_of(contig_id.size(), -1);
+    std::vector<int32_t> mc(NRD), ms(NRD), me(NRD); std::vector<double> mi(NRD);
+    for (size_t r = 0; r < NRD; ++r) {
+      const MapLine& B = lines[(size_t)best[r]];
+      int& k = rel_of[(size_t)B.contig];
+      if (k < 0) { k = (int)relevant.size(); relevant.emplace(contig_id[(size_t)B.contig], k); }
+      if (B.start > (size_t)INT32_MAX || B.stop > (size_t)INT32_MAX) die("--genes: a mapping of " + contig_id[(size_t)B.contig] + " lies beyond position 2^31");
+      mc[r] = k; ms[r] = (int32_t)B.start; me[r] = (int32_t)B.stop; mi[r] = B.ident;
+    }
+    gene::Annotations A; gene::Results R;
+    try { gene::read_annotations(gene::annotations_path(db), relevant, relevant.size(), A); gene::read_proteins(gene::proteins_path(db), A); }
+    catch (const gene::Error& e) { die(std::string("--genes: ") + e.what()); }
+    std::cout << "Gene-level analysis: found " << relevant.size() << " relevant contig IDs, of which we have annotations for " << A.n_contigs_annotated << "." << std::endl;
+    if (A.n_proteins_absent) {
+      char pct[32]; snprintf(pct, sizeof pct, "%.2f", 100.0 * (double)A.n_proteins_absent / (double)A.n_protein_lines);
+      std::cout << "Warning: " << pct << "% of a total of " << A.n_protein_lines << " in the protein annotations are not in the genome annotations." << std::endl;
+    }
+    R.group_reads.assign(A.groups.size(), 0); R.group_median.assign(A.groups.size(), 0.0); R.feat_reads.assign(A.feat_name.size(), 0);
+    mm_ctx* const ctx = devs[0].ctx;
+    ck(ctx, mm_gene_overlap(ctx, (int32_t)relevant.size(), A.contig_gene_off.data(), A.start.data(), A.stop.data(), A.group.data(), (int32_t)A.groups.size(),
+                            A.group_feat_off.data(), A.group_feat.data(), (int32_t)A.feat_name.size(), (int64_t)NRD, mc.data(), ms.data(), me.data(), mi.data(),
+                            R.group_reads.data(), R.group_median.data(), R.feat_reads.data(), &R.maps_on_annotated), "gene-level analysis");
+    std::cout << "Of " << NRD << " mapped reads, " << R.maps_on_annotated << " go to contigs with annotations and " << ((int64_t)NRD - R.maps_on_annotated) << " to contigs without." << std::endl;
+    size_t n_genes = 0, n_prot = 0, n_annot = 0;
+    gene::found_counts(A, R, &n_genes, &n_prot, &n_annot);
+    std::cout << "Found " << n_genes << " genes and " << n_prot << " proteins, of which " << n_annot << " carry any type of additional annotation." << std::endl;
+    try {
+      gene::write_gene_table(mapped + ".EM.geneLevelAnalysis", A, R);
+      const std::vector<std::string> written = gene::write_protein_tables(mapped + ".EM", A, R, NRD);
+      for (int t = 0; t < gene::N_TYPES; ++t) {                   // (a table an earlier run left and this one does not have)
+        const std::string fn = mapped + ".EM.proteins." + gene::type_name(t);
+        if (std::find(written.begin(), written.end(), fn) == written.end()) ::remove(fn.c_str());
+      }
+      std::cout << "Produced " << mapped << ".EM.geneLevelAnalysis";
+      for (const std::string& fn : written) std::cout << ", " << fn;
+      std::cout << std::endl;
+    } catch (const gene::Error& e) { die(std::string("--genes: ") + e.what()); }
+  }
   // --bootstrap B: replicates 0..B-1 of the weighted EM (mm_em_bootstrap), started from the point estimate, dealt to the devices in contiguous
   // ranges; every device holds the whole EM problem and tiles its range to its free memory.  The result depends on neither.
   void bootstrap() {
@@ -572,6 +616,7 @@ struct ClassifyRun {
     pc.lap("c6 WIMP");
     if (boot.B > 0) { write_bootstrap(mapped + ".EM.WIMP.bootstrap", T, fmap, readsPer); pc.lap("c6b WIMP bootstrap"); }
     if (lca.on) { write_lca_reads(mapped + ".EM.reads2Taxon.lca"); write_kreport(mapped + ".EM.kreport", T, *lca_job, nTotal, nUnmapped + nTooShort); pc.lap("c6c LCA files"); }
+    if (genes.on) { gene_analysis(); pc.lap("c6d gene-level analysis"); }
     side_files.join();
     if (!unknown_written)
       std::cerr << "Warning: " << db << "/contigNstats_windowSize_1000.txt not found - " << mapped << ".EM.evidenceUnknownSpecies is not written." << std::endl;
@@ -618,11 +663,12 @@ struct ClassifyRun {
 };
 
 int classify_one(const std::vector<Dev>& devs, EmReduce reduce, const std::string& mapped, const std::string& db, size_t minReadsU,
-                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept, BootOpts boot, LcaOpts lca, const CliSwitches& sw) {
+                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept, BootOpts boot, LcaOpts lca, GeneOpts genes, const CliSwitches& sw) {
   ClassifyRun run(devs, reduce, mapped, db, minReadsU, leave_now, need_devices, sw);
   run.kept = kept;
   run.boot = boot;
   run.lca = lca;
+  run.genes = genes;
   return run.run();
 }
 

@@ -59,7 +59,11 @@ struct BootOpts { int B = 0; uint64_t seed = 1; };
 // --lca T (classify, mapDirectly --then-classify; not in the reference): the confidence threshold of the LCA assignment, a decimal in [0.51, 1].
 // Off without the flag: nothing changes and no file appears.
 struct LcaOpts { bool on = false; double tau = 0; };
+// --genes (classify, mapDirectly --then-classify; the reference's geneLevelAnalysis.pl): the gene- and annotation-level analysis of the reads' best
+// mappings against DB/DB_annotations.txt and DB/DB_proteins.faa.annotated.  Off without the flag: nothing changes and no file appears.
+struct GeneOpts { bool on = false; };
 BootOpts boot_options(const Options& o);                         // (metamaps_main.cpp: they end the program on a malformed value)
 LcaOpts lca_options(const Options& o);
+GeneOpts gene_options(const Options& o);
 
 }  // namespace

@@ -7,7 +7,7 @@
 //
 //   metamaps mapDirectly [--all] [--compress-output] -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
-//   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]] [--lca T]
+//   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]] [--lca T] [--genes]
 //
 // --gpus N uses devices 0..N-1 of the node, one context per device on its own host thread (where the reference has -t N worker
 // threads, computeMap.hpp:104-176 / fEM.h:1229): mapping shards the read batches (index replicated) or the index chunks
@@ -56,6 +56,12 @@
 // assignment").  PREFIX.EM.reads2Taxon.lca (readID, taxonID, rank, mass) and PREFIX.EM.kreport (the six-column Kraken report) are added; every
 // other output is unchanged.
 //
+// --genes (classify, mapDirectly --then-classify; the reference's geneLevelAnalysis.pl, its README's "COG group analysis"): which annotated genes
+// the reads' best mappings overlap.  Needs DB/DB_annotations.txt and DB/DB_proteins.faa.annotated (a gene-annotated database); a missing one ends the
+// run before any work.  The interval join, the per-gene median identities and the per-read de-duplicated feature counts run on the first device
+// (mm_gene_overlap, DESIGN.md §4 "Gene-level analysis").  PREFIX.EM.geneLevelAnalysis (gene, locus tag, protein, product, reads, median identity) and
+// PREFIX.EM.proteins.{GO,KEGG,BiGG,OG,COG} (feature, supporting reads, their share of the mapped reads) are added; every other output is unchanged.
+//
 // Not provided: classifyU (disabled upstream).
 
 
@@ -84,13 +90,15 @@ Options parse(int argc, char** argv) {
     if (a == "--stream-chunks") { o.stream = true; continue; }
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
-    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc") { o.v[a.substr(2)] = "1"; continue; }
+    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--genes") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
                    "         sketching; -m, identities and mapping qualities are in compressed space, reported lengths and coordinates are raw\n"
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
-                   "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n";
+                   "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
+                   "  --genes  (classify, mapDirectly --then-classify) gene-level analysis against DB_annotations.txt and DB_proteins.faa.annotated of the DB:\n"
+                   "         adds PREFIX.EM.geneLevelAnalysis and PREFIX.EM.proteins.{GO,KEGG,BiGG,OG,COG}\n";
       exit(0);
     }
     std::string key = alias.count(a) ? alias.at(a) : (a.rfind("--", 0) == 0 ? a.substr(2) : "");
@@ -133,6 +141,9 @@ LcaOpts lca_options(const Options& o) {
   return l;
 }
 
+// --genes: a bare flag (GeneOpts, cli_common.hpp)
+GeneOpts gene_options(const Options& o) { GeneOpts g; g.on = o.v.count("genes") > 0; return g; }
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -149,6 +160,14 @@ int main(int argc, char** argv) {
   if (boot.B && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--bootstrap needs classify or mapDirectly --then-classify");
   const LcaOpts lca = lca_options(o);
   if (lca.on && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--lca needs classify or mapDirectly --then-classify");
+  const GeneOpts genes = gene_options(o);
+  if (genes.on && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--genes needs classify or mapDirectly --then-classify");
+  if (genes.on && (mode == "mapDirectly" || o.v.count("DB"))) {  // (a database without gene annotations: said before any work)
+    const std::string& db = mode == "classify" ? o.v.at("DB") : o.v.at("then-classify");
+    struct stat probe;
+    if (stat(gene::annotations_path(db).c_str(), &probe) != 0) die("--genes: please supply a gene-annotated database (file " + gene::annotations_path(db) + " not found).");
+    if (stat(gene::proteins_path(db).c_str(), &probe) != 0) die("--genes: please supply a protein annotation file (file " + gene::proteins_path(db) + " not found).");
+  }
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
   if (mode == "mapDirectly" || mode == "index" || mode == "mapAgainstIndex") return map_mode(o, mode, sw);
   if (mode == "classify") {
@@ -179,8 +198,8 @@ int main(int argc, char** argv) {
     const size_t minReadsU = o.v.count("minreads") ? std::stoull(o.v.at("minreads")) : 10000;   // parseCmdArgs.hpp:462-471
     const std::vector<std::string> files = split(o.v.at("mappings"), ",");
     for (size_t fi = 0; fi < files.size(); ++fi) {
-      if (fi + 1 == files.size()) classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, [&] { since("mappings file done"); }, need_devices, nullptr, boot, lca, sw);
-      else classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, nullptr, need_devices, nullptr, boot, lca, sw);
+      if (fi + 1 == files.size()) classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, [&] { since("mappings file done"); }, need_devices, nullptr, boot, lca, genes, sw);
+      else classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, nullptr, need_devices, nullptr, boot, lca, genes, sw);
       need_devices();
       for (auto& d : devs) mm_comm_destroy(d.ctx);
       since("mappings file done");

@@ -8,6 +8,7 @@
 #include "mm_synth.hpp"
 #include "mm_hpc.hpp"
 #include "mm_lca.hpp"
+#include "mm_gene.hpp"
 #include <chrono>
 #include <new>
 #include <rccl/rccl.h>
@@ -940,6 +941,21 @@ int mm_em_lca(mm_em* em, const double* f, int32_t n_nodes, const int32_t* parent
               int32_t* node_out, double* mass_out, int64_t* direct_out) {
   if (!em || !f || !parent || !taxon_node || !node_out || n_nodes <= 0) return MM_ERR_ARG;
   return guarded(em->ctx, [&] { MM_HIP(hipSetDevice(em->ctx->device)); mm::lca_run(em, f, n_nodes, parent, taxon_node, threshold, node_out, mass_out, direct_out); });
+}
+int mm_gene_overlap(mm_ctx* ctx, int32_t n_contigs, const int64_t* contig_gene_off, const int32_t* gene_start, const int32_t* gene_stop,
+                    const int32_t* gene_group, int32_t n_groups, const int64_t* group_feat_off, const int32_t* group_feat, int32_t n_feats,
+                    int64_t n_maps, const int32_t* map_contig, const int32_t* map_start, const int32_t* map_stop, const double* map_ident,
+                    int64_t* group_reads, double* group_median, int64_t* feat_reads, int64_t* maps_on_annotated) {
+  if (!ctx) return MM_ERR_ARG;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(n_contigs >= 0 && n_groups >= 0 && n_feats >= 0 && n_maps >= 0 && contig_gene_off && group_feat_off, MM_ERR_ARG, "mm_gene_overlap: a negative size or no offsets");
+    const int64_t ng = n_contigs > 0 ? contig_gene_off[n_contigs] : 0;
+    MM_REQUIRE((ng <= 0 || (gene_start && gene_stop && gene_group)) && (n_maps == 0 || (map_contig && map_start && map_stop && map_ident)) &&
+               (n_groups == 0 || (group_reads && group_median)) && (group_feat_off[n_groups] <= 0 || group_feat), MM_ERR_ARG, "mm_gene_overlap: a null array");
+    mm::gene_overlap_run(ctx, mm::GeneIn{n_contigs, contig_gene_off, gene_start, gene_stop, gene_group, n_groups, group_feat_off, group_feat, n_feats,
+                                         n_maps, map_contig, map_start, map_stop, map_ident}, group_reads, group_median, feat_reads, maps_on_annotated);
+  });
 }
 
 // ---- communicator -------------------------------------------------------------------------------------

@@ -97,6 +97,9 @@ inline const EnvSwitch* env_table(size_t* n) {
     // ---- library: EM and exchange (mm_post.hip, mm_api.hip)
     {"MM_EM_FORCE_COLLECTIVE", "unset", "test", "a one-rank communicator keeps P1-P3' | ncclAllReduce | finalize instead of P1-P3 alone (how one GPU drives the multi-rank path)"},
     {"MM_EM_GRID", "by size", "tuning", "workgroups of the EM kernels; by default enough for about 160 reads and 448 mappings each, 256 at least, one per read at most; when set: at most 1024 and one per 256 reads"},
+    // ---- library: gene-level analysis (mm_gene.hip)
+    {"MM_GENE_PAIR_BUDGET", "2^26", "test", "(mapping, gene) pairs, feature keys and median keys per tile of mm_gene_overlap (small values: many tiles on small inputs; no result depends on it)"},
+    {"MM_GENE_TIMING", "unset", "debug", "device times of mm_gene_overlap's stages (events) on stderr (tools/gene_kernel_stats.py)"},
     {"MM_CLI_FORMAT_PART", "10000", "test", "mapping records per formatter thread of a batch (the text of a batch is formatted in up to eight parts and joined)"},
     {"MM_CLI_CLASSIFY_FROM_FILE", "unset", "test", "mapDirectly --then-classify reads PREFIX back and tokenises it (as `classify` does) instead of taking the lines it has just formatted from memory"},
     {"MM_GATHER_SELF_SEND", "unset", "test", "mm_mapping_gather sends the owner's own parts through ncclSend / ncclRecv too (one-GPU test of the exchange)"},
