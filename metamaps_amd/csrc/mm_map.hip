@@ -13,6 +13,7 @@
 #include <memory>
 #include <rocprim/rocprim.hpp>
 #include "mm_l2_core.hpp"
+#include "mm_size_classes.hpp"
 #include "mm_l2.hpp"
 #include "mm_l2z.hpp"
 #include "mm_l2_dense.hpp"
@@ -301,16 +302,13 @@ struct MapRun {
     // up to 16384 minimizers: radix sort in LDS, 4 ... 64 elements per thread.  The sort's cost follows the elements per thread, so the
     // reads are grouped by the capacity they really need (a 10 kb read has ~2 200 minimizers: 10 per thread instead of 16).
     // Single-element lists are "sorted" already but still need their sketch written.
-    static const int ipts[] = {4, 6, 8, 10, 12, 16, 20, 24, 32, 40, 48, 64};
-    uint8_t cls_of_need[66];                                      // elements per thread needed -> index into ipts; [0]: empty, [65]: beyond the LDS sort
-    for (int need = 0, i = 0; need <= 64; ++need) { while (ipts[i] < need) ++i; cls_of_need[need] = (uint8_t)i; }
-    cls_of_need[0] = 12; cls_of_need[65] = 12;
+    static_assert(ipt_list_is<4, 6, 8, 10, 12, 16, 20, 24, 32, 40, 48, 64>(SKETCH_IPTS), "the dispatch below lists the classes of mm_size_classes.hpp");
     uint64_t big_seen = 0;
     HostLap hl;
-    const ReadBins RB = bin_reads(n, 12, [&](int64_t r) -> int {
+    const ReadBins RB = bin_reads(n, N_SKETCH_CLASSES, [&](int64_t r) -> int {
       const uint64_t c = hoff()[(size_t)r + 1] - hoff()[(size_t)r];
-      big_seen |= (uint64_t)(c > 16384);
-      return cls_of_need[std::min<uint64_t>((c + 255) / 256, 65)];
+      big_seen |= (uint64_t)(c > SKETCH_LDS_MAX);
+      return sketch_class_index(c);                                // (empty reads and those beyond the LDS sort are left out)
     });
     const bool any_big = big_seen != 0;
     {
@@ -322,7 +320,7 @@ struct MapRun {
       for (auto& run : RB.runs) {
         const unsigned nb = (unsigned)run.second;
         const int32_t* lp = list.p + at;
-        dispatch<4, 6, 8, 10, 12, 16, 20, 24, 32, 40, 48, 64>(ipts[run.first], [&](auto ipt_tag) {
+        dispatch<4, 6, 8, 10, 12, 16, 20, 24, 32, 40, 48, 64>(SKETCH_IPTS[run.first], [&](auto ipt_tag) {
           constexpr int IPT = decltype(ipt_tag)::value;
           using SortT = rocprim::block_radix_sort<uint32_t, 256, IPT, uint16_t>;
           using ScanT = rocprim::block_scan<int, 256>;
@@ -344,7 +342,7 @@ struct MapRun {
   // sketches of the reads beyond 16 384 minimizers: keys of all of them back to back, one segmented device sort, unique + strand per read
   void sketch_big_segmented() {
     std::vector<int32_t> big; std::vector<uint64_t> koff{0};
-    for (int64_t r = 0; r < n; ++r) { const uint64_t c = hoff()[(size_t)r + 1] - hoff()[(size_t)r]; if (c > 16384) { big.push_back((int32_t)r); koff.push_back(koff.back() + c); } }
+    for (int64_t r = 0; r < n; ++r) { const uint64_t c = hoff()[(size_t)r + 1] - hoff()[(size_t)r]; if (c > SKETCH_LDS_MAX) { big.push_back((int32_t)r); koff.push_back(koff.back() + c); } }
     const size_t nb = big.size(); const uint64_t nk = koff.back();
     MM_REQUIRE(nk < ((uint64_t)1 << 32), MM_ERR_LIMIT, "more than 2^32 minimizers of reads beyond 16384 minimizers in one batch");
     DBuf<int32_t> d_big(nb); d_big.upload(big.data(), nb, st);
@@ -623,16 +621,12 @@ struct MapRun {
 
   // the LDS radix sort over the reads of up to 4096 hits; true: longer lists are left
   bool sort_hits_radix(int key_bits) {
-    static const int ipts[] = {1, 2, 3, 4, 6, 8, 12, 16};
-    uint8_t cls_of_need[18];                                    // elements per thread needed -> index into ipts; [17]: beyond 4096 hits
-    for (int need = 0, i = 0; need <= 16; ++need) { while (ipts[i] < need) ++i; cls_of_need[need] = (uint8_t)i; }
-    cls_of_need[17] = 8;
+    static_assert(ipt_list_is<1, 2, 3, 4, 6, 8, 12, 16>(HIT_SORT_IPTS), "the dispatch below lists the classes of mm_size_classes.hpp");
     uint64_t left_seen = 0;
-    const ReadBins RB = bin_reads(n, 8, [&](int64_t r) -> int {
+    const ReadBins RB = bin_reads(n, N_HIT_SORT_CLASSES, [&](int64_t r) -> int {
       const uint64_t c = (uint64_t)hits_of(r);
-      left_seen |= (uint64_t)(c > 4096);
-      const unsigned k = cls_of_need[std::min<uint64_t>((c + 255) / 256, 17)];
-      return c <= 1 ? 8 : (int)k;                              // zero or one hit: nothing to sort
+      left_seen |= (uint64_t)(c > HIT_SORT_LDS_MAX);
+      return hit_sort_class_index(c);                          // (zero or one hit: nothing to sort; more than 4096: left)
     });
     hl("K4 bin");
     DBuf<int32_t> list(std::max<size_t>(RB.order.size(), 1));
@@ -641,7 +635,7 @@ struct MapRun {
     size_t at = 0;
     for (auto& run : RB.runs) {
       const int32_t* lp = list.p + at;
-      dispatch<1, 2, 3, 4, 6, 8, 12, 16>(ipts[run.first], [&](auto tag) {
+      dispatch<1, 2, 3, 4, 6, 8, 12, 16>(HIT_SORT_IPTS[run.first], [&](auto tag) {
         constexpr int IPT = decltype(tag)::value;
         using SortT = rocprim::block_radix_sort<uint64_t, 256, IPT>;
         const size_t lds = sizeof(typename SortT::storage_type) + 16;
@@ -667,7 +661,7 @@ struct MapRun {
     uint64_t in_run = 0, longest_run = 0;
     for (int64_t r = 0; r < n; ++r) {
       const uint64_t c = (uint64_t)hits_of(r);
-      if (c <= 4096) continue;
+      if (c <= HIT_SORT_LDS_MAX) continue;
       MM_REQUIRE(c < max_keys, MM_ERR_LIMIT, "one read has more seed hits than a segmented sort takes (2^32 - 1, or MM_SEGSORT_MAX_KEYS)");
       if (in_run + c >= max_keys) { run_at.push_back(seg_reads.size()); in_run = 0; }
       seg_reads.push_back((int32_t)r);
