@@ -29,7 +29,7 @@ extern "C" {
                             * 4: mm_sketch_batch, mm_ctx_release_cached, mm_index_dup_neighbours;
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
-                            *    mm_em_lca, mm_gene_overlap (additions to 6) */
+                            *    mm_em_lca, mm_gene_overlap, mm_ident_filter (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -430,6 +430,25 @@ int mm_gene_overlap(mm_ctx* ctx, int32_t n_contigs, const int64_t* contig_gene_o
                     int64_t n_maps, const int32_t* map_contig, const int32_t* map_start, const int32_t* map_stop, const double* map_ident,
                     int64_t* group_reads /* [n_groups] */, double* group_median /* [n_groups], NaN where group_reads is 0 */,
                     int64_t* feat_reads /* [n_feats], may be NULL */, int64_t* maps_on_annotated /* may be NULL */);
+
+/* ---- identity filter (classify --min-identity; the reference's util/filterLowIdentityEntities.pl) ------------ */
+/* Which genomes of an EM problem have best mappings of low median identity, and the EM problem without them.  Reads r with entries
+ * [read_off[r], read_off[r+1]); taxon[i] in [0, n_taxa); ident[i]: the entry's identity in percent; best[r]: an entry of read r (ignored for a
+ * read without entries).  sorted_max: the largest identity of every read with entries, ascending (room for n_reads values; n_with_entries are
+ * written); n_le: how many of them are <= thr_percent.  taxon_reads[t]: reads with taxon[best[r]] == t; taxon_median[t]: the element of 0-based
+ * rank taxon_reads[t] / 2 of their ident[best[r]] in ascending order (the upper median), NaN where there is none; taxon_removed[t] =
+ * taxon_reads[t] > 0 && taxon_median[t] < thr_percent; read_removed[r] = taxon_removed[taxon[best[r]]], 0 for a read without entries.
+ * The filtered problem (all five NULL, or none): an entry is kept iff its taxon is not removed, a read iff it keeps an entry; entry_src
+ * (room for all entries) and read_src (room for n_reads) are the original indices of the kept ones, ascending; read_off_out (room for
+ * n_reads + 1) the offsets of the kept reads into entry_src.  Zero reads and zero entries are valid.  Nothing is written on an error.
+ * MM_ERR_ARG: offsets that do not start at 0 and ascend, a taxon out of range, a best[r] outside its read's entries, a negative or NaN identity
+ * (-0.0 is taken as 0), a NaN threshold.  MM_ERR_LIMIT: 2^32 reads or more (ranks are 32-bit; entry indices are 64-bit). */
+int mm_ident_filter(mm_ctx* ctx, int64_t n_reads, const int64_t* read_off /* [n_reads+1] */, const int32_t* taxon, const double* ident,
+                    const int64_t* best /* [n_reads] */, int32_t n_taxa, double thr_percent,
+                    double* sorted_max /* [reads with entries] */, int64_t* n_with_entries, int64_t* n_le,
+                    int64_t* taxon_reads /* [n_taxa] */, double* taxon_median /* [n_taxa] */, uint8_t* taxon_removed /* [n_taxa] */,
+                    uint8_t* read_removed /* [n_reads] */,
+                    int64_t* read_src, int64_t* entry_src, int64_t* read_off_out, int64_t* n_reads_out, int64_t* n_entries_out);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------------------------- */
 #define MM_COMM_ID_BYTES 128

@@ -190,6 +190,7 @@ def lib() -> C.CDLL:
             "mm_em_bootstrap": (C.c_int, [vp, vp, i32, i32, u64, vp, C.c_int, vp, vp, vp, vp]),
             "mm_em_lca": (C.c_int, [vp, vp, i32, vp, vp, f64, vp, vp, vp]),
             "mm_gene_overlap": (C.c_int, [vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, P(i64)]),
+            "mm_ident_filter": (C.c_int, [vp, i64, vp, vp, vp, vp, i32, f64, vp, P(i64), P(i64), vp, vp, vp, vp, vp, vp, vp, P(i64), P(i64)]),
             "mm_comm_unique_id": (C.c_int, [C.c_char_p]),
             "mm_comm_init": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
             "mm_comm_allreduce_f64": (C.c_int, [vp, vp, i64]),
@@ -462,6 +463,31 @@ class Context:
                                          len(mc), _ptr(mc), _ptr(ms), _ptr(me), _ptr(mi), _ptr(reads), _ptr(median), _ptr(feats),
                                          C.byref(on) if want_annotated else None))
         return reads, median, feats, (on.value if want_annotated else None)
+
+    def ident_filter(self, read_off, taxon, ident, best, n_taxa: int, thr_percent: float, want_filtered: bool = True) -> dict:
+        """the identity filter of an EM problem (mm_ident_filter; classify --min-identity): ident in percent, best[r] an entry of read r.  Returns a
+        dict of sorted_max, n_le, taxon_reads, taxon_median (NaN for a taxon without reads), taxon_removed, read_removed and, with want_filtered,
+        read_src, entry_src, read_off_out of the problem without the removed taxa."""
+        off, tx = np.ascontiguousarray(read_off, dtype=np.int64), np.ascontiguousarray(taxon, dtype=np.int32)
+        idn, bst = np.ascontiguousarray(ident, dtype=np.float64), np.ascontiguousarray(best, dtype=np.int64)
+        nr, ne = len(off) - 1, len(tx)
+        smax = np.full(nr, -1.0)
+        reads, median = np.full(n_taxa, -1, dtype=np.int64), np.full(n_taxa, -1.0)
+        t_rem, r_rem = np.full(n_taxa, 255, dtype=np.uint8), np.full(nr, 255, dtype=np.uint8)
+        n_with, n_le, n_r, n_e = C.c_int64(-1), C.c_int64(-1), C.c_int64(-1), C.c_int64(-1)
+        rs, es, ro = (np.full(nr, -1, dtype=np.int64), np.full(ne, -1, dtype=np.int64), np.full(nr + 1, -1, dtype=np.int64)) if want_filtered else (None, None, None)
+        out = dict(sorted_max=smax, taxon_reads=reads, taxon_median=median, taxon_removed=t_rem, read_removed=r_rem, read_src=rs, entry_src=es, read_off_out=ro)
+        st = lib().mm_ident_filter(self.h, nr, _ptr(off), _ptr(tx), _ptr(idn), _ptr(bst), n_taxa, float(thr_percent), _ptr(smax), C.byref(n_with), C.byref(n_le),
+                                   _ptr(reads), _ptr(median), _ptr(t_rem), _ptr(r_rem), _ptr(rs), _ptr(es), _ptr(ro),
+                                   C.byref(n_r) if want_filtered else None, C.byref(n_e) if want_filtered else None)
+        if st != 0:
+            err = MMError(st, lib().mm_last_error(self.h).decode(errors="replace"))
+            err.outputs = dict(out, n_with_entries=n_with.value, n_le=n_le.value, n_reads_out=n_r.value, n_entries_out=n_e.value)   # (as they were handed in)
+            raise err
+        out.update(sorted_max=smax[:n_with.value], n_le=n_le.value, taxon_removed=t_rem.astype(bool), read_removed=r_rem.astype(bool))
+        if want_filtered:
+            out.update(read_src=rs[:n_r.value], entry_src=es[:n_e.value], read_off_out=ro[:n_r.value + 1])
+        return out
 
     # ---- communicator
     @staticmethod

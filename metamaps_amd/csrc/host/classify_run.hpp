@@ -5,6 +5,7 @@
 #include "cli_device.hpp"
 #include "cli_switches.hpp"
 #include "gene_annot.hpp"
+#include "ident_filter.hpp"
 #include "query_reader.hpp"
 #include "taxonomy.hpp"
 #include <fcntl.h>
@@ -56,10 +57,10 @@ void print_em_round(long long it, double ll, double ll_prev) {  // the per-round
   if (it > 0) std::cout << "\tImprovement: " << ll - ll_prev << "\n\tRelative   : " << ll / ll_prev << std::endl;
 }
 // f: start frequencies in, final frequencies out; post[mapping], best[read] (index into the whole mapping list) out; lca (may be null): every
-// rank's reads assigned behind its posteriors, the ranks' direct counts added
+// rank's reads assigned behind its posteriors, the ranks' direct counts added; rounds (may be null): the EM rounds that were run
 void run_em_sharded(const std::vector<Dev>& devs, EmReduce reduce, const std::vector<int64_t>& off, const std::vector<int32_t>& taxon,
                     const std::vector<double>& mapq, const std::vector<double>& inv, size_t NT, std::vector<double>& f,
-                    std::vector<double>& post, std::vector<int64_t>& best, LcaJob* lca, const CliSwitches& sw) {
+                    std::vector<double>& post, std::vector<int64_t>& best, LcaJob* lca, const CliSwitches& sw, long long* rounds = nullptr) {
   const size_t G = devs.size();
   if (reduce == EmReduce::None && G != 1) die("internal error: several EM ranks without a reduction");
   char comm_id[MM_COMM_ID_BYTES];
@@ -92,6 +93,7 @@ void run_em_sharded(const std::vector<Dev>& devs, EmReduce reduce, const std::ve
         done += n_iter;
         if (stopped || n_iter == 0) break;
       }
+      if (d == 0 && rounds) *rounds = done;
     } else {
       for (long long it = 0; it < MAX_ITER; ++it) {
         ck(ctx, mm_em_iterate(em, f_cur.data(), part[d].data(), &part[d][NT]), "em");
@@ -103,6 +105,7 @@ void run_em_sharded(const std::vector<Dev>& devs, EmReduce reduce, const std::ve
           for (size_t t = 0; t < NT; ++t) f_cur[t] = tot[t] / sum;
           const double ll = tot[NT];
           print_em_round(it, ll, ll_prev);
+          if (rounds) *rounds = it + 1;
           if (it > 0 && (ll - ll_prev) <= 1 && (1 - ll / ll_prev) < 0.0001) host_stop = true;
           ll_prev = ll;
         }
@@ -161,6 +164,7 @@ struct ClassifyRun {
   std::vector<int32_t> boot_pres; std::vector<double> boot_f;
   LcaOpts lca; std::unique_ptr<LcaJob> lca_job;                   // --lca
   GeneOpts genes;                                                 // --genes
+  IdentOpts identf_opts;                                          // --min-identity, --refit
 
   ClassifyRun(const std::vector<Dev>& devs_, EmReduce reduce_, const std::string& mapped_, const std::string& db_, size_t minReadsU_, const std::function<void()>& leave_now_,
               const std::function<void()>& need_devices_, const CliSwitches& sw_)
@@ -512,6 +516,91 @@ struct ClassifyRun {
       o << *R.L << "\t" << R.t << "\t" << (R.t == "0" ? std::string("Unclassified") : T.T.at(R.t).sci) << "\t" << R.em << num;
     }
   }
+  // a line of PREFIX.EM: the mapping line with field 14 replaced by std::to_string(posterior) (fEM.h:705)
+  static void em_line(std::string& s, const MapLine& L, double p) { s.append(L.p, (size_t)L.last_space + 1); append_f6(s, p); s += '\n'; }
+  // the lines PREFIX.EM.reads2Taxon ends in: the unmapped and the too short reads at taxon 0
+  std::string unmapped_reads2taxon() const {
+    std::string out, ln;
+    std::ifstream s(mapped + ".meta.unmappedReadsLengths");
+    while (std::getline(s, ln)) { if (ln.empty()) continue; out += split(ln, "\t").at(1); out += "\t0\n"; }
+    return out;
+  }
+  static void write_text(const std::string& fn, const std::string& text) { std::ofstream o(fn); o.write(text.data(), (std::streamsize)text.size()); }
+  // --min-identity T: the genomes whose best mappings have a median identity below 100 T are removed, on the first device for all reads (mm_ident_filter;
+  // medians do not merge across shards); PREFIX.extractedIdentities and PREFIX.EM-filtered{,.reads2Taxon,.WIMP} beside the WIMP
+  void identity_filter() {
+    identf::Filter F;
+    F.thr = identf_opts.T * 100.0;                                 // (the script's $identityThreshold *= 100)
+    const size_t NT = taxa.size(), NE = lines.size();
+    F.ident.resize(NE);
+    for (size_t i = 0; i < NE; ++i) F.ident[i] = identf::identity_value(lines[i].p, lines[i].last_space);
+    F.sorted_max.resize(NRD); F.taxon_reads.resize(NT); F.taxon_median.resize(NT); F.taxon_removed.resize(NT); F.read_removed.resize(NRD);
+    if (identf_opts.refit) { F.read_src.resize(NRD); F.entry_src.resize(NE); F.read_off_out.resize(NRD + 1); }
+    mm_ctx* const ctx = devs[0].ctx;
+    const bool rf = identf_opts.refit;
+    ck(ctx, mm_ident_filter(ctx, (int64_t)NRD, off.data(), taxon.data(), F.ident.data(), best.data(), (int32_t)NT, F.thr, F.sorted_max.data(), &F.n_with, &F.n_le,
+                            F.taxon_reads.data(), F.taxon_median.data(), F.taxon_removed.data(), F.read_removed.data(), rf ? F.read_src.data() : nullptr,
+                            rf ? F.entry_src.data() : nullptr, rf ? F.read_off_out.data() : nullptr, rf ? &F.n_reads_out : nullptr, rf ? &F.n_entries_out : nullptr),
+       "identity filter");
+    F.sorted_max.resize((size_t)F.n_with);
+    identf::write_identities(mapped + ".extractedIdentities", F, off, lines);
+    std::string em, r2;
+    std::vector<int64_t> kept(NT, 0);
+    for (size_t r = 0; r < NRD; ++r) {
+      const size_t b = (size_t)best[r];
+      const MapLine& B = lines[b];
+      r2.append(B.p, (size_t)((const char*)memchr(B.p, ' ', B.n) - B.p)); r2 += '\t';
+      if (F.read_removed[r]) r2 += '0';
+      else { r2 += taxa[(size_t)taxon[b]]; em_line(em, B, post[b]); kept[(size_t)taxon[b]]++; }
+      r2 += '\n';
+    }
+    write_text(mapped + ".EM-filtered", em);
+    write_text(mapped + ".EM-filtered.reads2Taxon", r2 + unmapped_reads2taxon());
+    identf::write_filtered_wimp(mapped + ".EM-filtered.WIMP", *tax, taxa, kept, F.reads_removed(), nUnmapped, (size_t)F.n_with);
+    char msg[256];
+    snprintf(msg, sizeof msg, "Identity filter: threshold %g, median identity %g, %lld of %lld best identities at or below it, %zu of %zu genomes removed, %zu reads set to unclassified",
+             F.thr, F.n_with ? F.sorted_max[(size_t)F.n_with / 2] : 0.0, (long long)F.n_le, (long long)F.n_with, F.genomes_removed(), F.genomes_hit(), F.reads_removed());
+    std::cout << msg << std::endl;
+    if (rf) identity_refit(F);
+  }
+  // --refit: the EM again on the mappings of the genomes that stay, from the flat start of em() and over the same devices; PREFIX.EM-filtered.refit (the
+  // kept lines with their new posteriors), .refit.reads2Taxon (a read that lost every mapping: 0) and .refit.WIMP (such reads count as unmapped)
+  void identity_refit(identf::Filter& F) {
+    const size_t NT = taxa.size(), NR2 = (size_t)F.n_reads_out, NE2 = (size_t)F.n_entries_out, lost = (size_t)F.n_with - NR2;
+    F.read_src.resize(NR2); F.entry_src.resize(NE2); F.read_off_out.resize(NR2 + 1);
+    std::vector<int32_t> tx(NE2); std::vector<double> mq(NE2), iv(NE2);
+    for (size_t k = 0; k < NE2; ++k) { const size_t e = (size_t)F.entry_src[k]; tx[k] = taxon[e]; mq[k] = mapq[e]; iv[k] = inv[e]; }
+    std::vector<double> f2(NT, 1 / (double)NT), post2(NE2, 0.0); std::vector<int64_t> best2(NR2, 0);
+    long long rounds = 0;
+    if (NR2 > 0) {
+      std::cout << "Starting EM on the filtered mappings..." << std::endl;
+      if (reduce == EmReduce::Rccl) for (auto& d : devs) mm_comm_destroy(d.ctx);   // (run_em_sharded sets the communicator up)
+      run_em_sharded(devs, reduce, F.read_off_out, tx, mq, iv, NT, f2, post2, best2, nullptr, sw, &rounds);
+    }
+    std::string em, r2;
+    std::vector<size_t> readsPerIdx(NT, 0);
+    size_t k = 0;                                                  // the next kept read
+    for (size_t r = 0; r < NRD; ++r) {
+      const MapLine& A = lines[(size_t)off[r]];
+      r2.append(A.p, (size_t)((const char*)memchr(A.p, ' ', A.n) - A.p)); r2 += '\t';
+      if (k < NR2 && (size_t)F.read_src[k] == r) {
+        for (size_t j = (size_t)F.read_off_out[k]; j < (size_t)F.read_off_out[k + 1]; ++j) em_line(em, lines[(size_t)F.entry_src[j]], post2[j]);
+        const size_t t = (size_t)tx[(size_t)best2[k]];
+        r2 += taxa[t]; readsPerIdx[t]++; ++k;
+      } else r2 += '0';
+      r2 += '\n';
+    }
+    write_text(mapped + ".EM-filtered.refit", em);
+    write_text(mapped + ".EM-filtered.refit.reads2Taxon", r2 + unmapped_reads2taxon());
+    std::map<std::string, size_t> readsPer; std::map<std::string, double> fmap;
+    for (size_t t = 0; t < NT; ++t) { if (readsPerIdx[t]) readsPer[taxa[t]] = readsPerIdx[t]; fmap[taxa[t]] = f2[t]; }
+    { const double minF = 0.9 * (1.0 / (double)NR2); std::set<std::string> drop;   // cleanF (fEM.h:1135-1163) with the kept reads as ReadsMapped
+      for (auto& e : fmap) if (e.second < minF && !readsPer.count(e.first)) drop.insert(e.first);
+      for (auto& d : drop) fmap.erase(d);
+      double s = 0; for (auto& e : fmap) s += e.second; for (auto& e : fmap) e.second /= s; }
+    write_wimp(mapped + ".EM-filtered.refit.WIMP", *tax, fmap, readsPer, nTotal, nUnmapped + lost, nTooShort);
+    std::cout << "Refit: " << NR2 << " reads, " << NE2 << " mappings, " << lost << " reads lost every mapping, " << rounds << " EM iterations" << std::endl;
+  }
   void write_outputs() {
     Taxonomy& T = *tax;
     std::cout << "Outputting mappings with adjusted alignment qualities." << std::endl;
@@ -543,9 +632,7 @@ struct ClassifyRun {
         char num[64];
         for (size_t r = r0; r < r1; ++r) {                         // fEM.h:684-779
           for (size_t i = (size_t)off[r]; i < (size_t)off[r + 1]; ++i) {   // the line with field 14 replaced by std::to_string(posterior) (:705)
-            O.em.append(lines[i].p, (size_t)lines[i].last_space + 1);
-            append_f6(O.em, post[i]);
-            O.em += '\n';
+            em_line(O.em, lines[i], post[i]);
           }
           const size_t b = (size_t)best[r];
           const MapLine& B = lines[b];
@@ -617,6 +704,7 @@ struct ClassifyRun {
     if (boot.B > 0) { write_bootstrap(mapped + ".EM.WIMP.bootstrap", T, fmap, readsPer); pc.lap("c6b WIMP bootstrap"); }
     if (lca.on) { write_lca_reads(mapped + ".EM.reads2Taxon.lca"); write_kreport(mapped + ".EM.kreport", T, *lca_job, nTotal, nUnmapped + nTooShort); pc.lap("c6c LCA files"); }
     if (genes.on) { gene_analysis(); pc.lap("c6d gene-level analysis"); }
+    if (identf_opts.on) { identity_filter(); pc.lap("c6e identity filter"); }
     side_files.join();
     if (!unknown_written)
       std::cerr << "Warning: " << db << "/contigNstats_windowSize_1000.txt not found - " << mapped << ".EM.evidenceUnknownSpecies is not written." << std::endl;
@@ -663,12 +751,13 @@ struct ClassifyRun {
 };
 
 int classify_one(const std::vector<Dev>& devs, EmReduce reduce, const std::string& mapped, const std::string& db, size_t minReadsU,
-                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept, BootOpts boot, LcaOpts lca, GeneOpts genes, const CliSwitches& sw) {
+                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept, BootOpts boot, LcaOpts lca, GeneOpts genes, IdentOpts identf_opts, const CliSwitches& sw) {
   ClassifyRun run(devs, reduce, mapped, db, minReadsU, leave_now, need_devices, sw);
   run.kept = kept;
   run.boot = boot;
   run.lca = lca;
   run.genes = genes;
+  run.identf_opts = identf_opts;
   return run.run();
 }
 

@@ -62,8 +62,13 @@ struct LcaOpts { bool on = false; double tau = 0; };
 // --genes (classify, mapDirectly --then-classify; the reference's geneLevelAnalysis.pl): the gene- and annotation-level analysis of the reads' best
 // mappings against DB/DB_annotations.txt and DB/DB_proteins.faa.annotated.  Off without the flag: nothing changes and no file appears.
 struct GeneOpts { bool on = false; };
+// --min-identity T [--refit] (classify, mapDirectly --then-classify; the reference's util/filterLowIdentityEntities.pl): genomes whose best mappings have
+// a median identity below T (a decimal in [0, 1], the script's --identityThreshold) are removed and their reads set to unclassified in PREFIX.EM-filtered*;
+// --refit (not in the reference) also runs the EM again without the removed genomes' mappings.  Off without the flag: nothing changes and no file appears.
+struct IdentOpts { bool on = false, refit = false; double T = 0; };
 BootOpts boot_options(const Options& o);                         // (metamaps_main.cpp: they end the program on a malformed value)
 LcaOpts lca_options(const Options& o);
 GeneOpts gene_options(const Options& o);
+IdentOpts ident_options(const Options& o);
 
 }  // namespace

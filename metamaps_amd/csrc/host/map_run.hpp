@@ -938,7 +938,7 @@ struct MapRun {
       const bool last = fi + 1 == prefixes.size();
       KeptLines kl; kl.cname = &cname;
       if (keep_lines && fi < kept.size()) for (const auto& d : kept[fi]) kl.parts.push_back(KeptLines::Part{d->text.data(), d->meta.data(), d->meta.size(), d->off.data(), d->lens.size()});
-      classify_one(devs, reduce, prefixes[fi], o.v.at("then-classify"), minReadsU, last ? leave : std::function<void()>(), nullptr, keep_lines ? &kl : nullptr, boot_options(o), lca_options(o), gene_options(o), sw);
+      classify_one(devs, reduce, prefixes[fi], o.v.at("then-classify"), minReadsU, last ? leave : std::function<void()>(), nullptr, keep_lines ? &kl : nullptr, boot_options(o), lca_options(o), gene_options(o), ident_options(o), sw);
       if (keep_lines && fi < kept.size()) kept[fi].clear();
       for (auto& d : devs) mm_comm_destroy(d.ctx);
       pc.lap("9 classify");

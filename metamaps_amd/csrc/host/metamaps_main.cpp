@@ -7,7 +7,7 @@
 //
 //   metamaps mapDirectly [--all] [--compress-output] -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
-//   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]] [--lca T] [--genes]
+//   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]] [--lca T] [--genes] [--min-identity T [--refit]]
 //
 // --gpus N uses devices 0..N-1 of the node, one context per device on its own host thread (where the reference has -t N worker
 // threads, computeMap.hpp:104-176 / fEM.h:1229): mapping shards the read batches (index replicated) or the index chunks
@@ -62,6 +62,13 @@
 // (mm_gene_overlap, DESIGN.md §4 "Gene-level analysis").  PREFIX.EM.geneLevelAnalysis (gene, locus tag, protein, product, reads, median identity) and
 // PREFIX.EM.proteins.{GO,KEGG,BiGG,OG,COG} (feature, supporting reads, their share of the mapped reads) are added; every other output is unchanged.
 //
+// --min-identity T [--refit] (classify, mapDirectly --then-classify; the reference's util/filterLowIdentityEntities.pl, its README's "Filtering out WIMP entries
+// with low median identity"): T in [0, 1] is the script's --identityThreshold.  Genomes whose best mappings have a median identity (field 13 of the mapping
+// line, in percent) below 100 T are removed, on the first device (mm_ident_filter, DESIGN.md §4 "Identity filter").  PREFIX.extractedIdentities (every
+// read's largest identity, ascending), PREFIX.EM-filtered (the best mapping of every read that stays), PREFIX.EM-filtered.reads2Taxon (removed reads at 0)
+// and PREFIX.EM-filtered.WIMP are added; every other output is unchanged.  --refit (not in the reference) drops the removed genomes' mappings and runs the
+// EM again on what is left, so that a read whose best genome went can go to its next one: PREFIX.EM-filtered.refit, .refit.reads2Taxon, .refit.WIMP.
+//
 // Not provided: classifyU (disabled upstream).
 
 
@@ -90,7 +97,7 @@ Options parse(int argc, char** argv) {
     if (a == "--stream-chunks") { o.stream = true; continue; }
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
-    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--genes") { o.v[a.substr(2)] = "1"; continue; }
+    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
@@ -98,7 +105,10 @@ Options parse(int argc, char** argv) {
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
                    "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
                    "  --genes  (classify, mapDirectly --then-classify) gene-level analysis against DB_annotations.txt and DB_proteins.faa.annotated of the DB:\n"
-                   "         adds PREFIX.EM.geneLevelAnalysis and PREFIX.EM.proteins.{GO,KEGG,BiGG,OG,COG}\n";
+                   "         adds PREFIX.EM.geneLevelAnalysis and PREFIX.EM.proteins.{GO,KEGG,BiGG,OG,COG}\n"
+                   "  --min-identity T  (classify, mapDirectly --then-classify) T in [0, 1]: genomes whose best mappings have a median identity below T are removed and\n"
+                   "         their reads set to unclassified; adds PREFIX.extractedIdentities and PREFIX.EM-filtered{,.reads2Taxon,.WIMP}\n"
+                   "  --refit  (with --min-identity) also runs the EM again without the removed genomes' mappings; adds PREFIX.EM-filtered.refit{,.reads2Taxon,.WIMP}\n";
       exit(0);
     }
     std::string key = alias.count(a) ? alias.at(a) : (a.rfind("--", 0) == 0 ? a.substr(2) : "");
@@ -144,6 +154,20 @@ LcaOpts lca_options(const Options& o) {
 // --genes: a bare flag (GeneOpts, cli_common.hpp)
 GeneOpts gene_options(const Options& o) { GeneOpts g; g.on = o.v.count("genes") > 0; return g; }
 
+// --min-identity T [--refit]: validated here (IdentOpts, cli_common.hpp)
+IdentOpts ident_options(const Options& o) {
+  IdentOpts f;
+  f.refit = o.v.count("refit") > 0;
+  if (!o.v.count("min-identity")) { if (f.refit) die("--refit needs --min-identity T"); return f; }
+  const std::string& v = o.v.at("min-identity");
+  const bool decimal = !v.empty() && v.size() <= 32 && v.find_first_not_of("0123456789.") == std::string::npos && v.find_first_of("0123456789") != std::string::npos &&
+                       std::count(v.begin(), v.end(), '.') <= 1;
+  const double x = decimal ? strtod(v.c_str(), nullptr) : -1;
+  if (!decimal || !(x >= 0.0 && x <= 1.0)) die("--min-identity takes a decimal threshold from 0 to 1, not '" + v + "'");
+  f.on = true; f.T = x;
+  return f;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -168,6 +192,8 @@ int main(int argc, char** argv) {
     if (stat(gene::annotations_path(db).c_str(), &probe) != 0) die("--genes: please supply a gene-annotated database (file " + gene::annotations_path(db) + " not found).");
     if (stat(gene::proteins_path(db).c_str(), &probe) != 0) die("--genes: please supply a protein annotation file (file " + gene::proteins_path(db) + " not found).");
   }
+  const IdentOpts identf_opts = ident_options(o);
+  if ((identf_opts.on || identf_opts.refit) && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--min-identity and --refit need classify or mapDirectly --then-classify");
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
   if (mode == "mapDirectly" || mode == "index" || mode == "mapAgainstIndex") return map_mode(o, mode, sw);
   if (mode == "classify") {
@@ -198,8 +224,8 @@ int main(int argc, char** argv) {
     const size_t minReadsU = o.v.count("minreads") ? std::stoull(o.v.at("minreads")) : 10000;   // parseCmdArgs.hpp:462-471
     const std::vector<std::string> files = split(o.v.at("mappings"), ",");
     for (size_t fi = 0; fi < files.size(); ++fi) {
-      if (fi + 1 == files.size()) classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, [&] { since("mappings file done"); }, need_devices, nullptr, boot, lca, genes, sw);
-      else classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, nullptr, need_devices, nullptr, boot, lca, genes, sw);
+      if (fi + 1 == files.size()) classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, [&] { since("mappings file done"); }, need_devices, nullptr, boot, lca, genes, identf_opts, sw);
+      else classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, nullptr, need_devices, nullptr, boot, lca, genes, identf_opts, sw);
       need_devices();
       for (auto& d : devs) mm_comm_destroy(d.ctx);
       since("mappings file done");

@@ -9,6 +9,7 @@
 #include "mm_hpc.hpp"
 #include "mm_lca.hpp"
 #include "mm_gene.hpp"
+#include "mm_ident.hpp"
 #include <chrono>
 #include <new>
 #include <rccl/rccl.h>
@@ -955,6 +956,23 @@ int mm_gene_overlap(mm_ctx* ctx, int32_t n_contigs, const int64_t* contig_gene_o
                (n_groups == 0 || (group_reads && group_median)) && (group_feat_off[n_groups] <= 0 || group_feat), MM_ERR_ARG, "mm_gene_overlap: a null array");
     mm::gene_overlap_run(ctx, mm::GeneIn{n_contigs, contig_gene_off, gene_start, gene_stop, gene_group, n_groups, group_feat_off, group_feat, n_feats,
                                          n_maps, map_contig, map_start, map_stop, map_ident}, group_reads, group_median, feat_reads, maps_on_annotated);
+  });
+}
+int mm_ident_filter(mm_ctx* ctx, int64_t n_reads, const int64_t* read_off, const int32_t* taxon, const double* ident, const int64_t* best, int32_t n_taxa,
+                    double thr_percent, double* sorted_max, int64_t* n_with_entries, int64_t* n_le, int64_t* taxon_reads, double* taxon_median,
+                    uint8_t* taxon_removed, uint8_t* read_removed, int64_t* read_src, int64_t* entry_src, int64_t* read_off_out, int64_t* n_reads_out,
+                    int64_t* n_entries_out) {
+  if (!ctx) return MM_ERR_ARG;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(n_reads >= 0 && n_taxa >= 0 && read_off && n_with_entries && n_le, MM_ERR_ARG, "mm_ident_filter: a negative size, no offsets or no counts");
+    const int n_filtered = (read_src != nullptr) + (entry_src != nullptr) + (read_off_out != nullptr) + (n_reads_out != nullptr) + (n_entries_out != nullptr);
+    MM_REQUIRE(n_filtered == 0 || n_filtered == 5, MM_ERR_ARG, "mm_ident_filter: the outputs of the filtered problem are null as a group or not at all");
+    MM_REQUIRE((n_reads == 0 || (best && read_removed && sorted_max)) && (read_off[0] != 0 || n_reads == 0 || read_off[n_reads] <= 0 || (taxon && ident)) &&
+               (n_taxa == 0 || (taxon_reads && taxon_median && taxon_removed)), MM_ERR_ARG, "mm_ident_filter: a null array");
+    mm::ident_filter_run(ctx, mm::IdentIn{n_reads, read_off, taxon, ident, best, n_taxa, thr_percent},
+                         mm::IdentOut{sorted_max, n_with_entries, n_le, taxon_reads, taxon_median, taxon_removed, read_removed, read_src, entry_src, read_off_out,
+                                      n_reads_out, n_entries_out});
   });
 }
 
