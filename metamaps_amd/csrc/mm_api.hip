@@ -13,7 +13,7 @@
 #include <chrono>
 #include <new>
 #include <rccl/rccl.h>
-#include <rocprim/rocprim.hpp>
+#include "mm_prims.hpp"
 
 namespace mm {
 void seqset_upload(mm_seqset* s);
@@ -616,10 +616,8 @@ static mm_mapping* merge_parts_device(mm_ctx* ctx, int64_t n, const std::vector<
     const unsigned gb = (unsigned)mm::ceil_div(n + 1, 256);
     merge_count_kernel<<<dim3(gb), dim3(256), 0, st>>>(d_parts.p, (int)parts.size(), n, cnt.p);
     MM_KERNEL_CHECK();
-    size_t tmp_bytes = 0;
-    MM_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, cnt.p, M->rec_off.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
-    mm::DBuf<uint8_t> tmp(std::max<size_t>(tmp_bytes, 1));
-    MM_HIP(rocprim::exclusive_scan(tmp.p, tmp_bytes, cnt.p, M->rec_off.p, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), st));
+    mm::DBuf<uint8_t> tmp;
+    mm::exclusive_scan(tmp, cnt.p, M->rec_off.p, (size_t)n + 1, st);
     M->h_rec_off = M->rec_off.to_host(st);
     M->n_rec = (int64_t)M->h_rec_off[(size_t)n];
     M->rec.alloc(std::max<size_t>((size_t)M->n_rec, 1));

@@ -9,16 +9,16 @@
 //   (c)       (mapping, group) pairs at their offsets; reads per group with 64-bit vector atomics
 //   (e)       every pair expands to keys feature << mb | mapping through group_feat_off; the keys are radix-sorted; heads of runs of equal
 //             keys are counted per feature (a mapping counts once per feature however many of its genes carry it)
-//   (d)       identities get ranks from one sort of their bit patterns (non-negative doubles order as their 64-bit patterns); a second walk
+//   (d)       identities get ranks from one sort of their bit patterns (mm_prims.hpp, rank_by_bits; non-negative doubles order as their 64-bit patterns); a second walk
 //             writes the keys group << rb | rank into the group's range [first[g], first[g] + n_g) (first: the scan of the reads per group;
 //             the place inside the range comes from a cursor, the sort that follows makes it immaterial); the keys are radix-sorted; the
 //             median of group g is the identity whose rank sits at first[g] + (n_g - 1) / 2
 // Tiling: (c) and (e) run over ranges of mappings that hold at most `budget` pairs and `budget` feature keys (a single mapping beyond it is a
 // range of its own), group and feature counts add up; (d) runs over ranges of groups that hold at most `budget` keys, each with a walk over
 // all mappings that keeps the range's groups — a group's selection is never split.  No result depends on the budget.
-// All pair, key and mapping indices are 64-bit; positions are int32.
+// The sorts and scans are rocprim's, through mm_prims.hpp, and share the job's one scratch buffer.  All pair, key and mapping indices are 64-bit; positions are int32.
 #include "mm_gene.hpp"
-#include <rocprim/rocprim.hpp>
+#include "mm_prims.hpp"
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -111,10 +111,6 @@ __global__ void __launch_bounds__(256) gene_rank_kernel(const uint32_t* __restri
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) rank[perm[i]] = (uint32_t)i;
 }
-__global__ void __launch_bounds__(256) gene_iota_kernel(uint32_t* __restrict__ v, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) v[i] = (uint32_t)i;
-}
 // (e) feature ids per pair (nf[n] = 0 for the scan's total), then the keys
 __global__ void __launch_bounds__(256) gene_pair_feats_kernel(const int32_t* __restrict__ pair_group, int64_t n, const int64_t* __restrict__ foff, uint64_t* __restrict__ nf) {
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -156,27 +152,10 @@ __global__ void __launch_bounds__(256) gene_select_kernel(int32_t g0, int32_t g1
 
 namespace {
 
-int bits_for(uint64_t n) { int b = 1; while (b < 64 && (n >> b)) ++b; return b; }   // bits that hold 0 .. n
 unsigned walk_grid(int64_t n) { return (unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div(n, 256), 1), 2048); }
-unsigned flat_grid(int64_t n) { return (unsigned)std::max<int64_t>(ceil_div(n, 256), 1); }
-
-// MM_GENE_TIMING=1: the stages' device times (events on the context's stream) on stderr
-struct GeneClock {
-  const bool on = getenv("MM_GENE_TIMING") != nullptr;
-  hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
-  double ms[6] = {0, 0, 0, 0, 0, 0};                               // ranks, count, scan, fill, features, medians
-  explicit GeneClock(hipStream_t s) : st(s) { if (on) { MM_HIP(hipEventCreate(&a)); MM_HIP(hipEventCreate(&b)); } }
-  ~GeneClock() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  void start() { if (on) MM_HIP(hipEventRecord(a, st)); }
-  void stop(int k) { if (!on) return; MM_HIP(hipEventRecord(b, st)); MM_HIP(hipEventSynchronize(b)); float t = 0; MM_HIP(hipEventElapsedTime(&t, a, b)); ms[k] += t; }
-  void report(int64_t pairs, int64_t keys, size_t map_tiles, size_t group_tiles) const {
-    if (on) fprintf(stderr, "MM_GENE_TIMING ranks %.3f count %.3f scan %.3f fill %.3f features %.3f medians %.3f ms; %lld pairs, %lld feature keys, %zu mapping tiles, %zu group tiles\n",
-                    ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], (long long)pairs, (long long)keys, map_tiles, group_tiles);
-  }
-};
-
 struct GeneJob {
-  const GeneIn& in; hipStream_t st; int64_t budget; GeneClock clk;
+  const GeneIn& in; hipStream_t st; int64_t budget;
+  StageClock<6> clk;                                               // MM_GENE_TIMING=1: ranks, count, scan, fill, features, medians on stderr
   int64_t NG = 0, NM = 0; int rb = 1;
   DBuf<int64_t> d_off, d_foff; DBuf<int32_t> d_start, d_stop, d_pmax, d_group, d_feat, d_mc, d_ms, d_me;
   DBuf<uint32_t> d_rank; DBuf<uint64_t> d_ident_sorted, d_cnt, d_kcnt, d_pair_off, d_key_off, d_first;
@@ -185,19 +164,11 @@ struct GeneJob {
   std::vector<uint64_t> h_pair_off, h_key_off;
   GeneTable T{}; GeneMapsDev M{};
 
-  GeneJob(const GeneIn& in_, hipStream_t st_, int64_t budget_) : in(in_), st(st_), budget(budget_), clk(st_) {}
+  GeneJob(const GeneIn& in_, hipStream_t st_, int64_t budget_) : in(in_), st(st_), budget(budget_), clk(getenv("MM_GENE_TIMING") != nullptr, st_) {}
 
-  void scan(const uint64_t* src, uint64_t* dst, size_t n) {
-    size_t bytes = 0;
-    MM_HIP(rocprim::exclusive_scan(nullptr, bytes, src, dst, (uint64_t)0, n, rocprim::plus<uint64_t>(), st));
-    if (tmp.n < bytes) tmp.alloc(bytes);
-    MM_HIP(rocprim::exclusive_scan(tmp.p, bytes, src, dst, (uint64_t)0, n, rocprim::plus<uint64_t>(), st));
-  }
-  void sort_keys(uint64_t* src, uint64_t* dst, size_t n, int bits) {
-    size_t bytes = 0;
-    MM_HIP(rocprim::radix_sort_keys(nullptr, bytes, src, dst, n, 0, (unsigned)bits, st));
-    if (tmp.n < bytes) tmp.alloc(bytes);
-    MM_HIP(rocprim::radix_sort_keys(tmp.p, bytes, src, dst, n, 0, (unsigned)bits, st));
+  void report(size_t map_tiles, size_t group_tiles) const {
+    if (clk.on) fprintf(stderr, "MM_GENE_TIMING ranks %.3f count %.3f scan %.3f fill %.3f features %.3f medians %.3f ms; %lld pairs, %lld feature keys, %zu mapping tiles, %zu group tiles\n",
+                        clk.ms[0], clk.ms[1], clk.ms[2], clk.ms[3], clk.ms[4], clk.ms[5], (long long)h_pair_off[(size_t)NM], (long long)h_key_off[(size_t)NM], map_tiles, group_tiles);
   }
   void upload() {
     NG = in.contig_gene_off[in.n_contigs]; NM = in.n_maps;
@@ -230,11 +201,7 @@ struct GeneJob {
     DBuf<uint64_t> d_bits(nm); DBuf<uint32_t> d_iota(nm), d_perm(nm);
     d_bits.upload(bits.data(), nm, st);
     d_ident_sorted.alloc(nm); d_rank.alloc(nm);
-    gene_iota_kernel<<<dim3(flat_grid(NM)), dim3(256), 0, st>>>(d_iota.p, NM); MM_KERNEL_CHECK();
-    size_t bytes = 0;
-    MM_HIP(rocprim::radix_sort_pairs(nullptr, bytes, d_bits.p, d_ident_sorted.p, d_iota.p, d_perm.p, nm, 0, 64, st));
-    if (tmp.n < bytes) tmp.alloc(bytes);
-    MM_HIP(rocprim::radix_sort_pairs(tmp.p, bytes, d_bits.p, d_ident_sorted.p, d_iota.p, d_perm.p, nm, 0, 64, st));
+    rank_by_bits(tmp, d_bits.p, d_ident_sorted.p, d_iota.p, d_perm.p, nm, st);
     gene_rank_kernel<<<dim3(flat_grid(NM)), dim3(256), 0, st>>>(d_perm.p, NM, d_rank.p); MM_KERNEL_CHECK();
     MM_HIP(mm::stream_sync(st));                                   // (bits, and the buffers of this scope)
     clk.stop(0);
@@ -249,7 +216,7 @@ struct GeneJob {
     MM_KERNEL_CHECK();
     clk.stop(1);
     clk.start();
-    scan(d_cnt.p, d_pair_off.p, nm + 1); scan(d_kcnt.p, d_key_off.p, nm + 1);
+    exclusive_scan(tmp, d_cnt.p, d_pair_off.p, nm + 1, st); exclusive_scan(tmp, d_kcnt.p, d_key_off.p, nm + 1, st);
     h_pair_off = d_pair_off.to_host(st); h_key_off = d_key_off.to_host(st);
     clk.stop(2);
   }
@@ -266,9 +233,9 @@ struct GeneJob {
     clk.start();
     const int mb = bits_for((uint64_t)(m1 - m0));
     gene_pair_feats_kernel<<<dim3(flat_grid(np + 1)), dim3(256), 0, st>>>(pair_group.p, np, d_foff.p, nf.p); MM_KERNEL_CHECK();
-    scan(nf.p, koff.p, (size_t)np + 1);
+    exclusive_scan(tmp, nf.p, koff.p, (size_t)np + 1, st);
     gene_expand_kernel<<<dim3(flat_grid(np)), dim3(256), 0, st>>>(pair_map.p, pair_group.p, np, m0, d_foff.p, d_feat.p, koff.p, mb, keys.p); MM_KERNEL_CHECK();
-    sort_keys(keys.p, keys2.p, (size_t)nk, mb + bits_for((uint64_t)in.n_feats));
+    sort_keys(tmp, keys.p, keys2.p, (size_t)nk, 0, mb + bits_for((uint64_t)in.n_feats), st);
     gene_heads_kernel<<<dim3(flat_grid(ceil_div(nk, GENE_HEAD_ITEMS))), dim3(256), 0, st>>>(keys2.p, nk, mb, d_feat_reads.p); MM_KERNEL_CHECK();
     clk.stop(4);
   }
@@ -316,7 +283,7 @@ struct GeneJob {
       if (nk > 0) {
         gene_walk_kernel<<<dim3(walk_grid(NM)), dim3(256), 0, st>>>(T, M, (int64_t)0, NM, GeneMedianOp{d_group.p, g0, g1, d_first.p, f0, d_cursor.p, d_rank.p, rb, keys.p});
         MM_KERNEL_CHECK();
-        sort_keys(keys.p, keys2.p, (size_t)nk, rb + bits_for((uint64_t)(g1 - g0)));
+        sort_keys(tmp, keys.p, keys2.p, (size_t)nk, 0, rb + bits_for((uint64_t)(g1 - g0)), st);
       }
       gene_select_kernel<<<dim3(flat_grid(g1 - g0)), dim3(256), 0, st>>>(g0, g1, d_group_reads.p, d_first.p, f0, keys2.p, rb, d_ident_sorted.p, med.p); MM_KERNEL_CHECK();
     }
@@ -360,7 +327,7 @@ void gene_overlap_run(mm_ctx* ctx, const GeneIn& in, int64_t* group_reads, doubl
   std::copy(h_reads.begin(), h_reads.end(), group_reads);
   if (feat_reads) { J.d_feat_reads.download((unsigned long long*)feat_reads, (size_t)in.n_feats, J.st); MM_HIP(mm::stream_sync(J.st)); }
   const size_t group_tiles = J.h_pair_off[(size_t)in.n_maps] > 0 ? J.medians(h_reads, group_median) : 0;
-  J.clk.report((int64_t)J.h_pair_off[(size_t)in.n_maps], (int64_t)J.h_key_off[(size_t)in.n_maps], map_tiles, group_tiles);
+  J.report(map_tiles, group_tiles);
 }
 
 }  // namespace mm

@@ -1,34 +1,26 @@
 // The identity filter of an EM problem (classify --min-identity; the reference does it in util/filterLowIdentityEntities.pl; DESIGN.md section 4,
 // "Identity filter"; the definition: mm_ident_core.hpp).  All of it runs on the device:
-//   reads     ident_reads_kernel runs mm_ident_core.hpp's ident_read for every read, in the shape of mm_lca.hip: four consecutive reads per
-//             wavefront, a group of 16 lanes each with one entry per lane, for reads of <= IDENT_GROUP entries; the whole wavefront strides over a
+//   reads     ident_reads_kernel runs mm_ident_core.hpp's ident_read for every read, in the loop of mm_lca.hip (mm_prims.hpp, for_each_read_tile):
+//             four consecutive reads per wavefront, a group of 16 lanes each with one entry per lane, for reads of <= IDENT_GROUP entries; the whole wavefront strides over a
 //             longer read.  It leaves the bits of read_max[r] and of ident[best[r]] (IDENT_NONE for a read without entries: behind every
 //             identity), taxon[best[r]] (n_taxa for such a read: a bucket behind every taxon) and counts the reads per taxon with 64-bit vector
 //             atomics.  A maximum is the same in either shape, so the split point changes no result.
 //   sort      one radix sort of the read_max bits (non-negative doubles order as their 64-bit patterns) gives sorted_max; two binary searches
 //             give the number of reads with entries (the first IDENT_NONE) and n_le (the first pattern above the threshold's)
-//   medians   as stage (d) of mm_gene.hip: the best identities are sorted with their read indices and every read gets its global rank; the keys
+//   medians   as stage (d) of mm_gene.hip, from the same rank_by_bits: the best identities are sorted with their read indices and every read gets its global rank; the keys
 //             taxon << rb | rank are radix-sorted; first[] is the scan of the reads per taxon; the median of taxon t is the identity whose rank
 //             sits at first[t] + n_t / 2; removed[t] follows
 //   compact   read_removed[r] from removed[]; a flag per entry (its taxon is not removed), an exclusive scan, a flag per read (its scanned range
 //             is not empty), a second scan, and a scatter of the kept indices: entry_src, read_src, read_off_out
-// The buffers are not tiled: the job holds 12 bytes per entry on top of the inputs and 48 per read, far below the EM problem that is resident
+// The sorts and scans are rocprim's, through mm_prims.hpp, and share the job's one scratch buffer.  The buffers are not tiled: the job holds 12 bytes per entry on top of the inputs and 48 per read, far below the EM problem that is resident
 // beside it.  Entry and read indices are 64-bit; ranks are 32-bit, hence MM_ERR_LIMIT at 2^32 reads.
 #include "mm_ident.hpp"
-#include <rocprim/rocprim.hpp>
+#include "mm_prims.hpp"
 #include <algorithm>
 #include <limits>
 
 namespace mm {
 
-template <int W> struct IdentLanes {                              // W consecutive lanes of a wavefront (W a power of two)
-  __device__ int lane() const { return (int)(threadIdx.x & (W - 1)); }
-  __device__ int width() const { return W; }
-  __device__ uint64_t max(uint64_t x) const {                     // (a butterfly: the same bits in every lane)
-    for (int d = W / 2; d > 0; d >>= 1) { const uint64_t y = (uint64_t)__shfl_xor((unsigned long long)x, d, W); x = y > x ? y : x; }
-    return x;
-  }
-};
 struct IdentOwnEntry {                                            // the one entry of this lane (0 for a lane without one: below or equal to every identity)
   uint64_t b;
   __device__ uint64_t bits(int64_t) const { return b; }
@@ -46,27 +38,17 @@ __device__ inline void ident_store(const IdentReadsArgs& a, int64_t r, int64_t n
   atomicAdd(&a.taxon_reads[t], 1ull);
 }
 __global__ void __launch_bounds__(256) ident_reads_kernel(IdentReadsArgs a) {
-  constexpr int PER_WAVE = 64 / IDENT_GROUP;
-  const int lane = threadIdx.x & 63, gl = lane & (IDENT_GROUP - 1), grp = lane / IDENT_GROUP;
-  const int64_t n_waves = (int64_t)gridDim.x * 4, wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  for (int64_t r0 = wave * PER_WAVE; r0 < a.n_reads; r0 += n_waves * PER_WAVE) {   // (the same for every lane of the wavefront)
-    {                                                              // the tile's short reads, and its reads without entries
-      const int64_t r = r0 + grp;
-      int64_t lo = 0, n = 0;
-      if (r < a.n_reads) { lo = a.read_off[r]; n = a.read_off[r + 1] - lo; }
-      const bool mine = r < a.n_reads && n <= IDENT_GROUP;
+  for_each_read_tile<IDENT_GROUP>(a.read_off, a.n_reads,
+    [&](int64_t r, int64_t lo, int64_t n, bool mine, int gl) {    // the tile's short reads, and its reads without entries
       IdentOwnEntry e{0};
       if (mine && gl < n) e.b = ident_bits(a.ident[lo + gl]);
-      const uint64_t mx = ident_read(IdentLanes<IDENT_GROUP>{}, e, mine ? n : 0);
+      const uint64_t mx = ident_read(Lanes<IDENT_GROUP>{}, e, mine ? n : 0);
       if (mine && gl == 0) ident_store(a, r, n, mx);
-    }
-    for (int q = 0; q < PER_WAVE && r0 + q < a.n_reads; ++q) {     // its long reads, one after the other
-      const int64_t lo = a.read_off[r0 + q], n = a.read_off[r0 + q + 1] - lo;
-      if (n <= IDENT_GROUP) continue;
-      const uint64_t mx = ident_read(IdentLanes<64>{}, IdentReadEntries{a.ident, lo}, n);
-      if (lane == 0) ident_store(a, r0 + q, n, mx);
-    }
-  }
+    },
+    [&](int64_t r, int64_t lo, int64_t n) {                       // its long reads, one after the other
+      const uint64_t mx = ident_read(Lanes<64>{}, IdentReadEntries{a.ident, lo}, n);
+      if (Lanes<64>{}.lane() == 0) ident_store(a, r, n, mx);
+    });
 }
 
 // first index of the ascending a[0, n) with a[i] >= x (lower) or a[i] > x (upper)
@@ -81,10 +63,6 @@ __global__ void ident_counts_kernel(const uint64_t* __restrict__ sorted, int64_t
   const int64_t with = ident_bound(sorted, n, IDENT_NONE, false);
   counts[0] = with;
   counts[1] = le_none ? 0 : ident_bound(sorted, with, thr_bits, true);
-}
-__global__ void __launch_bounds__(256) ident_iota_kernel(uint32_t* __restrict__ v, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) v[i] = (uint32_t)i;
 }
 // perm[i]: the read at global rank i of the best identities; the key of that read
 __global__ void __launch_bounds__(256) ident_keys_kernel(const uint32_t* __restrict__ perm, int64_t n, const int32_t* __restrict__ best_taxon, int rb, uint64_t* __restrict__ keys) {
@@ -131,44 +109,19 @@ __global__ void __launch_bounds__(256) ident_scatter_reads_kernel(const uint8_t*
 
 namespace {
 
-int ident_bits_for(uint64_t n) { int b = 1; while (b < 64 && (n >> b)) ++b; return b; }   // bits that hold 0 .. n
-unsigned ident_flat_grid(int64_t n) { return (unsigned)std::max<int64_t>(ceil_div(n, 256), 1); }
-
-// MM_IDENT_TIMING=1: the stages' device times (events on the context's stream) on stderr
-struct IdentClock {
-  const bool on = getenv("MM_IDENT_TIMING") != nullptr;
-  hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
-  double ms[4] = {0, 0, 0, 0};                                     // reads, sort, medians, compact
-  explicit IdentClock(hipStream_t s) : st(s) { if (on) { MM_HIP(hipEventCreate(&a)); MM_HIP(hipEventCreate(&b)); } }
-  ~IdentClock() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  void start() { if (on) MM_HIP(hipEventRecord(a, st)); }
-  void stop(int k) { if (!on) return; MM_HIP(hipEventRecord(b, st)); MM_HIP(hipEventSynchronize(b)); float t = 0; MM_HIP(hipEventElapsedTime(&t, a, b)); ms[k] += t; }
-  void report(int64_t reads, int64_t entries) const {
-    if (on) fprintf(stderr, "MM_IDENT_TIMING reads %.3f sort %.3f medians %.3f compact %.3f ms; %lld reads, %lld entries\n", ms[0], ms[1], ms[2], ms[3], (long long)reads, (long long)entries);
-  }
-};
-
 struct IdentJob {
-  const IdentIn& in; const IdentOut& out; hipStream_t st; IdentClock clk;
+  const IdentIn& in; const IdentOut& out; hipStream_t st;
+  StageClock<4> clk;                                               // MM_IDENT_TIMING=1: reads, sort, medians, compact on stderr
   const int64_t NR, NE; const size_t nr, ne, nt;
   DBuf<int64_t> d_off, d_best, d_counts; DBuf<int32_t> d_taxon, d_best_taxon; DBuf<double> d_ident;
   DBuf<uint64_t> d_max_bits, d_best_bits, d_sorted_max, d_best_sorted, d_median; DBuf<unsigned long long> d_taxon_reads; DBuf<uint8_t> d_removed, d_read_removed;
   DBuf<uint8_t> tmp;
 
   IdentJob(const IdentIn& in_, const IdentOut& out_, hipStream_t st_)
-      : in(in_), out(out_), st(st_), clk(st_), NR(in_.n_reads), NE(in_.read_off[in_.n_reads]), nr((size_t)NR), ne((size_t)NE), nt((size_t)in_.n_taxa) {}
+      : in(in_), out(out_), st(st_), clk(getenv("MM_IDENT_TIMING") != nullptr, st_), NR(in_.n_reads), NE(in_.read_off[in_.n_reads]), nr((size_t)NR), ne((size_t)NE), nt((size_t)in_.n_taxa) {}
 
-  void sort_keys(uint64_t* src, uint64_t* dst, size_t n, int bits) {
-    size_t bytes = 0;
-    MM_HIP(rocprim::radix_sort_keys(nullptr, bytes, src, dst, n, 0, (unsigned)bits, st));
-    if (tmp.n < bytes) tmp.alloc(bytes);
-    MM_HIP(rocprim::radix_sort_keys(tmp.p, bytes, src, dst, n, 0, (unsigned)bits, st));
-  }
-  template <class In> void scan(const In* src, int64_t* dst, size_t n) {
-    size_t bytes = 0;
-    MM_HIP(rocprim::exclusive_scan(nullptr, bytes, src, dst, (int64_t)0, n, rocprim::plus<int64_t>(), st));
-    if (tmp.n < bytes) tmp.alloc(bytes);
-    MM_HIP(rocprim::exclusive_scan(tmp.p, bytes, src, dst, (int64_t)0, n, rocprim::plus<int64_t>(), st));
+  void report() const {
+    if (clk.on) fprintf(stderr, "MM_IDENT_TIMING reads %.3f sort %.3f medians %.3f compact %.3f ms; %lld reads, %lld entries\n", clk.ms[0], clk.ms[1], clk.ms[2], clk.ms[3], (long long)NR, (long long)NE);
   }
   void reads() {
     d_off.alloc(nr + 1); d_off.upload(in.read_off, nr + 1, st);
@@ -178,7 +131,7 @@ struct IdentJob {
     d_max_bits.alloc(nr); d_best_bits.alloc(nr); d_best_taxon.alloc(nr);
     d_taxon_reads.alloc(nt + 1); d_taxon_reads.zero(st);           // ([n_taxa] stays 0: the scan's total)
     clk.start();
-    const dim3 grid((unsigned)std::min<int64_t>(ceil_div(NR, 256 / IDENT_GROUP), 2048)), blk(256);
+    const dim3 grid(read_tile_grid<IDENT_GROUP>(NR)), blk(256);
     ident_reads_kernel<<<grid, blk, 0, st>>>(IdentReadsArgs{d_off.p, d_taxon.p, d_ident.p, d_best.p, NR, in.n_taxa, d_max_bits.p, d_best_bits.p, d_best_taxon.p, d_taxon_reads.p});
     MM_KERNEL_CHECK();
     clk.stop(0);
@@ -186,7 +139,7 @@ struct IdentJob {
   void sort_max() {
     clk.start();
     d_sorted_max.alloc(nr); d_counts.alloc(2);
-    sort_keys(d_max_bits.p, d_sorted_max.p, nr, 64);
+    sort_keys(tmp, d_max_bits.p, d_sorted_max.p, nr, 0, 64, st);
     ident_counts_kernel<<<dim3(1), dim3(64), 0, st>>>(d_sorted_max.p, NR, ident_bits(in.thr < 0 ? 0.0 : in.thr), in.thr < 0, d_counts.p); MM_KERNEL_CHECK();
     const std::vector<int64_t> c = d_counts.to_host(st);
     clk.stop(1);
@@ -196,21 +149,17 @@ struct IdentJob {
   }
   void medians() {
     clk.start();
-    const int rb = ident_bits_for((uint64_t)NR), tb = ident_bits_for((uint64_t)in.n_taxa);
+    const int rb = bits_for((uint64_t)NR), tb = bits_for((uint64_t)in.n_taxa);
     DBuf<uint32_t> d_iota(nr), d_perm(nr); DBuf<uint64_t> d_keys(nr), d_keys2(nr); DBuf<int64_t> d_first(nt + 1);
     d_best_sorted.alloc(nr); d_median.alloc(std::max<size_t>(nt, 1)); d_removed.alloc(std::max<size_t>(nt, 1));
-    ident_iota_kernel<<<dim3(ident_flat_grid(NR)), dim3(256), 0, st>>>(d_iota.p, NR); MM_KERNEL_CHECK();
-    size_t bytes = 0;
-    MM_HIP(rocprim::radix_sort_pairs(nullptr, bytes, d_best_bits.p, d_best_sorted.p, d_iota.p, d_perm.p, nr, 0, 64, st));
-    if (tmp.n < bytes) tmp.alloc(bytes);
-    MM_HIP(rocprim::radix_sort_pairs(tmp.p, bytes, d_best_bits.p, d_best_sorted.p, d_iota.p, d_perm.p, nr, 0, 64, st));
-    ident_keys_kernel<<<dim3(ident_flat_grid(NR)), dim3(256), 0, st>>>(d_perm.p, NR, d_best_taxon.p, rb, d_keys.p); MM_KERNEL_CHECK();
-    sort_keys(d_keys.p, d_keys2.p, nr, rb + tb);
-    scan(d_taxon_reads.p, d_first.p, nt + 1);
-    ident_select_kernel<<<dim3(ident_flat_grid(in.n_taxa)), dim3(256), 0, st>>>(in.n_taxa, d_taxon_reads.p, d_first.p, d_keys2.p, rb, d_best_sorted.p, in.thr, d_median.p, d_removed.p);
+    rank_by_bits(tmp, d_best_bits.p, d_best_sorted.p, d_iota.p, d_perm.p, nr, st);
+    ident_keys_kernel<<<dim3(flat_grid(NR)), dim3(256), 0, st>>>(d_perm.p, NR, d_best_taxon.p, rb, d_keys.p); MM_KERNEL_CHECK();
+    sort_keys(tmp, d_keys.p, d_keys2.p, nr, 0, rb + tb, st);
+    exclusive_scan(tmp, d_taxon_reads.p, d_first.p, nt + 1, st);
+    ident_select_kernel<<<dim3(flat_grid(in.n_taxa)), dim3(256), 0, st>>>(in.n_taxa, d_taxon_reads.p, d_first.p, d_keys2.p, rb, d_best_sorted.p, in.thr, d_median.p, d_removed.p);
     MM_KERNEL_CHECK();
     d_read_removed.alloc(nr);
-    ident_read_removed_kernel<<<dim3(ident_flat_grid(NR)), dim3(256), 0, st>>>(d_best_taxon.p, NR, in.n_taxa, d_removed.p, d_read_removed.p); MM_KERNEL_CHECK();
+    ident_read_removed_kernel<<<dim3(flat_grid(NR)), dim3(256), 0, st>>>(d_best_taxon.p, NR, in.n_taxa, d_removed.p, d_read_removed.p); MM_KERNEL_CHECK();
     static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counts are copied as they lie");
     d_taxon_reads.download((unsigned long long*)out.taxon_reads, nt, st);
     d_median.download((uint64_t*)out.taxon_median, nt, st);
@@ -222,12 +171,12 @@ struct IdentJob {
   void compact() {
     clk.start();
     DBuf<uint8_t> d_ekeep(ne + 1), d_rkeep(nr + 1); DBuf<int64_t> d_epos(ne + 1), d_rpos(nr + 1), d_entry_src(ne), d_read_src(nr), d_off_out(nr + 1);
-    ident_entry_flags_kernel<<<dim3(ident_flat_grid(NE + 1)), dim3(256), 0, st>>>(d_taxon.p, NE, d_removed.p, d_ekeep.p); MM_KERNEL_CHECK();
-    scan(d_ekeep.p, d_epos.p, ne + 1);
-    ident_read_flags_kernel<<<dim3(ident_flat_grid(NR + 1)), dim3(256), 0, st>>>(d_off.p, NR, d_epos.p, d_rkeep.p); MM_KERNEL_CHECK();
-    scan(d_rkeep.p, d_rpos.p, nr + 1);
-    ident_scatter_entries_kernel<<<dim3(ident_flat_grid(NE)), dim3(256), 0, st>>>(d_ekeep.p, d_epos.p, NE, d_entry_src.p); MM_KERNEL_CHECK();
-    ident_scatter_reads_kernel<<<dim3(ident_flat_grid(NR + 1)), dim3(256), 0, st>>>(d_rkeep.p, d_rpos.p, NR, d_off.p, d_epos.p, d_read_src.p, d_off_out.p); MM_KERNEL_CHECK();
+    ident_entry_flags_kernel<<<dim3(flat_grid(NE + 1)), dim3(256), 0, st>>>(d_taxon.p, NE, d_removed.p, d_ekeep.p); MM_KERNEL_CHECK();
+    exclusive_scan(tmp, d_ekeep.p, d_epos.p, ne + 1, st);
+    ident_read_flags_kernel<<<dim3(flat_grid(NR + 1)), dim3(256), 0, st>>>(d_off.p, NR, d_epos.p, d_rkeep.p); MM_KERNEL_CHECK();
+    exclusive_scan(tmp, d_rkeep.p, d_rpos.p, nr + 1, st);
+    ident_scatter_entries_kernel<<<dim3(flat_grid(NE)), dim3(256), 0, st>>>(d_ekeep.p, d_epos.p, NE, d_entry_src.p); MM_KERNEL_CHECK();
+    ident_scatter_reads_kernel<<<dim3(flat_grid(NR + 1)), dim3(256), 0, st>>>(d_rkeep.p, d_rpos.p, NR, d_off.p, d_epos.p, d_read_src.p, d_off_out.p); MM_KERNEL_CHECK();
     int64_t n_e = 0, n_r = 0;
     d_epos.download(&n_e, 1, st, ne); d_rpos.download(&n_r, 1, st, nr);
     MM_HIP(mm::stream_sync(st));
@@ -258,7 +207,7 @@ void ident_filter_run(mm_ctx* ctx, const IdentIn& in, const IdentOut& out) {
   J.medians();
   if (filtered) J.compact();
   MM_HIP(mm::stream_sync(J.st));
-  J.clk.report(J.NR, J.NE);
+  J.report();
 }
 
 }  // namespace mm

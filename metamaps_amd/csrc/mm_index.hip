@@ -4,7 +4,7 @@
 // flags for the L2 sliding window, occurrence histogram.
 #include "mm_index.hpp"
 #include "mm_minimizer.hpp"
-#include <rocprim/rocprim.hpp>
+#include "mm_prims.hpp"
 #include <algorithm>
 #include <cstdlib>
 
@@ -349,10 +349,7 @@ void index_build(mm_ctx* ctx, const mm_seqset* contigs, int k, int w, mm_index* 
   I->occ.alloc((size_t)N + 2);                                  // +2: the seed-hit filter reads lists in aligned 16-byte pieces
   DBuf<uint8_t> sort_tmp;                                        // the library's double buffers (12 B per element), kept across the partitions: every
   auto library_sort = [&](uint32_t* kin, uint64_t* vin, uint32_t* kout, uint64_t* vout, size_t cnt) {   // fresh 18 GB block is recycled memory the driver clears first
-    size_t tmp_bytes = 0;
-    MM_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, kin, kout, vin, vout, cnt, 0, 32, st));
-    if (sort_tmp.bytes() < tmp_bytes) sort_tmp.alloc(tmp_bytes);
-    MM_HIP(rocprim::radix_sort_pairs(sort_tmp.p, tmp_bytes, kin, kout, vin, vout, cnt, 0, 32, st));
+    sort_pairs(sort_tmp, kin, kout, vin, vout, cnt, 0, 32, st);
     MM_HIP(mm::stream_sync(st));
   };
   const char* pm_env = getenv("MM_INDEX_PART_MAX");              // tests force the partitioned path on small inputs
@@ -384,9 +381,8 @@ void index_build(mm_ctx* ctx, const mm_seqset* contigs, int k, int w, mm_index* 
     DBuf<uint64_t> toff((size_t)ntile + 1), scan_tmp2;
     int64_t maxp = 0; for (auto c : part_cnt) maxp = std::max(maxp, c);
     key_in.alloc((size_t)maxp); val_in.alloc((size_t)maxp);
-    { size_t tb = 0;                                             // (sized for the largest partition once)
-      MM_HIP(rocprim::radix_sort_pairs(nullptr, tb, key_in.p, key_out.p, val_in.p, I->occ.p, (size_t)maxp, 0, 32, st));
-      sort_tmp.alloc(tb + (tb >> 6)); }
+    { const size_t tb = scratch_bytes([&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, key_in.p, key_out.p, val_in.p, I->occ.p, (size_t)maxp, 0, 32, st); });
+      sort_tmp.alloc(tb + (tb >> 6)); }                          // (sized for the largest partition once)
     int64_t done = 0;
     for (size_t p = 0; p < parts.size(); ++p) {
       if (part_cnt[p] == 0) continue;

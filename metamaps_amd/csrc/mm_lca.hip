@@ -5,24 +5,18 @@
 //                tin and posterior of the entry stay in registers, every pass is a butterfly over the group;
 //   long reads   (repeat-rich samples: thousands of entries) the whole wavefront strides over the read's entries, pass after pass; the
 //                entries come from memory again (the loads hit the cache), the reductions are butterflies over 64 lanes.
-// Both classes of a tile of four reads are handled by the wavefront that owns the tile; the loops of lca_read run while ANY lane of the
+// Both classes of a tile of four reads are handled by the wavefront that owns the tile (the loop over the tiles and the lanes' butterflies:
+// mm_prims.hpp, for_each_read_tile and Lanes<W>; the kernel hands it the two routines); the loops of lca_read run while ANY lane of the
 // wavefront needs them (groups that are done idle), so every shuffle is executed by all 64 lanes.  A sum that is exact in double is the same
 // in either shape, so the split point does not change such results.
 // tin / tout / parent of the tree lie in LDS when it has at most LCA_LDS_NODES nodes (the per-entry lookups tin[node] are gathers), else in
 // global memory.  direct[v] counts the reads assigned to v with 64-bit vector atomics.  All entry and read indices are 64-bit.
 #include "mm_lca.hpp"
+#include "mm_prims.hpp"
 #include <algorithm>
 
 namespace mm {
 
-template <int W> struct LcaLanes {                                // W consecutive lanes of a wavefront (W a power of two)
-  __device__ int lane() const { return (int)(threadIdx.x & (W - 1)); }
-  __device__ int width() const { return W; }
-  __device__ double sum(double x) const { for (int d = W / 2; d > 0; d >>= 1) x += __shfl_xor(x, d, W); return x; }   // (a butterfly: the same bits in every lane)
-  __device__ int32_t min(int32_t x) const { for (int d = W / 2; d > 0; d >>= 1) x = ::min(x, __shfl_xor(x, d, W)); return x; }
-  __device__ int32_t max(int32_t x) const { for (int d = W / 2; d > 0; d >>= 1) x = ::max(x, __shfl_xor(x, d, W)); return x; }
-  __device__ bool any(bool b) const { return __any(b) != 0; }     // of the whole wavefront
-};
 struct LcaOwnEntry {                                              // the one entry of this lane
   int32_t node_, tin_; double p_;
   __device__ int32_t node(int64_t) const { return node_; }
@@ -57,29 +51,19 @@ template <bool IN_LDS> __global__ void __launch_bounds__(256) lca_assign_kernel(
     __syncthreads();
     T = LcaTree{lca_sh, lca_sh + n, lca_sh + 2 * n};
   }
-  constexpr int PER_WAVE = 64 / LCA_GROUP;
-  const int lane = threadIdx.x & 63, gl = lane & (LCA_GROUP - 1), grp = lane / LCA_GROUP;
-  const int64_t n_waves = (int64_t)gridDim.x * 4, wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  for (int64_t r0 = wave * PER_WAVE; r0 < a.n_reads; r0 += n_waves * PER_WAVE) {   // (the same for every lane of the wavefront)
-    {                                                              // the tile's short reads, and its reads without entries
-      const int64_t r = r0 + grp;
-      int64_t lo = 0, n = 0;
-      if (r < a.n_reads) { lo = a.read_off[r]; n = a.read_off[r + 1] - lo; }
-      const bool mine = r < a.n_reads && n <= LCA_GROUP;
+  for_each_read_tile<LCA_GROUP>(a.read_off, a.n_reads,
+    [&](int64_t r, int64_t lo, int64_t n, bool mine, int gl) {    // the tile's short reads, and its reads without entries
       LcaOwnEntry e{0, 0, 0.0};
       if (mine && gl < n) { e.node_ = a.taxon_node[a.taxon[lo + gl]]; e.tin_ = T.tin[e.node_]; e.p_ = a.post[lo + gl]; }
       double m;
-      const int32_t v = lca_read(LcaLanes<LCA_GROUP>{}, e, mine ? n : 0, T, a.tau, &m);
+      const int32_t v = lca_read(Lanes<LCA_GROUP>{}, e, mine ? n : 0, T, a.tau, &m);
       if (mine && gl == 0) lca_store(a, r, v, m);
-    }
-    for (int q = 0; q < PER_WAVE && r0 + q < a.n_reads; ++q) {     // its long reads, one after the other
-      const int64_t lo = a.read_off[r0 + q], n = a.read_off[r0 + q + 1] - lo;
-      if (n <= LCA_GROUP) continue;
+    },
+    [&](int64_t r, int64_t lo, int64_t n) {                       // its long reads, one after the other
       double m;
-      const int32_t v = lca_read(LcaLanes<64>{}, LcaReadEntries{a.taxon, a.post, a.taxon_node, T.tin, lo}, n, T, a.tau, &m);
-      if (lane == 0) lca_store(a, r0 + q, v, m);
-    }
-  }
+      const int32_t v = lca_read(Lanes<64>{}, LcaReadEntries{a.taxon, a.post, a.taxon_node, T.tin, lo}, n, T, a.tau, &m);
+      if (Lanes<64>{}.lane() == 0) lca_store(a, r, v, m);
+    });
 }
 
 void lca_run(mm_em* E, const double* f, int32_t n_nodes, const int32_t* parent, const int32_t* taxon_node, double tau,
@@ -102,7 +86,7 @@ void lca_run(mm_em* E, const double* f, int32_t n_nodes, const int32_t* parent, 
   if (NR > 0) {
     LcaArgs a{E->read_off.p, E->taxon.p, E->post.p, E->n_reads, d_tn.p, LcaTree{d_tree.p, d_tree.p + N, d_tree.p + 2 * N}, n_nodes, tau,
               d_node.p, d_mass.p, d_direct.p};
-    const dim3 grid((unsigned)std::min<int64_t>(ceil_div(E->n_reads, 256 / LCA_GROUP), 2048)), blk(256);
+    const dim3 grid(read_tile_grid<LCA_GROUP>(E->n_reads)), blk(256);
     if (n_nodes <= LCA_LDS_NODES) lca_assign_kernel<true><<<grid, blk, 3 * N * sizeof(int32_t), st>>>(a);
     else lca_assign_kernel<false><<<grid, blk, 0, st>>>(a);
     MM_KERNEL_CHECK();

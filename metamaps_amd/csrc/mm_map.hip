@@ -11,7 +11,7 @@
 #include "mm_map.hpp"
 #include <functional>
 #include <memory>
-#include <rocprim/rocprim.hpp>
+#include "mm_prims.hpp"
 #include "mm_l2_core.hpp"
 #include "mm_size_classes.hpp"
 #include "mm_l2.hpp"
@@ -350,10 +350,8 @@ struct MapRun {
     DBuf<uint64_t> keys((size_t)nk), sorted((size_t)nk);
     sketch_keys_kernel<<<dim3((unsigned)nb), dim3(256), 0, st>>>(M->mz.rec.p, M->mz.off.p, d_big.p, d_koff.p, keys.p);
     MM_KERNEL_CHECK();
-    size_t tmp_bytes = 0;
-    MM_HIP(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, keys.p, sorted.p, (unsigned int)nk, (unsigned int)nb, d_koff.p, d_koff.p + 1, 0, 64, st));
-    DBuf<uint8_t> tmp(std::max<size_t>(tmp_bytes, 16));
-    MM_HIP(rocprim::segmented_radix_sort_keys((void*)tmp.p, tmp_bytes, keys.p, sorted.p, (unsigned int)nk, (unsigned int)nb, d_koff.p, d_koff.p + 1, 0, 64, st));
+    DBuf<uint8_t> tmp;
+    with_scratch(tmp, [&](void* t, size_t& b) { return rocprim::segmented_radix_sort_keys(t, b, keys.p, sorted.p, (unsigned int)nk, (unsigned int)nb, d_koff.p, d_koff.p + 1, 0, 64, st); });
     sketch_finish_kernel<<<dim3((unsigned)nb), dim3(256), 0, st>>>(M->mz.rec.p, M->mz.off.p, d_big.p, d_koff.p, sorted.p, M->sk_hash.p, M->sk_strand.p, M->sk_n.p, M->amb.p);
     MM_KERNEL_CHECK();
     MM_HIP(mm::stream_sync(st));                          // big / koff are upload sources
@@ -676,10 +674,7 @@ struct MapRun {
     DBuf<uint64_t> d_hb(ns), d_he(ns), d_cb(ns), d_ce(ns);
     d_hb.upload(hb.data(), ns, st); d_he.upload(he.data(), ns, st);
     auto seg_sort = [&](uint64_t* in, uint64_t* out, uint64_t count, size_t nseg, uint64_t* begins, uint64_t* ends) {
-      size_t tmp_bytes = 0;
-      MM_HIP(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, in, out, (unsigned int)count, (unsigned int)nseg, begins, ends, 0, key_bits, st));
-      DBuf<uint8_t> tmp(std::max<size_t>(tmp_bytes, 16));
-      MM_HIP(rocprim::segmented_radix_sort_keys((void*)tmp.p, tmp_bytes, in, out, (unsigned int)count, (unsigned int)nseg, begins, ends, 0, key_bits, st));
+      with_scratch([&](void* t, size_t& b) { return rocprim::segmented_radix_sort_keys(t, b, in, out, (unsigned int)count, (unsigned int)nseg, begins, ends, 0, key_bits, st); });
     };
     if (compact) {
       d_cb.upload(cb.data(), ns, st); d_ce.upload(ce.data(), ns, st);
@@ -969,10 +964,8 @@ struct MapRun {
     DBuf<uint64_t> key(ng), val(ng), key2(ng), val2(ng);
     l2_group_keys_kernel<<<dim3((unsigned)ceil_div((int64_t)ng, 256)), dim3(256), 0, st>>>(g0.p, gn.p, M->cand.p, (int64_t)ng, key.p, val.p);
     int cbits = 1; while (cbits < 31 && ((int64_t)1 << cbits) < I->n_contigs) ++cbits;
-    size_t tmp_bytes = 0;                                     // (positions at 4 kb granularity: bits 12 .. 32 + contig bits)
-    MM_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key.p, key2.p, val.p, val2.p, ng, 12u, (unsigned)(32 + cbits), st));
-    DBuf<uint8_t> tmp(std::max<size_t>(tmp_bytes, 1));
-    MM_HIP(rocprim::radix_sort_pairs((void*)tmp.p, tmp_bytes, key.p, key2.p, val.p, val2.p, ng, 12u, (unsigned)(32 + cbits), st));
+    DBuf<uint8_t> tmp;
+    sort_pairs(tmp, key.p, key2.p, val.p, val2.p, ng, 12, 32 + cbits, st);   // (positions at 4 kb granularity: bits 12 .. 32 + contig bits)
     l2_group_unpack_kernel<<<dim3((unsigned)ceil_div((int64_t)ng, 256)), dim3(256), 0, st>>>(val2.p, (int64_t)ng, g0.p, gn.p);
     MM_KERNEL_CHECK();
   }

@@ -4,7 +4,7 @@
 #include "mm_map.hpp"
 #include "mm_em.hpp"
 #include <rccl/rccl.h>
-#include <rocprim/rocprim.hpp>
+#include "mm_prims.hpp"
 #include <cfloat>
 #include <numeric>
 
@@ -268,10 +268,8 @@ void em_create_from_mapping(mm_ctx* ctx, const mm_mapping* M, const int32_t* con
     MM_KERNEL_CHECK();
     // CSR by taxon, entries in read order inside each taxon (stable sort)
     int bits = 1; while ((1LL << bits) < (int64_t)n_taxa) ++bits;
-    size_t tmp_bytes = 0;
-    MM_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key.p, key2.p, val.p, val2.p, (size_t)ne, 0, bits, st));
-    DBuf<uint8_t> tmp(tmp_bytes);
-    MM_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, key.p, key2.p, val.p, val2.p, (size_t)ne, 0, bits, st));
+    DBuf<uint8_t> tmp;
+    sort_pairs(tmp, key.p, key2.p, val.p, val2.p, (size_t)ne, 0, bits, st);
     em_perm_kernel<<<dim3((unsigned)ceil_div(ne, 256)), dim3(256), 0, st>>>(val2.p, ne, E->perm.p);
     MM_KERNEL_CHECK();
   }
