@@ -5,6 +5,7 @@
 #include "mm_em.hpp"
 #include <rccl/rccl.h>
 #include "mm_prims.hpp"
+#include "mm_post_core.hpp"
 #include <cfloat>
 #include <numeric>
 
@@ -12,52 +13,12 @@ namespace mm {
 
 // ---------------------------------------------------------------------------------------------------
 // Text round trips are part of the reference's numerics: identities and mapping qualities
-// are printed with 6 significant digits (ostream default) and parsed back with stod.  parse6() returns
-// the double that stod would return for the "%g" rendering of v.  For a float-valued v the scaling by a
-// power of ten is exact in double, so ties (…5 exactly) are detected exactly and rounded half-to-even as
-// glibc's printf does.
+// are printed with 6 significant digits (ostream default) and parsed back with stod.  parse6() restates
+// that round trip in arithmetic; what it promises (bit-equal to strtod of the "%g" text from 1e-17 up,
+// within 4 * 2^-53 of it below, 0 where the text is a denormal, never NaN or infinite for a finite value)
+// is written out in mm_post_core.hpp, with pow10_int, dev_identity, dev_binom_pmf, mapq_success_p and
+// em_stop_now: one text for these kernels and for the host build that tests/test_post_core.py checks.
 // ---------------------------------------------------------------------------------------------------
-__host__ __device__ inline double pow10_int(int t) {
-  const double tab[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
-  if (t >= 0 && t <= 22) return tab[t];
-  return pow(10.0, (double)t);
-}
-__host__ __device__ inline double parse6(double v) {
-  if (v == 0.0 || !(v == v)) return v;
-  double a = fabs(v);
-  int e = (int)floor(log10(a));
-  {                                                              // fix log10 rounding at decade boundaries
-    double pe = e >= 0 ? pow10_int(e) : 1.0 / pow10_int(-e);
-    if (a < pe) --e; else if (a >= pe * 10.0) ++e;
-  }
-  int t = 5 - e;
-  double x = t >= 0 ? a * pow10_int(t) : a / pow10_int(-t);
-  double d = rint(x);
-  if (d >= 1e6) { d /= 10.0; t -= 1; }
-  double r = t >= 0 ? d / pow10_int(t) : d * pow10_int(-t);
-  if (r < DBL_MIN) r = 0.0;                                      // stod throws out_of_range → reference uses 0, fEM.h:269-275
-  return v < 0 ? -r : r;
-}
-
-// float math of Stat::j2md (map_stats.hpp:44) and the identity of computeMap.hpp:406,411
-__host__ __device__ inline float dev_identity(int shared, int s, int k) {
-  float j = (float)(1.0 * shared / s);
-  float md;
-  if (j == 0) md = 1.0f;
-  else if (j == 1) md = 0.0f;
-  else md = (float)((-1.0 / k) * log(2.0 * j / (double)(1 + j)));
-  return 100 * (1 - md);
-}
-
-__device__ inline double dev_binom_pmf(int n, double p, int k) {  // boost pdf(binomial), mapWrap.h:340
-  if (k < 0 || k > n) return 0.0;
-  if (p == 0) return k == 0 ? 1.0 : 0.0;
-  if (p == 1) return k == n ? 1.0 : 0.0;
-  if (n == 0) return 1.0;
-  if (k == 0) return pow(1 - p, (double)n);
-  if (k == n) return pow(p, (double)k);
-  return exp(lgamma((double)n + 1) - lgamma((double)k + 1) - lgamma((double)(n - k) + 1) + k * log(p) + (n - k) * log1p(-p));
-}
 
 // K8 in three launches, one thread per MAPPING where the arithmetic is (round 3 ran one thread per READ through three serial loops
 // of f64 lgamma / pow: 3.2 ms per 10^5-read batch, 423 k records).
@@ -77,12 +38,7 @@ __global__ void __launch_bounds__(256) mapq_likelihood_kernel(mm_map_record* __r
   const uint64_t lo = rec_off[r], hi = rec_off[r + 1];
   double maxid = -1;
   for (uint64_t j = lo; j < hi; ++j) { const double id = ident[j]; if (id > maxid) maxid = id; }
-  maxid = exp(-(1 - maxid));                                      // :261
-  const int nk = read_len[r] - k + 1;                             // :266
-  const double surv = pow(maxid, (double)k);                      // :335
-  const double es = round(surv * nk);
-  const double eu = nk + (nk - es);
-  const double p = es / eu;
+  const double p = mapq_success_p(maxid, read_len[r], k);         // :261-266, :335-339
   rec[i].mapq = dev_binom_pmf(rec[i].sketch, p, rec[i].shared);
 }
 __global__ void __launch_bounds__(256) mapq_normalise_kernel(mm_map_record* __restrict__ rec, const uint64_t* __restrict__ rec_off, int64_t n_reads, int* __restrict__ err) {
@@ -476,7 +432,7 @@ __device__ inline void em_stop_rule(long long* ctrl, double ll, double* ll_trace
   const double ll_prev = __longlong_as_double(ctrl[2]);
   const long long ti = it - ctrl[3];                               // ctrl[3]: iteration the trace buffer starts at (mm_em_continue)
   if (ti >= 0 && ti < ll_cap) ll_trace[ti] = ll;
-  if (it > 0 && (ll - ll_prev) <= 1 && (1 - ll / ll_prev) < 0.0001) ctrl[1] = 1;   // fEM.h:624-639
+  if (em_stop_now(it, ll, ll_prev)) ctrl[1] = 1;                  // fEM.h:624-639
   if (!ctrl[1] && it + 1 >= it_limit) ctrl[1] = 2;                 // the caller's limit, unless the rule has just fired (a rule stop is final, a limit stop is lifted by mm_em_continue)
   ctrl[2] = __double_as_longlong(ll);
   ctrl[0] = it + 1;

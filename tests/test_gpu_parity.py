@@ -556,8 +556,7 @@ def test_em_from_mapping_equals_host_built_problem(ctx):
         f = ph / ph.sum()
     p1, b1 = e_host.posteriors(f); p2, b2 = e_dev.posteriors(f)
     assert np.array_equal(b1, b2)
-    # (mapping qualities around 1e-35 round differently in numpy's and the device's 6-digit rounding: posteriors that small only)
-    assert np.allclose(p1, p2, rtol=1e-12, atol=1e-30)
+    assert np.allclose(p1, p2, rtol=1e-12, atol=0)
     e_host.close(); e_dev.close(); M.close(); idx.close(); reads.close(); ref.close()
 
 
