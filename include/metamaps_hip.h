@@ -29,7 +29,7 @@ extern "C" {
                             * 4: mm_sketch_batch, mm_ctx_release_cached, mm_index_dup_neighbours;
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
-                            *    mm_em_lca, mm_gene_overlap, mm_ident_filter (additions to 6) */
+                            *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -449,6 +449,24 @@ int mm_ident_filter(mm_ctx* ctx, int64_t n_reads, const int64_t* read_off /* [n_
                     int64_t* taxon_reads /* [n_taxa] */, double* taxon_median /* [n_taxa] */, uint8_t* taxon_removed /* [n_taxa] */,
                     uint8_t* read_removed /* [n_reads] */,
                     int64_t* read_src, int64_t* entry_src, int64_t* read_off_out, int64_t* n_reads_out, int64_t* n_entries_out);
+
+/* Exact edit distances (not in the reference; DESIGN.md section 1, "Edit distances"; the definition: csrc/mm_edit_core.hpp), by Myers' bit-vector
+ * recurrence on the device, one job per wavefront.  Job i aligns read read[i] of `reads` (its reverse complement for strand[i] == -1, the whole
+ * read) to the window [ws[i], we[i]) of contig contig[i] of `reference`, the window's ends free: dist_out[i] is the smallest unit-cost Levenshtein
+ * distance d to a substring of the window, end_out[i] the smallest end b (window coordinates, half-open) of a substring at that distance,
+ * begin_out[i] the largest start a with Lev = d for that end.  A C G T match the same letter in either case, every other byte matches nothing.
+ * dist_out[i] = -1 (and begin = end = -1) where d > max_dist[i] or the read is longer than 65 536 bases.  Every job is checked before anything is
+ * launched; MM_ERR_ARG with the broken rule as the message and the outputs untouched: a read or contig outside its set, a strand that is neither
+ * +1 nor -1, a negative max_dist, a window that ends before it starts or lies outside its contig.  n_jobs == 0 is valid. */
+int mm_edit_infix(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand,
+                  const int32_t* contig, const int64_t* ws, const int64_t* we, const int32_t* max_dist,
+                  int32_t* dist_out, int64_t* begin_out, int64_t* end_out);
+/* The same for every record of a mapping, in mm_mapping_fetch order, the jobs made on the device: the window is contig[ws, we) with
+ * pad = 64 + L / 16, ws = max(0, ref_start - pad), we = min(C, ref_start + L + pad), and max_dist = floor(1.5 L (100 - perc_identity) / 100).
+ * dist_out[i] = d, first_out[i] = ws + a, last_out[i] = ws + b - 1 (0-based inclusive contig coordinates), or -1 -1 -1 where the record is not
+ * aligned.  `reads` is the set that was mapped, `reference` the set whose contig numbering the records use; cap: room in the output arrays. */
+int mm_mapping_edit_distances(mm_ctx* ctx, const mm_mapping* mapping, const mm_seqset* reads, const mm_seqset* reference, float perc_identity,
+                              int32_t* dist_out, int64_t* first_out, int64_t* last_out, int64_t cap);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------------------------- */
 #define MM_COMM_ID_BYTES 128

@@ -191,6 +191,8 @@ def lib() -> C.CDLL:
             "mm_em_lca": (C.c_int, [vp, vp, i32, vp, vp, f64, vp, vp, vp]),
             "mm_gene_overlap": (C.c_int, [vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, P(i64)]),
             "mm_ident_filter": (C.c_int, [vp, i64, vp, vp, vp, vp, i32, f64, vp, P(i64), P(i64), vp, vp, vp, vp, vp, vp, vp, P(i64), P(i64)]),
+            "mm_edit_infix": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "mm_mapping_edit_distances": (C.c_int, [vp, vp, vp, vp, f32, vp, vp, vp, i64]),
             "mm_comm_unique_id": (C.c_int, [C.c_char_p]),
             "mm_comm_init": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
             "mm_comm_allreduce_f64": (C.c_int, [vp, vp, i64]),
@@ -488,6 +490,24 @@ class Context:
         if want_filtered:
             out.update(read_src=rs[:n_r.value], entry_src=es[:n_e.value], read_off_out=ro[:n_r.value + 1])
         return out
+
+    def edit_infix(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, ws, we, max_dist, out=None):
+        """exact edit distances of arbitrary jobs (mm_edit_infix): read[i] of `reads` on strand[i] against contig[i][ws[i], we[i]) of `reference` within
+        max_dist[i].  Returns (dist, begin, end), window coordinates, half-open; dist -1: not aligned.  out: the three arrays to write into."""
+        rd, sd, cg, md = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, max_dist))
+        w0, w1 = np.ascontiguousarray(ws, dtype=np.int64), np.ascontiguousarray(we, dtype=np.int64)
+        n = len(rd)
+        assert all(len(x) == n for x in (sd, cg, md, w0, w1))
+        dist, begin, end = out if out is not None else (np.full(n, -2, dtype=np.int32), np.full(n, -2, dtype=np.int64), np.full(n, -2, dtype=np.int64))
+        self.check(lib().mm_edit_infix(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(w0), _ptr(w1), _ptr(md), _ptr(dist), _ptr(begin), _ptr(end)))
+        return dist, begin, end
+
+    def mapping_edit_distances(self, mapping: "Mapping", reads: "SeqSet", reference: "SeqSet", perc_identity: float, n_records: int):
+        """exact edit distance and 0-based inclusive contig coordinates of every record of a mapping, in fetch order (mm_mapping_edit_distances);
+        (-1, -1, -1) where a record is not aligned"""
+        dist, first, last = np.full(n_records, -2, dtype=np.int32), np.full(n_records, -2, dtype=np.int64), np.full(n_records, -2, dtype=np.int64)
+        self.check(lib().mm_mapping_edit_distances(self.h, mapping.h, reads.h, reference.h, float(perc_identity), _ptr(dist), _ptr(first), _ptr(last), n_records))
+        return dist, first, last
 
     # ---- communicator
     @staticmethod

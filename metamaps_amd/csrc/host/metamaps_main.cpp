@@ -43,6 +43,14 @@
 // the buffer the tokeniser works on; any bgzip'd mappings file is accepted.  A corrupt or truncated file ends the run with the compressed
 // offset of the bad block.  A plain gzip mappings file (no BGZF blocks) is refused with a message that says so.
 //
+// --edit-distance (mapDirectly; not in the reference): PREFIX.editDistances beside PREFIX, one line per mapping line in the same order,
+// "readID contigID strand d first last": the exact unit-cost edit distance of the whole read (its reverse complement for strand -) to the best
+// substring of the window contig[ref_start - pad, ref_start + L + pad), pad = 64 + L / 16, and that substring's 0-based inclusive coordinates;
+// "NA NA NA" where the distance is above floor(1.5 L (100 - pi) / 100) or the read is longer than 65 536 bases.  Aligned on the device that mapped
+// the batch (mm_mapping_edit_distances, host/edit_dist.hpp); every device keeps its packed reference (0.25 bytes per base) and a batch's reads live
+// until its distances are fetched.  PREFIX, .meta* and .parameters are the bytes of a run without the flag.  Refused: --hpc, index, mapAgainstIndex,
+// classify, and any run whose chunk indexes are sharded or streamed (--shard-index, --stream-chunks, or an index that does not fit one device).
+//
 // --hpc (mapDirectly; not in the reference; minimap2's -H): homopolymer-compressed mapping.  Every maximal run of equal bytes of the reference and
 // of the reads — as hashed: upper-cased, IUPAC and N kept — becomes one byte, on the device (mm_seqset_hpc): the reference once per device behind
 // its upload, every read batch on the context that maps it.  The pipeline then runs unchanged on the compressed sequences: -m, the len < w and
@@ -97,11 +105,14 @@ Options parse(int argc, char** argv) {
     if (a == "--stream-chunks") { o.stream = true; continue; }
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
-    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
+    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
                    "         sketching; -m, identities and mapping qualities are in compressed space, reported lengths and coordinates are raw\n"
+                   "  --edit-distance  (mapDirectly) also writes PREFIX.editDistances: readID contigID strand d first last for every line of PREFIX, the exact edit\n"
+                   "         distance of the read inside the window around its mapped position and the 0-based inclusive contig coordinates of that alignment\n"
+                   "         (NA NA NA beyond 1.5 (100 - pi) % of the read length); not with --hpc, --shard-index, --stream-chunks\n"
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
                    "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
                    "  --genes  (classify, mapDirectly --then-classify) gene-level analysis against DB_annotations.txt and DB_proteins.faa.annotated of the DB:\n"
@@ -195,6 +206,11 @@ int main(int argc, char** argv) {
   const IdentOpts identf_opts = ident_options(o);
   if ((identf_opts.on || identf_opts.refit) && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--min-identity and --refit need classify or mapDirectly --then-classify");
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
+  if (o.v.count("edit-distance")) {                              // (refused before any device work)
+    if (mode != "mapDirectly") die("--edit-distance belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
+    if (o.v.count("hpc")) die("--edit-distance cannot be combined with --hpc: the raw reference does not stay on the device");
+    if (o.stream || o.shard) die("--edit-distance cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");
+  }
   if (mode == "mapDirectly" || mode == "index" || mode == "mapAgainstIndex") return map_mode(o, mode, sw);
   if (mode == "classify") {
     if (o.v.count("hpc")) die("--hpc belongs to mapDirectly: classify reads the raw coordinates a --hpc mapping reports and takes no such flag");

@@ -10,6 +10,7 @@
 #include "mm_lca.hpp"
 #include "mm_gene.hpp"
 #include "mm_ident.hpp"
+#include "mm_edit.hpp"
 #include <chrono>
 #include <new>
 #include <rccl/rccl.h>
@@ -971,6 +972,26 @@ int mm_ident_filter(mm_ctx* ctx, int64_t n_reads, const int64_t* read_off, const
     mm::ident_filter_run(ctx, mm::IdentIn{n_reads, read_off, taxon, ident, best, n_taxa, thr_percent},
                          mm::IdentOut{sorted_max, n_with_entries, n_le, taxon_reads, taxon_median, taxon_removed, read_removed, read_src, entry_src, read_off_out,
                                       n_reads_out, n_entries_out});
+  });
+}
+int mm_edit_infix(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand,
+                  const int32_t* contig, const int64_t* ws, const int64_t* we, const int32_t* max_dist, int32_t* dist_out, int64_t* begin_out, int64_t* end_out) {
+  if (!ctx || !reads || !reference) return MM_ERR_ARG;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(n_jobs >= 0 && n_jobs < ((int64_t)1 << 31), n_jobs < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_edit_infix: a negative number of jobs, or 2^31 or more");
+    MM_REQUIRE(n_jobs == 0 || (read && strand && contig && ws && we && max_dist && dist_out && begin_out && end_out), MM_ERR_ARG, "mm_edit_infix: a null array");
+    mm::edit_infix_run(ctx, reads, reference, mm::EditInfixIn{n_jobs, read, strand, contig, ws, we, max_dist}, dist_out, begin_out, end_out);
+  });
+}
+int mm_mapping_edit_distances(mm_ctx* ctx, const mm_mapping* mapping, const mm_seqset* reads, const mm_seqset* reference, float perc_identity,
+                              int32_t* dist_out, int64_t* first_out, int64_t* last_out, int64_t cap) {
+  if (!ctx || !mapping || !reads || !reference) return MM_ERR_ARG;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(mapping->n_rec < ((int64_t)1 << 31), MM_ERR_LIMIT, "mm_mapping_edit_distances: 2^31 records or more");
+    MM_REQUIRE(mapping->n_rec == 0 || (dist_out && first_out && last_out), MM_ERR_ARG, "mm_mapping_edit_distances: a null array");
+    mm::edit_mapping_run(ctx, mapping, reads, reference, perc_identity, dist_out, first_out, last_out, cap);
   });
 }
 

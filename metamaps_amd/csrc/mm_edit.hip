@@ -1,0 +1,197 @@
+// Exact edit distances of mappings on the device (mapDirectly --edit-distance; not in the reference; DESIGN.md section 1, "Edit distances"; the
+// definition: mm_edit_core.hpp; the recurrence, its 64-lane schedule and the driver of a pass: mm_edit_bv_core.hpp, the text the host tests run).
+//   jobs      (read, strand, contig, ws, we, max_dist), 32-bit each, in device arrays: uploaded after edit_job_check (mm_edit_infix), or written by
+//             edit_jobs_kernel from the mapping's records with the window and cap rules (mm_mapping_edit_distances)
+//   align     edit_bv_kernel<BT>: one job per wavefront, a workgroup is one wavefront, the job is blockIdx.x (plus the launch's first job).  Per job a
+//             bounded prologue narrows the sets' exception runs to the ones inside the read and the window (binary searches with a fixed number of
+//             rounds); bv_align then runs pass 1 and pass 2.  A lane's Pv / Mv are registers (BT of them each, the class of the read's blocks per
+//             lane: 1 2 4 8 16 32), Peq is in LDS (BT KiB at most, sized per launch from the longest read of the class), the window's symbols
+//             come straight from the packed set, 64 columns at a time.  There is no job counter, no atomic, no barrier (a lane reads only the LDS
+//             words it wrote), no loop whose trip count depends on the strings.
+//   classes   one launch per class that the read set can need, over all jobs: a wavefront whose job is of another class returns at once
+// An exception run holds a byte other than A C G T (mm_seq.hip upper-cases before it packs), so a base inside a run matches nothing and every
+// other base is its 2-bit code: lower case needs no care here.
+#include "mm_edit.hpp"
+#include "mm_prims.hpp"
+
+namespace mm {
+
+struct EditSeq {                                                  // the bases of a set by stream coordinate; the runs may be narrowed to a stretch
+  const uint32_t* packed; const uint64_t* exc_start; const uint32_t* exc_len; int64_t n_exc; int rounds;
+  // first run that ends behind g, in `rounds` rounds (2^rounds > n_exc)
+  __device__ int64_t lower(uint64_t g) const {
+    int64_t lo = 0, hi = n_exc;
+    for (int r = 0; r < rounds; ++r)
+      if (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (exc_start[mid] + exc_len[mid] <= g) lo = mid + 1; else hi = mid; }
+    return lo;
+  }
+  __device__ uint32_t sym(int64_t g) const {
+    if (n_exc) { const int64_t r = lower((uint64_t)g); if (r < n_exc && exc_start[r] <= (uint64_t)g) return BV_SYM_NONE; }
+    return (packed[g >> 4] >> (2 * (g & 15))) & 3u;
+  }
+  __device__ EditSeq narrowed(uint64_t g0, uint64_t g1) const {   // the runs that touch [g0, g1)
+    EditSeq s = *this;
+    if (!n_exc) return s;
+    const int64_t r0 = lower(g0), r1 = g1 > g0 ? lower(g1 - 1) : r0;
+    const int64_t end = r1 < n_exc && exc_start[r1] < g1 ? r1 + 1 : r1;
+    s.exc_start += r0; s.exc_len += r0; s.n_exc = end > r0 ? end - r0 : 0;
+    return s;
+  }
+};
+static EditSeq edit_seq(const mm_seqset* S) { return EditSeq{S->packed.p, S->exc_start.p, S->exc_len.p, S->n_exc, bits_for((uint64_t)S->n_exc)}; }
+
+struct EditJobs {
+  const int32_t* read; const int32_t* strand; const int32_t* contig; const int32_t* ws; const int32_t* we; const int32_t* max_dist;
+  int32_t* dist; int32_t* a; int32_t* b; int64_t n;
+};
+
+struct BvWaveLanes {                                              // one lane per thread of a 64-thread workgroup
+  static constexpr int HELD = 1;
+  __device__ int lane(int) const { return (int)threadIdx.x; }
+  template <class T> __device__ void up(const T* v, T* o) const { o[0] = __shfl_up(v[0], 1); }
+  template <class T> __device__ T pick(const T* v, int l) const { return __shfl(v[0], l); }
+};
+
+template <int BT> __global__ void __launch_bounds__(BV_LANES) edit_bv_kernel(EditSeq Q, const uint64_t* __restrict__ q_base, const int32_t* __restrict__ q_len,
+                                                                            EditSeq R, const uint64_t* __restrict__ r_base, EditJobs J, int64_t job0) {
+  extern __shared__ uint32_t edit_peq[];
+  const int64_t job = job0 + (int64_t)blockIdx.x;
+  if (job >= J.n) return;
+  const int32_t read = J.read[job];
+  if (read < 0) return;                                           // (a record that edit_jobs_kernel refused)
+  const int32_t m = q_len[read];
+  if (m > EDIT_MAX_READ || bv_class(bv_per_lane(m)) != BT) return;   // too long: stays not aligned; another class: that launch's
+  const int32_t ws = J.ws[job], n = J.we[job] - ws;
+  const uint64_t qg = q_base[read], rg = r_base[J.contig[job]] + (uint64_t)ws;
+  int32_t d, a, b;
+  bv_align<BT>(BvWaveLanes{}, Q.narrowed(qg, qg + (uint64_t)m), (int64_t)qg, m, J.strand[job], R.narrowed(rg, rg + (uint64_t)n), (int64_t)rg, n, J.max_dist[job], edit_peq, &d, &a, &b);
+  if (threadIdx.x == 0) { J.dist[job] = d; J.a[job] = d < 0 ? -1 : a; J.b[job] = d < 0 ? -1 : b; }
+}
+
+struct EditRecArgs {
+  const mm_map_record* rec; int64_t n; const int32_t* q_len; int64_t n_reads; const int32_t* r_len; int64_t n_contigs; float pi;
+  int32_t* read; int32_t* strand; int32_t* contig; int32_t* ws; int32_t* we; int32_t* max_dist; int32_t* bad;
+};
+__global__ void __launch_bounds__(256) edit_jobs_kernel(EditRecArgs A) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= A.n) return;
+  const mm_map_record r = A.rec[i];
+  const bool ok = r.read >= 0 && r.read < A.n_reads && r.ref_contig >= 0 && r.ref_contig < A.n_contigs && (r.strand == 1 || r.strand == -1);
+  int64_t ws = 0, we = 0; int32_t cap = 0;
+  if (ok) { const int64_t L = A.q_len[r.read]; edit_window(r.ref_start, L, A.r_len[r.ref_contig], &ws, &we); cap = edit_cap(L, A.pi); }
+  else *A.bad = 1;
+  A.read[i] = ok ? r.read : -1; A.strand[i] = r.strand; A.contig[i] = ok ? r.ref_contig : 0; A.ws[i] = (int32_t)ws; A.we[i] = (int32_t)we; A.max_dist[i] = cap;
+}
+// dist, ws + a, ws + b - 1 as the caller's types (-1 -1 -1: not aligned); ws null: a and b as they are
+__global__ void __launch_bounds__(256) edit_coords_kernel(EditJobs J, bool contig_coords, int64_t* __restrict__ first, int64_t* __restrict__ last) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= J.n) return;
+  const bool al = J.dist[i] >= 0;
+  first[i] = !al ? -1 : contig_coords ? (int64_t)J.ws[i] + J.a[i] : J.a[i];
+  last[i] = !al ? -1 : contig_coords ? (int64_t)J.ws[i] + J.b[i] - 1 : J.b[i];
+}
+
+namespace {
+
+constexpr int EDIT_N_CLASSES = 6;                                 // BT = 1 << c
+constexpr int64_t EDIT_GRID_MAX = (int64_t)1 << 30;               // workgroups per launch
+
+struct EditRun {
+  mm_ctx* ctx; const mm_seqset* reads; const mm_seqset* ref; hipStream_t st; int64_t n;
+  StageClock<2> clk;                                               // MM_EDIT_TIMING=1: jobs, align on stderr
+  DBuf<int32_t> d_read, d_strand, d_contig, d_ws, d_we, d_md, d_dist, d_a, d_b;
+  DBuf<int64_t> d_first, d_last;
+
+  EditRun(mm_ctx* c, const mm_seqset* q, const mm_seqset* r, int64_t n_)
+      : ctx(c), reads(q), ref(r), st(c->stream), n(n_), clk(getenv("MM_EDIT_TIMING") != nullptr, c->stream) {
+    const size_t k = (size_t)std::max<int64_t>(n, 1);
+    d_read.alloc(k); d_strand.alloc(k); d_contig.alloc(k); d_ws.alloc(k); d_we.alloc(k); d_md.alloc(k); d_dist.alloc(k); d_a.alloc(k); d_b.alloc(k);
+    d_first.alloc(k); d_last.alloc(k);
+  }
+  EditJobs jobs() const { return EditJobs{d_read.p, d_strand.p, d_contig.p, d_ws.p, d_we.p, d_md.p, d_dist.p, d_a.p, d_b.p, n}; }
+
+  template <int BT> void launch(int32_t B, int64_t job0, int64_t count) {
+    const size_t lds = (size_t)bv_peq_words(B) * sizeof(uint32_t);
+    edit_bv_kernel<BT><<<dim3((unsigned)count), dim3(BV_LANES), lds, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, edit_seq(ref), ref->d_base.p, jobs(), job0);
+    MM_KERNEL_CHECK();
+  }
+  // every class that a read of the set can need, over all jobs; the LDS of a launch from the longest read of its class
+  void align() {
+    int32_t B_of[EDIT_N_CLASSES] = {};
+    for (const int32_t L : reads->len) {
+      if (L > EDIT_MAX_READ) continue;
+      const int32_t B = std::max(bv_per_lane(L), 1); int c = 0;      // (an empty read: the first class, no block)
+      while ((1 << c) < B) ++c;
+      B_of[c] = std::max(B_of[c], B);
+    }
+    MM_HIP(hipMemsetAsync(d_dist.p, 0xFF, d_dist.bytes(), st)); MM_HIP(hipMemsetAsync(d_a.p, 0xFF, d_a.bytes(), st)); MM_HIP(hipMemsetAsync(d_b.p, 0xFF, d_b.bytes(), st));
+    clk.start();
+    for (int c = 0; c < EDIT_N_CLASSES; ++c) {
+      if (!B_of[c]) continue;
+      for (int64_t job0 = 0; job0 < n; job0 += EDIT_GRID_MAX) {
+        const int64_t count = std::min(EDIT_GRID_MAX, n - job0);
+        switch (c) {
+          case 0: launch<1>(B_of[c], job0, count); break;
+          case 1: launch<2>(B_of[c], job0, count); break;
+          case 2: launch<4>(B_of[c], job0, count); break;
+          case 3: launch<8>(B_of[c], job0, count); break;
+          case 4: launch<16>(B_of[c], job0, count); break;
+          default: launch<32>(B_of[c], job0, count); break;
+        }
+      }
+    }
+    clk.stop(1);
+  }
+  void fetch(bool contig_coords, int32_t* dist, int64_t* first, int64_t* last) {
+    edit_coords_kernel<<<dim3(flat_grid(n)), dim3(256), 0, st>>>(jobs(), contig_coords, d_first.p, d_last.p); MM_KERNEL_CHECK();
+    d_dist.download(dist, (size_t)n, st); d_first.download(first, (size_t)n, st); d_last.download(last, (size_t)n, st);
+    MM_HIP(mm::stream_sync(st));
+    if (clk.on) fprintf(stderr, "MM_EDIT_TIMING jobs %.3f align %.3f ms; %lld jobs\n", clk.ms[0], clk.ms[1], (long long)n);
+  }
+};
+
+void edit_sets_check(const mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const char* who) {
+  MM_REQUIRE(reads->frozen && ref->frozen, MM_ERR_STATE, std::string(who) + ": a sequence set is not uploaded");
+  MM_REQUIRE(reads->ctx->device == ctx->device && ref->ctx->device == ctx->device, MM_ERR_ARG, std::string(who) + ": a sequence set lives on another device");
+}
+
+}  // namespace
+
+void edit_infix_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const EditInfixIn& in, int32_t* dist, int64_t* begin, int64_t* end) {
+  edit_sets_check(ctx, reads, ref, "mm_edit_infix");
+  const size_t n = (size_t)in.n_jobs;
+  std::vector<int32_t> ws(n), we(n);
+  for (size_t i = 0; i < n; ++i) {                                // every job, before anything is launched
+    const int bad = edit_job_check(in.read[i], in.strand[i], in.contig[i], in.max_dist[i], in.ws[i], in.we[i], reads->count(), ref->count(), ref->len.data());
+    MM_REQUIRE(!bad, MM_ERR_ARG, std::string("mm_edit_infix: ") + edit_arg_message(bad));
+    ws[i] = (int32_t)in.ws[i]; we[i] = (int32_t)in.we[i];
+  }
+  if (n == 0) return;
+  EditRun J(ctx, reads, ref, in.n_jobs);
+  J.d_read.upload(in.read, n, J.st); J.d_strand.upload(in.strand, n, J.st); J.d_contig.upload(in.contig, n, J.st);
+  J.d_ws.upload(ws.data(), n, J.st); J.d_we.upload(we.data(), n, J.st); J.d_md.upload(in.max_dist, n, J.st);
+  J.align();
+  J.fetch(false, dist, begin, end);
+}
+
+void edit_mapping_run(mm_ctx* ctx, const mm_mapping* M, const mm_seqset* reads, const mm_seqset* ref, float pi, int32_t* dist, int64_t* first, int64_t* last, int64_t cap) {
+  edit_sets_check(ctx, reads, ref, "mm_mapping_edit_distances");
+  MM_REQUIRE(M->ctx->device == ctx->device, MM_ERR_ARG, "mm_mapping_edit_distances: the mapping lives on another device");
+  MM_REQUIRE(!M->sketch_only, MM_ERR_STATE, "mm_mapping_edit_distances: the mapping has no records");
+  MM_REQUIRE(reads->count() == M->n_reads, MM_ERR_ARG, "mm_mapping_edit_distances: the read set is not the one that was mapped");
+  MM_REQUIRE(cap >= M->n_rec, MM_ERR_ARG, "output capacity too small");
+  if (M->n_rec == 0) return;
+  EditRun J(ctx, reads, ref, M->n_rec);
+  DBuf<int32_t> d_bad(1); d_bad.zero(J.st);
+  J.clk.start();
+  edit_jobs_kernel<<<dim3(flat_grid(J.n)), dim3(256), 0, J.st>>>(EditRecArgs{M->rec.p, J.n, reads->d_len.p, reads->count(), ref->d_len.p, ref->count(), pi,
+                                                                             J.d_read.p, J.d_strand.p, J.d_contig.p, J.d_ws.p, J.d_we.p, J.d_md.p, d_bad.p});
+  MM_KERNEL_CHECK();
+  const int32_t bad = d_bad.to_host(J.st)[0];
+  J.clk.stop(0);
+  MM_REQUIRE(!bad, MM_ERR_ARG, "mm_mapping_edit_distances: a record's read, contig or strand lies outside the sets (is `reference` the set the index was built from?)");
+  J.align();
+  J.fetch(true, dist, first, last);
+}
+
+}  // namespace mm

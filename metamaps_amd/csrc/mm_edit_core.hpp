@@ -1,5 +1,5 @@
 // Exact edit distances of mappings (not in the reference; DESIGN.md section 1, "Edit distances"): the definition, and the one text of the alignment for
-// the host build and for a device build (no kernel uses it yet: DESIGN.md says why).
+// the host build and for a device build (the device path runs mm_edit_bv_core.hpp against this definition; this routine stays host-only: DESIGN.md says why).
 //   record       read r of length L on contig c of length C at ref_start, strand +1 / -1
 //   Q            the read; for strand -1 its reverse complement.  m = L
 //   window       R = contig[ws, we), ws = max(0, ref_start - pad), we = min(C, ref_start + L + pad), pad = 64 + L / 16.  n = we - ws

@@ -1,0 +1,72 @@
+"""What profiles/edit_kernel_stats.txt is made from: mm_mapping_edit_distances on one batch of bench size (10^5 synthetic ONT-error reads of 10 kb against a
+uniform synthetic reference, best mappings only) timed stage by stage with events on the context's stream (MM_EDIT_TIMING=1, three calls in a fresh child
+process), and csrc/mm_edit_core.hpp's edit_infix_host on one host thread over a sample of the same jobs (tools/edit_host_align.cpp, built with g++ into
+tools/_tmp/), which also holds the device's answers against the host's.
+Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes profiles/edit_kernel_stats.txt)"""
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+K, PI, READ_LEN = 16, 80.0, 10_000
+
+
+def child(n_reads, n_sample):
+    from metamaps_amd import capi
+    ctx = capi.Context(0)
+    ref = ctx.synth_reference(seed=20260928, n_species=25, strains_per_species=4, genome_len=2_200_000, strain_divergence=0.02, genus_divergence=0.2)
+    w = capi.lib().mm_recommended_window(1e-3, K, PI, 1000, ref.total_bases)
+    idx = ctx.index(ref, K, w)
+    reads, _ = ctx.synth_reads(ref, seed=1000, n_reads=n_reads, read_len=READ_LEN, read_len_min=0, sub_rate=0.04, ins_rate=0.03, del_rate=0.05, frac_random=0.05, n_abundant=100)
+    M = ctx.map_batch(idx, reads, K, w, pi=PI)
+    M.keep_best(K)
+    off, rec = M.fetch()
+    n = len(rec)
+    print(f"{n_reads} reads of {READ_LEN} bases against {ref.total_bases} reference bases (k {K}, w {w}, pi {PI}): {n} best mappings", flush=True)
+    for rep in range(3):
+        t0 = time.perf_counter()
+        dist, first, last = ctx.mapping_edit_distances(M, reads, ref, PI, n)
+        dt = time.perf_counter() - t0
+        al = dist >= 0
+        print(f"mm_mapping_edit_distances call {rep}: {1e3 * dt:.1f} ms wall with the copies to the host, {n / dt:.0f} jobs/s; {int(al.sum())} of {n} aligned, "
+              f"mean distance {float(dist[al].mean()) if al.any() else float('nan'):.1f}, mean aligned length {float((last[al] - first[al] + 1).mean()) if al.any() else float('nan'):.1f}", flush=True)
+    pick = np.random.default_rng(1).choice(n, size=min(n_sample, n), replace=False)
+    rl, cl = reads.lengths(), ref.lengths()
+    lines = []
+    for i in pick:
+        r = rec[i]
+        L, C = int(rl[r["read"]]), int(cl[r["ref_contig"]])
+        pad = 64 + L // 16
+        ws, we = min(max(0, int(r["ref_start"]) - pad), C), min(C, int(r["ref_start"]) + L + pad)
+        we = max(we, ws)
+        cap = int(np.floor(1.5 * L * (100.0 - float(np.float32(PI))) / 100.0))
+        d, a, b = (int(dist[i]), int(first[i]) - ws, int(last[i]) + 1 - ws) if dist[i] >= 0 else (-1, -1, -1)
+        lines.append(f"{int(r['strand'])} {cap} {d} {a} {b} ={reads.fetch(int(r['read']), L).decode()} ={ref.fetch(int(r['ref_contig']), C)[ws:we].decode()}")
+    M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
+    exe = os.path.join(ROOT, "tools", "_tmp", "edit_host_align")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tools", "edit_host_align.cpp")], check=True)
+    subprocess.run([exe], input=("\n".join(lines) + "\n").encode(), check=True)
+
+
+def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--child":
+        return child(int(sys.argv[2]), int(sys.argv[3]))
+    n_reads = int(sys.argv[1]) if len(sys.argv) > 1 else 100_000
+    n_sample = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(n_reads), str(n_sample)], env=dict(os.environ, MM_EDIT_TIMING="1"),
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1500)
+    text = f"tools/edit_kernel_stats.py {n_reads} {n_sample}: one batch of {n_reads} reads, best mappings only; host sample of {n_sample} jobs\n" + p.stdout.decode()
+    print(text)
+    if p.returncode != 0:
+        sys.exit(p.returncode)
+    with open(os.path.join(ROOT, "profiles", "edit_kernel_stats.txt"), "w") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()
