@@ -29,7 +29,8 @@ extern "C" {
                             * 4: mm_sketch_batch, mm_ctx_release_cached, mm_index_dup_neighbours;
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
-                            *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances (additions to 6) */
+                            *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances,
+                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_* (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -49,6 +50,7 @@ typedef struct mm_index mm_index;      /* reference sketch of one index chunk, r
 typedef struct mm_mapping mm_mapping;  /* mapping results of one read batch, resident in HBM      */
 typedef struct mm_em mm_em;            /* EM state (mappings x taxa) resident in HBM              */
 typedef struct mm_gzip mm_gzip;        /* a plain gzip stream being inflated on a context's device */
+typedef struct mm_alignment mm_alignment;  /* base-level alignments (CIGAR runs) of a batch of jobs, in host memory */
 typedef struct mm_hpc_map mm_hpc_map;  /* compressed -> raw coordinates of a homopolymer-compressed set, resident in HBM */
 
 /* ---- context -------------------------------------------------------------------------------- */
@@ -467,6 +469,27 @@ int mm_edit_infix(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* referenc
  * aligned.  `reads` is the set that was mapped, `reference` the set whose contig numbering the records use; cap: room in the output arrays. */
 int mm_mapping_edit_distances(mm_ctx* ctx, const mm_mapping* mapping, const mm_seqset* reads, const mm_seqset* reference, float perc_identity,
                               int32_t* dist_out, int64_t* first_out, int64_t* last_out, int64_t cap);
+
+/* Base-level alignments of the same jobs ("Alignments"; the definition: csrc/mm_edit_core.hpp).  A job that is aligned has d, a,
+ * b as above.  Let Q be the oriented read of length m, T = window[a, b) of length n, and E[i][j] the unit-cost edit distance of Q[i, m) to T[j, n)
+ * (E[m][j] = n - j, E[i][n] = m - i, E[0][0] = d).  The alignment is the walk from (0, 0) to (m, n) that takes at each cell the first of
+ *   =  if i < m, j < n and Q[i] matches T[j]           -> (i + 1, j + 1)
+ *   X  if i < m, j < n and E[i+1][j+1] + 1 == E[i][j]  -> (i + 1, j + 1)
+ *   I  if i < m and E[i+1][j] + 1 == E[i][j]           -> (i + 1, j)      (consumes a read base)
+ *   D  otherwise                                       -> (i, j + 1)      (consumes a window base)
+ * with equal neighbours merged into runs, each one 32-bit word as in BAM: len << 4 | op, I = 1, D = 2, = = 7, X = 8.  X + I + D bases = d,
+ * = + X + I = m, = + X + D = n, at most 2 d + 1 runs, the first and the last never D.  A job that is not aligned, and an empty read, has no runs.
+ * For strand -1 the runs are those of the reverse-complemented read along the forward contig (PAF's convention).
+ * mm_edit_infix_align: the checks and messages of mm_edit_infix, nothing launched on a bad job, *out NULL on every error.  mm_mapping_align: the
+ * window and cap rules of mm_mapping_edit_distances.  dist / first / last are exactly what those two calls return for the same jobs (window
+ * coordinates half-open for the former, 0-based inclusive contig coordinates for the latter, -1 -1 -1: not aligned).  The runs of job i are
+ * ops[op_off[i], op_off[i + 1]).  The result lives in host memory until mm_alignment_destroy; no result depends on MM_EDIT_TRACE_MB. */
+int mm_edit_infix_align(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand,
+                        const int32_t* contig, const int64_t* ws, const int64_t* we, const int32_t* max_dist, mm_alignment** out);
+int mm_mapping_align(mm_ctx* ctx, const mm_mapping* mapping, const mm_seqset* reads, const mm_seqset* reference, float perc_identity, mm_alignment** out);
+int mm_alignment_sizes(const mm_alignment* al, int64_t* n_jobs, int64_t* n_ops);
+int mm_alignment_fetch(const mm_alignment* al, int32_t* dist /* [n_jobs] */, int64_t* first, int64_t* last, int64_t* op_off /* [n_jobs + 1] */, uint32_t* ops /* [n_ops] */);
+void mm_alignment_destroy(mm_alignment* al);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------------------------- */
 #define MM_COMM_ID_BYTES 128

@@ -193,6 +193,11 @@ def lib() -> C.CDLL:
             "mm_ident_filter": (C.c_int, [vp, i64, vp, vp, vp, vp, i32, f64, vp, P(i64), P(i64), vp, vp, vp, vp, vp, vp, vp, P(i64), P(i64)]),
             "mm_edit_infix": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
             "mm_mapping_edit_distances": (C.c_int, [vp, vp, vp, vp, f32, vp, vp, vp, i64]),
+            "mm_edit_infix_align": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+            "mm_mapping_align": (C.c_int, [vp, vp, vp, vp, f32, vp]),
+            "mm_alignment_sizes": (C.c_int, [vp, vp, vp]),
+            "mm_alignment_fetch": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+            "mm_alignment_destroy": (None, [vp]),
             "mm_comm_unique_id": (C.c_int, [C.c_char_p]),
             "mm_comm_init": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
             "mm_comm_allreduce_f64": (C.c_int, [vp, vp, i64]),
@@ -508,6 +513,38 @@ class Context:
         dist, first, last = np.full(n_records, -2, dtype=np.int32), np.full(n_records, -2, dtype=np.int64), np.full(n_records, -2, dtype=np.int64)
         self.check(lib().mm_mapping_edit_distances(self.h, mapping.h, reads.h, reference.h, float(perc_identity), _ptr(dist), _ptr(first), _ptr(last), n_records))
         return dist, first, last
+
+    def _alignment(self, status, handle):
+        """(dist, first, last, op_off, ops) of an mm_alignment, which is destroyed; `handle` is NULL after an error"""
+        try:
+            self.check(status)
+            n, k = C.c_int64(0), C.c_int64(0)
+            assert lib().mm_alignment_sizes(handle, C.byref(n), C.byref(k)) == 0
+            dist, first, last = np.full(n.value, -2, dtype=np.int32), np.full(n.value, -2, dtype=np.int64), np.full(n.value, -2, dtype=np.int64)
+            op_off, ops = np.zeros(n.value + 1, dtype=np.int64), np.zeros(k.value, dtype=np.uint32)
+            assert lib().mm_alignment_fetch(handle, _ptr(dist), _ptr(first), _ptr(last), _ptr(op_off), _ptr(ops)) == 0
+            return dist, first, last, op_off, ops
+        finally:
+            self.last_alignment_handle = handle.value              # (what the call left in *out: None after a refusal)
+            if handle.value:
+                lib().mm_alignment_destroy(handle)
+
+    def edit_infix_align(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, ws, we, max_dist):
+        """edit_infix's jobs with their base-level alignments (mm_edit_infix_align).  Returns (dist, begin, end, op_off, ops): the first three as
+        edit_infix gives them; the runs of job i are ops[op_off[i]:op_off[i + 1]], each len << 4 | op with I = 1, D = 2, = = 7, X = 8."""
+        rd, sd, cg, md = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, max_dist))
+        w0, w1 = np.ascontiguousarray(ws, dtype=np.int64), np.ascontiguousarray(we, dtype=np.int64)
+        n = len(rd)
+        assert all(len(x) == n for x in (sd, cg, md, w0, w1))
+        h = C.c_void_p(0xDEAD)                                      # (the call sets it, to NULL on an error)
+        st = lib().mm_edit_infix_align(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(w0), _ptr(w1), _ptr(md), C.byref(h))
+        return self._alignment(st, h)
+
+    def mapping_align(self, mapping: "Mapping", reads: "SeqSet", reference: "SeqSet", perc_identity: float):
+        """mapping_edit_distances with the base-level alignment of every record, in fetch order (mm_mapping_align): (dist, first, last, op_off, ops)"""
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_mapping_align(self.h, mapping.h, reads.h, reference.h, float(perc_identity), C.byref(h))
+        return self._alignment(st, h)
 
     # ---- communicator
     @staticmethod

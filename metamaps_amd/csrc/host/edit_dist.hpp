@@ -9,12 +9,9 @@
 
 namespace {
 
-// the lines of one batch; rec: the batch's records as fetched (the order of the lines of PREFIX); consumes nothing
-void edit_distance_lines(mm_ctx* ctx, const mm_mapping* m, const mm_seqset* reads, const mm_seqset* reference, float pi, const std::vector<std::string>& names,
-                         const std::vector<int64_t>& off, const std::vector<mm_map_record>& rec, const std::vector<std::string>& cname, std::string& out) {
-  std::vector<int32_t> dist(rec.size());
-  std::vector<int64_t> first(rec.size()), last(rec.size());
-  ck(ctx, mm_mapping_edit_distances(ctx, m, reads, reference, pi, dist.data(), first.data(), last.data(), (int64_t)rec.size()), "edit distances");
+// the lines of one batch from its records' d, first, last; rec: the batch's records as fetched (the order of the lines of PREFIX)
+void edit_distance_text(const int32_t* dist, const int64_t* first, const int64_t* last, const std::vector<std::string>& names, const std::vector<int64_t>& off,
+                        const std::vector<mm_map_record>& rec, const std::vector<std::string>& cname, std::string& out) {
   out.clear();
   out.reserve(rec.size() * 64);
   for (size_t r = 0; r + 1 < off.size(); ++r)
@@ -24,6 +21,14 @@ void edit_distance_lines(mm_ctx* ctx, const mm_mapping* m, const mm_seqset* read
       if (dist[(size_t)i] < 0) { out += " NA NA NA\n"; continue; }
       out += ' '; append_int(out, dist[(size_t)i]); out += ' '; append_int(out, (long long)first[(size_t)i]); out += ' '; append_int(out, (long long)last[(size_t)i]); out += '\n';
     }
+}
+// ... aligned here; consumes nothing
+void edit_distance_lines(mm_ctx* ctx, const mm_mapping* m, const mm_seqset* reads, const mm_seqset* reference, float pi, const std::vector<std::string>& names,
+                         const std::vector<int64_t>& off, const std::vector<mm_map_record>& rec, const std::vector<std::string>& cname, std::string& out) {
+  std::vector<int32_t> dist(rec.size());
+  std::vector<int64_t> first(rec.size()), last(rec.size());
+  ck(ctx, mm_mapping_edit_distances(ctx, m, reads, reference, pi, dist.data(), first.data(), last.data(), (int64_t)rec.size()), "edit distances");
+  edit_distance_text(dist.data(), first.data(), last.data(), names, off, rec, cname, out);
 }
 
 }  // namespace

@@ -6,6 +6,7 @@
 #include "cli_device.hpp"
 #include "cli_switches.hpp"
 #include "edit_dist.hpp"
+#include "paf_out.hpp"
 #include "fast_format.hpp"
 #include "id_set.hpp"
 #include "query_reader.hpp"
@@ -149,6 +150,7 @@ struct MapRun {
   // compressed ones: clen holds the compressed contig lengths, clen_raw what is printed; hpc_map[d] translates the records' coordinates on device d
   const bool hpc = o.v.count("hpc") != 0;
   const bool edit = o.v.count("edit-distance") != 0;             // --edit-distance: the packed reference stays on every device, a batch's reads live until its distances are fetched (edit_dist.hpp)
+  const bool paf = o.v.count("paf") != 0;                        // --paf (implies --edit-distance): the same call also gives the CIGARs of PREFIX.paf (paf_out.hpp)
   std::vector<int> clen_raw; std::vector<mm_hpc_map*> hpc_map;
   struct Chunk { int first, count; std::string file; };
   std::vector<Chunk> chunks;
@@ -168,7 +170,7 @@ struct MapRun {
   mm_map_params mp{};
   std::vector<int32_t> chunk_base;
   // what a worker hands to the writer: the finished text of one batch
-  struct Done { size_t file = 0; std::vector<std::string> names; std::vector<int> lens; std::vector<int> clens /* --hpc: the compressed lengths (lens stay raw) */; std::vector<int64_t> off; std::string text; std::string gz /* --compress-output: the text as BGZF members */; std::string edit /* --edit-distance: the batch's lines of PREFIX.editDistances */; std::vector<LineMeta> meta; double t_mapq = 0, t_fetch = 0, t_format = 0; };
+  struct Done { size_t file = 0; std::vector<std::string> names; std::vector<int> lens; std::vector<int> clens /* --hpc: the compressed lengths (lens stay raw) */; std::vector<int64_t> off; std::string text; std::string gz /* --compress-output: the text as BGZF members */; std::string edit /* --edit-distance: the batch's lines of PREFIX.editDistances */; std::string paf /* --paf: the batch's lines of PREFIX.paf */; std::vector<LineMeta> meta; double t_mapq = 0, t_fetch = 0, t_format = 0; };
   // --then-classify: the batches of every query file as they were written, in order (text + the parsed fields of every line): what classify takes instead of the file
   const bool keep_lines = o.v.count("then-classify") && !sw.classify_from_file;
   // --compress-output: the mappings go to PREFIX.gz as BGZF; a batch's text is deflated by the context that mapped it, right behind its formatting
@@ -593,7 +595,7 @@ struct MapRun {
                 << (place == Place::Sharded ? "the chunk indexes are spread over the devices" : "chunk indexes are built and mapped one after the other") << "\n";
     }
     if (place != Place::Replicated && NC == 1 && !from_index && !maxMem) die("--stream-chunks / --shard-index need --maxmemory (the chunk rule of the reference, winSketch.hpp:274-329)");
-    if (edit && place != Place::Replicated) die("--edit-distance needs the whole reference resident on every device, and this index does not fit one: run without it");
+    if (edit && place != Place::Replicated) die(std::string(paf ? "--paf" : "--edit-distance") + " needs the whole reference resident on every device, and this index does not fit one: run without it");
     for (auto& d : devs) d.idx.assign(NC, nullptr);
     thr_of.assign(NC, INT_MAX);
   }
@@ -688,7 +690,9 @@ struct MapRun {
     const auto f1 = std::chrono::steady_clock::now();
     std::vector<mm_map_record> rec((size_t)dn->off.back());
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), rec.data(), (int64_t)rec.size()), "fetch");
-    if (reads) { edit_distance_lines(ctx, m, reads, refset[dev], pi, dn->names, dn->off, rec, cname, dn->edit); mm_seqset_destroy(reads); }
+    if (reads && paf) alignment_lines(ctx, m, reads, refset[dev], pi, dn->names, dn->lens, dn->off, rec, cname, clen, dn->edit, dn->paf);
+    else if (reads) edit_distance_lines(ctx, m, reads, refset[dev], pi, dn->names, dn->off, rec, cname, dn->edit);
+    if (reads) mm_seqset_destroy(reads);
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
     format_records(dn->names, dn->lens, dn->off, rec, cname, hpc ? clen_raw : clen, k, dn->text, keep_lines ? &dn->meta : nullptr, hpc ? raw_end.data() : nullptr, sw);
@@ -720,6 +724,7 @@ struct MapRun {
       std::ofstream out(out_name, std::ios::binary), unm(prefix + ".meta.unmappedReadsLengths");
       if (!out.is_open()) die("Cannot open output file " + out_name);
       std::ofstream ed; if (edit) { ed.open(prefix + ".editDistances", std::ios::binary); if (!ed.is_open()) die("Cannot open output file " + prefix + ".editDistances"); }
+      std::ofstream pf; if (paf) { pf.open(prefix + ".paf", std::ios::binary); if (!pf.is_open()) die("Cannot open output file " + prefix + ".paf"); }
       size_t total = 0, tooShort = 0, mapped = 0, notMapped = 0; IdSet seen;   // (id_set.hpp: a std::set of 10^6 IDs bounded the mapping phase)
       for (;;) {
         std::unique_ptr<Done> d = next(fi, seq);
@@ -738,6 +743,7 @@ struct MapRun {
         }
         if (compress) out.write(d->gz.data(), (std::streamsize)d->gz.size()); else out << d->text;
         if (edit) { ed << d->edit; std::string().swap(d->edit); }
+        if (paf) { pf << d->paf; std::string().swap(d->paf); }
         std::string().swap(d->gz);
         if (keep_lines) { if (kept.size() <= fi) kept.resize(fi + 1); d->names.clear(); d->names.shrink_to_fit(); kept[fi].push_back(std::move(d)); }
       }

@@ -51,6 +51,12 @@
 // until its distances are fetched.  PREFIX, .meta* and .parameters are the bytes of a run without the flag.  Refused: --hpc, index, mapAgainstIndex,
 // classify, and any run whose chunk indexes are sharded or streamed (--shard-index, --stream-chunks, or an index that does not fit one device).
 //
+// --paf (mapDirectly; not in the reference; implies --edit-distance): also PREFIX.paf, one PAF line per ALIGNED line of PREFIX in the same order,
+// "readID L 0 L strand contigID contigLen first last+1 matches alignmentLength 255 NM:i:d cg:Z:CIGAR" with = X I D runs: the base-level alignment
+// behind d, first and last (the definition: csrc/mm_edit_core.hpp; for strand - the reverse-complemented read along the forward contig).  The context
+// that mapped a batch traces it on the device in the one call that also gives the .editDistances lines (mm_mapping_align, host/paf_out.hpp).  A mapping
+// that is not aligned has no PAF line.  PREFIX.paf is plain text even under --compress-output.  Refused wherever --edit-distance is.
+//
 // --hpc (mapDirectly; not in the reference; minimap2's -H): homopolymer-compressed mapping.  Every maximal run of equal bytes of the reference and
 // of the reads — as hashed: upper-cased, IUPAC and N kept — becomes one byte, on the device (mm_seqset_hpc): the reference once per device behind
 // its upload, every read batch on the context that maps it.  The pipeline then runs unchanged on the compressed sequences: -m, the len < w and
@@ -105,7 +111,7 @@ Options parse(int argc, char** argv) {
     if (a == "--stream-chunks") { o.stream = true; continue; }
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
-    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
+    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
@@ -113,6 +119,8 @@ Options parse(int argc, char** argv) {
                    "  --edit-distance  (mapDirectly) also writes PREFIX.editDistances: readID contigID strand d first last for every line of PREFIX, the exact edit\n"
                    "         distance of the read inside the window around its mapped position and the 0-based inclusive contig coordinates of that alignment\n"
                    "         (NA NA NA beyond 1.5 (100 - pi) % of the read length); not with --hpc, --shard-index, --stream-chunks\n"
+                   "  --paf  (mapDirectly) implies --edit-distance and also writes PREFIX.paf: one PAF line with NM and a cg:Z: CIGAR of = X I D runs for every aligned\n"
+                   "         line of PREFIX, the alignment traced on the device; not with --hpc, --shard-index, --stream-chunks\n"
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
                    "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
                    "  --genes  (classify, mapDirectly --then-classify) gene-level analysis against DB_annotations.txt and DB_proteins.faa.annotated of the DB:\n"
@@ -206,10 +214,12 @@ int main(int argc, char** argv) {
   const IdentOpts identf_opts = ident_options(o);
   if ((identf_opts.on || identf_opts.refit) && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--min-identity and --refit need classify or mapDirectly --then-classify");
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
+  if (o.v.count("paf")) o.v["edit-distance"] = "1";              // (--paf implies it, and inherits its refusals under its own name)
   if (o.v.count("edit-distance")) {                              // (refused before any device work)
-    if (mode != "mapDirectly") die("--edit-distance belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
-    if (o.v.count("hpc")) die("--edit-distance cannot be combined with --hpc: the raw reference does not stay on the device");
-    if (o.stream || o.shard) die("--edit-distance cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");
+    const std::string flag = o.v.count("paf") ? "--paf" : "--edit-distance";
+    if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
+    if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reference does not stay on the device");
+    if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");
   }
   if (mode == "mapDirectly" || mode == "index" || mode == "mapAgainstIndex") return map_mode(o, mode, sw);
   if (mode == "classify") {

@@ -1,0 +1,44 @@
+// mapDirectly --paf: PREFIX.paf beside PREFIX and PREFIX.editDistances, one line per ALIGNED line of PREFIX in that order (tab-separated):
+//   readID  L  0  L  +|-  contigID  contigLen  first  last+1  n_eq  n_eq+n_X+n_I+n_D  255  NM:i:d  cg:Z:<runs with = X I D>
+// The read is aligned whole (query start 0, end L); first / last+1 are the alignment's 0-based half-open contig coordinates; for strand - the CIGAR is that
+// of the reverse-complemented read along the forward contig, as PAF has it.  A mapping that is not aligned (NA NA NA in .editDistances) has no line.
+// One call (mm_mapping_align) on the context that mapped the batch gives d, first, last and the runs: the lines of PREFIX.editDistances come from the
+// same answer (edit_dist.hpp: the bytes of a run with --edit-distance alone), nothing is aligned twice.
+#pragma once
+#include "edit_dist.hpp"
+
+namespace {
+
+void alignment_lines(mm_ctx* ctx, const mm_mapping* m, const mm_seqset* reads, const mm_seqset* reference, float pi, const std::vector<std::string>& names,
+                     const std::vector<int>& lens, const std::vector<int64_t>& off, const std::vector<mm_map_record>& rec, const std::vector<std::string>& cname,
+                     const std::vector<int>& clen, std::string& edit, std::string& paf) {
+  mm_alignment* al = nullptr;
+  ck(ctx, mm_mapping_align(ctx, m, reads, reference, pi, &al), "alignments");
+  int64_t n_jobs = 0, n_ops = 0;
+  mm_alignment_sizes(al, &n_jobs, &n_ops);
+  if (n_jobs != (int64_t)rec.size()) die("internal error: alignments and records differ in number");
+  std::vector<int32_t> dist(rec.size());
+  std::vector<int64_t> first(rec.size()), last(rec.size()), op_off(rec.size() + 1);
+  std::vector<uint32_t> ops((size_t)n_ops);
+  mm_alignment_fetch(al, dist.data(), first.data(), last.data(), op_off.data(), ops.data());
+  mm_alignment_destroy(al);
+  edit_distance_text(dist.data(), first.data(), last.data(), names, off, rec, cname, edit);
+  paf.clear();
+  paf.reserve(rec.size() * 96 + ops.size() * 4);
+  static const char LETTER[16] = {'?', 'I', 'D', '?', '?', '?', '?', '=', 'X', '?', '?', '?', '?', '?', '?', '?'};
+  for (size_t r = 0; r + 1 < off.size(); ++r)
+    for (int64_t i = off[r]; i < off[r + 1]; ++i) {
+      if (dist[(size_t)i] < 0) continue;
+      const mm_map_record& x = rec[(size_t)i];
+      long long n_eq = 0, n_all = 0;
+      for (int64_t k = op_off[(size_t)i]; k < op_off[(size_t)i + 1]; ++k) { const uint32_t w = ops[(size_t)k]; n_all += w >> 4; if ((w & 15u) == 7u) n_eq += w >> 4; }
+      paf += names[r]; paf += '\t'; append_int(paf, lens[r]); paf += "\t0\t"; append_int(paf, lens[r]); paf += '\t'; paf += x.strand == 1 ? '+' : '-'; paf += '\t';
+      paf += cname[(size_t)x.ref_contig]; paf += '\t'; append_int(paf, clen[(size_t)x.ref_contig]); paf += '\t'; append_int(paf, (long long)first[(size_t)i]); paf += '\t';
+      append_int(paf, (long long)last[(size_t)i] + 1); paf += '\t'; append_int(paf, n_eq); paf += '\t'; append_int(paf, n_all); paf += "\t255\tNM:i:"; append_int(paf, dist[(size_t)i]);
+      paf += "\tcg:Z:";
+      for (int64_t k = op_off[(size_t)i]; k < op_off[(size_t)i + 1]; ++k) { const uint32_t w = ops[(size_t)k]; append_int(paf, (long long)(w >> 4)); paf += LETTER[w & 15u]; }
+      paf += '\n';
+    }
+}
+
+}  // namespace

@@ -994,6 +994,45 @@ int mm_mapping_edit_distances(mm_ctx* ctx, const mm_mapping* mapping, const mm_s
     mm::edit_mapping_run(ctx, mapping, reads, reference, perc_identity, dist_out, first_out, last_out, cap);
   });
 }
+struct mm_alignment { mm::EditAlignment a; };                      // (host memory only: nothing of the device's outlives the call that made it)
+int mm_edit_infix_align(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand,
+                        const int32_t* contig, const int64_t* ws, const int64_t* we, const int32_t* max_dist, mm_alignment** out) {
+  if (!ctx || !reads || !reference || !out) return MM_ERR_ARG;
+  *out = nullptr;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(n_jobs >= 0 && n_jobs < ((int64_t)1 << 31), n_jobs < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_edit_infix_align: a negative number of jobs, or 2^31 or more");
+    MM_REQUIRE(n_jobs == 0 || (read && strand && contig && ws && we && max_dist), MM_ERR_ARG, "mm_edit_infix_align: a null array");
+    std::unique_ptr<mm_alignment> al(new mm_alignment());
+    mm::edit_infix_align_run(ctx, reads, reference, mm::EditInfixIn{n_jobs, read, strand, contig, ws, we, max_dist}, &al->a);
+    *out = al.release();
+  });
+}
+int mm_mapping_align(mm_ctx* ctx, const mm_mapping* mapping, const mm_seqset* reads, const mm_seqset* reference, float perc_identity, mm_alignment** out) {
+  if (!ctx || !mapping || !reads || !reference || !out) return MM_ERR_ARG;
+  *out = nullptr;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(mapping->n_rec < ((int64_t)1 << 31), MM_ERR_LIMIT, "mm_mapping_align: 2^31 records or more");
+    std::unique_ptr<mm_alignment> al(new mm_alignment());
+    mm::edit_mapping_align_run(ctx, mapping, reads, reference, perc_identity, &al->a);
+    *out = al.release();
+  });
+}
+int mm_alignment_sizes(const mm_alignment* al, int64_t* n_jobs, int64_t* n_ops) {
+  if (!al || !n_jobs || !n_ops) return MM_ERR_ARG;
+  *n_jobs = (int64_t)al->a.dist.size(); *n_ops = (int64_t)al->a.ops.size();
+  return MM_OK;
+}
+int mm_alignment_fetch(const mm_alignment* al, int32_t* dist, int64_t* first, int64_t* last, int64_t* op_off, uint32_t* ops) {
+  if (!al || !op_off || (!al->a.dist.empty() && (!dist || !first || !last)) || (!al->a.ops.empty() && !ops)) return MM_ERR_ARG;
+  const mm::EditAlignment& a = al->a;
+  if (!a.dist.empty()) { memcpy(dist, a.dist.data(), a.dist.size() * sizeof(int32_t)); memcpy(first, a.first.data(), a.first.size() * sizeof(int64_t)); memcpy(last, a.last.data(), a.last.size() * sizeof(int64_t)); }
+  memcpy(op_off, a.op_off.data(), a.op_off.size() * sizeof(int64_t));
+  if (!a.ops.empty()) memcpy(ops, a.ops.data(), a.ops.size() * sizeof(uint32_t));
+  return MM_OK;
+}
+void mm_alignment_destroy(mm_alignment* al) { delete al; }
 
 // ---- communicator -------------------------------------------------------------------------------------
 int mm_comm_unique_id(char id[MM_COMM_ID_BYTES]) {

@@ -8,6 +8,18 @@
 //   d            min over 0 <= a <= b <= n of the unit-cost Levenshtein distance of Q and R[a, b) (the read global, the window's ends free)
 //   b            the smallest end at which some R[a, b) has distance d;  a: the largest start with Lev(Q, R[a, b)) = d
 //   not aligned  d > cap, or L > EDIT_MAX_READ
+// The alignment of a job that is aligned (mapDirectly --paf; mm_edit_trace_core.hpp computes it; DESIGN.md section 1, "Alignments"):
+//   T, E         T = window[a, b) of length n = b - a.  E[i][j] = the unit-cost edit distance of Q[i, m) to T[j, n): E[m][j] = n - j, E[i][n] = m - i,
+//                E[0][0] = d.  Bases match as above
+//   walk         from (0, 0) to (m, n), at each cell the first of these that applies:
+//                  =  if i < m, j < n and Q[i] matches T[j]                  -> (i + 1, j + 1)
+//                  X  if i < m, j < n and E[i + 1][j + 1] + 1 == E[i][j]     -> (i + 1, j + 1)
+//                  I  if i < m and E[i + 1][j] + 1 == E[i][j]                -> (i + 1, j)       it consumes a read base
+//                  D  otherwise                                             -> (i, j + 1)       it consumes a window base
+//   runs         equal neighbouring operations merged, each one word as BAM has them: len << 4 | op, I = 1, D = 2, = = 7, X = 8
+//   follows      the X + I + D bases are d; = + X + I = m and = + X + D = n; at most 2 d + 1 runs (d edits separate at most d + 1 runs of =); the first
+//                and the last run are never D (b is the smallest end and a the largest start at distance d)
+//   no runs      a job that is not aligned, and m = 0
 // Wavefront alignment (Marco-Sola et al. 2021) in its edit-distance form, without traceback.  Diagonal k = j - i; H_s[k] = the furthest read index i
 // on diagonal k that s edits reach.  Pass 1 starts on every diagonal k >= 0 (the window's start is free), H_0[k] = extend(0, k), and goes
 //   H_s[k] = extend(max(H_{s-1}[k] + 1, H_{s-1}[k-1], H_{s-1}[k+1] + 1)) clipped to i <= m and i + k <= n

@@ -2,7 +2,11 @@
 uniform synthetic reference, best mappings only) timed stage by stage with events on the context's stream (MM_EDIT_TIMING=1, three calls in a fresh child
 process), and csrc/mm_edit_core.hpp's edit_infix_host on one host thread over a sample of the same jobs (tools/edit_host_align.cpp, built with g++ into
 tools/_tmp/), which also holds the device's answers against the host's.
-Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes profiles/edit_kernel_stats.txt)"""
+Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes profiles/edit_kernel_stats.txt)
+       python tools/edit_kernel_stats.py --align [n_reads]            (writes profiles/edit_trace_stats.txt)
+--align: the same batch through mm_mapping_align (the alignments behind the distances: mm_edit_trace_core.hpp) in one child process under one timeout: one
+distance-only call as the yardstick, then two aligning calls with their jobs / align / trace stage times, the scratch budget and the launches it led to (the
+MM_EDIT_TIMING line), the runs, and the size PREFIX.paf would have for these mappings (reads named read<i>, contigs contig<c>)."""
 import os
 import subprocess
 import sys
@@ -53,9 +57,73 @@ def child(n_reads, n_sample):
     subprocess.run([exe], input=("\n".join(lines) + "\n").encode(), check=True)
 
 
+def paf_bytes(dist, first, last, op_off, ops, read, read_len, contig, contig_len):
+    """the bytes of PREFIX.paf for these answers with reads named read<i> and contigs contig<c>, and those of its CIGAR text; also holds the runs against
+    dist, the read lengths and first / last (X + I + D = d, = + X + I = m, = + X + D = n)"""
+    ln, op = (ops >> 4).astype(np.int64), (ops & 15).astype(np.int64)
+    al = dist >= 0
+    job = np.repeat(np.arange(len(dist)), np.diff(op_off))
+
+    def per_job(v):
+        return np.bincount(job, weights=v, minlength=len(dist)).astype(np.int64)[al]
+
+    def digits(v):
+        return np.floor(np.log10(np.maximum(v, 1))).astype(np.int64) + 1
+    n_eq, n_all = per_job(ln * (op == 7)), per_job(ln)
+    assert np.array_equal(n_all - n_eq, dist[al]), "X + I + D bases = d"
+    assert np.array_equal(per_job(ln * (op != 2)), read_len[al]), "= + X + I = m"
+    assert np.array_equal(per_job(ln * (op != 1)), (last - first + 1)[al]), "= + X + D = n"
+    cg = int(per_job(digits(ln) + 1).sum())
+    cols = [digits(read[al]) + 4, 2 * digits(read_len[al]), digits(contig[al]) + 6, digits(contig_len[al]), digits(first[al]), digits(last[al] + 1), digits(n_eq), digits(n_all),
+            digits(dist[al].astype(np.int64))]
+    fixed = 13 + 1 + len("0") + len("+") + len("255") + len("NM:i:") + len("cg:Z:")       # 13 tabs, the newline and the constant fields
+    return int(sum(int(c.sum()) for c in cols)) + fixed * int(al.sum()) + cg, cg
+
+
+def child_align(n_reads):
+    from metamaps_amd import capi
+    ctx = capi.Context(0)
+    ref = ctx.synth_reference(seed=20260928, n_species=25, strains_per_species=4, genome_len=2_200_000, strain_divergence=0.02, genus_divergence=0.2)
+    w = capi.lib().mm_recommended_window(1e-3, K, PI, 1000, ref.total_bases)
+    idx = ctx.index(ref, K, w)
+    reads, _ = ctx.synth_reads(ref, seed=1000, n_reads=n_reads, read_len=READ_LEN, read_len_min=0, sub_rate=0.04, ins_rate=0.03, del_rate=0.05, frac_random=0.05, n_abundant=100)
+    M = ctx.map_batch(idx, reads, K, w, pi=PI)
+    M.keep_best(K)
+    off, rec = M.fetch()
+    n = len(rec)
+    print(f"{n_reads} reads of {READ_LEN} bases against {ref.total_bases} reference bases (k {K}, w {w}, pi {PI}): {n} best mappings", flush=True)
+    t0 = time.perf_counter()
+    dist0, first0, last0 = ctx.mapping_edit_distances(M, reads, ref, PI, n)
+    print(f"mm_mapping_edit_distances (distance only): {1e3 * (time.perf_counter() - t0):.1f} ms wall with the copies to the host", flush=True)
+    for rep in range(2):
+        t0 = time.perf_counter()
+        dist, first, last, op_off, ops = ctx.mapping_align(M, reads, ref, PI)
+        dt = time.perf_counter() - t0
+        assert np.array_equal(dist, dist0) and np.array_equal(first, first0) and np.array_equal(last, last0)
+        print(f"mm_mapping_align call {rep}: {1e3 * dt:.1f} ms wall with the copies to the host, {n / dt:.0f} jobs/s; {int((dist >= 0).sum())} of {n} aligned, "
+              f"{len(ops)} runs ({len(ops) / max(n, 1):.1f} per job, {4 * len(ops) / 1e6:.1f} MB)", flush=True)
+    rl, cl = reads.lengths()[rec["read"]].astype(np.int64), ref.lengths()[rec["ref_contig"]].astype(np.int64)
+    total, cg = paf_bytes(dist, first, last, op_off, ops, rec["read"].astype(np.int64), rl, rec["ref_contig"].astype(np.int64), cl)
+    print(f"PREFIX.paf of these mappings: {total / 1e6:.1f} MB, {cg / 1e6:.1f} MB of it CIGAR text", flush=True)
+    M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--child":
         return child(int(sys.argv[2]), int(sys.argv[3]))
+    if len(sys.argv) > 1 and sys.argv[1] == "--child-align":
+        return child_align(int(sys.argv[2]))
+    if len(sys.argv) > 1 and sys.argv[1] == "--align":
+        n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-align", str(n_reads)], env=dict(os.environ, MM_EDIT_TIMING="1"),
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1100)
+        text = f"tools/edit_kernel_stats.py --align {n_reads}: one batch of {n_reads} reads, best mappings only; MM_EDIT_TRACE_MB {os.environ.get('MM_EDIT_TRACE_MB', 'unset')}\n" + p.stdout.decode()
+        print(text)
+        if p.returncode != 0:
+            sys.exit(p.returncode)
+        with open(os.path.join(ROOT, "profiles", "edit_trace_stats.txt"), "w") as f:
+            f.write(text)
+        return None
     n_reads = int(sys.argv[1]) if len(sys.argv) > 1 else 100_000
     n_sample = int(sys.argv[2]) if len(sys.argv) > 2 else 200
     p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(n_reads), str(n_sample)], env=dict(os.environ, MM_EDIT_TIMING="1"),
