@@ -30,7 +30,7 @@ extern "C" {
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
                             *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances,
-                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_* (additions to 6) */
+                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_* (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -51,6 +51,7 @@ typedef struct mm_mapping mm_mapping;  /* mapping results of one read batch, res
 typedef struct mm_em mm_em;            /* EM state (mappings x taxa) resident in HBM              */
 typedef struct mm_gzip mm_gzip;        /* a plain gzip stream being inflated on a context's device */
 typedef struct mm_alignment mm_alignment;  /* base-level alignments (CIGAR runs) of a batch of jobs, in host memory */
+typedef struct mm_bam mm_bam;          /* BGZF members holding BAM records of a batch of jobs, in host memory */
 typedef struct mm_hpc_map mm_hpc_map;  /* compressed -> raw coordinates of a homopolymer-compressed set, resident in HBM */
 
 /* ---- context -------------------------------------------------------------------------------- */
@@ -490,6 +491,33 @@ int mm_mapping_align(mm_ctx* ctx, const mm_mapping* mapping, const mm_seqset* re
 int mm_alignment_sizes(const mm_alignment* al, int64_t* n_jobs, int64_t* n_ops);
 int mm_alignment_fetch(const mm_alignment* al, int32_t* dist /* [n_jobs] */, int64_t* first, int64_t* last, int64_t* op_off /* [n_jobs + 1] */, uint32_t* ops /* [n_ops] */);
 void mm_alignment_destroy(mm_alignment* al);
+
+/* BAM records (SAM/BAM specification v1.6) of jobs that were aligned, encoded and deflated on the context's device ("BAM
+ * output"; the record: csrc/mm_bam_core.hpp).  The arrays are the caller's: read / strand / contig name the jobs, dist / first / op_off / ops are
+ * what mm_alignment_fetch gave for them (first: the 0-based contig coordinate of the alignment's first base), flag / mapq / names go into the
+ * records as they are.  A job with dist < 0, and one whose read is empty, has no record.  A record: refID = contig, pos = first, bin =
+ * reg2bin(first, first + reference span), l_seq = the read's length, next_refID = next_pos = -1, tlen = 0; the CIGAR is the runs as they are; SEQ
+ * is the read as its set holds it (for strand -1 reversed, each 4-bit code of =ACMGRSVTWYHKDBN bit-reversed; a byte outside the table is N), QUAL is
+ * 0xFF; the tags are NM:i (int32) = dist, MD:Z from the runs and the forward reference, and, for more than 65 535 runs, CG:B,I with the runs
+ * while the CIGAR field holds <l_seq>S<span>N.  The records of consecutive jobs go into groups of at most group_bytes raw bytes (0: 255 MiB; a larger
+ * record is a group of its own); each group is deflated where it was written and only its BGZF members come to the host, back to back.  The
+ * inflated stream does not depend on group_bytes.  The file's header and the 28-byte end-of-file block are the caller's to write.
+ * MM_ERR_ARG with "job <index>: rule <number>: ..." in mm_last_error, *out NULL and nothing written, for the lowest job that breaks a rule:
+ *   1 a read or contig outside its set                      5 the = X I runs do not add up to the read's length
+ *   2 a strand that is not +1 / -1, or flag & 0x10 that     6 first < 0, or first plus the = X D runs passes the contig's end
+ *     disagrees with it                                     7 the X I D runs do not add up to dist
+ *   3 a name of 0 or more than 254 bytes                    (rule 1 is asked of every job, the others of the jobs that have a record)
+ *   4 a run whose op is not 1, 2, 7 or 8, or of length 0 */
+int mm_bam_encode(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs,
+                  const int32_t* read, const int32_t* strand, const int32_t* contig,        /* the jobs that were aligned   */
+                  const int32_t* dist, const int64_t* first,                                /* dist < 0: no record          */
+                  const int64_t* op_off /* [n_jobs + 1] */, const uint32_t* ops,            /* as mm_alignment_fetch gives  */
+                  const uint16_t* flag, const uint8_t* mapq,
+                  const int64_t* name_off /* [n_jobs + 1] */, const char* names,
+                  int64_t group_bytes, mm_bam** out);
+int mm_bam_sizes(const mm_bam* bam, int64_t* n_records, int64_t* raw_bytes, int64_t* bgzf_bytes);
+int mm_bam_fetch(const mm_bam* bam, uint8_t* bgzf /* [bgzf_bytes] */);
+void mm_bam_destroy(mm_bam* bam);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------------------------- */
 #define MM_COMM_ID_BYTES 128

@@ -198,6 +198,10 @@ def lib() -> C.CDLL:
             "mm_alignment_sizes": (C.c_int, [vp, vp, vp]),
             "mm_alignment_fetch": (C.c_int, [vp, vp, vp, vp, vp, vp]),
             "mm_alignment_destroy": (None, [vp]),
+            "mm_bam_encode": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+            "mm_bam_sizes": (C.c_int, [vp, vp, vp, vp]),
+            "mm_bam_fetch": (C.c_int, [vp, vp]),
+            "mm_bam_destroy": (None, [vp]),
             "mm_comm_unique_id": (C.c_int, [C.c_char_p]),
             "mm_comm_init": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
             "mm_comm_allreduce_f64": (C.c_int, [vp, vp, i64]),
@@ -545,6 +549,32 @@ class Context:
         h = C.c_void_p(0xDEAD)
         st = lib().mm_mapping_align(self.h, mapping.h, reads.h, reference.h, float(perc_identity), C.byref(h))
         return self._alignment(st, h)
+
+    def bam_encode(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, flag, mapq, names, group_bytes=0):
+        """BAM records of aligned jobs as BGZF members (mm_bam_encode).  names: one bytes object per job.  Returns (members back to back as bytes,
+        number of records, raw bytes of the records)."""
+        rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
+        fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
+        op, fl, mq = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(flag, dtype=np.uint16), np.ascontiguousarray(mapq, dtype=np.uint8)
+        n = len(rd)
+        assert all(len(x) == n for x in (sd, cg, ds, fs, fl, mq, names)) and len(oo) == n + 1
+        no = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in names], out=no[1:])
+        text = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8).copy()
+        h = C.c_void_p(0xDEAD)                                      # (the call sets it, to NULL on an error)
+        st = lib().mm_bam_encode(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(fl), _ptr(mq), _ptr(no),
+                                 _ptr(text), int(group_bytes), C.byref(h))
+        try:
+            self.check(st)
+            nr, raw, nb = C.c_int64(-1), C.c_int64(-1), C.c_int64(-1)
+            assert lib().mm_bam_sizes(h, C.byref(nr), C.byref(raw), C.byref(nb)) == 0
+            out = np.zeros(max(nb.value, 1), dtype=np.uint8)
+            assert lib().mm_bam_fetch(h, _ptr(out)) == 0
+            return out[:nb.value].tobytes(), nr.value, raw.value
+        finally:
+            self.last_bam_handle = h.value                          # (what the call left in *out: None after a refusal)
+            if h.value:
+                lib().mm_bam_destroy(h)
 
     # ---- communicator
     @staticmethod

@@ -7,6 +7,7 @@
 #include "cli_switches.hpp"
 #include "edit_dist.hpp"
 #include "paf_out.hpp"
+#include "bam_out.hpp"
 #include "fast_format.hpp"
 #include "id_set.hpp"
 #include "query_reader.hpp"
@@ -151,6 +152,8 @@ struct MapRun {
   const bool hpc = o.v.count("hpc") != 0;
   const bool edit = o.v.count("edit-distance") != 0;             // --edit-distance: the packed reference stays on every device, a batch's reads live until its distances are fetched (edit_dist.hpp)
   const bool paf = o.v.count("paf") != 0;                        // --paf (implies --edit-distance): the same call also gives the CIGARs of PREFIX.paf (paf_out.hpp)
+  const bool bam = o.v.count("bam") != 0;                        // --bam (implies --edit-distance): that alignment also becomes the records of PREFIX.bam, encoded and deflated on the device (bam_out.hpp)
+  std::string bam_head;                                          // the header of every PREFIX.bam as BGZF members (the contigs are the run's)
   std::vector<int> clen_raw; std::vector<mm_hpc_map*> hpc_map;
   struct Chunk { int first, count; std::string file; };
   std::vector<Chunk> chunks;
@@ -170,7 +173,7 @@ struct MapRun {
   mm_map_params mp{};
   std::vector<int32_t> chunk_base;
   // what a worker hands to the writer: the finished text of one batch
-  struct Done { size_t file = 0; std::vector<std::string> names; std::vector<int> lens; std::vector<int> clens /* --hpc: the compressed lengths (lens stay raw) */; std::vector<int64_t> off; std::string text; std::string gz /* --compress-output: the text as BGZF members */; std::string edit /* --edit-distance: the batch's lines of PREFIX.editDistances */; std::string paf /* --paf: the batch's lines of PREFIX.paf */; std::vector<LineMeta> meta; double t_mapq = 0, t_fetch = 0, t_format = 0; };
+  struct Done { size_t file = 0; std::vector<std::string> names; std::vector<int> lens; std::vector<int> clens /* --hpc: the compressed lengths (lens stay raw) */; std::vector<int64_t> off; std::string text; std::string gz /* --compress-output: the text as BGZF members */; std::string edit /* --edit-distance: the batch's lines of PREFIX.editDistances */; std::string paf /* --paf: the batch's lines of PREFIX.paf */; std::string bam /* --bam: the batch's records of PREFIX.bam as BGZF members */; std::vector<LineMeta> meta; double t_mapq = 0, t_fetch = 0, t_format = 0; };
   // --then-classify: the batches of every query file as they were written, in order (text + the parsed fields of every line): what classify takes instead of the file
   const bool keep_lines = o.v.count("then-classify") && !sw.classify_from_file;
   // --compress-output: the mappings go to PREFIX.gz as BGZF; a batch's text is deflated by the context that mapped it, right behind its formatting
@@ -595,7 +598,7 @@ struct MapRun {
                 << (place == Place::Sharded ? "the chunk indexes are spread over the devices" : "chunk indexes are built and mapped one after the other") << "\n";
     }
     if (place != Place::Replicated && NC == 1 && !from_index && !maxMem) die("--stream-chunks / --shard-index need --maxmemory (the chunk rule of the reference, winSketch.hpp:274-329)");
-    if (edit && place != Place::Replicated) die(std::string(paf ? "--paf" : "--edit-distance") + " needs the whole reference resident on every device, and this index does not fit one: run without it");
+    if (edit && place != Place::Replicated) die(std::string(bam ? "--bam" : paf ? "--paf" : "--edit-distance") + " needs the whole reference resident on every device, and this index does not fit one: run without it");
     for (auto& d : devs) d.idx.assign(NC, nullptr);
     thr_of.assign(NC, INT_MAX);
   }
@@ -690,12 +693,17 @@ struct MapRun {
     const auto f1 = std::chrono::steady_clock::now();
     std::vector<mm_map_record> rec((size_t)dn->off.back());
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), rec.data(), (int64_t)rec.size()), "fetch");
-    if (reads && paf) alignment_lines(ctx, m, reads, refset[dev], pi, dn->names, dn->lens, dn->off, rec, cname, clen, dn->edit, dn->paf);
-    else if (reads) edit_distance_lines(ctx, m, reads, refset[dev], pi, dn->names, dn->off, rec, cname, dn->edit);
-    if (reads) mm_seqset_destroy(reads);
+    BatchAlignment al;                                             // one fetch serves .editDistances, .paf and .bam
+    if (reads && (paf || bam)) {
+      fetch_alignment(ctx, m, reads, refset[dev], pi, rec.size(), al);
+      edit_distance_text(al.dist.data(), al.first.data(), al.last.data(), dn->names, dn->off, rec, cname, dn->edit);
+      if (paf) paf_text(al, dn->names, dn->lens, dn->off, rec, cname, clen, dn->paf);
+    } else if (reads) edit_distance_lines(ctx, m, reads, refset[dev], pi, dn->names, dn->off, rec, cname, dn->edit);
+    if (reads && !bam) { mm_seqset_destroy(reads); reads = nullptr; }
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
     format_records(dn->names, dn->lens, dn->off, rec, cname, hpc ? clen_raw : clen, k, dn->text, keep_lines ? &dn->meta : nullptr, hpc ? raw_end.data() : nullptr, sw);
+    if (reads) { bam_members(ctx, reads, refset[dev], al, rec, dn->names, dn->off, dn->text, dn->bam); mm_seqset_destroy(reads); }   // --bam: the mapping qualities come from the formatted lines; the reads have stayed for SEQ
     if (compress) deflate_text(ctx, *dn);
     const auto f3 = std::chrono::steady_clock::now();
     pc.add("7a mapping qualities + offsets", std::chrono::duration<double>(f1 - f0).count());
@@ -725,6 +733,7 @@ struct MapRun {
       if (!out.is_open()) die("Cannot open output file " + out_name);
       std::ofstream ed; if (edit) { ed.open(prefix + ".editDistances", std::ios::binary); if (!ed.is_open()) die("Cannot open output file " + prefix + ".editDistances"); }
       std::ofstream pf; if (paf) { pf.open(prefix + ".paf", std::ios::binary); if (!pf.is_open()) die("Cannot open output file " + prefix + ".paf"); }
+      std::ofstream bf; if (bam) { bf.open(prefix + ".bam", std::ios::binary); if (!bf.is_open()) die("Cannot open output file " + prefix + ".bam"); bf.write(bam_head.data(), (std::streamsize)bam_head.size()); }
       size_t total = 0, tooShort = 0, mapped = 0, notMapped = 0; IdSet seen;   // (id_set.hpp: a std::set of 10^6 IDs bounded the mapping phase)
       for (;;) {
         std::unique_ptr<Done> d = next(fi, seq);
@@ -744,13 +753,15 @@ struct MapRun {
         if (compress) out.write(d->gz.data(), (std::streamsize)d->gz.size()); else out << d->text;
         if (edit) { ed << d->edit; std::string().swap(d->edit); }
         if (paf) { pf << d->paf; std::string().swap(d->paf); }
+        if (bam) { bf.write(d->bam.data(), (std::streamsize)d->bam.size()); std::string().swap(d->bam); }
         std::string().swap(d->gz);
         if (keep_lines) { if (kept.size() <= fi) kept.resize(fi + 1); d->names.clear(); d->names.shrink_to_fit(); kept[fi].push_back(std::move(d)); }
       }
       if (keep_lines && kept.size() <= fi) kept.resize(fi + 1);
-      if (compress) { static const unsigned char eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0}; out.write((const char*)eof, 28); }
+      static const unsigned char eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0}; if (compress) out.write((const char*)eof, 28);
       out.close();
       if (!out) die("Error writing " + out_name);
+      if (bam) { bf.write((const char*)eof, 28); bf.close(); if (!bf) die("Error writing " + prefix + ".bam"); }
       std::ofstream meta(prefix + ".meta");                      // mapWrap.h:178-184
       meta << "TotalReads " << total << "\nReadsTooShort " << tooShort << "\nReadsMapped " << mapped << "\nReadsNotMapped " << notMapped << "\n";
       std::ofstream ps(prefix + ".parameters");                  // mapWrap.h:196-211
@@ -969,6 +980,7 @@ struct MapRun {
     build_resident_indexes();
     mp = mm_map_params{k, w, pi, minLen};
     for (auto& ch : chunks) chunk_base.push_back(ch.first);
+    if (bam) bam_head = bam_header_members(ctx0, cname, clen);    // (before the workers take the first device's context)
     start_reader();
     if (prewarm.joinable()) prewarm.join();
     if (place != Place::Replicated) for (auto*& c : wctx) if (c) { mm_ctx_destroy(c); c = nullptr; }   // (the other modes drive one context per device)

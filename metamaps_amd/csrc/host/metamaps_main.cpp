@@ -57,6 +57,13 @@
 // that mapped a batch traces it on the device in the one call that also gives the .editDistances lines (mm_mapping_align, host/paf_out.hpp).  A mapping
 // that is not aligned has no PAF line.  PREFIX.paf is plain text even under --compress-output.  Refused wherever --edit-distance is.
 //
+// --bam (mapDirectly; not in the reference; implies --edit-distance; may be combined with --paf): also PREFIX.bam, one BAM record (SAM/BAM specification
+// v1.6) per ALIGNED line of PREFIX in the same order, unsorted, a read's records together (GO:query): the CIGAR of = X I D runs, NM, MD, the read's bases
+// (for strand - reverse-complemented) and 0xFF qualities; mapq from the printed field 14 of the record's line, 0x100 on every record of a read but the one
+// with the largest field 14 (host/bam_out.hpp).  The device that mapped a batch encodes its records from the alignment the .editDistances and .paf lines
+// come from and deflates them where they lie (mm_bam_encode); the file is BGZF whatever --compress-output says and ends with the end-of-file block.
+// Every other file of the run is the file of the same run without the flag.  Refused wherever --edit-distance is.
+//
 // --hpc (mapDirectly; not in the reference; minimap2's -H): homopolymer-compressed mapping.  Every maximal run of equal bytes of the reference and
 // of the reads — as hashed: upper-cased, IUPAC and N kept — becomes one byte, on the device (mm_seqset_hpc): the reference once per device behind
 // its upload, every read batch on the context that maps it.  The pipeline then runs unchanged on the compressed sequences: -m, the len < w and
@@ -111,7 +118,7 @@ Options parse(int argc, char** argv) {
     if (a == "--stream-chunks") { o.stream = true; continue; }
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
-    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
+    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" || a == "--bam" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
@@ -121,6 +128,8 @@ Options parse(int argc, char** argv) {
                    "         (NA NA NA beyond 1.5 (100 - pi) % of the read length); not with --hpc, --shard-index, --stream-chunks\n"
                    "  --paf  (mapDirectly) implies --edit-distance and also writes PREFIX.paf: one PAF line with NM and a cg:Z: CIGAR of = X I D runs for every aligned\n"
                    "         line of PREFIX, the alignment traced on the device; not with --hpc, --shard-index, --stream-chunks\n"
+                   "  --bam  (mapDirectly) implies --edit-distance and also writes PREFIX.bam (BGZF): one BAM record with the CIGAR, NM and MD for every aligned line of\n"
+                   "         PREFIX, encoded and deflated on the device; may be combined with --paf; not with --hpc, --shard-index, --stream-chunks\n"
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
                    "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
                    "  --genes  (classify, mapDirectly --then-classify) gene-level analysis against DB_annotations.txt and DB_proteins.faa.annotated of the DB:\n"
@@ -214,9 +223,9 @@ int main(int argc, char** argv) {
   const IdentOpts identf_opts = ident_options(o);
   if ((identf_opts.on || identf_opts.refit) && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--min-identity and --refit need classify or mapDirectly --then-classify");
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
-  if (o.v.count("paf")) o.v["edit-distance"] = "1";              // (--paf implies it, and inherits its refusals under its own name)
+  if (o.v.count("paf") || o.v.count("bam")) o.v["edit-distance"] = "1";   // (--paf and --bam imply it, and inherit its refusals under their own names)
   if (o.v.count("edit-distance")) {                              // (refused before any device work)
-    const std::string flag = o.v.count("paf") ? "--paf" : "--edit-distance";
+    const std::string flag = o.v.count("bam") ? "--bam" : o.v.count("paf") ? "--paf" : "--edit-distance";
     if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reference does not stay on the device");
     if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");

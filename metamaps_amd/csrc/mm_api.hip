@@ -11,6 +11,7 @@
 #include "mm_gene.hpp"
 #include "mm_ident.hpp"
 #include "mm_edit.hpp"
+#include "mm_bam.hpp"
 #include <chrono>
 #include <new>
 #include <rccl/rccl.h>
@@ -1033,6 +1034,33 @@ int mm_alignment_fetch(const mm_alignment* al, int32_t* dist, int64_t* first, in
   return MM_OK;
 }
 void mm_alignment_destroy(mm_alignment* al) { delete al; }
+
+struct mm_bam { mm::BamMembers b; };                               // (host memory only, as mm_alignment)
+int mm_bam_encode(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
+                  const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint16_t* flag, const uint8_t* mapq,
+                  const int64_t* name_off, const char* names, int64_t group_bytes, mm_bam** out) {
+  if (!ctx || !reads || !reference || !out) return MM_ERR_ARG;
+  *out = nullptr;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(n_jobs >= 0 && n_jobs < ((int64_t)1 << 31), n_jobs < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_bam_encode: a negative number of jobs, or 2^31 or more");
+    MM_REQUIRE(n_jobs == 0 || (read && strand && contig && dist && first && op_off && flag && mapq && name_off), MM_ERR_ARG, "mm_bam_encode: a null array");
+    std::unique_ptr<mm_bam> b(new mm_bam());
+    mm::bam_encode_run(ctx, reads, reference, mm::BamIn{n_jobs, read, strand, contig, dist, first, op_off, ops, flag, mapq, name_off, names}, group_bytes, &b->b);
+    *out = b.release();
+  });
+}
+int mm_bam_sizes(const mm_bam* b, int64_t* n_records, int64_t* raw_bytes, int64_t* bgzf_bytes) {
+  if (!b || !n_records || !raw_bytes || !bgzf_bytes) return MM_ERR_ARG;
+  *n_records = b->b.n_records; *raw_bytes = b->b.raw_bytes; *bgzf_bytes = (int64_t)b->b.bgzf.size();
+  return MM_OK;
+}
+int mm_bam_fetch(const mm_bam* b, uint8_t* bgzf) {
+  if (!b || (!b->b.bgzf.empty() && !bgzf)) return MM_ERR_ARG;
+  if (!b->b.bgzf.empty()) memcpy(bgzf, b->b.bgzf.data(), b->b.bgzf.size());
+  return MM_OK;
+}
+void mm_bam_destroy(mm_bam* b) { delete b; }
 
 // ---- communicator -------------------------------------------------------------------------------------
 int mm_comm_unique_id(char id[MM_COMM_ID_BYTES]) {

@@ -109,6 +109,22 @@ namespace mm {
 
 int64_t bgzf_deflate_bound(int64_t in_bytes) { return mmd::bound(in_bytes); }
 
+// The blocks of input that already lies on the device: d_in holds in_bytes bytes (16-byte aligned, 16 readable bytes behind them), n blocks of
+// BLOCK_IN bytes, mmd::LAUNCH_BLOCKS at most.  Member b comes back at down + b * MEMBER_MAX (host memory, pinned or not) with sizes[b] bytes;
+// the input never visits the host.  Returns when both are there.
+void bgzf_deflate_resident(mm_ctx* ctx, const uint8_t* d_in, int64_t in_bytes, int64_t n, uint8_t* down, int32_t* sizes) {
+  hipStream_t st = ctx->stream;
+  DBuf<uint8_t> d_slots((size_t)n * mmd::MEMBER_MAX);
+  const unsigned grid = (unsigned)std::min<int64_t>(n, (int64_t)std::max(1, ctx->cus) * 2);
+  DBuf<uint32_t> d_tok((size_t)grid * mmd::TOK_CAP);
+  DBuf<int32_t> d_sizes((size_t)n);
+  bgzf_deflate_kernel<<<dim3(grid), dim3(64), 0, st>>>(d_in, in_bytes, (int32_t)n, d_slots.p, d_tok.p, d_sizes.p);
+  MM_KERNEL_CHECK();
+  d_sizes.download(sizes, (size_t)n, st);
+  d_slots.download(down, (size_t)n * mmd::MEMBER_MAX, st);
+  MM_HIP(mm::stream_sync(st));
+}
+
 // mm_bgzf_deflate's body.  Argument errors throw MM_ERR_ARG.
 void bgzf_deflate(mm_ctx* ctx, const uint8_t* in, int64_t in_bytes, uint8_t* out, int64_t out_cap, int64_t* out_bytes, int32_t* n_blocks) {
   MM_REQUIRE(in_bytes >= 0 && out_bytes && n_blocks && (in_bytes == 0 || (in && out)), MM_ERR_ARG, "mm_bgzf_deflate: null pointer or negative size");
@@ -125,7 +141,7 @@ void bgzf_deflate(mm_ctx* ctx, const uint8_t* in, int64_t in_bytes, uint8_t* out
   };
   const char* const he = getenv("MM_DEFLATE_HOST");
   const bool host = he && *he && strcmp(he, "0") != 0;
-  const int64_t CHUNK = 4096;                                    // blocks per launch (255 MiB of input)
+  const int64_t CHUNK = mmd::LAUNCH_BLOCKS;
   std::vector<int32_t> sizes;
   std::vector<int64_t> offs;
   int64_t o = 0;
@@ -144,16 +160,9 @@ void bgzf_deflate(mm_ctx* ctx, const uint8_t* in, int64_t in_bytes, uint8_t* out
       hipStream_t st = ctx->stream;
       uint8_t* const up = (uint8_t*)ctx->pinned_up_at_least((size_t)cbytes);
       par(nthr, [&](size_t t) { const size_t a = (size_t)cbytes * t / nthr, b = (size_t)cbytes * (t + 1) / nthr; if (b > a) memcpy(up + a, cin + a, b - a); });
-      DBuf<uint8_t> d_in((size_t)cbytes + 16), d_slots((size_t)n * mmd::MEMBER_MAX);
+      DBuf<uint8_t> d_in((size_t)cbytes + 16);
       d_in.upload(up, (size_t)cbytes, st);
-      const unsigned grid = (unsigned)std::min<int64_t>(n, (int64_t)std::max(1, ctx->cus) * 2);
-      DBuf<uint32_t> d_tok((size_t)grid * mmd::TOK_CAP);
-      DBuf<int32_t> d_sizes((size_t)n);
-      bgzf_deflate_kernel<<<dim3(grid), dim3(64), 0, st>>>(d_in.p, cbytes, (int32_t)n, d_slots.p, d_tok.p, d_sizes.p);
-      MM_KERNEL_CHECK();
-      d_sizes.download(sizes.data(), (size_t)n, st);
-      d_slots.download(down, (size_t)n * mmd::MEMBER_MAX, st);
-      MM_HIP(mm::stream_sync(st));
+      bgzf_deflate_resident(ctx, d_in.p, cbytes, n, down, sizes.data());
     }
     offs.resize((size_t)n);
     for (int64_t b = 0; b < n; ++b) {

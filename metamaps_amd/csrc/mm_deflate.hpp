@@ -41,6 +41,7 @@ namespace mmd {
 using mmi::Consts;
 constexpr uint32_t BLOCK_IN = 0xff00;                            // input bytes per BGZF block (what bgzip uses)
 constexpr uint32_t MEMBER_MAX = 65536;                           // bytes a member's destination holds (a member is at most BLOCK_IN + 31)
+constexpr int64_t LAUNCH_BLOCKS = 4096;                          // blocks per launch of the kernel (255 MiB of input)
 constexpr uint32_t G = 64;                                       // positions per search step, tokens per emit round
 constexpr uint32_t HASH_BITS = 12, MIN_MATCH = 4, MAX_MATCH = 258, WINDOW = 32768;
 constexpr uint32_t STAGE_WORDS = 1024, STAGE_MARGIN = 112;       // the output window; a round adds at most 64 * 48 bits = 96 words

@@ -4,6 +4,11 @@ process), and csrc/mm_edit_core.hpp's edit_infix_host on one host thread over a 
 tools/_tmp/), which also holds the device's answers against the host's.
 Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes profiles/edit_kernel_stats.txt)
        python tools/edit_kernel_stats.py --align [n_reads]            (writes profiles/edit_trace_stats.txt)
+       python tools/edit_kernel_stats.py --bam [n_reads]              (writes profiles/bam_encode_stats.txt)
+--bam: the same batch through mm_mapping_align once and then twice through mm_bam_encode (the BAM records of these alignments, encoded and deflated on the
+device: mm_bam_core.hpp, mm_bam.hip): the upload / size / scan / write / deflate stage times (the MM_BAM_TIMING line), the wall time of the call with its
+copies, raw and BGZF bytes, beside the same run's mm_mapping_align time (the MM_EDIT_TIMING line) and the size PREFIX.paf would have.  The members are
+inflated on the host and counted against the raw bytes.  One run is one run.
 --align: the same batch through mm_mapping_align (the alignments behind the distances: mm_edit_trace_core.hpp) in one child process under one timeout: one
 distance-only call as the yardstick, then two aligning calls with their jobs / align / trace stage times, the scratch budget and the launches it led to (the
 MM_EDIT_TIMING line), the runs, and the size PREFIX.paf would have for these mappings (reads named read<i>, contigs contig<c>)."""
@@ -108,7 +113,62 @@ def child_align(n_reads):
     M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
 
 
+def child_bam(n_reads):
+    import io
+    import gzip
+    from metamaps_amd import capi
+    ctx = capi.Context(0)
+    ref = ctx.synth_reference(seed=20260928, n_species=25, strains_per_species=4, genome_len=2_200_000, strain_divergence=0.02, genus_divergence=0.2)
+    w = capi.lib().mm_recommended_window(1e-3, K, PI, 1000, ref.total_bases)
+    idx = ctx.index(ref, K, w)
+    reads, _ = ctx.synth_reads(ref, seed=1000, n_reads=n_reads, read_len=READ_LEN, read_len_min=0, sub_rate=0.04, ins_rate=0.03, del_rate=0.05, frac_random=0.05, n_abundant=100)
+    M = ctx.map_batch(idx, reads, K, w, pi=PI)
+    M.keep_best(K)
+    off, rec = M.fetch()
+    n = len(rec)
+    print(f"{n_reads} reads of {READ_LEN} bases against {ref.total_bases} reference bases (k {K}, w {w}, pi {PI}): {n} best mappings", flush=True)
+    t0 = time.perf_counter()
+    dist, first, last, op_off, ops = ctx.mapping_align(M, reads, ref, PI)
+    dt = time.perf_counter() - t0
+    print(f"mm_mapping_align: {1e3 * dt:.1f} ms wall with the copies to the host; {int((dist >= 0).sum())} of {n} aligned, {len(ops)} runs ({4 * len(ops) / 1e6:.1f} MB)", flush=True)
+    rl, cl = reads.lengths()[rec["read"]].astype(np.int64), ref.lengths()[rec["ref_contig"]].astype(np.int64)
+    total, cg = paf_bytes(dist, first, last, op_off, ops, rec["read"].astype(np.int64), rl, rec["ref_contig"].astype(np.int64), cl)
+    print(f"PREFIX.paf of these mappings: {total / 1e6:.1f} MB, {cg / 1e6:.1f} MB of it CIGAR text (its formatting on the host is not timed here)", flush=True)
+    strand = rec["strand"].astype(np.int32)
+    names = [b"read%d" % r for r in rec["read"]]
+    args = dict(read=rec["read"], strand=strand, contig=rec["ref_contig"], dist=dist, first=first, op_off=op_off, ops=ops, flag=np.where(strand < 0, 0x10, 0), mapq=np.full(n, 60), names=names)
+    for rep in range(2):
+        t0 = time.perf_counter()
+        data, n_rec, raw = ctx.bam_encode(reads, ref, **args)
+        dt = time.perf_counter() - t0
+        print(f"mm_bam_encode call {rep}: {1e3 * dt:.1f} ms wall with the copies (the Python wrapper's own included), {n_rec} records, {raw / 1e6:.1f} MB raw, {len(data) / 1e6:.1f} MB BGZF "
+              f"({raw / max(n_rec, 1):.0f} B per record raw)", flush=True)
+    got = 0
+    with gzip.GzipFile(fileobj=io.BytesIO(data)) as z:
+        while True:
+            piece = z.read(1 << 26)
+            if not piece:
+                break
+            got += len(piece)
+    assert got == raw and n_rec == int((dist >= 0).sum()), (got, raw, n_rec)
+    print(f"the members inflate to {got} bytes on the host: the raw bytes", flush=True)
+    M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--child-bam":
+        return child_bam(int(sys.argv[2]))
+    if len(sys.argv) > 1 and sys.argv[1] == "--bam":
+        n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-bam", str(n_reads)], env=dict(os.environ, MM_EDIT_TIMING="1", MM_BAM_TIMING="1"),
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1100)
+        text = f"tools/edit_kernel_stats.py --bam {n_reads}: one batch of {n_reads} reads, best mappings only; one run\n" + p.stdout.decode()
+        print(text)
+        if p.returncode != 0:
+            sys.exit(p.returncode)
+        with open(os.path.join(ROOT, "profiles", "bam_encode_stats.txt"), "w") as f:
+            f.write(text)
+        return None
     if len(sys.argv) > 1 and sys.argv[1] == "--child":
         return child(int(sys.argv[2]), int(sys.argv[3]))
     if len(sys.argv) > 1 and sys.argv[1] == "--child-align":
