@@ -1,5 +1,6 @@
 // Unaligned (or aligned) BAM as a query file for the `metamaps` host program: the BGZF block walk (also of bgzip-compressed FASTA/FASTQ),
-// parallel raw inflate of the blocks (or a caller's segment inflater: the CLI's inflates on the device) and the record parse.  Host only, no device dependencies: tests/test_bam_reader.cpp checks it on the CPU against a BAM writer in Python.
+// parallel raw inflate of the blocks (or a caller's segment inflater: the CLI's inflates on the device) and the record parse.  Host only, no device
+// dependencies: tests/test_bam_reader.cpp checks it on the CPU against a BAM writer in Python.
 //
 // What a record becomes is what `samtools fastq -n` writes for it: secondary (0x100) and supplementary (0x800) records are skipped, a record
 // with 0x10 is the reverse complement of the read as sequenced (the complement of a 4-bit code is its bit reversal: A<->T, C<->G, M<->K, R<->Y,

@@ -21,7 +21,11 @@ namespace {
 // A mapping line as `classify` sees it once it has tokenised the file (fEM.h:234-275): where the line lies in the text, and the values of the fields it reads
 // — identity and mapping quality as the PRINTED text parses, not as the floats they were printed from.  `mapDirectly --then-classify` keeps these beside the
 // text it writes, so that classify in the same process neither reads the file back nor tokenises it.
-struct LineMeta { uint32_t beg, ls /* the blank before field 14, relative to beg */, n /* length without the newline */; int32_t contig /* index into the reference's contigs */, len, start, stop /* field 9: start + len - 1, or its raw translation with --hpc */; double ident, mapq; };
+struct LineMeta {
+  uint32_t beg, ls /* the blank before field 14, relative to beg */, n /* length without the newline */;
+  int32_t contig /* index into the reference's contigs */, len, start, stop /* field 9: start + len - 1, or its raw translation with --hpc */;
+  double ident, mapq;
+};
 enum class EmReduce { None, Rccl, Host };
 struct KeptLines {                                               // the mapping lines of one output prefix as mapDirectly wrote them, batch after batch, with their parsed fields
   struct Part { const char* text; const LineMeta* meta; size_t n_lines; const int64_t* off; size_t n_reads; };
@@ -308,7 +312,10 @@ struct ClassifyRun {
       off.clear();
       for (size_t t = 0; t < NTH; ++t) for (int64_t st0 : pieces[t].starts) off.push_back(st0 + (int64_t)line0[t]);
       if (off.empty()) off.push_back(0);
-      auto place = [&](size_t t) { MapLine* o = lines.data() + line0[t]; const auto& src = pieces[t].lines; for (size_t i = 0; i < src.size(); ++i) { o[i] = src[i]; o[i].contig = remap[t][(size_t)src[i].contig]; } };
+      auto place = [&](size_t t) {
+        MapLine* o = lines.data() + line0[t]; const auto& src = pieces[t].lines;
+        for (size_t i = 0; i < src.size(); ++i) { o[i] = src[i]; o[i].contig = remap[t][(size_t)src[i].contig]; }
+      };
       { std::vector<std::thread> pool; for (size_t t = 1; t < NTH; ++t) pool.emplace_back(place, t); place(0); for (auto& th : pool) th.join(); }
       if (!lines.empty()) off.push_back((int64_t)lines.size());
     }
@@ -319,11 +326,18 @@ struct ClassifyRun {
     contig_taxon_id.assign(contig_id.size(), std::string());
     for (size_t c = 0; c < contig_id.size(); ++c) { contig_taxon_id[c] = extract_taxon(contig_id[c]); taxaSet.insert(contig_taxon_id[c]); }
     if (taxaSet.empty()) die("No relevant taxon IDs found in your mappings file - is it possible that none of your reads are mapped?");
-    { std::ifstream s(mapped + ".meta"); if (!s.is_open()) die("The file " + mapped + ".meta is not present or could not be opened - this file is generated automatically as part of the mapping process, so please check whether the mapping process finished successfully.");
+    { std::ifstream s(mapped + ".meta");
+      if (!s.is_open()) die("The file " + mapped + ".meta is not present or could not be opened - this file is generated automatically as part of the "
+                            "mapping process, so please check whether the mapping process finished successfully.");
       std::string a; size_t b; while (s >> a >> b) st[a] = b; }
     nUnmapped = st.at("ReadsNotMapped"); nTooShort = st.at("ReadsTooShort"); nTotal = st.at("TotalReads");
     { std::ifstream s(db + "/taxonInfo.txt"); if (!s.is_open()) die("Could not open file " + db + "/taxonInfo.txt -- perhaps you have specified an incomplete DB?");
-      std::string ln; while (std::getline(s, ln)) { if (ln.empty()) continue; auto f = split(ln, " "); for (auto& c : split(f.at(1), ";")) { auto kv = split(c, "="); TI[f.at(0)][kv.at(0)] = std::stoull(kv.at(1)); } } }
+      std::string ln;
+      while (std::getline(s, ln)) {
+        if (ln.empty()) continue;
+        auto f = split(ln, " ");
+        for (auto& c : split(f.at(1), ";")) { auto kv = split(c, "="); TI[f.at(0)][kv.at(0)] = std::stoull(kv.at(1)); }
+      } }
   }
   void per_mapping_fields() {
     taxa.assign(taxaSet.begin(), taxaSet.end());
@@ -751,7 +765,8 @@ struct ClassifyRun {
 };
 
 int classify_one(const std::vector<Dev>& devs, EmReduce reduce, const std::string& mapped, const std::string& db, size_t minReadsU,
-                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept, BootOpts boot, LcaOpts lca, GeneOpts genes, IdentOpts identf_opts, const CliSwitches& sw) {
+                 const std::function<void()>& leave_now, const std::function<void()>& need_devices, const KeptLines* kept, BootOpts boot, LcaOpts lca,
+                 GeneOpts genes, IdentOpts identf_opts, const CliSwitches& sw) {
   ClassifyRun run(devs, reduce, mapped, db, minReadsU, leave_now, need_devices, sw);
   run.kept = kept;
   run.boot = boot;

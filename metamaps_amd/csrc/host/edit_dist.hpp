@@ -2,8 +2,9 @@
 //   readID contigID strand d first last        (strand + / -; first, last: 0-based inclusive contig coordinates; "NA NA NA": not aligned)
 // d, first and last come from the device (mm_mapping_edit_distances: Myers' bit-vector alignment of every record inside the window around its
 // mapped position, within floor(1.5 L (100 - pi) / 100) edits).  The context that mapped a batch aligns it, against its device's packed reference,
-// before the batch's reads and mapping are destroyed.
+// before the batch's reads and mapping are destroyed (map_outputs.hpp).  Text only: nothing here calls the device.
 #pragma once
+#include "../../../include/metamaps_hip.h"
 #include "cli_common.hpp"
 #include "fast_format.hpp"
 
@@ -21,14 +22,6 @@ void edit_distance_text(const int32_t* dist, const int64_t* first, const int64_t
       if (dist[(size_t)i] < 0) { out += " NA NA NA\n"; continue; }
       out += ' '; append_int(out, dist[(size_t)i]); out += ' '; append_int(out, (long long)first[(size_t)i]); out += ' '; append_int(out, (long long)last[(size_t)i]); out += '\n';
     }
-}
-// ... aligned here; consumes nothing
-void edit_distance_lines(mm_ctx* ctx, const mm_mapping* m, const mm_seqset* reads, const mm_seqset* reference, float pi, const std::vector<std::string>& names,
-                         const std::vector<int64_t>& off, const std::vector<mm_map_record>& rec, const std::vector<std::string>& cname, std::string& out) {
-  std::vector<int32_t> dist(rec.size());
-  std::vector<int64_t> first(rec.size()), last(rec.size());
-  ck(ctx, mm_mapping_edit_distances(ctx, m, reads, reference, pi, dist.data(), first.data(), last.data(), (int64_t)rec.size()), "edit distances");
-  edit_distance_text(dist.data(), first.data(), last.data(), names, off, rec, cname, out);
 }
 
 }  // namespace

@@ -1,16 +1,15 @@
-// One run of mapDirectly / index / mapAgainstIndex (MapRun), and what only it uses: the formatter of the mapping lines.
+// One run of mapDirectly / index / mapAgainstIndex (MapRun).  What it stands on: the reference loader (ref_loader.hpp), the formatter of the
+// mapping lines (map_format.hpp) and a batch's side outputs (map_outputs.hpp, the files of side_files.hpp).
 #pragma once
-#include "../cpu_budget.hpp"
-#include "../task_pool.hpp"
 #include "classify_run.hpp"
 #include "cli_device.hpp"
 #include "cli_switches.hpp"
-#include "edit_dist.hpp"
-#include "paf_out.hpp"
-#include "bam_out.hpp"
-#include "fast_format.hpp"
 #include "id_set.hpp"
+#include "index_files.hpp"
+#include "map_format.hpp"
+#include "map_outputs.hpp"
 #include "query_reader.hpp"
+#include "ref_loader.hpp"
 #include <climits>
 #include <cmath>
 #include <fstream>
@@ -38,102 +37,6 @@ namespace {
 //   streamed     (--stream-chunks, or automatic when not even that fits) rounds of N chunks, one per device, built, mapped
 //                against every (device-resident) read batch and dropped.
 
-// records of one batch -> the text of PREFIX (computeMap.hpp:565-581 + the two fields of mapWrap.h:311-320), reads in order
-// fields 10 and 13 of a mapping line are functions of (conserved sketches, sketch size) alone: formatted once per pair and kept.  The table belongs
-// to the CALLER (one per formatting slot of a worker thread) and lives as long as that thread: the pool threads of format_records are new with every
-// batch, and a table that was theirs (thread_local) was rebuilt — 0.8 MB cleared, every pair formatted again — by every one of them for every batch:
-// 19 ms per batch of 85 000 lines, the whole of a worker's "finish" time.
-struct FormatCache {
-  struct Pair { uint64_t key; char ids[16], corr[16]; uint8_t n_ids, n_corr; double ident; };   // ident: the printed identity read back / 100 (what classify parses, fEM.h:264)
-  static constexpr size_t CB = 1 << 14;
-  std::vector<Pair> slots; int k = -1;
-  void prepare(int k_now) { if (slots.size() != CB || k != k_now) { slots.assign(CB, Pair{~0ull, {0}, {0}, 0, 0, 0.0}); k = k_now; } }
-};
-static void format_range(const std::vector<std::string>& names, const std::vector<int>& lens, const std::vector<int64_t>& off,
-                         const std::vector<mm_map_record>& rec, const std::vector<std::string>& cname, const std::vector<int>& clen, int k, size_t r0, size_t r1, std::string& out,
-                         FormatCache& fc, std::vector<LineMeta>* meta, const int64_t* raw_end /* --hpc: field 9 of every record; else nullptr */) {
-  out.clear();
-  if (meta) { meta->clear(); meta->reserve((size_t)(off[r1] - off[r0])); }
-  out.reserve((size_t)(off[r1] - off[r0]) * 160);
-  // no printf anywhere on the line (fast_format.hpp) — 4.2 M lines took 2 s of the mapping phase of a million reads
-  using Pair = FormatCache::Pair;
-  fc.prepare(k);
-  std::vector<Pair>& cache = fc.slots;
-  std::string tmp;
-  for (size_t r = r0; r < r1; ++r) {
-    const int len = lens[r];
-    for (int64_t i = off[r]; i < off[r + 1]; ++i) {
-      const mm_map_record& x = rec[(size_t)i];
-      const uint64_t key = (uint64_t)(uint32_t)x.sketch << 32 | (uint32_t)x.shared;
-      Pair& P = cache[(size_t)((key * 0x9E3779B97F4A7C15ull) >> 50)];
-      if (P.key != key) {
-        float id; mm_identity(x.shared, x.sketch, k, &id, nullptr);
-        tmp.clear(); append_g6(tmp, (double)id);                   // operator<<(float): %g with 6 significant digits; printed, then re-parsed (mapWrap.h:237)
-        P.n_ids = (uint8_t)tmp.size(); memcpy(P.ids, tmp.data(), tmp.size());
-        const double reported = strtod(tmp.c_str(), nullptr) / 100.0;
-        P.ident = reported;
-        const float corrected = std::exp(-(1 - reported));        // mapWrap.h:311
-        tmp.clear(); append_g6(tmp, (double)(corrected * 100));
-        P.n_corr = (uint8_t)tmp.size(); memcpy(P.corr, tmp.data(), tmp.size());
-        P.key = key;
-      }
-      const size_t line_beg = out.size();
-      out += names[r];
-      out += ' '; append_int(out, len); out += " 0 "; append_int(out, len - 1); out += ' '; out += x.strand == 1 ? '+' : '-'; out += ' ';
-      out += cname[(size_t)x.ref_contig];
-      out += ' '; append_int(out, clen[(size_t)x.ref_contig]);
-      out += ' '; append_int(out, x.ref_start); out += ' '; append_int(out, raw_end ? (long long)raw_end[(size_t)i] : (long long)x.ref_start + len - 1);
-      out += ' '; out.append(P.ids, P.n_ids);
-      out += ' '; append_int(out, x.shared); out += ' '; append_int(out, x.sketch);
-      out += ' '; out.append(P.corr, P.n_corr);
-      const size_t ls = out.size();
-      out += ' '; append_g6(out, x.mapq);                          // :318-320
-      if (meta) meta->push_back(LineMeta{(uint32_t)line_beg, (uint32_t)(ls - line_beg), (uint32_t)(out.size() - line_beg), (int32_t)x.ref_contig, (int32_t)len, (int32_t)x.ref_start, (int32_t)(raw_end ? raw_end[(size_t)i] : (int64_t)x.ref_start + len - 1),
-                                         P.ident, mapq_as_classify_reads_it(out.data() + ls + 1, out.size() - ls - 1)});
-      out += '\n';
-    }
-  }
-}
-// the mapping lines of a batch (mapWrap.h:300-323): ranges of reads formatted by a few threads, joined in read order
-void format_records(const std::vector<std::string>& names, const std::vector<int>& lens, const std::vector<int64_t>& off,
-                    const std::vector<mm_map_record>& rec, const std::vector<std::string>& cname, const std::vector<int>& clen, int k, std::string& out, std::vector<LineMeta>* meta,
-                    const int64_t* raw_end, const CliSwitches& sw) {
-  const size_t n = names.size();
-  const size_t per_part = sw.format_part;
-  const size_t T = std::max<size_t>(1, std::min<size_t>({(size_t)8, (size_t)std::max(per_part < 10000 ? 8u : 1u, mm::cpu_budget() / 4), rec.size() / per_part + 1}));   // (a quarter of the CPU budget per worker: four workers rarely format at the same moment)
-  static thread_local std::vector<FormatCache> caches(8);          // (the calling thread's: a worker of mapDirectly formats batch after batch)
-  if (T == 1) { format_range(names, lens, off, rec, cname, clen, k, 0, n, out, caches[0], meta, raw_end); return; }
-  std::vector<size_t> cut(T + 1, n);
-  cut[0] = 0;
-  { size_t t = 1; for (size_t r = 0; r < n && t < T; ++r) if ((uint64_t)off[r] >= (uint64_t)rec.size() * t / T) cut[t++] = r; }
-  static thread_local std::vector<std::string> part_store(8);      // (kept with their capacity: fresh text buffers are page faults, batch after batch)
-  std::vector<std::string>& part = part_store;
-  FormatCache* const fcs = caches.data();
-  static thread_local std::vector<std::vector<LineMeta>> meta_store(8);
-  std::vector<std::vector<LineMeta>>& metas = meta_store;        // (the CALLING thread's: the helpers below must not name the thread_local themselves)
-  const auto q0 = std::chrono::steady_clock::now();
-  std::vector<double> took(T, 0.0);
-  auto timed = [&](size_t t) { const auto a = std::chrono::steady_clock::now(); format_range(names, lens, off, rec, cname, clen, k, cut[t], cut[t + 1], part[t], fcs[t], meta ? &metas[t] : nullptr, raw_end);
-                               took[t] = std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); };
-  static thread_local TaskPool helpers(7);                         // (task_pool.hpp: the calling worker's own helpers, there from batch to batch)
-  const auto q1 = q0;
-  helpers.run(T, timed);
-  const auto q2 = std::chrono::steady_clock::now();
-  size_t total = 0; for (size_t t = 0; t < T; ++t) total += part[t].size();
-  out.clear(); out.reserve(total);
-  if (meta) { meta->clear(); meta->reserve(rec.size()); }
-  for (size_t t = 0; t < T; ++t) {
-    if (meta) for (LineMeta lm : metas[t]) { lm.beg += (uint32_t)out.size(); meta->push_back(lm); }
-    out += part[t];
-  }
-  if (sw.format_trace) {
-    const auto q3 = std::chrono::steady_clock::now();
-    double mx = 0; for (double x : took) mx = std::max(mx, x);
-    fprintf(stderr, "FORMAT_TRACE %zu records, %zu threads: all parts %.2f ms (own part %.2f ms, slowest part %.2f ms), join text %.2f ms\n", rec.size(), T,
-            std::chrono::duration<double, std::milli>(q2 - q1).count(), took[0] * 1e3, mx * 1e3, std::chrono::duration<double, std::milli>(q3 - q2).count());
-  }
-}
-
 // One run of mapDirectly / index / mapAgainstIndex.  The state every stage shares lives in the object; the stages are its methods, in the order run()
 // calls them: parameters -> devices -> reference (parsed, packed, uploaded) or stored index -> chunk plan -> placement of the chunk indexes
 // (replicated / sharded / streamed) -> read batches through the worker pipeline (replicated) or chunk-major rounds with the exchange of the
@@ -150,12 +53,13 @@ struct MapRun {
   // --hpc: the sequences are homopolymer-compressed on the device (mm_seqset_hpc) and everything from the chunk plan to the mapping qualities sees the
   // compressed ones: clen holds the compressed contig lengths, clen_raw what is printed; hpc_map[d] translates the records' coordinates on device d
   const bool hpc = o.v.count("hpc") != 0;
-  const bool edit = o.v.count("edit-distance") != 0;             // --edit-distance: the packed reference stays on every device, a batch's reads live until its distances are fetched (edit_dist.hpp)
-  const bool paf = o.v.count("paf") != 0;                        // --paf (implies --edit-distance): the same call also gives the CIGARs of PREFIX.paf (paf_out.hpp)
-  const bool bam = o.v.count("bam") != 0;                        // --bam (implies --edit-distance): that alignment also becomes the records of PREFIX.bam, encoded and deflated on the device (bam_out.hpp)
-  std::string bam_head;                                          // the header of every PREFIX.bam as BGZF members (the contigs are the run's)
+  // --edit-distance, --paf, --bam (the last two imply the first): the side files of the run (side_files.hpp).  With any of them the packed reference
+  // stays on every device and a batch's reads live until its alignment is fetched, under --bam until its records are encoded (map_outputs.hpp)
+  const SideSet side = side_files_of(o);
+  const bool edit = side[SIDE_EDIT];
+  std::string bgzf_head;                                         // what a BGZF side file starts with: the header of every PREFIX.bam as BGZF members (the contigs are the run's)
   std::vector<int> clen_raw; std::vector<mm_hpc_map*> hpc_map;
-  struct Chunk { int first, count; std::string file; };
+  using Chunk = IndexChunk;                                      // (index_files.hpp)
   std::vector<Chunk> chunks;
   // The packed reference (2 bits per base + exception runs, a quarter of the FASTA's size) lives on every device that builds indexes
   // from it; the host holds contig names and lengths only.  Index chunks are cut out of it on the device (mm_seqset_slice).
@@ -173,8 +77,20 @@ struct MapRun {
   mm_map_params mp{};
   std::vector<int32_t> chunk_base;
   // what a worker hands to the writer: the finished text of one batch
-  struct Done { size_t file = 0; std::vector<std::string> names; std::vector<int> lens; std::vector<int> clens /* --hpc: the compressed lengths (lens stay raw) */; std::vector<int64_t> off; std::string text; std::string gz /* --compress-output: the text as BGZF members */; std::string edit /* --edit-distance: the batch's lines of PREFIX.editDistances */; std::string paf /* --paf: the batch's lines of PREFIX.paf */; std::string bam /* --bam: the batch's records of PREFIX.bam as BGZF members */; std::vector<LineMeta> meta; double t_mapq = 0, t_fetch = 0, t_format = 0; };
-  // --then-classify: the batches of every query file as they were written, in order (text + the parsed fields of every line): what classify takes instead of the file
+  struct Done {
+    size_t file = 0;
+    std::vector<std::string> names;
+    std::vector<int> lens;
+    std::vector<int> clens;                                        // --hpc: the compressed lengths (lens stay raw)
+    std::vector<int64_t> off;
+    std::string text;
+    std::string gz;                                                // --compress-output: the text as BGZF members
+    SideBytes side;                                                // what the batch adds to every side file (side_files.hpp): lines, or BGZF members
+    std::vector<LineMeta> meta;
+    double t_mapq = 0, t_fetch = 0, t_format = 0;
+  };
+  // --then-classify: the batches of every query file as they were written, in order (text + the parsed fields of every line): what classify takes
+  // instead of the file
   const bool keep_lines = o.v.count("then-classify") && !sw.classify_from_file;
   // --compress-output: the mappings go to PREFIX.gz as BGZF; a batch's text is deflated by the context that mapped it, right behind its formatting
   const bool compress = o.v.count("compress-output") != 0;
@@ -212,14 +128,8 @@ struct MapRun {
         pval = mm_estimate_pvalue(minLen * 2 / w, k, pi, minLen, refSize);
       } else w = mm_recommended_window(pval, k, pi, minLen, refSize);
     } else {                                                       // the parameters travel with the index (mapWrap.h:447-461)
-      std::ifstream a(ipre + ".arguments");
-      if (!a.is_open()) die("Cannot open file " + ipre + ".arguments for deserialization.");
-      std::string key, val; std::map<std::string, std::string> kv;
-      while (a >> key && std::getline(a, val)) { while (!val.empty() && val[0] == ' ') val.erase(0, 1); kv[key] = val; }
-      for (const char* need : {"kmerSize", "windowSize", "minReadLength", "percentageIdentity", "p_value", "referenceSize", "maximumMemory", "reference"})
-        if (!kv.count(need)) die("Index " + ipre + " is incomplete (" + need + " missing in .arguments)");
-      k = std::stoi(kv["kmerSize"]); w = std::stoi(kv["windowSize"]); minLen = std::stoi(kv["minReadLength"]); pi = std::stof(kv["percentageIdentity"]);
-      pval = std::stod(kv["p_value"]); refSize = std::stoull(kv["referenceSize"]); maxMem = std::stoull(kv["maximumMemory"]); ref = kv["reference"];
+      const IndexArguments a = read_index_arguments(ipre);
+      k = a.k; w = a.w; minLen = a.minLen; pi = a.pi; pval = a.pval; refSize = a.refSize; maxMem = a.maxMem; ref = a.ref;
     }
     if (!only_index) {
       queries = split(o.v.at("query"), ","); prefixes = split(o.v.at("output"), ",");
@@ -299,141 +209,14 @@ struct MapRun {
 
   // ---- reference (winSketch.hpp:180-365): parsed, packed and uploaded to every device that builds indexes from it
   void load_reference() {
-    struct Group { std::deque<std::string> seq; std::vector<std::string> names; uint64_t bases = 0; };
-    const uint64_t GROUP_BASES = sw.ref_group_bases;
-    std::vector<std::vector<mm_seqset*>> parts(only_index ? 1 : G);
-    double t_pack = 0;
-    auto consume = [&](Group& g) {                               // names and lengths in file order, then pack + upload to every device
-      for (size_t i = 0; i < g.seq.size(); ++i) { cname.push_back(std::move(g.names[i])); clen.push_back((int)g.seq[i].size()); ref_bases += g.seq[i].size(); }
-      const auto t0 = std::chrono::steady_clock::now();
-      on_each(parts.size(), [&](size_t d) {
-        mm_seqset* p; ck(devs[d].ctx, mm_seqset_create(devs[d].ctx, &p), "seqset");
-        for (auto& q : g.seq) ck(devs[d].ctx, mm_seqset_add_view(p, q.data(), (int64_t)q.size()), "add contig");
-        ck(devs[d].ctx, mm_seqset_upload(p), "upload reference");
-        parts[d].push_back(p);
-      });
-      t_pack += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    };
-    // records of `f` (all, or those that start before `stop` in memory mode) in groups of GROUP_BASES handed to `emit`; false when the
-    // reader gave up before `stop` (a truncated quality string ends the file for kseq, kseq.h:204)
-    auto parse_groups = [&](SeqFile& f, size_t stop, const std::function<void(std::unique_ptr<Group>)>& emit) -> bool {
-      auto g = std::make_unique<Group>();
-      bool ok = true;
-      for (;;) {
-        if (stop != (size_t)-1) { const size_t ps = f.peek_start(); if (ps == (size_t)-1 || ps >= stop) break; }
-        if (!f.next()) { ok = stop == (size_t)-1; break; }
-        g->names.push_back(f.name);
-        if (f.view) g->seq.emplace_back(f.view, f.view_len); else { g->seq.push_back(std::move(f.seq)); f.seq.clear(); }
-        g->bases += g->seq.back().size();
-        if (g->bases >= GROUP_BASES) { emit(std::move(g)); g = std::make_unique<Group>(); }
-      }
-      if (!g->seq.empty()) emit(std::move(g));
-      return ok;
-    };
-    MappedFile rmf;
-    if (!sw.no_mmap && !sw.ref_sequential && rmf.open(ref)) {
-      // A plain file: blocks of the mapping parsed by several threads (the block parser of the query files below: a block's records
-      // count only once the block before it has been seen to end exactly where this one starts), consumed — packed, uploaded — in file
-      // order.  The winSketch.hpp:242-252 loop reads contig by contig; here the text of at most P + 2 blocks of 256 MB is resident, and the
-      // mapped pages of a block are given back once it is consumed (they would count as resident until the end otherwise: 27 GB).
-      const size_t blk = sw.ref_block_bytes;
-      const size_t nb = std::max<size_t>(1, (rmf.size + blk - 1) / blk);
-      std::vector<size_t> start(nb + 1, rmf.size);
-      start[0] = 0;
-      struct Block { std::vector<std::unique_ptr<Group>> out; size_t next = 0; bool done = false, empty = false, over = false; };
-      std::vector<Block> blocks(nb);
-      std::mutex bm; std::condition_variable bcv; size_t next_block = 0, consumed = 0; bool abandon = false;
-      const unsigned P = (unsigned)std::max<size_t>(1, std::min<size_t>({nb, (size_t)8, (size_t)std::max(1u, mm::cpu_budget() / 2)}));
-      auto worker = [&]() {
-        for (;;) {
-          size_t j;
-          {
-            std::unique_lock<std::mutex> lk(bm);
-            bcv.wait(lk, [&] { return abandon || next_block >= nb || next_block < consumed + P + 1; });   // not too far ahead of the consumer
-            if (abandon || next_block >= nb) return;
-            j = next_block++;
-          }
-          if (j > 0) start[j] = rmf.sync(j * blk, std::min(rmf.size, (j + 1) * blk));
-          Block& B = blocks[j];
-          const size_t lim = std::min(rmf.size, (j + 1) * blk);
-          if (j == 0 || start[j] < lim) {
-            SeqFile f(rmf.data, j == 0 ? 0 : start[j], rmf.size);
-            B.over = !parse_groups(f, lim, [&](std::unique_ptr<Group> g) { B.out.push_back(std::move(g)); });
-            B.next = f.peek_start();
-          } else B.empty = true;
-          { std::lock_guard<std::mutex> lk(bm); B.done = true; }
-          bcv.notify_all();
-        }
-      };
-      std::vector<std::thread> pool;
-      for (unsigned t = 0; t < P; ++t) pool.emplace_back(worker);
-      size_t expect = 0; bool chain_ok = true, file_over = false;
-      for (size_t j = 0; j < nb && chain_ok && !file_over; ++j) {
-        { std::unique_lock<std::mutex> lk(bm); bcv.wait(lk, [&] { return blocks[j].done; }); }
-        Block& B = blocks[j];
-        if (!B.empty) {
-          if (j > 0 && start[j] != expect) { chain_ok = false; break; }
-          for (auto& g : B.out) consume(*g);
-          B.out.clear();
-          if (B.over || B.next == (size_t)-1) { file_over = true; break; }
-          expect = B.next;
-        } else if (expect < std::min(rmf.size, (j + 1) * blk)) { chain_ok = false; break; }
-        { std::lock_guard<std::mutex> lk(bm); consumed = j + 1; } bcv.notify_all();
-        if (j > 0) rmf.drop(((j - 1) * blk) & ~(size_t)4095, (j * blk) & ~(size_t)4095);   // (block j - 1: its last record may end inside block j, parsed by now)
-      }
-      { std::lock_guard<std::mutex> lk(bm); abandon = true; } bcv.notify_all();
-      for (auto& t : pool) t.join();
-      if (!chain_ok) {                                           // a block did not start where the parse stood: the rest sequentially, from there
-        for (auto& B : blocks) B.out.clear();
-        SeqFile f(rmf.data, expect, rmf.size);
-        parse_groups(f, (size_t)-1, [&](std::unique_ptr<Group> g) { consume(*g); });
-      }
-    } else {
-      // gzip, pipes: a parser thread fills groups, the main thread packs and uploads each while the next one is parsed.  Host memory: two groups.
-      std::mutex gm; std::condition_variable gcv; std::deque<std::unique_ptr<Group>> ready; bool parsed = false;
-      double t_gzip = -1;                                        // the device gzip reader's wall time (its phase line), -1 if zlib read the file
-      std::thread parser([&]() {
-        if (!sw.gzip_host_inflate && is_plain_gzip_file(ref)) {   // plain gzip: inflated on the device, on a context of the parser's own
-          const auto g_t0 = std::chrono::steady_clock::now();
-          mm_ctx* gctx = nullptr;
-          if (mm_ctx_create(devs[0].phys, &gctx) != MM_OK) die("cannot create the reference reader's inflate context");
-          {
-            DeviceGzip z(gctx, ref);
-            SeqFile f([&](std::vector<unsigned char>& buf) -> size_t { return z.fill(buf); });
-            parse_groups(f, (size_t)-1, [&](std::unique_ptr<Group> g) {
-              std::unique_lock<std::mutex> lk(gm); gcv.wait(lk, [&] { return ready.size() < 2; }); ready.push_back(std::move(g)); gcv.notify_all();
-            });
-          }
-          mm_ctx_destroy(gctx);
-          std::lock_guard<std::mutex> lk(gm); parsed = true; gcv.notify_all();
-          t_gzip = std::chrono::duration<double>(std::chrono::steady_clock::now() - g_t0).count();
-          return;
-        }
-        SeqFile f(ref);
-        parse_groups(f, (size_t)-1, [&](std::unique_ptr<Group> g) {
-          std::unique_lock<std::mutex> lk(gm); gcv.wait(lk, [&] { return ready.size() < 2; }); ready.push_back(std::move(g)); gcv.notify_all();
-        });
-        std::lock_guard<std::mutex> lk(gm); parsed = true; gcv.notify_all();
-      });
-      for (;;) {
-        std::unique_ptr<Group> g;
-        { std::unique_lock<std::mutex> lk(gm); gcv.wait(lk, [&] { return !ready.empty() || parsed; }); if (ready.empty()) break; g = std::move(ready.front()); ready.pop_front(); gcv.notify_all(); }
-        consume(*g);
-      }
-      parser.join();
-      if (t_gzip >= 0) pc.add("1g reference gzip reader (device inflate + parse, inside 1)", t_gzip);
-    }
-    on_each(parts.size(), [&](size_t d) {
-      if (parts[d].size() == 1) { refset[d] = parts[d][0]; return; }
-      if (parts[d].empty()) { ck(devs[d].ctx, mm_seqset_create(devs[d].ctx, &refset[d]), "seqset"); ck(devs[d].ctx, mm_seqset_upload(refset[d]), "upload reference"); return; }
-      ck(devs[d].ctx, mm_seqset_concat(devs[d].ctx, parts[d].data(), (int)parts[d].size(), &refset[d]), "reference");
-      for (auto* p : parts[d]) mm_seqset_destroy(p);
-    });
+    ReferenceLoader loader(sw, devs, only_index ? 1 : G, pc, cname, clen, ref_bases);
+    loader.load(ref, refset);
     pc.lap("1 reference parse + pack + upload");
-    pc.add("2 reference pack+upload (inside 1)", t_pack);
+    pc.add("2 reference pack+upload (inside 1)", loader.t_pack);
     if (hpc) compress_reference();
     if (!only_index) { if (!sw.late_reader) start_reader(); start_prewarm(); }   // (MM_CLI_LATE_READER: measurement aid — the reader starts when the index is built)
-    query_free();                                                // the packed reference now lives on the device (0.25 B per base, for as long as chunks are cut out of it): what is left is what the indexes get
+    // the packed reference now lives on the device (0.25 B per base, for as long as chunks are cut out of it): what is left is what the indexes get
+    query_free();
   }
 
   // --hpc: the reference of every device compressed where it lies, once, before the chunk plan; the raw packed set goes, the map stays
@@ -513,7 +296,7 @@ struct MapRun {
 
   // `metamaps index`: PREFIX.N.seqset (or .mmidx with --full-index) per chunk + PREFIX.index / .arguments / .contigs (mapWrap.h:358-405)
   int write_index_files() {
-    { std::ofstream flag(ipre + ".index"); if (!flag.is_open()) die("Cannot open " + ipre + ".index"); flag << 0 << "\n"; }   // mapWrap.h:363-366
+    write_index_flag(ipre, 0, {});                               // (index_files.hpp: the text files of a stored index)
     std::vector<std::string> chunk_files;
     const bool full = o.v.count("full-index") != 0;            // the device index itself (mm_index_save) instead of the packed reference it is rebuilt from
     for (size_t c = 0; c < chunks.size(); ++c) {
@@ -537,42 +320,13 @@ struct MapRun {
     }
     if (whole) mm_index_destroy(whole);
     drop_refsets();
-    std::ofstream args(ipre + ".arguments");
-    if (!args.is_open()) die("Cannot open file " + ipre + ".arguments for serialization.");
-    args.precision(17);
-    args << "kmerSize " << k << "\nwindowSize " << w << "\nminReadLength " << minLen << "\npercentageIdentity " << pi << "\np_value " << pval
-         << "\nreferenceSize " << refSize << "\nmaximumMemory " << maxMem << "\nreference " << ref << "\n";
-    std::ofstream cf(ipre + ".contigs");
-    for (size_t c = 0; c < chunks.size(); ++c)
-      for (int i = chunks[c].first; i < chunks[c].first + chunks[c].count; ++i) cf << cname[(size_t)i] << "\t" << clen[(size_t)i] << "\t" << c + 1 << "\n";
-    std::ofstream flag(ipre + ".index");                       // mapWrap.h:395-402
-    flag << 1 << "\n";
-    for (auto& fn : chunk_files) { flag << fn << "\n"; std::cout << "Stored state in file " << fn << "\n"; }
+    IndexArguments a;
+    a.k = k; a.w = w; a.minLen = minLen; a.pi = pi; a.pval = pval; a.refSize = refSize; a.maxMem = maxMem; a.ref = ref;
+    write_index_arguments(ipre, a);
+    write_index_contigs(ipre, chunks, cname, clen);
+    write_index_flag(ipre, 1, chunk_files);
     mm_ctx_destroy(ctx0);
     return 0;
-  }
-
-  // `metamaps mapAgainstIndex`: the chunk list and the contig table of a stored index (mapWrap.h:443-554)
-  void read_index_files() {
-    std::ifstream flag(ipre + ".index");
-    if (!flag.is_open()) die("Index " + ipre + " not found (" + ipre + ".index)");
-    int done = 0; flag >> done;
-    if (done != 1) die("Index " + ipre + " is not complete.");    // mapWrap.h:466-470
-    std::vector<std::string> chunk_files; std::string fn;
-    while (flag >> fn) chunk_files.push_back(fn);
-    std::ifstream cf(ipre + ".contigs");
-    if (!cf.is_open()) die("Cannot open " + ipre + ".contigs");
-    std::vector<int> chunk_of; std::string line;
-    while (std::getline(cf, line)) {
-      auto fl = split(line, "\t");
-      if (fl.size() != 3) die("Weird line in " + ipre + ".contigs");
-      cname.push_back(fl[0]); clen.push_back(std::stoi(fl[1])); chunk_of.push_back(std::stoi(fl[2])); ref_bases += (uint64_t)clen.back();
-    }
-    for (size_t c = 0; c < chunk_files.size(); ++c) {
-      int first = -1, count = 0;
-      for (size_t i = 0; i < chunk_of.size(); ++i) if (chunk_of[i] == (int)c + 1) { if (first < 0) first = (int)i; ++count; }
-      chunks.push_back(Chunk{first < 0 ? 0 : first, count, chunk_files[c]});
-    }
   }
 
   // ---- where the chunk indexes live
@@ -598,7 +352,9 @@ struct MapRun {
                 << (place == Place::Sharded ? "the chunk indexes are spread over the devices" : "chunk indexes are built and mapped one after the other") << "\n";
     }
     if (place != Place::Replicated && NC == 1 && !from_index && !maxMem) die("--stream-chunks / --shard-index need --maxmemory (the chunk rule of the reference, winSketch.hpp:274-329)");
-    if (edit && place != Place::Replicated) die(std::string(bam ? "--bam" : paf ? "--paf" : "--edit-distance") + " needs the whole reference resident on every device, and this index does not fit one: run without it");
+    if (edit && place != Place::Replicated)
+      die(std::string(side[SIDE_BAM] ? "--bam" : side[SIDE_PAF] ? "--paf" : "--edit-distance")
+          + " needs the whole reference resident on every device, and this index does not fit one: run without it");
     for (auto& d : devs) d.idx.assign(NC, nullptr);
     thr_of.assign(NC, INT_MAX);
   }
@@ -678,7 +434,9 @@ struct MapRun {
     if (!o.all) ck(ctx, mm_mapping_keep_best(ctx, pm, k), "best mappings");
     return pm;
   }
-  std::unique_ptr<Done> finish_mapping(mm_ctx* ctx, size_t dev, mm_mapping* m, std::vector<std::string>&& names, std::vector<int>&& lens, std::vector<int>&& clens, size_t file, mm_seqset* reads = nullptr) {   // mapping qualities + text; consumes m (and the reads that --edit-distance has kept)
+  // mapping qualities + text + side outputs; consumes m (and the reads that the side outputs have kept: none in the sharded and streamed modes)
+  std::unique_ptr<Done> finish_mapping(mm_ctx* ctx, size_t dev, mm_mapping* m, std::vector<std::string>&& names, std::vector<int>&& lens,
+                                       std::vector<int>&& clens, size_t file, ReadsPtr reads = nullptr) {
     auto dn = std::make_unique<Done>();
     dn->file = file; dn->names = std::move(names); dn->lens = std::move(lens); dn->clens = std::move(clens);
     const auto f0 = std::chrono::steady_clock::now();
@@ -693,37 +451,33 @@ struct MapRun {
     const auto f1 = std::chrono::steady_clock::now();
     std::vector<mm_map_record> rec((size_t)dn->off.back());
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), rec.data(), (int64_t)rec.size()), "fetch");
-    BatchAlignment al;                                             // one fetch serves .editDistances, .paf and .bam
-    if (reads && (paf || bam)) {
-      fetch_alignment(ctx, m, reads, refset[dev], pi, rec.size(), al);
-      edit_distance_text(al.dist.data(), al.first.data(), al.last.data(), dn->names, dn->off, rec, cname, dn->edit);
-      if (paf) paf_text(al, dn->names, dn->lens, dn->off, rec, cname, clen, dn->paf);
-    } else if (reads) edit_distance_lines(ctx, m, reads, refset[dev], pi, dn->names, dn->off, rec, cname, dn->edit);
-    if (reads && !bam) { mm_seqset_destroy(reads); reads = nullptr; }
+    BatchSideOutputs so{side, {}};                                 // one alignment fetch serves .editDistances, .paf and .bam
+    so.from_mapping(ctx, m, reads, refset[dev], pi, rec, dn->names, dn->lens, dn->off, cname, clen, dn->side);
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
-    format_records(dn->names, dn->lens, dn->off, rec, cname, hpc ? clen_raw : clen, k, dn->text, keep_lines ? &dn->meta : nullptr, hpc ? raw_end.data() : nullptr, sw);
-    if (reads) { bam_members(ctx, reads, refset[dev], al, rec, dn->names, dn->off, dn->text, dn->bam); mm_seqset_destroy(reads); }   // --bam: the mapping qualities come from the formatted lines; the reads have stayed for SEQ
+    format_records(dn->names, dn->lens, dn->off, rec, cname, hpc ? clen_raw : clen, k, dn->text, keep_lines ? &dn->meta : nullptr,
+                   hpc ? raw_end.data() : nullptr, sw);
+    so.from_text(ctx, reads, refset[dev], rec, dn->names, dn->off, dn->text, dn->side);   // --bam: the mapping qualities come from the formatted lines
     if (compress) deflate_text(ctx, *dn);
     const auto f3 = std::chrono::steady_clock::now();
     pc.add("7a mapping qualities + offsets", std::chrono::duration<double>(f1 - f0).count());
     pc.add("7b fetch records", std::chrono::duration<double>(f2 - f1).count());
     pc.add("7c format", std::chrono::duration<double>(f3 - f2).count());
-    dn->t_mapq = std::chrono::duration<double>(f1 - f0).count(); dn->t_fetch = std::chrono::duration<double>(f2 - f1).count(); dn->t_format = std::chrono::duration<double>(f3 - f2).count();
+    dn->t_mapq = std::chrono::duration<double>(f1 - f0).count();
+    dn->t_fetch = std::chrono::duration<double>(f2 - f1).count();
+    dn->t_format = std::chrono::duration<double>(f3 - f2).count();
     return dn;
   }
-  // the text of a batch as BGZF members (mm_bgzf_deflate: blocks of 65 280 bytes, each a member of its own, so the batches' members
-  // concatenate in output order); the text itself is kept only where --then-classify takes its lines from memory
+  // the text of a batch as BGZF members (map_outputs.hpp: the batches' members concatenate in output order); the text itself is kept only
+  // where --then-classify takes its lines from memory
   void deflate_text(mm_ctx* ctx, Done& dn) {
     const auto z0 = std::chrono::steady_clock::now();
-    dn.gz.resize((size_t)mm_bgzf_deflate_bound((int64_t)dn.text.size()));
-    int64_t nbytes = 0; int32_t nblocks = 0;
-    ck(ctx, mm_bgzf_deflate(ctx, (const uint8_t*)dn.text.data(), (int64_t)dn.text.size(), (uint8_t*)&dn.gz[0], (int64_t)dn.gz.size(), &nbytes, &nblocks), "deflate the mappings");
-    dn.gz.resize((size_t)nbytes);
+    bgzf_members(ctx, dn.text, dn.gz, "deflate the mappings");
     if (!keep_lines) std::string().swap(dn.text);
     pc.add("7d deflate", std::chrono::duration<double>(std::chrono::steady_clock::now() - z0).count());
   }
-  void write_all(const std::function<std::unique_ptr<Done>(size_t, size_t)>& next /* (file, seq): batch `seq` if it belongs to that file, nullptr once the file has ended */) {
+  // next(file, seq): batch `seq` if it belongs to that file, nullptr once the file has ended
+  void write_all(const std::function<std::unique_ptr<Done>(size_t, size_t)>& next) {
     size_t seq = 0;
     for (size_t fi = 0; fi < queries.size(); ++fi) {
       const std::string& prefix = prefixes[fi];
@@ -731,9 +485,12 @@ struct MapRun {
       const std::string out_name = compress ? prefix + ".gz" : prefix;
       std::ofstream out(out_name, std::ios::binary), unm(prefix + ".meta.unmappedReadsLengths");
       if (!out.is_open()) die("Cannot open output file " + out_name);
-      std::ofstream ed; if (edit) { ed.open(prefix + ".editDistances", std::ios::binary); if (!ed.is_open()) die("Cannot open output file " + prefix + ".editDistances"); }
-      std::ofstream pf; if (paf) { pf.open(prefix + ".paf", std::ios::binary); if (!pf.is_open()) die("Cannot open output file " + prefix + ".paf"); }
-      std::ofstream bf; if (bam) { bf.open(prefix + ".bam", std::ios::binary); if (!bf.is_open()) die("Cannot open output file " + prefix + ".bam"); bf.write(bam_head.data(), (std::streamsize)bam_head.size()); }
+      std::array<std::ofstream, N_SIDE> sf;
+      for (size_t s = 0; s < N_SIDE; ++s) if (side[s]) {
+        sf[s].open(prefix + kSideFiles[s].suffix, std::ios::binary);
+        if (!sf[s].is_open()) die("Cannot open output file " + prefix + kSideFiles[s].suffix);
+        if (kSideFiles[s].bgzf) sf[s].write(bgzf_head.data(), (std::streamsize)bgzf_head.size());
+      }
       size_t total = 0, tooShort = 0, mapped = 0, notMapped = 0; IdSet seen;   // (id_set.hpp: a std::set of 10^6 IDs bounded the mapping phase)
       for (;;) {
         std::unique_ptr<Done> d = next(fi, seq);
@@ -751,17 +508,22 @@ struct MapRun {
           ++mapped;
         }
         if (compress) out.write(d->gz.data(), (std::streamsize)d->gz.size()); else out << d->text;
-        if (edit) { ed << d->edit; std::string().swap(d->edit); }
-        if (paf) { pf << d->paf; std::string().swap(d->paf); }
-        if (bam) { bf.write(d->bam.data(), (std::streamsize)d->bam.size()); std::string().swap(d->bam); }
+        for (size_t s = 0; s < N_SIDE; ++s) if (side[s]) {
+          sf[s].write(d->side[s].data(), (std::streamsize)d->side[s].size());
+          std::string().swap(d->side[s]);
+        }
         std::string().swap(d->gz);
         if (keep_lines) { if (kept.size() <= fi) kept.resize(fi + 1); d->names.clear(); d->names.shrink_to_fit(); kept[fi].push_back(std::move(d)); }
       }
       if (keep_lines && kept.size() <= fi) kept.resize(fi + 1);
-      static const unsigned char eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0}; if (compress) out.write((const char*)eof, 28);
+      if (compress) out.write((const char*)kBgzfEof, sizeof kBgzfEof);
       out.close();
       if (!out) die("Error writing " + out_name);
-      if (bam) { bf.write((const char*)eof, 28); bf.close(); if (!bf) die("Error writing " + prefix + ".bam"); }
+      for (size_t s = 0; s < N_SIDE; ++s) if (side[s]) {
+        if (kSideFiles[s].bgzf) sf[s].write((const char*)kBgzfEof, sizeof kBgzfEof);
+        sf[s].close();
+        if (!sf[s]) die("Error writing " + prefix + kSideFiles[s].suffix);
+      }
       std::ofstream meta(prefix + ".meta");                      // mapWrap.h:178-184
       meta << "TotalReads " << total << "\nReadsTooShort " << tooShort << "\nReadsMapped " << mapped << "\nReadsNotMapped " << notMapped << "\n";
       std::ofstream ps(prefix + ".parameters");                  // mapWrap.h:196-211
@@ -774,16 +536,19 @@ struct MapRun {
   }
 
   void run_replicated() {
-    // ---- workers: four contexts per device (--workers-per-gpu; three until round 4: with ten batches of 10^5 reads in one file the GPU idled 60 % of the mapping phase), so that packing, result download and text formatting of one batch overlap the
+    // ---- workers: four contexts per device (--workers-per-gpu; three until round 4: with ten batches of 10^5 reads in one file the GPU idled
+    // 60 % of the mapping phase), so that packing, result download and text formatting of one batch overlap the
     // kernels of the other; the device's chunk indexes are shared (read-only) by its contexts
     // The kernels of a batch fill the device; batches mapped side by side only take turns on it, and four workers that start together
     // then also finish together: they packed, fetched and formatted at the same time with the device idle, and mapped at the same time
     // in each other's way (the done-times of the workers came in groups of four, 60 ms apart).  So at most MAP_SLOTS batches per device are
     // inside their mapping section at a time (two: one fills the host-side gaps of the other), which staggers the workers.
     const size_t MAP_SLOTS = sw.map_slots;
-    struct Slots { std::mutex m; std::condition_variable cv; size_t free_ = 0;
-                   void acquire() { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&] { return free_ > 0; }); --free_; }
-                   void release() { { std::lock_guard<std::mutex> lk(m); ++free_; } cv.notify_one(); } };
+    struct Slots {
+      std::mutex m; std::condition_variable cv; size_t free_ = 0;
+      void acquire() { std::unique_lock<std::mutex> lk(m); cv.wait(lk, [&] { return free_ > 0; }); --free_; }
+      void release() { { std::lock_guard<std::mutex> lk(m); ++free_; } cv.notify_one(); }
+    };
     std::vector<Slots> map_slots(G);
     for (auto& sl : map_slots) sl.free_ = MAP_SLOTS;
     std::vector<std::thread> workers;
@@ -792,13 +557,13 @@ struct MapRun {
       if (!ctx && mm_ctx_create(devs[d].phys, &ctx) != MM_OK) die("cannot create a worker context");
       while (std::unique_ptr<Batch> bt = reader.take()) {
         const auto t0 = std::chrono::steady_clock::now();
-        mm_seqset* reads = upload_batch(ctx, *bt);
-        std::vector<int> clens; if (hpc) clens = compressed_lengths(ctx, reads);
+        ReadsPtr reads(upload_batch(ctx, *bt));
+        std::vector<int> clens; if (hpc) clens = compressed_lengths(ctx, reads.get());
         const auto t1 = std::chrono::steady_clock::now();
         std::vector<mm_mapping*> parts;
         map_slots[d].acquire();
         const auto t1a = std::chrono::steady_clock::now();
-        for (size_t c = 0; c < NC; ++c) parts.push_back(map_chunk(ctx, devs[d].idx[c], reads, c ? parts[0] : nullptr));
+        for (size_t c = 0; c < NC; ++c) parts.push_back(map_chunk(ctx, devs[d].idx[c], reads.get(), c ? parts[0] : nullptr));
         map_slots[d].release();
         mm_map_stats gst{}; if (sw.timing) mm_mapping_get_stats(parts[0], &gst);   // (device time of the batch's stages by the library's own events)
         mm_mapping* m = parts[0];
@@ -806,17 +571,24 @@ struct MapRun {
           ck(ctx, mm_mapping_concat(ctx, parts.data(), chunk_base.data(), (int)parts.size(), &m), "merge chunks");
           for (auto* pm : parts) mm_mapping_destroy(pm);
         }
-        if (!edit) { mm_seqset_destroy(reads); reads = nullptr; }
+        if (!edit) reads.reset();                                  // no side output needs them
         const auto t2 = std::chrono::steady_clock::now();
         const size_t seq = bt->seq;
-        auto dn = finish_mapping(ctx, d, m, std::move(bt->names), std::move(bt->lens), std::move(clens), bt->file, reads);
+        auto dn = finish_mapping(ctx, d, m, std::move(bt->names), std::move(bt->lens), std::move(clens), bt->file, std::move(reads));
         const auto t3 = std::chrono::steady_clock::now();
-        pc.add("5 reads pack+upload", std::chrono::duration<double>(t1 - t0).count());
-        pc.add("6 map", std::chrono::duration<double>(t2 - t1a).count());
-        pc.add("6a waited for the device", std::chrono::duration<double>(t1a - t1).count());
-        pc.add("7 mapq+fetch+format", std::chrono::duration<double>(t3 - t2).count());
-        if (sw.timing) { std::ostringstream os; os << "INFO, worker " << d << "." << wi << " batch " << seq << ": upload " << std::chrono::duration<double>(t1 - t0).count() << " map "
-          << std::chrono::duration<double>(t2 - t1a).count() << " (waited " << std::chrono::duration<double>(t1a - t1).count() << "; device ms: K1 " << gst.ms_minimizer << " K2 " << gst.ms_sketch << " K3 " << gst.ms_probe_gather << " K4 " << gst.ms_sort_hits + gst.ms_l1_scan << " K5 " << gst.ms_l2 << " all " << gst.ms_total << ") finish " << std::chrono::duration<double>(t3 - t2).count() << " (mapq " << dn->t_mapq << " fetch " << dn->t_fetch << " format " << dn->t_format << ") done at +" << std::chrono::duration<double>(t3 - pc.t0).count() << " s\n"; std::cerr << os.str(); }
+        auto secs = [](std::chrono::steady_clock::duration x) { return std::chrono::duration<double>(x).count(); };
+        pc.add("5 reads pack+upload", secs(t1 - t0));
+        pc.add("6 map", secs(t2 - t1a));
+        pc.add("6a waited for the device", secs(t1a - t1));
+        pc.add("7 mapq+fetch+format", secs(t3 - t2));
+        if (sw.timing) {
+          std::ostringstream os;
+          os << "INFO, worker " << d << "." << wi << " batch " << seq << ": upload " << secs(t1 - t0) << " map " << secs(t2 - t1a)
+             << " (waited " << secs(t1a - t1) << "; device ms: K1 " << gst.ms_minimizer << " K2 " << gst.ms_sketch << " K3 " << gst.ms_probe_gather
+             << " K4 " << gst.ms_sort_hits + gst.ms_l1_scan << " K5 " << gst.ms_l2 << " all " << gst.ms_total << ") finish " << secs(t3 - t2)
+             << " (mapq " << dn->t_mapq << " fetch " << dn->t_fetch << " format " << dn->t_format << ") done at +" << secs(t3 - pc.t0) << " s\n";
+          std::cerr << os.str();
+        }
         reader.recycle(std::move(bt));
         writer.put(seq, std::move(dn));
       }
@@ -836,17 +608,26 @@ struct MapRun {
 
   void run_chunk_major() {
     // ---- sharded / streamed: every read batch is packed onto every device and stays there (2 bits per base) ...
-    struct Held { size_t file = 0; std::vector<std::string> names; std::vector<int> lens, clens /* --hpc: compressed */; std::vector<mm_seqset*> reads;
-                  std::vector<mm_mapping*> sk;                 // per device: the batch's minimizers + sketches (mm_sketch_batch), computed once for all chunks
-                  std::vector<mm_mapping*> part;               // per chunk: the batch's records against that chunk, on the device that holds the chunk (c mod G)
-                  std::vector<std::vector<int64_t>> poff; std::vector<std::vector<mm_map_record>> prec; };   // --host-gather: the same in host memory (rounds 1-3)
+    struct Held {
+      size_t file = 0;
+      std::vector<std::string> names;
+      std::vector<int> lens, clens;                                // (clens: --hpc, the compressed lengths)
+      std::vector<mm_seqset*> reads;                               // per device
+      std::vector<mm_mapping*> sk;                                 // per device: the batch's minimizers + sketches (mm_sketch_batch), computed once for all chunks
+      std::vector<mm_mapping*> part;                               // per chunk: the batch's records against that chunk, on the device that holds the chunk (c mod G)
+      std::vector<std::vector<int64_t>> poff;                      // --host-gather: the same in host memory (rounds 1-3)
+      std::vector<std::vector<mm_map_record>> prec;
+    };
     // How the records of a batch reach the device that merges them (unifyFiles, mapWrap.h:128-145, in place of the PREFIX.N files):
     //   rccl  (several physical devices) mm_mapping_gather: ncclSend / ncclRecv over xGMI, one collective per batch
     //   peer  (logical devices of one GPU, or --peer-gather) mm_mapping_concat pulls the parts of other contexts with device-to-device copies
     //   host  (--host-gather) mm_mapping_fetch + mm_mapping_from_parts: through host memory, the path of rounds 1-3, kept as the cross-check
     bool distinct = true; for (size_t a = 0; a < G; ++a) for (size_t b2 = a + 1; b2 < G; ++b2) distinct = distinct && devs[a].phys != devs[b2].phys;
-    enum class Gather { Rccl, Peer, Host } gather = o.v.count("host-gather") ? Gather::Host : (G > 1 && distinct && !o.v.count("peer-gather")) ? Gather::Rccl : Gather::Peer;
-    if (sw.timing) std::cerr << "INFO, records of the chunks are gathered by " << (gather == Gather::Rccl ? "RCCL send / receive" : gather == Gather::Peer ? "device-to-device copies" : "the host") << "\n";
+    enum class Gather { Rccl, Peer, Host };
+    const Gather gather = o.v.count("host-gather") ? Gather::Host : (G > 1 && distinct && !o.v.count("peer-gather")) ? Gather::Rccl : Gather::Peer;
+    if (sw.timing)
+      std::cerr << "INFO, records of the chunks are gathered by "
+                << (gather == Gather::Rccl ? "RCCL send / receive" : gather == Gather::Peer ? "device-to-device copies" : "the host") << "\n";
     std::vector<Held> held;
     while (std::unique_ptr<Batch> bt = reader.take()) {
       held.emplace_back();
@@ -914,7 +695,8 @@ struct MapRun {
           std::vector<mm_mapping*> mine; std::vector<int32_t> ids;
           for (size_t c = d; c < NC; c += G) { mine.push_back(h.part[c]); ids.push_back((int32_t)c); }
           mm_mapping* m = nullptr;
-          ck(ctx, mm_mapping_gather(ctx, (int)(b % G), (int64_t)h.names.size(), (hpc ? h.clens : h.lens).data(), &mp, mine.data(), ids.data(), (int)mine.size(), (int)NC, chunk_rank.data(), chunk_base.data(), &m), "gather chunks");
+          ck(ctx, mm_mapping_gather(ctx, (int)(b % G), (int64_t)h.names.size(), (hpc ? h.clens : h.lens).data(), &mp, mine.data(), ids.data(), (int)mine.size(),
+                                    (int)NC, chunk_rank.data(), chunk_base.data(), &m), "gather chunks");
           if (b % G == d) merged[b] = m;
           for (auto* pm : mine) mm_mapping_destroy(pm);
         }
@@ -960,8 +742,10 @@ struct MapRun {
     for (size_t fi = 0; fi < prefixes.size(); ++fi) {
       const bool last = fi + 1 == prefixes.size();
       KeptLines kl; kl.cname = &cname;
-      if (keep_lines && fi < kept.size()) for (const auto& d : kept[fi]) kl.parts.push_back(KeptLines::Part{d->text.data(), d->meta.data(), d->meta.size(), d->off.data(), d->lens.size()});
-      classify_one(devs, reduce, prefixes[fi], o.v.at("then-classify"), minReadsU, last ? leave : std::function<void()>(), nullptr, keep_lines ? &kl : nullptr, boot_options(o), lca_options(o), gene_options(o), ident_options(o), sw);
+      if (keep_lines && fi < kept.size())
+        for (const auto& d : kept[fi]) kl.parts.push_back(KeptLines::Part{d->text.data(), d->meta.data(), d->meta.size(), d->off.data(), d->lens.size()});
+      classify_one(devs, reduce, prefixes[fi], o.v.at("then-classify"), minReadsU, last ? leave : std::function<void()>(), nullptr, keep_lines ? &kl : nullptr,
+                   boot_options(o), lca_options(o), gene_options(o), ident_options(o), sw);
       if (keep_lines && fi < kept.size()) kept[fi].clear();
       for (auto& d : devs) mm_comm_destroy(d.ctx);
       pc.lap("9 classify");
@@ -975,12 +759,12 @@ struct MapRun {
       load_reference();
       plan_chunks();
       if (only_index) return write_index_files();
-    } else read_index_files();
+    } else read_index_files(ipre, cname, clen, ref_bases, chunks);   // `metamaps mapAgainstIndex` (mapWrap.h:443-554)
     decide_placement();
     build_resident_indexes();
     mp = mm_map_params{k, w, pi, minLen};
     for (auto& ch : chunks) chunk_base.push_back(ch.first);
-    if (bam) bam_head = bam_header_members(ctx0, cname, clen);    // (before the workers take the first device's context)
+    if (side[SIDE_BAM]) bgzf_head = bam_header_members(ctx0, cname, clen);   // (before the workers take the first device's context)
     start_reader();
     if (prewarm.joinable()) prewarm.join();
     if (place != Place::Replicated) for (auto*& c : wctx) if (c) { mm_ctx_destroy(c); c = nullptr; }   // (the other modes drive one context per device)

@@ -47,14 +47,14 @@
 // "readID contigID strand d first last": the exact unit-cost edit distance of the whole read (its reverse complement for strand -) to the best
 // substring of the window contig[ref_start - pad, ref_start + L + pad), pad = 64 + L / 16, and that substring's 0-based inclusive coordinates;
 // "NA NA NA" where the distance is above floor(1.5 L (100 - pi) / 100) or the read is longer than 65 536 bases.  Aligned on the device that mapped
-// the batch (mm_mapping_edit_distances, host/edit_dist.hpp); every device keeps its packed reference (0.25 bytes per base) and a batch's reads live
+// the batch (mm_mapping_edit_distances, host/map_outputs.hpp); every device keeps its packed reference (0.25 bytes per base) and a batch's reads live
 // until its distances are fetched.  PREFIX, .meta* and .parameters are the bytes of a run without the flag.  Refused: --hpc, index, mapAgainstIndex,
 // classify, and any run whose chunk indexes are sharded or streamed (--shard-index, --stream-chunks, or an index that does not fit one device).
 //
 // --paf (mapDirectly; not in the reference; implies --edit-distance): also PREFIX.paf, one PAF line per ALIGNED line of PREFIX in the same order,
 // "readID L 0 L strand contigID contigLen first last+1 matches alignmentLength 255 NM:i:d cg:Z:CIGAR" with = X I D runs: the base-level alignment
 // behind d, first and last (the definition: csrc/mm_edit_core.hpp; for strand - the reverse-complemented read along the forward contig).  The context
-// that mapped a batch traces it on the device in the one call that also gives the .editDistances lines (mm_mapping_align, host/paf_out.hpp).  A mapping
+// that mapped a batch traces it on the device in the one call that also gives the .editDistances lines (mm_mapping_align, host/map_outputs.hpp).  A mapping
 // that is not aligned has no PAF line.  PREFIX.paf is plain text even under --compress-output.  Refused wherever --edit-distance is.
 //
 // --bam (mapDirectly; not in the reference; implies --edit-distance; may be combined with --paf): also PREFIX.bam, one BAM record (SAM/BAM specification
@@ -118,7 +118,8 @@ Options parse(int argc, char** argv) {
     if (a == "--stream-chunks") { o.stream = true; continue; }
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
-    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" || a == "--bam" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
+    if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" ||
+        a == "--bam" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
@@ -221,7 +222,8 @@ int main(int argc, char** argv) {
     if (stat(gene::proteins_path(db).c_str(), &probe) != 0) die("--genes: please supply a protein annotation file (file " + gene::proteins_path(db) + " not found).");
   }
   const IdentOpts identf_opts = ident_options(o);
-  if ((identf_opts.on || identf_opts.refit) && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--min-identity and --refit need classify or mapDirectly --then-classify");
+  if ((identf_opts.on || identf_opts.refit) && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify")))
+    die("--min-identity and --refit need classify or mapDirectly --then-classify");
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
   if (o.v.count("paf") || o.v.count("bam")) o.v["edit-distance"] = "1";   // (--paf and --bam imply it, and inherit its refusals under their own names)
   if (o.v.count("edit-distance")) {                              // (refused before any device work)

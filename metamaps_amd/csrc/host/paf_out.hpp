@@ -2,27 +2,23 @@
 //   readID  L  0  L  +|-  contigID  contigLen  first  last+1  n_eq  n_eq+n_X+n_I+n_D  255  NM:i:d  cg:Z:<runs with = X I D>
 // The read is aligned whole (query start 0, end L); first / last+1 are the alignment's 0-based half-open contig coordinates; for strand - the CIGAR is that
 // of the reverse-complemented read along the forward contig, as PAF has it.  A mapping that is not aligned (NA NA NA in .editDistances) has no line.
-// One call (mm_mapping_align) on the context that mapped the batch gives d, first, last and the runs, fetched once (BatchAlignment): the lines of
-// PREFIX.editDistances (edit_dist.hpp: the bytes of a run with --edit-distance alone), the lines of PREFIX.paf and the records of PREFIX.bam
-// (bam_out.hpp) come from the same answer, nothing is aligned twice.
+// One call (mm_mapping_align, map_outputs.hpp) on the context that mapped the batch gives d, first, last and the runs, fetched once (BatchAlignment):
+// the lines of PREFIX.editDistances (edit_dist.hpp: the bytes of a run with --edit-distance alone), the lines of PREFIX.paf and the records of
+// PREFIX.bam (bam_out.hpp) come from the same answer, nothing is aligned twice.  Text only: nothing here calls the device.
 #pragma once
-#include "edit_dist.hpp"
+#include "../../../include/metamaps_hip.h"
+#include "cli_common.hpp"
+#include "fast_format.hpp"
 
 namespace {
 
 // what mm_alignment_fetch gives for the records of one batch, in the order of the lines of PREFIX
-struct BatchAlignment { std::vector<int32_t> dist; std::vector<int64_t> first, last, op_off; std::vector<uint32_t> ops; };
-
-void fetch_alignment(mm_ctx* ctx, const mm_mapping* m, const mm_seqset* reads, const mm_seqset* reference, float pi, size_t n_rec, BatchAlignment& A) {
-  mm_alignment* al = nullptr;
-  ck(ctx, mm_mapping_align(ctx, m, reads, reference, pi, &al), "alignments");
-  int64_t n_jobs = 0, n_ops = 0;
-  mm_alignment_sizes(al, &n_jobs, &n_ops);
-  if (n_jobs != (int64_t)n_rec) die("internal error: alignments and records differ in number");
-  A.dist.resize(n_rec); A.first.resize(n_rec); A.last.resize(n_rec); A.op_off.resize(n_rec + 1); A.ops.resize((size_t)n_ops);
-  mm_alignment_fetch(al, A.dist.data(), A.first.data(), A.last.data(), A.op_off.data(), A.ops.data());
-  mm_alignment_destroy(al);
-}
+struct BatchAlignment {
+  std::vector<int32_t> dist;                                     // per record: the edit distance, -1: not aligned
+  std::vector<int64_t> first, last;                              // per record: the alignment's 0-based inclusive contig coordinates
+  std::vector<int64_t> op_off;                                   // per record: where its runs start in ops (one more entry than records)
+  std::vector<uint32_t> ops;                                     // the runs, BAM's words: len << 4 | op with I = 1, D = 2, = = 7, X = 8
+};
 
 void paf_text(const BatchAlignment& A, const std::vector<std::string>& names, const std::vector<int>& lens, const std::vector<int64_t>& off, const std::vector<mm_map_record>& rec,
               const std::vector<std::string>& cname, const std::vector<int>& clen, std::string& paf) {

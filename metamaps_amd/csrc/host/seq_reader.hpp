@@ -19,7 +19,8 @@
 #include <vector>
 
 namespace {
-[[noreturn]] inline void seq_reader_die(const std::string& m) { std::cerr << m << std::endl; std::cout.flush(); fflush(nullptr); _exit(1); }   // (_exit: other threads may be inside the HIP runtime, metamaps_main.cpp die())
+// (_exit: other threads may be inside the HIP runtime, metamaps_main.cpp die())
+[[noreturn]] inline void seq_reader_die(const std::string& m) { std::cerr << m << std::endl; std::cout.flush(); fflush(nullptr); _exit(1); }
 
 // FASTA/FASTQ(.gz) records with kseq's observable behaviour (common/kseq.h:170-207)
 // Three sources: a (gz) file read through zlib in 1 MiB pieces, a caller's `fill` (the inflated segments of a bgzip file: the record parse
@@ -77,7 +78,10 @@ class SeqFile {
       if (nl && nl > p && nl + 1 < fe && nl[1] == '+') {
         const size_t L = (size_t)(nl - p);
         unsigned char bad = 0;
-        for (const unsigned char* q = p; q < nl; ++q) { const unsigned char b = *q; bad |= (unsigned char)((unsigned char)(b - 33) > 93) | (unsigned char)(b == '+') | (unsigned char)(b == '>') | (unsigned char)(b == '@'); }
+        for (const unsigned char* q = p; q < nl; ++q) {
+          const unsigned char b = *q;
+          bad |= (unsigned char)((unsigned char)(b - 33) > 93) | (unsigned char)(b == '+') | (unsigned char)(b == '>') | (unsigned char)(b == '@');
+        }
         const unsigned char* pl = (const unsigned char*)memchr(nl + 1, '\n', (size_t)(fe - nl - 1));
         if (!bad && pl && (size_t)(fe - pl - 1) >= L && (pl + 1 + L == fe || pl[1 + L] == '\n')) {
           const unsigned char* ql = pl + 1;
@@ -98,7 +102,10 @@ class SeqFile {
         const unsigned char* const nl = (const unsigned char*)memchr(p, '\n', end_ - beg_);
         const unsigned char* const le = nl ? nl : buf_.data() + end_;
         unsigned char bad = 0;                                   // (byte-wise OR reduction: vectorises)
-        for (const unsigned char* q = p; q < le; ++q) { const unsigned char b = *q; bad |= (unsigned char)((unsigned char)(b - 33) > 93) | (unsigned char)(b == '+') | (unsigned char)(b == '>') | (unsigned char)(b == '@'); }
+        for (const unsigned char* q = p; q < le; ++q) {
+          const unsigned char b = *q;
+          bad |= (unsigned char)((unsigned char)(b - 33) > 93) | (unsigned char)(b == '+') | (unsigned char)(b == '>') | (unsigned char)(b == '@');
+        }
         if (!bad && le > p) { seq.append((const char*)p, (size_t)(le - p)); beg_ = (size_t)(le - buf_.data()) + (nl ? 1 : 0); continue; }
       }
       const unsigned char* const e = p + std::min<size_t>(end_ - beg_, 16384);   // (resize zero-fills: keep the pieces small)

@@ -40,16 +40,29 @@ struct Taxonomy {                                                // meta/taxonom
   explicit Taxonomy(const std::string& dir) {
     std::map<std::string, std::string> sci; std::string ln;
     std::ifstream nm(dir + "/names.dmp"); if (!nm.is_open()) die("Cannot open file " + dir + "/names.dmp -- is '" + dir + "' a valid NCBI taxonomy?");
-    while (std::getline(nm, ln)) { if (ln.empty()) continue; auto f = fields(ln); if (f.size() > 3 && f[3] == "scientific name") sci[f[0]] = f[1]; else if (f.size() > 3 && f[3] == "genbank common name") sci[f[0]]; }
+    while (std::getline(nm, ln)) {
+      if (ln.empty()) continue;
+      auto f = fields(ln);
+      if (f.size() > 3 && f[3] == "scientific name") sci[f[0]] = f[1]; else if (f.size() > 3 && f[3] == "genbank common name") sci[f[0]];
+    }
     std::ifstream nd(dir + "/nodes.dmp"); if (!nd.is_open()) die("Cannot open file " + dir + "/nodes.dmp");
-    while (std::getline(nd, ln)) { if (ln.empty()) continue; auto f = fields(ln); if (!sci.count(f[0])) die("No name for taxon ID " + f[0] + " in taxonomy directory " + dir); T[f[0]] = TaxNode{f[1], f[2], sci[f[0]]}; }
+    while (std::getline(nd, ln)) {
+      if (ln.empty()) continue;
+      auto f = fields(ln);
+      if (!sci.count(f[0])) die("No name for taxon ID " + f[0] + " in taxonomy directory " + dir);
+      T[f[0]] = TaxNode{f[1], f[2], sci[f[0]]};
+    }
     std::cout << "Read taxonomy from " << dir << " -- have " << T.size() << " nodes." << std::endl;
   }
   std::map<std::string, std::string> upward_by_ranks(std::string id, const std::set<std::string>& want) const {   // taxonomy.h:76-111
     std::map<std::string, std::string> r;
     std::vector<std::string> up{id};
     while (id != "1") { id = T.at(id).parent; up.push_back(id); }
-    for (auto& n : up) { const std::string& rank = T.at(n).rank; if (!want.count(rank)) continue; if (rank != "no rank") { if (r.count(rank)) die("Node " + up[0] + " has multiple entries for rank " + rank); r[rank] = n; } }
+    for (auto& n : up) {
+      const std::string& rank = T.at(n).rank;
+      if (!want.count(rank)) continue;
+      if (rank != "no rank") { if (r.count(rank)) die("Node " + up[0] + " has multiple entries for rank " + rank); r[rank] = n; }
+    }
     for (auto& w : want) if (!r.count(w)) r[w] = "Undefined";
     return r;
   }
@@ -75,7 +88,8 @@ static double mapq_as_classify_reads_it(const char* p, size_t n) {
   if (parse_g6_text(p, n, &v)) return v;
   const std::string t(p, n);
   errno = 0; v = strtod(t.c_str(), nullptr);
-  if (errno == ERANGE) v = t.find("e-") != std::string::npos ? 0.0 : v;   // (std::stod throws on a denormal; the reference then takes 0, fEM.h:269-275 — an overflow cannot be printed by this program)
+  // (std::stod throws on a denormal; the reference then takes 0, fEM.h:269-275 — an overflow cannot be printed by this program)
+  if (errno == ERANGE) v = t.find("e-") != std::string::npos ? 0.0 : v;
   return v;
 }
 
