@@ -30,7 +30,7 @@ extern "C" {
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
                             *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances,
-                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_* (additions to 6) */
+                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_*, mm_pileup_* (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -52,6 +52,8 @@ typedef struct mm_em mm_em;            /* EM state (mappings x taxa) resident in
 typedef struct mm_gzip mm_gzip;        /* a plain gzip stream being inflated on a context's device */
 typedef struct mm_alignment mm_alignment;  /* base-level alignments (CIGAR runs) of a batch of jobs, in host memory */
 typedef struct mm_bam mm_bam;          /* BGZF members holding BAM records of a batch of jobs, in host memory */
+typedef struct mm_pileup mm_pileup;    /* a table of (key, count) pileup events, unique keys ascending, in host memory */
+typedef struct mm_pileup_result mm_pileup_result;  /* the kept sites and the per-contig coverage of a run's pileup, in host memory */
 typedef struct mm_hpc_map mm_hpc_map;  /* compressed -> raw coordinates of a homopolymer-compressed set, resident in HBM */
 
 /* ---- context -------------------------------------------------------------------------------- */
@@ -518,6 +520,34 @@ int mm_bam_encode(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* referenc
 int mm_bam_sizes(const mm_bam* bam, int64_t* n_records, int64_t* raw_bytes, int64_t* bgzf_bytes);
 int mm_bam_fetch(const mm_bam* bam, uint8_t* bgzf /* [bgzf_bytes] */);
 void mm_bam_destroy(mm_bam* bam);
+
+/* The pileup of aligned jobs: what differs from the reference, counted per column on the context's device ("Pileup"; the
+ * definition: csrc/mm_pileup_core.hpp).  A job contributes where use[i] != 0 and dist[i] >= 0.  Walking its runs from r = first, i = 0 in the oriented
+ * read Q: an = run gives nothing; an X run of n the events (contig, r + t, code(Q[i + t])), A 0 C 1 G 2 T 3, any other byte N 4; a D run of n the events
+ * (contig, r + t, 5); an I run ONE event (contig, r > first ? r - 1 : first, 6): the base before the insertion, `first` for a leading one.
+ * key = contig << 35 | pos << 3 | code (2^29 contigs at most: MM_ERR_ARG beyond), so keys order by contig, position, code.
+ * mm_pileup_events returns the events of one call's jobs as (key, count) pairs with unique keys in ascending order.  It applies mm_bam_encode's rules
+ * 1, 2 (the strand), 4, 5 and 6 to the jobs it uses: MM_ERR_ARG with "mm_pileup_events: job <index>: rule <number>: ..." for the lowest offender.
+ * mm_pileup_merge takes any multiset of pairs (unsorted, keys may repeat) and returns the table with equal keys summed; a sum above 2^32 - 1 is
+ * MM_ERR_ARG.  mm_pileup_finish takes a merged table (keys ascending and unique, every key a position of `reference`: MM_ERR_ARG otherwise) and the
+ * intervals [iv_first, iv_last] on iv_contig of EVERY contributing alignment of the run: depth(contig, pos) is the number of intervals that hold pos;
+ * an entry is kept where count >= min_count && (double)count >= min_frac * (double)depth, and carries the reference's byte at its position.  Per contig:
+ * alignments (its intervals), covered (positions of depth >= 1: the length of the intervals' union) and sum_depth (the sum of last - first + 1).
+ * All arrays are the caller's; results live in host memory until destroyed; an error leaves *out NULL and launches nothing further. */
+int mm_pileup_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs,
+                     const int32_t* read, const int32_t* strand, const int32_t* contig, const int32_t* dist, const int64_t* first,
+                     const int64_t* op_off /* [n_jobs + 1] */, const uint32_t* ops, const uint8_t* use /* [n_jobs] */, mm_pileup** out);
+int mm_pileup_merge(mm_ctx* ctx, int64_t n, const uint64_t* keys, const uint32_t* counts, mm_pileup** out);
+int mm_pileup_sizes(const mm_pileup* table, int64_t* n_pairs);
+int mm_pileup_fetch(const mm_pileup* table, uint64_t* keys /* [n_pairs] */, uint32_t* counts);
+void mm_pileup_destroy(mm_pileup* table);
+int mm_pileup_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* keys, const uint32_t* counts,
+                     int64_t n_iv, const int32_t* iv_contig, const int64_t* iv_first, const int64_t* iv_last,
+                     int64_t min_count, double min_frac, mm_pileup_result** out);
+int mm_pileup_result_sizes(const mm_pileup_result* result, int64_t* n_sites, int64_t* n_contigs);
+int mm_pileup_result_fetch_sites(const mm_pileup_result* result, uint64_t* key /* [n_sites] */, uint32_t* count, uint32_t* depth, uint8_t* ref_byte);
+int mm_pileup_result_fetch_contigs(const mm_pileup_result* result, int64_t* alignments /* [n_contigs] */, int64_t* covered, int64_t* sum_depth);
+void mm_pileup_result_destroy(mm_pileup_result* result);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------------------------- */
 #define MM_COMM_ID_BYTES 128

@@ -202,6 +202,16 @@ def lib() -> C.CDLL:
             "mm_bam_sizes": (C.c_int, [vp, vp, vp, vp]),
             "mm_bam_fetch": (C.c_int, [vp, vp]),
             "mm_bam_destroy": (None, [vp]),
+            "mm_pileup_events": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "mm_pileup_merge": (C.c_int, [vp, i64, vp, vp, vp]),
+            "mm_pileup_sizes": (C.c_int, [vp, vp]),
+            "mm_pileup_fetch": (C.c_int, [vp, vp, vp]),
+            "mm_pileup_destroy": (None, [vp]),
+            "mm_pileup_finish": (C.c_int, [vp, vp, i64, vp, vp, i64, vp, vp, vp, i64, f64, vp]),
+            "mm_pileup_result_sizes": (C.c_int, [vp, vp, vp]),
+            "mm_pileup_result_fetch_sites": (C.c_int, [vp, vp, vp, vp, vp]),
+            "mm_pileup_result_fetch_contigs": (C.c_int, [vp, vp, vp, vp]),
+            "mm_pileup_result_destroy": (None, [vp]),
             "mm_comm_unique_id": (C.c_int, [C.c_char_p]),
             "mm_comm_init": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
             "mm_comm_allreduce_f64": (C.c_int, [vp, vp, i64]),
@@ -575,6 +585,64 @@ class Context:
             self.last_bam_handle = h.value                          # (what the call left in *out: None after a refusal)
             if h.value:
                 lib().mm_bam_destroy(h)
+
+    def _pileup_table(self, status, handle):
+        """(keys, counts) of an mm_pileup, which is destroyed; `handle` is NULL after an error"""
+        try:
+            self.check(status)
+            n = C.c_int64(-1)
+            assert lib().mm_pileup_sizes(handle, C.byref(n)) == 0
+            keys, counts = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint32)
+            assert lib().mm_pileup_fetch(handle, _ptr(keys), _ptr(counts)) == 0
+            return keys, counts
+        finally:
+            self.last_pileup_handle = handle.value                  # (what the call left in *out: None after a refusal)
+            if handle.value:
+                lib().mm_pileup_destroy(handle)
+
+    def pileup_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use):
+        """the pileup events of the jobs with use != 0 and dist >= 0 (mm_pileup_events): (keys, counts), keys contig << 35 | pos << 3 | code unique
+        and ascending, code A 0 C 1 G 2 T 3 N 4, a deleted base 5, an insertion behind the base 6"""
+        rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
+        fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
+        op, us = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(use, dtype=np.uint8)
+        n = len(rd)
+        assert all(len(x) == n for x in (sd, cg, ds, fs, us)) and len(oo) == n + 1
+        h = C.c_void_p(0xDEAD)                                      # (the call sets it, to NULL on an error)
+        st = lib().mm_pileup_events(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), C.byref(h))
+        return self._pileup_table(st, h)
+
+    def pileup_merge(self, keys, counts):
+        """any (key, count) pairs, unsorted, keys may repeat -> the table with equal keys summed (mm_pileup_merge)"""
+        ks, cs = np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(counts, dtype=np.uint32)
+        assert len(ks) == len(cs)
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_pileup_merge(self.h, len(ks), _ptr(ks), _ptr(cs), C.byref(h))
+        return self._pileup_table(st, h)
+
+    def pileup_finish(self, reference: "SeqSet", keys, counts, iv_contig, iv_first, iv_last, min_count=3, min_frac=0.2):
+        """the kept sites of a merged table and every contig's coverage from the intervals of all contributing alignments (mm_pileup_finish): a dict with
+        key, count, depth, ref_byte per kept site and alignments, covered, sum_depth per contig of the reference"""
+        ks, cs = np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(counts, dtype=np.uint32)
+        ic = np.ascontiguousarray(iv_contig, dtype=np.int32)
+        i0, i1 = np.ascontiguousarray(iv_first, dtype=np.int64), np.ascontiguousarray(iv_last, dtype=np.int64)
+        assert len(ks) == len(cs) and len(ic) == len(i0) == len(i1)
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_pileup_finish(self.h, reference.h, len(ks), _ptr(ks), _ptr(cs), len(ic), _ptr(ic), _ptr(i0), _ptr(i1), int(min_count), float(min_frac), C.byref(h))
+        try:
+            self.check(st)
+            ns, nc = C.c_int64(-1), C.c_int64(-1)
+            assert lib().mm_pileup_result_sizes(h, C.byref(ns), C.byref(nc)) == 0
+            out = dict(key=np.zeros(ns.value, dtype=np.uint64), count=np.zeros(ns.value, dtype=np.uint32), depth=np.zeros(ns.value, dtype=np.uint32),
+                       ref_byte=np.zeros(ns.value, dtype=np.uint8), alignments=np.full(nc.value, -1, dtype=np.int64), covered=np.full(nc.value, -1, dtype=np.int64),
+                       sum_depth=np.full(nc.value, -1, dtype=np.int64))
+            assert lib().mm_pileup_result_fetch_sites(h, _ptr(out["key"]), _ptr(out["count"]), _ptr(out["depth"]), _ptr(out["ref_byte"])) == 0
+            assert lib().mm_pileup_result_fetch_contigs(h, _ptr(out["alignments"]), _ptr(out["covered"]), _ptr(out["sum_depth"])) == 0
+            return out
+        finally:
+            self.last_pileup_handle = h.value
+            if h.value:
+                lib().mm_pileup_result_destroy(h)
 
     # ---- communicator
     @staticmethod

@@ -1,10 +1,12 @@
-// The side outputs of a batch of mapDirectly (the rows of side_files.hpp: PREFIX.editDistances, .paf, .bam) and the device calls they need.  The text
-// and byte rules are in edit_dist.hpp, paf_out.hpp and bam_out.hpp, which call nothing; everything here runs on the context that mapped the batch.
+// The side outputs of a batch of mapDirectly (the rows of side_files.hpp: PREFIX.editDistances, .paf, .bam) and the device calls they need, and the run's
+// pileup (PREFIX.pileup, .pileup.contigs), which every batch adds to.  The text and byte rules are in edit_dist.hpp, paf_out.hpp, bam_out.hpp and
+// pileup_out.hpp, which call nothing; everything of a batch runs on the context that mapped it, the pileup's last merge and finish on the first device.
 #pragma once
 #include "bam_out.hpp"
 #include "cli_device.hpp"
 #include "edit_dist.hpp"
 #include "paf_out.hpp"
+#include "pileup_out.hpp"
 #include "side_files.hpp"
 #include <memory>
 
@@ -30,20 +32,72 @@ std::string bam_header_members(mm_ctx* ctx, const std::vector<std::string>& cnam
   return gz;
 }
 
+// (key, count) pairs and their sums through mm_pileup_merge, which leaves them unique and ascending
+void pileup_merge_pairs(mm_ctx* ctx, std::vector<uint64_t>& keys, std::vector<uint32_t>& counts) {
+  mm_pileup* t = nullptr;
+  ck(ctx, mm_pileup_merge(ctx, (int64_t)keys.size(), keys.data(), counts.data(), &t), "pileup merge");
+  int64_t n = 0;
+  mm_pileup_sizes(t, &n);
+  keys.resize((size_t)n); counts.resize((size_t)n);
+  mm_pileup_fetch(t, keys.data(), counts.data());
+  mm_pileup_destroy(t);
+}
+// --pileup, per batch: the events of the primary aligned records (use) counted on the context that mapped the batch, appended to the file's accumulator;
+// above merge_pairs pairs the accumulator is replaced by its merge
+void pileup_add_batch(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, const BamFields& F, const BatchAlignment& al, size_t merge_pairs, PileupAcc& acc) {
+  const std::vector<uint8_t> use = pileup_use(F.flag, al.dist);
+  mm_pileup* t = nullptr;
+  ck(ctx, mm_pileup_events(ctx, reads, reference, (int64_t)use.size(), F.read.data(), F.strand.data(), F.contig.data(), al.dist.data(), al.first.data(), al.op_off.data(),
+                           al.ops.data(), use.data(), &t), "pileup events");
+  int64_t n = 0;
+  mm_pileup_sizes(t, &n);
+  std::vector<uint64_t> keys((size_t)n); std::vector<uint32_t> counts((size_t)n);
+  mm_pileup_fetch(t, keys.data(), counts.data());
+  mm_pileup_destroy(t);
+  std::lock_guard<std::mutex> lk(acc.m);
+  acc.keys.insert(acc.keys.end(), keys.begin(), keys.end()); acc.counts.insert(acc.counts.end(), counts.begin(), counts.end());
+  acc.add_intervals(use, F.contig, al.first, al.last);
+  if (acc.keys.size() > merge_pairs) pileup_merge_pairs(ctx, acc.keys, acc.counts);
+}
+// --pileup, after the last batch of a query file: one merge, one mm_pileup_finish against the reference of `ctx`, and the two files
+void pileup_write(mm_ctx* ctx, const mm_seqset* reference, PileupAcc& acc, const PileupOpts& po, const std::string& prefix, const std::vector<std::string>& cname,
+                  const std::vector<int>& clen) {
+  pileup_merge_pairs(ctx, acc.keys, acc.counts);
+  mm_pileup_result* r = nullptr;
+  ck(ctx, mm_pileup_finish(ctx, reference, (int64_t)acc.keys.size(), acc.keys.data(), acc.counts.data(), (int64_t)acc.iv_contig.size(), acc.iv_contig.data(), acc.iv_first.data(),
+                           acc.iv_last.data(), po.min_count, po.min_frac, &r), "pileup");
+  int64_t n_sites = 0, n_contigs = 0;
+  mm_pileup_result_sizes(r, &n_sites, &n_contigs);
+  std::vector<uint64_t> key((size_t)n_sites); std::vector<uint32_t> count((size_t)n_sites), depth((size_t)n_sites); std::vector<uint8_t> ref_byte((size_t)n_sites);
+  std::vector<int64_t> alignments((size_t)n_contigs), covered((size_t)n_contigs), sum_depth((size_t)n_contigs);
+  mm_pileup_result_fetch_sites(r, key.data(), count.data(), depth.data(), ref_byte.data());
+  mm_pileup_result_fetch_contigs(r, alignments.data(), covered.data(), sum_depth.data());
+  mm_pileup_result_destroy(r);
+  if (n_contigs != (int64_t)cname.size()) die("internal error: the pileup's contigs and the reference's differ in number");
+  const std::string texts[2] = {pileup_text(key, count, depth, ref_byte, cname), pileup_contigs_text(alignments, covered, sum_depth, cname, clen)};
+  const char* const suffix[2] = {".pileup", ".pileup.contigs"};
+  for (int f = 0; f < 2; ++f) {
+    FILE* out = fopen((prefix + suffix[f]).c_str(), "wb");
+    if (!out || fwrite(texts[f].data(), 1, texts[f].size(), out) != texts[f].size() || fclose(out) != 0) die("Error writing " + prefix + suffix[f]);
+  }
+}
+
 // The side outputs of one batch, in the two steps the order of a batch's device calls leaves: the alignment needs the mapping, which goes before the
 // lines are formatted; the BAM records need the formatted lines (their mapping qualities are read from the text).  One alignment serves all three files.
 struct BatchSideOutputs {
   const SideSet& on;
   BatchAlignment al;
+  PileupAcc* pile = nullptr;                                     // --pileup: the accumulator of the batch's query file
+  size_t pile_merge_pairs = 0;
 
   // while the mapping lives: d, first, last (and the runs, where .paf or .bam want them) fetched once -> the lines of .editDistances and .paf.
-  // The reads go here unless .bam needs them for SEQ.  Nothing happens without reads (no side file was asked for).
+  // The reads go here unless .bam needs them for SEQ or the pileup for its mismatched bases.  Nothing happens without reads (no side file was asked for).
   void from_mapping(mm_ctx* ctx, const mm_mapping* m, ReadsPtr& reads, const mm_seqset* reference, float pi, const std::vector<mm_map_record>& rec,
                     const std::vector<std::string>& names, const std::vector<int>& lens, const std::vector<int64_t>& off, const std::vector<std::string>& cname,
                     const std::vector<int>& clen, SideBytes& out) {
     if (!reads) return;
     const size_t n = rec.size();
-    if (on[SIDE_PAF] || on[SIDE_BAM]) {
+    if (on[SIDE_PAF] || on[SIDE_BAM] || pile) {
       mm_alignment* a = nullptr;
       ck(ctx, mm_mapping_align(ctx, m, reads.get(), reference, pi, &a), "alignments");
       int64_t n_jobs = 0, n_ops = 0;
@@ -58,10 +112,11 @@ struct BatchSideOutputs {
     }
     edit_distance_text(al.dist.data(), al.first.data(), al.last.data(), names, off, rec, cname, out[SIDE_EDIT]);
     if (on[SIDE_PAF]) paf_text(al, names, lens, off, rec, cname, clen, out[SIDE_PAF]);
-    if (!on[SIDE_BAM]) reads.reset();
+    if (!on[SIDE_BAM] && !pile) reads.reset();
   }
 
-  // once the lines are formatted: the batch's BAM records as BGZF members, encoded and deflated on the device; the reads, kept for this, go
+  // once the lines are formatted: the batch's BAM records as BGZF members, encoded and deflated on the device, and its pileup events (both go by
+  // bam_fields' primary record, which needs the lines); the reads, kept for this, go
   void from_text(mm_ctx* ctx, ReadsPtr& reads, const mm_seqset* reference, const std::vector<mm_map_record>& rec, const std::vector<std::string>& names,
                  const std::vector<int64_t>& off, const std::string& text, SideBytes& out) {
     if (!reads) return;
@@ -69,6 +124,8 @@ struct BatchSideOutputs {
     members.clear();
     if (!rec.empty()) {
       const BamFields F = bam_fields(al.dist, rec, names, off, text);
+      if (pile) pileup_add_batch(ctx, reads.get(), reference, F, al, pile_merge_pairs, *pile);
+      if (!on[SIDE_BAM]) { reads.reset(); return; }
       mm_bam* b = nullptr;
       ck(ctx, mm_bam_encode(ctx, reads.get(), reference, (int64_t)rec.size(), F.read.data(), F.strand.data(), F.contig.data(), al.dist.data(), al.first.data(),
                             al.op_off.data(), al.ops.data(), F.flag.data(), F.mapq.data(), F.name_off.data(), F.all_names.data(), 0, &b), "BAM records");

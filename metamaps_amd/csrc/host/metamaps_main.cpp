@@ -5,7 +5,8 @@
 // exclusively through the C ABI in include/metamaps_hip.h.  Host work here is what stays host work in the
 // reference too: argument parsing, FASTA/FASTQ(.gz) reading, text formatting, taxonomy bookkeeping.
 //
-//   metamaps mapDirectly [--all] [--compress-output] -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
+//   metamaps mapDirectly [--all] [--compress-output] [--edit-distance] [--paf] [--bam] [--pileup [--pileup-min-count N] [--pileup-min-frac F]]
+//                        -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
 //   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]] [--lca T] [--genes] [--min-identity T [--refit]]
 //
@@ -64,6 +65,16 @@
 // come from and deflates them where they lie (mm_bam_encode); the file is BGZF whatever --compress-output says and ends with the end-of-file block.
 // Every other file of the run is the file of the same run without the flag.  Refused wherever --edit-distance is.
 //
+// --pileup [--pileup-min-count N] [--pileup-min-frac F] (mapDirectly; not in the reference; implies --edit-distance; may be combined with --paf and --bam): also
+// PREFIX.pileup and PREFIX.pileup.contigs, what a column-by-column count over the PRIMARY records of PREFIX.bam gives (a read's aligned record with the largest
+// field 14, the first of equals: under --all a read counts once).  PREFIX.pileup: "contigID pos ref alt count depth" (tabs; pos 0-based) for every (position,
+// alt) that count >= N (an integer >= 1, default 3) and count >= F * depth (a decimal in [0, 1], default 0.2) reads support, alt one of A C G T N, - for a deleted
+// base, + for an insertion behind this base; depth counts the primary alignments that span the position, deleted bases included.  PREFIX.pileup.contigs:
+// "contigID length alignments covered sumDepth" for every contig with a primary alignment.  The device that mapped a batch counts its events from the traced
+// alignment (mm_pileup_events, csrc/mm_pileup_core.hpp); only what differs from the reference comes to the host, where the run's pairs are merged on the device
+// whenever they pass MM_PILEUP_MERGE_PAIRS; the first device finishes (mm_pileup_finish).  Both files are plain text.  Every other file of the run is the file of
+// the same run without the flag.  Refused wherever --edit-distance is; the two thresholds are refused without --pileup (host/pileup_out.hpp).
+//
 // --hpc (mapDirectly; not in the reference; minimap2's -H): homopolymer-compressed mapping.  Every maximal run of equal bytes of the reference and
 // of the reads — as hashed: upper-cased, IUPAC and N kept — becomes one byte, on the device (mm_seqset_hpc): the reference once per device behind
 // its upload, every read batch on the context that maps it.  The pipeline then runs unchanged on the compressed sequences: -m, the len < w and
@@ -119,7 +130,7 @@ Options parse(int argc, char** argv) {
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
     if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" ||
-        a == "--bam" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
+        a == "--bam" || a == "--pileup" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
@@ -131,6 +142,10 @@ Options parse(int argc, char** argv) {
                    "         line of PREFIX, the alignment traced on the device; not with --hpc, --shard-index, --stream-chunks\n"
                    "  --bam  (mapDirectly) implies --edit-distance and also writes PREFIX.bam (BGZF): one BAM record with the CIGAR, NM and MD for every aligned line of\n"
                    "         PREFIX, encoded and deflated on the device; may be combined with --paf; not with --hpc, --shard-index, --stream-chunks\n"
+                   "  --pileup [--pileup-min-count N] [--pileup-min-frac F]  (mapDirectly) implies --edit-distance and also writes PREFIX.pileup (contigID pos ref alt count depth for\n"
+                   "         every difference from the reference that at least N (default 3) primary alignments and F (default 0.2) of the depth support; alt - is a deleted\n"
+                   "         base, + an insertion behind the base) and PREFIX.pileup.contigs (contigID length alignments covered sumDepth), counted on the device; may be\n"
+                   "         combined with --paf and --bam; not with --hpc, --shard-index, --stream-chunks\n"
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
                    "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
                    "  --genes  (classify, mapDirectly --then-classify) gene-level analysis against DB_annotations.txt and DB_proteins.faa.annotated of the DB:\n"
@@ -225,9 +240,10 @@ int main(int argc, char** argv) {
   if ((identf_opts.on || identf_opts.refit) && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify")))
     die("--min-identity and --refit need classify or mapDirectly --then-classify");
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
-  if (o.v.count("paf") || o.v.count("bam")) o.v["edit-distance"] = "1";   // (--paf and --bam imply it, and inherit its refusals under their own names)
+  const PileupOpts pileup_opts = pileup_options(o);             // (validated before any work; MapRun reads them again)
+  if (o.v.count("paf") || o.v.count("bam") || pileup_opts.on) o.v["edit-distance"] = "1";   // (--paf, --bam and --pileup imply it, and inherit its refusals under their own names)
   if (o.v.count("edit-distance")) {                              // (refused before any device work)
-    const std::string flag = o.v.count("bam") ? "--bam" : o.v.count("paf") ? "--paf" : "--edit-distance";
+    const std::string flag = pileup_opts.on ? "--pileup" : o.v.count("bam") ? "--bam" : o.v.count("paf") ? "--paf" : "--edit-distance";
     if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reference does not stay on the device");
     if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");

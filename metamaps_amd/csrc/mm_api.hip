@@ -12,6 +12,7 @@
 #include "mm_ident.hpp"
 #include "mm_edit.hpp"
 #include "mm_bam.hpp"
+#include "mm_pileup.hpp"
 #include <chrono>
 #include <new>
 #include <rccl/rccl.h>
@@ -1061,6 +1062,77 @@ int mm_bam_fetch(const mm_bam* b, uint8_t* bgzf) {
   return MM_OK;
 }
 void mm_bam_destroy(mm_bam* b) { delete b; }
+
+struct mm_pileup { mm::PileupTable t; };                           // (host memory only, as mm_alignment)
+struct mm_pileup_result { mm::PileupResult r; };
+int mm_pileup_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
+                     const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, mm_pileup** out) {
+  if (!ctx || !reads || !reference || !out) return MM_ERR_ARG;
+  *out = nullptr;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(n_jobs >= 0 && n_jobs < ((int64_t)1 << 31), n_jobs < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_pileup_events: a negative number of jobs, or 2^31 or more");
+    MM_REQUIRE(n_jobs == 0 || (read && strand && contig && dist && first && op_off && use), MM_ERR_ARG, "mm_pileup_events: a null array");
+    std::unique_ptr<mm_pileup> t(new mm_pileup());
+    mm::pileup_events_run(ctx, reads, reference, mm::PileupIn{n_jobs, read, strand, contig, dist, first, op_off, ops, use}, &t->t);
+    *out = t.release();
+  });
+}
+int mm_pileup_merge(mm_ctx* ctx, int64_t n, const uint64_t* keys, const uint32_t* counts, mm_pileup** out) {
+  if (!ctx || !out) return MM_ERR_ARG;
+  *out = nullptr;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(n >= 0 && n < ((int64_t)1 << 32), n < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_pileup_merge: a negative number of pairs, or 2^32 or more");
+    MM_REQUIRE(n == 0 || (keys && counts), MM_ERR_ARG, "mm_pileup_merge: a null array");
+    std::unique_ptr<mm_pileup> t(new mm_pileup());
+    mm::pileup_merge_run(ctx, n, keys, counts, &t->t);
+    *out = t.release();
+  });
+}
+int mm_pileup_sizes(const mm_pileup* t, int64_t* n_pairs) {
+  if (!t || !n_pairs) return MM_ERR_ARG;
+  *n_pairs = (int64_t)t->t.keys.size();
+  return MM_OK;
+}
+int mm_pileup_fetch(const mm_pileup* t, uint64_t* keys, uint32_t* counts) {
+  if (!t || (!t->t.keys.empty() && (!keys || !counts))) return MM_ERR_ARG;
+  if (!t->t.keys.empty()) { memcpy(keys, t->t.keys.data(), t->t.keys.size() * sizeof(uint64_t)); memcpy(counts, t->t.counts.data(), t->t.counts.size() * sizeof(uint32_t)); }
+  return MM_OK;
+}
+void mm_pileup_destroy(mm_pileup* t) { delete t; }
+int mm_pileup_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* keys, const uint32_t* counts, int64_t n_iv, const int32_t* iv_contig,
+                     const int64_t* iv_first, const int64_t* iv_last, int64_t min_count, double min_frac, mm_pileup_result** out) {
+  if (!ctx || !reference || !out) return MM_ERR_ARG;
+  *out = nullptr;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(n >= 0 && n < ((int64_t)1 << 32) && n_iv >= 0 && n_iv < ((int64_t)1 << 32), n < 0 || n_iv < 0 ? MM_ERR_ARG : MM_ERR_LIMIT,
+               "mm_pileup_finish: a negative number of entries or intervals, or 2^32 or more");
+    MM_REQUIRE((n == 0 || (keys && counts)) && (n_iv == 0 || (iv_contig && iv_first && iv_last)), MM_ERR_ARG, "mm_pileup_finish: a null array");
+    std::unique_ptr<mm_pileup_result> r(new mm_pileup_result());
+    mm::pileup_finish_run(ctx, reference, mm::PileupFinishIn{n, keys, counts, n_iv, iv_contig, iv_first, iv_last, min_count, min_frac}, &r->r);
+    *out = r.release();
+  });
+}
+int mm_pileup_result_sizes(const mm_pileup_result* r, int64_t* n_sites, int64_t* n_contigs) {
+  if (!r || !n_sites || !n_contigs) return MM_ERR_ARG;
+  *n_sites = (int64_t)r->r.key.size(); *n_contigs = (int64_t)r->r.alignments.size();
+  return MM_OK;
+}
+int mm_pileup_result_fetch_sites(const mm_pileup_result* r, uint64_t* key, uint32_t* count, uint32_t* depth, uint8_t* ref_byte) {
+  if (!r || (!r->r.key.empty() && (!key || !count || !depth || !ref_byte))) return MM_ERR_ARG;
+  const size_t k = r->r.key.size();
+  if (k) { memcpy(key, r->r.key.data(), k * 8); memcpy(count, r->r.count.data(), k * 4); memcpy(depth, r->r.depth.data(), k * 4); memcpy(ref_byte, r->r.ref_byte.data(), k); }
+  return MM_OK;
+}
+int mm_pileup_result_fetch_contigs(const mm_pileup_result* r, int64_t* alignments, int64_t* covered, int64_t* sum_depth) {
+  if (!r || (!r->r.alignments.empty() && (!alignments || !covered || !sum_depth))) return MM_ERR_ARG;
+  const size_t k = r->r.alignments.size();
+  if (k) { memcpy(alignments, r->r.alignments.data(), k * 8); memcpy(covered, r->r.covered.data(), k * 8); memcpy(sum_depth, r->r.sum_depth.data(), k * 8); }
+  return MM_OK;
+}
+void mm_pileup_result_destroy(mm_pileup_result* r) { delete r; }
 
 // ---- communicator -------------------------------------------------------------------------------------
 int mm_comm_unique_id(char id[MM_COMM_ID_BYTES]) {

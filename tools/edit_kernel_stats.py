@@ -5,6 +5,10 @@ tools/_tmp/), which also holds the device's answers against the host's.
 Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes profiles/edit_kernel_stats.txt)
        python tools/edit_kernel_stats.py --align [n_reads]            (writes profiles/edit_trace_stats.txt)
        python tools/edit_kernel_stats.py --bam [n_reads]              (writes profiles/bam_encode_stats.txt)
+       python tools/edit_kernel_stats.py --pileup [n_reads]           (writes profiles/pileup_stats.txt)
+--pileup: the same batch through mm_mapping_align and mm_bam_encode once each, then twice through mm_pileup_events (every aligned best mapping contributes:
+mm_pileup_core.hpp, mm_pileup.hip) and once through mm_pileup_merge and mm_pileup_finish at the default thresholds: the stage times (the MM_PILEUP_TIMING
+lines), the wall time of each call with its copies, the pairs of the batch and the bytes fetched, beside that run's align and encode times.  One run is one run.
 --bam: the same batch through mm_mapping_align once and then twice through mm_bam_encode (the BAM records of these alignments, encoded and deflated on the
 device: mm_bam_core.hpp, mm_bam.hip): the upload / size / scan / write / deflate stage times (the MM_BAM_TIMING line), the wall time of the call with its
 copies, raw and BGZF bytes, beside the same run's mm_mapping_align time (the MM_EDIT_TIMING line) and the size PREFIX.paf would have.  The members are
@@ -155,7 +159,65 @@ def child_bam(n_reads):
     M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
 
 
+def child_pileup(n_reads):
+    from metamaps_amd import capi
+    ctx = capi.Context(0)
+    ref = ctx.synth_reference(seed=20260928, n_species=25, strains_per_species=4, genome_len=2_200_000, strain_divergence=0.02, genus_divergence=0.2)
+    w = capi.lib().mm_recommended_window(1e-3, K, PI, 1000, ref.total_bases)
+    idx = ctx.index(ref, K, w)
+    reads, _ = ctx.synth_reads(ref, seed=1000, n_reads=n_reads, read_len=READ_LEN, read_len_min=0, sub_rate=0.04, ins_rate=0.03, del_rate=0.05, frac_random=0.05, n_abundant=100)
+    M = ctx.map_batch(idx, reads, K, w, pi=PI)
+    M.keep_best(K)
+    off, rec = M.fetch()
+    n = len(rec)
+    print(f"{n_reads} reads of {READ_LEN} bases against {ref.total_bases} reference bases (k {K}, w {w}, pi {PI}): {n} best mappings", flush=True)
+    t0 = time.perf_counter()
+    dist, first, last, op_off, ops = ctx.mapping_align(M, reads, ref, PI)
+    dt = time.perf_counter() - t0
+    print(f"mm_mapping_align: {1e3 * dt:.1f} ms wall with the copies to the host; {int((dist >= 0).sum())} of {n} aligned, {len(ops)} runs ({4 * len(ops) / 1e6:.1f} MB)", flush=True)
+    strand = rec["strand"].astype(np.int32)
+    t0 = time.perf_counter()
+    data, n_rec, raw = ctx.bam_encode(reads, ref, read=rec["read"], strand=strand, contig=rec["ref_contig"], dist=dist, first=first, op_off=op_off, ops=ops,
+                                      flag=np.where(strand < 0, 0x10, 0), mapq=np.full(n, 60), names=[b"read%d" % r for r in rec["read"]])
+    dt = time.perf_counter() - t0
+    print(f"mm_bam_encode: {1e3 * dt:.1f} ms wall with the copies (the Python wrapper's own included), {n_rec} records, {raw / 1e6:.1f} MB raw, {len(data) / 1e6:.1f} MB BGZF", flush=True)
+    del data
+    args = dict(read=rec["read"], strand=strand, contig=rec["ref_contig"], dist=dist, first=first, op_off=op_off, ops=ops, use=np.ones(n, dtype=np.uint8))
+    for rep in range(2):
+        t0 = time.perf_counter()
+        keys, counts = ctx.pileup_events(reads, ref, **args)
+        dt = time.perf_counter() - t0
+        print(f"mm_pileup_events call {rep}: {1e3 * dt:.1f} ms wall with the copies, {len(keys)} pairs of {int(counts.sum())} events ({12 * len(keys) / 1e6:.1f} MB fetched, "
+              f"{12 * len(keys) / max(int((dist >= 0).sum()), 1):.0f} B per aligned read)", flush=True)
+    t0 = time.perf_counter()
+    mk, mc = ctx.pileup_merge(np.concatenate([keys, keys]), np.concatenate([counts, counts]))
+    dt = time.perf_counter() - t0
+    assert np.array_equal(mk, keys) and np.array_equal(mc, 2 * counts)
+    print(f"mm_pileup_merge of the table with itself: {1e3 * dt:.1f} ms wall with the copies, {2 * len(keys)} pairs in, {len(mk)} out", flush=True)
+    al = dist >= 0
+    t0 = time.perf_counter()
+    res = ctx.pileup_finish(ref, keys, counts, rec["ref_contig"][al], first[al], last[al])
+    dt = time.perf_counter() - t0
+    assert np.all(res["count"] <= res["depth"]) and int(res["alignments"].sum()) == int(al.sum()) and int(res["sum_depth"].sum()) == int((last[al] - first[al] + 1).sum())
+    print(f"mm_pileup_finish (min_count 3, min_frac 0.2): {1e3 * dt:.1f} ms wall with the copies, {len(res['key'])} of {len(keys)} entries kept, "
+          f"{int((res['alignments'] > 0).sum())} contigs with alignments, {int(res['covered'].sum())} positions covered, summed depth {int(res['sum_depth'].sum())}", flush=True)
+    M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--child-pileup":
+        return child_pileup(int(sys.argv[2]))
+    if len(sys.argv) > 1 and sys.argv[1] == "--pileup":
+        n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-pileup", str(n_reads)],
+                           env=dict(os.environ, MM_EDIT_TIMING="1", MM_BAM_TIMING="1", MM_PILEUP_TIMING="1"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1100)
+        text = f"tools/edit_kernel_stats.py --pileup {n_reads}: one batch of {n_reads} reads, best mappings only; one run\n" + p.stdout.decode()
+        print(text)
+        if p.returncode != 0:
+            sys.exit(p.returncode)
+        with open(os.path.join(ROOT, "profiles", "pileup_stats.txt"), "w") as f:
+            f.write(text)
+        return None
     if len(sys.argv) > 1 and sys.argv[1] == "--child-bam":
         return child_bam(int(sys.argv[2]))
     if len(sys.argv) > 1 and sys.argv[1] == "--bam":
