@@ -30,7 +30,7 @@ extern "C" {
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
                             *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances,
-                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_*, mm_pileup_* (additions to 6) */
+                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_*, mm_pileup_*, mm_vcf_* (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -54,6 +54,8 @@ typedef struct mm_alignment mm_alignment;  /* base-level alignments (CIGAR runs)
 typedef struct mm_bam mm_bam;          /* BGZF members holding BAM records of a batch of jobs, in host memory */
 typedef struct mm_pileup mm_pileup;    /* a table of (key, count) pileup events, unique keys ascending, in host memory */
 typedef struct mm_pileup_result mm_pileup_result;  /* the kept sites and the per-contig coverage of a run's pileup, in host memory */
+typedef struct mm_vcf mm_vcf;          /* a table of (w0, w1, count) alleles, unique keys ascending, in host memory */
+typedef struct mm_vcf_result mm_vcf_result;  /* the kept alleles of a run with their depths and reference windows, in host memory */
 typedef struct mm_hpc_map mm_hpc_map;  /* compressed -> raw coordinates of a homopolymer-compressed set, resident in HBM */
 
 /* ---- context -------------------------------------------------------------------------------- */
@@ -548,6 +550,38 @@ int mm_pileup_result_sizes(const mm_pileup_result* result, int64_t* n_sites, int
 int mm_pileup_result_fetch_sites(const mm_pileup_result* result, uint64_t* key /* [n_sites] */, uint32_t* count, uint32_t* depth, uint8_t* ref_byte);
 int mm_pileup_result_fetch_contigs(const mm_pileup_result* result, int64_t* alignments /* [n_contigs] */, int64_t* covered, int64_t* sum_depth);
 void mm_pileup_result_destroy(mm_pileup_result* result);
+
+/* The alleles of aligned jobs: SNVs, deletions and insertions that are canonical across reads, left-aligned and counted on the context's device (DESIGN.md
+ * section 1, "VCF"; the definition: csrc/mm_vcf_core.hpp).  A job contributes where use[i] != 0 and dist[i] >= 0.  Walking its runs from r = first, i = 0
+ * in the oriented read Q, with last its last contig position: an X run of n gives an SNV (contig, r + t, code(Q[i + t])) per base of A C G T; a D run of n
+ * with first < r and r + n <= last a deletion of n anchored at a = r - 1; an I run of n with first < r <= last whose bases are all A C G T an insertion of
+ * S = Q[i .. i + n) anchored at a = r - 1.  Indel runs at an end of the alignment are edges, not alleles.  An indel is shifted left, at most 256 times:
+ * a deletion while a > first and ref[a] == ref[a + n], an insertion while a > first and ref[a] == the last base of S, which then turns right by one; a
+ * reference byte outside A C G T stops the shift.  Key: w0 = contig << 35 | pos << 3 | code (code: the alt's 0-3, 5 deletion, 6 insertion; pos: the SNV's
+ * position or the shifted anchor), w1 = 0 (SNV), n (deletion), n << 48 | the bases 2 bits each, base j at bits 2j (insertion, n <= 24), n << 48
+ * (insertion, n > 24: symbolic).  Keys order by (w0, w1).
+ * mm_vcf_events returns the alleles of one call's jobs as (w0, w1, count) triples with unique keys in ascending order.  It applies mm_bam_encode's rules
+ * 1, 2, 4, 5 and 6 and rule 8 (an I or D run between other runs of 2^16 bases or more) to the jobs it uses: MM_ERR_ARG with "mm_vcf_events: job <index>:
+ * rule <number>: ..." for the lowest offender.  mm_vcf_merge takes any multiset of triples and returns the table with equal keys summed; a sum above
+ * 2^32 - 1 is MM_ERR_ARG.  mm_vcf_finish takes a merged table (keys ascending and unique, every key an allele on `reference`: MM_ERR_ARG otherwise) and the
+ * intervals of EVERY contributing alignment of the run, as mm_pileup_finish does: depth is the number of intervals that hold pos; an allele is kept where
+ * count >= min_count && (double)count >= min_frac * (double)depth, and carries MM_VCF_WINDOW reference bytes from pos on (0 beyond the contig's end).
+ * All arrays are the caller's; results live in host memory until destroyed; an error leaves *out NULL and launches nothing further. */
+#define MM_VCF_WINDOW 25
+int mm_vcf_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs,
+                  const int32_t* read, const int32_t* strand, const int32_t* contig, const int32_t* dist, const int64_t* first,
+                  const int64_t* op_off /* [n_jobs + 1] */, const uint32_t* ops, const uint8_t* use /* [n_jobs] */, mm_vcf** out);
+int mm_vcf_merge(mm_ctx* ctx, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, mm_vcf** out);
+int mm_vcf_sizes(const mm_vcf* table, int64_t* n_triples);
+int mm_vcf_fetch(const mm_vcf* table, uint64_t* w0 /* [n_triples] */, uint64_t* w1, uint32_t* counts);
+void mm_vcf_destroy(mm_vcf* table);
+int mm_vcf_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts,
+                  int64_t n_iv, const int32_t* iv_contig, const int64_t* iv_first, const int64_t* iv_last,
+                  int64_t min_count, double min_frac, mm_vcf_result** out);
+int mm_vcf_result_sizes(const mm_vcf_result* result, int64_t* n_alleles);
+int mm_vcf_result_fetch(const mm_vcf_result* result, uint64_t* w0 /* [n_alleles] */, uint64_t* w1, uint32_t* count, uint32_t* depth,
+                        uint8_t* window /* [MM_VCF_WINDOW * n_alleles] */);
+void mm_vcf_result_destroy(mm_vcf_result* result);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------------------------- */
 #define MM_COMM_ID_BYTES 128

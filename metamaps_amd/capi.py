@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmetamaps_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "metamaps_hip.h")
 
 COMM_ID_BYTES = 128
+VCF_WINDOW = 25                                                     # reference bytes a kept allele of mm_vcf_finish carries (the header's window constant)
 MM_ERR_ARG = -1
 MM_ERR_LIMIT = -5
 MM_ERR_DATA = -8
@@ -212,6 +213,15 @@ def lib() -> C.CDLL:
             "mm_pileup_result_fetch_sites": (C.c_int, [vp, vp, vp, vp, vp]),
             "mm_pileup_result_fetch_contigs": (C.c_int, [vp, vp, vp, vp]),
             "mm_pileup_result_destroy": (None, [vp]),
+            "mm_vcf_events": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "mm_vcf_merge": (C.c_int, [vp, i64, vp, vp, vp, vp]),
+            "mm_vcf_sizes": (C.c_int, [vp, vp]),
+            "mm_vcf_fetch": (C.c_int, [vp, vp, vp, vp]),
+            "mm_vcf_destroy": (None, [vp]),
+            "mm_vcf_finish": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, f64, vp]),
+            "mm_vcf_result_sizes": (C.c_int, [vp, vp]),
+            "mm_vcf_result_fetch": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+            "mm_vcf_result_destroy": (None, [vp]),
             "mm_comm_unique_id": (C.c_int, [C.c_char_p]),
             "mm_comm_init": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
             "mm_comm_allreduce_f64": (C.c_int, [vp, vp, i64]),
@@ -643,6 +653,63 @@ class Context:
             self.last_pileup_handle = h.value
             if h.value:
                 lib().mm_pileup_result_destroy(h)
+
+    def _vcf_table(self, status, handle):
+        """(w0, w1, counts) of an mm_vcf, which is destroyed; `handle` is NULL after an error"""
+        try:
+            self.check(status)
+            n = C.c_int64(-1)
+            assert lib().mm_vcf_sizes(handle, C.byref(n)) == 0
+            w0, w1, counts = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint32)
+            assert lib().mm_vcf_fetch(handle, _ptr(w0), _ptr(w1), _ptr(counts)) == 0
+            return w0, w1, counts
+        finally:
+            self.last_vcf_handle = handle.value                     # (what the call left in *out: None after a refusal)
+            if handle.value:
+                lib().mm_vcf_destroy(handle)
+
+    def vcf_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use):
+        """the left-aligned alleles of the jobs with use != 0 and dist >= 0 (mm_vcf_events): (w0, w1, counts), keys unique and ascending by (w0, w1);
+        w0 = contig << 35 | pos << 3 | code (the alt's 0-3, a deletion 5, an insertion 6), w1 = 0, the deletion's length, or the insertion's length << 48
+        | its bases (2 bits each, up to 24)"""
+        rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
+        fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
+        op, us = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(use, dtype=np.uint8)
+        n = len(rd)
+        assert all(len(x) == n for x in (sd, cg, ds, fs, us)) and len(oo) == n + 1
+        h = C.c_void_p(0xDEAD)                                      # (the call sets it, to NULL on an error)
+        st = lib().mm_vcf_events(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), C.byref(h))
+        return self._vcf_table(st, h)
+
+    def vcf_merge(self, w0, w1, counts):
+        """any (w0, w1, count) triples, unsorted, keys may repeat -> the table with equal keys summed (mm_vcf_merge)"""
+        a, b, cs = np.ascontiguousarray(w0, dtype=np.uint64), np.ascontiguousarray(w1, dtype=np.uint64), np.ascontiguousarray(counts, dtype=np.uint32)
+        assert len(a) == len(b) == len(cs)
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_vcf_merge(self.h, len(a), _ptr(a), _ptr(b), _ptr(cs), C.byref(h))
+        return self._vcf_table(st, h)
+
+    def vcf_finish(self, reference: "SeqSet", w0, w1, counts, iv_contig, iv_first, iv_last, min_count=3, min_frac=0.2):
+        """the kept alleles of a merged table, their depths from the intervals of all contributing alignments and their reference windows (mm_vcf_finish):
+        a dict with w0, w1, count, depth and window (25 bytes per allele)"""
+        a, b, cs = np.ascontiguousarray(w0, dtype=np.uint64), np.ascontiguousarray(w1, dtype=np.uint64), np.ascontiguousarray(counts, dtype=np.uint32)
+        ic = np.ascontiguousarray(iv_contig, dtype=np.int32)
+        i0, i1 = np.ascontiguousarray(iv_first, dtype=np.int64), np.ascontiguousarray(iv_last, dtype=np.int64)
+        assert len(a) == len(b) == len(cs) and len(ic) == len(i0) == len(i1)
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_vcf_finish(self.h, reference.h, len(a), _ptr(a), _ptr(b), _ptr(cs), len(ic), _ptr(ic), _ptr(i0), _ptr(i1), int(min_count), float(min_frac), C.byref(h))
+        try:
+            self.check(st)
+            n = C.c_int64(-1)
+            assert lib().mm_vcf_result_sizes(h, C.byref(n)) == 0
+            out = dict(w0=np.zeros(n.value, dtype=np.uint64), w1=np.zeros(n.value, dtype=np.uint64), count=np.zeros(n.value, dtype=np.uint32),
+                       depth=np.zeros(n.value, dtype=np.uint32), window=np.full((n.value, VCF_WINDOW), 0xEE, dtype=np.uint8))
+            assert lib().mm_vcf_result_fetch(h, _ptr(out["w0"]), _ptr(out["w1"]), _ptr(out["count"]), _ptr(out["depth"]), _ptr(out["window"])) == 0
+            return out
+        finally:
+            self.last_vcf_handle = h.value
+            if h.value:
+                lib().mm_vcf_result_destroy(h)
 
     # ---- communicator
     @staticmethod

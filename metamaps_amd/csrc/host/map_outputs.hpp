@@ -1,6 +1,7 @@
 // The side outputs of a batch of mapDirectly (the rows of side_files.hpp: PREFIX.editDistances, .paf, .bam) and the device calls they need, and the run's
-// pileup (PREFIX.pileup, .pileup.contigs), which every batch adds to.  The text and byte rules are in edit_dist.hpp, paf_out.hpp, bam_out.hpp and
-// pileup_out.hpp, which call nothing; everything of a batch runs on the context that mapped it, the pileup's last merge and finish on the first device.
+// pileup (PREFIX.pileup, .pileup.contigs) and alleles (PREFIX.vcf), which every batch adds to.  The text and byte rules are in edit_dist.hpp, paf_out.hpp,
+// bam_out.hpp, pileup_out.hpp and vcf_out.hpp, which call nothing; everything of a batch runs on the context that mapped it, the last merge and the finish of
+// the pileup and of the alleles on the first device.
 #pragma once
 #include "bam_out.hpp"
 #include "cli_device.hpp"
@@ -8,6 +9,7 @@
 #include "paf_out.hpp"
 #include "pileup_out.hpp"
 #include "side_files.hpp"
+#include "vcf_out.hpp"
 #include <memory>
 
 namespace {
@@ -82,6 +84,61 @@ void pileup_write(mm_ctx* ctx, const mm_seqset* reference, PileupAcc& acc, const
   }
 }
 
+// (w0, w1, count) triples and their sums through mm_vcf_merge, which leaves them unique and ascending
+void vcf_merge_triples(mm_ctx* ctx, VcfAcc& acc) {
+  mm_vcf* t = nullptr;
+  ck(ctx, mm_vcf_merge(ctx, (int64_t)acc.w0.size(), acc.w0.data(), acc.w1.data(), acc.counts.data(), &t), "vcf merge");
+  int64_t n = 0;
+  mm_vcf_sizes(t, &n);
+  acc.w0.resize((size_t)n); acc.w1.resize((size_t)n); acc.counts.resize((size_t)n);
+  mm_vcf_fetch(t, acc.w0.data(), acc.w1.data(), acc.counts.data());
+  mm_vcf_destroy(t);
+}
+// --vcf, per batch: the alleles of the primary aligned records (use) emitted, left-aligned and counted on the context that mapped the batch, appended to the
+// file's accumulator, which is replaced by its merge above merge_pairs triples; own_intervals: no pileup keeps the alignments' intervals, so this does
+void vcf_add_batch(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, const BamFields& F, const BatchAlignment& al, size_t merge_pairs, bool own_intervals, VcfAcc& acc) {
+  const std::vector<uint8_t> use = pileup_use(F.flag, al.dist);
+  mm_vcf* t = nullptr;
+  ck(ctx, mm_vcf_events(ctx, reads, reference, (int64_t)use.size(), F.read.data(), F.strand.data(), F.contig.data(), al.dist.data(), al.first.data(), al.op_off.data(), al.ops.data(),
+                        use.data(), &t), "vcf events");
+  int64_t n = 0;
+  mm_vcf_sizes(t, &n);
+  std::vector<uint64_t> w0((size_t)n), w1((size_t)n); std::vector<uint32_t> counts((size_t)n);
+  mm_vcf_fetch(t, w0.data(), w1.data(), counts.data());
+  mm_vcf_destroy(t);
+  std::lock_guard<std::mutex> lk(acc.m);
+  acc.w0.insert(acc.w0.end(), w0.begin(), w0.end()); acc.w1.insert(acc.w1.end(), w1.begin(), w1.end()); acc.counts.insert(acc.counts.end(), counts.begin(), counts.end());
+  if (own_intervals) acc.iv.add_intervals(use, F.contig, al.first, al.last);
+  if (acc.w0.size() > merge_pairs) vcf_merge_triples(ctx, acc);
+}
+// --vcf, after the last batch of a query file: one merge, one mm_vcf_finish against the reference of `ctx` over the intervals in `iv` (the file's pileup
+// accumulator, or the VCF's own), and the file
+void vcf_write(mm_ctx* ctx, const mm_seqset* reference, VcfAcc& acc, const PileupAcc& iv, const VcfOpts& vo, const std::string& prefix, const std::vector<std::string>& cname,
+               const std::vector<int>& clen) {
+  vcf_merge_triples(ctx, acc);
+  mm_vcf_result* r = nullptr;
+  ck(ctx, mm_vcf_finish(ctx, reference, (int64_t)acc.w0.size(), acc.w0.data(), acc.w1.data(), acc.counts.data(), (int64_t)iv.iv_contig.size(), iv.iv_contig.data(), iv.iv_first.data(),
+                        iv.iv_last.data(), vo.min_count, vo.min_frac, &r), "vcf");
+  int64_t n = 0;
+  mm_vcf_result_sizes(r, &n);
+  std::vector<uint64_t> w0((size_t)n), w1((size_t)n); std::vector<uint32_t> count((size_t)n), depth((size_t)n); std::vector<uint8_t> window((size_t)n * MM_VCF_WINDOW);
+  mm_vcf_result_fetch(r, w0.data(), w1.data(), count.data(), depth.data(), window.data());
+  mm_vcf_result_destroy(r);
+  const std::string text = vcf_header(cname, clen) + vcf_lines(w0, w1, count, depth, window, cname);
+  FILE* out = fopen((prefix + ".vcf").c_str(), "wb");
+  if (!out || fwrite(text.data(), 1, text.size(), out) != text.size() || fclose(out) != 0) die("Error writing " + prefix + ".vcf");
+}
+// the run's accumulators, one per query file, and what is written from them after the last batch (the pileup first: the VCF may read its intervals)
+struct RunVariants {
+  std::deque<PileupAcc> pile; std::deque<VcfAcc> vcf;
+  void resize(bool pileup_on, bool vcf_on, size_t n_files) { if (pileup_on) pile.resize(n_files); if (vcf_on) vcf.resize(n_files); }
+  void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const std::vector<std::string>& prefixes, const std::vector<std::string>& cname,
+             const std::vector<int>& clen) {
+    for (size_t fi = 0; fi < pile.size(); ++fi) pileup_write(ctx, reference, pile[fi], po, prefixes[fi], cname, clen);
+    for (size_t fi = 0; fi < vcf.size(); ++fi) vcf_write(ctx, reference, vcf[fi], pile.empty() ? vcf[fi].iv : pile[fi], vo, prefixes[fi], cname, clen);
+  }
+};
+
 // The side outputs of one batch, in the two steps the order of a batch's device calls leaves: the alignment needs the mapping, which goes before the
 // lines are formatted; the BAM records need the formatted lines (their mapping qualities are read from the text).  One alignment serves all three files.
 struct BatchSideOutputs {
@@ -89,15 +146,17 @@ struct BatchSideOutputs {
   BatchAlignment al;
   PileupAcc* pile = nullptr;                                     // --pileup: the accumulator of the batch's query file
   size_t pile_merge_pairs = 0;
+  VcfAcc* vcf = nullptr;                                         // --vcf: the accumulator of the batch's query file
+  size_t vcf_merge_pairs = 0;
 
   // while the mapping lives: d, first, last (and the runs, where .paf or .bam want them) fetched once -> the lines of .editDistances and .paf.
-  // The reads go here unless .bam needs them for SEQ or the pileup for its mismatched bases.  Nothing happens without reads (no side file was asked for).
+  // The reads go here unless .bam needs them for SEQ or the pileup or the VCF for their mismatched and inserted bases.  Nothing happens without reads (no side file was asked for).
   void from_mapping(mm_ctx* ctx, const mm_mapping* m, ReadsPtr& reads, const mm_seqset* reference, float pi, const std::vector<mm_map_record>& rec,
                     const std::vector<std::string>& names, const std::vector<int>& lens, const std::vector<int64_t>& off, const std::vector<std::string>& cname,
                     const std::vector<int>& clen, SideBytes& out) {
     if (!reads) return;
     const size_t n = rec.size();
-    if (on[SIDE_PAF] || on[SIDE_BAM] || pile) {
+    if (on[SIDE_PAF] || on[SIDE_BAM] || pile || vcf) {
       mm_alignment* a = nullptr;
       ck(ctx, mm_mapping_align(ctx, m, reads.get(), reference, pi, &a), "alignments");
       int64_t n_jobs = 0, n_ops = 0;
@@ -112,10 +171,10 @@ struct BatchSideOutputs {
     }
     edit_distance_text(al.dist.data(), al.first.data(), al.last.data(), names, off, rec, cname, out[SIDE_EDIT]);
     if (on[SIDE_PAF]) paf_text(al, names, lens, off, rec, cname, clen, out[SIDE_PAF]);
-    if (!on[SIDE_BAM] && !pile) reads.reset();
+    if (!on[SIDE_BAM] && !pile && !vcf) reads.reset();
   }
 
-  // once the lines are formatted: the batch's BAM records as BGZF members, encoded and deflated on the device, and its pileup events (both go by
+  // once the lines are formatted: the batch's BAM records as BGZF members, encoded and deflated on the device, and its pileup events and alleles (all go by
   // bam_fields' primary record, which needs the lines); the reads, kept for this, go
   void from_text(mm_ctx* ctx, ReadsPtr& reads, const mm_seqset* reference, const std::vector<mm_map_record>& rec, const std::vector<std::string>& names,
                  const std::vector<int64_t>& off, const std::string& text, SideBytes& out) {
@@ -125,6 +184,7 @@ struct BatchSideOutputs {
     if (!rec.empty()) {
       const BamFields F = bam_fields(al.dist, rec, names, off, text);
       if (pile) pileup_add_batch(ctx, reads.get(), reference, F, al, pile_merge_pairs, *pile);
+      if (vcf) vcf_add_batch(ctx, reads.get(), reference, F, al, vcf_merge_pairs, !pile, *vcf);
       if (!on[SIDE_BAM]) { reads.reset(); return; }
       mm_bam* b = nullptr;
       ck(ctx, mm_bam_encode(ctx, reads.get(), reference, (int64_t)rec.size(), F.read.data(), F.strand.data(), F.contig.data(), al.dist.data(), al.first.data(),

@@ -58,7 +58,8 @@ struct MapRun {
   const SideSet side = side_files_of(o);
   const bool edit = side[SIDE_EDIT];
   const PileupOpts pileup = pileup_options(o);                   // --pileup (implies --edit-distance): one accumulator per query file (pileup_out.hpp)
-  std::deque<PileupAcc> pile;
+  const VcfOpts vcf = vcf_options(o);                            // --vcf (implies --edit-distance): the same (vcf_out.hpp)
+  RunVariants var;
   std::string bgzf_head;                                         // what a BGZF side file starts with: the header of every PREFIX.bam as BGZF members (the contigs are the run's)
   std::vector<int> clen_raw; std::vector<mm_hpc_map*> hpc_map;
   using Chunk = IndexChunk;                                      // (index_files.hpp)
@@ -355,7 +356,7 @@ struct MapRun {
     }
     if (place != Place::Replicated && NC == 1 && !from_index && !maxMem) die("--stream-chunks / --shard-index need --maxmemory (the chunk rule of the reference, winSketch.hpp:274-329)");
     if (edit && place != Place::Replicated)
-      die(std::string(pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : side[SIDE_PAF] ? "--paf" : "--edit-distance")
+      die(std::string(vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : side[SIDE_PAF] ? "--paf" : "--edit-distance")
           + " needs the whole reference resident on every device, and this index does not fit one: run without it");
     for (auto& d : devs) d.idx.assign(NC, nullptr);
     thr_of.assign(NC, INT_MAX);
@@ -453,7 +454,7 @@ struct MapRun {
     const auto f1 = std::chrono::steady_clock::now();
     std::vector<mm_map_record> rec((size_t)dn->off.back());
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), rec.data(), (int64_t)rec.size()), "fetch");
-    BatchSideOutputs so{side, {}, pileup.on ? &pile[file] : nullptr, sw.pileup_merge_pairs};   // one alignment fetch serves .editDistances, .paf, .bam and the pileup
+    BatchSideOutputs so{side, {}, pileup.on ? &var.pile[file] : nullptr, sw.pileup_merge_pairs, vcf.on ? &var.vcf[file] : nullptr, sw.vcf_merge_pairs};   // one alignment for all of them
     so.from_mapping(ctx, m, reads, refset[dev], pi, rec, dn->names, dn->lens, dn->off, cname, clen, dn->side);
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
@@ -766,14 +767,14 @@ struct MapRun {
     build_resident_indexes();
     mp = mm_map_params{k, w, pi, minLen};
     for (auto& ch : chunks) chunk_base.push_back(ch.first);
-    if (pileup.on) pile.resize(prefixes.size());
+    var.resize(pileup.on, vcf.on, prefixes.size());
     if (side[SIDE_BAM]) bgzf_head = bam_header_members(ctx0, cname, clen);   // (before the workers take the first device's context)
     start_reader();
     if (prewarm.joinable()) prewarm.join();
     if (place != Place::Replicated) for (auto*& c : wctx) if (c) { mm_ctx_destroy(c); c = nullptr; }   // (the other modes drive one context per device)
     if (place == Place::Replicated) run_replicated(); else run_chunk_major();
     pc.lap("8 write");
-    for (size_t fi = 0; fi < pile.size(); ++fi) pileup_write(ctx0, refset[0], pile[fi], pileup, prefixes[fi], cname, clen);
+    var.write(ctx0, refset[0], pileup, vcf, prefixes, cname, clen);
     then_classify();
     if (!sw.full_teardown) { if (reader.th.joinable()) reader.th.join(); pc.report(); finish_fast(); }
     drop_refsets();

@@ -5,7 +5,7 @@
 // exclusively through the C ABI in include/metamaps_hip.h.  Host work here is what stays host work in the
 // reference too: argument parsing, FASTA/FASTQ(.gz) reading, text formatting, taxonomy bookkeeping.
 //
-//   metamaps mapDirectly [--all] [--compress-output] [--edit-distance] [--paf] [--bam] [--pileup [--pileup-min-count N] [--pileup-min-frac F]]
+//   metamaps mapDirectly [--all] [--compress-output] [--edit-distance] [--paf] [--bam] [--pileup [--pileup-min-count N] [--pileup-min-frac F]] [--vcf [--vcf-min-count N] [--vcf-min-frac F]]
 //                        -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
 //   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]] [--lca T] [--genes] [--min-identity T [--refit]]
@@ -75,6 +75,16 @@
 // whenever they pass MM_PILEUP_MERGE_PAIRS; the first device finishes (mm_pileup_finish).  Both files are plain text.  Every other file of the run is the file of
 // the same run without the flag.  Refused wherever --edit-distance is; the two thresholds are refused without --pileup (host/pileup_out.hpp).
 //
+// --vcf [--vcf-min-count N] [--vcf-min-frac F] (mapDirectly; not in the reference; implies --edit-distance; may be combined with --paf, --bam and --pileup): also
+// PREFIX.vcf (VCFv4.2, sites only), the alleles of the same primary records: an SNV per mismatched base of A C G T, a deletion or an insertion per I or D run
+// with an aligned base on both sides, every indel shifted left against the reference (at most 256 steps, not past the alignment's first base) so that equal
+// variants of different reads count together; indels of up to 24 bases are spelt out, longer ones are <DEL> and <INS> with SVLEN and END.  INFO carries DP
+// (the primary alignments that span POS) and AO (those that carry the allele); an allele is kept where AO >= N (default 3) and AO >= F * DP (default 0.2).
+// The device that mapped a batch emits, shifts and counts its alleles from the traced alignment (mm_vcf_events, csrc/mm_vcf_core.hpp); the run's triples are
+// merged on the device whenever they pass MM_VCF_MERGE_PAIRS; the first device finishes (mm_vcf_finish).  No genotypes, FORMAT columns, qualities or
+// multi-allelic records.  Plain text; an empty run writes the header.  Every other file of the run is the file of the same run without the flag.  Refused
+// wherever --edit-distance is; the two thresholds are refused without --vcf (host/vcf_out.hpp).
+//
 // --hpc (mapDirectly; not in the reference; minimap2's -H): homopolymer-compressed mapping.  Every maximal run of equal bytes of the reference and
 // of the reads — as hashed: upper-cased, IUPAC and N kept — becomes one byte, on the device (mm_seqset_hpc): the reference once per device behind
 // its upload, every read batch on the context that maps it.  The pipeline then runs unchanged on the compressed sequences: -m, the len < w and
@@ -130,7 +140,7 @@ Options parse(int argc, char** argv) {
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
     if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" ||
-        a == "--bam" || a == "--pileup" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
+        a == "--bam" || a == "--pileup" || a == "--vcf" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
@@ -146,6 +156,10 @@ Options parse(int argc, char** argv) {
                    "         every difference from the reference that at least N (default 3) primary alignments and F (default 0.2) of the depth support; alt - is a deleted\n"
                    "         base, + an insertion behind the base) and PREFIX.pileup.contigs (contigID length alignments covered sumDepth), counted on the device; may be\n"
                    "         combined with --paf and --bam; not with --hpc, --shard-index, --stream-chunks\n"
+                   "  --vcf [--vcf-min-count N] [--vcf-min-frac F]  (mapDirectly) implies --edit-distance and also writes PREFIX.vcf (VCFv4.2, sites only): SNVs, deletions and\n"
+                   "         insertions of the primary alignments, indels left-aligned on the device so that equal variants count together, with DP and AO; kept where at least N\n"
+                   "         (default 3) alignments and F (default 0.2) of the depth carry the allele; may be combined with --paf, --bam and --pileup; not with --hpc,\n"
+                   "         --shard-index, --stream-chunks\n"
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
                    "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
                    "  --genes  (classify, mapDirectly --then-classify) gene-level analysis against DB_annotations.txt and DB_proteins.faa.annotated of the DB:\n"
@@ -241,9 +255,10 @@ int main(int argc, char** argv) {
     die("--min-identity and --refit need classify or mapDirectly --then-classify");
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
   const PileupOpts pileup_opts = pileup_options(o);             // (validated before any work; MapRun reads them again)
-  if (o.v.count("paf") || o.v.count("bam") || pileup_opts.on) o.v["edit-distance"] = "1";   // (--paf, --bam and --pileup imply it, and inherit its refusals under their own names)
+  const VcfOpts vcf_opts = vcf_options(o);                      // (the same)
+  if (o.v.count("paf") || o.v.count("bam") || pileup_opts.on || vcf_opts.on) o.v["edit-distance"] = "1";   // (all four imply it, and inherit its refusals under their own names)
   if (o.v.count("edit-distance")) {                              // (refused before any device work)
-    const std::string flag = pileup_opts.on ? "--pileup" : o.v.count("bam") ? "--bam" : o.v.count("paf") ? "--paf" : "--edit-distance";
+    const std::string flag = vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup" : o.v.count("bam") ? "--bam" : o.v.count("paf") ? "--paf" : "--edit-distance";
     if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reference does not stay on the device");
     if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");

@@ -13,6 +13,7 @@
 #include "mm_edit.hpp"
 #include "mm_bam.hpp"
 #include "mm_pileup.hpp"
+#include "mm_vcf.hpp"
 #include <chrono>
 #include <new>
 #include <rccl/rccl.h>
@@ -1133,6 +1134,73 @@ int mm_pileup_result_fetch_contigs(const mm_pileup_result* r, int64_t* alignment
   return MM_OK;
 }
 void mm_pileup_result_destroy(mm_pileup_result* r) { delete r; }
+
+struct mm_vcf { mm::VcfTable t; };                                 // (host memory only, as mm_pileup)
+struct mm_vcf_result { mm::VcfResult r; };
+int mm_vcf_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
+                  const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, mm_vcf** out) {
+  if (!ctx || !reads || !reference || !out) return MM_ERR_ARG;
+  *out = nullptr;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(n_jobs >= 0 && n_jobs < ((int64_t)1 << 31), n_jobs < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_vcf_events: a negative number of jobs, or 2^31 or more");
+    MM_REQUIRE(n_jobs == 0 || (read && strand && contig && dist && first && op_off && use), MM_ERR_ARG, "mm_vcf_events: a null array");
+    std::unique_ptr<mm_vcf> t(new mm_vcf());
+    mm::vcf_events_run(ctx, reads, reference, mm::PileupIn{n_jobs, read, strand, contig, dist, first, op_off, ops, use}, &t->t);
+    *out = t.release();
+  });
+}
+int mm_vcf_merge(mm_ctx* ctx, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, mm_vcf** out) {
+  if (!ctx || !out) return MM_ERR_ARG;
+  *out = nullptr;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(n >= 0 && n < ((int64_t)1 << 32), n < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_vcf_merge: a negative number of triples, or 2^32 or more");
+    MM_REQUIRE(n == 0 || (w0 && w1 && counts), MM_ERR_ARG, "mm_vcf_merge: a null array");
+    std::unique_ptr<mm_vcf> t(new mm_vcf());
+    mm::vcf_merge_run(ctx, n, w0, w1, counts, &t->t);
+    *out = t.release();
+  });
+}
+int mm_vcf_sizes(const mm_vcf* t, int64_t* n_triples) {
+  if (!t || !n_triples) return MM_ERR_ARG;
+  *n_triples = (int64_t)t->t.w0.size();
+  return MM_OK;
+}
+int mm_vcf_fetch(const mm_vcf* t, uint64_t* w0, uint64_t* w1, uint32_t* counts) {
+  if (!t || (!t->t.w0.empty() && (!w0 || !w1 || !counts))) return MM_ERR_ARG;
+  const size_t k = t->t.w0.size();
+  if (k) { memcpy(w0, t->t.w0.data(), k * 8); memcpy(w1, t->t.w1.data(), k * 8); memcpy(counts, t->t.counts.data(), k * 4); }
+  return MM_OK;
+}
+void mm_vcf_destroy(mm_vcf* t) { delete t; }
+int mm_vcf_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, int64_t n_iv, const int32_t* iv_contig,
+                  const int64_t* iv_first, const int64_t* iv_last, int64_t min_count, double min_frac, mm_vcf_result** out) {
+  if (!ctx || !reference || !out) return MM_ERR_ARG;
+  *out = nullptr;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    MM_REQUIRE(n >= 0 && n < ((int64_t)1 << 32) && n_iv >= 0 && n_iv < ((int64_t)1 << 32), n < 0 || n_iv < 0 ? MM_ERR_ARG : MM_ERR_LIMIT,
+               "mm_vcf_finish: a negative number of entries or intervals, or 2^32 or more");
+    MM_REQUIRE((n == 0 || (w0 && w1 && counts)) && (n_iv == 0 || (iv_contig && iv_first && iv_last)), MM_ERR_ARG, "mm_vcf_finish: a null array");
+    std::unique_ptr<mm_vcf_result> r(new mm_vcf_result());
+    mm::vcf_finish_run(ctx, reference, mm::VcfFinishIn{n, w0, w1, counts, n_iv, iv_contig, iv_first, iv_last, min_count, min_frac}, &r->r);
+    *out = r.release();
+  });
+}
+int mm_vcf_result_sizes(const mm_vcf_result* r, int64_t* n_alleles) {
+  if (!r || !n_alleles) return MM_ERR_ARG;
+  *n_alleles = (int64_t)r->r.w0.size();
+  return MM_OK;
+}
+int mm_vcf_result_fetch(const mm_vcf_result* r, uint64_t* w0, uint64_t* w1, uint32_t* count, uint32_t* depth, uint8_t* window) {
+  if (!r || (!r->r.w0.empty() && (!w0 || !w1 || !count || !depth || !window))) return MM_ERR_ARG;
+  const size_t k = r->r.w0.size();
+  if (k) { memcpy(w0, r->r.w0.data(), k * 8); memcpy(w1, r->r.w1.data(), k * 8); memcpy(count, r->r.count.data(), k * 4); memcpy(depth, r->r.depth.data(), k * 4); }
+  if (k) memcpy(window, r->r.window.data(), r->r.window.size());
+  return MM_OK;
+}
+void mm_vcf_result_destroy(mm_vcf_result* r) { delete r; }
 
 // ---- communicator -------------------------------------------------------------------------------------
 int mm_comm_unique_id(char id[MM_COMM_ID_BYTES]) {

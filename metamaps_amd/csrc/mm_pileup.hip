@@ -13,33 +13,14 @@
 //            reference's byte; per contig the alignments, the summed lengths and the union's length (each interval adds what lies beyond the running
 //            maximum of the ends before it, an inclusive max-scan) with 64-bit vector atomics.
 // No kernel here waits for another workgroup; the only atomics are the error words' minimum and the per-contig sums.
+// The lane policy, the job arrays, the reduction (reduce_sorted, over one- or two-word keys) and the interval sort are shared with mm_vcf.hip: mm_pileup_dev.hpp.
 #include "mm_pileup.hpp"
 #include "mm_pileup_core.hpp"
+#include "mm_pileup_dev.hpp"
 #include "mm_edit_seq.hpp"
 #include "mm_prims.hpp"
 
 namespace mm {
-
-struct PileWaveLanes {                                            // one lane per thread of a 64-thread workgroup
-  static constexpr uint32_t W = 64;
-  __device__ uint32_t lane() const { return threadIdx.x; }
-  __device__ int64_t scan_add(int64_t v, int64_t* total) const {
-    long long x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const long long y = __shfl_up(x, o, 64); if ((int)threadIdx.x >= o) x += y; }
-    *total = (int64_t)__shfl(x, 63, 64);
-    return (int64_t)x - v;
-  }
-  __device__ uint64_t ballot(bool b) const { return (uint64_t)__ballot(b); }
-  __device__ int64_t pick(int64_t v, uint32_t l) const { return (int64_t)__shfl((long long)v, (int)l, 64); }
-};
-struct PileBytes { EditSeq s; int64_t g0; __device__ uint8_t byte(int64_t i) const { return s.byte(g0 + i); } };   // read coordinate -> the set's byte
-
-struct PileJobs {
-  int64_t n; const int32_t* read; const int32_t* strand; const int32_t* contig; const int32_t* dist; const int64_t* first;
-  const int64_t* op_off; const uint32_t* ops; const uint8_t* use;
-};
-constexpr unsigned long long PILE_NO_ERROR = ~0ull;
 
 __global__ void __launch_bounds__(64) pile_count_kernel(const int32_t* __restrict__ q_len, int64_t n_reads, const int32_t* __restrict__ r_len, int64_t n_contigs, PileJobs J,
                                                         int64_t job0, int64_t* __restrict__ counts, unsigned long long* __restrict__ err) {
@@ -68,17 +49,18 @@ __global__ void __launch_bounds__(64) pile_emit_kernel(EditSeq Q, const uint64_t
                 keys + off[job]);
 }
 
-// head[i]: sorted[i] starts a segment of equal keys; head[n] = 0 for the scan's total
-__global__ void __launch_bounds__(256) pile_heads_kernel(const uint64_t* __restrict__ sorted, int64_t n, uint8_t* __restrict__ head) {
+// head[i]: sorted[i] starts a segment of equal keys; head[n] = 0 for the scan's total.  A key is sorted[i], with `second` (mm_vcf.hip's two-word keys) the
+// pair (sorted[i], second[i]).
+__global__ void __launch_bounds__(256) pile_heads_kernel(const uint64_t* __restrict__ sorted, const uint64_t* __restrict__ second, int64_t n, uint8_t* __restrict__ head) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) head[i] = i == 0 || sorted[i] != sorted[i - 1] ? 1 : 0;
+  if (i < n) head[i] = i == 0 || sorted[i] != sorted[i - 1] || (second && second[i] != second[i - 1]) ? 1 : 0;
   else if (i == n) head[i] = 0;
 }
 // the segments' keys and first indexes; start[number of segments] = n
-__global__ void __launch_bounds__(256) pile_segments_kernel(const uint64_t* __restrict__ sorted, int64_t n, const uint8_t* __restrict__ head, const int64_t* __restrict__ pos,
-                                                            uint64_t* __restrict__ ukeys, int64_t* __restrict__ start) {
+__global__ void __launch_bounds__(256) pile_segments_kernel(const uint64_t* __restrict__ sorted, const uint64_t* __restrict__ second, int64_t n, const uint8_t* __restrict__ head,
+                                                            const int64_t* __restrict__ pos, uint64_t* __restrict__ ukeys, uint64_t* __restrict__ ukeys2, int64_t* __restrict__ start) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n && head[i]) { ukeys[pos[i]] = sorted[i]; start[pos[i]] = i; }
+  if (i < n && head[i]) { ukeys[pos[i]] = sorted[i]; if (second) ukeys2[pos[i]] = second[i]; start[pos[i]] = i; }
   else if (i == n) start[pos[n]] = n;
 }
 // csum == nullptr: a segment's count is its length; else the sum of its counts, csum their exclusive prefix sums; *over: some sum passes 2^32 - 1
@@ -134,24 +116,23 @@ __global__ void __launch_bounds__(256) pile_coverage_kernel(const uint64_t* __re
   if (gain) atomicAdd(&covered[c], gain);
 }
 
-namespace {
-constexpr int64_t PILE_GRID_MAX = (int64_t)1 << 30;               // workgroups per launch
-
-void pile_offsets_check(const int64_t* off, int64_t n) {
+void pile_offsets_check(const int64_t* off, int64_t n, const char* who) {
   bool ok = off[0] >= 0;
   for (int64_t i = 0; ok && i < n; ++i) ok = off[i] <= off[i + 1];
-  MM_REQUIRE(ok, MM_ERR_ARG, "mm_pileup_events: op_off does not start at 0 or more, or falls");
+  MM_REQUIRE(ok, MM_ERR_ARG, std::string(who) + ": op_off does not start at 0 or more, or falls");
 }
-int contig_bits(int64_t n_contigs) { return bits_for((uint64_t)std::max<int64_t>(n_contigs - 1, 0)); }
 
 // The segments of equal keys of sorted[0, n), n > 0: their keys, and their counts — the segments' lengths, or with d_counts (in the order of sorted,
-// n + 1 entries, the last one 0) the sums of their counts.  Returns false where a sum passes 2^32 - 1.
-bool reduce_sorted(DBuf<uint8_t>& tmp, const uint64_t* sorted, const uint32_t* d_counts, int64_t n, hipStream_t st, PileupTable* out) {
+// n + 1 entries, the last one 0) the sums of their counts.  With `second` a key is the pair (sorted[i], second[i]) and keys2 gets the second words.
+// Returns false where a sum passes 2^32 - 1.
+bool reduce_sorted(DBuf<uint8_t>& tmp, const uint64_t* sorted, const uint64_t* second, const uint32_t* d_counts, int64_t n, hipStream_t st, std::vector<uint64_t>* keys,
+                   std::vector<uint64_t>* keys2, std::vector<uint32_t>* counts) {
   const size_t k = (size_t)n;
-  DBuf<uint8_t> d_head(k + 1); DBuf<int64_t> d_pos(k + 1), d_start(k + 1); DBuf<uint64_t> d_ukeys(k), d_csum; DBuf<uint32_t> d_ucount(k); DBuf<unsigned long long> d_over(1);
-  pile_heads_kernel<<<dim3(flat_grid(n + 1)), dim3(256), 0, st>>>(sorted, n, d_head.p); MM_KERNEL_CHECK();
+  DBuf<uint8_t> d_head(k + 1); DBuf<int64_t> d_pos(k + 1), d_start(k + 1); DBuf<uint64_t> d_ukeys(k), d_ukeys2(second ? k : 1), d_csum; DBuf<uint32_t> d_ucount(k);
+  DBuf<unsigned long long> d_over(1);
+  pile_heads_kernel<<<dim3(flat_grid(n + 1)), dim3(256), 0, st>>>(sorted, second, n, d_head.p); MM_KERNEL_CHECK();
   exclusive_scan(tmp, d_head.p, d_pos.p, k + 1, st);
-  pile_segments_kernel<<<dim3(flat_grid(n + 1)), dim3(256), 0, st>>>(sorted, n, d_head.p, d_pos.p, d_ukeys.p, d_start.p); MM_KERNEL_CHECK();
+  pile_segments_kernel<<<dim3(flat_grid(n + 1)), dim3(256), 0, st>>>(sorted, second, n, d_head.p, d_pos.p, d_ukeys.p, d_ukeys2.p, d_start.p); MM_KERNEL_CHECK();
   int64_t n_seg = 0;
   d_pos.download(&n_seg, 1, st, k);
   MM_HIP(mm::stream_sync(st));
@@ -160,11 +141,24 @@ bool reduce_sorted(DBuf<uint8_t>& tmp, const uint64_t* sorted, const uint32_t* d
   pile_counts_kernel<<<dim3(flat_grid(n_seg)), dim3(256), 0, st>>>(d_start.p, n_seg, d_counts ? d_csum.p : nullptr, d_ucount.p, d_over.p); MM_KERNEL_CHECK();
   const unsigned long long over = d_over.to_host(st)[0];
   if (over != PILE_NO_ERROR) return false;
-  out->keys = d_ukeys.to_host(st, (size_t)n_seg);
-  out->counts = d_ucount.to_host(st, (size_t)n_seg);
+  *keys = d_ukeys.to_host(st, (size_t)n_seg);
+  if (second) *keys2 = d_ukeys2.to_host(st, (size_t)n_seg);
+  *counts = d_ucount.to_host(st, (size_t)n_seg);
   return true;
 }
-}  // namespace
+
+// The interval keys of n > 0 alignments (host arrays) on the device: starts ascending with end_of[i] the end that belongs to starts[i], ends ascending.
+void sorted_interval_keys(DBuf<uint8_t>& tmp, int64_t n, const int32_t* contig, const int64_t* first, const int64_t* last, int bits, hipStream_t st, DBuf<uint64_t>& starts,
+                          DBuf<uint64_t>& end_of, DBuf<uint64_t>& ends) {
+  const size_t v = (size_t)n;
+  DBuf<int32_t> d_c(v); DBuf<int64_t> d_f(v), d_l(v); DBuf<uint64_t> d_skey(v), d_ekey(v);
+  d_c.upload(contig, v, st); d_f.upload(first, v, st); d_l.upload(last, v, st);
+  pile_interval_keys_kernel<<<dim3(flat_grid(n)), dim3(256), 0, st>>>(d_c.p, d_f.p, d_l.p, n, d_skey.p, d_ekey.p); MM_KERNEL_CHECK();
+  sort_pairs(tmp, d_skey.p, starts.p, d_ekey.p, end_of.p, v, 0, bits, st);
+  sort_keys(tmp, d_ekey.p, ends.p, v, 0, bits, st);
+  MM_HIP(mm::stream_sync(st));                                     // (the buffers of this scope)
+}
+int contig_bits(int64_t n_contigs) { return bits_for((uint64_t)std::max<int64_t>(n_contigs - 1, 0)); }
 
 void pileup_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const PileupIn& in, PileupTable* out) {
   MM_REQUIRE(reads->frozen && ref->frozen, MM_ERR_STATE, "mm_pileup_events: a sequence set is not uploaded");
@@ -173,7 +167,7 @@ void pileup_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref
   out->keys.clear(); out->counts.clear();
   const int64_t n = in.n_jobs;
   if (n == 0) return;
-  pile_offsets_check(in.op_off, n);
+  pile_offsets_check(in.op_off, n, "mm_pileup_events");
   const size_t k = (size_t)n, n_ops = (size_t)in.op_off[n];
   MM_REQUIRE(n_ops == 0 || in.ops, MM_ERR_ARG, "mm_pileup_events: a null array");
   hipStream_t st = ctx->stream;
@@ -221,7 +215,7 @@ void pileup_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref
     sort_keys(tmp, d_keys.p, d_sorted.p, (size_t)total, 0, mmp::CONTIG_SHIFT + contig_bits(ref->count()), st);
     clk.stop(4);
     clk.start();
-    reduce_sorted(tmp, d_sorted.p, nullptr, total, st, out);
+    reduce_sorted(tmp, d_sorted.p, nullptr, nullptr, total, st, &out->keys, nullptr, &out->counts);
     clk.stop(5);
   }
   if (clk.on)
@@ -246,7 +240,7 @@ void pileup_merge_run(mm_ctx* ctx, int64_t n, const uint64_t* keys, const uint32
   sort_pairs(tmp, d_keys.p, d_sorted.p, d_counts.p, d_csorted.p, k, 0, bits_for(top), st);
   clk.stop(1);
   clk.start();
-  const bool ok = reduce_sorted(tmp, d_sorted.p, d_csorted.p, n, st, out);
+  const bool ok = reduce_sorted(tmp, d_sorted.p, nullptr, d_csorted.p, n, st, &out->keys, nullptr, &out->counts);
   clk.stop(2);
   if (!ok) { out->keys.clear(); out->counts.clear(); }
   MM_REQUIRE(ok, MM_ERR_ARG, "mm_pileup_merge: the counts of a key add up to more than 2^32 - 1");
@@ -285,15 +279,8 @@ void pileup_finish_run(mm_ctx* ctx, const mm_seqset* ref, const PileupFinishIn& 
   const int bits = 32 + contig_bits(ref->count());
 
   clk.start();
-  DBuf<uint64_t> d_skey(std::max<size_t>(v, 1)), d_ekey(std::max<size_t>(v, 1)), d_starts(std::max<size_t>(v, 1)), d_end_of(std::max<size_t>(v, 1)), d_ends(std::max<size_t>(v, 1));
-  if (v) {
-    DBuf<int32_t> d_c(v); DBuf<int64_t> d_f(v), d_l(v);
-    d_c.upload(in.iv_contig, v, st); d_f.upload(in.iv_first, v, st); d_l.upload(in.iv_last, v, st);
-    pile_interval_keys_kernel<<<dim3(flat_grid(in.n_iv)), dim3(256), 0, st>>>(d_c.p, d_f.p, d_l.p, in.n_iv, d_skey.p, d_ekey.p); MM_KERNEL_CHECK();
-    sort_pairs(tmp, d_skey.p, d_starts.p, d_ekey.p, d_end_of.p, v, 0, bits, st);
-    sort_keys(tmp, d_ekey.p, d_ends.p, v, 0, bits, st);
-    MM_HIP(mm::stream_sync(st));                                   // (the three upload buffers of this scope)
-  }
+  DBuf<uint64_t> d_starts(std::max<size_t>(v, 1)), d_end_of(std::max<size_t>(v, 1)), d_ends(std::max<size_t>(v, 1));
+  if (v) sorted_interval_keys(tmp, in.n_iv, in.iv_contig, in.iv_first, in.iv_last, bits, st, d_starts, d_end_of, d_ends);
   clk.stop(0);
 
   clk.start();

@@ -6,6 +6,10 @@ Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes pr
        python tools/edit_kernel_stats.py --align [n_reads]            (writes profiles/edit_trace_stats.txt)
        python tools/edit_kernel_stats.py --bam [n_reads]              (writes profiles/bam_encode_stats.txt)
        python tools/edit_kernel_stats.py --pileup [n_reads]           (writes profiles/pileup_stats.txt)
+       python tools/edit_kernel_stats.py --vcf [n_reads]              (writes profiles/vcf_stats.txt)
+--vcf: the run of --pileup, and behind it in the same process the same alignments twice through mm_vcf_events (mm_vcf_core.hpp, mm_vcf.hip) and once through
+mm_vcf_merge and mm_vcf_finish at the default thresholds: the MM_VCF_TIMING lines, the wall times, the events, triples and bytes fetched, beside that run's
+mm_pileup_events, which is the comparison.  One run is one run.
 --pileup: the same batch through mm_mapping_align and mm_bam_encode once each, then twice through mm_pileup_events (every aligned best mapping contributes:
 mm_pileup_core.hpp, mm_pileup.hip) and once through mm_pileup_merge and mm_pileup_finish at the default thresholds: the stage times (the MM_PILEUP_TIMING
 lines), the wall time of each call with its copies, the pairs of the batch and the bytes fetched, beside that run's align and encode times.  One run is one run.
@@ -159,7 +163,7 @@ def child_bam(n_reads):
     M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
 
 
-def child_pileup(n_reads):
+def child_pileup(n_reads, vcf=False):
     from metamaps_amd import capi
     ctx = capi.Context(0)
     ref = ctx.synth_reference(seed=20260928, n_species=25, strains_per_species=4, genome_len=2_200_000, strain_divergence=0.02, genus_divergence=0.2)
@@ -201,12 +205,45 @@ def child_pileup(n_reads):
     assert np.all(res["count"] <= res["depth"]) and int(res["alignments"].sum()) == int(al.sum()) and int(res["sum_depth"].sum()) == int((last[al] - first[al] + 1).sum())
     print(f"mm_pileup_finish (min_count 3, min_frac 0.2): {1e3 * dt:.1f} ms wall with the copies, {len(res['key'])} of {len(keys)} entries kept, "
           f"{int((res['alignments'] > 0).sum())} contigs with alignments, {int(res['covered'].sum())} positions covered, summed depth {int(res['sum_depth'].sum())}", flush=True)
+    if vcf:
+        del keys, counts, mk, mc, res
+        for rep in range(2):
+            t0 = time.perf_counter()
+            w0, w1, counts = ctx.vcf_events(reads, ref, **args)
+            dt = time.perf_counter() - t0
+            print(f"mm_vcf_events call {rep}: {1e3 * dt:.1f} ms wall with the copies, {len(w0)} triples of {int(counts.sum())} alleles ({20 * len(w0) / 1e6:.1f} MB fetched, "
+                  f"{20 * len(w0) / max(int((dist >= 0).sum()), 1):.0f} B per aligned read), {int(((w0 & 7) == 5).sum())} deletions, {int(((w0 & 7) == 6).sum())} insertions", flush=True)
+        t0 = time.perf_counter()
+        m0, m1, mc = ctx.vcf_merge(np.concatenate([w0, w0]), np.concatenate([w1, w1]), np.concatenate([counts, counts]))
+        dt = time.perf_counter() - t0
+        assert np.array_equal(m0, w0) and np.array_equal(m1, w1) and np.array_equal(mc, 2 * counts)
+        print(f"mm_vcf_merge of the table with itself: {1e3 * dt:.1f} ms wall with the copies, {2 * len(w0)} triples in, {len(m0)} out", flush=True)
+        del m0, m1, mc
+        t0 = time.perf_counter()
+        res = ctx.vcf_finish(ref, w0, w1, counts, rec["ref_contig"][al], first[al], last[al])
+        dt = time.perf_counter() - t0
+        print(f"mm_vcf_finish (min_count 3, min_frac 0.2): {1e3 * dt:.1f} ms wall with the copies, {len(res['w0'])} of {len(w0)} alleles kept, "
+              f"{int((res['count'] > res['depth']).sum())} of them with count > depth", flush=True)
     M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
 
 
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--child-pileup":
         return child_pileup(int(sys.argv[2]))
+    if len(sys.argv) > 1 and sys.argv[1] == "--child-vcf":
+        return child_pileup(int(sys.argv[2]), vcf=True)
+    if len(sys.argv) > 1 and sys.argv[1] == "--vcf":
+        n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-vcf", str(n_reads)],
+                           env=dict(os.environ, MM_EDIT_TIMING="1", MM_BAM_TIMING="1", MM_PILEUP_TIMING="1", MM_VCF_TIMING="1"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                           timeout=1100)
+        text = f"tools/edit_kernel_stats.py --vcf {n_reads}: one batch of {n_reads} reads, best mappings only; one run\n" + p.stdout.decode()
+        print(text)
+        if p.returncode != 0:
+            sys.exit(p.returncode)
+        with open(os.path.join(ROOT, "profiles", "vcf_stats.txt"), "w") as f:
+            f.write(text)
+        return None
     if len(sys.argv) > 1 and sys.argv[1] == "--pileup":
         n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-pileup", str(n_reads)],
