@@ -34,40 +34,59 @@ std::string bam_header_members(mm_ctx* ctx, const std::vector<std::string>& cnam
   return gz;
 }
 
-// (key, count) pairs and their sums through mm_pileup_merge, which leaves them unique and ascending
-void pileup_merge_pairs(mm_ctx* ctx, std::vector<uint64_t>& keys, std::vector<uint32_t>& counts) {
-  mm_pileup* t = nullptr;
-  ck(ctx, mm_pileup_merge(ctx, (int64_t)keys.size(), keys.data(), counts.data(), &t), "pileup merge");
-  int64_t n = 0;
-  mm_pileup_sizes(t, &n);
-  keys.resize((size_t)n); counts.resize((size_t)n);
-  mm_pileup_fetch(t, keys.data(), counts.data());
-  mm_pileup_destroy(t);
+// The device's calls of --pileup and of --vcf in one shape, for the three functions below: a pileup table has one-word keys, a VCF table two.
+// fetch: the rows behind a handle, which goes.
+struct PileupCalls {
+  using Table = mm_pileup;
+  static constexpr const char* events_what = "pileup events"; static constexpr const char* merge_what = "pileup merge";
+  static constexpr auto events = mm_pileup_events;
+  static int merge(mm_ctx* ctx, const VariantRows& v, Table** t) { return mm_pileup_merge(ctx, (int64_t)v.w0.size(), v.w0.data(), v.counts.data(), t); }
+  static void fetch(Table* t, VariantRows& v) {
+    int64_t n = 0;
+    mm_pileup_sizes(t, &n); v.resize((size_t)n, false); mm_pileup_fetch(t, v.w0.data(), v.counts.data()); mm_pileup_destroy(t);
+  }
+};
+struct VcfCalls {
+  using Table = mm_vcf;
+  static constexpr const char* events_what = "vcf events"; static constexpr const char* merge_what = "vcf merge";
+  static constexpr auto events = mm_vcf_events;
+  static int merge(mm_ctx* ctx, const VariantRows& v, Table** t) { return mm_vcf_merge(ctx, (int64_t)v.w0.size(), v.w0.data(), v.w1.data(), v.counts.data(), t); }
+  static void fetch(Table* t, VariantRows& v) {
+    int64_t n = 0;
+    mm_vcf_sizes(t, &n); v.resize((size_t)n, true); mm_vcf_fetch(t, v.w0.data(), v.w1.data(), v.counts.data()); mm_vcf_destroy(t);
+  }
+};
+// rows and their sums through the output's merge, which leaves them unique and ascending
+template <class C> void merge_rows(mm_ctx* ctx, VariantRows& v) {
+  typename C::Table* t = nullptr;
+  ck(ctx, C::merge(ctx, v, &t), C::merge_what);
+  C::fetch(t, v);
 }
-// --pileup, per batch: the events of the primary aligned records (use) counted on the context that mapped the batch, appended to the file's accumulator;
-// above merge_pairs pairs the accumulator is replaced by its merge
-void pileup_add_batch(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, const BamFields& F, const BatchAlignment& al, size_t merge_pairs, PileupAcc& acc) {
-  const std::vector<uint8_t> use = pileup_use(F.flag, al.dist);
-  mm_pileup* t = nullptr;
-  ck(ctx, mm_pileup_events(ctx, reads, reference, (int64_t)use.size(), F.read.data(), F.strand.data(), F.contig.data(), al.dist.data(), al.first.data(), al.op_off.data(),
-                           al.ops.data(), use.data(), &t), "pileup events");
-  int64_t n = 0;
-  mm_pileup_sizes(t, &n);
-  std::vector<uint64_t> keys((size_t)n); std::vector<uint32_t> counts((size_t)n);
-  mm_pileup_fetch(t, keys.data(), counts.data());
-  mm_pileup_destroy(t);
+// --pileup and --vcf, per batch: the events (alleles) of the primary aligned records (use) counted on the context that mapped the batch, appended to the
+// file's accumulator; above merge_pairs rows the accumulator is replaced by its merge
+template <class C> void add_batch(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, const BamFields& F, const BatchAlignment& al, const std::vector<uint8_t>& use,
+                                  size_t merge_pairs, VariantAcc& acc) {
+  typename C::Table* t = nullptr;
+  ck(ctx, C::events(ctx, reads, reference, (int64_t)use.size(), F.read.data(), F.strand.data(), F.contig.data(), al.dist.data(), al.first.data(), al.op_off.data(), al.ops.data(),
+                    use.data(), &t), C::events_what);
+  VariantRows got;
+  C::fetch(t, got);
   std::lock_guard<std::mutex> lk(acc.m);
-  acc.keys.insert(acc.keys.end(), keys.begin(), keys.end()); acc.counts.insert(acc.counts.end(), counts.begin(), counts.end());
-  acc.add_intervals(use, F.contig, al.first, al.last);
-  if (acc.keys.size() > merge_pairs) pileup_merge_pairs(ctx, acc.keys, acc.counts);
+  VariantRows& a = acc.rows;
+  a.w0.insert(a.w0.end(), got.w0.begin(), got.w0.end()); a.w1.insert(a.w1.end(), got.w1.begin(), got.w1.end()); a.counts.insert(a.counts.end(), got.counts.begin(), got.counts.end());
+  if (a.w0.size() > merge_pairs) merge_rows<C>(ctx, a);
+}
+void write_or_die(const std::string& path, const std::string& text) {
+  FILE* out = fopen(path.c_str(), "wb");
+  if (!out || fwrite(text.data(), 1, text.size(), out) != text.size() || fclose(out) != 0) die("Error writing " + path);
 }
 // --pileup, after the last batch of a query file: one merge, one mm_pileup_finish against the reference of `ctx`, and the two files
-void pileup_write(mm_ctx* ctx, const mm_seqset* reference, PileupAcc& acc, const PileupOpts& po, const std::string& prefix, const std::vector<std::string>& cname,
+void pileup_write(mm_ctx* ctx, const mm_seqset* reference, VariantRows& v, const Intervals& iv, const PileupOpts& po, const std::string& prefix, const std::vector<std::string>& cname,
                   const std::vector<int>& clen) {
-  pileup_merge_pairs(ctx, acc.keys, acc.counts);
+  merge_rows<PileupCalls>(ctx, v);
   mm_pileup_result* r = nullptr;
-  ck(ctx, mm_pileup_finish(ctx, reference, (int64_t)acc.keys.size(), acc.keys.data(), acc.counts.data(), (int64_t)acc.iv_contig.size(), acc.iv_contig.data(), acc.iv_first.data(),
-                           acc.iv_last.data(), po.min_count, po.min_frac, &r), "pileup");
+  ck(ctx, mm_pileup_finish(ctx, reference, (int64_t)v.w0.size(), v.w0.data(), v.counts.data(), (int64_t)iv.contig.size(), iv.contig.data(), iv.first.data(), iv.last.data(),
+                           po.min_count, po.min_frac, &r), "pileup");
   int64_t n_sites = 0, n_contigs = 0;
   mm_pileup_result_sizes(r, &n_sites, &n_contigs);
   std::vector<uint64_t> key((size_t)n_sites); std::vector<uint32_t> count((size_t)n_sites), depth((size_t)n_sites); std::vector<uint8_t> ref_byte((size_t)n_sites);
@@ -76,66 +95,36 @@ void pileup_write(mm_ctx* ctx, const mm_seqset* reference, PileupAcc& acc, const
   mm_pileup_result_fetch_contigs(r, alignments.data(), covered.data(), sum_depth.data());
   mm_pileup_result_destroy(r);
   if (n_contigs != (int64_t)cname.size()) die("internal error: the pileup's contigs and the reference's differ in number");
-  const std::string texts[2] = {pileup_text(key, count, depth, ref_byte, cname), pileup_contigs_text(alignments, covered, sum_depth, cname, clen)};
-  const char* const suffix[2] = {".pileup", ".pileup.contigs"};
-  for (int f = 0; f < 2; ++f) {
-    FILE* out = fopen((prefix + suffix[f]).c_str(), "wb");
-    if (!out || fwrite(texts[f].data(), 1, texts[f].size(), out) != texts[f].size() || fclose(out) != 0) die("Error writing " + prefix + suffix[f]);
-  }
+  write_or_die(prefix + ".pileup", pileup_text(key, count, depth, ref_byte, cname));
+  write_or_die(prefix + ".pileup.contigs", pileup_contigs_text(alignments, covered, sum_depth, cname, clen));
 }
-
-// (w0, w1, count) triples and their sums through mm_vcf_merge, which leaves them unique and ascending
-void vcf_merge_triples(mm_ctx* ctx, VcfAcc& acc) {
-  mm_vcf* t = nullptr;
-  ck(ctx, mm_vcf_merge(ctx, (int64_t)acc.w0.size(), acc.w0.data(), acc.w1.data(), acc.counts.data(), &t), "vcf merge");
-  int64_t n = 0;
-  mm_vcf_sizes(t, &n);
-  acc.w0.resize((size_t)n); acc.w1.resize((size_t)n); acc.counts.resize((size_t)n);
-  mm_vcf_fetch(t, acc.w0.data(), acc.w1.data(), acc.counts.data());
-  mm_vcf_destroy(t);
-}
-// --vcf, per batch: the alleles of the primary aligned records (use) emitted, left-aligned and counted on the context that mapped the batch, appended to the
-// file's accumulator, which is replaced by its merge above merge_pairs triples; own_intervals: no pileup keeps the alignments' intervals, so this does
-void vcf_add_batch(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, const BamFields& F, const BatchAlignment& al, size_t merge_pairs, bool own_intervals, VcfAcc& acc) {
-  const std::vector<uint8_t> use = pileup_use(F.flag, al.dist);
-  mm_vcf* t = nullptr;
-  ck(ctx, mm_vcf_events(ctx, reads, reference, (int64_t)use.size(), F.read.data(), F.strand.data(), F.contig.data(), al.dist.data(), al.first.data(), al.op_off.data(), al.ops.data(),
-                        use.data(), &t), "vcf events");
-  int64_t n = 0;
-  mm_vcf_sizes(t, &n);
-  std::vector<uint64_t> w0((size_t)n), w1((size_t)n); std::vector<uint32_t> counts((size_t)n);
-  mm_vcf_fetch(t, w0.data(), w1.data(), counts.data());
-  mm_vcf_destroy(t);
-  std::lock_guard<std::mutex> lk(acc.m);
-  acc.w0.insert(acc.w0.end(), w0.begin(), w0.end()); acc.w1.insert(acc.w1.end(), w1.begin(), w1.end()); acc.counts.insert(acc.counts.end(), counts.begin(), counts.end());
-  if (own_intervals) acc.iv.add_intervals(use, F.contig, al.first, al.last);
-  if (acc.w0.size() > merge_pairs) vcf_merge_triples(ctx, acc);
-}
-// --vcf, after the last batch of a query file: one merge, one mm_vcf_finish against the reference of `ctx` over the intervals in `iv` (the file's pileup
-// accumulator, or the VCF's own), and the file
-void vcf_write(mm_ctx* ctx, const mm_seqset* reference, VcfAcc& acc, const PileupAcc& iv, const VcfOpts& vo, const std::string& prefix, const std::vector<std::string>& cname,
+// --vcf, after the last batch of a query file: one merge, one mm_vcf_finish against the reference of `ctx` over the file's intervals, and the file
+void vcf_write(mm_ctx* ctx, const mm_seqset* reference, VariantRows& v, const Intervals& iv, const VcfOpts& vo, const std::string& prefix, const std::vector<std::string>& cname,
                const std::vector<int>& clen) {
-  vcf_merge_triples(ctx, acc);
+  merge_rows<VcfCalls>(ctx, v);
   mm_vcf_result* r = nullptr;
-  ck(ctx, mm_vcf_finish(ctx, reference, (int64_t)acc.w0.size(), acc.w0.data(), acc.w1.data(), acc.counts.data(), (int64_t)iv.iv_contig.size(), iv.iv_contig.data(), iv.iv_first.data(),
-                        iv.iv_last.data(), vo.min_count, vo.min_frac, &r), "vcf");
+  ck(ctx, mm_vcf_finish(ctx, reference, (int64_t)v.w0.size(), v.w0.data(), v.w1.data(), v.counts.data(), (int64_t)iv.contig.size(), iv.contig.data(), iv.first.data(), iv.last.data(),
+                        vo.min_count, vo.min_frac, &r), "vcf");
   int64_t n = 0;
   mm_vcf_result_sizes(r, &n);
   std::vector<uint64_t> w0((size_t)n), w1((size_t)n); std::vector<uint32_t> count((size_t)n), depth((size_t)n); std::vector<uint8_t> window((size_t)n * MM_VCF_WINDOW);
   mm_vcf_result_fetch(r, w0.data(), w1.data(), count.data(), depth.data(), window.data());
   mm_vcf_result_destroy(r);
-  const std::string text = vcf_header(cname, clen) + vcf_lines(w0, w1, count, depth, window, cname);
-  FILE* out = fopen((prefix + ".vcf").c_str(), "wb");
-  if (!out || fwrite(text.data(), 1, text.size(), out) != text.size() || fclose(out) != 0) die("Error writing " + prefix + ".vcf");
+  write_or_die(prefix + ".vcf", vcf_header(cname, clen) + vcf_lines(w0, w1, count, depth, window, cname));
 }
-// the run's accumulators, one per query file, and what is written from them after the last batch (the pileup first: the VCF may read its intervals)
+// the run's accumulators, one set per query file, and what is written from them after the last batch (every pileup before the first VCF)
 struct RunVariants {
-  std::deque<PileupAcc> pile; std::deque<VcfAcc> vcf;
-  void resize(bool pileup_on, bool vcf_on, size_t n_files) { if (pileup_on) pile.resize(n_files); if (vcf_on) vcf.resize(n_files); }
+  struct File { Intervals iv; VariantAcc pile, vcf; };
+  bool pileup_on = false, vcf_on = false;
+  std::deque<File> files;
+  void resize(bool pileup, bool vcf, size_t n_files) { pileup_on = pileup; vcf_on = vcf; if (pileup || vcf) files.resize(n_files); }
+  VariantAcc* pile(size_t f) { return pileup_on ? &files[f].pile : nullptr; }
+  VariantAcc* vcf(size_t f) { return vcf_on ? &files[f].vcf : nullptr; }
+  Intervals* intervals(size_t f) { return files.empty() ? nullptr : &files[f].iv; }
   void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const std::vector<std::string>& prefixes, const std::vector<std::string>& cname,
              const std::vector<int>& clen) {
-    for (size_t fi = 0; fi < pile.size(); ++fi) pileup_write(ctx, reference, pile[fi], po, prefixes[fi], cname, clen);
-    for (size_t fi = 0; fi < vcf.size(); ++fi) vcf_write(ctx, reference, vcf[fi], pile.empty() ? vcf[fi].iv : pile[fi], vo, prefixes[fi], cname, clen);
+    for (size_t fi = 0; pileup_on && fi < files.size(); ++fi) pileup_write(ctx, reference, files[fi].pile.rows, files[fi].iv, po, prefixes[fi], cname, clen);
+    for (size_t fi = 0; vcf_on && fi < files.size(); ++fi) vcf_write(ctx, reference, files[fi].vcf.rows, files[fi].iv, vo, prefixes[fi], cname, clen);
   }
 };
 
@@ -144,10 +133,11 @@ struct RunVariants {
 struct BatchSideOutputs {
   const SideSet& on;
   BatchAlignment al;
-  PileupAcc* pile = nullptr;                                     // --pileup: the accumulator of the batch's query file
+  VariantAcc* pile = nullptr;                                    // --pileup: the accumulator of the batch's query file
   size_t pile_merge_pairs = 0;
-  VcfAcc* vcf = nullptr;                                         // --vcf: the accumulator of the batch's query file
+  VariantAcc* vcf = nullptr;                                     // --vcf: the accumulator of the batch's query file
   size_t vcf_merge_pairs = 0;
+  Intervals* iv = nullptr;                                       // --pileup, --vcf: the contributing alignments of the batch's query file
 
   // while the mapping lives: d, first, last (and the runs, where .paf or .bam want them) fetched once -> the lines of .editDistances and .paf.
   // The reads go here unless .bam needs them for SEQ or the pileup or the VCF for their mismatched and inserted bases.  Nothing happens without reads (no side file was asked for).
@@ -183,8 +173,12 @@ struct BatchSideOutputs {
     members.clear();
     if (!rec.empty()) {
       const BamFields F = bam_fields(al.dist, rec, names, off, text);
-      if (pile) pileup_add_batch(ctx, reads.get(), reference, F, al, pile_merge_pairs, *pile);
-      if (vcf) vcf_add_batch(ctx, reads.get(), reference, F, al, vcf_merge_pairs, !pile, *vcf);
+      if (pile || vcf) {
+        const std::vector<uint8_t> use = pileup_use(F.flag, al.dist);
+        iv->add_intervals(use, F.contig, al.first, al.last);
+        if (pile) add_batch<PileupCalls>(ctx, reads.get(), reference, F, al, use, pile_merge_pairs, *pile);
+        if (vcf) add_batch<VcfCalls>(ctx, reads.get(), reference, F, al, use, vcf_merge_pairs, *vcf);
+      }
       if (!on[SIDE_BAM]) { reads.reset(); return; }
       mm_bam* b = nullptr;
       ck(ctx, mm_bam_encode(ctx, reads.get(), reference, (int64_t)rec.size(), F.read.data(), F.strand.data(), F.contig.data(), al.dist.data(), al.first.data(),

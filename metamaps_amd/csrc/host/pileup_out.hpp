@@ -50,13 +50,20 @@ std::vector<uint8_t> pileup_use(const std::vector<uint16_t>& flag, const std::ve
   return use;
 }
 
-// what the batches of one query file leave behind for its pileup
-struct PileupAcc {
+// (key, count) rows of the pileup (w1 empty) or of the VCF (w1: the keys' second words), as they come from the device and go back to it
+struct VariantRows {
+  std::vector<uint64_t> w0, w1; std::vector<uint32_t> counts;
+  void resize(size_t n, bool two_words) { w0.resize(n); if (two_words) w1.resize(n); counts.resize(n); }
+};
+// what the batches of one query file leave behind for its pileup or for its VCF: rows, merged now and then (keys may repeat)
+struct VariantAcc { std::mutex m; VariantRows rows; };
+// every contributing alignment of a query file's run, once for the pileup and the VCF
+struct Intervals {
   std::mutex m;
-  std::vector<uint64_t> keys; std::vector<uint32_t> counts;      // pairs, merged now and then: keys may repeat
-  std::vector<int32_t> iv_contig; std::vector<int64_t> iv_first, iv_last;   // every contributing alignment of the run
-  void add_intervals(const std::vector<uint8_t>& use, const std::vector<int32_t>& contig, const std::vector<int64_t>& first, const std::vector<int64_t>& last) {
-    for (size_t i = 0; i < use.size(); ++i) if (use[i]) { iv_contig.push_back(contig[i]); iv_first.push_back(first[i]); iv_last.push_back(last[i]); }
+  std::vector<int32_t> contig; std::vector<int64_t> first, last;
+  void add_intervals(const std::vector<uint8_t>& use, const std::vector<int32_t>& c, const std::vector<int64_t>& f, const std::vector<int64_t>& l) {
+    std::lock_guard<std::mutex> lk(m);
+    for (size_t i = 0; i < use.size(); ++i) if (use[i]) { contig.push_back(c[i]); first.push_back(f[i]); last.push_back(l[i]); }
   }
 };
 

@@ -12,7 +12,7 @@
 //              Kept: count >= N (default 3) and count >= F * depth (default 0.2); mm_vcf_finish decides, on the first device, and hands back the
 //              reference bytes ref[pos .. pos + 25) that REF is printed from.
 //   accumulator  a batch's (w0, w1, count) triples are appended under a mutex, 20 bytes each; above MM_VCF_MERGE_PAIRS triples (64 * 2^20) they are replaced by
-//              their mm_vcf_merge (map_outputs.hpp).  The intervals of the contributing alignments are the pileup's where --pileup runs too: one copy.
+//              their mm_vcf_merge (map_outputs.hpp).  The accumulator and the intervals of the contributing alignments are pileup_out.hpp's: one copy of the intervals serves both.
 // Text, arrays and the option values only (the key's fields: mm_vcf_core.hpp, plain host code here): nothing here calls the device.
 #pragma once
 #include "../mm_vcf_core.hpp"
@@ -43,13 +43,6 @@ VcfOpts vcf_options(const Options& o) {
   }
   return p;
 }
-
-// what the batches of one query file leave behind for its VCF; iv: the intervals of every contributing alignment, kept here only where no pileup keeps them
-struct VcfAcc {
-  std::mutex m;
-  std::vector<uint64_t> w0, w1; std::vector<uint32_t> counts;    // triples, merged now and then: keys may repeat
-  PileupAcc iv;
-};
 
 std::string vcf_header(const std::vector<std::string>& cname, const std::vector<int>& clen) {
   std::string t = "##fileformat=VCFv4.2\n##source=metamaps mapDirectly --vcf\n";

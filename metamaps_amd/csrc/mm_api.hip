@@ -55,6 +55,39 @@ int guarded(mm_ctx* ctx, F&& f) {
   catch (const std::bad_alloc&) { if (ctx) ctx->err = "host allocation failed"; return MM_ERR_NOMEM; }
   catch (const std::exception& e) { if (ctx) ctx->err = e.what(); return MM_ERR_DEVICE; }
 }
+// An entry point that hands back a new object of the context's device: fill(object) makes it, and *out stays NULL unless fill returns.
+template <typename H, typename F>
+int created(mm_ctx* ctx, H** out, F&& fill) {
+  *out = nullptr;
+  return guarded(ctx, [&] {
+    MM_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<H> h(new H());
+    fill(*h);
+    *out = h.release();
+  });
+}
+// what the entry points over aligned jobs, over key tables and over their finishes ask of their counts and arrays (who: the entry point's name)
+void require_jobs(const char* who, int64_t n_jobs, bool arrays) {
+  MM_REQUIRE(n_jobs >= 0 && n_jobs < ((int64_t)1 << 31), n_jobs < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, std::string(who) + ": a negative number of jobs, or 2^31 or more");
+  MM_REQUIRE(n_jobs == 0 || arrays, MM_ERR_ARG, std::string(who) + ": a null array");
+}
+void require_rows(const char* who, const char* rows, int64_t n, bool arrays) {
+  MM_REQUIRE(n >= 0 && n < ((int64_t)1 << 32), n < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, std::string(who) + ": a negative number of " + rows + ", or 2^32 or more");
+  MM_REQUIRE(n == 0 || arrays, MM_ERR_ARG, std::string(who) + ": a null array");
+}
+void require_finish(const char* who, int64_t n, int64_t n_iv, bool rows, bool intervals) {
+  MM_REQUIRE(n >= 0 && n < ((int64_t)1 << 32) && n_iv >= 0 && n_iv < ((int64_t)1 << 32), n < 0 || n_iv < 0 ? MM_ERR_ARG : MM_ERR_LIMIT,
+             std::string(who) + ": a negative number of entries or intervals, or 2^32 or more");
+  MM_REQUIRE((n == 0 || rows) && (n_iv == 0 || intervals), MM_ERR_ARG, std::string(who) + ": a null array");
+}
+// the rows of a key table (mm_pileup, mm_vcf) into the caller's arrays; w1: null for a table of one-word keys
+int table_fetch(const mm::KeyTable& t, uint64_t* w0, uint64_t* w1, uint32_t* counts) {
+  const size_t k = t.w0.size();
+  if (k && (!w0 || !counts || (!t.w1.empty() && !w1))) return MM_ERR_ARG;
+  if (k) { memcpy(w0, t.w0.data(), k * 8); memcpy(counts, t.counts.data(), k * 4); }
+  if (k && !t.w1.empty()) memcpy(w1, t.w1.data(), k * 8);
+  return MM_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1042,14 +1075,9 @@ int mm_bam_encode(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* referenc
                   const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint16_t* flag, const uint8_t* mapq,
                   const int64_t* name_off, const char* names, int64_t group_bytes, mm_bam** out) {
   if (!ctx || !reads || !reference || !out) return MM_ERR_ARG;
-  *out = nullptr;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    MM_REQUIRE(n_jobs >= 0 && n_jobs < ((int64_t)1 << 31), n_jobs < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_bam_encode: a negative number of jobs, or 2^31 or more");
-    MM_REQUIRE(n_jobs == 0 || (read && strand && contig && dist && first && op_off && flag && mapq && name_off), MM_ERR_ARG, "mm_bam_encode: a null array");
-    std::unique_ptr<mm_bam> b(new mm_bam());
-    mm::bam_encode_run(ctx, reads, reference, mm::BamIn{n_jobs, read, strand, contig, dist, first, op_off, ops, flag, mapq, name_off, names}, group_bytes, &b->b);
-    *out = b.release();
+  return created(ctx, out, [&](mm_bam& b) {
+    require_jobs("mm_bam_encode", n_jobs, read && strand && contig && dist && first && op_off && flag && mapq && name_off);
+    mm::bam_encode_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, mm::BamColumns{flag, mapq, name_off, names}, group_bytes, &b.b);
   });
 }
 int mm_bam_sizes(const mm_bam* b, int64_t* n_records, int64_t* raw_bytes, int64_t* bgzf_bytes) {
@@ -1064,67 +1092,47 @@ int mm_bam_fetch(const mm_bam* b, uint8_t* bgzf) {
 }
 void mm_bam_destroy(mm_bam* b) { delete b; }
 
-struct mm_pileup { mm::PileupTable t; };                           // (host memory only, as mm_alignment)
+struct mm_pileup { mm::KeyTable t; };                              // (host memory only, as mm_alignment; one-word keys: t.w1 stays empty)
 struct mm_pileup_result { mm::PileupResult r; };
 int mm_pileup_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
                      const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, mm_pileup** out) {
   if (!ctx || !reads || !reference || !out) return MM_ERR_ARG;
-  *out = nullptr;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    MM_REQUIRE(n_jobs >= 0 && n_jobs < ((int64_t)1 << 31), n_jobs < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_pileup_events: a negative number of jobs, or 2^31 or more");
-    MM_REQUIRE(n_jobs == 0 || (read && strand && contig && dist && first && op_off && use), MM_ERR_ARG, "mm_pileup_events: a null array");
-    std::unique_ptr<mm_pileup> t(new mm_pileup());
-    mm::pileup_events_run(ctx, reads, reference, mm::PileupIn{n_jobs, read, strand, contig, dist, first, op_off, ops, use}, &t->t);
-    *out = t.release();
+  return created(ctx, out, [&](mm_pileup& t) {
+    require_jobs("mm_pileup_events", n_jobs, read && strand && contig && dist && first && op_off && use);
+    mm::pileup_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, &t.t);
   });
 }
 int mm_pileup_merge(mm_ctx* ctx, int64_t n, const uint64_t* keys, const uint32_t* counts, mm_pileup** out) {
   if (!ctx || !out) return MM_ERR_ARG;
-  *out = nullptr;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    MM_REQUIRE(n >= 0 && n < ((int64_t)1 << 32), n < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_pileup_merge: a negative number of pairs, or 2^32 or more");
-    MM_REQUIRE(n == 0 || (keys && counts), MM_ERR_ARG, "mm_pileup_merge: a null array");
-    std::unique_ptr<mm_pileup> t(new mm_pileup());
-    mm::pileup_merge_run(ctx, n, keys, counts, &t->t);
-    *out = t.release();
+  return created(ctx, out, [&](mm_pileup& t) {
+    require_rows("mm_pileup_merge", "pairs", n, keys && counts);
+    mm::merge_run(ctx, n, keys, nullptr, counts, "mm_pileup_merge", "MM_PILEUP_TIMING", &t.t);
   });
 }
 int mm_pileup_sizes(const mm_pileup* t, int64_t* n_pairs) {
   if (!t || !n_pairs) return MM_ERR_ARG;
-  *n_pairs = (int64_t)t->t.keys.size();
+  *n_pairs = (int64_t)t->t.w0.size();
   return MM_OK;
 }
-int mm_pileup_fetch(const mm_pileup* t, uint64_t* keys, uint32_t* counts) {
-  if (!t || (!t->t.keys.empty() && (!keys || !counts))) return MM_ERR_ARG;
-  if (!t->t.keys.empty()) { memcpy(keys, t->t.keys.data(), t->t.keys.size() * sizeof(uint64_t)); memcpy(counts, t->t.counts.data(), t->t.counts.size() * sizeof(uint32_t)); }
-  return MM_OK;
-}
+int mm_pileup_fetch(const mm_pileup* t, uint64_t* keys, uint32_t* counts) { return t ? table_fetch(t->t, keys, nullptr, counts) : MM_ERR_ARG; }
 void mm_pileup_destroy(mm_pileup* t) { delete t; }
 int mm_pileup_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* keys, const uint32_t* counts, int64_t n_iv, const int32_t* iv_contig,
                      const int64_t* iv_first, const int64_t* iv_last, int64_t min_count, double min_frac, mm_pileup_result** out) {
   if (!ctx || !reference || !out) return MM_ERR_ARG;
-  *out = nullptr;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    MM_REQUIRE(n >= 0 && n < ((int64_t)1 << 32) && n_iv >= 0 && n_iv < ((int64_t)1 << 32), n < 0 || n_iv < 0 ? MM_ERR_ARG : MM_ERR_LIMIT,
-               "mm_pileup_finish: a negative number of entries or intervals, or 2^32 or more");
-    MM_REQUIRE((n == 0 || (keys && counts)) && (n_iv == 0 || (iv_contig && iv_first && iv_last)), MM_ERR_ARG, "mm_pileup_finish: a null array");
-    std::unique_ptr<mm_pileup_result> r(new mm_pileup_result());
-    mm::pileup_finish_run(ctx, reference, mm::PileupFinishIn{n, keys, counts, n_iv, iv_contig, iv_first, iv_last, min_count, min_frac}, &r->r);
-    *out = r.release();
+  return created(ctx, out, [&](mm_pileup_result& r) {
+    require_finish("mm_pileup_finish", n, n_iv, keys && counts, iv_contig && iv_first && iv_last);
+    mm::pileup_finish_run(ctx, reference, mm::FinishIn{n, keys, nullptr, counts, n_iv, iv_contig, iv_first, iv_last, min_count, min_frac}, &r.r);
   });
 }
 int mm_pileup_result_sizes(const mm_pileup_result* r, int64_t* n_sites, int64_t* n_contigs) {
   if (!r || !n_sites || !n_contigs) return MM_ERR_ARG;
-  *n_sites = (int64_t)r->r.key.size(); *n_contigs = (int64_t)r->r.alignments.size();
+  *n_sites = (int64_t)r->r.w0.size(); *n_contigs = (int64_t)r->r.alignments.size();
   return MM_OK;
 }
 int mm_pileup_result_fetch_sites(const mm_pileup_result* r, uint64_t* key, uint32_t* count, uint32_t* depth, uint8_t* ref_byte) {
-  if (!r || (!r->r.key.empty() && (!key || !count || !depth || !ref_byte))) return MM_ERR_ARG;
-  const size_t k = r->r.key.size();
-  if (k) { memcpy(key, r->r.key.data(), k * 8); memcpy(count, r->r.count.data(), k * 4); memcpy(depth, r->r.depth.data(), k * 4); memcpy(ref_byte, r->r.ref_byte.data(), k); }
+  if (!r || (!r->r.w0.empty() && (!key || !count || !depth || !ref_byte))) return MM_ERR_ARG;
+  const size_t k = r->r.w0.size();
+  if (k) { memcpy(key, r->r.w0.data(), k * 8); memcpy(count, r->r.count.data(), k * 4); memcpy(depth, r->r.depth.data(), k * 4); memcpy(ref_byte, r->r.ref_byte.data(), k); }
   return MM_OK;
 }
 int mm_pileup_result_fetch_contigs(const mm_pileup_result* r, int64_t* alignments, int64_t* covered, int64_t* sum_depth) {
@@ -1135,31 +1143,21 @@ int mm_pileup_result_fetch_contigs(const mm_pileup_result* r, int64_t* alignment
 }
 void mm_pileup_result_destroy(mm_pileup_result* r) { delete r; }
 
-struct mm_vcf { mm::VcfTable t; };                                 // (host memory only, as mm_pileup)
+struct mm_vcf { mm::KeyTable t; };                                 // (host memory only, as mm_pileup; two-word keys)
 struct mm_vcf_result { mm::VcfResult r; };
 int mm_vcf_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
                   const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, mm_vcf** out) {
   if (!ctx || !reads || !reference || !out) return MM_ERR_ARG;
-  *out = nullptr;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    MM_REQUIRE(n_jobs >= 0 && n_jobs < ((int64_t)1 << 31), n_jobs < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_vcf_events: a negative number of jobs, or 2^31 or more");
-    MM_REQUIRE(n_jobs == 0 || (read && strand && contig && dist && first && op_off && use), MM_ERR_ARG, "mm_vcf_events: a null array");
-    std::unique_ptr<mm_vcf> t(new mm_vcf());
-    mm::vcf_events_run(ctx, reads, reference, mm::PileupIn{n_jobs, read, strand, contig, dist, first, op_off, ops, use}, &t->t);
-    *out = t.release();
+  return created(ctx, out, [&](mm_vcf& t) {
+    require_jobs("mm_vcf_events", n_jobs, read && strand && contig && dist && first && op_off && use);
+    mm::vcf_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, &t.t);
   });
 }
 int mm_vcf_merge(mm_ctx* ctx, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, mm_vcf** out) {
   if (!ctx || !out) return MM_ERR_ARG;
-  *out = nullptr;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    MM_REQUIRE(n >= 0 && n < ((int64_t)1 << 32), n < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_vcf_merge: a negative number of triples, or 2^32 or more");
-    MM_REQUIRE(n == 0 || (w0 && w1 && counts), MM_ERR_ARG, "mm_vcf_merge: a null array");
-    std::unique_ptr<mm_vcf> t(new mm_vcf());
-    mm::vcf_merge_run(ctx, n, w0, w1, counts, &t->t);
-    *out = t.release();
+  return created(ctx, out, [&](mm_vcf& t) {
+    require_rows("mm_vcf_merge", "triples", n, w0 && w1 && counts);
+    mm::merge_run(ctx, n, w0, w1, counts, "mm_vcf_merge", "MM_VCF_TIMING", &t.t);
   });
 }
 int mm_vcf_sizes(const mm_vcf* t, int64_t* n_triples) {
@@ -1167,25 +1165,14 @@ int mm_vcf_sizes(const mm_vcf* t, int64_t* n_triples) {
   *n_triples = (int64_t)t->t.w0.size();
   return MM_OK;
 }
-int mm_vcf_fetch(const mm_vcf* t, uint64_t* w0, uint64_t* w1, uint32_t* counts) {
-  if (!t || (!t->t.w0.empty() && (!w0 || !w1 || !counts))) return MM_ERR_ARG;
-  const size_t k = t->t.w0.size();
-  if (k) { memcpy(w0, t->t.w0.data(), k * 8); memcpy(w1, t->t.w1.data(), k * 8); memcpy(counts, t->t.counts.data(), k * 4); }
-  return MM_OK;
-}
+int mm_vcf_fetch(const mm_vcf* t, uint64_t* w0, uint64_t* w1, uint32_t* counts) { return t ? table_fetch(t->t, w0, w1, counts) : MM_ERR_ARG; }
 void mm_vcf_destroy(mm_vcf* t) { delete t; }
 int mm_vcf_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, int64_t n_iv, const int32_t* iv_contig,
                   const int64_t* iv_first, const int64_t* iv_last, int64_t min_count, double min_frac, mm_vcf_result** out) {
   if (!ctx || !reference || !out) return MM_ERR_ARG;
-  *out = nullptr;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    MM_REQUIRE(n >= 0 && n < ((int64_t)1 << 32) && n_iv >= 0 && n_iv < ((int64_t)1 << 32), n < 0 || n_iv < 0 ? MM_ERR_ARG : MM_ERR_LIMIT,
-               "mm_vcf_finish: a negative number of entries or intervals, or 2^32 or more");
-    MM_REQUIRE((n == 0 || (w0 && w1 && counts)) && (n_iv == 0 || (iv_contig && iv_first && iv_last)), MM_ERR_ARG, "mm_vcf_finish: a null array");
-    std::unique_ptr<mm_vcf_result> r(new mm_vcf_result());
-    mm::vcf_finish_run(ctx, reference, mm::VcfFinishIn{n, w0, w1, counts, n_iv, iv_contig, iv_first, iv_last, min_count, min_frac}, &r->r);
-    *out = r.release();
+  return created(ctx, out, [&](mm_vcf_result& r) {
+    require_finish("mm_vcf_finish", n, n_iv, w0 && w1 && counts, iv_contig && iv_first && iv_last);
+    mm::vcf_finish_run(ctx, reference, mm::FinishIn{n, w0, w1, counts, n_iv, iv_contig, iv_first, iv_last, min_count, min_frac}, &r.r);
   });
 }
 int mm_vcf_result_sizes(const mm_vcf_result* r, int64_t* n_alleles) {

@@ -11,54 +11,29 @@
 //            to the host.  One buffer of the largest group's size serves every group.
 // No kernel here has an atomic other than the error word's, a barrier between workgroups or a loop that waits for another workgroup.
 // The runs are the caller's (mm_alignment is a host object) and are uploaded whole: 4 bytes per run against the 27 KB of a 10 kb read's record.
+// The jobs' arrays, their checks, the launch loop and the error word are mm_jobs_dev.hpp's, shared with mm_pileup.hip and mm_vcf.hip; flag, mapq and the
+// names are this file's own columns (BamColumns).
 #include "mm_bam.hpp"
 #include "mm_bam_core.hpp"
 #include "mm_deflate.hpp"
-#include "mm_edit_seq.hpp"
+#include "mm_jobs_dev.hpp"
 #include "mm_prims.hpp"
 
 namespace mm {
 
-struct BamWaveLanes {                                             // one lane per thread of a 64-thread workgroup
-  static constexpr uint32_t W = 64;
-  __device__ uint32_t lane() const { return threadIdx.x; }
-  __device__ int64_t scan_add(int64_t v, int64_t* total) const {
-    long long x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const long long y = __shfl_up(x, o, 64); if ((int)threadIdx.x >= o) x += y; }
-    *total = (int64_t)__shfl(x, 63, 64);
-    return (int64_t)x - v;
-  }
-  __device__ int64_t scan_max(int64_t v, int64_t* total) const {  // of values >= 0; the lowest lane gets 0
-    long long x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const long long y = __shfl_up(x, o, 64); if ((int)threadIdx.x >= o && y > x) x = y; }
-    *total = (int64_t)__shfl(x, 63, 64);
-    const long long below = __shfl_up(x, 1, 64);
-    return threadIdx.x ? (int64_t)below : 0;
-  }
-};
-struct BamBytes { EditSeq s; int64_t g0; __device__ uint8_t byte(int64_t i) const { return s.byte(g0 + i); } };   // sequence coordinate -> the set's byte
-
-struct BamJobs {
-  int64_t n; const int32_t* read; const int32_t* strand; const int32_t* contig; const int32_t* dist; const int64_t* first;
-  const int64_t* op_off; const uint32_t* ops; const uint16_t* flag; const uint8_t* mapq; const int64_t* name_off; const char* names;
-};
-constexpr unsigned long long BAM_NO_ERROR = ~0ull;
-
-__global__ void __launch_bounds__(64) bam_size_kernel(const int32_t* __restrict__ q_len, int64_t n_reads, const int32_t* __restrict__ r_len, int64_t n_contigs, BamJobs J,
-                                                      int64_t job0, int64_t* __restrict__ sizes, unsigned long long* __restrict__ err) {
+__global__ void __launch_bounds__(64) bam_size_kernel(const int32_t* __restrict__ q_len, int64_t n_reads, const int32_t* __restrict__ r_len, int64_t n_contigs, AlignedJobs J,
+                                                      BamColumns C, int64_t job0, int64_t* __restrict__ sizes, unsigned long long* __restrict__ err) {
   const int64_t job = job0 + (int64_t)blockIdx.x;
   if (job >= J.n) return;
-  BamWaveLanes p;
+  WaveLanes p;
   const int32_t read = J.read[job], contig = J.contig[job], dist = J.dist[job];
   int rule = mmb::check_set(read, n_reads, contig, n_contigs);
   int64_t size = 0;
   if (!rule && dist >= 0 && q_len[read] > 0) {
-    const int64_t l_name = J.name_off[job + 1] - J.name_off[job], n_ops = J.op_off[job + 1] - J.op_off[job], first = J.first[job];
-    rule = mmb::check_head(J.strand[job], J.flag[job], l_name);
+    const int64_t l_name = C.name_off[job + 1] - C.name_off[job], n_ops = J.op_off[job + 1] - J.op_off[job], first = J.first[job];
+    rule = mmb::check_head(J.strand[job], C.flag[job], l_name);
     if (!rule) {
-      const mmb::Walk w = mmb::md_walk<false>(p, BamBytes{}, J.ops + J.op_off[job], n_ops, first, nullptr);   // (sizing reads no reference byte)
+      const mmb::Walk w = mmb::md_walk<false>(p, SeqBytes{}, J.ops + J.op_off[job], n_ops, first, nullptr);   // (sizing reads no reference byte)
       rule = mmb::check_walk(w, q_len[read], first, r_len[contig], dist);
       if (!rule) size = mmb::record_size(l_name, q_len[read], n_ops, w.md_len);
     }
@@ -71,66 +46,47 @@ __global__ void __launch_bounds__(64) bam_size_kernel(const int32_t* __restrict_
 
 // the records of the jobs [job0, job1) of a group to raw + (off[job] - off0); a job of size 0 has none
 __global__ void __launch_bounds__(64) bam_write_kernel(EditSeq Q, const uint64_t* __restrict__ q_base, const int32_t* __restrict__ q_len, EditSeq R,
-                                                       const uint64_t* __restrict__ r_base, const int32_t* __restrict__ r_len, BamJobs J, int64_t job0, int64_t job1,
-                                                       const int64_t* __restrict__ off, int64_t off0, uint8_t* __restrict__ raw) {
+                                                       const uint64_t* __restrict__ r_base, const int32_t* __restrict__ r_len, AlignedJobs J, BamColumns C, int64_t job0,
+                                                       int64_t job1, const int64_t* __restrict__ off, int64_t off0, uint8_t* __restrict__ raw) {
   const int64_t job = job0 + (int64_t)blockIdx.x;
   if (job >= job1 || off[job + 1] == off[job]) return;
-  BamWaveLanes p;
+  WaveLanes p;
   const int32_t read = J.read[job], contig = J.contig[job];
   const uint64_t qg = q_base[read], rg = r_base[contig];
   mmb::Job j;
   j.ops = J.ops + J.op_off[job]; j.n_ops = J.op_off[job + 1] - J.op_off[job];
-  j.name = J.names + J.name_off[job]; j.l_name = (int32_t)(J.name_off[job + 1] - J.name_off[job]);
-  j.first = J.first[job]; j.m = q_len[read]; j.refid = contig; j.strand = J.strand[job]; j.dist = J.dist[job]; j.flag = J.flag[job]; j.mapq = J.mapq[job];
-  mmb::write_record(p, j, BamBytes{Q.narrowed(qg, qg + (uint64_t)j.m), (int64_t)qg}, BamBytes{R.narrowed(rg, rg + (uint64_t)r_len[contig]), (int64_t)rg}, raw + (off[job] - off0));
+  j.name = C.names + C.name_off[job]; j.l_name = (int32_t)(C.name_off[job + 1] - C.name_off[job]);
+  j.first = J.first[job]; j.m = q_len[read]; j.refid = contig; j.strand = J.strand[job]; j.dist = J.dist[job]; j.flag = C.flag[job]; j.mapq = C.mapq[job];
+  mmb::write_record(p, j, SeqBytes{Q.narrowed(qg, qg + (uint64_t)j.m), (int64_t)qg}, SeqBytes{R.narrowed(rg, rg + (uint64_t)r_len[contig]), (int64_t)rg}, raw + (off[job] - off0));
 }
 
-namespace {
-constexpr int64_t BAM_GRID_MAX = (int64_t)1 << 30;                // workgroups per launch
-
-void offsets_check(const int64_t* off, int64_t n, const char* what) {
-  bool ok = off[0] >= 0;
-  for (int64_t i = 0; ok && i < n; ++i) ok = off[i] <= off[i + 1];
-  MM_REQUIRE(ok, MM_ERR_ARG, std::string("mm_bam_encode: ") + what + " does not start at 0 or more, or falls");
-}
-}  // namespace
-
-void bam_encode_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const BamIn& in, int64_t group_bytes, BamMembers* out) {
-  MM_REQUIRE(reads->frozen && ref->frozen, MM_ERR_STATE, "mm_bam_encode: a sequence set is not uploaded");
-  MM_REQUIRE(reads->ctx->device == ctx->device && ref->ctx->device == ctx->device, MM_ERR_ARG, "mm_bam_encode: a sequence set lives on another device");
+void bam_encode_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& jobs_in, const BamColumns& in, int64_t group_bytes, BamMembers* out) {
+  AlignedJobsDev jobs(ctx, reads, ref, jobs_in, "mm_bam_encode");
   MM_REQUIRE(group_bytes >= 0, MM_ERR_ARG, "mm_bam_encode: a negative group_bytes");
   out->bgzf.clear(); out->n_records = 0; out->raw_bytes = 0;
-  const int64_t n = in.n_jobs;
+  const int64_t n = jobs_in.n_jobs;
   if (n == 0) return;
-  offsets_check(in.op_off, n, "op_off");
-  offsets_check(in.name_off, n, "name_off");
-  const size_t k = (size_t)n, n_ops = (size_t)in.op_off[n], n_name = (size_t)in.name_off[n];
-  MM_REQUIRE((n_ops == 0 || in.ops) && (n_name == 0 || in.names), MM_ERR_ARG, "mm_bam_encode: a null array");
+  offsets_check(in.name_off, n, "mm_bam_encode", "name_off");
+  const size_t k = (size_t)n, n_ops = jobs.n_ops, n_name = (size_t)in.name_off[n];
+  MM_REQUIRE(n_name == 0 || in.names, MM_ERR_ARG, "mm_bam_encode: a null array");
   hipStream_t st = ctx->stream;
   StageClock<5> clk(getenv("MM_BAM_TIMING") != nullptr, st);       // upload, size, scan, write, deflate (with the members' way to the host)
 
   clk.start();
-  DBuf<int32_t> d_read(k), d_strand(k), d_contig(k), d_dist(k);
-  DBuf<int64_t> d_first(k), d_op_off(k + 1), d_name_off(k + 1), d_sizes(k + 1), d_off(k + 1);
-  DBuf<uint32_t> d_ops(std::max<size_t>(n_ops, 1));
+  const AlignedJobs J = jobs.upload(st);
+  DBuf<int64_t> d_name_off(k + 1), d_sizes(k + 1), d_off(k + 1);
   DBuf<uint16_t> d_flag(k); DBuf<uint8_t> d_mapq(k); DBuf<char> d_names(std::max<size_t>(n_name, 1));
-  DBuf<unsigned long long> d_err(1);
-  d_read.upload(in.read, k, st); d_strand.upload(in.strand, k, st); d_contig.upload(in.contig, k, st); d_dist.upload(in.dist, k, st); d_first.upload(in.first, k, st);
-  d_op_off.upload(in.op_off, k + 1, st); d_name_off.upload(in.name_off, k + 1, st); d_ops.upload(in.ops, n_ops, st);
-  d_flag.upload(in.flag, k, st); d_mapq.upload(in.mapq, k, st); d_names.upload(in.names, n_name, st);
+  d_name_off.upload(in.name_off, k + 1, st); d_flag.upload(in.flag, k, st); d_mapq.upload(in.mapq, k, st); d_names.upload(in.names, n_name, st);
   d_sizes.zero(st);
-  MM_HIP(hipMemsetAsync(d_err.p, 0xFF, sizeof(unsigned long long), st));
   clk.stop(0);
-  const BamJobs J{n, d_read.p, d_strand.p, d_contig.p, d_dist.p, d_first.p, d_op_off.p, d_ops.p, d_flag.p, d_mapq.p, d_name_off.p, d_names.p};
+  const BamColumns C{d_flag.p, d_mapq.p, d_name_off.p, d_names.p};
 
   clk.start();
-  for (int64_t job0 = 0; job0 < n; job0 += BAM_GRID_MAX) {
-    bam_size_kernel<<<dim3((unsigned)std::min(BAM_GRID_MAX, n - job0)), dim3(64), 0, st>>>(reads->d_len.p, reads->count(), ref->d_len.p, ref->count(), J, job0, d_sizes.p, d_err.p);
-    MM_KERNEL_CHECK();
-  }
-  const unsigned long long e = d_err.to_host(st)[0];
+  for_job_grids(0, n, [&](int64_t a, dim3 grid) {
+    bam_size_kernel<<<grid, dim3(64), 0, st>>>(reads->d_len.p, reads->count(), ref->d_len.p, ref->count(), J, C, a, d_sizes.p, jobs.err.p);
+  });
+  jobs.require_no_error(st, mmb::rule_text);
   clk.stop(1);
-  MM_REQUIRE(e == BAM_NO_ERROR, MM_ERR_ARG, "mm_bam_encode: job " + std::to_string(e >> 4) + ": " + mmb::rule_text((int)(e & 15)));
 
   clk.start();
   DBuf<uint8_t> tmp;
@@ -157,11 +113,10 @@ void bam_encode_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, c
     const int64_t j0 = cut[g], j1 = cut[g + 1], bytes = off[(size_t)j1] - off[(size_t)j0];
     if (bytes == 0) continue;
     clk.start();
-    for (int64_t a = j0; a < j1; a += BAM_GRID_MAX) {
-      bam_write_kernel<<<dim3((unsigned)std::min(BAM_GRID_MAX, j1 - a)), dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, edit_seq(ref), ref->d_base.p, ref->d_len.p,
-                                                                                            J, a, j1, d_off.p, off[(size_t)j0], d_raw.p);
-      MM_KERNEL_CHECK();
-    }
+    for_job_grids(j0, j1, [&](int64_t a, dim3 grid) {
+      bam_write_kernel<<<grid, dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, edit_seq(ref), ref->d_base.p, ref->d_len.p, J, C, a, j1, d_off.p, off[(size_t)j0],
+                                                  d_raw.p);
+    });
     clk.stop(3);
     clk.start();
     const int64_t nb = mmd::n_blocks_of(bytes);
