@@ -14,6 +14,8 @@
  * from one host thread at a time, different contexts (one per GPU of a node, or several on one GPU) may be
  * driven from different threads concurrently, and an index may be read by mm_map_batch through any context of
  * the device it lives on.  There is no CPU fallback: mm_ctx_create fails when no gfx950 device is present.
+ * A function that hands back a new handle through `out` (mm_seqset_hpc: through `out` and `map`) does so on MM_OK alone: on every
+ * error *out is NULL and what the call had made is freed.
  */
 #ifndef METAMAPS_HIP_H
 #define METAMAPS_HIP_H
@@ -485,7 +487,7 @@ int mm_mapping_edit_distances(mm_ctx* ctx, const mm_mapping* mapping, const mm_s
  * with equal neighbours merged into runs, each one 32-bit word as in BAM: len << 4 | op, I = 1, D = 2, = = 7, X = 8.  X + I + D bases = d,
  * = + X + I = m, = + X + D = n, at most 2 d + 1 runs, the first and the last never D.  A job that is not aligned, and an empty read, has no runs.
  * For strand -1 the runs are those of the reverse-complemented read along the forward contig (PAF's convention).
- * mm_edit_infix_align: the checks and messages of mm_edit_infix, nothing launched on a bad job, *out NULL on every error.  mm_mapping_align: the
+ * mm_edit_infix_align: the checks and messages of mm_edit_infix, nothing launched on a bad job.  mm_mapping_align: the
  * window and cap rules of mm_mapping_edit_distances.  dist / first / last are exactly what those two calls return for the same jobs (window
  * coordinates half-open for the former, 0-based inclusive contig coordinates for the latter, -1 -1 -1: not aligned).  The runs of job i are
  * ops[op_off[i], op_off[i + 1]).  The result lives in host memory until mm_alignment_destroy; no result depends on MM_EDIT_TRACE_MB. */

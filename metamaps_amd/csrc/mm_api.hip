@@ -14,62 +14,56 @@
 #include "mm_bam.hpp"
 #include "mm_pileup.hpp"
 #include "mm_vcf.hpp"
+#include "mm_seq.hpp"
+#include "mm_codec.hpp"
 #include <chrono>
 #include <new>
-#include <rccl/rccl.h>
-#include "mm_prims.hpp"
-
-namespace mm {
-void seqset_upload(mm_seqset* s);
-void seqset_upload_nt16(mm_seqset* s);
-int64_t bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const int64_t* comp_off, const int32_t* comp_len, int32_t n,
-                     uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status);
-void bgzf_deflate(mm_ctx* ctx, const uint8_t* in, int64_t in_bytes, uint8_t* out, int64_t out_cap, int64_t* out_bytes, int32_t* n_blocks);
-int64_t bgzf_deflate_bound(int64_t in_bytes);
-mm_gzip* gzip_open(mm_ctx* ctx, int64_t chunk, int64_t segment);
-void gzip_close(mm_gzip* g);
-int gzip_feed(mm_gzip* g, const uint8_t* comp, int64_t n, bool last, int64_t* avail);
-int64_t gzip_read(mm_gzip* g, uint8_t* out, int64_t cap);
-void gzip_stats(const mm_gzip* g, int64_t* counts, double* seconds);
-mm_ctx* gzip_ctx(const mm_gzip* g);
-void seqset_save(mm_seqset* s, const char* path);
-void seqset_load(mm_seqset* s, const char* path);
-void seqset_fetch(mm_seqset* s, int64_t i, char* out, int64_t cap);
-void seqset_fetch_range(mm_seqset* s, int64_t first, int64_t count, char* out, int64_t cap);
-void seqset_slice(const mm_seqset* s, int64_t first, int64_t count, mm_seqset* o);
-void seqset_concat(const mm_seqset* const* parts, int n_parts, mm_seqset* o);
-}
 
 namespace {
 // a context is bound to the calling thread for the duration of a call: its device (hipSetDevice is per thread), its
 // stream and its allocator.  Several contexts — one per GPU, or several on one GPU — may be driven from different threads.
-void bind(mm_ctx* ctx) {
-  if (ctx->device >= 0 && ctx->stream) (void)hipSetDevice(ctx->device);
+// (No device is selected while the context has no stream yet: mm_ctx_create's own lambda does that.)  checked: a failing hipSetDevice throws.
+void bind(mm_ctx* ctx, bool checked = false) {
   mm::current_stream() = ctx->stream; mm::current_alloc() = &ctx->alloc;
+  if (ctx->device < 0 || !ctx->stream) return;
+  if (checked) MM_HIP(hipSetDevice(ctx->device)); else (void)hipSetDevice(ctx->device);
 }
 template <typename F>
 int guarded(mm_ctx* ctx, F&& f) {
-  if (ctx) bind(ctx);
-  try { f(); return MM_OK; }
+  try { if (ctx) bind(ctx, true); f(); return MM_OK; }
   catch (const mm::Error& e) { if (ctx) ctx->err = e.what(); return e.status; }
   catch (const std::bad_alloc&) { if (ctx) ctx->err = "host allocation failed"; return MM_ERR_NOMEM; }
   catch (const std::exception& e) { if (ctx) ctx->err = e.what(); return MM_ERR_DEVICE; }
 }
-// An entry point that hands back a new object of the context's device: fill(object) makes it, and *out stays NULL unless fill returns.
+// The entry points that hand back a new object: *out is NULL unless they return MM_OK — when the arguments are refused ...
+template <typename H> int refused(H** out) { if (out) *out = nullptr; return MM_ERR_ARG; }
+template <typename H> auto set_ctx(H& h, mm_ctx* ctx, int) -> decltype((void)(h.ctx = ctx)) { h.ctx = ctx; }
+template <typename H> void set_ctx(H&, mm_ctx*, long) {}            // (handles of host memory alone carry no context)
+// ... and when making the object fails: fill(object) makes it on the context's device, and *out stays NULL unless fill returns.
 template <typename H, typename F>
 int created(mm_ctx* ctx, H** out, F&& fill) {
   *out = nullptr;
   return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
     std::unique_ptr<H> h(new H());
+    set_ctx(*h, ctx, 0);
     fill(*h);
     *out = h.release();
   });
+}
+// ... and one whose object the callee makes, or declines to make, itself (mm_gzip, whose struct is its unit's own; mm_mapping_gather off the owner)
+template <typename H, typename F>
+int adopted(mm_ctx* ctx, H** out, F&& make) {
+  *out = nullptr;
+  return guarded(ctx, [&] { *out = make(); });
 }
 // what the entry points over aligned jobs, over key tables and over their finishes ask of their counts and arrays (who: the entry point's name)
 void require_jobs(const char* who, int64_t n_jobs, bool arrays) {
   MM_REQUIRE(n_jobs >= 0 && n_jobs < ((int64_t)1 << 31), n_jobs < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, std::string(who) + ": a negative number of jobs, or 2^31 or more");
   MM_REQUIRE(n_jobs == 0 || arrays, MM_ERR_ARG, std::string(who) + ": a null array");
+}
+void require_records(const char* who, int64_t n_rec, bool arrays) {
+  MM_REQUIRE(n_rec < ((int64_t)1 << 31), MM_ERR_LIMIT, std::string(who) + ": 2^31 records or more");
+  MM_REQUIRE(n_rec == 0 || arrays, MM_ERR_ARG, std::string(who) + ": a null array");
 }
 void require_rows(const char* who, const char* rows, int64_t n, bool arrays) {
   MM_REQUIRE(n >= 0 && n < ((int64_t)1 << 32), n < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, std::string(who) + ": a negative number of " + rows + ", or 2^32 or more");
@@ -170,7 +164,6 @@ const char* mm_last_error(const mm_ctx* ctx) { return ctx ? ctx->err.c_str() : "
 int mm_ctx_device_info(mm_ctx* ctx, char* name, size_t name_cap, int* cus, uint64_t* hbm_total, uint64_t* hbm_free) {
   if (!ctx) return MM_ERR_ARG;
   return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
     hipDeviceProp_t p;
     MM_HIP(hipGetDeviceProperties(&p, ctx->device));
     if (name && name_cap) { snprintf(name, name_cap, "%s (%s)", p.name, p.gcnArchName); }
@@ -187,14 +180,14 @@ int mm_ctx_synchronize(mm_ctx* ctx) {
 }
 int mm_ctx_release_cached(mm_ctx* ctx) {
   if (!ctx) return MM_ERR_ARG;
-  return guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); ctx->alloc.trim(); mm::big_pool_trim(ctx->device); });
+  return guarded(ctx, [&] { ctx->alloc.trim(); mm::big_pool_trim(ctx->device); });
 }
 void* mm_ctx_stream(mm_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
 // ---- sequences ----------------------------------------------------------------------------------------
 int mm_seqset_create(mm_ctx* ctx, mm_seqset** out) {
-  if (!ctx || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] { auto* s = new mm_seqset; s->ctx = ctx; *out = s; });
+  if (!ctx || !out) return refused(out);
+  return created(ctx, out, [](mm_seqset&) {});
 }
 void mm_seqset_destroy(mm_seqset* s) { if (s) { bind(s->ctx); delete s; } }
 int mm_seqset_add(mm_seqset* s, const char* ascii, int64_t len) {
@@ -230,7 +223,7 @@ int mm_bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const 
                     uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status) {
   if (!ctx || n < 0 || comp_bytes < 0 || out_cap < 0 || (n > 0 && (!comp || !comp_off || !comp_len || !out_off)) || (!out && out_cap > 0)) return MM_ERR_ARG;
   int64_t bad = 0;
-  const int rc = guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); bad = mm::bgzf_inflate(ctx, comp, comp_bytes, comp_off, comp_len, n, out, out_cap, out_off, status); });
+  const int rc = guarded(ctx, [&] { bad = mm::bgzf_inflate(ctx, comp, comp_bytes, comp_off, comp_len, n, out, out_cap, out_off, status); });
   if (rc != MM_OK) return rc;
   if (bad) { ctx->err = "mm_bgzf_inflate: " + std::to_string(bad) + " corrupt BGZF block(s)"; return MM_ERR_DATA; }
   return MM_OK;
@@ -238,17 +231,16 @@ int mm_bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const 
 int64_t mm_bgzf_deflate_bound(int64_t in_bytes) { return in_bytes < 0 ? 0 : mm::bgzf_deflate_bound(in_bytes); }
 int mm_bgzf_deflate(mm_ctx* ctx, const uint8_t* in, int64_t in_bytes, uint8_t* out, int64_t out_cap, int64_t* out_bytes, int32_t* n_blocks) {
   if (!ctx || !out_bytes || !n_blocks || in_bytes < 0 || (in_bytes > 0 && (!in || !out))) return MM_ERR_ARG;
-  return guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); mm::bgzf_deflate(ctx, in, in_bytes, out, out_cap, out_bytes, n_blocks); });
+  return guarded(ctx, [&] { mm::bgzf_deflate(ctx, in, in_bytes, out, out_cap, out_bytes, n_blocks); });
 }
 int mm_gzip_open(mm_ctx* ctx, int64_t chunk_bytes, int64_t segment_bytes, mm_gzip** out) {
-  if (!ctx || !out || chunk_bytes < 0 || segment_bytes < 0) return MM_ERR_ARG;
-  *out = nullptr;
-  return guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); *out = mm::gzip_open(ctx, chunk_bytes, segment_bytes); });
+  if (!ctx || !out || chunk_bytes < 0 || segment_bytes < 0) return refused(out);
+  return adopted(ctx, out, [&] { return mm::gzip_open(ctx, chunk_bytes, segment_bytes); });
 }
 int mm_gzip_feed(mm_gzip* g, const uint8_t* comp, int64_t n, int last, int64_t* avail) {
   if (!g || n < 0 || (n > 0 && !comp)) return MM_ERR_ARG;
   int bad = 0;
-  const int rc = guarded(mm::gzip_ctx(g), [&] { MM_HIP(hipSetDevice(mm::gzip_ctx(g)->device)); bad = mm::gzip_feed(g, comp, n, last != 0, avail); });
+  const int rc = guarded(mm::gzip_ctx(g), [&] { bad = mm::gzip_feed(g, comp, n, last != 0, avail); });
   if (rc != MM_OK) return rc;
   return bad ? MM_ERR_DATA : MM_OK;
 }
@@ -265,43 +257,30 @@ int mm_gzip_stats(const mm_gzip* g, int64_t* counts, double* seconds) {
 void mm_gzip_close(mm_gzip* g) {
   if (!g) return;
   mm_ctx* ctx = mm::gzip_ctx(g);
-  (void)guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); mm::gzip_close(g); });
+  (void)guarded(ctx, [&] { mm::gzip_close(g); });
 }
 int mm_seqset_upload(mm_seqset* s) {
   if (!s) return MM_ERR_ARG;
-  return guarded(s->ctx, [&] { MM_HIP(hipSetDevice(s->ctx->device)); if (s->staged_kind == 2) mm::seqset_upload_nt16(s); else mm::seqset_upload(s); });
+  return guarded(s->ctx, [&] { if (s->staged_kind == 2) mm::seqset_upload_nt16(s); else mm::seqset_upload(s); });
 }
 int mm_seqset_save(mm_seqset* s, const char* path) {
   if (!s || !path) return MM_ERR_ARG;
-  return guarded(s->ctx, [&] { MM_HIP(hipSetDevice(s->ctx->device)); mm::seqset_save(s, path); });
+  return guarded(s->ctx, [&] { mm::seqset_save(s, path); });
 }
 int mm_seqset_load(mm_ctx* ctx, const char* path, mm_seqset** out) {
-  if (!ctx || !path || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    auto* S = new mm_seqset; S->ctx = ctx;
-    try { mm::seqset_load(S, path); } catch (...) { delete S; throw; }
-    *out = S;
-  });
+  if (!ctx || !path || !out) return refused(out);
+  return created(ctx, out, [&](mm_seqset& S) { mm::seqset_load(&S, path); });
 }
 int mm_seqset_slice(mm_ctx* ctx, const mm_seqset* set, int64_t first, int64_t count, mm_seqset** out) {
-  if (!ctx || !set || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
+  if (!ctx || !set || !out) return refused(out);
+  return created(ctx, out, [&](mm_seqset& S) {
     MM_REQUIRE(set->ctx->device == ctx->device, MM_ERR_ARG, "mm_seqset_slice: the set lives on another device than the context");
-    auto* S = new mm_seqset; S->ctx = ctx;
-    try { mm::seqset_slice(set, first, count, S); } catch (...) { delete S; throw; }
-    *out = S;
+    mm::seqset_slice(set, first, count, &S);
   });
 }
 int mm_seqset_concat(mm_ctx* ctx, const mm_seqset* const* parts, int n_parts, mm_seqset** out) {
-  if (!ctx || !parts || n_parts <= 0 || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    auto* S = new mm_seqset; S->ctx = ctx;
-    try { mm::seqset_concat(parts, n_parts, S); } catch (...) { delete S; throw; }
-    *out = S;
-  });
+  if (!ctx || !parts || n_parts <= 0 || !out) return refused(out);
+  return created(ctx, out, [&](mm_seqset& S) { mm::seqset_concat(parts, n_parts, &S); });
 }
 int64_t mm_seqset_count(const mm_seqset* s) { return s ? (s->frozen ? s->count() : (int64_t)s->staged.size()) : 0; }
 int64_t mm_seqset_total_bases(const mm_seqset* s) { return s ? s->total_bases : 0; }
@@ -322,19 +301,17 @@ int mm_seqset_fetch_range(mm_seqset* s, int64_t first, int64_t count, char* asci
 
 // ---- homopolymer compression (mm_hpc.hip) -------------------------------------------------------------
 int mm_seqset_hpc(mm_ctx* ctx, const mm_seqset* raw, mm_seqset** out, mm_hpc_map** map) {
-  if (!ctx || !raw || !out) return MM_ERR_ARG;
-  *out = nullptr; if (map) *map = nullptr;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    std::unique_ptr<mm_seqset> S(new mm_seqset); S->ctx = ctx;
+  if (map) *map = nullptr;
+  if (!ctx || !raw || !out) return refused(out);
+  return created(ctx, out, [&](mm_seqset& S) {                  // (two objects: the map is let go only where the set is, behind the last call that can throw)
     std::unique_ptr<mm_hpc_map> M(map ? new mm_hpc_map : nullptr);
-    mm::seqset_hpc(ctx, raw, S.get(), M.get());
-    *out = S.release(); if (map) *map = M.release();
+    mm::seqset_hpc(ctx, raw, &S, M.get());
+    if (map) *map = M.release();
   });
 }
 int mm_hpc_map_to_raw(mm_hpc_map* map, const int32_t* seq, const int64_t* pos, int64_t n, int64_t* first_out, int64_t* last_out) {
   if (!map || n < 0 || (n > 0 && (!seq || !pos || !first_out || !last_out))) return MM_ERR_ARG;
-  return guarded(map->ctx, [&] { MM_HIP(hipSetDevice(map->ctx->device)); mm::hpc_map_to_raw(map, seq, pos, n, first_out, last_out); });
+  return guarded(map->ctx, [&] { mm::hpc_map_to_raw(map, seq, pos, n, first_out, last_out); });
 }
 int mm_hpc_map_lengths(const mm_hpc_map* map, int32_t* raw_len, int32_t* compressed_len) {
   if (!map) return MM_ERR_ARG;
@@ -345,32 +322,31 @@ int mm_hpc_map_lengths(const mm_hpc_map* map, int32_t* raw_len, int32_t* compres
 int64_t mm_hpc_map_device_bytes(const mm_hpc_map* map) { return map ? (int64_t)map->device_bytes() : 0; }
 int mm_mapping_to_raw(mm_ctx* ctx, mm_mapping* m, const mm_hpc_map* ref_map, int64_t* end_out, int64_t cap) {
   if (!ctx || !m || !ref_map || cap < 0 || (!end_out && cap > 0)) return MM_ERR_ARG;
-  return guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); mm::mapping_to_raw(ctx, m, ref_map, end_out, cap); });
+  return guarded(ctx, [&] { mm::mapping_to_raw(ctx, m, ref_map, end_out, cap); });
 }
 void mm_hpc_map_destroy(mm_hpc_map* map) { if (map) { bind(map->ctx); delete map; } }
 
 int mm_synth_reference(mm_ctx* ctx, const mm_synth_ref_params* p, mm_seqset** out) {
-  if (!ctx || !p || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); auto* s = new mm_seqset; s->ctx = ctx; try { mm::synth_reference(ctx, *p, s); } catch (...) { delete s; throw; } *out = s; });
+  if (!ctx || !p || !out) return refused(out);
+  return created(ctx, out, [&](mm_seqset& s) { mm::synth_reference(ctx, *p, &s); });
 }
 int mm_synth_community(mm_ctx* ctx, const mm_synth_community_params* p, mm_seqset** out, int32_t* contig_genome) {
-  if (!ctx || !p || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] { auto* s = new mm_seqset; s->ctx = ctx; try { mm::synth_community(ctx, *p, s, contig_genome); } catch (...) { delete s; throw; } *out = s; });
+  if (!ctx || !p || !out) return refused(out);
+  return created(ctx, out, [&](mm_seqset& s) { mm::synth_community(ctx, *p, &s, contig_genome); });
 }
 int mm_synth_community_species(const mm_synth_community_params* p, int32_t* genome_species) {
   if (!p || !genome_species) return MM_ERR_ARG;
   return guarded(nullptr, [&] { mm::synth_community_species(*p, genome_species); });
 }
 int mm_synth_reads(mm_ctx* ctx, const mm_seqset* reference, const mm_synth_read_params* p, mm_seqset** out, int32_t* truth_genome) {
-  if (!ctx || !reference || !p || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); auto* s = new mm_seqset; s->ctx = ctx; try { mm::synth_reads(ctx, reference, *p, s, truth_genome); } catch (...) { delete s; throw; } *out = s; });
+  if (!ctx || !reference || !p || !out) return refused(out);
+  return created(ctx, out, [&](mm_seqset& s) { mm::synth_reads(ctx, reference, *p, &s, truth_genome); });
 }
 
 // ---- minimizer tap ------------------------------------------------------------------------------------
 int mm_minimizers(mm_ctx* ctx, const mm_seqset* s, int k, int w, int64_t* offsets, uint32_t* hash, int32_t* wpos, int32_t* strand, int64_t cap) {
   if (!ctx || !s) return MM_ERR_ARG;
   return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
     mm::MinimizerSet ms;
     mm::run_minimizers(ctx, s, k, w, {}, false, ms);
     if (offsets) for (size_t i = 0; i < ms.h_off.size(); ++i) offsets[i] = (int64_t)ms.h_off[i];
@@ -388,18 +364,12 @@ int mm_minimizers(mm_ctx* ctx, const mm_seqset* s, int k, int w, int64_t* offset
 
 // ---- index --------------------------------------------------------------------------------------------
 int mm_index_build(mm_ctx* ctx, const mm_seqset* contigs, int k, int w, mm_index** out) {
-  if (!ctx || !contigs || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    auto* I = new mm_index;
-    try { mm::index_build(ctx, contigs, k, w, I); } catch (...) { delete I; throw; }
-    *out = I;
-  });
+  if (!ctx || !contigs || !out) return refused(out);
+  return created(ctx, out, [&](mm_index& I) { mm::index_build(ctx, contigs, k, w, &I); });
 }
 int mm_index_plan_chunks(mm_ctx* ctx, const mm_index* whole, uint64_t max_memory_bytes, int32_t* first_contig, int32_t cap, int32_t* n_chunks) {
   if (!ctx || !whole || !n_chunks) return MM_ERR_ARG;
   return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
     std::vector<int32_t> fc;
     mm::index_plan_chunks(ctx, whole, max_memory_bytes, fc);
     *n_chunks = (int32_t)fc.size();
@@ -411,20 +381,11 @@ int mm_index_plan_chunks(mm_ctx* ctx, const mm_index* whole, uint64_t max_memory
 }
 int mm_index_save(mm_index* idx, const char* path) {
   if (!idx || !path) return MM_ERR_ARG;
-  return guarded(idx->ctx, [&] {
-    MM_HIP(hipSetDevice(idx->ctx->device));
-    mm::index_save(idx, path);
-  });
+  return guarded(idx->ctx, [&] { mm::index_save(idx, path); });
 }
 int mm_index_load(mm_ctx* ctx, const char* path, mm_index** out) {
-  if (!ctx || !path || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    auto* I = new mm_index;
-    I->ctx = ctx;
-    try { mm::index_load(ctx, path, I); } catch (...) { delete I; throw; }
-    *out = I;
-  });
+  if (!ctx || !path || !out) return refused(out);
+  return created(ctx, out, [&](mm_index& I) { mm::index_load(ctx, path, &I); });
 }
 void mm_index_destroy(mm_index* idx) { if (idx) { bind(idx->ctx); delete idx; } }
 int mm_index_get_info(const mm_index* idx, mm_index_info* out) {
@@ -442,21 +403,8 @@ int mm_index_freq_hist(mm_index* idx, int64_t* counts, int64_t* n_hashes, int64_
   for (auto& kv : idx->hist) { counts[i] = kv.first; n_hashes[i] = kv.second; ++i; }
   return MM_OK;
 }
-// winSketch.hpp:452-494 on an accumulated histogram.  `prev_threshold` is the threshold left by the previous
-// chunk (INT_MAX for the first): the reference keeps the old value when the loop breaks before assigning.
 int mm_freq_threshold_from_hist(const int64_t* counts, const int64_t* n_hashes, int64_t n, int64_t n_unique_hashes, int prev_threshold) {
-  int thr = prev_threshold;
-  if (n_unique_hashes <= 0) return thr;                        // :456 — empty lookup: nothing happens
-  float pct = 0.001f;                                          // :91
-  int64_t ignore = n_unique_hashes * pct / 100;                // :466 float arithmetic, truncated
-  int64_t sum = 0;
-  for (int64_t i = n - 1; i >= 0; --i) {                       // most frequent first
-    sum += n_hashes[i];
-    if (sum < ignore) thr = (int)counts[i];
-    else if (sum == ignore) { thr = (int)counts[i]; break; }
-    else break;
-  }
-  return thr;
+  return mm::stats::freq_threshold_from_hist(counts, n_hashes, n, n_unique_hashes, prev_threshold);
 }
 int mm_index_set_freq_threshold(mm_index* idx, int threshold) {
   if (!idx) return MM_ERR_ARG;
@@ -465,41 +413,11 @@ int mm_index_set_freq_threshold(mm_index* idx, int threshold) {
 }
 int mm_index_entries(mm_index* idx, uint32_t* hash, int32_t* contig, int32_t* wpos, int32_t* strand, int64_t cap) {
   if (!idx) return MM_ERR_ARG;
-  return guarded(idx->ctx, [&] {
-    MM_REQUIRE(cap >= idx->N, MM_ERR_ARG, "output capacity too small");
-    auto h = idx->pos.to_host(idx->ctx->stream, (size_t)idx->N);
-    int64_t c = 0;
-    for (int64_t i = 0; i < idx->N; ++i) {
-      while (c + 1 < (int64_t)idx->h_cstart.size() && (uint64_t)i >= idx->h_cstart[(size_t)c + 1]) ++c;
-      if (hash) hash[i] = h[(size_t)i].hash;
-      if (contig) contig[i] = (int32_t)c;
-      if (wpos) wpos[i] = mm::pw_wpos(h[(size_t)i].pw);
-      if (strand) strand[i] = mm::pw_strand(h[(size_t)i].pw);
-    }
-  });
+  return guarded(idx->ctx, [&] { mm::index_entries(idx, hash, contig, wpos, strand, cap); });
 }
-
 int mm_index_dup_neighbours(mm_index* idx, int32_t* prev_dist, int32_t* next_dist, int64_t cap) {
   if (!idx || !prev_dist || !next_dist) return MM_ERR_ARG;
-  return guarded(idx->ctx, [&] {
-    MM_REQUIRE(cap >= idx->N, MM_ERR_ARG, "output capacity too small");
-    if (idx->N == 0) return;
-    hipStream_t st = idx->ctx->stream;
-    auto h = idx->pos.to_host(st, (size_t)idx->N);
-    auto bits = idx->dup_bits.to_host(st), rank = idx->dup_rank.to_host(st);
-    auto dist = idx->dup_dist.to_host(st);
-    for (int64_t i = 0; i < idx->N; ++i) {
-      prev_dist[i] = 0; next_dist[i] = 0;
-      const uint32_t fl = h[(size_t)i].pw & (mm::PW_DP | mm::PW_DN);
-      const bool bit = (bits[(size_t)(i >> 6)] >> (i & 63)) & 1ull;
-      MM_REQUIRE(bit == (fl != 0), MM_ERR_DEVICE, "duplicate bitmap and entry flags disagree");
-      if (!fl) continue;
-      const uint64_t r = rank[(size_t)(i >> 6)] + (uint64_t)__builtin_popcountll(bits[(size_t)(i >> 6)] & ((1ull << (i & 63)) - 1ull));
-      MM_REQUIRE(r < dist.size(), MM_ERR_DEVICE, "duplicate rank out of range");
-      if (fl & mm::PW_DP) prev_dist[i] = (int32_t)(dist[(size_t)r] & 0xffffu);
-      if (fl & mm::PW_DN) next_dist[i] = (int32_t)(dist[(size_t)r] >> 16);
-    }
-  });
+  return guarded(idx->ctx, [&] { mm::index_dup_neighbours(idx, prev_dist, next_dist, cap); });
 }
 
 // ---- statistics ---------------------------------------------------------------------------------------
@@ -523,68 +441,47 @@ void mm_identity(int shared, int s, int k, float* ident, float* ident_upper) {
 
 // ---- mapping ------------------------------------------------------------------------------------------
 int mm_map_batch(mm_ctx* ctx, const mm_index* idx, const mm_seqset* reads, const mm_map_params* p, mm_mapping** out) {
-  if (!ctx || !idx || !reads || !p || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
+  if (!ctx || !idx || !reads || !p || !out) return refused(out);
+  return created(ctx, out, [&](mm_mapping& M) {
     MM_REQUIRE(idx->ctx->device == ctx->device, MM_ERR_ARG, "mm_map_batch: the index lives on another device than the context");
     MM_REQUIRE(reads->ctx->device == ctx->device, MM_ERR_ARG, "mm_map_batch: the reads live on another device than the context");
-    auto* M = new mm_mapping;
-    try { mm::map_batch(ctx, idx, reads, *p, M); } catch (...) { delete M; throw; }
-    *out = M;
+    mm::map_batch(ctx, idx, reads, *p, &M);
   });
 }
 int mm_map_batch_reusing(mm_ctx* ctx, const mm_index* idx, const mm_seqset* reads, const mm_map_params* p, const mm_mapping* sketch_of, mm_mapping** out) {
-  if (!ctx || !idx || !reads || !p || !sketch_of || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
+  if (!ctx || !idx || !reads || !p || !sketch_of || !out) return refused(out);
+  return created(ctx, out, [&](mm_mapping& M) {
     MM_REQUIRE(idx->ctx->device == ctx->device && reads->ctx->device == ctx->device && sketch_of->ctx->device == ctx->device, MM_ERR_ARG,
                "mm_map_batch_reusing: index, reads and donor mapping must live on the context's device");
     MM_REQUIRE(!sketch_of->released, MM_ERR_STATE, "mm_map_batch_reusing: the donor mapping has released its intermediates");
     MM_REQUIRE(sketch_of->n_reads == reads->count() && sketch_of->read_len == reads->len && sketch_of->params.k == p->k && sketch_of->params.w == p->w &&
                sketch_of->params.min_read_len == p->min_read_len, MM_ERR_ARG, "mm_map_batch_reusing: the donor mapping is of other reads or other parameters");
-    auto* M = new mm_mapping;
-    M->sketch_donor = sketch_of;
-    try { mm::map_batch(ctx, idx, reads, *p, M); } catch (...) { delete M; throw; }
-    M->sketch_donor = nullptr;
-    *out = M;
+    M.sketch_donor = sketch_of;
+    mm::map_batch(ctx, idx, reads, *p, &M);
+    M.sketch_donor = nullptr;
   });
 }
 int mm_sketch_batch(mm_ctx* ctx, const mm_seqset* reads, const mm_map_params* p, mm_mapping** out) {
-  if (!ctx || !reads || !p || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
+  if (!ctx || !reads || !p || !out) return refused(out);
+  return created(ctx, out, [&](mm_mapping& M) {
     MM_REQUIRE(reads->ctx->device == ctx->device, MM_ERR_ARG, "mm_sketch_batch: the reads live on another device than the context");
-    auto* M = new mm_mapping;
-    M->sketch_only = true;
-    try { mm::map_batch(ctx, nullptr, reads, *p, M); } catch (...) { delete M; throw; }
-    *out = M;
+    M.sketch_only = true;
+    mm::map_batch(ctx, nullptr, reads, *p, &M);
   });
 }
 int mm_map_batch_phased(mm_ctx* ctx, const mm_index* idx, const mm_seqset* reads, const mm_map_params* p, void (*at_stage)(void*, int), void* user, mm_mapping** out) {
-  if (!ctx || !idx || !reads || !p || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
+  if (!ctx || !idx || !reads || !p || !out) return refused(out);
+  return created(ctx, out, [&](mm_mapping& M) {
     MM_REQUIRE(idx->ctx->device == ctx->device, MM_ERR_ARG, "mm_map_batch_phased: the index lives on another device than the context");
     MM_REQUIRE(reads->ctx->device == ctx->device, MM_ERR_ARG, "mm_map_batch_phased: the reads live on another device than the context");
-    auto* M = new mm_mapping;
-    M->at_stage = at_stage; M->at_stage_user = user;
-    try { mm::map_batch(ctx, idx, reads, *p, M); } catch (...) { delete M; throw; }
-    *out = M;
+    M.at_stage = at_stage; M.at_stage_user = user;
+    mm::map_batch(ctx, idx, reads, *p, &M);
   });
 }
 void mm_mapping_destroy(mm_mapping* m) { if (m) { bind(m->ctx); delete m; } }
 int mm_mapping_release_intermediates(mm_mapping* m) {
   if (!m) return MM_ERR_ARG;
-  return guarded(m->ctx, [&] {
-    MM_HIP(hipSetDevice(m->ctx->device));
-    m->mz = mm::MinimizerSet{};
-    m->sk_hash.release(); m->sk_strand.release(); m->sk_n.release(); m->amb.release();
-    m->min_hits.release(); m->accept_min.release();
-    m->read_hit_off.release(); m->hits.release(); m->cand_off.release(); m->cand.release(); m->cand_read.release(); m->l2.release();
-    std::vector<int32_t>().swap(m->h_sk_n); std::vector<int32_t>().swap(m->h_min_hits);
-    std::vector<uint64_t>().swap(m->h_read_hit_off); std::vector<uint64_t>().swap(m->h_cand_off);
-    m->n_cand = 0; m->released = true;
-  });
+  return guarded(m->ctx, [&] { m->release_intermediates(); });
 }
 int mm_mapping_get_stats(const mm_mapping* m, mm_map_stats* out) {
   if (!m || !out) return MM_ERR_ARG;
@@ -610,227 +507,31 @@ int mm_mapping_fetch(mm_mapping* m, int64_t* offsets, mm_map_record* records, in
 int mm_mapping_add_qualities(mm_ctx* ctx, mm_mapping* m, const mm_seqset* reads, int k) {
   if (!ctx || !m) return MM_ERR_ARG;
   (void)reads;
-  return guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); mm::mapping_add_qualities(ctx, m, k); });
+  return guarded(ctx, [&] { mm::mapping_add_qualities(ctx, m, k); });
 }
-// read-wise concatenation of per-chunk record lists in chunk order (unifyFiles, mapWrap.h:128-132); small, done on the host
-// ---- read-wise merge of the records of several index chunks, chunk order preserved (unifyFiles, mapWrap.h:128-132) — on the device.
-// Rounds 1-3 merged on the host (download, a serial loop, upload), also for chunk indexes resident on ONE device.
-struct PartDev { const uint64_t* off; const mm_map_record* rec; int32_t base; int32_t pad; };
-__global__ void __launch_bounds__(256) merge_count_kernel(const PartDev* __restrict__ parts, int n_parts, int64_t n, uint64_t* __restrict__ cnt) {
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r > n) return;
-  uint64_t c = 0;
-  if (r < n) for (int p = 0; p < n_parts; ++p) c += parts[p].off[r + 1] - parts[p].off[r];
-  cnt[r] = c;
-}
-__global__ void __launch_bounds__(256) merge_copy_kernel(const PartDev* __restrict__ parts, int n_parts, int64_t n, const uint64_t* __restrict__ off,
-                                                         mm_map_record* __restrict__ out) {
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r >= n) return;
-  uint64_t o = off[r];
-  for (int p = 0; p < n_parts; ++p) {
-    const PartDev P = parts[p];
-    for (uint64_t i = P.off[r]; i < P.off[r + 1]; ++i) { mm_map_record x = P.rec[i]; x.ref_contig += P.base; out[o++] = x; }
-  }
-}
-static mm_mapping* merge_parts_device(mm_ctx* ctx, int64_t n, const std::vector<int32_t>& read_len, const mm_map_params& params, const std::vector<PartDev>& parts) {
-  hipStream_t st = ctx->stream;
-  auto* M = new mm_mapping;
-  try {
-    M->ctx = ctx; M->n_reads = n; M->params = params; M->read_len = read_len;
-    M->active.assign((size_t)n, 0);
-    M->stats = mm_map_stats{};
-    M->stats.n_reads = n;
-    for (int64_t r = 0; r < n; ++r) {
-      const int L = read_len[(size_t)r];
-      const bool ok = !(L < params.w || L < params.k || L < params.min_read_len);   // computeMap.hpp:137
-      M->active[(size_t)r] = ok;
-      if (ok) { M->stats.n_reads_long_enough++; M->stats.bases_long_enough += L; }
-    }
-    mm::DBuf<PartDev> d_parts(parts.size()); d_parts.upload(parts.data(), parts.size(), st);
-    mm::DBuf<uint64_t> cnt((size_t)n + 1);
-    M->rec_off.alloc((size_t)n + 1);
-    const unsigned gb = (unsigned)mm::ceil_div(n + 1, 256);
-    merge_count_kernel<<<dim3(gb), dim3(256), 0, st>>>(d_parts.p, (int)parts.size(), n, cnt.p);
-    MM_KERNEL_CHECK();
-    mm::DBuf<uint8_t> tmp;
-    mm::exclusive_scan(tmp, cnt.p, M->rec_off.p, (size_t)n + 1, st);
-    M->h_rec_off = M->rec_off.to_host(st);
-    M->n_rec = (int64_t)M->h_rec_off[(size_t)n];
-    M->rec.alloc(std::max<size_t>((size_t)M->n_rec, 1));
-    if (n > 0 && M->n_rec > 0) {
-      merge_copy_kernel<<<dim3((unsigned)mm::ceil_div(n, 256)), dim3(256), 0, st>>>(d_parts.p, (int)parts.size(), n, M->rec_off.p, M->rec.p);
-      MM_KERNEL_CHECK();
-    }
-    M->d_read_len.alloc((size_t)std::max<int64_t>(n, 1)); M->d_read_len.upload(M->read_len.data(), (size_t)n, st);
-    M->stats.n_mappings = M->n_rec;
-    for (int64_t r = 0; r < n; ++r) if (M->h_rec_off[(size_t)r + 1] > M->h_rec_off[(size_t)r]) M->stats.n_reads_mapped++;
-    M->released = true;                                          // records only: the debug taps have nothing to show
-    MM_HIP(mm::stream_sync(st));
-  } catch (...) { delete M; throw; }
-  return M;
-}
-static void add_part_stats(mm_mapping* M, mm_mapping* const* parts, int n_parts) {   // work counters and stage times: summed over the chunks; per-read facts: of chunk 0
-  for (int p = 0; p < n_parts; ++p) {
-    const mm_map_stats& S = parts[p]->stats;
-    M->stats.sum_hits += S.sum_hits; M->stats.n_candidates += S.n_candidates; M->stats.sum_hits_kept += S.sum_hits_kept;
-    M->stats.sum_l2_stream_entries += S.sum_l2_stream_entries; M->stats.sum_l2_evals += S.sum_l2_evals;
-    M->stats.n_l2_rebuilds += S.n_l2_rebuilds; M->stats.n_l2_wide_redo += S.n_l2_wide_redo;
-    M->stats.ms_minimizer += S.ms_minimizer; M->stats.ms_sketch += S.ms_sketch; M->stats.ms_probe_gather += S.ms_probe_gather;
-    M->stats.ms_sort_hits += S.ms_sort_hits; M->stats.ms_l1_scan += S.ms_l1_scan; M->stats.ms_l2 += S.ms_l2; M->stats.ms_compact += S.ms_compact;
-    M->stats.ms_total += S.ms_total; M->stats.ms_hit_filter += S.ms_hit_filter;
-  }
-  if (n_parts > 0) {
-    M->stats.sum_sketch = parts[0]->stats.sum_sketch; M->stats.n_ambiguous_sketch_reads = parts[0]->stats.n_ambiguous_sketch_reads;
-    M->stats.n_reads_giant = parts[0]->stats.n_reads_giant;
-  }
-}
-// Parts may live in any context of this process: those of another DEVICE come over with a peer copy (xGMI), nothing is staged on the host.
+// ---- read-wise merge of chunk mappings (mm_merge.hip) --------------------------------------------------
 int mm_mapping_concat(mm_ctx* ctx, mm_mapping* const* parts, const int32_t* contig_base, int n_parts, mm_mapping** out) {
-  if (!ctx || !parts || n_parts <= 0 || !out) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    const int64_t n = parts[0]->n_reads;
-    std::vector<PartDev> pv((size_t)n_parts);
-    std::vector<mm::DBuf<uint64_t>> t_off((size_t)n_parts); std::vector<mm::DBuf<mm_map_record>> t_rec((size_t)n_parts);
-    for (int p = 0; p < n_parts; ++p) {
-      mm_mapping* P = parts[p];
-      MM_REQUIRE(P->n_reads == n, MM_ERR_ARG, "chunk results cover different read sets");
-      MM_REQUIRE(!P->sketch_only && P->rec_off.p && (P->n_rec == 0 || P->rec.p), MM_ERR_STATE, "mm_mapping_concat: a part holds no records (a mm_sketch_batch result is no chunk mapping)");
-      pv[(size_t)p] = PartDev{P->rec_off.p, P->rec.p, contig_base ? contig_base[p] : 0, 0};
-      if (P->ctx->device != ctx->device) {                       // (the part's own stream has been waited for by the call that made it)
-        t_off[(size_t)p].alloc((size_t)n + 1); t_rec[(size_t)p].alloc(std::max<size_t>((size_t)P->n_rec, 1));
-        MM_HIP(hipMemcpyPeerAsync(t_off[(size_t)p].p, ctx->device, P->rec_off.p, P->ctx->device, sizeof(uint64_t) * ((size_t)n + 1), ctx->stream));
-        if (P->n_rec > 0) MM_HIP(hipMemcpyPeerAsync(t_rec[(size_t)p].p, ctx->device, P->rec.p, P->ctx->device, sizeof(mm_map_record) * (size_t)P->n_rec, ctx->stream));
-        pv[(size_t)p].off = t_off[(size_t)p].p; pv[(size_t)p].rec = t_rec[(size_t)p].p;
-      }
-    }
-    mm_mapping* M = merge_parts_device(ctx, n, parts[0]->read_len, parts[0]->params, pv);
-    add_part_stats(M, parts, n_parts);
-    *out = M;
-  });
+  if (!ctx || !parts || n_parts <= 0 || !out) return refused(out);
+  return created(ctx, out, [&](mm_mapping& M) { mm::mapping_concat(ctx, parts, contig_base, n_parts, &M); });
 }
 int mm_mapping_from_parts(mm_ctx* ctx, int64_t n_reads, const int32_t* read_len, const mm_map_params* p, int n_parts,
                           const int64_t* const* offsets, const mm_map_record* const* records, const int32_t* contig_base, mm_mapping** out) {
-  if (!ctx || n_reads < 0 || (!read_len && n_reads > 0) || !p || n_parts <= 0 || !offsets || !records || !out) return MM_ERR_ARG;
-  for (int i = 0; i < n_parts; ++i) if (!offsets[i] || (!records[i] && offsets[i][n_reads] > 0)) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    std::vector<int32_t> len(read_len, read_len + n_reads);
-    std::vector<PartDev> pv((size_t)n_parts);
-    std::vector<mm::DBuf<uint64_t>> t_off((size_t)n_parts); std::vector<mm::DBuf<mm_map_record>> t_rec((size_t)n_parts);
-    for (int i = 0; i < n_parts; ++i) {
-      const size_t nr = (size_t)offsets[i][n_reads];
-      t_off[(size_t)i].alloc((size_t)n_reads + 1); t_off[(size_t)i].upload((const uint64_t*)offsets[i], (size_t)n_reads + 1, ctx->stream);
-      t_rec[(size_t)i].alloc(std::max<size_t>(nr, 1)); t_rec[(size_t)i].upload(records[i], nr, ctx->stream);
-      pv[(size_t)i] = PartDev{t_off[(size_t)i].p, t_rec[(size_t)i].p, contig_base ? contig_base[i] : 0, 0};
-    }
-    *out = merge_parts_device(ctx, n_reads, len, *p, pv);
-  });
+  if (!ctx || n_reads < 0 || (!read_len && n_reads > 0) || !p || n_parts <= 0 || !offsets || !records || !out) return refused(out);
+  for (int i = 0; i < n_parts; ++i) if (!offsets[i] || (!records[i] && offsets[i][n_reads] > 0)) return refused(out);
+  return created(ctx, out, [&](mm_mapping& M) { mm::mapping_from_parts(ctx, n_reads, read_len, *p, n_parts, offsets, records, contig_base, &M); });
 }
-// The same exchange between the ranks of a communicator (one process per GPU, or one thread per GPU of one process): ncclSend / ncclRecv of the
-// offsets, then of the records, straight between the devices.  Collective: every rank calls it for the same batch.
 int mm_mapping_gather(mm_ctx* ctx, int owner, int64_t n_reads, const int32_t* read_len, const mm_map_params* p, mm_mapping* const* parts, const int32_t* chunk_id,
                       int n_parts, int n_chunks, const int32_t* chunk_rank, const int32_t* contig_base, mm_mapping** out) {
-  if (!ctx || !p || n_reads < 0 || (!read_len && n_reads > 0) || n_parts < 0 || (n_parts > 0 && (!parts || !chunk_id)) || n_chunks <= 0 || !chunk_rank || !out) return MM_ERR_ARG;
-  *out = nullptr;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int rank = ctx->comm ? ctx->comm_rank : 0, nranks = ctx->comm ? ctx->comm_size : 1;
-    MM_REQUIRE(owner >= 0 && owner < nranks, MM_ERR_ARG, "mm_mapping_gather: owner is no rank of the communicator");
-    ncclComm_t comm = (ncclComm_t)ctx->comm;
-    const bool self_send = getenv("MM_GATHER_SELF_SEND") != nullptr && comm;   // test hook: the owner's own parts go through ncclSend / ncclRecv too
-    auto nccl_ok = [&](ncclResult_t rc, const char* what) { MM_REQUIRE(rc == ncclSuccess, MM_ERR_COMM, std::string(what) + ": " + ncclGetErrorString(rc)); };
-    std::vector<int> part_of((size_t)n_chunks, -1);              // chunk -> index into parts[] (this rank's chunks)
-    for (int i = 0; i < n_parts; ++i) {
-      MM_REQUIRE(chunk_id[i] >= 0 && chunk_id[i] < n_chunks && chunk_rank[chunk_id[i]] == rank && parts[i] && parts[i]->n_reads == n_reads, MM_ERR_ARG, "mm_mapping_gather: a part is not a chunk of this rank");
-      MM_REQUIRE(parts[i]->ctx->device == ctx->device, MM_ERR_ARG, "mm_mapping_gather: parts live on the rank's own device");
-      MM_REQUIRE(!parts[i]->sketch_only && parts[i]->rec_off.p && (parts[i]->n_rec == 0 || parts[i]->rec.p), MM_ERR_STATE, "mm_mapping_gather: a part holds no records (a mm_sketch_batch result is no chunk mapping)");
-      part_of[(size_t)chunk_id[i]] = i;
-    }
-    for (int c = 0; c < n_chunks; ++c) MM_REQUIRE(chunk_rank[c] != rank || part_of[(size_t)c] >= 0, MM_ERR_ARG, "mm_mapping_gather: a chunk of this rank has no part");
-    const size_t n1 = (size_t)n_reads + 1;
-    if (rank != owner) {                                         // my chunks, ascending: all offset arrays, then all record arrays
-      MM_REQUIRE(comm, MM_ERR_STATE, "mm_mapping_gather needs a communicator (mm_comm_init)");
-      nccl_ok(ncclGroupStart(), "ncclGroupStart");
-      for (int c = 0; c < n_chunks; ++c) if (chunk_rank[c] == rank) nccl_ok(ncclSend(parts[part_of[(size_t)c]]->rec_off.p, n1, ncclUint64, owner, comm, st), "ncclSend");
-      nccl_ok(ncclGroupEnd(), "ncclGroupEnd");
-      nccl_ok(ncclGroupStart(), "ncclGroupStart");
-      for (int c = 0; c < n_chunks; ++c) if (chunk_rank[c] == rank) { mm_mapping* P = parts[part_of[(size_t)c]]; if (P->n_rec > 0) nccl_ok(ncclSend(P->rec.p, sizeof(mm_map_record) * (size_t)P->n_rec, ncclInt8, owner, comm, st), "ncclSend"); }
-      nccl_ok(ncclGroupEnd(), "ncclGroupEnd");
-      MM_HIP(mm::stream_sync(st));
-      return;
-    }
-    std::vector<mm::DBuf<uint64_t>> t_off((size_t)n_chunks); std::vector<mm::DBuf<mm_map_record>> t_rec((size_t)n_chunks);
-    auto remote = [&](int c) { return chunk_rank[c] != rank || self_send; };
-    bool any_remote = false;
-    for (int c = 0; c < n_chunks; ++c) any_remote = any_remote || remote(c);
-    std::vector<uint64_t> n_rec_of((size_t)n_chunks, 0);
-    if (any_remote) {
-      MM_REQUIRE(comm, MM_ERR_STATE, "mm_mapping_gather needs a communicator (mm_comm_init)");
-      nccl_ok(ncclGroupStart(), "ncclGroupStart");
-      for (int c = 0; c < n_chunks; ++c) {
-        if (!remote(c)) continue;
-        t_off[(size_t)c].alloc(n1);
-        if (chunk_rank[c] == rank) nccl_ok(ncclSend(parts[part_of[(size_t)c]]->rec_off.p, n1, ncclUint64, rank, comm, st), "ncclSend");
-        nccl_ok(ncclRecv(t_off[(size_t)c].p, n1, ncclUint64, chunk_rank[c], comm, st), "ncclRecv");
-      }
-      nccl_ok(ncclGroupEnd(), "ncclGroupEnd");
-      for (int c = 0; c < n_chunks; ++c) if (remote(c)) t_off[(size_t)c].download(&n_rec_of[(size_t)c], 1, st, (size_t)n_reads);
-      MM_HIP(mm::stream_sync(st));
-      nccl_ok(ncclGroupStart(), "ncclGroupStart");
-      for (int c = 0; c < n_chunks; ++c) {
-        if (!remote(c) || n_rec_of[(size_t)c] == 0) continue;
-        t_rec[(size_t)c].alloc((size_t)n_rec_of[(size_t)c]);
-        if (chunk_rank[c] == rank) nccl_ok(ncclSend(parts[part_of[(size_t)c]]->rec.p, sizeof(mm_map_record) * (size_t)n_rec_of[(size_t)c], ncclInt8, rank, comm, st), "ncclSend");
-        nccl_ok(ncclRecv(t_rec[(size_t)c].p, sizeof(mm_map_record) * (size_t)n_rec_of[(size_t)c], ncclInt8, chunk_rank[c], comm, st), "ncclRecv");
-      }
-      nccl_ok(ncclGroupEnd(), "ncclGroupEnd");
-    }
-    std::vector<PartDev> pv((size_t)n_chunks);
-    for (int c = 0; c < n_chunks; ++c) {
-      const int32_t base = contig_base ? contig_base[c] : 0;
-      if (remote(c)) pv[(size_t)c] = PartDev{t_off[(size_t)c].p, t_rec[(size_t)c].p, base, 0};
-      else { mm_mapping* P = parts[part_of[(size_t)c]]; pv[(size_t)c] = PartDev{P->rec_off.p, P->rec.p, base, 0}; }
-    }
-    std::vector<int32_t> len(read_len, read_len + n_reads);
-    *out = merge_parts_device(ctx, n_reads, len, *p, pv);
-    if (*out) {
-      std::vector<mm_mapping*> mine(parts, parts + n_parts);
-      add_part_stats(*out, mine.data(), n_parts);                // (of the owner's own chunks: the counters of the other ranks stay with them)
-    }
+  if (!ctx || !p || n_reads < 0 || (!read_len && n_reads > 0) || n_parts < 0 || (n_parts > 0 && (!parts || !chunk_id)) || n_chunks <= 0 || !chunk_rank || !out) return refused(out);
+  return adopted(ctx, out, [&]() -> mm_mapping* {               // (NULL without an error on every rank but the owner)
+    std::unique_ptr<mm_mapping> M(new mm_mapping);
+    return mm::mapping_gather(ctx, owner, n_reads, read_len, *p, parts, chunk_id, n_parts, n_chunks, chunk_rank, contig_base, M.get()) ? M.release() : nullptr;
   });
 }
 
 int mm_mapping_keep_best(mm_ctx* ctx, mm_mapping* m, int k) {
   if (!ctx || !m) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    // default (non --all) reporting, computeMap.hpp:546-587: per read keep the mappings whose (float) identity is
-    // >= best - 1.0; the comparison happens in double exactly as there.  Record lists are small: host side.
-    std::vector<mm_map_record> recs((size_t)m->n_rec), kept;
-    m->rec.download(recs.data(), recs.size(), ctx->stream);
-    MM_HIP(mm::stream_sync(ctx->stream));
-    std::vector<uint64_t> off((size_t)m->n_reads + 1, 0);
-    int64_t mapped = 0;
-    for (int64_t r = 0; r < m->n_reads; ++r) {
-      const uint64_t a = m->h_rec_off[(size_t)r], b = m->h_rec_off[(size_t)r + 1];
-      float best = 0;
-      std::vector<float> id((size_t)(b - a));
-      for (uint64_t i = a; i < b; ++i) {
-        float ub; mm::stats::identity(recs[(size_t)i].shared, recs[(size_t)i].sketch, k, &id[(size_t)(i - a)], &ub);
-        if (id[(size_t)(i - a)] > best) best = id[(size_t)(i - a)];
-      }
-      for (uint64_t i = a; i < b; ++i) if (id[(size_t)(i - a)] >= best - 1.0) kept.push_back(recs[(size_t)i]);
-      off[(size_t)r + 1] = kept.size();
-      if (off[(size_t)r + 1] > off[(size_t)r]) ++mapped;
-    }
-    m->n_rec = (int64_t)kept.size();
-    m->rec.alloc(std::max<size_t>(kept.size(), 1)); m->rec.upload(kept.data(), kept.size(), ctx->stream);
-    m->rec_off.upload(off.data(), off.size(), ctx->stream);
-    m->h_rec_off = off;
-    m->stats.n_mappings = m->n_rec; m->stats.n_reads_mapped = mapped;
-    MM_HIP(mm::stream_sync(ctx->stream));
-  });
+  return guarded(ctx, [&] { mm::mapping_keep_best(ctx, m, k); });
 }
 
 int mm_debug_sketch(mm_mapping* m, int64_t* offsets, uint32_t* hash, int32_t* strand, int64_t cap) {
@@ -901,32 +602,19 @@ int mm_debug_min_hits(mm_mapping* m, int32_t* min_hits) {
 int mm_debug_probed_lists(mm_mapping* m, const mm_index* idx, int64_t* hist, int32_t n_bins) {
   if (m && m->released) return MM_ERR_STATE;
   if (!m || !idx || !hist || n_bins < 3) return MM_ERR_ARG;
-  return guarded(m->ctx, [&] {
-    MM_HIP(hipSetDevice(m->ctx->device));
-    mm::probed_list_hist(m->ctx, idx, m, n_bins, hist);
-  });
+  return guarded(m->ctx, [&] { mm::probed_list_hist(m->ctx, idx, m, n_bins, hist); });
 }
 
 // ---- EM -----------------------------------------------------------------------------------------------
 int mm_em_create(mm_ctx* ctx, int64_t n_reads, const int64_t* read_off, const int32_t* taxon, const double* mapq, const double* inv_nloc,
                  int32_t n_taxa, mm_em** out) {
-  if (!ctx || !read_off || !out || n_reads < 0 || n_taxa <= 0) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    auto* E = new mm_em;
-    try { mm::em_create(ctx, n_reads, read_off, taxon, mapq, inv_nloc, n_taxa, E); } catch (...) { delete E; throw; }
-    *out = E;
-  });
+  if (!ctx || !read_off || !out || n_reads < 0 || n_taxa <= 0) return refused(out);
+  return created(ctx, out, [&](mm_em& E) { mm::em_create(ctx, n_reads, read_off, taxon, mapq, inv_nloc, n_taxa, &E); });
 }
 int mm_em_create_from_mapping(mm_ctx* ctx, const mm_mapping* m, const int32_t* contig_taxon, const int32_t* contig_len, int32_t n_contigs,
                               int32_t n_taxa, mm_em** out) {
-  if (!ctx || !m || !contig_taxon || !contig_len || !out || n_contigs < 0 || n_taxa <= 0) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    auto* E = new mm_em;
-    try { mm::em_create_from_mapping(ctx, m, contig_taxon, contig_len, n_contigs, n_taxa, E); } catch (...) { delete E; throw; }
-    *out = E;
-  });
+  if (!ctx || !m || !contig_taxon || !contig_len || !out || n_contigs < 0 || n_taxa <= 0) return refused(out);
+  return created(ctx, out, [&](mm_em& E) { mm::em_create_from_mapping(ctx, m, contig_taxon, contig_len, n_contigs, n_taxa, &E); });
 }
 int mm_em_taxon_counts(mm_em* em, int64_t* counts) {
   if (!em || !counts) return MM_ERR_ARG;
@@ -945,20 +633,19 @@ int mm_em_sizes(const mm_em* em, int64_t* n_reads, int64_t* n_entries, int32_t* 
 void mm_em_destroy(mm_em* em) { if (em) { bind(em->ctx); delete em; } }
 int mm_em_iterate(mm_em* em, const double* f, double* f_partial, double* ll_partial) {
   if (!em || !f || !f_partial || !ll_partial) return MM_ERR_ARG;
-  return guarded(em->ctx, [&] { MM_HIP(hipSetDevice(em->ctx->device)); mm::em_iterate(em, f, f_partial, ll_partial); });
+  return guarded(em->ctx, [&] { mm::em_iterate(em, f, f_partial, ll_partial); });
 }
 int mm_em_iterate_allreduce(mm_em* em, const double* f, double* f_next, double* ll) {
   if (!em || !f || !f_next || !ll) return MM_ERR_ARG;
-  return guarded(em->ctx, [&] { MM_HIP(hipSetDevice(em->ctx->device)); mm::em_iterate_allreduce(em, f, f_next, ll); });
+  return guarded(em->ctx, [&] { mm::em_iterate_allreduce(em, f, f_next, ll); });
 }
 int mm_em_run(mm_em* em, const double* f0, int max_iter, double* f_out, double* ll_trace, int ll_cap, int* n_iter) {
   if (!em || !f0 || max_iter <= 0 || !n_iter) return MM_ERR_ARG;
-  return guarded(em->ctx, [&] { MM_HIP(hipSetDevice(em->ctx->device)); *n_iter = mm::em_run(em, f0, max_iter, f_out, ll_trace, ll_cap, nullptr); });
+  return guarded(em->ctx, [&] { *n_iter = mm::em_run(em, f0, max_iter, f_out, ll_trace, ll_cap, nullptr); });
 }
 int mm_em_continue(mm_em* em, int max_iter, double* f_out, double* ll_trace, int ll_cap, int* n_iter, int* stopped) {
   if (!em || max_iter <= 0 || !n_iter) return MM_ERR_ARG;
   return guarded(em->ctx, [&] {
-    MM_HIP(hipSetDevice(em->ctx->device));
     bool st = false;
     *n_iter = mm::em_run(em, nullptr, max_iter, f_out, ll_trace, ll_cap, &st);
     if (stopped) *stopped = st ? 1 : 0;
@@ -966,17 +653,17 @@ int mm_em_continue(mm_em* em, int max_iter, double* f_out, double* ll_trace, int
 }
 int mm_em_posteriors(mm_em* em, const double* f, double* post, int64_t* best) {
   if (!em || !f) return MM_ERR_ARG;
-  return guarded(em->ctx, [&] { MM_HIP(hipSetDevice(em->ctx->device)); mm::em_posteriors(em, f, post, best); });
+  return guarded(em->ctx, [&] { mm::em_posteriors(em, f, post, best); });
 }
 int mm_em_bootstrap(mm_em* em, const double* f_start, int32_t rep0, int32_t n_rep, uint64_t seed, const uint8_t* weights,
                     int max_iter, double* f_out, double* ll_out, int32_t* n_iter, int32_t* stopped) {
   if (!em || !f_start || n_rep <= 0 || rep0 < 0 || (int64_t)rep0 + n_rep - 1 > INT32_MAX || max_iter <= 0 || !f_out || !ll_out || !n_iter || !stopped) return MM_ERR_ARG;
-  return guarded(em->ctx, [&] { MM_HIP(hipSetDevice(em->ctx->device)); mm::boot_run(em, f_start, rep0, n_rep, seed, weights, max_iter, f_out, ll_out, n_iter, stopped); });
+  return guarded(em->ctx, [&] { mm::boot_run(em, f_start, rep0, n_rep, seed, weights, max_iter, f_out, ll_out, n_iter, stopped); });
 }
 int mm_em_lca(mm_em* em, const double* f, int32_t n_nodes, const int32_t* parent, const int32_t* taxon_node, double threshold,
               int32_t* node_out, double* mass_out, int64_t* direct_out) {
   if (!em || !f || !parent || !taxon_node || !node_out || n_nodes <= 0) return MM_ERR_ARG;
-  return guarded(em->ctx, [&] { MM_HIP(hipSetDevice(em->ctx->device)); mm::lca_run(em, f, n_nodes, parent, taxon_node, threshold, node_out, mass_out, direct_out); });
+  return guarded(em->ctx, [&] { mm::lca_run(em, f, n_nodes, parent, taxon_node, threshold, node_out, mass_out, direct_out); });
 }
 int mm_gene_overlap(mm_ctx* ctx, int32_t n_contigs, const int64_t* contig_gene_off, const int32_t* gene_start, const int32_t* gene_stop,
                     const int32_t* gene_group, int32_t n_groups, const int64_t* group_feat_off, const int32_t* group_feat, int32_t n_feats,
@@ -984,7 +671,6 @@ int mm_gene_overlap(mm_ctx* ctx, int32_t n_contigs, const int64_t* contig_gene_o
                     int64_t* group_reads, double* group_median, int64_t* feat_reads, int64_t* maps_on_annotated) {
   if (!ctx) return MM_ERR_ARG;
   return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
     MM_REQUIRE(n_contigs >= 0 && n_groups >= 0 && n_feats >= 0 && n_maps >= 0 && contig_gene_off && group_feat_off, MM_ERR_ARG, "mm_gene_overlap: a negative size or no offsets");
     const int64_t ng = n_contigs > 0 ? contig_gene_off[n_contigs] : 0;
     MM_REQUIRE((ng <= 0 || (gene_start && gene_stop && gene_group)) && (n_maps == 0 || (map_contig && map_start && map_stop && map_ident)) &&
@@ -999,7 +685,6 @@ int mm_ident_filter(mm_ctx* ctx, int64_t n_reads, const int64_t* read_off, const
                     int64_t* n_entries_out) {
   if (!ctx) return MM_ERR_ARG;
   return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
     MM_REQUIRE(n_reads >= 0 && n_taxa >= 0 && read_off && n_with_entries && n_le, MM_ERR_ARG, "mm_ident_filter: a negative size, no offsets or no counts");
     const int n_filtered = (read_src != nullptr) + (entry_src != nullptr) + (read_off_out != nullptr) + (n_reads_out != nullptr) + (n_entries_out != nullptr);
     MM_REQUIRE(n_filtered == 0 || n_filtered == 5, MM_ERR_ARG, "mm_ident_filter: the outputs of the filtered problem are null as a group or not at all");
@@ -1014,9 +699,7 @@ int mm_edit_infix(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* referenc
                   const int32_t* contig, const int64_t* ws, const int64_t* we, const int32_t* max_dist, int32_t* dist_out, int64_t* begin_out, int64_t* end_out) {
   if (!ctx || !reads || !reference) return MM_ERR_ARG;
   return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    MM_REQUIRE(n_jobs >= 0 && n_jobs < ((int64_t)1 << 31), n_jobs < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_edit_infix: a negative number of jobs, or 2^31 or more");
-    MM_REQUIRE(n_jobs == 0 || (read && strand && contig && ws && we && max_dist && dist_out && begin_out && end_out), MM_ERR_ARG, "mm_edit_infix: a null array");
+    require_jobs("mm_edit_infix", n_jobs, read && strand && contig && ws && we && max_dist && dist_out && begin_out && end_out);
     mm::edit_infix_run(ctx, reads, reference, mm::EditInfixIn{n_jobs, read, strand, contig, ws, we, max_dist}, dist_out, begin_out, end_out);
   });
 }
@@ -1024,35 +707,24 @@ int mm_mapping_edit_distances(mm_ctx* ctx, const mm_mapping* mapping, const mm_s
                               int32_t* dist_out, int64_t* first_out, int64_t* last_out, int64_t cap) {
   if (!ctx || !mapping || !reads || !reference) return MM_ERR_ARG;
   return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    MM_REQUIRE(mapping->n_rec < ((int64_t)1 << 31), MM_ERR_LIMIT, "mm_mapping_edit_distances: 2^31 records or more");
-    MM_REQUIRE(mapping->n_rec == 0 || (dist_out && first_out && last_out), MM_ERR_ARG, "mm_mapping_edit_distances: a null array");
+    require_records("mm_mapping_edit_distances", mapping->n_rec, dist_out && first_out && last_out);
     mm::edit_mapping_run(ctx, mapping, reads, reference, perc_identity, dist_out, first_out, last_out, cap);
   });
 }
 struct mm_alignment { mm::EditAlignment a; };                      // (host memory only: nothing of the device's outlives the call that made it)
 int mm_edit_infix_align(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand,
                         const int32_t* contig, const int64_t* ws, const int64_t* we, const int32_t* max_dist, mm_alignment** out) {
-  if (!ctx || !reads || !reference || !out) return MM_ERR_ARG;
-  *out = nullptr;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    MM_REQUIRE(n_jobs >= 0 && n_jobs < ((int64_t)1 << 31), n_jobs < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_edit_infix_align: a negative number of jobs, or 2^31 or more");
-    MM_REQUIRE(n_jobs == 0 || (read && strand && contig && ws && we && max_dist), MM_ERR_ARG, "mm_edit_infix_align: a null array");
-    std::unique_ptr<mm_alignment> al(new mm_alignment());
-    mm::edit_infix_align_run(ctx, reads, reference, mm::EditInfixIn{n_jobs, read, strand, contig, ws, we, max_dist}, &al->a);
-    *out = al.release();
+  if (!ctx || !reads || !reference || !out) return refused(out);
+  return created(ctx, out, [&](mm_alignment& al) {
+    require_jobs("mm_edit_infix_align", n_jobs, read && strand && contig && ws && we && max_dist);
+    mm::edit_infix_align_run(ctx, reads, reference, mm::EditInfixIn{n_jobs, read, strand, contig, ws, we, max_dist}, &al.a);
   });
 }
 int mm_mapping_align(mm_ctx* ctx, const mm_mapping* mapping, const mm_seqset* reads, const mm_seqset* reference, float perc_identity, mm_alignment** out) {
-  if (!ctx || !mapping || !reads || !reference || !out) return MM_ERR_ARG;
-  *out = nullptr;
-  return guarded(ctx, [&] {
-    MM_HIP(hipSetDevice(ctx->device));
-    MM_REQUIRE(mapping->n_rec < ((int64_t)1 << 31), MM_ERR_LIMIT, "mm_mapping_align: 2^31 records or more");
-    std::unique_ptr<mm_alignment> al(new mm_alignment());
-    mm::edit_mapping_align_run(ctx, mapping, reads, reference, perc_identity, &al->a);
-    *out = al.release();
+  if (!ctx || !mapping || !reads || !reference || !out) return refused(out);
+  return created(ctx, out, [&](mm_alignment& al) {
+    require_records("mm_mapping_align", mapping->n_rec, true);
+    mm::edit_mapping_align_run(ctx, mapping, reads, reference, perc_identity, &al.a);
   });
 }
 int mm_alignment_sizes(const mm_alignment* al, int64_t* n_jobs, int64_t* n_ops) {
@@ -1074,7 +746,7 @@ struct mm_bam { mm::BamMembers b; };                               // (host memo
 int mm_bam_encode(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
                   const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint16_t* flag, const uint8_t* mapq,
                   const int64_t* name_off, const char* names, int64_t group_bytes, mm_bam** out) {
-  if (!ctx || !reads || !reference || !out) return MM_ERR_ARG;
+  if (!ctx || !reads || !reference || !out) return refused(out);
   return created(ctx, out, [&](mm_bam& b) {
     require_jobs("mm_bam_encode", n_jobs, read && strand && contig && dist && first && op_off && flag && mapq && name_off);
     mm::bam_encode_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, mm::BamColumns{flag, mapq, name_off, names}, group_bytes, &b.b);
@@ -1096,14 +768,14 @@ struct mm_pileup { mm::KeyTable t; };                              // (host memo
 struct mm_pileup_result { mm::PileupResult r; };
 int mm_pileup_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
                      const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, mm_pileup** out) {
-  if (!ctx || !reads || !reference || !out) return MM_ERR_ARG;
+  if (!ctx || !reads || !reference || !out) return refused(out);
   return created(ctx, out, [&](mm_pileup& t) {
     require_jobs("mm_pileup_events", n_jobs, read && strand && contig && dist && first && op_off && use);
     mm::pileup_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, &t.t);
   });
 }
 int mm_pileup_merge(mm_ctx* ctx, int64_t n, const uint64_t* keys, const uint32_t* counts, mm_pileup** out) {
-  if (!ctx || !out) return MM_ERR_ARG;
+  if (!ctx || !out) return refused(out);
   return created(ctx, out, [&](mm_pileup& t) {
     require_rows("mm_pileup_merge", "pairs", n, keys && counts);
     mm::merge_run(ctx, n, keys, nullptr, counts, "mm_pileup_merge", "MM_PILEUP_TIMING", &t.t);
@@ -1118,7 +790,7 @@ int mm_pileup_fetch(const mm_pileup* t, uint64_t* keys, uint32_t* counts) { retu
 void mm_pileup_destroy(mm_pileup* t) { delete t; }
 int mm_pileup_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* keys, const uint32_t* counts, int64_t n_iv, const int32_t* iv_contig,
                      const int64_t* iv_first, const int64_t* iv_last, int64_t min_count, double min_frac, mm_pileup_result** out) {
-  if (!ctx || !reference || !out) return MM_ERR_ARG;
+  if (!ctx || !reference || !out) return refused(out);
   return created(ctx, out, [&](mm_pileup_result& r) {
     require_finish("mm_pileup_finish", n, n_iv, keys && counts, iv_contig && iv_first && iv_last);
     mm::pileup_finish_run(ctx, reference, mm::FinishIn{n, keys, nullptr, counts, n_iv, iv_contig, iv_first, iv_last, min_count, min_frac}, &r.r);
@@ -1147,14 +819,14 @@ struct mm_vcf { mm::KeyTable t; };                                 // (host memo
 struct mm_vcf_result { mm::VcfResult r; };
 int mm_vcf_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
                   const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, mm_vcf** out) {
-  if (!ctx || !reads || !reference || !out) return MM_ERR_ARG;
+  if (!ctx || !reads || !reference || !out) return refused(out);
   return created(ctx, out, [&](mm_vcf& t) {
     require_jobs("mm_vcf_events", n_jobs, read && strand && contig && dist && first && op_off && use);
     mm::vcf_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, &t.t);
   });
 }
 int mm_vcf_merge(mm_ctx* ctx, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, mm_vcf** out) {
-  if (!ctx || !out) return MM_ERR_ARG;
+  if (!ctx || !out) return refused(out);
   return created(ctx, out, [&](mm_vcf& t) {
     require_rows("mm_vcf_merge", "triples", n, w0 && w1 && counts);
     mm::merge_run(ctx, n, w0, w1, counts, "mm_vcf_merge", "MM_VCF_TIMING", &t.t);
@@ -1169,7 +841,7 @@ int mm_vcf_fetch(const mm_vcf* t, uint64_t* w0, uint64_t* w1, uint32_t* counts) 
 void mm_vcf_destroy(mm_vcf* t) { delete t; }
 int mm_vcf_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, int64_t n_iv, const int32_t* iv_contig,
                   const int64_t* iv_first, const int64_t* iv_last, int64_t min_count, double min_frac, mm_vcf_result** out) {
-  if (!ctx || !reference || !out) return MM_ERR_ARG;
+  if (!ctx || !reference || !out) return refused(out);
   return created(ctx, out, [&](mm_vcf_result& r) {
     require_finish("mm_vcf_finish", n, n_iv, w0 && w1 && counts, iv_contig && iv_first && iv_last);
     mm::vcf_finish_run(ctx, reference, mm::FinishIn{n, w0, w1, counts, n_iv, iv_contig, iv_first, iv_last, min_count, min_frac}, &r.r);
@@ -1200,14 +872,7 @@ int mm_comm_init(mm_ctx* ctx, const char id[MM_COMM_ID_BYTES], int rank, int nra
 }
 int mm_comm_info(mm_ctx* ctx, int* n_ranks, int* rank) {
   if (!ctx) return MM_ERR_ARG;
-  return guarded(ctx, [&] {
-    int n = 1, r = 0;
-    if (ctx->comm) {
-      MM_REQUIRE(ncclCommCount((ncclComm_t)ctx->comm, &n) == ncclSuccess && ncclCommUserRank((ncclComm_t)ctx->comm, &r) == ncclSuccess, MM_ERR_COMM, "ncclCommCount / ncclCommUserRank failed");
-    }
-    if (n_ranks) *n_ranks = n;
-    if (rank) *rank = r;
-  });
+  return guarded(ctx, [&] { mm::comm_info(ctx, n_ranks, rank); });
 }
 int mm_comm_share(mm_ctx* ctx, mm_ctx* owner) {
   if (!ctx || !owner || ctx == owner) return MM_ERR_ARG;
@@ -1219,7 +884,7 @@ int mm_comm_share(mm_ctx* ctx, mm_ctx* owner) {
 }
 int mm_comm_allreduce_f64(mm_ctx* ctx, double* host_inout, int64_t n) {
   if (!ctx || (!host_inout && n > 0)) return MM_ERR_ARG;
-  return guarded(ctx, [&] { MM_HIP(hipSetDevice(ctx->device)); mm::comm_allreduce_f64(ctx, host_inout, n); });
+  return guarded(ctx, [&] { mm::comm_allreduce_f64(ctx, host_inout, n); });
 }
 void mm_comm_destroy(mm_ctx* ctx) { if (ctx) mm::comm_destroy(ctx); }
 

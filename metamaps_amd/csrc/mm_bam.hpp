@@ -1,6 +1,7 @@
 // BAM records of a batch of aligned jobs, encoded and deflated on the device (mm_bam.hip; the record: mm_bam_core.hpp).
 #pragma once
 #include "mm_jobs_dev.hpp"
+#include "mm_codec.hpp"                                            // (bgzf_deflate_resident: BGZF members of input that lies on the device)
 #include <vector>
 
 namespace mm {
@@ -10,6 +11,4 @@ struct BamColumns { const uint16_t* flag; const uint8_t* mapq; const int64_t* na
 struct BamMembers { std::vector<uint8_t> bgzf; int64_t n_records = 0, raw_bytes = 0; };
 constexpr int64_t BAM_GROUP_BYTES = (int64_t)4096 * 0xff00;       // group_bytes 0: what one launch of the deflate kernel takes (255 MiB of records)
 void bam_encode_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, const AlignedJobsIn& jobs, const BamColumns& in, int64_t group_bytes, BamMembers* out);
-// mm_deflate.hip: BGZF members of input that lies on the device
-void bgzf_deflate_resident(mm_ctx* ctx, const uint8_t* d_in, int64_t in_bytes, int64_t n, uint8_t* down, int32_t* sizes);
 }

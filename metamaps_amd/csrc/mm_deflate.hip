@@ -9,7 +9,7 @@
 // they go to a buffer in global memory, 255 KiB per resident workgroup, written once in rising order by the search and read once by the emit.
 // Each member is written to a 64 KiB slot of its own (16-byte stores from the window); the host packs the members while it copies them
 // out of the pinned staging.
-#include "mm_common.hpp"
+#include "mm_codec.hpp"
 #include "mm_deflate.hpp"
 #include <zlib.h>
 #include <algorithm>

@@ -41,6 +41,7 @@ void em_estep(mm_em* E, const double* f);
 void em_posteriors(mm_em* E, const double* f, double* post, int64_t* best);
 void comm_unique_id(char* id);
 void comm_init(mm_ctx* ctx, const char* id, int rank, int nranks);
+void comm_info(mm_ctx* ctx, int* n_ranks, int* rank);
 void comm_allreduce_f64(mm_ctx* ctx, double* host, int64_t n);
 void comm_destroy(mm_ctx* ctx);
 }

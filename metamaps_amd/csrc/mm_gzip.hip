@@ -9,7 +9,7 @@
 //
 // LDS of gz_jobs_kernel: the Huffman tables and code lengths (~6 KiB), the constant tables (~1.4 KiB) and the 4 KiB input ring: ~12 KiB.
 // The output and its window stay in HBM (a slot is WIN + cap entries), so occupancy is set by registers, not by LDS.
-#include "mm_common.hpp"
+#include "mm_codec.hpp"
 #include "mm_gzip.hpp"
 #include "mm_wave_lanes.hpp"
 #include <algorithm>

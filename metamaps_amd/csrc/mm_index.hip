@@ -690,4 +690,37 @@ void index_load(mm_ctx* ctx, const char* path, mm_index* I) {
   MM_HIP(mm::stream_sync(st));
 }
 
+// ---- taps: the entries in position order, and the same-hash neighbours decoded from bitmap, rank and distances (mm_index.hpp) ----
+void index_entries(mm_index* idx, uint32_t* hash, int32_t* contig, int32_t* wpos, int32_t* strand, int64_t cap) {
+  MM_REQUIRE(cap >= idx->N, MM_ERR_ARG, "output capacity too small");
+  auto h = idx->pos.to_host(idx->ctx->stream, (size_t)idx->N);
+  int64_t c = 0;
+  for (int64_t i = 0; i < idx->N; ++i) {
+    while (c + 1 < (int64_t)idx->h_cstart.size() && (uint64_t)i >= idx->h_cstart[(size_t)c + 1]) ++c;
+    if (hash) hash[i] = h[(size_t)i].hash;
+    if (contig) contig[i] = (int32_t)c;
+    if (wpos) wpos[i] = pw_wpos(h[(size_t)i].pw);
+    if (strand) strand[i] = pw_strand(h[(size_t)i].pw);
+  }
+}
+void index_dup_neighbours(mm_index* idx, int32_t* prev_dist, int32_t* next_dist, int64_t cap) {
+  MM_REQUIRE(cap >= idx->N, MM_ERR_ARG, "output capacity too small");
+  if (idx->N == 0) return;
+  hipStream_t st = idx->ctx->stream;
+  auto h = idx->pos.to_host(st, (size_t)idx->N);
+  auto bits = idx->dup_bits.to_host(st), rank = idx->dup_rank.to_host(st);
+  auto dist = idx->dup_dist.to_host(st);
+  for (int64_t i = 0; i < idx->N; ++i) {
+    prev_dist[i] = 0; next_dist[i] = 0;
+    const uint32_t fl = h[(size_t)i].pw & (PW_DP | PW_DN);
+    const bool bit = (bits[(size_t)(i >> 6)] >> (i & 63)) & 1ull;
+    MM_REQUIRE(bit == (fl != 0), MM_ERR_DEVICE, "duplicate bitmap and entry flags disagree");
+    if (!fl) continue;
+    const uint64_t r = rank[(size_t)(i >> 6)] + (uint64_t)__builtin_popcountll(bits[(size_t)(i >> 6)] & ((1ull << (i & 63)) - 1ull));
+    MM_REQUIRE(r < dist.size(), MM_ERR_DEVICE, "duplicate rank out of range");
+    if (fl & PW_DP) prev_dist[i] = (int32_t)(dist[(size_t)r] & 0xffffu);
+    if (fl & PW_DN) next_dist[i] = (int32_t)(dist[(size_t)r] >> 16);
+  }
+}
+
 }  // namespace mm

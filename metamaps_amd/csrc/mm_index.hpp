@@ -129,5 +129,7 @@ void index_build(mm_ctx* ctx, const mm_seqset* contigs, int k, int w, mm_index* 
 void index_plan_chunks(mm_ctx* ctx, const mm_index* whole, uint64_t max_memory, std::vector<int32_t>& first_contig);
 void index_save(const mm_index* idx, const char* path);
 void index_load(mm_ctx* ctx, const char* path, mm_index* out);
+void index_entries(mm_index* idx, uint32_t* hash, int32_t* contig, int32_t* wpos, int32_t* strand, int64_t cap);
+void index_dup_neighbours(mm_index* idx, int32_t* prev_dist, int32_t* next_dist, int64_t cap);
 
 }  // namespace mm

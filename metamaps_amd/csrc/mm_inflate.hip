@@ -6,7 +6,7 @@
 // stores), the two Huffman tables and the code lengths (~6 KiB) and a copy of the constant tables (~1.4 KiB: the CRC table lookups are a
 // dependent chain, LDS latency instead of a global load per byte) and a 4 KiB ring of the block's compressed bytes.  ~77 KiB: two workgroups
 // per CU.
-#include "mm_common.hpp"
+#include "mm_codec.hpp"
 #include "mm_inflate.hpp"
 #include "mm_wave_lanes.hpp"
 #include <algorithm>

@@ -48,10 +48,26 @@ struct mm_mapping {
   std::vector<uint64_t> h_rec_off;
   bool has_mapq = false;
   bool released = false;                     // mm_mapping_release_intermediates: only the records are left
+  void release_intermediates() {             // everything of K1 .. K5 above; a member added there is released here
+    mz = mm::MinimizerSet{};
+    sk_hash.release(); sk_strand.release(); sk_n.release(); amb.release();
+    min_hits.release(); accept_min.release();
+    read_hit_off.release(); hits.release(); cand_off.release(); cand.release(); cand_read.release(); l2.release();
+    std::vector<int32_t>().swap(h_sk_n); std::vector<int32_t>().swap(h_min_hits);
+    std::vector<uint64_t>().swap(h_read_hit_off); std::vector<uint64_t>().swap(h_cand_off);
+    n_cand = 0; released = true;
+  }
 };
 
 namespace mm {
 void map_batch(mm_ctx* ctx, const mm_index* I, const mm_seqset* reads, const mm_map_params& P, mm_mapping* M);
 void mapping_add_qualities(mm_ctx* ctx, mm_mapping* M, int k);
+void mapping_keep_best(mm_ctx* ctx, mm_mapping* M, int k);
 void probed_list_hist(mm_ctx* ctx, const mm_index* I, const mm_mapping* M, int nb, int64_t* hist);
+// mm_merge.hip: the read-wise merge of chunk mappings into M.  mapping_gather: true on the owner, the only rank whose M is filled.
+void mapping_concat(mm_ctx* ctx, mm_mapping* const* parts, const int32_t* contig_base, int n_parts, mm_mapping* M);
+void mapping_from_parts(mm_ctx* ctx, int64_t n_reads, const int32_t* read_len, const mm_map_params& params, int n_parts, const int64_t* const* offsets,
+                        const mm_map_record* const* records, const int32_t* contig_base, mm_mapping* M);
+bool mapping_gather(mm_ctx* ctx, int owner, int64_t n_reads, const int32_t* read_len, const mm_map_params& params, mm_mapping* const* parts, const int32_t* chunk_id,
+                    int n_parts, int n_chunks, const int32_t* chunk_rank, const int32_t* contig_base, mm_mapping* M);
 }

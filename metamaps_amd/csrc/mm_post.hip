@@ -6,6 +6,7 @@
 #include <rccl/rccl.h>
 #include "mm_prims.hpp"
 #include "mm_post_core.hpp"
+#include "mm_stats.hpp"
 #include <cfloat>
 #include <numeric>
 
@@ -67,6 +68,34 @@ void mapping_add_qualities(mm_ctx* ctx, mm_mapping* M, int k) {
   auto he = err.to_host(st);
   MM_REQUIRE(he[0] == 0, MM_ERR_NUMERIC, "likelihood sum of a read is 0 (the reference aborts here, mapWrap.h:298)");
   M->has_mapq = true;
+}
+
+// default (non --all) reporting, computeMap.hpp:546-587: per read keep the mappings whose (float) identity is
+// >= best - 1.0; the comparison happens in double exactly as there.  Record lists are small: host side.
+void mapping_keep_best(mm_ctx* ctx, mm_mapping* m, int k) {
+  std::vector<mm_map_record> recs((size_t)m->n_rec), kept;
+  m->rec.download(recs.data(), recs.size(), ctx->stream);
+  MM_HIP(mm::stream_sync(ctx->stream));
+  std::vector<uint64_t> off((size_t)m->n_reads + 1, 0);
+  int64_t mapped = 0;
+  for (int64_t r = 0; r < m->n_reads; ++r) {
+    const uint64_t a = m->h_rec_off[(size_t)r], b = m->h_rec_off[(size_t)r + 1];
+    float best = 0;
+    std::vector<float> id((size_t)(b - a));
+    for (uint64_t i = a; i < b; ++i) {
+      float ub; mm::stats::identity(recs[(size_t)i].shared, recs[(size_t)i].sketch, k, &id[(size_t)(i - a)], &ub);
+      if (id[(size_t)(i - a)] > best) best = id[(size_t)(i - a)];
+    }
+    for (uint64_t i = a; i < b; ++i) if (id[(size_t)(i - a)] >= best - 1.0) kept.push_back(recs[(size_t)i]);
+    off[(size_t)r + 1] = kept.size();
+    if (off[(size_t)r + 1] > off[(size_t)r]) ++mapped;
+  }
+  m->n_rec = (int64_t)kept.size();
+  m->rec.alloc(std::max<size_t>(kept.size(), 1)); m->rec.upload(kept.data(), kept.size(), ctx->stream);
+  m->rec_off.upload(off.data(), off.size(), ctx->stream);
+  m->h_rec_off = off;
+  m->stats.n_mappings = m->n_rec; m->stats.n_reads_mapped = mapped;
+  MM_HIP(mm::stream_sync(ctx->stream));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -644,6 +673,14 @@ void comm_init(mm_ctx* ctx, const char* id, int rank, int nranks) {
   ncclResult_t rc = ncclCommInitRank(&c, nranks, u, rank);
   MM_REQUIRE(rc == ncclSuccess, MM_ERR_COMM, std::string("ncclCommInitRank: ") + ncclGetErrorString(rc));
   ctx->comm = c; ctx->comm_rank = rank; ctx->comm_size = nranks;
+}
+void comm_info(mm_ctx* ctx, int* n_ranks, int* rank) {
+  int n = 1, r = 0;
+  if (ctx->comm) {
+    MM_REQUIRE(ncclCommCount((ncclComm_t)ctx->comm, &n) == ncclSuccess && ncclCommUserRank((ncclComm_t)ctx->comm, &r) == ncclSuccess, MM_ERR_COMM, "ncclCommCount / ncclCommUserRank failed");
+  }
+  if (n_ranks) *n_ranks = n;
+  if (rank) *rank = r;
 }
 void comm_allreduce_f64(mm_ctx* ctx, double* host, int64_t n) {
   if (!ctx->comm || n <= 0) return;

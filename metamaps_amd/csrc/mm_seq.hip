@@ -1,5 +1,6 @@
 // Sequence sets in HBM (packed 2-bit + exception runs) and the K1 driver.
 #include "mm_minimizer.hpp"
+#include "mm_seq.hpp"
 #include <algorithm>
 #include <thread>
 #include <atomic>

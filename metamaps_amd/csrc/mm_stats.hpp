@@ -124,6 +124,22 @@ inline int recommended_window(double pcut, int k, int alphabet, float pi, int ql
   int w = 2.0 * qlen / pick;
   return std::min(std::max(w, 1), qlen);
 }
+// winSketch.hpp:452-494 on an accumulated histogram.  `prev_threshold` is the threshold left by the previous
+// chunk (INT_MAX for the first): the reference keeps the old value when the loop breaks before assigning.
+inline int freq_threshold_from_hist(const int64_t* counts, const int64_t* n_hashes, int64_t n, int64_t n_unique_hashes, int prev_threshold) {
+  int thr = prev_threshold;
+  if (n_unique_hashes <= 0) return thr;                        // :456 — empty lookup: nothing happens
+  float pct = 0.001f;                                          // :91
+  int64_t ignore = n_unique_hashes * pct / 100;                // :466 float arithmetic, truncated
+  int64_t sum = 0;
+  for (int64_t i = n - 1; i >= 0; --i) {                       // most frequent first
+    sum += n_hashes[i];
+    if (sum < ignore) thr = (int)counts[i];
+    else if (sum == ignore) { thr = (int)counts[i]; break; }
+    else break;
+  }
+  return thr;
+}
 
 // Per-sketch-size thresholds used by the kernels:
 //   min_hits   = estimateMinimumHitsRelaxed(s)                   L1 (computeMap.hpp:325)

@@ -23,3 +23,16 @@ def test_no_function_above_200_lines_in_the_host_program():
     wide = out.strip().split("\n")[-3].split()                     # "longest line: W csrc/host/NAME:LINE"
     assert wide[:2] == ["longest", "line:"] and 100 < int(wide[2]) <= 200, out   # (100 <: the lines were measured)
     assert not any("load_reference" in ln for ln in out.split("\n")[:12]), out     # (once the longest host function of the CLI, 137 lines: now ref_loader.hpp's pieces)
+    parsed = out.strip().split("\n")[-4].split()                   # "library files: NAME.hip ..."
+    assert parsed[:2] == ["library", "files:"] and "mm_merge.hip" in parsed and "mm_api.hip" in parsed, out   # (the chunk merge is library host code under the 200-line rule)
+
+
+def test_the_c_surface_holds_no_kernels_no_rccl_and_no_stand_in_declarations():
+    """mm_api.hip turns exceptions into status codes and owns handle lifetimes: device code and collectives live in the units it calls, and what
+    it calls is declared in their headers, where the compiler checks the declarations against the definitions."""
+    src = open(os.path.join(ROOT, "metamaps_amd", "csrc", "mm_api.hip")).read()
+    assert "__global__" not in src and "<<<" not in src
+    assert "rccl" not in src and "nccl" not in src
+    assert "namespace mm {" not in src
+    mk = open(os.path.join(ROOT, "metamaps_amd", "csrc", "Makefile")).read()
+    assert "mm_merge.hip" in mk

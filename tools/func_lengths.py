@@ -2,6 +2,7 @@
 round-6 item 8); and of the device allocator's headers (mm_alloc.hpp, mm_alloc_rules.hpp, mm_stream.hpp): none above 60.  A function = a brace block whose opening line ends in ') {' or ') const {' (or carries a trailing comment behind that); methods of structs count.
 Device code is left out: a function whose declaration carries __global__ or __device__, on the opening line or on the earlier lines of a multi-line signature
 (back to the previous ';', '}' or blank line).  Kernels are judged by other means.
+The line before them lists the library's .hip files in which host functions were found.
 The line before the last names the longest file of metamaps_amd/csrc/host/: none above 800 lines (the CLI was one file of 2 488; map_run.hpp stood at 999
 by squeezing its lines), and the line before that the longest line of those files: none above 200 characters."""
 import glob, os, re, sys
@@ -43,6 +44,7 @@ if __name__ == "__main__":
         print(f"{n:5d}  {f}:{l}  {name}")
     files = sorted((len(open(f).read().split("\n")) - 1, os.path.relpath(f, ROOT)) for f in glob.glob(os.path.join(csrc, "host", "*")))
     wide = max((len(ln), os.path.relpath(f, ROOT), i + 1) for f in glob.glob(os.path.join(csrc, "host", "*")) for i, ln in enumerate(open(f).read().split("\n")))
+    print("library files: " + " ".join(sorted({os.path.basename(f) for _, f, _, _ in lib})))   # (every csrc/*.hip in which a host function was found)
     print(f"longest line: {wide[0]} {wide[1]}:{wide[2]}")
     print(f"longest file: {files[-1][0]} {files[-1][1]} of {len(files)} csrc/host")
     print(f"functions: {len(host)} csrc/host {len(lib)} csrc/*.hip {len(alloc)} csrc/mm_alloc.hpp+mm_alloc_rules.hpp+mm_stream.hpp")
