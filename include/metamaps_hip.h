@@ -410,8 +410,11 @@ int mm_em_posteriors(mm_em* em, const double* f, double* post /* [n_entries] */,
  * started from f_start with weights w(r,i) = boot_weight(seed, r, i), or weights[(r-rep0)*n_reads + i] if weights != NULL.
  * f_out [n_rep*n_taxa] (replicate-major), ll_out [n_rep], n_iter [n_rep], stopped [n_rep] (1: stop rule, 0: max_iter reached).
  * Read i is the i-th read WITH a mapping (reads without one are not resampled), so n_reads above counts those reads.  The stop rule is
- * mm_em_run's, per replicate; a replicate that has stopped is frozen.  Results do not depend on how the replicates are split over calls
- * or devices.  The communicator of the context is never used.  MM_ERR_LIMIT when the per-replicate buffers (n_entries*n_rep*8 bytes of
+ * mm_em_run's, per replicate; a replicate that has stopped is frozen.  A replicate whose weighted sample is EMPTY (no read with a mapping
+ * has a weight > 0, or `em` has no mapping at all) has no estimate: its f_out row is all 0, ll_out 0, n_iter 0, stopped 1, and it costs no
+ * iterations.  max_iter <= 0 is refused, so n_iter == 0 identifies such a replicate: a caller leaves it out of its statistics (the chance
+ * is e^-n per replicate for n reads with a mapping).  The other replicates are what they are without it.  Results do not depend on how
+ * the replicates are split over calls or devices.  The communicator of the context is never used.  MM_ERR_LIMIT when the per-replicate buffers (n_entries*n_rep*8 bytes of
  * posteriors and n_taxa*n_rep*8 of frequencies) exceed the device, MM_ERR_NOMEM when they do not fit its free memory: the caller tiles. */
 int mm_em_bootstrap(mm_em* em, const double* f_start, int32_t rep0, int32_t n_rep, uint64_t seed, const uint8_t* weights,
                     int max_iter, double* f_out, double* ll_out, int32_t* n_iter, int32_t* stopped);

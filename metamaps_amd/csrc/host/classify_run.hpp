@@ -166,6 +166,7 @@ struct ClassifyRun {
   std::vector<double> f, post; std::vector<int64_t> best;
   BootOpts boot;                                                  // --bootstrap: the replicates' frequencies of the present taxa, [replicate][boot_pres]
   std::vector<int32_t> boot_pres; std::vector<double> boot_f;
+  std::vector<char> boot_empty;                                   // [replicate]: it drew no read (mm_em_bootstrap: n_iter == 0) and has no estimate
   LcaOpts lca; std::unique_ptr<LcaJob> lca_job;                   // --lca
   GeneOpts genes;                                                 // --genes
   IdentOpts identf_opts;                                          // --min-identity, --refit
@@ -444,7 +445,8 @@ struct ClassifyRun {
     } catch (const gene::Error& e) { die(std::string("--genes: ") + e.what()); }
   }
   // --bootstrap B: replicates 0..B-1 of the weighted EM (mm_em_bootstrap), started from the point estimate, dealt to the devices in contiguous
-  // ranges; every device holds the whole EM problem and tiles its range to its free memory.  The result depends on neither.
+  // ranges; every device holds the whole EM problem and tiles its range to its free memory.  The result depends on neither.  A replicate that
+  // drew no read (e^-n of them for n mapped reads: small samples only) has no estimate and is left out of every statistic.
   void bootstrap() {
     if (boot.B <= 0) return;
     const auto t0 = std::chrono::steady_clock::now();
@@ -452,6 +454,7 @@ struct ClassifyRun {
     { std::vector<char> has(NT, 0); for (int32_t t : taxon) has[(size_t)t] = 1; for (size_t t = 0; t < NT; ++t) if (has[t]) boot_pres.push_back((int32_t)t); }
     const size_t NP = boot_pres.size();
     boot_f.assign(B * NP, 0.0);
+    boot_empty.assign(B, 0);
     const int MAX_ITER = 10000;
     std::atomic<long long> at_cap{0}; std::atomic<int> it_min{INT_MAX}, it_max{0};
     on_each(G, [&](size_t d) {
@@ -472,6 +475,7 @@ struct ClassifyRun {
         ck(ctx, mm_em_bootstrap(em, f.data(), (int32_t)r0, (int32_t)n, boot.seed, nullptr, MAX_ITER, fo.data(), llo.data(), nit.data(), stp.data()), "bootstrap");
         for (size_t k = 0; k < n; ++k) {
           for (size_t j = 0; j < NP; ++j) boot_f[(r0 + k) * NP + j] = fo[k * NT + (size_t)boot_pres[j]];
+          if (nit[k] == 0) { boot_empty[r0 + k] = 1; continue; }
           if (!stp[k]) ++at_cap;
           int v = it_min.load(); while (nit[k] < v && !it_min.compare_exchange_weak(v, nit[k])) {}
           v = it_max.load(); while (nit[k] > v && !it_max.compare_exchange_weak(v, nit[k])) {}
@@ -480,13 +484,16 @@ struct ClassifyRun {
       mm_em_destroy(em);
     });
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const size_t n_empty = (size_t)std::count(boot_empty.begin(), boot_empty.end(), (char)1);
+    const std::string left_out = std::to_string(n_empty) + " of " + std::to_string(B) + " drew no read and are left out";
+    if (B - n_empty < 2) die("--bootstrap: " + left_out + ": fewer than two replicates to describe");
     std::cout << "Bootstrap: " << B << " replicates, seed " << boot.seed << ", " << it_min.load() << "-" << it_max.load() << " EM iterations per replicate, "
-              << secs << " s on " << G << " device(s)" << std::endl;
+              << secs << " s on " << G << " device(s)" << (n_empty ? ", " + left_out : std::string()) << std::endl;
     if (at_cap) std::cerr << "Warning: " << at_cap.load() << " of " << B << " bootstrap replicates reached " << MAX_ITER << " EM iterations without meeting the stop rule." << std::endl;
   }
   // PREFIX.EM.WIMP.bootstrap: the WIMP's rows without the -3 count rows, its EMFrequency text, and over the replicates (each through cleanF with
-  // the point estimate's best-mapping tallies, then the WIMP's upward sums and per-level normalisation) mean, SD (B - 1), 2.5 % and 97.5 %
-  // quantiles (linear between order statistics)
+  // the point estimate's best-mapping tallies, then the WIMP's upward sums and per-level normalisation) mean, SD (n - 1), 2.5 % and 97.5 %
+  // quantiles (linear between order statistics), n = the replicates that drew a read (bootstrap() has seen to n >= 2)
   void write_bootstrap(const std::string& fn, const Taxonomy& T, const std::map<std::string, double>& fmap, const std::map<std::string, size_t>& readsPer) {
     const size_t B = (size_t)boot.B, NP = boot_pres.size();
     UpMemo memo;
@@ -501,6 +508,7 @@ struct ClassifyRun {
     for (auto& R : rows) R.v.reserve(B);
     const double minF = 0.9 * (1.0 / (double)st.at("ReadsMapped"));
     for (size_t b = 0; b < B; ++b) {
+      if (boot_empty[b]) continue;
       std::map<std::string, double> fm;                            // cleanF (fEM.h:1135-1163) of the replicate (taxa without a mapping: 0, dropped)
       for (size_t j = 0; j < NP; ++j) { const std::string& id = taxa[(size_t)boot_pres[j]]; const double v = boot_f[b * NP + j]; if (!(v < minF) || readsPer.count(id)) fm[id] = v; }
       double s = 0; for (auto& e : fm) s += e.second; for (auto& e : fm) e.second /= s;
@@ -523,10 +531,11 @@ struct ClassifyRun {
     };
     char num[128];
     for (auto& R : rows) {
-      double mean = 0; for (double v : R.v) mean += v; mean /= (double)B;
+      const size_t n = R.v.size();
+      double mean = 0; for (double v : R.v) mean += v; mean /= (double)n;
       double ss = 0; for (double v : R.v) ss += (v - mean) * (v - mean);
       std::vector<double> x = R.v; std::sort(x.begin(), x.end());
-      snprintf(num, sizeof num, "\t%.6g\t%.6g\t%.6g\t%.6g\n", mean, std::sqrt(ss / (double)(B - 1)), quantile(x, 0.025), quantile(x, 0.975));
+      snprintf(num, sizeof num, "\t%.6g\t%.6g\t%.6g\t%.6g\n", mean, std::sqrt(ss / (double)(n - 1)), quantile(x, 0.025), quantile(x, 0.975));
       o << *R.L << "\t" << R.t << "\t" << (R.t == "0" ? std::string("Unclassified") : T.T.at(R.t).sci) << "\t" << R.em << num;
     }
   }

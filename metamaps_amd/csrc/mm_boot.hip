@@ -4,7 +4,8 @@
 //   f_r     <- sum_r / sum_t sum_r[t]                                                               (fEM.h:606-615)
 //   ll_r     = sum_i w(r, i) * log S_r(i)                                                           (fEM.h:578)
 // with the reference's stop rule per replicate (fEM.h:624-639); a replicate that has stopped is frozen.  The weights come from
-// mm_boot_core.hpp (or from the caller) and are never stored.
+// mm_boot_core.hpp (or from the caller) and are never stored.  A replicate whose weighted sample is empty has no estimate: f_r = 0, ll_r = 0,
+// no iterations, stopped (P3b sees a total of exactly 0 in its first iteration and freezes it).
 //
 // The loop is the point EM's (mm_post.hip: P1 | P2 | P3 per iteration, enqueued in groups with one read of the control words behind each)
 // with a replicate dimension.  A tile is 64 replicates, one per lane of a wavefront:
@@ -38,7 +39,7 @@ struct BootLoop {
   double* wg_ll_b;                                                // [n_wg][B]
   double* tsum_b;                                                 // [n_present][B]
   double* f_b;                                                    // [n_taxa][B] (rows of present taxa only)
-  long long* ctrl_b;                                              // [B][4]: iterations done, stopped (1: rule, 2: limit), bits of the previous ll, 0
+  long long* ctrl_b;                                              // [B][4]: iterations done, stopped (1: rule, 2: limit, 3: empty sample), bits of the previous ll, 0
   int B, rep0; uint64_t seed; const uint8_t* weights;             // weights: [B][n_mapped] from the caller, or nullptr: boot_weight
   long long it_limit;
 };
@@ -154,10 +155,15 @@ __global__ void __launch_bounds__(1024) boot_p3_kernel(BootLoop a, int n_wg) {
   for (int d = 512; d >= BOOT_RT; d >>= 1) { if (tid < d) { sh_t[tid] += sh_t[tid + d]; sh_l[tid] += sh_l[tid + d]; } __syncthreads(); }
   const double total = sh_t[rr], llr = sh_l[rr];
   if (!on) return;
-  for (int p = row; p < a.n_present; p += BOOT_P3_ROWS) a.f_b[(int64_t)a.present[p] * B + rep] = a.tsum_b[(int64_t)p * B + rep] / total;   // fEM.h:606-615
+  // A replicate that drew no read (every mapped read at weight 0, or a problem without mappings): every posterior is exactly 0, so total == 0
+  // in its first iteration, and only then (a read of weight w adds posteriors that sum to w).  fEM.h:606-615 would divide 0 by 0: f_r = 0,
+  // ll_r = 0, no iteration counted, frozen.
+  const bool empty = total == 0;
+  for (int p = row; p < a.n_present; p += BOOT_P3_ROWS) a.f_b[(int64_t)a.present[p] * B + rep] = empty ? 0.0 : a.tsum_b[(int64_t)p * B + rep] / total;   // fEM.h:606-615
   if (row == 0) {                                                 // the stop rule of this replicate (fEM.h:624-639), as em_stop_rule
     long long* c = a.ctrl_b + (int64_t)rep * 4;
     const long long it = c[0];
+    if (empty && it == 0) { c[2] = 0; c[1] = 3; return; }
     const double ll_prev = __longlong_as_double(c[2]);
     long long stop = 0;
     if (it > 0 && (llr - ll_prev) <= 1 && (1 - llr / ll_prev) < 0.0001) stop = 1;
@@ -243,7 +249,7 @@ int boot_run(mm_em* E, const double* f_start, int32_t rep0, int32_t n_rep, uint6
     double ll; memcpy(&ll, &bits, sizeof ll);
     if (ll_out) ll_out[r] = ll;
     if (n_iter) n_iter[r] = (int32_t)h[(size_t)r * 4];
-    if (stopped) stopped[r] = h[(size_t)r * 4 + 1] == 1 ? 1 : 0;
+    if (stopped) stopped[r] = h[(size_t)r * 4 + 1] == 1 || h[(size_t)r * 4 + 1] == 3 ? 1 : 0;   // (3: an empty sample, n_iter == 0)
   }
   return 0;
 }

@@ -1,7 +1,8 @@
 """References for the K8 / K9 arithmetic (metamaps_amd/csrc/mm_post_core.hpp, mm_post.hip), for tests/test_post_core.py and
 tests/test_gpu_post_edges.py: the exact binomial mass (mpmath, 60 digits), the float64 restatement of the read's success probability and of the
 6-digit text round trip, the scale S of the binomial formula's error, and a float64 host EM with exact sums (math.fsum) and the reference's
-order of products.  Nothing here touches the device or the library."""
+order of products, with optional per-read weights (the bootstrap of mm_boot.hip; tests/boot_cases.py, tests/test_gpu_boot_edges.py).  Nothing
+here touches the device or the library."""
 import math
 
 import mpmath
@@ -94,28 +95,36 @@ def stop_now(it: int, ll: float, ll_prev: float) -> bool:
     return it > 0 and (ll - ll_prev) <= 1 and (1 - ll / ll_prev) < 0.0001
 
 
-def em_reference(read_off, taxon, mapq, inv_nloc, n_taxa, f0, max_iter=1000):
+def em_reference(read_off, taxon, mapq, inv_nloc, n_taxa, f0, max_iter=1000, w=None):
     """float64 EM with the reference's order of products (f * 1/nLoc * mapq, fEM.h:353) and exact sums over the mappings of a read, the
     posteriors of a taxon and the reads' logs.  Returns (f, log-likelihoods, margins): margins[i] = how far, relatively, the two stop quantities
-    of iteration i stand off their thresholds (gain vs 1, 1 - ll / ll_prev vs 1e-4)."""
+    of iteration i stand off their thresholds (gain vs 1, 1 - ll / ll_prev vs 1e-4).  It ends with the stop rule or after max_iter iterations.
+    w: an integer weight per read (the bootstrap's weighted EM, mm_boot.hip): posteriors are w[r] * l / S[r], the log-likelihood sums
+    w[r] * log S[r], a read with w == 0 adds nothing.  A weighted sample without a mapped read of w > 0 has no estimate: (zeros, no
+    log-likelihood, no margins) — what boot_expected turns into the library's empty replicate."""
     read_off = np.asarray(read_off, dtype=np.int64); taxon = np.asarray(taxon, dtype=np.int64)
-    w = np.asarray(inv_nloc, dtype=np.float64); q = np.asarray(mapq, dtype=np.float64)
+    inv = np.asarray(inv_nloc, dtype=np.float64); q = np.asarray(mapq, dtype=np.float64)
     f = np.asarray(f0, dtype=np.float64).copy()
     sizes = np.diff(read_off)
-    full = np.nonzero(sizes)[0]
+    wr = np.ones(len(sizes)) if w is None else np.asarray(w, dtype=np.float64)
+    assert wr.shape == sizes.shape and np.all(wr >= 0) and np.all(wr == np.floor(wr))
+    full = np.nonzero((sizes > 0) & (wr > 0))[0]
+    if len(full) == 0:
+        return np.zeros(n_taxa), np.zeros(0), []
     by_taxon = [np.nonzero(taxon == t)[0] for t in range(n_taxa)] if len(taxon) < 200_000 else None
     if by_taxon is None:
         order = np.argsort(taxon, kind="stable"); cut = np.searchsorted(taxon[order], np.arange(n_taxa + 1))
         by_taxon = [order[cut[t]:cut[t + 1]] for t in range(n_taxa)]
+    w_entry = np.repeat(wr, sizes)
     lls, margins = [], []
     ll_prev = 0.0
     for it in range(max_iter):
-        l = f[taxon] * w * q
-        sums = np.zeros(len(sizes))
+        l = f[taxon] * inv * q
+        sums = np.ones(len(sizes))                                  # (reads that are not in the sample: their posteriors are w * l / 1 = 0)
         for r in full:
             sums[r] = math.fsum(l[read_off[r]:read_off[r + 1]])
-        post = l / np.repeat(sums, sizes)
-        ll = math.fsum(math.log(sums[r]) for r in full)
+        post = w_entry * l / np.repeat(sums, sizes)
+        ll = math.fsum(wr[r] * math.log(sums[r]) for r in full)
         tot = np.array([math.fsum(post[ix]) for ix in by_taxon])
         f = tot / math.fsum(tot)
         lls.append(ll)
@@ -126,6 +135,32 @@ def em_reference(read_off, taxon, mapq, inv_nloc, n_taxa, f0, max_iter=1000):
         if stop:
             break
     return f, np.array(lls), margins
+
+
+def boot_weights(read_off, seed=None, rep=None, row=None):
+    """the weight of every read in one replicate of the bootstrap: weights_np(seed, rep, i) — or row[i], one row of caller weights — for the
+    i-th read WITH a mapping, in read order; 0 for a read without one (it is not resampled)"""
+    from test_boot_core import weights_np
+    mapped = np.diff(np.asarray(read_off, dtype=np.int64)) > 0
+    n_mapped = int(np.count_nonzero(mapped))
+    w = np.zeros(len(mapped), dtype=np.int64)
+    if row is None:
+        w[mapped] = weights_np(np.uint64(seed), np.uint64(rep), np.arange(n_mapped, dtype=np.uint64))
+    else:
+        row = np.asarray(row)
+        assert row.shape == (n_mapped,)
+        w[mapped] = row
+    return w
+
+
+def boot_expected(read_off, taxon, mapq, inv_nloc, n_taxa, f_start, w, max_iter=10_000):
+    """what mm_em_bootstrap reports for one replicate of weights w: (f, ll, n_iter, stopped, margins).  An empty weighted sample is
+    f = 0, ll = 0, no iteration, stopped."""
+    f, lls, margins = em_reference(read_off, taxon, mapq, inv_nloc, n_taxa, f_start, max_iter=max_iter, w=w)
+    if len(lls) == 0:
+        return f, 0.0, 0, True, margins
+    stopped = stop_now(len(lls) - 1, lls[-1], lls[-2] if len(lls) > 1 else 0.0)
+    return f, float(lls[-1]), len(lls), bool(stopped), margins
 
 
 def posteriors_reference(read_off, taxon, mapq, inv_nloc, f):

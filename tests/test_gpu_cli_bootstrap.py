@@ -1,5 +1,6 @@
 """`classify --bootstrap B [--bootstrap-seed S]`: PREFIX.EM.WIMP.bootstrap beside unchanged outputs, independent of the devices and of the
-run, the same through `mapDirectly --then-classify`, strict flag values, and intervals of the size binomial sampling predicts."""
+run, the same through `mapDirectly --then-classify`, strict flag values, intervals of the size binomial sampling predicts, and replicates
+that drew no read (a sample of three mapped reads) left out of the statistics."""
 import glob
 import math
 import os
@@ -93,6 +94,54 @@ def test_same_file_for_any_devices_run_and_path(run):
     assert open(o + ".EM.WIMP.bootstrap", "rb").read() == ref
     d, _ = _classify(run, run["m1"], "seed4", ["--bootstrap", "40", "--bootstrap-seed", "4"])
     assert open(d + ".EM.WIMP.bootstrap", "rb").read() != ref
+
+
+def test_replicates_without_a_read_are_left_out(run):
+    """three mapped reads: e^-3 of the replicates draw none of them; their f is no estimate (mm_em_bootstrap: n_iter == 0) and must reach
+    neither mean nor SD nor quantiles — once it made a whole row NaN"""
+    from test_boot_core import weights_np
+    n_keep, B, seed = 3, 64, 7
+    src = run["m1"]
+    dst = str(run["dir"] / "three")
+    _copy_mappings(src, dst)
+    ids, kept = [], []
+    for ln in open(src):
+        rid = ln.split(" ")[0]
+        if rid not in ids:
+            if len(ids) == n_keep:
+                break
+            ids.append(rid)
+        kept.append(ln)
+    assert len(ids) == n_keep <= 4
+    with open(dst, "w") as o:
+        o.write("".join(kept))
+    meta = dict(ln.split() for ln in open(src + ".meta").read().splitlines() if ln.strip())
+    meta["TotalReads"] = str(int(meta["TotalReads"]) - int(meta["ReadsMapped"]) + n_keep)
+    meta["ReadsMapped"] = str(n_keep)
+    with open(dst + ".meta", "w") as o:
+        o.write("".join(f"{k} {v}\n" for k, v in meta.items()))
+    w = weights_np(np.uint64(seed), np.arange(B, dtype=np.uint64)[:, None], np.arange(n_keep, dtype=np.uint64)[None, :]).reshape(B, n_keep)
+    n_empty = int(np.count_nonzero(~w.any(axis=1)))
+    assert 1 <= n_empty <= B - 2
+    files = {}
+    for tag, devices in (("three_d0", ["0"]), ("three_d00", ["0,0", "--em-host-reduce"])):      # (one device twice: no collective between the two)
+        out = str(run["dir"] / tag)
+        _copy_mappings(dst, out)
+        p = _run(["classify", "--DB", run["db"].dir, "--mappings", out, "--minreads", "3", "--bootstrap", str(B), "--bootstrap-seed", str(seed), "--devices"] + devices)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        log = p.stdout.decode()
+        m = re.search(r"Bootstrap: 64 replicates, seed 7, (\d+)-(\d+) EM iterations per replicate, .*, (\d+) of 64 drew no read and are left out", log)
+        assert m, log[-2000:]
+        assert int(m.group(3)) == n_empty and 1 <= int(m.group(1)) <= int(m.group(2)) < 10_000
+        assert b"EM iterations without meeting the stop rule" not in p.stderr
+        files[tag] = open(out + ".EM.WIMP.bootstrap", "rb").read()
+    assert files["three_d0"] == files["three_d00"]
+    _, rows = _table(str(run["dir"] / "three_d0") + ".EM.WIMP.bootstrap")
+    assert rows
+    for r in rows:
+        assert all(re.fullmatch(r"[0-9.e+-]+", x) and math.isfinite(float(x)) for x in r[3:]), r       # no nan, no inf
+        mean, sd, lo, hi = map(float, r[4:])
+        assert sd >= 0 and lo <= mean <= hi, r
 
 
 @pytest.mark.parametrize("bad", [["--bootstrap", "1"], ["--bootstrap", "100001"], ["--bootstrap", "x"], ["--bootstrap", "-5"], ["--bootstrap", "2.5"],
