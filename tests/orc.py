@@ -96,13 +96,12 @@ class OracleIndex:
         self.o.L.orc_index_dump(self.h, _p(h), _p(s), _p(w), _p(st))
         return h, s, w, st
 
-    def map_read(self, seq: bytes, pi: float = 80.0):
+    def map_read(self, seq: bytes, pi: float = 80.0, ccap: int = 4096):
         cap = len(seq) + 16
         n = np.zeros(5, dtype=np.int32)
         skh = np.zeros(cap, dtype=np.uint32); sks = np.zeros(cap, dtype=np.int32)
         hcap = 1 << 23
         hs = np.zeros(hcap, dtype=np.int32); hw = np.zeros(hcap, dtype=np.int32)
-        ccap = 4096
         cand = np.zeros((ccap, 3), dtype=np.int32); l2 = np.zeros((ccap, 5), dtype=np.int64); mp = np.zeros((ccap, 6), dtype=np.int32)
         self.o.L.orc_map_read(self.h, seq, len(seq), pi, _p(n), _p(skh), _p(sks), cap, _p(hs), _p(hw), hcap, _p(cand), ccap, _p(l2), _p(mp), ccap)
         s, nh, mh, nc, nm = [int(x) for x in n]
