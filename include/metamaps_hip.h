@@ -32,7 +32,7 @@ extern "C" {
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
                             *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances,
-                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_*, mm_pileup_*, mm_vcf_* (additions to 6) */
+                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_*, mm_pileup_*, mm_vcf_*, mm_consensus* (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -58,6 +58,8 @@ typedef struct mm_pileup mm_pileup;    /* a table of (key, count) pileup events,
 typedef struct mm_pileup_result mm_pileup_result;  /* the kept sites and the per-contig coverage of a run's pileup, in host memory */
 typedef struct mm_vcf mm_vcf;          /* a table of (w0, w1, count) alleles, unique keys ascending, in host memory */
 typedef struct mm_vcf_result mm_vcf_result;  /* the kept alleles of a run with their depths and reference windows, in host memory */
+struct mm_consensus;                   /* the counters and the wrapped consensus text of a group of contigs, in host memory (no typedef: the entry
+                                          point that makes one carries the name) */
 typedef struct mm_hpc_map mm_hpc_map;  /* compressed -> raw coordinates of a homopolymer-compressed set, resident in HBM */
 
 /* ---- context -------------------------------------------------------------------------------- */
@@ -587,6 +589,35 @@ int mm_vcf_result_sizes(const mm_vcf_result* result, int64_t* n_alleles);
 int mm_vcf_result_fetch(const mm_vcf_result* result, uint64_t* w0 /* [n_alleles] */, uint64_t* w1, uint32_t* count, uint32_t* depth,
                         uint8_t* window /* [MM_VCF_WINDOW * n_alleles] */);
 void mm_vcf_result_destroy(mm_vcf_result* result);
+
+/* The consensus of the contigs [contig_lo, contig_hi) of `reference`: the sequence of the strain the reads come from, built on the context's device from a
+ * merged mm_vcf table and the intervals of EVERY contributing alignment ("Consensus"; the definition: csrc/mm_cons_core.hpp).  One call
+ * handles one group of contigs, and its device and host memory are bounded by the group's bases.  depth(c, p) is the number of intervals that hold p; p is
+ * called where depth >= min_depth.  A row is a candidate where depth(c, pos) >= min_depth && (double)count >= min_frac * (double)depth.  Candidates are taken
+ * per contig in key order: a deletion (anchor a, length n, footprint [a + 1, a + n]) is applied iff a + 1 lies behind the footprint end of every earlier
+ * candidate deletion, applied or not (of [10, 20], [15, 25] and [22, 30] only the first is applied; abutting deletions both are); an SNV or an insertion is
+ * applied iff its position is in no applied footprint and no earlier candidate of its kind sits there.  Per position the consensus holds nothing (deleted),
+ * or the applied SNV's alt, else N where the position is not called, else the reference's base (N for a byte outside A C G T); then the bases of an insertion
+ * applied there (n times N for an insertion of more than 24 bases, whose bases the key does not hold).  Per contig with an interval there are MM_CONS_STATS
+ * counters: alignments, called, written, consensusLength, snvs, deletions, deletedBases, insertions, insertedBases, dropped (candidates that were not
+ * applied).  A contig is written iff called >= max(1, ceil(min_called * length)); its consensusLength is 0 otherwise.  The text of a written contig is its
+ * bytes in lines of line_width, every line followed by \n.
+ * MM_ERR_ARG: min_depth < 1, min_frac outside [0.5, 1], min_called outside [0, 1], line_width < 1, a table that is not merged or holds a key that is no allele
+ * on `reference`, a row or an interval on a contig outside the range.  All of this is checked on the host before anything is launched.  All arrays are the
+ * caller's; the result lives in host memory until destroyed; an error leaves *out NULL and launches nothing further.  MM_CONS_TIMING=1 prints the stages'
+ * device times. */
+#define MM_CONS_STATS 10
+int mm_consensus(mm_ctx* ctx, const mm_seqset* reference, int32_t contig_lo, int32_t contig_hi,
+                 int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts,
+                 int64_t n_iv, const int32_t* iv_contig, const int64_t* iv_first, const int64_t* iv_last,
+                 int64_t min_depth, double min_frac, double min_called, int32_t line_width, struct mm_consensus** out);
+/* n_contigs: the group's contigs with an interval; n_written: those of them that are written; text_bytes: the bytes of their texts together */
+int mm_consensus_sizes(const struct mm_consensus* result, int64_t* n_contigs, int64_t* n_written, int64_t* text_bytes);
+/* the contigs with an interval, ascending, and their counters in the order given above */
+int mm_consensus_fetch_contigs(const struct mm_consensus* result, int32_t* contig /* [n_contigs] */, int64_t* stats /* [MM_CONS_STATS * n_contigs] */);
+/* the written contigs, ascending; the text of contig[j] is text[text_off[j], text_off[j + 1]) */
+int mm_consensus_fetch_text(const struct mm_consensus* result, int32_t* contig /* [n_written] */, int64_t* text_off /* [n_written + 1] */, uint8_t* text /* [text_bytes] */);
+void mm_consensus_destroy(struct mm_consensus* result);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------------------------- */
 #define MM_COMM_ID_BYTES 128

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmetamaps_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "metamaps_hip.h")
 
 COMM_ID_BYTES = 128
+CONS_STATS = 10                                                     # counters per contig of mm_consensus (the header's counter constant)
 VCF_WINDOW = 25                                                     # reference bytes a kept allele of mm_vcf_finish carries (the header's window constant)
 MM_ERR_ARG = -1
 MM_ERR_LIMIT = -5
@@ -222,6 +223,11 @@ def lib() -> C.CDLL:
             "mm_vcf_result_sizes": (C.c_int, [vp, vp]),
             "mm_vcf_result_fetch": (C.c_int, [vp, vp, vp, vp, vp, vp]),
             "mm_vcf_result_destroy": (None, [vp]),
+            "mm_consensus": (C.c_int, [vp, vp, C.c_int32, C.c_int32, i64, vp, vp, vp, i64, vp, vp, vp, i64, f64, f64, C.c_int32, vp]),
+            "mm_consensus_sizes": (C.c_int, [vp, vp, vp, vp]),
+            "mm_consensus_fetch_contigs": (C.c_int, [vp, vp, vp]),
+            "mm_consensus_fetch_text": (C.c_int, [vp, vp, vp, vp]),
+            "mm_consensus_destroy": (None, [vp]),
             "mm_comm_unique_id": (C.c_int, [C.c_char_p]),
             "mm_comm_init": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
             "mm_comm_allreduce_f64": (C.c_int, [vp, vp, i64]),
@@ -710,6 +716,31 @@ class Context:
             self.last_vcf_handle = h.value
             if h.value:
                 lib().mm_vcf_result_destroy(h)
+
+    def consensus(self, reference: "SeqSet", contig_lo, contig_hi, w0, w1, counts, iv_contig, iv_first, iv_last, min_depth=3, min_frac=0.5, min_called=0.0, line_width=60):
+        """the consensus of the contigs [contig_lo, contig_hi) from a merged allele table and the intervals of all contributing alignments (mm_consensus): a dict
+        with contig and stats (CONS_STATS counters per contig with an interval), written (the contigs whose text is there) and text ({contig: its wrapped lines})"""
+        a, b, cs = np.ascontiguousarray(w0, dtype=np.uint64), np.ascontiguousarray(w1, dtype=np.uint64), np.ascontiguousarray(counts, dtype=np.uint32)
+        ic = np.ascontiguousarray(iv_contig, dtype=np.int32)
+        i0, i1 = np.ascontiguousarray(iv_first, dtype=np.int64), np.ascontiguousarray(iv_last, dtype=np.int64)
+        assert len(a) == len(b) == len(cs) and len(ic) == len(i0) == len(i1)
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_consensus(self.h, reference.h, int(contig_lo), int(contig_hi), len(a), _ptr(a), _ptr(b), _ptr(cs), len(ic), _ptr(ic), _ptr(i0), _ptr(i1), int(min_depth),
+                                float(min_frac), float(min_called), int(line_width), C.byref(h))
+        try:
+            self.check(st)
+            n, nw, nb = C.c_int64(-1), C.c_int64(-1), C.c_int64(-1)
+            assert lib().mm_consensus_sizes(h, C.byref(n), C.byref(nw), C.byref(nb)) == 0
+            contig, stats = np.zeros(n.value, dtype=np.int32), np.zeros((n.value, CONS_STATS), dtype=np.int64)
+            written, off, text = np.zeros(nw.value, dtype=np.int32), np.full(nw.value + 1, -1, dtype=np.int64), np.full(nb.value, 0xEE, dtype=np.uint8)
+            assert lib().mm_consensus_fetch_contigs(h, _ptr(contig), _ptr(stats)) == 0
+            assert lib().mm_consensus_fetch_text(h, _ptr(written), _ptr(off), _ptr(text)) == 0
+            assert off[0] == 0 and off[-1] == nb.value
+            return dict(contig=contig, stats=stats, written=written, text={int(c): text[off[j]:off[j + 1]].tobytes() for j, c in enumerate(written)})
+        finally:
+            self.last_cons_handle = h.value                         # (what the call left in *out: None after a refusal)
+            if h.value:
+                lib().mm_consensus_destroy(h)
 
     # ---- communicator
     @staticmethod

@@ -1,10 +1,11 @@
 // The side outputs of a batch of mapDirectly (the rows of side_files.hpp: PREFIX.editDistances, .paf, .bam) and the device calls they need, and the run's
-// pileup (PREFIX.pileup, .pileup.contigs) and alleles (PREFIX.vcf), which every batch adds to.  The text and byte rules are in edit_dist.hpp, paf_out.hpp,
-// bam_out.hpp, pileup_out.hpp and vcf_out.hpp, which call nothing; everything of a batch runs on the context that mapped it, the last merge and the finish of
-// the pileup and of the alleles on the first device.
+// pileup (PREFIX.pileup, .pileup.contigs), alleles (PREFIX.vcf) and consensus (PREFIX.consensus.fa, .consensus.tsv), which every batch adds to.  The text and
+// byte rules are in edit_dist.hpp, paf_out.hpp, bam_out.hpp, pileup_out.hpp, vcf_out.hpp and consensus_out.hpp, which call nothing; everything of a batch runs
+// on the context that mapped it, the last merge and the finish of the pileup, of the alleles and of the consensus on the first device.
 #pragma once
 #include "bam_out.hpp"
 #include "cli_device.hpp"
+#include "consensus_out.hpp"
 #include "edit_dist.hpp"
 #include "paf_out.hpp"
 #include "pileup_out.hpp"
@@ -98,10 +99,9 @@ void pileup_write(mm_ctx* ctx, const mm_seqset* reference, VariantRows& v, const
   write_or_die(prefix + ".pileup", pileup_text(key, count, depth, ref_byte, cname));
   write_or_die(prefix + ".pileup.contigs", pileup_contigs_text(alignments, covered, sum_depth, cname, clen));
 }
-// --vcf, after the last batch of a query file: one merge, one mm_vcf_finish against the reference of `ctx` over the file's intervals, and the file
-void vcf_write(mm_ctx* ctx, const mm_seqset* reference, VariantRows& v, const Intervals& iv, const VcfOpts& vo, const std::string& prefix, const std::vector<std::string>& cname,
+// --vcf, after the last batch of a query file and the merge of its rows: one mm_vcf_finish against the reference of `ctx` over the file's intervals, and the file
+void vcf_write(mm_ctx* ctx, const mm_seqset* reference, const VariantRows& v, const Intervals& iv, const VcfOpts& vo, const std::string& prefix, const std::vector<std::string>& cname,
                const std::vector<int>& clen) {
-  merge_rows<VcfCalls>(ctx, v);
   mm_vcf_result* r = nullptr;
   ck(ctx, mm_vcf_finish(ctx, reference, (int64_t)v.w0.size(), v.w0.data(), v.w1.data(), v.counts.data(), (int64_t)iv.contig.size(), iv.contig.data(), iv.first.data(), iv.last.data(),
                         vo.min_count, vo.min_frac, &r), "vcf");
@@ -112,19 +112,65 @@ void vcf_write(mm_ctx* ctx, const mm_seqset* reference, VariantRows& v, const In
   mm_vcf_result_destroy(r);
   write_or_die(prefix + ".vcf", vcf_header(cname, clen) + vcf_lines(w0, w1, count, depth, window, cname));
 }
-// the run's accumulators, one set per query file, and what is written from them after the last batch (every pileup before the first VCF)
+// --consensus, after the last batch of a query file and the merge of its rows: the intervals in contig order, the groups of consensus_out.hpp, the rows of
+// a group cut out by key, one mm_consensus per group on `ctx`, and the two files appended to as the groups come
+void consensus_write(mm_ctx* ctx, const mm_seqset* reference, const VariantRows& v, const Intervals& iv, const ConsOpts& co, int64_t group_bases, const std::string& prefix,
+                     const std::vector<std::string>& cname, const std::vector<int>& clen) {
+  const std::vector<size_t> order = cons_interval_order(iv.contig);
+  std::vector<int32_t> ic(order.size()); std::vector<int64_t> i0(order.size()), i1(order.size());
+  for (size_t k = 0; k < order.size(); ++k) { ic[k] = iv.contig[order[k]]; i0[k] = iv.first[order[k]]; i1[k] = iv.last[order[k]]; }
+  FILE* fa = fopen((prefix + ".consensus.fa").c_str(), "wb");
+  FILE* tsv = fopen((prefix + ".consensus.tsv").c_str(), "wb");
+  if (!fa || !tsv) die("Error writing " + prefix + ".consensus.fa / .consensus.tsv");
+  auto put = [&](FILE* f, const char* p, size_t n) { if (fwrite(p, 1, n, f) != n) die("Error writing " + prefix + ".consensus.fa / .consensus.tsv"); };
+  const std::string head = cons_tsv_header();
+  put(tsv, head.data(), head.size());
+  std::vector<int32_t> contig, written; std::vector<int64_t> stats, text_off; std::vector<uint8_t> text;
+  for (const ConsGroupRange& g : cons_groups(clen, ic, group_bases)) {
+    const size_t r0 = (size_t)(std::lower_bound(v.w0.begin(), v.w0.end(), mmp::make_key(g.lo, 0, 0)) - v.w0.begin());
+    const size_t r1 = (size_t)(std::lower_bound(v.w0.begin(), v.w0.end(), mmp::make_key(g.hi, 0, 0)) - v.w0.begin());
+    const size_t v0 = (size_t)(std::lower_bound(ic.begin(), ic.end(), g.lo) - ic.begin()), v1 = (size_t)(std::lower_bound(ic.begin(), ic.end(), g.hi) - ic.begin());
+    struct mm_consensus* r = nullptr;
+    ck(ctx, mm_consensus(ctx, reference, g.lo, g.hi, (int64_t)(r1 - r0), v.w0.data() + r0, v.w1.data() + r0, v.counts.data() + r0, (int64_t)(v1 - v0), ic.data() + v0, i0.data() + v0,
+                         i1.data() + v0, co.min_depth, co.min_frac, co.min_called, CONS_LINE_WIDTH, &r), "consensus");
+    int64_t n = 0, nw = 0, bytes = 0;
+    mm_consensus_sizes(r, &n, &nw, &bytes);
+    contig.resize((size_t)n); stats.resize((size_t)n * MM_CONS_STATS); written.resize((size_t)nw); text_off.resize((size_t)nw + 1); text.resize((size_t)bytes);
+    mm_consensus_fetch_contigs(r, contig.data(), stats.data());
+    mm_consensus_fetch_text(r, written.data(), text_off.data(), text.data());
+    mm_consensus_destroy(r);
+    std::string rows;
+    for (size_t k = 0; k < (size_t)n; ++k) cons_tsv_row(cname[(size_t)contig[k]], clen[(size_t)contig[k]], &stats[k * MM_CONS_STATS], rows);
+    put(tsv, rows.data(), rows.size());
+    for (size_t k = 0; k < (size_t)nw; ++k) {
+      const std::string name = cons_fasta_name(cname[(size_t)written[k]]);
+      put(fa, name.data(), name.size());
+      put(fa, (const char*)text.data() + text_off[k], (size_t)(text_off[k + 1] - text_off[k]));
+    }
+  }
+  if (fclose(fa) != 0 || fclose(tsv) != 0) die("Error writing " + prefix + ".consensus.fa / .consensus.tsv");
+}
+// the run's accumulators, one set per query file, and what is written from them after the last batch (every pileup before the first VCF).  The alleles are
+// accumulated (vcf_on) for --vcf and for --consensus, merged once, and written as PREFIX.vcf under --vcf alone
 struct RunVariants {
   struct File { Intervals iv; VariantAcc pile, vcf; };
-  bool pileup_on = false, vcf_on = false;
+  bool pileup_on = false, vcf_on = false, vcf_file = false, cons_on = false;
   std::deque<File> files;
-  void resize(bool pileup, bool vcf, size_t n_files) { pileup_on = pileup; vcf_on = vcf; if (pileup || vcf) files.resize(n_files); }
+  void resize(bool pileup, bool vcf, bool cons, size_t n_files) {
+    pileup_on = pileup; vcf_on = vcf || cons; vcf_file = vcf; cons_on = cons;
+    if (pileup_on || vcf_on) files.resize(n_files);
+  }
   VariantAcc* pile(size_t f) { return pileup_on ? &files[f].pile : nullptr; }
   VariantAcc* vcf(size_t f) { return vcf_on ? &files[f].vcf : nullptr; }
   Intervals* intervals(size_t f) { return files.empty() ? nullptr : &files[f].iv; }
-  void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const std::vector<std::string>& prefixes, const std::vector<std::string>& cname,
-             const std::vector<int>& clen) {
+  void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const ConsOpts& co, int64_t cons_group_bases, const std::vector<std::string>& prefixes,
+             const std::vector<std::string>& cname, const std::vector<int>& clen) {
     for (size_t fi = 0; pileup_on && fi < files.size(); ++fi) pileup_write(ctx, reference, files[fi].pile.rows, files[fi].iv, po, prefixes[fi], cname, clen);
-    for (size_t fi = 0; vcf_on && fi < files.size(); ++fi) vcf_write(ctx, reference, files[fi].vcf.rows, files[fi].iv, vo, prefixes[fi], cname, clen);
+    for (size_t fi = 0; vcf_on && fi < files.size(); ++fi) {
+      merge_rows<VcfCalls>(ctx, files[fi].vcf.rows);
+      if (vcf_file) vcf_write(ctx, reference, files[fi].vcf.rows, files[fi].iv, vo, prefixes[fi], cname, clen);
+      if (cons_on) consensus_write(ctx, reference, files[fi].vcf.rows, files[fi].iv, co, cons_group_bases, prefixes[fi], cname, clen);
+    }
   }
 };
 
@@ -135,9 +181,9 @@ struct BatchSideOutputs {
   BatchAlignment al;
   VariantAcc* pile = nullptr;                                    // --pileup: the accumulator of the batch's query file
   size_t pile_merge_pairs = 0;
-  VariantAcc* vcf = nullptr;                                     // --vcf: the accumulator of the batch's query file
+  VariantAcc* vcf = nullptr;                                     // --vcf, --consensus: the accumulator of the batch's query file
   size_t vcf_merge_pairs = 0;
-  Intervals* iv = nullptr;                                       // --pileup, --vcf: the contributing alignments of the batch's query file
+  Intervals* iv = nullptr;                                       // --pileup, --vcf, --consensus: the contributing alignments of the batch's query file
 
   // while the mapping lives: d, first, last (and the runs, where .paf or .bam want them) fetched once -> the lines of .editDistances and .paf.
   // The reads go here unless .bam needs them for SEQ or the pileup or the VCF for their mismatched and inserted bases.  Nothing happens without reads (no side file was asked for).

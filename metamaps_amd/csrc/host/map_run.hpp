@@ -59,6 +59,7 @@ struct MapRun {
   const bool edit = side[SIDE_EDIT];
   const PileupOpts pileup = pileup_options(o);                   // --pileup (implies --edit-distance): one accumulator per query file (pileup_out.hpp)
   const VcfOpts vcf = vcf_options(o);                            // --vcf (implies --edit-distance): the same (vcf_out.hpp)
+  const ConsOpts cons = consensus_options(o);                    // --consensus (implies --edit-distance): --vcf's accumulator (consensus_out.hpp)
   RunVariants var;
   std::string bgzf_head;                                         // what a BGZF side file starts with: the header of every PREFIX.bam as BGZF members (the contigs are the run's)
   std::vector<int> clen_raw; std::vector<mm_hpc_map*> hpc_map;
@@ -356,7 +357,7 @@ struct MapRun {
     }
     if (place != Place::Replicated && NC == 1 && !from_index && !maxMem) die("--stream-chunks / --shard-index need --maxmemory (the chunk rule of the reference, winSketch.hpp:274-329)");
     if (edit && place != Place::Replicated)
-      die(std::string(vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : side[SIDE_PAF] ? "--paf" : "--edit-distance")
+      die(std::string(cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : side[SIDE_PAF] ? "--paf" : "--edit-distance")
           + " needs the whole reference resident on every device, and this index does not fit one: run without it");
     for (auto& d : devs) d.idx.assign(NC, nullptr);
     thr_of.assign(NC, INT_MAX);
@@ -767,14 +768,14 @@ struct MapRun {
     build_resident_indexes();
     mp = mm_map_params{k, w, pi, minLen};
     for (auto& ch : chunks) chunk_base.push_back(ch.first);
-    var.resize(pileup.on, vcf.on, prefixes.size());
+    var.resize(pileup.on, vcf.on, cons.on, prefixes.size());
     if (side[SIDE_BAM]) bgzf_head = bam_header_members(ctx0, cname, clen);   // (before the workers take the first device's context)
     start_reader();
     if (prewarm.joinable()) prewarm.join();
     if (place != Place::Replicated) for (auto*& c : wctx) if (c) { mm_ctx_destroy(c); c = nullptr; }   // (the other modes drive one context per device)
     if (place == Place::Replicated) run_replicated(); else run_chunk_major();
     pc.lap("8 write");
-    var.write(ctx0, refset[0], pileup, vcf, prefixes, cname, clen);
+    var.write(ctx0, refset[0], pileup, vcf, cons, sw.cons_group_bases, prefixes, cname, clen);
     then_classify();
     if (!sw.full_teardown) { if (reader.th.joinable()) reader.th.join(); pc.report(); finish_fast(); }
     drop_refsets();

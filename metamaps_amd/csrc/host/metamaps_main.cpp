@@ -6,6 +6,7 @@
 // reference too: argument parsing, FASTA/FASTQ(.gz) reading, text formatting, taxonomy bookkeeping.
 //
 //   metamaps mapDirectly [--all] [--compress-output] [--edit-distance] [--paf] [--bam] [--pileup [--pileup-min-count N] [--pileup-min-frac F]] [--vcf [--vcf-min-count N] [--vcf-min-frac F]]
+//                       [--consensus [--consensus-min-depth D] [--consensus-min-frac F] [--consensus-min-called C]]
 //                        -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
 //   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]] [--lca T] [--genes] [--min-identity T [--refit]]
@@ -140,7 +141,7 @@ Options parse(int argc, char** argv) {
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
     if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" ||
-        a == "--bam" || a == "--pileup" || a == "--vcf" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
+        a == "--bam" || a == "--pileup" || a == "--vcf" || a == "--consensus" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
@@ -159,6 +160,11 @@ Options parse(int argc, char** argv) {
                    "  --vcf [--vcf-min-count N] [--vcf-min-frac F]  (mapDirectly) implies --edit-distance and also writes PREFIX.vcf (VCFv4.2, sites only): SNVs, deletions and\n"
                    "         insertions of the primary alignments, indels left-aligned on the device so that equal variants count together, with DP and AO; kept where at least N\n"
                    "         (default 3) alignments and F (default 0.2) of the depth carry the allele; may be combined with --paf, --bam and --pileup; not with --hpc,\n"
+                   "         --shard-index, --stream-chunks\n"
+                   "  --consensus [--consensus-min-depth D] [--consensus-min-frac F] [--consensus-min-called C]  (mapDirectly) implies --edit-distance and also writes\n"
+                   "         PREFIX.consensus.fa, the sequence of the strain the reads come from (per contig the majority alleles of --vcf's table applied on the device where at\n"
+                   "         least D (default 3) primary alignments span a position and F (default 0.5) of them carry the allele, N below D; contigs with at least C (default 0)\n"
+                   "         of their length spanned), and PREFIX.consensus.tsv (per-contig counters); may be combined with --vcf, --paf, --bam and --pileup; not with --hpc,\n"
                    "         --shard-index, --stream-chunks\n"
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
                    "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
@@ -256,9 +262,10 @@ int main(int argc, char** argv) {
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
   const PileupOpts pileup_opts = pileup_options(o);             // (validated before any work; MapRun reads them again)
   const VcfOpts vcf_opts = vcf_options(o);                      // (the same)
-  if (o.v.count("paf") || o.v.count("bam") || pileup_opts.on || vcf_opts.on) o.v["edit-distance"] = "1";   // (all four imply it, and inherit its refusals under their own names)
+  const ConsOpts cons_opts = consensus_options(o);              // (the same)
+  if (o.v.count("paf") || o.v.count("bam") || pileup_opts.on || vcf_opts.on || cons_opts.on) o.v["edit-distance"] = "1";   // (all five imply it, and inherit its refusals under their own names)
   if (o.v.count("edit-distance")) {                              // (refused before any device work)
-    const std::string flag = vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup" : o.v.count("bam") ? "--bam" : o.v.count("paf") ? "--paf" : "--edit-distance";
+    const std::string flag = cons_opts.on ? "--consensus" : vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup" : o.v.count("bam") ? "--bam" : o.v.count("paf") ? "--paf" : "--edit-distance";
     if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reference does not stay on the device");
     if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");

@@ -14,6 +14,8 @@
 #include "mm_bam.hpp"
 #include "mm_pileup.hpp"
 #include "mm_vcf.hpp"
+#include "mm_cons.hpp"
+#include "mm_cons_core.hpp"
 #include "mm_seq.hpp"
 #include "mm_codec.hpp"
 #include <chrono>
@@ -860,6 +862,38 @@ int mm_vcf_result_fetch(const mm_vcf_result* r, uint64_t* w0, uint64_t* w1, uint
   return MM_OK;
 }
 void mm_vcf_result_destroy(mm_vcf_result* r) { delete r; }
+
+struct mm_consensus { mm::ConsResult r; };                         // (host memory only: one group's counters and text)
+static_assert(MM_CONS_STATS == mmc::STATS, "the header's counters are the definition's");
+int mm_consensus(mm_ctx* ctx, const mm_seqset* reference, int32_t contig_lo, int32_t contig_hi, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, int64_t n_iv,
+                 const int32_t* iv_contig, const int64_t* iv_first, const int64_t* iv_last, int64_t min_depth, double min_frac, double min_called, int32_t line_width,
+                 struct mm_consensus** out) {
+  if (!ctx || !reference || !out) return refused(out);
+  return created(ctx, out, [&](struct mm_consensus& r) {
+    require_finish("mm_consensus", n, n_iv, w0 && w1 && counts, iv_contig && iv_first && iv_last);
+    mm::consensus_run(ctx, reference, mm::ConsIn{contig_lo, contig_hi, mm::FinishIn{n, w0, w1, counts, n_iv, iv_contig, iv_first, iv_last, 1, min_frac}, min_depth, min_called, line_width},
+                      &r.r);
+  });
+}
+int mm_consensus_sizes(const struct mm_consensus* r, int64_t* n_contigs, int64_t* n_written, int64_t* text_bytes) {
+  if (!r || !n_contigs || !n_written || !text_bytes) return MM_ERR_ARG;
+  *n_contigs = (int64_t)r->r.contig.size(); *n_written = (int64_t)r->r.written.size(); *text_bytes = (int64_t)r->r.text.size();
+  return MM_OK;
+}
+int mm_consensus_fetch_contigs(const struct mm_consensus* r, int32_t* contig, int64_t* stats) {
+  if (!r || (!r->r.contig.empty() && (!contig || !stats))) return MM_ERR_ARG;
+  const size_t k = r->r.contig.size();
+  if (k) { memcpy(contig, r->r.contig.data(), k * 4); memcpy(stats, r->r.stats.data(), k * MM_CONS_STATS * 8); }
+  return MM_OK;
+}
+int mm_consensus_fetch_text(const struct mm_consensus* r, int32_t* contig, int64_t* text_off, uint8_t* text) {
+  if (!r || !text_off || (!r->r.written.empty() && (!contig || !text))) return MM_ERR_ARG;
+  const size_t k = r->r.written.size();
+  memcpy(text_off, r->r.text_off.data(), (k + 1) * 8);
+  if (k) { memcpy(contig, r->r.written.data(), k * 4); memcpy(text, r->r.text.data(), r->r.text.size()); }
+  return MM_OK;
+}
+void mm_consensus_destroy(struct mm_consensus* r) { delete r; }
 
 // ---- communicator -------------------------------------------------------------------------------------
 int mm_comm_unique_id(char id[MM_COMM_ID_BYTES]) {

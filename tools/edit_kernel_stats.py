@@ -7,6 +7,10 @@ Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes pr
        python tools/edit_kernel_stats.py --bam [n_reads]              (writes profiles/bam_encode_stats.txt)
        python tools/edit_kernel_stats.py --pileup [n_reads]           (writes profiles/pileup_stats.txt)
        python tools/edit_kernel_stats.py --vcf [n_reads]              (writes profiles/vcf_stats.txt)
+       python tools/edit_kernel_stats.py --consensus [n_reads]        (writes profiles/consensus_stats.txt)
+--consensus: the run of --vcf, and behind its mm_vcf_finish in the same process mm_consensus (mm_cons_core.hpp, mm_cons.hip) over the same table and intervals
+at the default thresholds, one call per group of at most 2^28 reference bases: the MM_CONS_TIMING lines, the wall time, the groups, the contigs written and the
+bytes of text, beside that run's mm_vcf_finish.  One run is one run.
 --vcf: the run of --pileup, and behind it in the same process the same alignments twice through mm_vcf_events (mm_vcf_core.hpp, mm_vcf.hip) and once through
 mm_vcf_merge and mm_vcf_finish at the default thresholds: the MM_VCF_TIMING lines, the wall times, the events, triples and bytes fetched, beside that run's
 mm_pileup_events, which is the comparison.  One run is one run.
@@ -163,7 +167,7 @@ def child_bam(n_reads):
     M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
 
 
-def child_pileup(n_reads, vcf=False):
+def child_pileup(n_reads, vcf=False, cons=False):
     from metamaps_amd import capi
     ctx = capi.Context(0)
     ref = ctx.synth_reference(seed=20260928, n_species=25, strains_per_species=4, genome_len=2_200_000, strain_divergence=0.02, genus_divergence=0.2)
@@ -224,6 +228,24 @@ def child_pileup(n_reads, vcf=False):
         dt = time.perf_counter() - t0
         print(f"mm_vcf_finish (min_count 3, min_frac 0.2): {1e3 * dt:.1f} ms wall with the copies, {len(res['w0'])} of {len(w0)} alleles kept, "
               f"{int((res['count'] > res['depth']).sum())} of them with count > depth", flush=True)
+    if cons:
+        clen, ic = ref.lengths(), rec["ref_contig"][al]
+        groups, lo = [], 0                                          # consecutive contigs of at most 2^28 bases; a longer contig is a group alone
+        while lo < len(clen):
+            hi = lo + 1
+            while hi < len(clen) and int(clen[lo:hi + 1].sum()) <= 1 << 28:
+                hi += 1
+            groups.append((lo, hi))
+            lo = hi
+        contigs = written = text_bytes = 0
+        t0 = time.perf_counter()
+        for lo, hi in groups:
+            rows, ivs = ((w0 >> 35) >= lo) & ((w0 >> 35) < hi), (ic >= lo) & (ic < hi)
+            got = ctx.consensus(ref, lo, hi, w0[rows], w1[rows], counts[rows], ic[ivs], first[al][ivs], last[al][ivs])
+            contigs += len(got["contig"]); written += len(got["written"]); text_bytes += sum(len(t) for t in got["text"].values())
+        dt = time.perf_counter() - t0
+        print(f"mm_consensus (min_depth 3, min_frac 0.5, min_called 0, 60 columns): {1e3 * dt:.1f} ms wall with the copies and the Python wrapper's slicing, {len(groups)} group(s) over "
+              f"{int(clen.sum())} reference bases, {contigs} contigs with alignments, {written} written, {text_bytes} bytes of text", flush=True)
     M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
 
 
@@ -232,6 +254,20 @@ def main():
         return child_pileup(int(sys.argv[2]))
     if len(sys.argv) > 1 and sys.argv[1] == "--child-vcf":
         return child_pileup(int(sys.argv[2]), vcf=True)
+    if len(sys.argv) > 1 and sys.argv[1] == "--child-consensus":
+        return child_pileup(int(sys.argv[2]), vcf=True, cons=True)
+    if len(sys.argv) > 1 and sys.argv[1] == "--consensus":
+        n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-consensus", str(n_reads)],
+                           env=dict(os.environ, MM_EDIT_TIMING="1", MM_BAM_TIMING="1", MM_PILEUP_TIMING="1", MM_VCF_TIMING="1", MM_CONS_TIMING="1"), stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, timeout=1100)
+        text = f"tools/edit_kernel_stats.py --consensus {n_reads}: one batch of {n_reads} reads, best mappings only; one run\n" + p.stdout.decode()
+        print(text)
+        if p.returncode != 0:
+            sys.exit(p.returncode)
+        with open(os.path.join(ROOT, "profiles", "consensus_stats.txt"), "w") as f:
+            f.write(text)
+        return None
     if len(sys.argv) > 1 and sys.argv[1] == "--vcf":
         n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-vcf", str(n_reads)],
