@@ -96,6 +96,19 @@ int mm_seqset_add_view(mm_seqset* s, const char* ascii, int64_t len);
  * other than A/C/G/T become exception runs of their letter).  A view, like mm_seqset_add_view: `nt16` stays valid until mm_seqset_upload
  * has returned, which packs the codes on the device.  One set holds either ASCII or 4-bit sequences: adding the other kind is MM_ERR_STATE. */
 int mm_seqset_add_nt16(mm_seqset* s, const uint8_t* nt16, int64_t n_bases, int reverse);
+/* Base qualities, one byte per base beside the packed bases.  mm_seqset_add_qual attaches `len` quality bytes to the sequence added last (by
+ * mm_seqset_add, _add_view or _add_nt16): offset 33 for the text of a FASTQ record, 0 for the raw Phred bytes of a BAM record; for an nt16 record
+ * added with reverse != 0 the bytes are in the record's order and are turned back with the bases.  A view: `qual` stays valid and unchanged until
+ * mm_seqset_upload has returned.  MM_ERR_ARG: no sequence yet, a second call for the same sequence, len other than that sequence's length, an
+ * offset other than 0 or 33, a set that is uploaded.  A set may mix sequences with and without qualities.  mm_seqset_upload stages the bytes as it
+ * does the bases and one kernel stores Phred 0..93 per base, 0xFF for a sequence without qualities; a byte outside [offset, offset + 93] is
+ * MM_ERR_DATA, mm_last_error names the lowest such sequence and the byte.  A set without any mm_seqset_add_qual call allocates and launches
+ * nothing for qualities.  mm_seqset_has_qual: 1 if any sequence of the set carries qualities.  mm_seqset_fetch_qual: the stored bytes of sequence i
+ * in read order (cap >= its length), 0xFF each for a sequence without qualities.  mm_seqset_slice and mm_seqset_concat carry the qualities;
+ * mm_seqset_save / _load and mm_seqset_hpc do not: their result has none. */
+int mm_seqset_add_qual(mm_seqset* s, const uint8_t* qual, int64_t len, int offset);
+int mm_seqset_has_qual(const mm_seqset* s);
+int mm_seqset_fetch_qual(mm_seqset* s, int64_t i, uint8_t* out, int64_t cap);
 /* Inflate n BGZF blocks (whole gzip members with the BC field: header + deflate + CRC32 + ISIZE) on the context's device, from host memory
  * into host memory.  Block i is comp[comp_off[i], comp_off[i] + comp_len[i]) (comp_bytes bytes in `comp`); its ISIZE inflated bytes go to
  * out[out_off[i], out_off[i] + ISIZE) (out_cap bytes in `out`); no other byte of `out` is written, nor the bytes of a block that fails.
@@ -509,7 +522,7 @@ void mm_alignment_destroy(mm_alignment* al);
  * records as they are.  A job with dist < 0, and one whose read is empty, has no record.  A record: refID = contig, pos = first, bin =
  * reg2bin(first, first + reference span), l_seq = the read's length, next_refID = next_pos = -1, tlen = 0; the CIGAR is the runs as they are; SEQ
  * is the read as its set holds it (for strand -1 reversed, each 4-bit code of =ACMGRSVTWYHKDBN bit-reversed; a byte outside the table is N), QUAL is
- * 0xFF; the tags are NM:i (int32) = dist, MD:Z from the runs and the forward reference, and, for more than 65 535 runs, CG:B,I with the runs
+ * the read's Phred bytes where its set carries qualities (mm_seqset_add_qual; reversed for strand -1), 0xFF on every base of a read without; the tags are NM:i (int32) = dist, MD:Z from the runs and the forward reference, and, for more than 65 535 runs, CG:B,I with the runs
  * while the CIGAR field holds <l_seq>S<span>N.  The records of consecutive jobs go into groups of at most group_bytes raw bytes (0: 255 MiB; a larger
  * record is a group of its own); each group is deflated where it was written and only its BGZF members come to the host, back to back.  The
  * inflated stream does not depend on group_bytes.  The file's header and the 28-byte end-of-file block are the caller's to write.
@@ -546,6 +559,15 @@ void mm_bam_destroy(mm_bam* bam);
 int mm_pileup_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs,
                      const int32_t* read, const int32_t* strand, const int32_t* contig, const int32_t* dist, const int64_t* first,
                      const int64_t* op_off /* [n_jobs + 1] */, const uint32_t* ops, const uint8_t* use /* [n_jobs] */, mm_pileup** out);
+/* The same under a base-quality floor min_base_quality (0..93: MM_ERR_ARG otherwise; 0 is mm_pileup_events bit for bit, and so is any floor on reads
+ * without qualities: "no quality" counts as 255).  With q(i) the quality of base i of the oriented read of m bases: the event of an X run at read
+ * index i + t is kept iff q(i + t) >= floor; the events of a D run met at read index i are kept together iff min(q(i - 1) if i > 0, q(i) if i < m) >=
+ * floor; the event of an I run of n iff min q(i .. i + n - 1) >= floor.  The table holds exactly the kept events.  Intervals, and so depth, do not
+ * depend on the floor. */
+int mm_pileup_events_q(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs,
+                       const int32_t* read, const int32_t* strand, const int32_t* contig, const int32_t* dist, const int64_t* first,
+                       const int64_t* op_off /* [n_jobs + 1] */, const uint32_t* ops, const uint8_t* use /* [n_jobs] */, int32_t min_base_quality,
+                       mm_pileup** out);
 int mm_pileup_merge(mm_ctx* ctx, int64_t n, const uint64_t* keys, const uint32_t* counts, mm_pileup** out);
 int mm_pileup_sizes(const mm_pileup* table, int64_t* n_pairs);
 int mm_pileup_fetch(const mm_pileup* table, uint64_t* keys /* [n_pairs] */, uint32_t* counts);
@@ -578,6 +600,12 @@ void mm_pileup_result_destroy(mm_pileup_result* result);
 int mm_vcf_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs,
                   const int32_t* read, const int32_t* strand, const int32_t* contig, const int32_t* dist, const int64_t* first,
                   const int64_t* op_off /* [n_jobs + 1] */, const uint32_t* ops, const uint8_t* use /* [n_jobs] */, mm_vcf** out);
+/* The same under mm_pileup_events_q's base-quality floor: an SNV, a deletion and an insertion are kept by the rules of the X, D and I run they come
+ * from, asked before the left shift, which acts on the alleles that were kept.  The rules' checks are unchanged. */
+int mm_vcf_events_q(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs,
+                    const int32_t* read, const int32_t* strand, const int32_t* contig, const int32_t* dist, const int64_t* first,
+                    const int64_t* op_off /* [n_jobs + 1] */, const uint32_t* ops, const uint8_t* use /* [n_jobs] */, int32_t min_base_quality,
+                    mm_vcf** out);
 int mm_vcf_merge(mm_ctx* ctx, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, mm_vcf** out);
 int mm_vcf_sizes(const mm_vcf* table, int64_t* n_triples);
 int mm_vcf_fetch(const mm_vcf* table, uint64_t* w0 /* [n_triples] */, uint64_t* w1, uint32_t* counts);

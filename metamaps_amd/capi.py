@@ -115,6 +115,9 @@ def lib() -> C.CDLL:
             "mm_seqset_add": (C.c_int, [vp, C.c_char_p, i64]),
             "mm_seqset_add_view": (C.c_int, [vp, C.c_char_p, i64]),
             "mm_seqset_add_nt16": (C.c_int, [vp, C.c_char_p, i64, C.c_int]),
+            "mm_seqset_add_qual": (C.c_int, [vp, C.c_char_p, i64, C.c_int]),
+            "mm_seqset_has_qual": (C.c_int, [vp]),
+            "mm_seqset_fetch_qual": (C.c_int, [vp, i64, vp, i64]),
             "mm_bgzf_inflate": (C.c_int, [vp, C.c_char_p, i64, vp, vp, C.c_int32, vp, i64, vp, vp]),
             "mm_bgzf_deflate_bound": (i64, [i64]),
             "mm_bgzf_deflate": (C.c_int, [vp, C.c_char_p, i64, vp, i64, P(i64), P(C.c_int32)]),
@@ -205,6 +208,7 @@ def lib() -> C.CDLL:
             "mm_bam_fetch": (C.c_int, [vp, vp]),
             "mm_bam_destroy": (None, [vp]),
             "mm_pileup_events": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "mm_pileup_events_q": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp]),
             "mm_pileup_merge": (C.c_int, [vp, i64, vp, vp, vp]),
             "mm_pileup_sizes": (C.c_int, [vp, vp]),
             "mm_pileup_fetch": (C.c_int, [vp, vp, vp]),
@@ -215,6 +219,7 @@ def lib() -> C.CDLL:
             "mm_pileup_result_fetch_contigs": (C.c_int, [vp, vp, vp, vp]),
             "mm_pileup_result_destroy": (None, [vp]),
             "mm_vcf_events": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "mm_vcf_events_q": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp]),
             "mm_vcf_merge": (C.c_int, [vp, i64, vp, vp, vp, vp]),
             "mm_vcf_sizes": (C.c_int, [vp, vp]),
             "mm_vcf_fetch": (C.c_int, [vp, vp, vp, vp]),
@@ -281,28 +286,42 @@ class Context:
         return lib().mm_ctx_stream(self.h) or 0
 
     # ---- sequences
-    def seqset(self, seqs) -> "SeqSet":
+    def _upload(self, s: "SeqSet") -> "SeqSet":
+        try:
+            self.check(lib().mm_seqset_upload(s.h))
+        except MMError:
+            s.close()
+            raise
+        return s
+
+    def seqset(self, seqs, quals=None, qual_offset=33) -> "SeqSet":
+        """an uploaded set of ASCII sequences; quals: per sequence its quality bytes (mm_seqset_add_qual with qual_offset) or None"""
         h = C.c_void_p()
         self.check(lib().mm_seqset_create(self.h, C.byref(h)))
         s = SeqSet(self, h)
-        for q in seqs:
+        keep = [None if q is None else bytes(q) for q in (quals if quals is not None else [])]   # viewed until the upload has returned
+        for i, q in enumerate(seqs):
             if isinstance(q, str):
                 q = q.encode()
             q = bytes(q)
             self.check(lib().mm_seqset_add(h, q, len(q)))
-        self.check(lib().mm_seqset_upload(h))
-        return s
+            if i < len(keep) and keep[i] is not None:
+                self.check(lib().mm_seqset_add_qual(h, keep[i], len(keep[i]), qual_offset))
+        return self._upload(s)
 
-    def seqset_nt16(self, records) -> "SeqSet":
-        """a set of BAM-packed reads: records are (4-bit code bytes, bases, reverse) as a BAM record stores them"""
+    def seqset_nt16(self, records, quals=None, qual_offset=0) -> "SeqSet":
+        """a set of BAM-packed reads: records are (4-bit code bytes, bases, reverse) as a BAM record stores them; quals: per record its quality
+        bytes in the record's order (mm_seqset_add_qual with qual_offset) or None"""
         h = C.c_void_p()
         self.check(lib().mm_seqset_create(self.h, C.byref(h)))
         s = SeqSet(self, h)
         keep = [bytes(b) for b, _, _ in records]                   # alive until the upload has returned
-        for b, (_, n, rev) in zip(keep, records):
+        keepq = [None if q is None else bytes(q) for q in (quals if quals is not None else [])]
+        for i, (b, (_, n, rev)) in enumerate(zip(keep, records)):
             self.check(lib().mm_seqset_add_nt16(h, b, n, 1 if rev else 0))
-        self.check(lib().mm_seqset_upload(h))
-        return s
+            if i < len(keepq) and keepq[i] is not None:
+                self.check(lib().mm_seqset_add_qual(h, keepq[i], len(keepq[i]), qual_offset))
+        return self._upload(s)
 
     def bgzf_inflate(self, blocks, out_off=None, out_cap=None):
         """BGZF blocks (bytes each, whole members) inflated on the device in one call (mm_bgzf_inflate).  Returns (out, status): `out` a
@@ -616,16 +635,20 @@ class Context:
             if handle.value:
                 lib().mm_pileup_destroy(handle)
 
-    def pileup_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use):
+    def pileup_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use, min_base_quality=None):
         """the pileup events of the jobs with use != 0 and dist >= 0 (mm_pileup_events): (keys, counts), keys contig << 35 | pos << 3 | code unique
-        and ascending, code A 0 C 1 G 2 T 3 N 4, a deleted base 5, an insertion behind the base 6"""
+        and ascending, code A 0 C 1 G 2 T 3 N 4, a deleted base 5, an insertion behind the base 6.  min_base_quality: mm_pileup_events_q's floor"""
         rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
         fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
         op, us = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(use, dtype=np.uint8)
         n = len(rd)
         assert all(len(x) == n for x in (sd, cg, ds, fs, us)) and len(oo) == n + 1
         h = C.c_void_p(0xDEAD)                                      # (the call sets it, to NULL on an error)
-        st = lib().mm_pileup_events(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), C.byref(h))
+        if min_base_quality is None:
+            st = lib().mm_pileup_events(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), C.byref(h))
+        else:
+            st = lib().mm_pileup_events_q(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), int(min_base_quality),
+                                          C.byref(h))
         return self._pileup_table(st, h)
 
     def pileup_merge(self, keys, counts):
@@ -674,17 +697,21 @@ class Context:
             if handle.value:
                 lib().mm_vcf_destroy(handle)
 
-    def vcf_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use):
+    def vcf_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use, min_base_quality=None):
         """the left-aligned alleles of the jobs with use != 0 and dist >= 0 (mm_vcf_events): (w0, w1, counts), keys unique and ascending by (w0, w1);
         w0 = contig << 35 | pos << 3 | code (the alt's 0-3, a deletion 5, an insertion 6), w1 = 0, the deletion's length, or the insertion's length << 48
-        | its bases (2 bits each, up to 24)"""
+        | its bases (2 bits each, up to 24).  min_base_quality: mm_vcf_events_q's floor"""
         rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
         fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
         op, us = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(use, dtype=np.uint8)
         n = len(rd)
         assert all(len(x) == n for x in (sd, cg, ds, fs, us)) and len(oo) == n + 1
         h = C.c_void_p(0xDEAD)                                      # (the call sets it, to NULL on an error)
-        st = lib().mm_vcf_events(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), C.byref(h))
+        if min_base_quality is None:
+            st = lib().mm_vcf_events(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), C.byref(h))
+        else:
+            st = lib().mm_vcf_events_q(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), int(min_base_quality),
+                                       C.byref(h))
         return self._vcf_table(st, h)
 
     def vcf_merge(self, w0, w1, counts):
@@ -813,6 +840,16 @@ class SeqSet:
         buf = C.create_string_buffer(length + 1)
         self.ctx.check(lib().mm_seqset_fetch(self.h, i, buf, length))
         return buf.raw[:length]
+
+    @property
+    def has_qual(self) -> bool:
+        return bool(lib().mm_seqset_has_qual(self.h))
+
+    def fetch_qual(self, i: int, length: int) -> bytes:
+        """the stored qualities of sequence i in read order (mm_seqset_fetch_qual): Phred bytes, 0xFF each where it has none"""
+        buf = np.zeros(max(length, 1), dtype=np.uint8)
+        self.ctx.check(lib().mm_seqset_fetch_qual(self.h, i, _ptr(buf), length))
+        return buf[:length].tobytes()
 
     def fetch_range(self, first: int, count: int):
         """(ASCII of sequences [first, first + count) back to back as a uint8 array, their lengths)"""

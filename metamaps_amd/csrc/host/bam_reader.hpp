@@ -4,8 +4,9 @@
 //
 // What a record becomes is what `samtools fastq -n` writes for it: secondary (0x100) and supplementary (0x800) records are skipped, a record
 // with 0x10 is the reverse complement of the read as sequenced (the complement of a 4-bit code is its bit reversal: A<->T, C<->G, M<->K, R<->Y,
-// V<->B, H<->D; S, W, N and '=' stay), the name is read_name without its NUL, qualities and tags are ignored, and paired-end flags (0x1, 0x40,
-// 0x80) are NOT interpreted: no /1 or /2 is appended.  The bases stay in BAM's packed 4-bit form (two per byte, high nibble first): the
+// V<->B, H<->D; S, W, N and '=' stay), the name is read_name without its NUL, the qualities are handed on as they lie (Record::qual: in the
+// record's order, so reversed where 0x10 is set), tags are ignored, and paired-end flags (0x1, 0x40, 0x80) are NOT interpreted: no /1 or /2 is
+// appended.  The bases stay in BAM's packed 4-bit form (two per byte, high nibble first): the
 // library packs them on the device (mm_seqset_add_nt16).
 #pragma once
 #include <fcntl.h>
@@ -105,6 +106,7 @@ struct Record {
   std::string name;
   const uint8_t* seq = nullptr;   // (l_seq + 1) / 2 bytes of 4-bit codes, valid until the next call of Reader::next
   int64_t l_seq = 0;
+  const uint8_t* qual = nullptr;  // l_seq raw Phred bytes in the record's order, valid as long as seq; nullptr: the record has none (its first quality byte is 0xFF)
   uint16_t flag = 0;
   bool reverse() const { return flag & 0x10; }
 };
@@ -230,6 +232,7 @@ class Reader {
       if (nul != std::string::npos) r.name.resize(nul);
       r.seq = h + 32 + l_name + 4 * n_cigar;
       r.l_seq = l_seq;
+      r.qual = l_seq > 0 && r.seq[seq_bytes] != 0xFF ? r.seq + seq_bytes : nullptr;
       r.flag = flag;
       return true;
     }

@@ -62,6 +62,10 @@ struct LcaOpts { bool on = false; double tau = 0; };
 // --genes (classify, mapDirectly --then-classify; the reference's geneLevelAnalysis.pl): the gene- and annotation-level analysis of the reads' best
 // mappings against DB/DB_annotations.txt and DB/DB_proteins.faa.annotated.  Off without the flag: nothing changes and no file appears.
 struct GeneOpts { bool on = false; };
+// --base-qualities, --min-base-quality Q (mapDirectly; not in the reference): the run keeps the queries' base qualities beside the bases on the device.
+// --bam writes them into QUAL; Q (0..93, implies --base-qualities) is the floor below which --pileup, --vcf and --consensus do not count a base's evidence
+// (mm_pileup_events_q).  Off without the flags: nothing changes.
+struct QualOpts { bool keep = false; int min_base_quality = 0; };
 // --min-identity T [--refit] (classify, mapDirectly --then-classify; the reference's util/filterLowIdentityEntities.pl): genomes whose best mappings have
 // a median identity below T (a decimal in [0, 1], the script's --identityThreshold) are removed and their reads set to unclassified in PREFIX.EM-filtered*;
 // --refit (not in the reference) also runs the EM again without the removed genomes' mappings.  Off without the flag: nothing changes and no file appears.

@@ -40,7 +40,7 @@ std::string bam_header_members(mm_ctx* ctx, const std::vector<std::string>& cnam
 struct PileupCalls {
   using Table = mm_pileup;
   static constexpr const char* events_what = "pileup events"; static constexpr const char* merge_what = "pileup merge";
-  static constexpr auto events = mm_pileup_events;
+  static constexpr auto events = mm_pileup_events_q;
   static int merge(mm_ctx* ctx, const VariantRows& v, Table** t) { return mm_pileup_merge(ctx, (int64_t)v.w0.size(), v.w0.data(), v.counts.data(), t); }
   static void fetch(Table* t, VariantRows& v) {
     int64_t n = 0;
@@ -50,7 +50,7 @@ struct PileupCalls {
 struct VcfCalls {
   using Table = mm_vcf;
   static constexpr const char* events_what = "vcf events"; static constexpr const char* merge_what = "vcf merge";
-  static constexpr auto events = mm_vcf_events;
+  static constexpr auto events = mm_vcf_events_q;
   static int merge(mm_ctx* ctx, const VariantRows& v, Table** t) { return mm_vcf_merge(ctx, (int64_t)v.w0.size(), v.w0.data(), v.w1.data(), v.counts.data(), t); }
   static void fetch(Table* t, VariantRows& v) {
     int64_t n = 0;
@@ -64,12 +64,12 @@ template <class C> void merge_rows(mm_ctx* ctx, VariantRows& v) {
   C::fetch(t, v);
 }
 // --pileup and --vcf, per batch: the events (alleles) of the primary aligned records (use) counted on the context that mapped the batch, appended to the
-// file's accumulator; above merge_pairs rows the accumulator is replaced by its merge
+// file's accumulator; above merge_pairs rows the accumulator is replaced by its merge.  min_base_quality: --min-base-quality's floor (0: none)
 template <class C> void add_batch(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, const BamFields& F, const BatchAlignment& al, const std::vector<uint8_t>& use,
-                                  size_t merge_pairs, VariantAcc& acc) {
+                                  int32_t min_base_quality, size_t merge_pairs, VariantAcc& acc) {
   typename C::Table* t = nullptr;
   ck(ctx, C::events(ctx, reads, reference, (int64_t)use.size(), F.read.data(), F.strand.data(), F.contig.data(), al.dist.data(), al.first.data(), al.op_off.data(), al.ops.data(),
-                    use.data(), &t), C::events_what);
+                    use.data(), min_base_quality, &t), C::events_what);
   VariantRows got;
   C::fetch(t, got);
   std::lock_guard<std::mutex> lk(acc.m);
@@ -100,8 +100,8 @@ void pileup_write(mm_ctx* ctx, const mm_seqset* reference, VariantRows& v, const
   write_or_die(prefix + ".pileup.contigs", pileup_contigs_text(alignments, covered, sum_depth, cname, clen));
 }
 // --vcf, after the last batch of a query file and the merge of its rows: one mm_vcf_finish against the reference of `ctx` over the file's intervals, and the file
-void vcf_write(mm_ctx* ctx, const mm_seqset* reference, const VariantRows& v, const Intervals& iv, const VcfOpts& vo, const std::string& prefix, const std::vector<std::string>& cname,
-               const std::vector<int>& clen) {
+void vcf_write(mm_ctx* ctx, const mm_seqset* reference, const VariantRows& v, const Intervals& iv, const VcfOpts& vo, int min_base_quality, const std::string& prefix,
+               const std::vector<std::string>& cname, const std::vector<int>& clen) {
   mm_vcf_result* r = nullptr;
   ck(ctx, mm_vcf_finish(ctx, reference, (int64_t)v.w0.size(), v.w0.data(), v.w1.data(), v.counts.data(), (int64_t)iv.contig.size(), iv.contig.data(), iv.first.data(), iv.last.data(),
                         vo.min_count, vo.min_frac, &r), "vcf");
@@ -110,7 +110,7 @@ void vcf_write(mm_ctx* ctx, const mm_seqset* reference, const VariantRows& v, co
   std::vector<uint64_t> w0((size_t)n), w1((size_t)n); std::vector<uint32_t> count((size_t)n), depth((size_t)n); std::vector<uint8_t> window((size_t)n * MM_VCF_WINDOW);
   mm_vcf_result_fetch(r, w0.data(), w1.data(), count.data(), depth.data(), window.data());
   mm_vcf_result_destroy(r);
-  write_or_die(prefix + ".vcf", vcf_header(cname, clen) + vcf_lines(w0, w1, count, depth, window, cname));
+  write_or_die(prefix + ".vcf", vcf_header(cname, clen, min_base_quality) + vcf_lines(w0, w1, count, depth, window, cname));
 }
 // --consensus, after the last batch of a query file and the merge of its rows: the intervals in contig order, the groups of consensus_out.hpp, the rows of
 // a group cut out by key, one mm_consensus per group on `ctx`, and the two files appended to as the groups come
@@ -163,12 +163,12 @@ struct RunVariants {
   VariantAcc* pile(size_t f) { return pileup_on ? &files[f].pile : nullptr; }
   VariantAcc* vcf(size_t f) { return vcf_on ? &files[f].vcf : nullptr; }
   Intervals* intervals(size_t f) { return files.empty() ? nullptr : &files[f].iv; }
-  void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const ConsOpts& co, int64_t cons_group_bases, const std::vector<std::string>& prefixes,
-             const std::vector<std::string>& cname, const std::vector<int>& clen) {
+  void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const ConsOpts& co, int min_base_quality, int64_t cons_group_bases,
+             const std::vector<std::string>& prefixes, const std::vector<std::string>& cname, const std::vector<int>& clen) {
     for (size_t fi = 0; pileup_on && fi < files.size(); ++fi) pileup_write(ctx, reference, files[fi].pile.rows, files[fi].iv, po, prefixes[fi], cname, clen);
     for (size_t fi = 0; vcf_on && fi < files.size(); ++fi) {
       merge_rows<VcfCalls>(ctx, files[fi].vcf.rows);
-      if (vcf_file) vcf_write(ctx, reference, files[fi].vcf.rows, files[fi].iv, vo, prefixes[fi], cname, clen);
+      if (vcf_file) vcf_write(ctx, reference, files[fi].vcf.rows, files[fi].iv, vo, min_base_quality, prefixes[fi], cname, clen);
       if (cons_on) consensus_write(ctx, reference, files[fi].vcf.rows, files[fi].iv, co, cons_group_bases, prefixes[fi], cname, clen);
     }
   }
@@ -184,6 +184,7 @@ struct BatchSideOutputs {
   VariantAcc* vcf = nullptr;                                     // --vcf, --consensus: the accumulator of the batch's query file
   size_t vcf_merge_pairs = 0;
   Intervals* iv = nullptr;                                       // --pileup, --vcf, --consensus: the contributing alignments of the batch's query file
+  int32_t min_base_quality = 0;                                  // --min-base-quality: the floor of the pileup's events and of the alleles
 
   // while the mapping lives: d, first, last (and the runs, where .paf or .bam want them) fetched once -> the lines of .editDistances and .paf.
   // The reads go here unless .bam needs them for SEQ or the pileup or the VCF for their mismatched and inserted bases.  Nothing happens without reads (no side file was asked for).
@@ -222,8 +223,8 @@ struct BatchSideOutputs {
       if (pile || vcf) {
         const std::vector<uint8_t> use = pileup_use(F.flag, al.dist);
         iv->add_intervals(use, F.contig, al.first, al.last);
-        if (pile) add_batch<PileupCalls>(ctx, reads.get(), reference, F, al, use, pile_merge_pairs, *pile);
-        if (vcf) add_batch<VcfCalls>(ctx, reads.get(), reference, F, al, use, vcf_merge_pairs, *vcf);
+        if (pile) add_batch<PileupCalls>(ctx, reads.get(), reference, F, al, use, min_base_quality, pile_merge_pairs, *pile);
+        if (vcf) add_batch<VcfCalls>(ctx, reads.get(), reference, F, al, use, min_base_quality, vcf_merge_pairs, *vcf);
       }
       if (!on[SIDE_BAM]) { reads.reset(); return; }
       mm_bam* b = nullptr;

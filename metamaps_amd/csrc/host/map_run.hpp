@@ -60,6 +60,7 @@ struct MapRun {
   const PileupOpts pileup = pileup_options(o);                   // --pileup (implies --edit-distance): one accumulator per query file (pileup_out.hpp)
   const VcfOpts vcf = vcf_options(o);                            // --vcf (implies --edit-distance): the same (vcf_out.hpp)
   const ConsOpts cons = consensus_options(o);                    // --consensus (implies --edit-distance): --vcf's accumulator (consensus_out.hpp)
+  const QualOpts qual = qual_options(o);                         // --base-qualities, --min-base-quality: the batches carry the reads' qualities to the device
   RunVariants var;
   std::string bgzf_head;                                         // what a BGZF side file starts with: the header of every PREFIX.bam as BGZF members (the contigs are the run's)
   std::vector<int> clen_raw; std::vector<mm_hpc_map*> hpc_map;
@@ -187,7 +188,7 @@ struct MapRun {
 
   // (started as soon as the reference has been parsed: the first batches are ready when the index is)
   void start_reader() { if (reader.th.joinable() || reader.started) return; reader.started = true; 
-    reader.th = std::thread([this]() { QueryReader(reader, queries, BATCH_READS, BATCH_BASES, devs[0].phys, pc, mapped, sw).run(); }); }
+    reader.th = std::thread([this]() { QueryReader(reader, queries, BATCH_READS, BATCH_BASES, devs[0].phys, pc, mapped, sw, qual.keep).run(); }); }
   void start_prewarm() {
     if (prewarm.joinable() || sw.no_prewarm) return;
     int64_t query_bytes = 0; for (auto& q : queries) query_bytes += (int64_t)file_size(q);
@@ -414,8 +415,11 @@ struct MapRun {
 
   mm_seqset* upload_batch(mm_ctx* ctx, const Batch& bt) {
     mm_seqset* reads; ck(ctx, mm_seqset_create(ctx, &reads), "seqset");
-    if (bt.nt16) for (size_t r = 0; r < bt.names.size(); ++r) ck(ctx, mm_seqset_add_nt16(reads, (const uint8_t*)bt.seq_of(r), (int64_t)bt.lens[r], bt.rev[r]), "add read");
-    else for (size_t r = 0; r < bt.names.size(); ++r) ck(ctx, mm_seqset_add_view(reads, bt.seq_of(r), (int64_t)bt.lens[r]), "add read");
+    for (size_t r = 0; r < bt.names.size(); ++r) {
+      if (bt.nt16) ck(ctx, mm_seqset_add_nt16(reads, (const uint8_t*)bt.seq_of(r), (int64_t)bt.lens[r], bt.rev[r]), "add read");
+      else ck(ctx, mm_seqset_add_view(reads, bt.seq_of(r), (int64_t)bt.lens[r]), "add read");
+      if (const char* q = bt.qual_of(r)) ck(ctx, mm_seqset_add_qual(reads, (const uint8_t*)q, (int64_t)bt.lens[r], bt.qual_offset), "add qualities");   // (--base-qualities)
+    }
     ck(ctx, mm_seqset_upload(reads), "upload reads");
     if (hpc) {                                                     // compressed on the context that maps the batch, between upload and K1
       mm_seqset* c = nullptr;
@@ -455,7 +459,7 @@ struct MapRun {
     const auto f1 = std::chrono::steady_clock::now();
     std::vector<mm_map_record> rec((size_t)dn->off.back());
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), rec.data(), (int64_t)rec.size()), "fetch");
-    BatchSideOutputs so{side, {}, var.pile(file), sw.pileup_merge_pairs, var.vcf(file), sw.vcf_merge_pairs, var.intervals(file)};   // one alignment for all of them
+    BatchSideOutputs so{side, {}, var.pile(file), sw.pileup_merge_pairs, var.vcf(file), sw.vcf_merge_pairs, var.intervals(file), qual.min_base_quality};   // one alignment for all of them
     so.from_mapping(ctx, m, reads, refset[dev], pi, rec, dn->names, dn->lens, dn->off, cname, clen, dn->side);
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
@@ -775,7 +779,7 @@ struct MapRun {
     if (place != Place::Replicated) for (auto*& c : wctx) if (c) { mm_ctx_destroy(c); c = nullptr; }   // (the other modes drive one context per device)
     if (place == Place::Replicated) run_replicated(); else run_chunk_major();
     pc.lap("8 write");
-    var.write(ctx0, refset[0], pileup, vcf, cons, sw.cons_group_bases, prefixes, cname, clen);
+    var.write(ctx0, refset[0], pileup, vcf, cons, qual.min_base_quality, sw.cons_group_bases, prefixes, cname, clen);
     then_classify();
     if (!sw.full_teardown) { if (reader.th.joinable()) reader.th.join(); pc.report(); finish_fast(); }
     drop_refsets();

@@ -61,7 +61,7 @@
 //
 // --bam (mapDirectly; not in the reference; implies --edit-distance; may be combined with --paf): also PREFIX.bam, one BAM record (SAM/BAM specification
 // v1.6) per ALIGNED line of PREFIX in the same order, unsorted, a read's records together (GO:query): the CIGAR of = X I D runs, NM, MD, the read's bases
-// (for strand - reverse-complemented) and 0xFF qualities; mapq from the printed field 14 of the record's line, 0x100 on every record of a read but the one
+// (for strand - reverse-complemented) and 0xFF qualities (the read's own under --base-qualities); mapq from the printed field 14 of the record's line, 0x100 on every record of a read but the one
 // with the largest field 14 (host/bam_out.hpp).  The device that mapped a batch encodes its records from the alignment the .editDistances and .paf lines
 // come from and deflates them where they lie (mm_bam_encode); the file is BGZF whatever --compress-output says and ends with the end-of-file block.
 // Every other file of the run is the file of the same run without the flag.  Refused wherever --edit-distance is.
@@ -85,6 +85,16 @@
 // merged on the device whenever they pass MM_VCF_MERGE_PAIRS; the first device finishes (mm_vcf_finish).  No genotypes, FORMAT columns, qualities or
 // multi-allelic records.  Plain text; an empty run writes the header.  Every other file of the run is the file of the same run without the flag.  Refused
 // wherever --edit-distance is; the two thresholds are refused without --vcf (host/vcf_out.hpp).
+//
+// --base-qualities, --min-base-quality Q (mapDirectly; not in the reference; samtools mpileup's -Q): the run keeps the base qualities of its queries (the quality
+// line of a FASTQ record in any of the text forms, the qual field of a BAM record; a FASTA record and a BAM record without have none) and uploads them beside
+// the bases, one byte per base (mm_seqset_add_qual; a quality character outside '!'..'~' ends the run).  --bam then writes every record's QUAL (reversed for
+// strand -; 0xFF for a read without); nothing else of PREFIX.bam changes.  --min-base-quality Q, an integer 0..93 that implies --base-qualities, is a floor for
+// --pileup, --vcf and --consensus: a mismatched base counts iff its quality is >= Q, a deletion iff the read's bases on either side of the gap have it, an
+// insertion iff all its bases have it; a read without qualities passes every floor (mm_pileup_events_q, mm_vcf_events_q).  The alignments' intervals are
+// untouched: depth, DP and PREFIX.pileup.contigs stay raw, so count / depth errs low under a floor.  With Q > 0 the VCF header gains "##minBaseQuality=Q".
+// --base-qualities needs --bam or --min-base-quality, --min-base-quality one of --pileup, --vcf, --consensus; both are refused wherever --edit-distance is.
+// Without the two flags every output is what it was.
 //
 // --hpc (mapDirectly; not in the reference; minimap2's -H): homopolymer-compressed mapping.  Every maximal run of equal bytes of the reference and
 // of the reads — as hashed: upper-cased, IUPAC and N kept — becomes one byte, on the device (mm_seqset_hpc): the reference once per device behind
@@ -141,7 +151,7 @@ Options parse(int argc, char** argv) {
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
     if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" ||
-        a == "--bam" || a == "--pileup" || a == "--vcf" || a == "--consensus" || a == "--genes" || a == "--refit") { o.v[a.substr(2)] = "1"; continue; }
+        a == "--bam" || a == "--pileup" || a == "--vcf" || a == "--consensus" || a == "--genes" || a == "--refit" || a == "--base-qualities") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
@@ -166,6 +176,10 @@ Options parse(int argc, char** argv) {
                    "         least D (default 3) primary alignments span a position and F (default 0.5) of them carry the allele, N below D; contigs with at least C (default 0)\n"
                    "         of their length spanned), and PREFIX.consensus.tsv (per-contig counters); may be combined with --vcf, --paf, --bam and --pileup; not with --hpc,\n"
                    "         --shard-index, --stream-chunks\n"
+                   "  --base-qualities  (mapDirectly, with --bam or --min-base-quality) the queries' base qualities (FASTQ, BAM) go to the device beside the bases;\n"
+                   "         PREFIX.bam carries them in QUAL (0xFF for a read without); not with --hpc, --shard-index, --stream-chunks\n"
+                   "  --min-base-quality Q  (mapDirectly, with --pileup, --vcf or --consensus) Q in [0, 93], implies --base-qualities: a mismatch counts only where its\n"
+                   "         base has quality >= Q, a deletion where the read's bases on both sides of it have, an insertion where all its bases have; DP and depth stay raw\n"
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
                    "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
                    "  --genes  (classify, mapDirectly --then-classify) gene-level analysis against DB_annotations.txt and DB_proteins.faa.annotated of the DB:\n"
@@ -263,6 +277,13 @@ int main(int argc, char** argv) {
   const PileupOpts pileup_opts = pileup_options(o);             // (validated before any work; MapRun reads them again)
   const VcfOpts vcf_opts = vcf_options(o);                      // (the same)
   const ConsOpts cons_opts = consensus_options(o);              // (the same)
+  if (o.v.count("base-qualities") || o.v.count("min-base-quality")) {   // (refused under the flag's own name wherever --edit-distance is, before any device work)
+    const std::string flag = o.v.count("min-base-quality") ? "--min-base-quality" : "--base-qualities";
+    (void)qual_options(o);                                       // (the value and what uses it; MapRun reads them again)
+    if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it carries the qualities of a run's reads to the device that aligns them");
+    if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: a homopolymer-compressed read has no per-base qualities");
+    if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");
+  }
   if (o.v.count("paf") || o.v.count("bam") || pileup_opts.on || vcf_opts.on || cons_opts.on) o.v["edit-distance"] = "1";   // (all five imply it, and inherit its refusals under their own names)
   if (o.v.count("edit-distance")) {                              // (refused before any device work)
     const std::string flag = cons_opts.on ? "--consensus" : vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup" : o.v.count("bam") ? "--bam" : o.v.count("paf") ? "--paf" : "--edit-distance";

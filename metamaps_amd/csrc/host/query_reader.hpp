@@ -65,6 +65,11 @@ struct Batch {
   std::vector<std::string> names; std::vector<int> lens; std::vector<size_t> off;
   std::vector<const char*> view;                                 // per read: where the sequence lies in a mapped query file, or nullptr (then arena + off)
   bool nt16 = false; std::vector<uint8_t> rev;                   // a batch of a BAM file: the arena holds 4-bit codes (mm_seqset_add_nt16), rev per read
+  // --base-qualities (keep_q: the batch was read under the flag; the two vectors stay empty otherwise): per read where its quality bytes lie in a mapped
+  // query file, or their offset in the arena, or neither (NO_QUAL: a FASTA record, a BAM record without); qual_offset: 33 for text, 0 for a BAM's Phred bytes
+  static constexpr size_t NO_QUAL = (size_t)-1;
+  bool keep_q = false; int qual_offset = 33;
+  std::vector<const char*> qview; std::vector<size_t> qoff;
   char* arena = nullptr; size_t cap = 0, used = 0;
   size_t seq = 0, file = 0;
   ~Batch() { free(arena); }
@@ -80,23 +85,43 @@ struct Batch {
   void put(const std::string& q) { reserve(used + q.size() + 1); memcpy(arena + used, q.data(), q.size()); off.push_back(used); view.push_back(nullptr); used += q.size(); }
   void put_view(const char* p) { off.push_back(0); view.push_back(p); }
   const char* seq_of(size_t r) const { return view[r] ? view[r] : arena + off[r]; }
+  const char* qual_of(size_t r) const { return !keep_q ? nullptr : qview[r] ? qview[r] : qoff[r] != NO_QUAL ? arena + qoff[r] : nullptr; }   // nullptr: read r has no qualities
+  void put_qual(const char* p, size_t n, bool reversed = false) {   // read r's n quality bytes into the arena (p == nullptr: it has none)
+    qview.push_back(nullptr);
+    if (!p) { qoff.push_back(NO_QUAL); return; }
+    reserve(used + n + 1);
+    if (reversed) std::reverse_copy(p, p + n, arena + used); else memcpy(arena + used, p, n);
+    qoff.push_back(used); used += n;
+  }
   void add(SeqFile& f) {                                         // the record `f` just returned
     names.push_back(f.name); lens.push_back((int)f.length());
     if (f.view) put_view(f.view); else put(f.seq);
+    if (f.keep_qual) {
+      keep_q = true;
+      if (f.qview) { qview.push_back(f.qview); qoff.push_back(NO_QUAL); }
+      else put_qual(f.has_qual ? f.qual.data() : nullptr, f.qual.size());
+    }
   }
-  void put_nt16(const bam::Record& r) {                          // a BAM record's codes as they are, or (MM_BAM_HOST_DECODE) decoded to ASCII here
+  // a BAM record's codes as they are, or (MM_BAM_HOST_DECODE) decoded to ASCII here; keep: its qualities behind them (turned back with the bases where the
+  // host decodes, by the library's kernel otherwise)
+  void put_nt16(const bam::Record& r, bool keep) {
     const size_t nb = nt16 ? ((size_t)r.l_seq + 1) / 2 : (size_t)r.l_seq;
     reserve(used + nb + 1);
     if (nt16) { memcpy(arena + used, r.seq, nb); rev.push_back(r.reverse() ? 1 : 0); }
     else bam::nt16_to_ascii(r.seq, (size_t)r.l_seq, r.reverse(), arena + used);
     names.push_back(r.name); lens.push_back((int)r.l_seq); off.push_back(used); view.push_back(nullptr); used += nb;
+    if (keep) { keep_q = true; qual_offset = 0; put_qual((const char*)r.qual, (size_t)r.l_seq, !nt16 && r.reverse()); }
   }
-  void reset() { names.clear(); lens.clear(); off.clear(); view.clear(); rev.clear(); nt16 = false; used = 0; }
+  void reset() { names.clear(); lens.clear(); off.clear(); view.clear(); rev.clear(); qview.clear(); qoff.clear(); nt16 = false; keep_q = false; qual_offset = 33; used = 0; }
   int64_t bases() const { int64_t b = 0; for (int L : lens) b += L; return b; }
   void absorb(Batch& o) {                                        // o's reads behind this batch's (the block parser's small batches joined up to the batch limits)
     const size_t base = used;
     if (o.used) { reserve(used + o.used); memcpy(arena + used, o.arena, o.used); used += o.used; }
     for (size_t i = 0; i < o.names.size(); ++i) { names.push_back(std::move(o.names[i])); lens.push_back(o.lens[i]); view.push_back(o.view[i]); off.push_back(o.view[i] ? 0 : base + o.off[i]); }
+    if (o.keep_q) {
+      keep_q = true;
+      for (size_t i = 0; i < o.qoff.size(); ++i) { qview.push_back(o.qview[i]); qoff.push_back(o.qoff[i] == NO_QUAL ? NO_QUAL : base + o.qoff[i]); }
+    }
   }
 };
 
@@ -121,6 +146,8 @@ struct Reader {
 // inflate context lives on, the run's phase clock, the mapped query files (alive until the end of the run: the batches point into them), the switches.
 struct QueryReader {
   Reader& reader; const std::vector<std::string>& queries; const int64_t BATCH_READS, BATCH_BASES; const int dev0; PhaseClock& pc; std::deque<MappedFile>& mapped; const CliSwitches& sw;
+  const bool keep_qual;                                          // --base-qualities: the batches carry the reads' qualities
+  size_t q_reads = 0, q_with = 0;                                // under the flag: the reads of the current query file, and those of them with qualities
   using Emit = std::function<void(std::unique_ptr<Batch>)>;
   size_t seq = 0;
   double r_waited = 0;                                           // the reader's own rate (MM_CLI_TIMING): its wall time without what it waited for a free queue slot
@@ -131,8 +158,9 @@ struct QueryReader {
   std::vector<int64_t> z_coff, z_ooff; std::vector<int32_t> z_clen, z_st;
   bam::SegmentInflater device_inflate;
 
-  QueryReader(Reader& reader_, const std::vector<std::string>& queries_, int64_t batch_reads, int64_t batch_bases, int dev0_, PhaseClock& pc_, std::deque<MappedFile>& mapped_, const CliSwitches& sw_)
-      : reader(reader_), queries(queries_), BATCH_READS(batch_reads), BATCH_BASES(batch_bases), dev0(dev0_), pc(pc_), mapped(mapped_), sw(sw_) {
+  QueryReader(Reader& reader_, const std::vector<std::string>& queries_, int64_t batch_reads, int64_t batch_bases, int dev0_, PhaseClock& pc_, std::deque<MappedFile>& mapped_, const CliSwitches& sw_,
+              bool keep_qual_ = false)
+      : reader(reader_), queries(queries_), BATCH_READS(batch_reads), BATCH_BASES(batch_bases), dev0(dev0_), pc(pc_), mapped(mapped_), sw(sw_), keep_qual(keep_qual_) {
     if (!sw.bgzf_host_inflate) device_inflate = [this](const uint8_t* file, const bam::SegBlock* b, size_t n, uint8_t* dst) { inflate_segment(file, b, n, dst); };
   }
   ~QueryReader() { if (zctx) mm_ctx_destroy(zctx); }
@@ -156,6 +184,7 @@ struct QueryReader {
   }
   void enqueue(std::unique_ptr<Batch> b, size_t fi) {
     b->seq = seq++; b->file = fi;
+    if (keep_qual) { q_reads += b->names.size(); for (size_t r = 0; r < b->names.size(); ++r) q_with += b->qual_of(r) != nullptr; }
     if (sw.timing) std::cerr << "INFO, reader: batch of " << b->names.size() << " reads parsed at +" << std::chrono::duration<double>(std::chrono::steady_clock::now() - pc.t0).count() << " s\n";
     std::unique_lock<std::mutex> lk(reader.m);
     const auto w0 = std::chrono::steady_clock::now();
@@ -202,7 +231,7 @@ struct QueryReader {
       bam::Reader br(queries[fi], P, (1LL << 29) - 1, true, sw.bam_device_inflate ? device_inflate : nullptr);
       bam::Record r;
       fill_batches([&] { return br.next(r); }, [&] { return (int64_t)r.l_seq; },
-                   [&](Batch& b) { if (b.names.empty()) { b.nt16 = !sw.bam_host_decode; b.reserve(first_reserve((int64_t)r.l_seq)); } b.put_nt16(r); },
+                   [&](Batch& b) { if (b.names.empty()) { b.nt16 = !sw.bam_host_decode; b.reserve(first_reserve((int64_t)r.l_seq)); } b.put_nt16(r, keep_qual); },
                    [&](std::unique_ptr<Batch> b) { enqueue(std::move(b), fi); });
     } catch (const bam::Error& e) { die(std::string("Error reading BAM: ") + e.what()); }
   }
@@ -213,6 +242,7 @@ struct QueryReader {
         while (!z.at_end()) if (const size_t n = z.inflate_segment(buf, 0)) return n;
         return 0;
       });
+      f.keep_qual = keep_qual;
       parse_all(f, fi);
     } catch (const bam::Error& e) { die(std::string("Error reading ") + queries[fi] + ": " + e.what()); }
   }
@@ -221,11 +251,12 @@ struct QueryReader {
     {
       DeviceGzip z(zctx, queries[fi]);
       SeqFile f([&](std::vector<unsigned char>& buf) -> size_t { return z.fill(buf); });
+      f.keep_qual = keep_qual;
       parse_all(f, fi);
     }
     (void)mm_ctx_release_cached(zctx);                           // (the stream's slots, up to 4.5 GiB, back to the driver beside the mapping)
   }
-  void read_sequential(size_t fi) { SeqFile f(queries[fi]); parse_all(f, fi); }   // gzip through zlib, pipes, ...
+  void read_sequential(size_t fi) { SeqFile f(queries[fi]); f.keep_qual = keep_qual; parse_all(f, fi); }   // gzip through zlib, pipes, ...
   void read_blocks(MappedFile& mf, size_t fi) {
     // blocks of the mapped file, parsed by several threads, handed on in file order; a block's batches only go out once the
     // block before it has been seen to end exactly where this one starts
@@ -252,6 +283,7 @@ struct QueryReader {
         const size_t lim = std::min(mf.size, (j + 1) * blk);
         if (j == 0 || start[j] < lim) {                        // records that start in [start[j], lim)
           SeqFile f(mf.data, j == 0 ? 0 : start[j], mf.size);
+          f.keep_qual = keep_qual;
           B.over = !parse_into(f, lim, [&](std::unique_ptr<Batch> b) { B.out.push_back(std::move(b)); });
           B.next = f.peek_start();
         } else B.empty = true;                                 // no record start was recognised in this block
@@ -289,6 +321,7 @@ struct QueryReader {
     if (!chain_ok) {                                           // a block did not start where the parse stood: the rest sequentially, from there
       for (auto& B : blocks) for (auto& b : B.out) reader.recycle(std::move(b));
       SeqFile f(mf.data, expect, mf.size);
+      f.keep_qual = keep_qual;
       parse_into(f, (size_t)-1, [&](std::unique_ptr<Batch> b) { enqueue(std::move(b), fi); });
     }
   }
@@ -311,6 +344,8 @@ struct QueryReader {
         else read_blocks(mapped.back(), fi);
       }
       if (lap) pc.add(lap, std::chrono::duration<double>(std::chrono::steady_clock::now() - f_t0).count());
+      if (keep_qual && q_reads && !q_with) std::cout << "INFO, --base-qualities: " << q << " carries no qualities: every base of its reads is without one (0xFF in PREFIX.bam)\n";
+      q_reads = q_with = 0;
       std::lock_guard<std::mutex> lk(reader.m); reader.file_end.push_back(seq); reader.cv.notify_all();
     }
     { const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - r_t0).count();

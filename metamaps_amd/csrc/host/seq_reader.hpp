@@ -46,6 +46,10 @@ class SeqFile {
  public:
   std::string name, seq;
   const char* view = nullptr; size_t view_len = 0;               // memory mode: the sequence where it lies in the file
+  // --base-qualities (keep_qual, set by the owner before the first record): the quality characters the parse validates are kept as well.  has_qual: the
+  // record just returned is a FASTQ record; its qualities are qview (beside `view`: the quality line where it lies in the file) or `qual`
+  bool keep_qual = false, has_qual = false;
+  const char* qview = nullptr; std::string qual;
   size_t rec_start = 0;
   explicit SeqFile(const std::string& path) : own_(1 << 20) { fp_ = gzopen(path.c_str(), "r"); if (!fp_) seq_reader_die("Cannot open " + path); buf_.p = own_.data(); }
   explicit SeqFile(std::function<size_t(std::vector<unsigned char>&)> fill) : own_(1), fill_(std::move(fill)) { buf_.p = own_.data(); }
@@ -61,10 +65,10 @@ class SeqFile {
   size_t length() const { return view ? view_len : seq.size(); }
   bool next() {
     int c;
-    view = nullptr; view_len = 0;
+    view = nullptr; view_len = 0; qview = nullptr; has_qual = false;
     if (!pending_) { while ((c = get()) != -1 && c != '>' && c != '@') {} if (c == -1) return false; pending_ = c; pending_pos_ = beg_ - 1; }
     rec_start = pending_pos_;
-    name.clear(); seq.clear();
+    name.clear(); seq.clear(); qual.clear();
     bool any = false;
     while ((c = get()) != -1 && !isspace(c)) { name.push_back((char)c); any = true; }
     if (c == -1 && !any) return false;
@@ -87,6 +91,7 @@ class SeqFile {
           const unsigned char* ql = pl + 1;
           unsigned char qb = 0;
           for (const unsigned char* q = ql; q < ql + L; ++q) qb |= (unsigned char)((unsigned char)(*q - 33) > 94);
+          if (!qb && keep_qual) { qview = (const char*)ql; has_qual = true; }
           if (!qb) { view = (const char*)p; view_len = L; beg_ = (size_t)(ql + L - base) + (ql + L < fe ? 1 : 0); pending_ = 0; return true; }   // (+1: kseq.h:200, below)
         }
       }
@@ -129,17 +134,18 @@ class SeqFile {
       const size_t want = seq.size() - got, avail = (size_t)(e - p);
       if (avail <= want) {                                       // the whole rest of the buffer cannot overshoot
         size_t cnt = 0;
-        for (const unsigned char* q = p; q < e; ++q) cnt += (unsigned)(*q - 33u) <= 94u;
+        for (const unsigned char* q = p; q < e; ++q) { const bool ok = (unsigned)(*q - 33u) <= 94u; cnt += ok; if (keep_qual && ok) qual.push_back((char)*q); }
         got += cnt; beg_ = end_;
       } else {
         unsigned char bad = 0;                                   // usual case: the next `want` bytes are the quality line
         for (const unsigned char* q = p; q < p + want; ++q) bad |= (unsigned char)((unsigned char)(*q - 33) > 94);
-        if (!bad) { got += want; beg_ += want; }
-        else { while (p < e && got < seq.size()) { got += (unsigned)(*p - 33u) <= 94u; ++p; } beg_ = (size_t)(p - buf_.data()); }
+        if (!bad) { if (keep_qual) qual.append((const char*)p, want); got += want; beg_ += want; }
+        else { while (p < e && got < seq.size()) { const bool ok = (unsigned)(*p - 33u) <= 94u; got += ok; if (keep_qual && ok) qual.push_back((char)*p); ++p; } beg_ = (size_t)(p - buf_.data()); }
       }
     }
     pending_ = 0;
     if (got != seq.size()) return false;                         // truncated quality string: kseq returns -2 and the callers' loops end (kseq.h:204)
+    has_qual = keep_qual;
     (void)get();                                                 // kseq.h:200 reads a character before it tests the count: the one behind the last quality is consumed too
     return true;                                                 // (normally the line's '\n'; a '@' that follows without a line break is lost, as in the reference)
   }

@@ -44,8 +44,10 @@ VcfOpts vcf_options(const Options& o) {
   return p;
 }
 
-std::string vcf_header(const std::vector<std::string>& cname, const std::vector<int>& clen) {
+// (min_base_quality > 0, --min-base-quality: one more line, which names the floor the alleles were counted under)
+std::string vcf_header(const std::vector<std::string>& cname, const std::vector<int>& clen, int min_base_quality = 0) {
   std::string t = "##fileformat=VCFv4.2\n##source=metamaps mapDirectly --vcf\n";
+  if (min_base_quality > 0) { t += "##minBaseQuality="; append_int(t, min_base_quality); t += "\n"; }
   for (size_t c = 0; c < cname.size(); ++c) { t += "##contig=<ID="; t += cname[c]; t += ",length="; append_int(t, clen[c]); t += ">\n"; }
   t += "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Primary alignments that span the position\">\n"
        "##INFO=<ID=AO,Number=1,Type=Integer,Description=\"Primary alignments that carry the allele\">\n"

@@ -221,6 +221,28 @@ int mm_seqset_add_nt16(mm_seqset* s, const uint8_t* nt16, int64_t n_bases, int r
     s->staged_rev.push_back(reverse ? 1 : 0);
   });
 }
+int mm_seqset_add_qual(mm_seqset* s, const uint8_t* qual, int64_t len, int offset) {
+  if (!s || (!qual && len > 0) || len < 0) return MM_ERR_ARG;
+  return guarded(s->ctx, [&] {
+    MM_REQUIRE(!s->frozen, MM_ERR_ARG, "mm_seqset_add_qual: the sequence set is already uploaded");
+    MM_REQUIRE(!s->staged.empty(), MM_ERR_ARG, "mm_seqset_add_qual: the set has no sequence yet");
+    MM_REQUIRE(offset == 0 || offset == 33, MM_ERR_ARG, "mm_seqset_add_qual: offset is not 0 or 33");
+    MM_REQUIRE((size_t)len == s->staged.back().second, MM_ERR_ARG, "mm_seqset_add_qual: len is not the length of the sequence added last");
+    s->staged_qual.resize(s->staged.size());
+    MM_REQUIRE(!s->staged_qual.back().set, MM_ERR_ARG, "mm_seqset_add_qual: the sequence added last has its qualities already");
+    s->staged_qual.back() = mm_seqset::StagedQual{qual, offset, true};
+  });
+}
+int mm_seqset_has_qual(const mm_seqset* s) {
+  if (!s) return 0;
+  if (s->frozen) return s->has_qual ? 1 : 0;
+  for (const auto& q : s->staged_qual) if (q.set) return 1;
+  return 0;
+}
+int mm_seqset_fetch_qual(mm_seqset* s, int64_t i, uint8_t* out, int64_t cap) {
+  if (!s || (!out && cap > 0)) return MM_ERR_ARG;
+  return guarded(s->ctx, [&] { mm::seqset_fetch_qual(s, i, out, cap); });
+}
 int mm_bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const int64_t* comp_off, const int32_t* comp_len, int32_t n,
                     uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status) {
   if (!ctx || n < 0 || comp_bytes < 0 || out_cap < 0 || (n > 0 && (!comp || !comp_off || !comp_len || !out_off)) || (!out && out_cap > 0)) return MM_ERR_ARG;
@@ -768,13 +790,17 @@ void mm_bam_destroy(mm_bam* b) { delete b; }
 
 struct mm_pileup { mm::KeyTable t; };                              // (host memory only, as mm_alignment; one-word keys: t.w1 stays empty)
 struct mm_pileup_result { mm::PileupResult r; };
-int mm_pileup_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
-                     const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, mm_pileup** out) {
+int mm_pileup_events_q(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
+                       const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, int32_t min_base_quality, mm_pileup** out) {
   if (!ctx || !reads || !reference || !out) return refused(out);
   return created(ctx, out, [&](mm_pileup& t) {
     require_jobs("mm_pileup_events", n_jobs, read && strand && contig && dist && first && op_off && use);
-    mm::pileup_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, &t.t);
+    mm::pileup_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, min_base_quality, &t.t);
   });
+}
+int mm_pileup_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
+                     const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, mm_pileup** out) {
+  return mm_pileup_events_q(ctx, reads, reference, n_jobs, read, strand, contig, dist, first, op_off, ops, use, 0, out);
 }
 int mm_pileup_merge(mm_ctx* ctx, int64_t n, const uint64_t* keys, const uint32_t* counts, mm_pileup** out) {
   if (!ctx || !out) return refused(out);
@@ -819,13 +845,17 @@ void mm_pileup_result_destroy(mm_pileup_result* r) { delete r; }
 
 struct mm_vcf { mm::KeyTable t; };                                 // (host memory only, as mm_pileup; two-word keys)
 struct mm_vcf_result { mm::VcfResult r; };
-int mm_vcf_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
-                  const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, mm_vcf** out) {
+int mm_vcf_events_q(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
+                    const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, int32_t min_base_quality, mm_vcf** out) {
   if (!ctx || !reads || !reference || !out) return refused(out);
   return created(ctx, out, [&](mm_vcf& t) {
     require_jobs("mm_vcf_events", n_jobs, read && strand && contig && dist && first && op_off && use);
-    mm::vcf_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, &t.t);
+    mm::vcf_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, min_base_quality, &t.t);
   });
+}
+int mm_vcf_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
+                  const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, mm_vcf** out) {
+  return mm_vcf_events_q(ctx, reads, reference, n_jobs, read, strand, contig, dist, first, op_off, ops, use, 0, out);
 }
 int mm_vcf_merge(mm_ctx* ctx, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, mm_vcf** out) {
   if (!ctx || !out) return refused(out);

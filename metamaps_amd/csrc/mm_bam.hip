@@ -5,7 +5,8 @@
 //            atomic minimum; the host reads the word before anything else is launched.
 //   offsets  an exclusive scan of the sizes (mm_prims.hpp).  The host reads them back and cuts the jobs into groups whose records fit group_bytes.
 //   write    bam_write_kernel: one wavefront per record of the group; the lanes share the name, the run words, the nibble-packed bases, the
-//            qualities and the pieces of the MD text.  Records start at any byte offset: everything is stored by bytes, 64 neighbouring ones per
+//            qualities (the bytes of the reads' quality plane where the set has one, 0xFF otherwise) and the pieces of the MD
+//            text.  Records start at any byte offset: everything is stored by bytes, 64 neighbouring ones per
 //            store of the wavefront.
 //   deflate  the group's records are the input of bgzf_deflate_kernel where they lie (mm_deflate.hip: bgzf_deflate_resident); only the members come
 //            to the host.  One buffer of the largest group's size serves every group.
@@ -47,7 +48,7 @@ __global__ void __launch_bounds__(64) bam_size_kernel(const int32_t* __restrict_
 // the records of the jobs [job0, job1) of a group to raw + (off[job] - off0); a job of size 0 has none
 __global__ void __launch_bounds__(64) bam_write_kernel(EditSeq Q, const uint64_t* __restrict__ q_base, const int32_t* __restrict__ q_len, EditSeq R,
                                                        const uint64_t* __restrict__ r_base, const int32_t* __restrict__ r_len, AlignedJobs J, BamColumns C, int64_t job0,
-                                                       int64_t job1, const int64_t* __restrict__ off, int64_t off0, uint8_t* __restrict__ raw) {
+                                                       int64_t job1, const int64_t* __restrict__ off, int64_t off0, const uint8_t* __restrict__ q_qual, uint8_t* __restrict__ raw) {
   const int64_t job = job0 + (int64_t)blockIdx.x;
   if (job >= job1 || off[job + 1] == off[job]) return;
   WaveLanes p;
@@ -57,7 +58,7 @@ __global__ void __launch_bounds__(64) bam_write_kernel(EditSeq Q, const uint64_t
   j.ops = J.ops + J.op_off[job]; j.n_ops = J.op_off[job + 1] - J.op_off[job];
   j.name = C.names + C.name_off[job]; j.l_name = (int32_t)(C.name_off[job + 1] - C.name_off[job]);
   j.first = J.first[job]; j.m = q_len[read]; j.refid = contig; j.strand = J.strand[job]; j.dist = J.dist[job]; j.flag = C.flag[job]; j.mapq = C.mapq[job];
-  mmb::write_record(p, j, SeqBytes{Q.narrowed(qg, qg + (uint64_t)j.m), (int64_t)qg}, SeqBytes{R.narrowed(rg, rg + (uint64_t)r_len[contig]), (int64_t)rg}, raw + (off[job] - off0));
+  mmb::write_record_q(p, j, SeqBytes{Q.narrowed(qg, qg + (uint64_t)j.m), (int64_t)qg, q_qual}, SeqBytes{R.narrowed(rg, rg + (uint64_t)r_len[contig]), (int64_t)rg}, raw + (off[job] - off0));
 }
 
 void bam_encode_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& jobs_in, const BamColumns& in, int64_t group_bytes, BamMembers* out) {
@@ -115,7 +116,7 @@ void bam_encode_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, c
     clk.start();
     for_job_grids(j0, j1, [&](int64_t a, dim3 grid) {
       bam_write_kernel<<<grid, dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, edit_seq(ref), ref->d_base.p, ref->d_len.p, J, C, a, j1, d_off.p, off[(size_t)j0],
-                                                  d_raw.p);
+                                                  reads->qual_ptr(), d_raw.p);
     });
     clk.stop(3);
     clk.start();

@@ -3,7 +3,7 @@
 // tests/bam_ref.py byte for byte).
 //
 //   record   block_size | refID pos l_read_name mapq bin n_cigar_op flag l_seq next_refID (-1) next_pos (-1) tlen (0) | read_name NUL | cigar |
-//            seq (4-bit codes of =ACMGRSVTWYHKDBN, first base in the high nibble) | qual (0xFF) | NM:i (int32) | MD:Z | CG:B,I (long CIGARs only)
+//            seq (4-bit codes of =ACMGRSVTWYHKDBN, first base in the high nibble) | qual (Phred bytes, 0xFF without) | NM:i (int32) | MD:Z | CG:B,I (long CIGARs only)
 //   cigar    the alignment's runs as they are (len << 4 | op; I 1, D 2, = 7, X 8).  More than 65 535 runs: the field holds l_seq S and refspan N,
 //            the runs go into the CG tag (the specification's convention).
 //   seq      the read as its set holds it, upper-cased; for strand - reversed, every code complemented by reversing its four bits.  A byte that is
@@ -21,7 +21,7 @@
 //   P::W, p.lane()              as in mm_deflate.hpp; per-lane code is `for (l = p.lane(); l < n; l += P::W)`
 //   p.scan_add(v, &total)       the sum of v over the lanes below this one, and over all lanes (host: 0 and v: its lanes run one by one, and the caller
 //   p.scan_max(v, &total)       keeps the running value); the same for the maximum of non-negative values
-// Q and R give q.byte(i), the read's byte i as stored (forward), and r.byte(j), the contig's byte j.
+// Q and R give q.byte(i), the read's byte i as stored (forward), and r.byte(j), the contig's byte j; write_record_q's Q also q.qual(i).
 //
 // Bounds: write_record reads ops[0, n_ops), name[0, l_name), q.byte(0 .. m - 1) and r.byte(first .. first + refspan - 1) and writes dst[0, size), size
 // the value record_size gave for the same job; the checks have passed before it runs, so first >= 0 and first + refspan <= the contig's length.
@@ -104,6 +104,22 @@ template <class Q> MM_HD uint32_t oriented_code(const Q& q, int32_t m, int32_t s
   return strand < 0 ? nt16_complement(nt16_code(q.byte(m - 1 - i))) : nt16_code(q.byte(i));
 }
 
+// A read source Q with qualities also gives q.qual(i), the stored quality of the read's base i (forward): Phred 0..93, 0xFF for "no quality".
+constexpr uint8_t QUAL_NONE = 0xFF;
+template <class Q> MM_HD uint8_t oriented_qual(const Q& q, int64_t m, int32_t strand, int64_t i) {   // of base i of the oriented read
+  return q.qual(strand < 0 ? m - 1 - i : i);
+}
+template <class Q> struct NoQual {                                // a source of bytes alone: every base is without quality
+  const Q& q;
+  MM_HD uint8_t byte(int64_t i) const { return q.byte(i); }
+  MM_HD uint8_t qual(int64_t) const { return QUAL_NONE; }
+};
+struct QualBytes {                                                // the host's source: the read's bytes and its stored qualities (null: none)
+  const uint8_t* b; const uint8_t* q;
+  uint8_t byte(int64_t i) const { return b[i]; }
+  uint8_t qual(int64_t i) const { return q ? q[i] : QUAL_NONE; }
+};
+
 // rule 1, asked of every job before anything is read through its indexes; the other rules are asked of the jobs that have a record (dist >= 0 and a
 // read that is not empty)
 MM_HD int check_set(int64_t read, int64_t n_reads, int64_t contig, int64_t n_contigs) {
@@ -166,7 +182,8 @@ MM_HD int64_t record_size(int64_t l_name, int64_t m, int64_t n_ops, int64_t md_l
 MM_HD void put32(uint8_t* o, uint32_t v) { o[0] = (uint8_t)v; o[1] = (uint8_t)(v >> 8); o[2] = (uint8_t)(v >> 16); o[3] = (uint8_t)(v >> 24); }
 
 // the record of a job whose checks have passed, at dst (any byte offset: everything is stored by bytes); returns its size
-template <class P, class Q, class R> MM_HD int64_t write_record(P& p, const Job& j, const Q& q, const R& ref, uint8_t* dst) {
+// (QUAL is the oriented read's qualities, 0xFF on every base of a read without)
+template <class P, class Q, class R> MM_HD int64_t write_record_q(P& p, const Job& j, const Q& q, const R& ref, uint8_t* dst) {
   const bool lc = long_cigar(j.n_ops);
   const int64_t n_field = lc ? 2 : j.n_ops, m = j.m;
   uint8_t* const name = dst + FIXED;
@@ -188,7 +205,7 @@ template <class P, class Q, class R> MM_HD int64_t write_record(P& p, const Job&
   else for (int64_t i = p.lane(); i < 4 * j.n_ops; i += P::W) cigar[i] = (uint8_t)(j.ops[i >> 2] >> (8 * (i & 3)));
   for (int64_t i = p.lane(); i < (m + 1) / 2; i += P::W)
     seq[i] = (uint8_t)(oriented_code(q, j.m, j.strand, (int32_t)(2 * i)) << 4 | (2 * i + 1 < m ? oriented_code(q, j.m, j.strand, (int32_t)(2 * i + 1)) : 0u));
-  for (int64_t i = p.lane(); i < m; i += P::W) qual[i] = 0xFF;
+  for (int64_t i = p.lane(); i < m; i += P::W) qual[i] = oriented_qual(q, m, j.strand, i);
   for (uint32_t l = p.lane(); l < 7; l += P::W) nm[l] = l == 0 ? 'N' : l == 1 ? 'M' : l == 2 ? 'i' : (uint8_t)((uint32_t)j.dist >> (8 * (l - 3)));
   for (uint32_t l = p.lane(); l < 4; l += P::W) { if (l < 3) md[l] = l == 0 ? 'M' : l == 1 ? 'D' : 'Z'; else md[3 + w.md_len] = 0; }
   if (lc) {
@@ -197,6 +214,11 @@ template <class P, class Q, class R> MM_HD int64_t write_record(P& p, const Job&
     for (int64_t i = p.lane(); i < 4 * j.n_ops; i += P::W) cg[8 + i] = (uint8_t)(j.ops[i >> 2] >> (8 * (i & 3)));
   }
   return size;
+}
+
+// the same of a read source without qualities
+template <class P, class Q, class R> MM_HD int64_t write_record(P& p, const Job& j, const Q& q, const R& ref, uint8_t* dst) {
+  return write_record_q(p, j, NoQual<Q>{q}, ref, dst);
 }
 
 // the host's lane policy: one lane

@@ -182,6 +182,8 @@ struct mm_seqset {
                                                                 // or, for a set of BAM's 4-bit codes (mm_seqset_add_nt16), (codes, bases)
   std::vector<uint8_t> staged_rev;                              // nt16 only: 1 = the record is the reverse complement of the read
   int staged_kind = 0;                                          // 0 nothing staged yet, 1 ASCII, 2 nt16: one set holds one kind
+  struct StagedQual { const uint8_t* p = nullptr; int offset = 0; bool set = false; };
+  std::vector<StagedQual> staged_qual;                          // mm_seqset_add_qual: the viewed quality bytes of staged[i] (shorter than `staged`: the rest have none)
   // host-side metadata (always valid after upload / synthesis)
   std::vector<int32_t> len;            // per sequence
   std::vector<uint64_t> base;          // [n+1] first base of sequence i in the packed stream (multiple of 16)
@@ -194,5 +196,10 @@ struct mm_seqset {
   mm::DBuf<uint32_t> exc_len;
   mm::DBuf<uint8_t> exc_byte;
   int64_t n_exc = 0;
+  // the quality plane (mm_seqset_add_qual; absent unless has_qual): byte base[i] + p is the Phred value 0..93 of base p of sequence i, 0xFF for "no
+  // quality" (a sequence added without qualities, and the padding)
+  bool has_qual = false;
+  mm::DBuf<uint8_t> qual;              // [base[n]]
+  const uint8_t* qual_ptr() const { return has_qual ? qual.p : nullptr; }
   int64_t count() const { return (int64_t)len.size(); }
 };

@@ -30,7 +30,11 @@ struct WaveLanes {                                                // one lane pe
   __device__ uint64_t ballot(bool b) const { return (uint64_t)__ballot(b); }
   __device__ int64_t pick(int64_t v, uint32_t l) const { return (int64_t)__shfl((long long)v, (int)l, 64); }
 };
-struct SeqBytes { EditSeq s; int64_t g0; __device__ uint8_t byte(int64_t i) const { return s.byte(g0 + i); } };   // read (or contig) coordinate -> the set's byte
+struct SeqBytes {                                                 // read (or contig) coordinate -> the set's byte, and the byte of its quality plane (null: no plane)
+  EditSeq s; int64_t g0; const uint8_t* q = nullptr;
+  __device__ uint8_t byte(int64_t i) const { return s.byte(g0 + i); }
+  __device__ uint8_t qual(int64_t i) const { return q ? q[g0 + i] : (uint8_t)0xFF; }
+};
 
 constexpr unsigned long long JOB_NO_ERROR = ~0ull;
 constexpr int64_t JOB_GRID_MAX = (int64_t)1 << 30;                // workgroups per launch

@@ -8,6 +8,8 @@
 //                     its read index and its place; a lane expands its own short run, the wavefront a run of more than 64 events.  Read bases come
 //                     through EditSeq::byte on a set narrowed to the read.  Keys are stored as 8-byte words, nothing else is written.
 //            reduce   one radix sort of the keys over the bits in use, then the segments of equal keys with their lengths (mm_keytable.hip).
+//            floor    mm_pileup_events_q: the emit kernel reads the reads' quality plane beside the bases and writes mmp::DROPPED in the place of an event
+//                     under the floor; every bit of it in use is set, so it sorts last, and its segment is cut off the table.  Floor 0: nothing differs.
 //   merge    mm_keytable.hip's merge_run over one-word keys: sort_pairs of (key, count) and the sums of the segments.
 //   finish   mm_keytable.hip's finish_kept with the reference's byte as a kept site's payload; per contig the alignments, the summed lengths and the
 //            union's length (each interval adds what lies beyond the running maximum of the ends before it, an inclusive max-scan) with 64-bit vector atomics.
@@ -35,15 +37,15 @@ __global__ void __launch_bounds__(64) pile_count_kernel(const int32_t* __restric
 }
 // the events of job to keys[off[job], off[job + 1]); a job without events (not used, not aligned, or all =) writes nothing
 __global__ void __launch_bounds__(64) pile_emit_kernel(EditSeq Q, const uint64_t* __restrict__ q_base, const int32_t* __restrict__ q_len, AlignedJobs J, int64_t job0,
-                                                       const int64_t* __restrict__ off, uint64_t* __restrict__ keys) {
+                                                       const int64_t* __restrict__ off, const uint8_t* __restrict__ q_qual, int32_t qmin, uint64_t* __restrict__ keys) {
   const int64_t job = job0 + (int64_t)blockIdx.x;
   if (job >= J.n || off[job + 1] == off[job]) return;
   WaveLanes p;
   const int32_t read = J.read[job];
   const uint64_t qg = q_base[read];
   const int64_t m = q_len[read];
-  mmp::emit_job(p, SeqBytes{Q.narrowed(qg, qg + (uint64_t)m), (int64_t)qg}, m, J.strand[job], J.contig[job], J.first[job], J.ops + J.op_off[job], J.op_off[job + 1] - J.op_off[job],
-                keys + off[job]);
+  mmp::emit_job_q(p, SeqBytes{Q.narrowed(qg, qg + (uint64_t)m), (int64_t)qg, q_qual}, m, J.strand[job], J.contig[job], J.first[job], J.ops + J.op_off[job],
+                  J.op_off[job + 1] - J.op_off[job], qmin, keys + off[job]);
 }
 // the intervals sorted by start key: end[i] belongs to start[i], pmax[i] is the largest end of the intervals 0 .. i
 __global__ void __launch_bounds__(256) pile_coverage_kernel(const uint64_t* __restrict__ start, const uint64_t* __restrict__ end, const uint64_t* __restrict__ pmax, int64_t n,
@@ -64,8 +66,10 @@ __global__ void __launch_bounds__(256) pile_coverage_kernel(const uint64_t* __re
   if (gain) atomicAdd(&covered[c], gain);
 }
 
-void pileup_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& in, const uint8_t* use, KeyTable* out) {
+void pileup_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& in, const uint8_t* use, int32_t min_base_quality, KeyTable* out) {
   AlignedJobsDev jobs(ctx, reads, ref, in, "mm_pileup_events");
+  MM_REQUIRE(min_base_quality >= 0 && min_base_quality <= 93, MM_ERR_ARG, "mm_pileup_events_q: min_base_quality is not in [0, 93]");
+  const int32_t qmin = reads->has_qual ? min_base_quality : 0;     // (reads without qualities pass every floor)
   MM_REQUIRE(ref->count() <= mmp::MAX_CONTIGS, MM_ERR_ARG, "mm_pileup_events: more than 2^29 contigs");
   out->clear();
   const int64_t n = in.n_jobs;
@@ -101,7 +105,7 @@ void pileup_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref
     clk.start();
     DBuf<uint64_t> d_keys((size_t)total);
     for_job_grids(0, n, [&](int64_t a, dim3 grid) {
-      pile_emit_kernel<<<grid, dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, J, a, d_off.p, d_keys.p);
+      pile_emit_kernel<<<grid, dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, J, a, d_off.p, reads->qual_ptr(), qmin, d_keys.p);
     });
     clk.stop(3);
     clk.start();
@@ -110,6 +114,7 @@ void pileup_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref
     clk.stop(4);
     clk.start();
     reduce_sorted(tmp, sorted, total, st, out);
+    if (qmin > 0 && !out->w0.empty() && out->w0.back() == mmp::DROPPED) { out->w0.pop_back(); out->counts.pop_back(); }   // the events under the floor: the last segment
     clk.stop(5);
   }
   if (clk.on)

@@ -15,6 +15,10 @@
 //   key      contig << 35 | pos << 3 | code: keys order by contig, position, code.  2^29 contigs at most.
 //   depth    of (contig, pos): the alignments on that contig with first <= pos <= last.  With the starts contig << 32 | first and the ends
 //            contig << 32 | last both ascending it is (starts <= x) - (ends < x) for x = contig << 32 | pos: two binary searches (depth_at).
+//   floor    mm_pileup_events_q's min_base_quality Qm > 0, with q(i) the quality of base i of the oriented read (mmb::oriented_qual; "no quality" is 255
+//            and passes every floor): the event of an X run at read index i + t is kept iff q(i + t) >= Qm; the n events of a D run met at read index
+//            i together iff min(q(i - 1) if i > 0, q(i) if i < m) >= Qm; the event of an I run iff min q(i .. i + n - 1) >= Qm.  An event that is not
+//            kept keeps its place and holds DROPPED, which sorts behind every key and is cut off the table.  Intervals and depth are untouched.
 //   checks   mm_bam_encode's rules 1, 2 (the strand), 4, 5 and 6 under its numbers (mm_bam_core.hpp): after them every read index of the walk
 //            is inside the read and every position inside the contig.
 //
@@ -23,7 +27,7 @@
 //   p.scan_add(v, &total)     the sum of v over the lanes below this one, and over all lanes (host: 0 and v)
 //   p.ballot(b)               bit l: lane l's b (host: bit 0)
 //   p.pick(v, l)              lane l's v (host: v)
-// Q gives q.byte(i), the read's byte i as its set holds it (forward).
+// Q gives q.byte(i), the read's byte i as its set holds it (forward); emit_job_q's Q also q.qual(i), its stored quality (mm_bam_core.hpp).
 //
 // Bounds: count_job reads ops[0, n_ops); emit_job reads the same and q.byte(0 .. m - 1) and writes out[0, events), events the value count_job gave
 // for the same job, whose checks have passed.
@@ -35,6 +39,7 @@ namespace mmp {
 constexpr uint32_t CODE_N = 4, CODE_DEL = 5, CODE_INS = 6, N_CODES = 7;
 constexpr int POS_SHIFT = 3, CONTIG_SHIFT = 35;
 constexpr int64_t MAX_CONTIGS = (int64_t)1 << 29;
+constexpr uint64_t DROPPED = ~0ull;                               // in the place of an event under the quality floor: code 7, which no key has; sorts last
 constexpr int64_t LONG_RUN = 64;                                  // a run with more events is expanded by all lanes of the tile
 
 MM_HD uint64_t make_key(int64_t contig, int64_t pos, uint32_t code) { return (uint64_t)contig << CONTIG_SHIFT | (uint64_t)pos << POS_SHIFT | code; }
@@ -96,8 +101,15 @@ template <class P> MM_HD int count_job(P& p, int64_t read, int64_t n_reads, int6
   return mmb::BAM_OK;
 }
 
-// the events of a job whose checks have passed to out[0, events), in the order of the walk; returns their number (the same in every lane)
-template <class P, class Q> MM_HD int64_t emit_job(P& p, const Q& q, int64_t m, int32_t strand, int64_t contig, int64_t first, const uint32_t* ops, int64_t n_ops, uint64_t* out) {
+// the D run met at read index i of the oriented read: the read's bases on either side of the gap
+template <class Q> MM_HD bool del_kept(const Q& q, int64_t m, int32_t strand, int64_t i, int32_t qmin) {
+  return (i <= 0 || mmb::oriented_qual(q, m, strand, i - 1) >= qmin) && (i >= m || mmb::oriented_qual(q, m, strand, i) >= qmin);
+}
+
+// the events of a job whose checks have passed to out[0, events), in the order of the walk; returns their number (the same in every lane).  Under
+// a floor qmin > 0 an event that is not kept leaves DROPPED in its place: count_job's number is that of the places.
+template <class P, class Q> MM_HD int64_t emit_job_q(P& p, const Q& q, int64_t m, int32_t strand, int64_t contig, int64_t first, const uint32_t* ops, int64_t n_ops, int32_t qmin,
+                                                     uint64_t* out) {
   int64_t rsum = 0, isum = 0, at = 0;                             // the running values: the same in every lane
   for (int64_t base = 0; base < n_ops; base += P::W) {
     const Run x = run_of(ops, base + p.lane(), n_ops);
@@ -106,20 +118,43 @@ template <class P, class Q> MM_HD int64_t emit_job(P& p, const Q& q, int64_t m, 
     const int64_t r = first + rsum + p.scan_add(x.good && x.op != mmb::OP_I ? x.len : 0, &tot); rsum += tot;
     const int64_t i = isum + p.scan_add(x.good && x.op != mmb::OP_D ? x.len : 0, &tot); isum += tot;
     const int64_t o = at + p.scan_add(ev, &tot); at += tot;
-    const bool wide = ev > LONG_RUN;
+    const bool ins = x.good && x.op == mmb::OP_I;
+    const bool wide = ev > LONG_RUN || (qmin > 0 && ins && x.len > LONG_RUN);   // (under a floor a long insertion's minimum is taken by all lanes)
     if (ev && !wide) {                                            // a short run: its own lane writes it
-      if (x.op == mmb::OP_I) out[o] = make_key(contig, r > first ? r - 1 : first, CODE_INS);
-      else for (int64_t t = 0; t < ev; ++t) out[o + t] = make_key(contig, r + t, x.op == mmb::OP_D ? CODE_DEL : oriented_code(q, m, strand, i + t));
+      if (ins) {
+        bool keep = true;
+        if (qmin > 0) for (int64_t t = 0; t < x.len; ++t) keep = keep && mmb::oriented_qual(q, m, strand, i + t) >= qmin;
+        out[o] = keep ? make_key(contig, r > first ? r - 1 : first, CODE_INS) : DROPPED;
+      } else if (x.op == mmb::OP_D) {
+        const bool keep = qmin <= 0 || del_kept(q, m, strand, i, qmin);
+        for (int64_t t = 0; t < ev; ++t) out[o + t] = keep ? make_key(contig, r + t, CODE_DEL) : DROPPED;
+      } else
+        for (int64_t t = 0; t < ev; ++t) out[o + t] = qmin <= 0 || mmb::oriented_qual(q, m, strand, i + t) >= qmin ? make_key(contig, r + t, oriented_code(q, m, strand, i + t)) : DROPPED;
     }
     for (uint64_t left = p.ballot(wide); left; left &= left - 1) {   // the long runs of the tile, one after the other, by all lanes
       uint32_t l = 0;
       while (!(left >> l & 1)) ++l;
-      const int64_t lr = p.pick(r, l), li = p.pick(i, l), lo = p.pick(o, l), ln = p.pick(ev, l);
-      const bool del = p.pick((int64_t)x.op, l) == (int64_t)mmb::OP_D;
-      for (int64_t t = p.lane(); t < ln; t += P::W) out[lo + t] = make_key(contig, lr + t, del ? CODE_DEL : oriented_code(q, m, strand, li + t));
+      const int64_t lr = p.pick(r, l), li = p.pick(i, l), lo = p.pick(o, l), ln = p.pick(ev, l), lop = p.pick((int64_t)x.op, l);
+      if (lop == (int64_t)mmb::OP_I) {                              // (qmin > 0) one event, kept iff no lane met a base below the floor
+        const int64_t n = p.pick(x.len, l);
+        bool low = false;
+        for (int64_t t = p.lane(); t < n; t += P::W) low = low || mmb::oriented_qual(q, m, strand, li + t) < qmin;
+        const bool drop = p.ballot(low) != 0;
+        if (p.lane() == 0) out[lo] = drop ? DROPPED : make_key(contig, lr > first ? lr - 1 : first, CODE_INS);
+        continue;
+      }
+      const bool del = lop == (int64_t)mmb::OP_D, keep_del = !del || qmin <= 0 || del_kept(q, m, strand, li, qmin);
+      for (int64_t t = p.lane(); t < ln; t += P::W)
+        out[lo + t] = del ? (keep_del ? make_key(contig, lr + t, CODE_DEL) : DROPPED)
+                          : qmin <= 0 || mmb::oriented_qual(q, m, strand, li + t) >= qmin ? make_key(contig, lr + t, oriented_code(q, m, strand, li + t)) : DROPPED;
     }
   }
   return at;
+}
+
+// the same without a floor, of a read source without qualities
+template <class P, class Q> MM_HD int64_t emit_job(P& p, const Q& q, int64_t m, int32_t strand, int64_t contig, int64_t first, const uint32_t* ops, int64_t n_ops, uint64_t* out) {
+  return emit_job_q(p, mmb::NoQual<Q>{q}, m, strand, contig, first, ops, n_ops, 0, out);
 }
 
 // first index of the ascending a[0, n) with a[i] >= x (upper: a[i] > x)

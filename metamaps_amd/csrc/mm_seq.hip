@@ -192,6 +192,7 @@ void seqset_upload(mm_seqset* s) {
     s->exc_byte.alloc(eb.size()); s->exc_byte.upload(eb.data(), eb.size(), st);
   }
   MM_HIP(mm::stream_sync(st));
+  seqset_upload_qual(s);
   s->staged.clear(); s->staged.shrink_to_fit(); s->owned.clear(); s->owned.shrink_to_fit();
   s->frozen = true;
 }
@@ -353,8 +354,117 @@ void seqset_upload_nt16(mm_seqset* s) {
     MM_HIP(mm::stream_sync(st));                                 // (the staging and the temporaries are released behind the kernels)
   }
   MM_HIP(mm::stream_sync(st));
+  seqset_upload_qual(s);
   s->staged.clear(); s->staged.shrink_to_fit(); s->staged_rev.clear(); s->staged_rev.shrink_to_fit();
   s->frozen = true;
+}
+
+// ---- the quality plane (mm_seqset_add_qual) ----------------------------------------------------------------------------------------------
+// The viewed bytes go up as they are, row i at base[i] of a staging of the plane's size (rows start on 16-byte boundaries, as the bases' words do), and
+// one kernel writes the plane from them: one lane per 16 bytes of the plane subtracts the row's offset, writes 0xFF into the padding and into rows
+// without qualities, and reads a reversed row (an nt16 record added with reverse = 1) from its end, so that byte p stays with base p as
+// nt16_pack_kernel reverse-complements it.  A byte outside [offset, offset + 93] puts (sequence << 8 | byte) into the error word with an atomic minimum.
+namespace {
+constexpr int QUAL_NONE = -1;                                      // a row's offset where it has no qualities
+constexpr uint32_t QUAL_MAX = 93;
+constexpr unsigned long long QUAL_NO_ERROR = ~0ull;
+
+__global__ void __launch_bounds__(256) qual_plane_kernel(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ base, const int32_t* __restrict__ len, const int8_t* __restrict__ offset,
+                                                         const uint8_t* __restrict__ rev, int64_t n, int64_t nwords, uint8_t* __restrict__ plane, unsigned long long* __restrict__ err) {
+  const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= nwords) return;
+  const uint64_t g = (uint64_t)w << 4;
+  const int64_t i = nt16_seq_of(base, n, g);
+  const int64_t L = len[i], j0 = (int64_t)(g - base[i]);
+  const int off = offset[i];
+  uint4 out = make_uint4(~0u, ~0u, ~0u, ~0u);
+  if (off != QUAL_NONE) {
+    const uint8_t* const row = raw + base[i];
+    const bool reversed = rev && rev[i];
+    uint32_t v[4];
+    if (j0 + 16 <= L) {                                            // a full piece: 16 bytes in one load; a reversed row's lie [L - 16 - j0, L - j0), at any byte offset
+      if (!reversed) { const uint4 x = *(const uint4*)(row + j0); v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w; }
+      else {
+        uint32_t x[4];
+        __builtin_memcpy(x, row + (L - 16 - j0), 16);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = __builtin_bswap32(x[3 - k]);
+      }
+    } else {                                                       // the row's last piece: byte by byte, the padding stays 0xFF
+      const int m = (int)(L - j0);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = ~0u;
+      for (int t = 0; t < m; ++t) {
+        const uint32_t b = row[reversed ? L - 1 - j0 - t : j0 + t];
+        v[t >> 2] = (v[t >> 2] & ~(255u << (8 * (t & 3)))) | b << (8 * (t & 3));
+      }
+    }
+    const int m = (int)(L - j0 < 16 ? L - j0 : 16);
+    uint32_t worst = ~0u;                                          // the smallest byte out of range
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      if (t >= m) continue;
+      const uint32_t b = (v[t >> 2] >> (8 * (t & 3))) & 255u, q = b - (uint32_t)off;
+      if (q > QUAL_MAX) worst = b < worst ? b : worst;
+      v[t >> 2] = (v[t >> 2] & ~(255u << (8 * (t & 3)))) | (q & 255u) << (8 * (t & 3));
+    }
+    if (worst != ~0u) atomicMin(err, (unsigned long long)i << 8 | worst);
+    out = make_uint4(v[0], v[1], v[2], v[3]);
+  }
+  *(uint4*)(plane + g) = out;
+}
+}  // namespace
+
+void seqset_upload_qual(mm_seqset* s) {
+  bool any = false;
+  for (const auto& q : s->staged_qual) any = any || q.set;
+  if (!any) { s->staged_qual.clear(); return; }                   // nothing is allocated and nothing launched for a set without qualities
+  hipStream_t st = s->ctx->stream;
+  const size_t n = s->staged.size(), nbytes = (size_t)s->base[n];
+  s->has_qual = true;
+  s->qual.alloc(nbytes);
+  if (nbytes) {
+    std::vector<int8_t> off(n, (int8_t)QUAL_NONE);
+    for (size_t i = 0; i < s->staged_qual.size(); ++i) if (s->staged_qual[i].set) off[i] = (int8_t)s->staged_qual[i].offset;
+    uint8_t* const stage = (uint8_t*)s->ctx->pinned_up_at_least(nbytes);   // (the bases' upload out of this buffer is through: the callers have waited for it)
+    const size_t nthr = (size_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)std::max(1u, mm::cpu_budget() / 2), 32, (uint64_t)(nbytes >> 23) + 1, (uint64_t)n}));
+    auto copy = [&](size_t t) {
+      for (size_t i = n * t / nthr; i < n * (t + 1) / nthr; ++i) if (off[i] != QUAL_NONE && s->len[i]) memcpy(stage + s->base[i], s->staged_qual[i].p, (size_t)s->len[i]);
+    };
+    if (nthr > 1) { if (!s->ctx->pack_pool) s->ctx->pack_pool = std::make_unique<TaskPool>(31); s->ctx->pack_pool->run(nthr, copy); }
+    else copy(0);
+    DBuf<uint8_t> d_raw(nbytes), d_rev;
+    d_raw.upload(stage, nbytes, st);
+    DBuf<int8_t> d_off(n);
+    d_off.upload(off.data(), n, st);
+    if (s->staged_kind == 2) { d_rev.alloc(n); d_rev.upload(s->staged_rev.data(), n, st); }
+    DBuf<unsigned long long> d_err(1);
+    MM_HIP(hipMemsetAsync(d_err.p, 0xFF, sizeof(unsigned long long), st));
+    const int64_t nwords = (int64_t)(nbytes >> 4);
+    qual_plane_kernel<<<dim3((unsigned)ceil_div(nwords, 256)), dim3(256), 0, st>>>(d_raw.p, s->d_base.p, s->d_len.p, d_off.p, d_rev.p, (int64_t)n, nwords, s->qual.p, d_err.p);
+    MM_KERNEL_CHECK();
+    const unsigned long long e = d_err.to_host(st)[0];
+    MM_HIP(mm::stream_sync(st));
+    if (e != QUAL_NO_ERROR) {
+      const size_t i = (size_t)(e >> 8);
+      s->has_qual = false; s->qual.release();
+      throw Error(MM_ERR_DATA, "mm_seqset_upload: sequence " + std::to_string(i) + " has the quality byte " + std::to_string((unsigned)(e & 255)) + ", outside [" +
+                                   std::to_string(off[i]) + ", " + std::to_string(off[i] + (int)QUAL_MAX) + "]");
+    }
+  }
+  s->staged_qual.clear(); s->staged_qual.shrink_to_fit();
+}
+
+void seqset_fetch_qual(mm_seqset* s, int64_t i, uint8_t* out, int64_t cap) {
+  MM_REQUIRE(s->frozen, MM_ERR_STATE, "sequence set not uploaded");
+  MM_REQUIRE(i >= 0 && i < s->count(), MM_ERR_ARG, "sequence index out of range");
+  const int64_t L = s->len[(size_t)i];
+  MM_REQUIRE(cap >= L, MM_ERR_ARG, "output buffer too small");
+  if (!L) return;
+  if (!s->has_qual) { memset(out, 0xFF, (size_t)L); return; }
+  hipStream_t st = s->ctx->stream;
+  MM_HIP(hipMemcpyAsync(out, s->qual.p + s->base[(size_t)i], (size_t)L, hipMemcpyDeviceToHost, st));
+  MM_HIP(mm::stream_sync(st));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -475,6 +585,10 @@ void seqset_slice(const mm_seqset* s, int64_t first, int64_t count, mm_seqset* o
   o->packed.alloc(nw + 1);                                       // (+1: the pad word every set ends on)
   if (nw) MM_HIP(hipMemcpyAsync(o->packed.p, s->packed.p + (b0 >> 4), nw * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
   MM_HIP(hipMemsetAsync(o->packed.p + nw, 0, sizeof(uint32_t), st));
+  if (s->has_qual) {                                             // the quality plane: the same range of the stream, one byte per base
+    o->has_qual = true; o->qual.alloc((size_t)(b1 - b0));
+    if (b1 > b0) MM_HIP(hipMemcpyAsync(o->qual.p, s->qual.p + b0, (size_t)(b1 - b0), hipMemcpyDeviceToDevice, st));
+  }
   std::vector<uint64_t> es, oes; std::vector<uint32_t> el, oel; std::vector<uint8_t> eb, oeb;
   exc_to_host(s, es, el, eb);
   const size_t lo = (size_t)(std::lower_bound(es.begin(), es.end(), b0) - es.begin()), hi = (size_t)(std::lower_bound(es.begin(), es.end(), b1) - es.begin());
@@ -492,12 +606,18 @@ void seqset_concat(const mm_seqset* const* parts, int n_parts, mm_seqset* o) {
   o->len.clear(); o->len.reserve(nseq); o->base.clear(); o->base.reserve(nseq + 1);
   o->total_bases = 0;
   o->packed.alloc((size_t)(bases >> 4) + 1);
+  for (int p = 0; p < n_parts; ++p) o->has_qual = o->has_qual || parts[p]->has_qual;
+  if (o->has_qual) o->qual.alloc((size_t)bases);                 // (a part without a plane gives rows of 0xFF)
   std::vector<uint64_t> oes; std::vector<uint32_t> oel; std::vector<uint8_t> oeb;
   uint64_t b0 = 0;
   for (int p = 0; p < n_parts; ++p) {
     const mm_seqset* s = parts[p];
     const size_t nw = (size_t)(s->base.back() >> 4);
     if (nw) MM_HIP(hipMemcpyAsync(o->packed.p + (b0 >> 4), s->packed.p, nw * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    if (o->has_qual && nw) {
+      if (s->has_qual) MM_HIP(hipMemcpyAsync(o->qual.p + b0, s->qual.p, nw << 4, hipMemcpyDeviceToDevice, st));
+      else MM_HIP(hipMemsetAsync(o->qual.p + b0, 0xFF, nw << 4, st));
+    }
     for (size_t i = 0; i < s->len.size(); ++i) { o->len.push_back(s->len[i]); o->base.push_back(b0 + s->base[i]); }
     o->total_bases += s->total_bases;
     std::vector<uint64_t> es; std::vector<uint32_t> el; std::vector<uint8_t> eb;

@@ -5,6 +5,8 @@
 namespace mm {
 void seqset_upload(mm_seqset* s);
 void seqset_upload_nt16(mm_seqset* s);
+void seqset_upload_qual(mm_seqset* s);                           // the quality plane of the staged sequences, called by the two above
+void seqset_fetch_qual(mm_seqset* s, int64_t i, uint8_t* out, int64_t cap);
 void seqset_save(mm_seqset* s, const char* path);
 void seqset_load(mm_seqset* s, const char* path);
 void seqset_fetch(mm_seqset* s, int64_t i, char* out, int64_t cap);

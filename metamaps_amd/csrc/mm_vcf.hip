@@ -38,15 +38,16 @@ __global__ void __launch_bounds__(64) vcf_count_kernel(const int32_t* __restrict
 }
 // the alleles of job to w0 and w1 [off[job], off[job + 1]); a job without any (not used, not aligned, or nothing but = and edge runs) writes nothing
 __global__ void __launch_bounds__(64) vcf_emit_kernel(EditSeq Q, const uint64_t* __restrict__ q_base, const int32_t* __restrict__ q_len, EditSeq R, const uint64_t* __restrict__ r_base,
-                                                      AlignedJobs J, int64_t job0, const int64_t* __restrict__ off, uint64_t* __restrict__ w0, uint64_t* __restrict__ w1) {
+                                                      AlignedJobs J, int64_t job0, const int64_t* __restrict__ off, const uint8_t* __restrict__ q_qual, int32_t qmin, uint64_t* __restrict__ w0,
+                                                      uint64_t* __restrict__ w1) {
   const int64_t job = job0 + (int64_t)blockIdx.x;
   if (job >= J.n || off[job + 1] == off[job]) return;
   WaveLanes p;
   const int32_t read = J.read[job], contig = J.contig[job];
   const uint64_t qg = q_base[read];
   const int64_t m = q_len[read];
-  mmv::emit_job(p, SeqBytes{Q.narrowed(qg, qg + (uint64_t)m), (int64_t)qg}, m, J.strand[job], SeqBytes{R, (int64_t)r_base[contig]}, contig, J.first[job], J.ops + J.op_off[job],
-                J.op_off[job + 1] - J.op_off[job], w0 + off[job], w1 + off[job]);
+  mmv::emit_job_q(p, SeqBytes{Q.narrowed(qg, qg + (uint64_t)m), (int64_t)qg, q_qual}, m, J.strand[job], SeqBytes{R, (int64_t)r_base[contig]}, contig, J.first[job],
+                  J.ops + J.op_off[job], J.op_off[job + 1] - J.op_off[job], qmin, w0 + off[job], w1 + off[job]);
 }
 
 namespace {
@@ -55,8 +56,10 @@ void cut_skipped(KeyTable* t) {                                   // the all-one
 }
 }  // namespace
 
-void vcf_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& in, const uint8_t* use, KeyTable* out) {
+void vcf_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& in, const uint8_t* use, int32_t min_base_quality, KeyTable* out) {
   AlignedJobsDev jobs(ctx, reads, ref, in, "mm_vcf_events");
+  MM_REQUIRE(min_base_quality >= 0 && min_base_quality <= 93, MM_ERR_ARG, "mm_vcf_events_q: min_base_quality is not in [0, 93]");
+  const int32_t qmin = reads->has_qual ? min_base_quality : 0;     // (reads without qualities pass every floor)
   MM_REQUIRE(ref->count() <= mmp::MAX_CONTIGS, MM_ERR_ARG, "mm_vcf_events: more than 2^29 contigs");
   out->clear();
   const int64_t n = in.n_jobs;
@@ -94,7 +97,7 @@ void vcf_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, c
     clk.start();
     DBuf<uint64_t> d_w0((size_t)total), d_w1((size_t)total);
     for_job_grids(0, n, [&](int64_t a, dim3 grid) {
-      vcf_emit_kernel<<<grid, dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, edit_seq(ref), ref->d_base.p, J, a, d_off.p, d_w0.p, d_w1.p);
+      vcf_emit_kernel<<<grid, dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, edit_seq(ref), ref->d_base.p, J, a, d_off.p, reads->qual_ptr(), qmin, d_w0.p, d_w1.p);
     });
     clk.stop(3);
     clk.start();

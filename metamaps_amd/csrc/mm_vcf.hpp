@@ -7,6 +7,6 @@ namespace mm {
 // the kept alleles in key order; window: mmv::WINDOW reference bytes per allele from its position on, zero beyond the contig's end
 struct VcfResult : KeptRows { std::vector<uint64_t> w1; std::vector<uint8_t> window; };
 // use: as mm_pileup.hpp's
-void vcf_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, const AlignedJobsIn& jobs, const uint8_t* use, KeyTable* out);
+void vcf_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, const AlignedJobsIn& jobs, const uint8_t* use, int32_t min_base_quality, KeyTable* out);
 void vcf_finish_run(mm_ctx* ctx, const mm_seqset* reference, const FinishIn& in, VcfResult* out);
 }

@@ -8,6 +8,11 @@ Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes pr
        python tools/edit_kernel_stats.py --pileup [n_reads]           (writes profiles/pileup_stats.txt)
        python tools/edit_kernel_stats.py --vcf [n_reads]              (writes profiles/vcf_stats.txt)
        python tools/edit_kernel_stats.py --consensus [n_reads]        (writes profiles/consensus_stats.txt)
+       python tools/edit_kernel_stats.py --qualities [n_reads] [--min-base-quality Q]   (writes profiles/qual_stats.txt)
+--qualities: the batch fetched to the host and uploaded again as a parser would hand it over, without and with seeded qualities (uniform in 2 .. 40 per base,
+independent of the bases): the upload's wall time both ways, then in the same process mm_bam_encode on the set without and with the plane, and
+mm_pileup_events_q and mm_vcf_events_q at floor 0 and at Q (default 20) with the rows of both tables at each floor.  Synthetic qualities do not correlate with
+the synthetic errors, so the shrinkage of the tables says nothing about real reads.  One run is one run.
 --consensus: the run of --vcf, and behind its mm_vcf_finish in the same process mm_consensus (mm_cons_core.hpp, mm_cons.hip) over the same table and intervals
 at the default thresholds, one call per group of at most 2^28 reference bases: the MM_CONS_TIMING lines, the wall time, the groups, the contigs written and the
 bytes of text, beside that run's mm_vcf_finish.  One run is one run.
@@ -249,7 +254,86 @@ def child_pileup(n_reads, vcf=False, cons=False):
     M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
 
 
+def child_qual(n_reads, floor):
+    from metamaps_amd import capi
+    ctx = capi.Context(0)
+    ref = ctx.synth_reference(seed=20260928, n_species=25, strains_per_species=4, genome_len=2_200_000, strain_divergence=0.02, genus_divergence=0.2)
+    w = capi.lib().mm_recommended_window(1e-3, K, PI, 1000, ref.total_bases)
+    idx = ctx.index(ref, K, w)
+    synth, _ = ctx.synth_reads(ref, seed=1000, n_reads=n_reads, read_len=READ_LEN, read_len_min=0, sub_rate=0.04, ins_rate=0.03, del_rate=0.05, frac_random=0.05, n_abundant=100)
+    buf, ln = synth.fetch_range(0, synth.count)                     # the batch as a parser would hand it over: ASCII on the host, and seeded qualities beside it
+    synth.close()
+    at = np.concatenate([[0], np.cumsum(ln, dtype=np.int64)])
+    text = buf.tobytes()
+    seqs = [text[at[i]:at[i + 1]] for i in range(len(ln))]
+    qual = np.random.default_rng(7).integers(2, 41, size=len(text), dtype=np.uint8).tobytes()
+    quals = [qual[at[i]:at[i + 1]] for i in range(len(ln))]
+    print(f"qualities: uniform in 2 .. 40 per base, seeded, independent of the bases and of the synthetic errors; floor {floor}", flush=True)
+    sets = {}
+    for rep in range(2):
+        for name, q in (("without", None), ("with", quals)):
+            if name in sets:
+                sets[name].close()
+            t0 = time.perf_counter()
+            sets[name] = ctx.seqset(seqs, quals=q, qual_offset=0)
+            dt = time.perf_counter() - t0
+            print(f"upload {name} the quality plane, call {rep}: {1e3 * dt:.1f} ms wall (the Python wrapper's adds included), {len(text) / 4e6:.1f} MB of packed bases"
+                  + (f" + {len(text) / 1e6:.1f} MB of qualities host to device" if q else ""), flush=True)
+    plain, reads = sets["without"], sets["with"]
+    M = ctx.map_batch(idx, reads, K, w, pi=PI)
+    M.keep_best(K)
+    off, rec = M.fetch()
+    n = len(rec)
+    print(f"{n_reads} reads of {READ_LEN} bases against {ref.total_bases} reference bases (k {K}, w {w}, pi {PI}): {n} best mappings", flush=True)
+    dist, first, last, op_off, ops = ctx.mapping_align(M, reads, ref, PI)
+    strand = rec["strand"].astype(np.int32)
+    jobs = dict(read=rec["read"], strand=strand, contig=rec["ref_contig"], dist=dist, first=first, op_off=op_off, ops=ops)
+    bam = dict(jobs, flag=np.where(strand < 0, 0x10, 0), mapq=np.full(n, 60), names=[b"read%d" % r for r in rec["read"]])
+    for rep in range(2):
+        for name, S in (("without", plain), ("with", reads)):
+            t0 = time.perf_counter()
+            data, n_rec, raw = ctx.bam_encode(S, ref, **bam)
+            dt = time.perf_counter() - t0
+            print(f"mm_bam_encode {name} qualities, call {rep}: {1e3 * dt:.1f} ms wall with the copies, {n_rec} records, {raw / 1e6:.1f} MB raw, {len(data) / 1e6:.1f} MB BGZF", flush=True)
+            del data
+    ev = dict(jobs, use=np.ones(n, dtype=np.uint8))
+    for rep in range(2):
+        for q in (0, floor):
+            t0 = time.perf_counter()
+            keys, counts = ctx.pileup_events(reads, ref, min_base_quality=q, **ev)
+            dt = time.perf_counter() - t0
+            print(f"mm_pileup_events_q floor {q}, call {rep}: {1e3 * dt:.1f} ms wall with the copies, {len(keys)} pairs of {int(counts.sum())} events", flush=True)
+            del keys, counts
+    for rep in range(2):
+        for q in (0, floor):
+            t0 = time.perf_counter()
+            w0, w1, counts = ctx.vcf_events(reads, ref, min_base_quality=q, **ev)
+            dt = time.perf_counter() - t0
+            print(f"mm_vcf_events_q floor {q}, call {rep}: {1e3 * dt:.1f} ms wall with the copies, {len(w0)} triples of {int(counts.sum())} alleles", flush=True)
+            del w0, w1, counts
+    M.close(); idx.close(); reads.close(); plain.close(); ref.close(); ctx.close()
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--child-qual":
+        return child_qual(int(sys.argv[2]), int(sys.argv[3]))
+    if len(sys.argv) > 1 and sys.argv[1] == "--qualities":
+        rest = sys.argv[2:]
+        floor = 20
+        if "--min-base-quality" in rest:
+            k = rest.index("--min-base-quality")
+            floor = int(rest[k + 1])
+            del rest[k:k + 2]
+        n_reads = int(rest[0]) if rest else 100_000
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-qual", str(n_reads), str(floor)],
+                           env=dict(os.environ, MM_BAM_TIMING="1", MM_PILEUP_TIMING="1", MM_VCF_TIMING="1"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1100)
+        text = f"tools/edit_kernel_stats.py --qualities {n_reads} --min-base-quality {floor}: one batch of {n_reads} reads, best mappings only; one run\n" + p.stdout.decode()
+        print(text)
+        if p.returncode != 0:
+            sys.exit(p.returncode)
+        with open(os.path.join(ROOT, "profiles", "qual_stats.txt"), "w") as f:
+            f.write(text)
+        return None
     if len(sys.argv) > 1 and sys.argv[1] == "--child-pileup":
         return child_pileup(int(sys.argv[2]))
     if len(sys.argv) > 1 and sys.argv[1] == "--child-vcf":
