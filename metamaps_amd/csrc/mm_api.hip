@@ -155,7 +155,7 @@ void mm_ctx_destroy(mm_ctx* ctx) {
   mm::comm_destroy(ctx);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   if (ctx->pinned_up) (void)hipHostFree(ctx->pinned_up);
-  ctx->l2_codes.release(); ctx->l2_masks.release();
+  ctx->l2_lists.release(); ctx->l2_masks.release();
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   if (ctx->aux_stream) { mm::stream_event_unregister(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }

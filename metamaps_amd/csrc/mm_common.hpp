@@ -144,8 +144,8 @@ struct mm_ctx {
   // per-(k, pi) cache of the host statistics thresholds (pure functions of the sketch size), mm_stats.hpp
   std::shared_ptr<void> lut_cache;
   int lut_k = 0; float lut_pi = 0;
-  // K5 scratch kept across batches: the per-entry code words of pass A (4 B per streamed entry slot, mm_l2.hpp), and the class masks of the long-read K5 classes
-  mm::GrowBuf l2_codes, l2_masks;
+  // K5 scratch kept across batches: the zone kernels' matched lists (mm_l2z.hpp), and the class masks of the zone kernels and of l2_kernel
+  mm::GrowBuf l2_lists, l2_masks;
   // pinned bounce buffer for result downloads into caller-owned (pageable) memory
   void* pinned = nullptr; size_t pinned_bytes = 0;
   // pinned staging buffer of sequence uploads (mm_seq.hip: the 2-bit words are packed straight into it), and the threads that pack

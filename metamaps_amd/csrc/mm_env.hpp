@@ -79,8 +79,8 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_L2_HOST_GROUPS", "unset", "test", "candidate groups formed on the host instead of by l2_group_kernel"},
     {"MM_L2_NO_GROUP_SORT", "unset", "test", "K5 workgroups in read order instead of the order of their candidates' positions"},
     {"MM_L2_GROUP_SORT_MIN", "2048", "tuning", "groups from which the launch order is sorted"},
-    {"MM_L2_V1", "unset", "test", "K5's 10 kb class through l2_kernel (rank codes per entry) instead of the zone kernel l2z_kernel (mm_l2z.hpp): the cross-check and the A/B"},
-    {"MM_L2_V1_LONG", "unset", "test", "the long-read classes (sketches of 3 073 .. 13 000 hashes) through l2_kernel, the 10 kb class through the zone kernel"},
+    {"MM_L2_V1", "unset", "test", "every candidate below 32 768 sketch hashes that is not on the dense path through l2_kernel's wide form (one wave per candidate) instead of the zone kernel l2z_kernel (mm_l2z.hpp), no device grouping: the cross-check"},
+    {"MM_L2_V1_LONG", "unset", "test", "only the long-read classes B and D (sketches of 3 073 .. 13 000 hashes) through l2_kernel's wide form, the 10 kb class through the zone kernel"},
     {"MM_L2_NO_FUSE", "unset", "test", "zone kernel without the band predicted from L1's seed-hit count: its masks always come from a second pass over the stream"},
     {"MM_L2_NO_RANGES", "unset", "test", "the zone kernel's waves search their candidates' index ranges themselves (until round 6) instead of taking them from l2_ranges_kernel (cross-check)"},
     {"MM_L2Z_FORCE_HANDBACK", "unset", "test", "the zone kernel hands every candidate that reaches its band loop to l2_kernel, as its pass-count guard does (the hand-back path against the default)"},

@@ -28,12 +28,15 @@
 // Exact evaluation, 64 windows per round.  The window sequence is the merge of two sorted time lists (leave / enter);
 // step indices come from cross-ranking two 64-entry chunks, window j is the state after j steps, and its shared count
 // follows from prefix sums over per-entry indicators plus a per-lane binary search of the pivot inside a 64-rank
-// "pivot zone" held in registers (block_slide below).  Pass A parks the rank code of every streamed entry in global
-// memory (4 B per entry) for the rebuilds, the rounds and the vote.
+// "pivot zone" held in registers (block_slide below).  Nothing is parked per entry: pass A keeps only the matched bit of every
+// streamed entry (one mask word per 64 entries), and the rebuilds, the rounds and the vote rank the entries they touch again
+// (bucket table + a few search steps in LDS).
 //
-// Launch shapes (mm_map.hip): reads are grouped by sketch size; the 10 kb class runs 4 candidates of a read per
-// workgroup sharing the sketch in LDS, 8-bit gap counters, 80 VGPRs (24 waves per CU); longer reads get masks for
-// 32 768 streamed entries and blocks of 2^j words.
+// Launch shapes (mm_map.hip): one wave per workgroup and candidate, the read's sketch, its bucket table and strand bits in LDS,
+// 16-bit counters, masks for 32 768 streamed entries in blocks of 2^j words.  SKIP=true is the "wide" form: sketches beyond the
+// zone kernels' classes (mm_l2z.hpp), their big list and pass-count hand-back, the redo of ambiguous strand votes, and every
+// class under MM_L2_V1 / MM_L2_V1_LONG (the zone kernels' cross-check).  The header also holds what the zone and dense kernels
+// (mm_l2z.hpp, mm_l2_dense.hpp) share with this one: the wave primitives, the range searches and the rank search.
 #pragma once
 #include "mm_index.hpp"
 #include "mm_map.hpp"
@@ -42,16 +45,14 @@
 
 namespace mm {
 
-// The skip path keeps one mask word per 64 streamed entries ("word"); NWQ = words / 64 is a template parameter
-// (2: up to 8 192 streamed entries, reads up to ~18 kb at w=8; 8: 32 768 entries).  Bounds are taken per block of BW words,
+// The skip path keeps one mask word per 64 streamed entries ("word"); NWQ = words / 64 (l2_kernel: L2_NWQ = 8, 32 768 entries; the zone
+// kernels' 10 kb class: 2, up to 8 192 streamed entries, reads up to ~18 kb at w=8).  Bounds are taken per block of BW words,
 // BW the smallest power of two with at most 128 blocks (two per lane).
 constexpr int L2_NBLK_MAX = 128;
+constexpr int L2_NWQ = 8;
 // bucket table over the top hash bits of the sketch: 1 024 buckets for the 10 kb class (sketches up to 3 072 hashes: at most four halving steps
 // inside a bucket; 2 048 buckets were measured in round 2 and cost in LDS what they saved), 4 096 for the long-read classes (sketches up to
 // 32 768: with 1 024 buckets their searches needed five steps and the generic loop, tools/l2_long_phases.py)
-#ifndef L2_WAVES_10K
-#define L2_WAVES_10K 6          // waves per SIMD the 10 kb class is compiled for: 6 = 80 registers, 15 of them spilled (round 5 measured 5 = 96 registers: tools/ab_build.sh)
-#endif
 #ifndef L2_TBITS_10K
 #define L2_TBITS_10K 10
 #endif
@@ -230,122 +231,99 @@ __device__ inline int l2_classify1(const uint32_t* __restrict__ Q, const uint16_
   return (lo < s && Q[lo] == h) ? lo : -(lo + 1);
 }
 
-// LDS layout: Q[smax] (shared by the waves of a workgroup) | per wave: D[smax] | mt | skip-ahead class arrays | slide scratch
+// LDS layout: Q[smax] | search table | strand bits | the wave's state: histogram | slide scratch (wide form), D[smax] | mt (full slide)
 constexpr int L2_SCRATCH_BYTES = 64 * 4 + 64 + 64;             // step times, step-has-deletion, step-has-addition
 __host__ __device__ inline size_t l2_skip_bytes(int nwq) { return (((size_t)(64 * nwq + 1) * (3 * 8 + 3 * 2)) + 15) & ~(size_t)15; }
 constexpr int L2_HBUCKETS = 1024;                              // coarse gap histogram of a rebuild (16-bit counters)
 constexpr int L2_SKETCH_LIMIT = 32 * L2_HBUCKETS;              // sketch sizes below this keep a histogram bucket narrower than the 64-rank zone
-template <typename DT>
-__host__ __device__ inline size_t l2_wave_bytes(int smax, bool skip, int nwq) {
-  if (skip && nwq > 2) return ((size_t)L2_HBUCKETS * 2 + L2_SCRATCH_BYTES + 15) & ~(size_t)15;   // long-read classes: histogram | slide scratch
-  if (skip) {                                                    // 10 kb class: D[smax] | mt | slide scratch
-    size_t b = (((size_t)smax * sizeof(DT) + 3) & ~(size_t)3) + (size_t)((smax + 31) / 32) * 4;
-    return (((b + 15) & ~(size_t)15) + L2_SCRATCH_BYTES + 15) & ~(size_t)15;
-  }
-  size_t b = (((size_t)smax * sizeof(DT) + 3) & ~(size_t)3) + (size_t)((smax + 31) / 32) * 4;   // full slide: D[smax] | mt
+__host__ __device__ inline size_t l2_wave_bytes(int smax, bool skip) {
+  if (skip) return ((size_t)L2_HBUCKETS * 2 + L2_SCRATCH_BYTES + 15) & ~(size_t)15;
+  size_t b = (((size_t)smax * sizeof(uint16_t) + 3) & ~(size_t)3) + (size_t)((smax + 31) / 32) * 4;
   return (b + 15) & ~(size_t)15;
 }
 __host__ __device__ inline size_t l2_qpart_bytes(int smax) { return ((size_t)(smax + L2_QPAD) * 4 + 15) & ~(size_t)15; }
 __host__ __device__ inline size_t l2_tpart_bytes(int nwq) { return ((size_t)l2_tsize(nwq) * 2 + 4 + 15) & ~(size_t)15; }
 // sketch | search table | strand bits of the sketch (two 64-bit words per 64 ranks: strand, unresolved duplicate)
 __host__ __device__ inline size_t l2_q_bytes(int smax, int nwq) { return l2_qpart_bytes(smax) + l2_tpart_bytes(nwq) + (size_t)((smax + 63) / 64) * 16; }
-template <typename DT>
-inline size_t l2_lds_bytes(int smax, bool skip, int waves, int nwq) { return l2_q_bytes(smax, nwq) + (size_t)waves * l2_wave_bytes<DT>(smax, skip, nwq); }
+inline size_t l2_lds_bytes(int smax, bool skip) { return l2_q_bytes(smax, L2_NWQ) + l2_wave_bytes(smax, skip); }
 
-// visibility of a wave's own LDS writes to its other lanes (workgroups may hold several independent waves)
+// visibility of a wave's own LDS writes to its other lanes (the zone kernels' workgroups hold several independent waves)
 __device__ inline void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
 }
 
-// SKIP: exact skip-ahead on/off.  DT: counter width of D (uint8_t compact / uint16_t wide).  WAVES: candidates per
-// workgroup; with WAVES > 1 the waves of a workgroup map candidates of ONE read and share its sketch Q in LDS.
-template <bool SKIP, typename DT, int WAVES, int NWQ>
-__global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(NWQ == 2 ? L2_WAVES_10K : 2))) l2_kernel(IndexView I, const int32_t* __restrict__ cand, const int32_t* __restrict__ cand_read,
+// SKIP: exact skip-ahead on (the wide form) / off (the literal full slide).  One wave per workgroup, one candidate per wave.
+template <bool SKIP>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) l2_kernel(IndexView I, const int32_t* __restrict__ cand, const int32_t* __restrict__ cand_read,
                                                 const uint32_t* __restrict__ sk_hash, const uint8_t* __restrict__ sk_strand,
                                                 const uint64_t* __restrict__ mz_off, const int32_t* __restrict__ sk_n,
                                                 const int32_t* __restrict__ read_len, const int32_t* __restrict__ accept_min,
                                                 int k, int w, int smax, L2Result* __restrict__ out,
                                                 unsigned long long* __restrict__ counters /* [0] streamed entries, [1] evaluated windows, [2] rebuilds */,
-                                                const int32_t* __restrict__ grp_cand0 /* WAVES>1: first candidate of the group */,
-                                                const int32_t* __restrict__ grp_n /* WAVES>1: candidates in the group */,
-                                                const int32_t* __restrict__ cand_list /* WAVES==1: optional indirection (fallback runs) */,
+                                                const int32_t* __restrict__ cand_list /* optional indirection: candidate of workgroup i (null: i itself) */,
                                                 int32_t* __restrict__ ovf_list, unsigned int* __restrict__ ovf_n,
                                                 uint8_t* __restrict__ amb_used /* optional: set per read when a vote read an unresolved strand */,
-                                                void* __restrict__ code_buf /* optional: 64*64*NWQ code words (2 bytes each for NWQ == 2, else 4) per scratch slot */,
-                                                uint8_t* __restrict__ mask_buf /* NWQ > 2: l2_skip_bytes(NWQ) per scratch slot */,
+                                                uint8_t* __restrict__ mask_buf /* SKIP: l2_skip_bytes(L2_NWQ) per scratch slot */,
                                                 unsigned int* __restrict__ slot_flags /* n_slots (a multiple of 8) words, all 0 between launches: a wave takes a free slot of its XCD's share for its lifetime (null: slot = wave number in the launch) */,
                                                 int n_slots) {
+  using DT = uint16_t;                                           // counter width of D
+  constexpr int NWQ = L2_NWQ;
   extern __shared__ __align__(16) uint32_t lds[];
   uint32_t* Q = lds;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  uint8_t* wbase = (uint8_t*)lds + l2_q_bytes(smax, NWQ) + (size_t)wave * l2_wave_bytes<DT>(smax, SKIP, NWQ);
-  DT* D = (DT*)wbase;                                            // (full slide only; the skip kernels keep a histogram here)
+  const int lane = threadIdx.x;
+  uint8_t* wbase = (uint8_t*)lds + l2_q_bytes(smax, NWQ);
+  DT* D = (DT*)wbase;                                            // (full slide only; the wide form keeps a histogram here)
   uint32_t* mt = (uint32_t*)(wbase + (((size_t)smax * sizeof(DT) + 3) & ~(size_t)3));
-  const int64_t c0 = WAVES > 1 ? (int64_t)grp_cand0[blockIdx.x] : (cand_list ? (int64_t)cand_list[blockIdx.x] : (int64_t)blockIdx.x);
-  const int r = cand_read[c0];                                   // every wave of the workgroup serves this read
+  const int64_t c = cand_list ? (int64_t)cand_list[blockIdx.x] : (int64_t)blockIdx.x;
+  const int r = cand_read[c];
   const int s = sk_n[r];
   const uint64_t qo = mz_off[r];
   const int len = read_len[r];
   uint16_t* T = (uint16_t*)((uint8_t*)lds + l2_qpart_bytes(smax));
   constexpr int TBITS = l2_tbits(NWQ), tshift = 32 - TBITS;
-  int* tmaxp = (int*)(T + ((l2_tsize(NWQ) + 1) & ~1));
   const int dbg_early = (int)counters[11] & 0xff;
-  auto early_out = [&]() { if (!(WAVES > 1 && wave >= grp_n[blockIdx.x]) && lane == 0) { L2Result z{}; out[c0 + (WAVES > 1 ? wave : 0)] = z; } };
+  auto early_out = [&]() { if (lane == 0) { L2Result z{}; out[c] = z; } };
   if (dbg_early == 6) { early_out(); return; }
-  for (int i = threadIdx.x; i < s; i += 64 * WAVES) Q[i] = sk_hash[qo + i];
+  for (int i = lane; i < s; i += 64) Q[i] = sk_hash[qo + i];
   if (dbg_early == 7) { __syncthreads(); early_out(); return; }
   // strand byte of every sketch entry (bit 0 strand, bit 1 unresolved duplicate: mm_map.hip, K2) as two bit sets: the vote
   // looks them up per matched entry, and a global load there is a second dependent memory latency in every step
   uint64_t* const SB = (uint64_t*)((uint8_t*)lds + l2_qpart_bytes(smax) + l2_tpart_bytes(NWQ));
-  for (int i0 = 64 * wave; i0 < s; i0 += 64 * WAVES) {
+  for (int i0 = 0; i0 < s; i0 += 64) {
     const uint8_t sbyte = i0 + lane < s ? sk_strand[qo + i0 + lane] : (uint8_t)0;
     const uint64_t b0 = __ballot(sbyte & 1), b1 = __ballot(sbyte & 2);
     if (lane == 0) { SB[2 * (i0 >> 6)] = b0; SB[2 * (i0 >> 6) + 1] = b1; }
   }
-  if (threadIdx.x < L2_QPAD) Q[s + threadIdx.x] = 0xffffffffu;
-  if (threadIdx.x == 0) *tmaxp = 0;
+  if (lane < L2_QPAD) Q[s + lane] = 0xffffffffu;
   __syncthreads();
   // T[b] = first rank whose bucket (l2_bucket) is >= b: element i is the answer for the buckets after Q[i-1]'s up to its own
   // (i == s closes the table), so every T entry is written exactly once, without searching
-  for (int i = threadIdx.x; i <= s; i += 64 * WAVES) {
+  for (int i = lane; i <= s; i += 64) {
     const int lo = i ? l2_bucket(Q[i - 1], tshift) + 1 : 0;
     const int hi = i < s ? l2_bucket(Q[i], tshift) : (1 << TBITS);
     for (int bb = lo; bb <= hi; ++bb) T[bb] = (uint16_t)i;
   }
   __syncthreads();
-  {                                                              // longest bucket: wave maximum first, one LDS atomic per wave
-    int tm = 0;
-    for (int bkt = threadIdx.x; bkt < (1 << TBITS); bkt += 64 * WAVES) tm = max(tm, (int)T[bkt + 1] - (int)T[bkt]);
-    tm = wave_max(tm);
-    if ((threadIdx.x & 63) == 0) atomicMax(tmaxp, tm);
-  }
-  __syncthreads();
-  const int tsteps = *tmaxp ? 32 - __clz(*tmaxp) : 0;
+  int tmax = 0;                                                  // longest bucket
+  for (int bkt = lane; bkt < (1 << TBITS); bkt += 64) tmax = max(tmax, (int)T[bkt + 1] - (int)T[bkt]);
+  tmax = wave_max(tmax);
+  const int tsteps = tmax ? 32 - __clz(tmax) : 0;
   const int dbg_flags = (int)counters[11];                       // timing aids: low byte MM_L2_STOP, bit 8 MM_L2_PHASES; 0 in normal operation
   const int dbg_stop = dbg_flags & 0xff;
-  if (WAVES > 1 && wave >= grp_n[blockIdx.x]) return;
-  const int64_t c = c0 + (WAVES > 1 ? wave : 0);
   if (dbg_stop) { if (lane == 0) { L2Result z{}; out[c] = z; } if (dbg_stop == 1) return; }
-  constexpr int DPER = 4 / (int)sizeof(DT);                      // counters per 32-bit word
-  // Pass A classifies every streamed entry once; its result (rank / gap code in the low 16 bits, strand and duplicate
-  // flags above) is parked in global memory, 4 bytes per entry, and read back by the rebuilds, the slide rounds and the
-  // vote instead of searching the sketch again.
-  // 10 kb class (NWQ == 2, sketch <= 3072): 13-bit code + 3 flag bits in 16 bits; other classes: 16-bit code + flags in 32 bits
-  using CW = std::conditional_t<NWQ == 2, uint16_t, uint32_t>;
-  // The code words and class masks of a candidate live in a scratch slot for as long as its wave does.  A launch has hundreds of
+  // The class masks of a candidate live in a scratch slot for as long as its wave does.  A launch can have hundreds of
   // thousands of waves and a few thousand of them are resident at a time: the slots are taken and given back (one flag word each),
-  // so the scratch of a launch is what its resident waves need — a few hundred MB that stay in the last-level cache between the pass
-  // that writes the words and the passes that read them — instead of 16-128 KB for every wave of the launch (7-20 GB per read batch).
+  // so the scratch of a launch is what its resident waves need and stays in the last-level cache between the pass
+  // that writes the words and the passes that read them.
   // The L2s of the XCDs are not coherent with each other (a line one holder left dirty in its XCD's L2 could be written back over
   // the next holder's data), so the slots are split by XCD — a wave takes one from the share of the XCD it runs on
   // (HW_REG_XCC_ID) and all traffic of a slot goes through ONE L2 for the whole launch.  Within an XCD the hand-over needs: the
   // holder's stores landed in L2 before the flag falls (s_waitcnt vmcnt(0): the L1 is write-through), and nothing from the new
   // holder — it writes every word before it reads it, and a CU's L1 follows its own stores.
-  CW* cw = nullptr;
   int slot = -1;
   auto acquire_slot = [&]() {
-    unsigned int sidx = WAVES > 1 ? blockIdx.x * WAVES + wave : blockIdx.x;
+    unsigned int sidx = blockIdx.x;
     if (slot_flags) {
       const unsigned int per = (unsigned int)n_slots >> 3;        // slots of one XCD (n_slots is a multiple of 8)
       const unsigned int lo = ((unsigned int)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u) * per;   // hwreg(HW_REG_XCC_ID, 0, 4)
@@ -354,7 +332,6 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
       sidx = lo + (unsigned int)__builtin_amdgcn_readfirstlane((int)t);
     }
     slot = (int)sidx;
-    if (code_buf) cw = (CW*)code_buf + (size_t)sidx * (size_t)(64 * 64 * NWQ);
   };
   auto release_slot = [&]() {                                    // (every read of the slot has returned: the wave used the values)
     if (slot_flags && slot >= 0) {
@@ -363,17 +340,6 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
     }
     slot = -1;
   };
-
-  bool have_codes = false;                                       // set once pass A has run
-  auto cw_make = [](int code, uint32_t flags) -> CW {
-    if constexpr (NWQ == 2) return (CW)(((uint32_t)code & 0x1fffu) | (flags << 13));
-    else return (CW)((uint32_t)(uint16_t)(int16_t)code | (flags << 16));
-  };
-  auto cw_code = [](CW ew) -> int {
-    if constexpr (NWQ == 2) return ((int)((uint32_t)ew << 19)) >> 19;
-    else return (int)(int16_t)(uint16_t)((uint32_t)ew & 0xffffu);
-  };
-  auto cw_flags = [](CW ew) -> uint32_t { if constexpr (NWQ == 2) return (uint32_t)ew >> 13; else return (uint32_t)ew >> 16; };
 
   const int contig = cand[3 * c], rs = cand[3 * c + 1], re = cand[3 * c + 2];
   const int cnt = len - (w - 1) - (k - 1);                       // computeMap.hpp:470
@@ -441,106 +407,17 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
   // zone edge the state is rebuilt from the window's entries, re-centred on the new pivot.
   int z0 = 0, cbase = 0, sb = 0, fz = 0;
   uint64_t pm = 0;
-  // 10 kb class (NWQ == 2): one gap counter per rank in LDS (D, packed 8-bit) and the matched bitmap, filled with LDS atomics
-  int overflow = 0;
-  constexpr int DBITS = 8 * (int)sizeof(DT);
-  auto rebuild_dense = [&](int nb, int ne) __attribute__((always_inline)) {
-    ++rebuilds;
-    uint32_t* Dw = (uint32_t*)D;
-    for (int i = lane; i < (s + DPER - 1) / DPER; i += 64) Dw[i] = 0;
-    for (int i = lane; i < (s + 31) / 32; i += 64) mt[i] = 0;
-    wave_sync();
-    // packed counter += 1, fire and forget.  A saturated counter carries into its neighbour, which lowers the sum of
-    // all counters by DMAX per carry: comparing that sum with the number of increments detects it exactly.
-    int n_inc = 0;
-    auto d_inc = [&](int g) {
-      atomicAdd(&Dw[g / DPER], 1u << (DBITS * (g % DPER)));
-      ++n_inc;
-    };
-    for (int base = nb; base < ne; base += 512) {                // eight loads in flight per wait
-      int cd[8]; uint32_t fl[8];
-      if (have_codes) {
-        const CW* __restrict__ pc = cw + (base - first) + lane;
+  // rank codes (rank if matched, -(gap + 1) if not) and flag bits of the 512 entries from `base` on, eight loads in flight
+  auto fetch8 = [&](int base, int (&cd)[8], uint32_t (&fl)[8]) {
+    Rec x[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { const CW ew = pc[min(64 * i, 64 * 64 * NWQ - 1 - (base - first) - lane)]; cd[i] = cw_code(ew); fl[i] = cw_flags(ew); }
-      } else {
-        Rec x[8];
+    for (int i = 0; i < 8; ++i) { const int j = base + lane + 64 * i; x[i] = pos[min(j, nmax)]; }
+    uint32_t hh[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { const int j = base + lane + 64 * i; x[i] = pos[min(j, nmax)]; }
-        uint32_t hh[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { hh[i] = x[i].hash; fl[i] = x[i].pw & 7u; }
-        l2_classify8(Q, T, tshift, tsteps, s, hh, cd);
-      }
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int j = base + lane + 64 * i;
-        if (base + 64 * i >= ne) continue;
-        const int code = cd[i];
-        const int g = -code - 1;
-        const bool in = j < ne;
-        if (in && code >= 0) atomicOr(&mt[code >> 5], 1u << (code & 31));
-        const bool wonly = in && code < 0 && g < s;
-        const bool flagged = wonly && (fl[i] & PW_DP);            // an earlier occurrence exists in the contig: inside the window?
-        const int dres = flagged ? dup_before(I, first0 + j, (int64_t)j - nb) : 0;
-        if (wonly && dres == 0) d_inc(g);
-        uint64_t fm = __ballot(dres < 0);                        // (windows of 65535+ entries only: a wave-wide scan each)
-        while (fm) {
-          const int l = __ffsll((unsigned long long)fm) - 1;
-          fm &= fm - 1;
-          const uint32_t hj = pos[base + l + 64 * i].hash;
-          const bool dup = wave_has_hash(pos, nb, base + l + 64 * i, hj, lane);
-          if (!dup && lane == l) d_inc(g);
-        }
-      }
-    }
-    wave_sync();
-    // pivot: R = min r with r + C(r) >= s.  Lane l sums the counters of its share of D word-wise; the first lane whose
-    // last rank satisfies the condition holds the pivot, and its share is resolved rank by rank with one wave scan.
-    const int NW = (s + DPER - 1) / DPER, wch = (NW + 63) / 64, rch = wch * DPER;
-    const int r_lo = min(lane * rch, s), r_hi = min(r_lo + rch, s);
-    int local = 0;
-    for (int wi = 0; wi < wch; ++wi) {
-      const int wd = lane * wch + wi;
-      const uint32_t v = wd < NW ? Dw[wd] : 0u;
-      local += sizeof(DT) == 1 ? (int)__builtin_amdgcn_sad_u8(v, 0u, 0u) : (int)((v & 0xffffu) + (v >> 16));
-    }
-    const int basec = wave_excl_scan(local, lane);
-    const int total = __builtin_amdgcn_readlane(basec, 63) + __builtin_amdgcn_readlane(local, 63);
-    if (wave_sum(n_inc) != total) overflow = 1;
-    const uint64_t hm = __ballot(r_lo < s && r_hi - 1 + basec + local >= s);
-    int R = s, cb = total;
-    if (hm) {
-      const int P = __builtin_ctzll(hm), rP = P * rch;
-      int acc = __builtin_amdgcn_readlane(basec, P);
-      for (int t0 = 0; t0 < rch; t0 += 64) {
-        const int r = rP + t0 + lane;
-        const bool in = r < s && t0 + lane < rch;
-        const int d = in ? (int)D[r] : 0;
-        const int ex = wave_excl_scan(d, lane);
-        const uint64_t m = __ballot(in && r + acc + ex + d >= s);
-        if (m) { const int l = __builtin_ctzll(m); R = rP + t0 + l; cb = acc + __builtin_amdgcn_readlane(ex, l); break; }
-        acc += __builtin_amdgcn_readlane(ex, 63) + __builtin_amdgcn_readlane(d, 63);
-      }
-    }
-    z0 = max(0, min(R - 32, s - 63));
-    const int rz = z0 + lane;
-    const int dz = rz < s ? (int)D[rz] : 0;
-    const int exz = wave_excl_scan(dz, lane);
-    fz = rz < s ? rz + exz + dz : (1 << 29);
-    cbase = cb - __builtin_amdgcn_readlane(exz, R - z0);          // D[0..z0) = D[0..R) - D[z0..R)
-    int sbl = 0;
-    for (int wd = lane; wd * 32 < z0; wd += 64) {
-      uint32_t m = mt[wd];
-      const int rem = z0 - wd * 32;
-      if (rem < 32) m &= (1u << rem) - 1u;
-      sbl += __popc(m);
-    }
-    sb = wave_sum(sbl);
-    pm = __ballot(rz < s && ((mt[rz >> 5] >> (rz & 31)) & 1u));
+    for (int i = 0; i < 8; ++i) { hh[i] = x[i].hash; fl[i] = x[i].pw & 7u; }
+    l2_classify8(Q, T, tshift, tsteps, s, hh, cd);
   };
-  // State of window [nb, ne) from scratch, in two passes over its entries (their rank codes come from pass A's parked
-  // words, or from a search where pass A did not run):
+  // State of window [nb, ne) from scratch, in two passes over its entries (each ranked in the sketch again):
   //   1. a coarse histogram of the distinct window-only hashes by gap (L2_HBUCKETS 16-bit LDS counters, fire and
   //      forget); its prefix sums locate the bucket of the pivot R = min r with r + C(r) >= s;
   //   2. with the zone centred on that bucket: window-only hashes between the bucket-aligned zone start and z0 (-> cbase),
@@ -553,46 +430,11 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
     uint32_t* Hw = (uint32_t*)wbase;                             // two 16-bit counters per word
     for (int i = lane; i < L2_HBUCKETS / 2; i += 64) Hw[i] = 0;
     wave_sync();
-    auto fetch8 = [&](int base, int (&cd)[8], uint32_t (&fl)[8]) {
-      if (have_codes) {
-        const CW* __restrict__ pc = cw + (base - first) + lane;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const CW ew = pc[min(64 * i, 64 * 64 * NWQ - 1 - (base - first) - lane)]; cd[i] = cw_code(ew); fl[i] = cw_flags(ew); }
-      } else {
-        Rec x[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const int j = base + lane + 64 * i; x[i] = pos[min(j, nmax)]; }
-        uint32_t hh[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { hh[i] = x[i].hash; fl[i] = x[i].pw & 7u; }
-        l2_classify8(Q, T, tshift, tsteps, s, hh, cd);
-      }
-    };
     // an entry flagged DP counts only if no earlier occurrence of its hash lies inside the window
     auto first_in_window = [&](int j) -> bool { return !wave_has_hash(pos, nb, j, pos[j].hash, lane); };
-    // the parked code words of [nb, ne), 512 entries per step; the loads of the next step are issued before the current one is
-    // processed (the long-read classes keep only 8-12 waves per CU: nothing else would cover the latency of each step)
+    // rank codes and flag bits of the entries of [nb, ne), 512 entries per step
     auto stream_codes = [&](auto&& body) __attribute__((always_inline)) {
-      if (have_codes) {
-        auto load_raw = [&](int base, CW (&raw)[8]) {
-          const CW* __restrict__ pc = cw + (base - first) + lane;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) raw[i] = pc[min(64 * i, 64 * 64 * NWQ - 1 - (base - first) - lane)];
-        };
-        CW cur[8], nxt[8];
-        load_raw(nb, cur);
-        for (int base = nb; base < ne; base += 512) {
-          if (base + 512 < ne) load_raw(base + 512, nxt);
-          int cd[8]; uint32_t fl[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) { cd[i] = cw_code(cur[i]); fl[i] = cw_flags(cur[i]); }
-          body(base, cd, fl);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) cur[i] = nxt[i];
-        }
-      } else {
-        for (int base = nb; base < ne; base += 512) { int cd[8]; uint32_t fl[8]; fetch8(base, cd, fl); body(base, cd, fl); }
-      }
+      for (int base = nb; base < ne; base += 512) { int cd[8]; uint32_t fl[8]; fetch8(base, cd, fl); body(base, cd, fl); }
     };
     stream_codes([&](int base, int (&cd)[8], uint32_t (&fl)[8]) __attribute__((always_inline)) {   // pass 1
 #pragma unroll
@@ -668,10 +510,6 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
     });
   };
 
-  auto rebuild_state = [&](int nb, int ne) __attribute__((always_inline)) {
-    if constexpr (NWQ == 2) rebuild_dense(nb, ne); else rebuild_hist(nb, ne);
-  };
-
   // ---- the reference's loop body (computeMap.hpp:496-533): evaluate [b,e), then MIIteratorL2::next ------
   int best = 0, bestR = 0, beg_pos = 0, last_pos = 0;
   int opt_b = 0, opt_e = 0, last_b = 0;
@@ -687,7 +525,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
   // ds_bpermute) and shared_j = sb_j + popcount(pm_j below R_j).  Events inside the zone are rare and applied one by one.
   // Only times up to min(A_63, B_63) are certain (later entries of the other list could interleave), the rest of the
   // chunk is redone by the next round.
-  int* tst = (int*)(wbase + (NWQ > 2 ? (size_t)L2_HBUCKETS * 2 : (((((size_t)smax * sizeof(DT) + 3) & ~(size_t)3) + (size_t)((smax + 31) / 32) * 4 + 15) & ~(size_t)15)));
+  int* tst = (int*)(wbase + (size_t)L2_HBUCKETS * 2);            // slide scratch behind the histogram (l2_wave_bytes)
   uint8_t* fdel = (uint8_t*)(tst + 64);
   uint8_t* fadd = fdel + 64;
   auto rank_search = [&](int arr, int v) -> int {                // number of leading lanes whose (ascending) arr < v
@@ -705,15 +543,13 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
   auto block_slide = [&](int b_stop) __attribute__((always_inline)) {
     constexpr int INF = 0x7fffffff;
     while (e < last_end && b < b_stop) {
-      if (pending_rebuild) { if (dbg_flags & 0x100) lap(4); rebuild_state(b, e); pending_rebuild = false; if (dbg_flags & 0x100) lap(3); if (dbg_stop == 8) break; }   // the only instance of the rebuild code
+      if (pending_rebuild) { if (dbg_flags & 0x100) lap(4); rebuild_hist(b, e); pending_rebuild = false; if (dbg_flags & 0x100) lap(3); if (dbg_stop == 8) break; }   // the only instance of the rebuild code
       if (dbg_stop == 9 && rounds >= 1) break;
       ++rounds;
       const Rec xb = pos[min(b + lane, nmax)];
       const Rec xe = pos[min(e + lane, nmax)];
       const int w64 = pw_wpos(pos[min(b + 64, nmax)].pw);
-      int cB, cE;
-      if (have_codes) { cB = cw_code(cw[min(b - first + lane, 64 * 64 * NWQ - 1)]); cE = cw_code(cw[min(e - first + lane, 64 * 64 * NWQ - 1)]); }
-      else { cB = l2_classify1(Q, T, tshift, tsteps, s, xb.hash); cE = l2_classify1(Q, T, tshift, tsteps, s, xe.hash); }
+      const int cB = l2_classify1(Q, T, tshift, tsteps, s, xb.hash), cE = l2_classify1(Q, T, tshift, tsteps, s, xe.hash);
       const int wpb = pw_wpos(xb.pw);
       int nextw = __shfl_down(wpb, 1, 64);
       if (lane == 63) nextw = w64;
@@ -885,8 +721,8 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
     constexpr int NWORDS_MAX = 64 * NWQ;
     int phase = (M <= 64 * NWORDS_MAX && M > 192) ? 0 : 2;
     bool finished = false;
-    // class masks and their prefix counts: LDS for the 10 kb class; for the long-read classes (NWQ > 2) they are written once
-    // and read a few times per block, so they live in global memory and the LDS they would take buys resident waves instead
+    // class masks and their prefix counts: written once and read a few times per block, so they live in global memory (the wave's
+    // scratch slot) and the LDS they would take buys resident waves instead
     acquire_slot();
     uint64_t* mAll = (uint64_t*)(mask_buf + (size_t)slot * l2_skip_bytes(NWQ));
     uint64_t* mLo = mAll + (NWORDS_MAX + 1);
@@ -906,7 +742,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
     // The kernel is bound by instruction issue (one wave instruction per cycle and CU), not by HBM, so the streaming
     // passes keep per-word work minimal: eight 512-byte loads off one address, masks handled as scalar bit sets
     // (ballots combined with s_and/s_andn2), per-word results parked in lane (word & 63) of register (word >> 6) and
-    // written to LDS once at the end, prefix counts by wave scans afterwards.
+    // written to the slot once at the end, prefix counts by wave scans afterwards.
     auto load8 = [&](Rec (&x)[8], int base) {
       if (base + 512 <= last_end) {
         const Rec* __restrict__ pp = pos + base + lane;
@@ -936,12 +772,12 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
     // "group entirely below last_end" as compile-time constants
     auto dispatch = [&](int q, bool full, auto&& body) {
 #define MM_L2_CASE(QV)                                                                                                  \
-      if constexpr (NWQ > QV) if (q == QV) { if (full) body(std::integral_constant<int, QV>{}, std::true_type{});        \
-                                             else body(std::integral_constant<int, QV>{}, std::false_type{}); return; }
+      if (q == QV) { if (full) body(std::integral_constant<int, QV>{}, std::true_type{});                                \
+                     else body(std::integral_constant<int, QV>{}, std::false_type{}); return; }
       MM_L2_CASE(0) MM_L2_CASE(1) MM_L2_CASE(2) MM_L2_CASE(3) MM_L2_CASE(4) MM_L2_CASE(5) MM_L2_CASE(6) MM_L2_CASE(7)
 #undef MM_L2_CASE
     };
-    static_assert(NWQ <= 8, "dispatch covers eight register sets");
+    static_assert(NWQ == 8, "dispatch covers eight register sets");
     // pass A: which entries carry a query hash; lane l keeps the masks of words l, l+64, ... and the position of their
     // first entry.  e_min of every block start (first entry with wpos >= wpos[block start] + cnt) afterwards, all blocks at
     // once: the word by ranking the target among the word starts, the entry by a binary search inside that word.
@@ -963,11 +799,6 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
           for (int i = 0; i < 8; ++i) hh[i] = x[i].hash;
           l2_classify8(Q, T, tshift, tsteps, s, hh, cd);
-        }
-        if (cw) {
-          CW* __restrict__ pc = cw + (base - first) + lane;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) if (base + 64 * i < last_end) pc[64 * i] = cw_make(cd[i], x[i].pw & 7u);
         }
         const int wd0 = (int)((base - first) >> 6);
         dispatch(wd0 >> 6, base + 512 <= last_end, [&](auto qtag, auto fulltag) {
@@ -1021,8 +852,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
       for (int q = 0; q < NWQ; ++q) { rLo[q] = 0; rA[q] = 0; }
       for (int wd0 = 0; wd0 < nwords; wd0 += 8) {
-        // (reads the entries, not the parked code words: half the bytes, but this pass is also what pulls the stream into
-        // L2/MALL for the sweep, whose scattered entry reads otherwise cost 1.3 ms more than the 0.3 ms saved here)
+        // (this pass is also what pulls the stream into L2/MALL for the sweep's scattered entry reads)
         Rec x[8];
         load8(x, first + wd0 * 64);
         dispatch(wd0 >> 6, first + wd0 * 64 + 512 <= last_end, [&](auto qtag, auto fulltag) {
@@ -1054,7 +884,6 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
     if (phase == 0) {
       lap(0);
       pass_matched();
-      have_codes = cw != nullptr;
       lap(1);
       if (dbg_stop == 2) { release_slot(); return; }
       // per block of `bspan` b's: largest window [bF, eHi), smallest window [bL, eLo)   (lane l owns blocks l and l+64)
@@ -1148,7 +977,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
       }
     }
   } else {                                                       // full slide, exactly the reference's order
-    for (int i = lane; i < (s + DPER - 1) / DPER; i += 64) ((uint32_t*)D)[i] = 0;
+    for (int i = lane; i < (s + 1) / 2; i += 64) ((uint32_t*)D)[i] = 0;   // (two counters per word)
     for (int i = lane; i < (s + 31) / 32; i += 64) mt[i] = 0;
     wave_sync();
     l2_reset(S);
@@ -1171,19 +1000,7 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
     int votes = 0, amb_votes = 0;                                 // votes of resolved strands / number of votes whose query strand is unresolved
     for (int base = opt_b; base < opt_e; base += 512) {
       int cd[8]; uint32_t fl[8];
-      if (have_codes) {
-        const CW* __restrict__ pc = cw + (base - first) + lane;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const CW ew = pc[min(64 * i, 64 * 64 * NWQ - 1 - (base - first) - lane)]; cd[i] = cw_code(ew); fl[i] = cw_flags(ew); }
-      } else {
-        Rec x[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const int j = base + lane + 64 * i; x[i] = pos[min(j, nmax)]; }
-        uint32_t hh[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { hh[i] = x[i].hash; fl[i] = x[i].pw & 7u; }
-        l2_classify8(Q, T, tshift, tsteps, s, hh, cd);
-      }
+      fetch8(base, cd, fl);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int j = base + lane + 64 * i;
@@ -1214,10 +1031,6 @@ __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu
     strand = votes > 0 ? 1 : -1;
   }
   release_slot();
-  if (NWQ == 2 && __ballot(overflow) != 0ull) {                   // a packed 8-bit counter saturated: hand the candidate to the full slide
-    if (lane == 0) ovf_list[atomicAdd(ovf_n, 1u)] = (int32_t)c;
-    accepted = 0; best = 0;
-  }
   if (lane == 0) {
     L2Result o;
     o.contig = contig; o.mean_pos = (beg_pos + last_pos) / 2;    // :537

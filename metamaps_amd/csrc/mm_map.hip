@@ -138,18 +138,19 @@ struct MapSwitches {
   const int dense_from = num(getenv("MM_L2_DENSE_FROM"), 13000);
   const bool dense_no_stop = on(getenv("MM_L2_DENSE_NO_STOP"));
   const bool no_small_groups = on(getenv("MM_L2_NO_SMALL_GROUPS"));   // cross-check / timing switch
+  // the zone kernels (mm_l2z.hpp) run the classes of sketches up to 16 384 hashes.  MM_L2_V1=1: every candidate below L2_SKETCH_LIMIT that is not
+  // on the dense path goes through l2_kernel's wide form instead, one wave per candidate (the zone kernels' cross-check)
+  const bool v2 = !on(getenv("MM_L2_V1"));
+  const bool v2_long = v2 && !on(getenv("MM_L2_V1_LONG"));       // (MM_L2_V1_LONG=1: only the long-read classes B and D go that way)
   // the workgroups of the 10 kb class are put together on the device while the L1 kernel still runs (l2_group_kernel);
   // MM_L2_HOST_GROUPS=1: the host loop makes them as well (cross-check)
-  const bool dev_groups = l2_skip && !on(getenv("MM_L2_HOST_GROUPS"));
+  const bool dev_groups = l2_skip && v2 && !on(getenv("MM_L2_HOST_GROUPS"));
   // scratch slots of the skip kernels (mm_l2.hpp): a slot per RESIDENT wave (the hardware keeps at most 32 per CU), taken and given
   // back by the waves through one flag word each; MM_L2_NO_SLOTS=1: one slot per wave of the launch, no flags (cross-check switch)
   // (MM_L2_SLOTS=n, rounded up to a multiple of 8: fewer slots than resident waves — they wait for each other's; tests of the hand-over)
   const bool l2_no_slots = on(getenv("MM_L2_NO_SLOTS"));
   const OptInt l2_slots_env = opt(getenv("MM_L2_SLOTS"));
   const size_t l2_slots = l2_slots_env.set ? ((size_t)std::max(l2_slots_env.v, 1) + 7) / 8 * 8 : 0;
-  // the zone kernels (mm_l2z.hpp, the default; MM_L2_V1=1: l2_kernel for every class): matched list + masks per slot
-  const bool v2 = !on(getenv("MM_L2_V1"));
-  const bool v2_long = v2 && !on(getenv("MM_L2_V1_LONG"));       // (MM_L2_V1_LONG=1: the long-read classes, sketches of 3 073 .. 13 000 hashes, through l2_kernel)
   const bool sort_groups = !on(getenv("MM_L2_NO_GROUP_SORT"));
   const OptInt group_sort_env = opt(getenv("MM_L2_GROUP_SORT_MIN"));   // (test hook: small batches take the sort too)
   const size_t group_sort_from = group_sort_env.set ? (size_t)std::max(group_sort_env.v, 1) : 2048;
@@ -228,7 +229,7 @@ struct MapRun {
   // K5, the skip classes only: released by l2_skip_classes where its block ended, in front of the compaction's allocations
   struct SkipClasses {
     DBuf<unsigned int> slot_flags;
-    DBuf<int32_t> big;                                           // candidates with more streamed entries than the zone kernel's masks hold: l2_kernel's widest class
+    DBuf<int32_t> big;                                           // candidates with more streamed entries than the zone kernel's masks hold: l2_kernel's wide form
     DBuf<unsigned int> big_n;
     std::vector<int32_t> gA0, gAn, gB0, gBn, gD0, gDn, listC, gS0, gSn;   // gS: groups of one or two candidates of the 10 kb class (two-wave workgroups)
     int smA = 0, smB = 0, smC = 0, smD = 0;
@@ -731,14 +732,14 @@ struct MapRun {
 
   // ---- K5/K6 launch helpers: the arguments every call site shares come from the run, the LDS size from the class
   // l2_kernel (mm_l2.hpp).  SKIP: hands reads shorter than w + k back through ovf and takes its scratch slot through slot_flags; the
-  // literal full slide (!SKIP) does neither.  One of (g0, gn) and `list` names the candidates.
-  template <bool SKIP, typename CNT, int NW, int NWQ>
-  void launch_l2(size_t grid, hipStream_t s, int sm, const int32_t* g0, const int32_t* gn, const int32_t* list, uint8_t* amb_ptr, void* codes, uint8_t* masks, int n_slots) {
-    const size_t lds = l2_lds_bytes<CNT>(sm, SKIP, NW, NWQ);
-    set_lds((const void*)l2_kernel<SKIP, CNT, NW, NWQ>, lds);
-    l2_kernel<SKIP, CNT, NW, NWQ><<<dim3((unsigned)grid), dim3(64 * NW), lds, s>>>(IV, M->cand.p, M->cand_read.p, M->sk_hash.p, M->sk_strand.p,
-        M->mz.off.p, M->sk_n.p, M->d_read_len.p, M->accept_min.p, P.k, P.w, sm, M->l2.p, counters.p, g0, gn, list, SKIP ? ovf.p : nullptr, SKIP ? ovf_n.p : nullptr, amb_ptr,
-        codes, masks, SKIP ? slot_flags_p() : nullptr, n_slots);
+  // literal full slide (!SKIP) does neither.  One wave per candidate of `list`.
+  template <bool SKIP>
+  void launch_l2(const int32_t* list, size_t nl, int sm, uint8_t* amb_ptr, uint8_t* masks, int n_slots) {
+    const size_t lds = l2_lds_bytes(sm, SKIP);
+    set_lds((const void*)l2_kernel<SKIP>, lds);
+    l2_kernel<SKIP><<<dim3((unsigned)nl), dim3(64), lds, st>>>(IV, M->cand.p, M->cand_read.p, M->sk_hash.p, M->sk_strand.p,
+        M->mz.off.p, M->sk_n.p, M->d_read_len.p, M->accept_min.p, P.k, P.w, sm, M->l2.p, counters.p, list, SKIP ? ovf.p : nullptr, SKIP ? ovf_n.p : nullptr, amb_ptr,
+        masks, SKIP ? slot_flags_p() : nullptr, n_slots);
     MM_KERNEL_CHECK();
   }
   // l2z_kernel (mm_l2z.hpp), groups of up to NW candidates of a read
@@ -751,27 +752,19 @@ struct MapRun {
         M->accept_min.p, P.k, P.w, sm, bbl, M->l2.p, counters.p, g0, gn, ovf.p, ovf_n.p, sk->big.p, sk->big_n.p, amb_used_p, (uint32_t*)lists, masks, slot_flags_p(), n_slots, cand_hint.p, cand_rng.p);
     MM_KERNEL_CHECK();
   }
-  // one wave per candidate of `list`, 16-bit counters, masks for 32 768 entries: class C, the zone kernels' big list, the redo of ambiguous votes
-  void launch_l2_wide(const int32_t* list, size_t nl, int sm, uint8_t* amb_ptr) {
-    launch_l2<true, uint16_t, 1, 8>(nl, st, sm, nullptr, nullptr, list, amb_ptr, nullptr, masks_for(nl), (int)slots_of(nl));
-  }
+  // the wide form: class C, the zone kernels' big list, the redo of ambiguous votes, every class under MM_L2_V1
+  void launch_l2_wide(const int32_t* list, size_t nl, int sm, uint8_t* amb_ptr) { launch_l2<true>(list, nl, sm, amb_ptr, masks_for(nl), (int)slots_of(nl)); }
   // the literal full slide over `list`
-  void launch_l2_full(const int32_t* list, size_t nl, uint8_t* amb_ptr) {
-    launch_l2<false, uint16_t, 1, 8>(nl, st, M->smax, nullptr, nullptr, list, amb_ptr, nullptr, nullptr, 0);
-  }
+  void launch_l2_full(const int32_t* list, size_t nl, uint8_t* amb_ptr) { launch_l2<false>(list, nl, M->smax, amb_ptr, nullptr, 0); }
 
   // scratch slots of the skip kernels: twice as many as waves can be resident (the 10 kb class keeps 24 per CU, the long-read classes 8-12), so that a
   // wave finds a free one at its first or second try
   unsigned int* slot_flags_p() const { return sw.l2_no_slots ? nullptr : sk->slot_flags.p; }
   size_t max_slots(int nwq) const { return sw.l2_no_slots ? (size_t)1 << 40 : sw.l2_slots ? sw.l2_slots : (size_t)ctx->cus * (nwq == 2 ? 64 : 32); }
   size_t slots_of(size_t n_waves, int nwq = 8) const { return std::min((std::max<size_t>(n_waves, 1) + 7) / 8 * 8, max_slots(nwq)); }   // (a multiple of 8: one share per XCD)
-  uint8_t* masks_for(size_t n_waves, int nwq = 8) { return (uint8_t*)ctx->l2_masks.at_least(ctx->alloc, slots_of(n_waves, nwq) * l2_skip_bytes(nwq)); }
-  // per-entry code words of pass A: one slot range per wave of a launch (the launches of a batch run one after the other
-  // on the stream, so they share the buffer); classes whose ranks do not fit 16 bits (C) search the sketch instead
-  void* codes_for(size_t n_waves, int nwq) {
-    return ctx->l2_codes.at_least(ctx->alloc, slots_of(n_waves, nwq) * (size_t)(64 * 64 * nwq) * (nwq == 2 ? sizeof(uint16_t) : sizeof(uint32_t)));
-  }
-  void* lists_for(size_t n_waves, int nwq) { return ctx->l2_codes.at_least(ctx->alloc, slots_of(n_waves, nwq) * l2z_list_bytes(nwq)); }
+  uint8_t* masks_for(size_t n_waves) { return (uint8_t*)ctx->l2_masks.at_least(ctx->alloc, slots_of(n_waves) * l2_skip_bytes(L2_NWQ)); }
+  // the zone kernels' matched lists and masks: one slot range per wave of a launch (the launches of a batch share the buffers)
+  void* lists_for(size_t n_waves, int nwq) { return ctx->l2_lists.at_least(ctx->alloc, slots_of(n_waves, nwq) * l2z_list_bytes(nwq)); }
   uint8_t* zmasks_for(size_t n_waves, int nwq) { return (uint8_t*)ctx->l2_masks.at_least(ctx->alloc, slots_of(n_waves, nwq) * l2z_mask_bytes(nwq)); }
 
   // ---- K5/K6
@@ -806,7 +799,7 @@ struct MapRun {
                                                                             sw.no_small_groups ? 1 : 0, d_gA0.p, d_gAn.p, d_gS0.p, d_gSn.p, grp_ctr.p);
       MM_KERNEL_CHECK();
     }
-    const size_t lds_wide = l2_lds_bytes<uint16_t>(M->smax, sw.l2_skip, 1, 8);
+    const size_t lds_wide = l2_lds_bytes(M->smax, sw.l2_skip);
     // Sketches of >= 32768 hashes (L2_SKETCH_LIMIT): the rebuild's 1024-bucket histogram would be as coarse as the 64-rank pivot
     // zone, and the window state of the full slide no longer fits LDS either -> always the dense path, state in global memory.
     for (int64_t r = 0; r < n && M->stats.n_reads_giant > 0; ++r) {
@@ -881,11 +874,12 @@ struct MapRun {
   }
 
   // Reads are grouped by sketch size so that one long read does not size the LDS state (and the occupancy) of all:
-  //   A  s <= 3072   (reads up to ~14 kb at w=8)  compact: 4 candidates of a read per workgroup share the sketch,
-  //                                                8-bit gap counters, masks for 8 192 streamed entries
-  //   B  s <= 7168   (~32 kb)                      the same with masks for 32 768 entries, kept in global memory
-  //   D  s <= 16384  (~74 kb)                      as B, launched separately so that B keeps its smaller sketch area
-  //   C  larger                                    one wave per workgroup, 16-bit counters, 32 768 entries
+  //   A  s <= 3072   (reads up to ~14 kb at w=8)  zone kernel: up to 4 candidates of a read per workgroup share the sketch,
+  //                                                masks for 8 192 streamed entries (groups of one or two: two-wave workgroups)
+  //   B  s <= 7168   (~32 kb)                      zone kernel with masks for 32 768 entries, the sketch left in global memory
+  //   D  s <= 16384  (~74 kb)                      as B, launched separately so that B keeps its smaller LDS area
+  //   C  larger                                    l2_kernel's wide form: one wave per workgroup and candidate, 32 768 entries
+  // (MM_L2_V1: A, B and D join C; MM_L2_V1_LONG: B and D do.)
   // Reads shorter than w+k are handed back by these kernels and go through the literal full slide.
   void l2_skip_classes() {
     sk = std::make_unique<SkipClasses>();
@@ -937,7 +931,8 @@ struct MapRun {
         for (uint64_t c0 = c_lo; c0 < c_hi; ++c0) s.listL.push_back((int32_t)c0);
         continue;
       }
-      if (sr <= 7168) {
+      const bool zone = sr <= 3072 ? sw.v2 : sr <= 16384 && sw.v2_long;   // (else class C)
+      if (zone && sr <= 7168) {
         auto& g0 = sr <= 3072 ? s.gA0 : s.gB0; auto& gn = sr <= 3072 ? s.gAn : s.gBn;
         (sr <= 3072 ? s.smA : s.smB) = std::max(sr <= 3072 ? s.smA : s.smB, sr);
         for (uint64_t c0 = c_lo; c0 < c_hi; c0 += 4) {
@@ -947,7 +942,7 @@ struct MapRun {
           if (sr <= 3072 && cnt <= 2 && !sw.no_small_groups) { s.gS0.push_back((int32_t)c0); s.gSn.push_back(cnt); }
           else { g0.push_back((int32_t)c0); gn.push_back(cnt); }
         }
-      } else if (sr <= 16384) {
+      } else if (zone) {
         s.smD = std::max(s.smD, sr);
         for (uint64_t c0 = c_lo; c0 < c_hi; c0 += 4) { s.gD0.push_back((int32_t)c0); s.gDn.push_back((int32_t)std::min<uint64_t>(4, c_hi - c0)); }
       } else if (sr < L2_SKETCH_LIMIT) {
@@ -982,8 +977,8 @@ struct MapRun {
     // caps it) so that small batches do not queue for each other's slots; one behind the other the larger launch sizes it
     const bool side_by_side = nA && nS && !sw.l2_no_slots && !sw.one_stream;   // (without slots the scratch is indexed by wave number of the launch: one launch at a time)
     const size_t n_waves = side_by_side ? nA * 4 + nS * 2 : std::max(nA * 4, nS * 2);
-    void* const codes = !(nA || nS) ? nullptr : sw.v2 ? lists_for(n_waves, 2) : codes_for(n_waves, 2);
-    uint8_t* const masks = !(nA || nS) ? nullptr : sw.v2 ? zmasks_for(n_waves, 2) : masks_for(n_waves, 2);
+    void* const lists = !(nA || nS) ? nullptr : lists_for(n_waves, 2);
+    uint8_t* const masks = !(nA || nS) ? nullptr : zmasks_for(n_waves, 2);
     const int n_slots = (int)slots_of(n_waves, 2);
     hipStream_t st_small = st;
     if (side_by_side) {
@@ -992,15 +987,10 @@ struct MapRun {
       MM_HIP(hipEventRecord(ctx->ev_fork, st));
       MM_HIP(hipStreamWaitEvent(st_small, ctx->ev_fork, 0));
     }
-    if (sw.v2) {
-      if (nA) launch_l2z<4, 2, true>(nA, st, smA, d_gA0.p, d_gAn.p, codes, masks, n_slots);
-      // groups of one or two candidates: a two-wave workgroup with the sketch in LDS holds 20 KB for two waves (16 waves per CU); with the sketch left
-      // in global memory it holds 10 KB and the CU its 24 waves
-      if (nS) launch_l2z<2, 2, false>(nS, st_small, smA, d_gS0.p, d_gSn.p, codes, masks, n_slots);
-    } else {
-      if (nA) launch_l2<true, uint8_t, 4, 2>(nA, st, smA, d_gA0.p, d_gAn.p, nullptr, amb_used_p, codes, masks, n_slots);
-      if (nS) launch_l2<true, uint8_t, 2, 2>(nS, st_small, smA, d_gS0.p, d_gSn.p, nullptr, amb_used_p, codes, masks, n_slots);
-    }
+    if (nA) launch_l2z<4, 2, true>(nA, st, smA, d_gA0.p, d_gAn.p, lists, masks, n_slots);
+    // groups of one or two candidates: a two-wave workgroup with the sketch in LDS holds 20 KB for two waves (16 waves per CU); with the sketch left
+    // in global memory it holds 10 KB and the CU its 24 waves
+    if (nS) launch_l2z<2, 2, false>(nS, st_small, smA, d_gS0.p, d_gSn.p, lists, masks, n_slots);
     if (side_by_side) {
       MM_HIP(hipEventRecord(ctx->ev_join, st_small));
       MM_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
@@ -1013,8 +1003,7 @@ struct MapRun {
     const size_t ng = g0.size();
     d_g0.upload(g0.data(), ng, st); d_gn.upload(gn.data(), gn.size(), st);
     sort_by_position(d_g0, d_gn, ng);
-    if (sw.v2_long) launch_l2z<4, 8, false>(ng, st, sm, d_g0.p, d_gn.p, lists_for(ng * 4, 8), zmasks_for(ng * 4, 8), (int)slots_of(ng * 4));
-    else launch_l2<true, uint8_t, 4, 8>(ng, st, sm, d_g0.p, d_gn.p, nullptr, amb_used_p, codes_for(ng * 4, 8), masks_for(ng * 4), (int)slots_of(ng * 4));
+    launch_l2z<4, 8, false>(ng, st, sm, d_g0.p, d_gn.p, lists_for(ng * 4, 8), zmasks_for(ng * 4, 8), (int)slots_of(ng * 4));
   }
 
   // candidates the skip kernels hand back (reads shorter than w+k): the literal full slide

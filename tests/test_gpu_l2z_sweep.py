@@ -1,4 +1,4 @@
-"""The zone kernel's sweep (mm_l2z.hpp) against l2_kernel (MM_L2_V1=1), and its hand-back of candidates to l2_kernel.
+"""The zone kernel's sweep (mm_l2z.hpp) against l2_kernel, one wave per candidate (MM_L2_V1=1), and its hand-back of candidates to l2_kernel.
 
 The block search between sweeps picks the next block whose bound passes by two ballots over the bounds (10 kb class); MM_L2Z_WALK_SEARCH makes it
 walk the blocks one at a time as the long-read classes do, and the two must visit the same blocks.  The pass-count guard of the band loop

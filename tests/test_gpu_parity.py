@@ -1128,8 +1128,8 @@ def test_l2_scratch_slots_hand_over(ctx, monkeypatch):
 
 def test_zone_kernel_equals_rank_code_kernel(ctx, monkeypatch):
     """K5 runs as the zone kernel (mm_l2z.hpp: membership through a bit table + compaction, window states from threshold masks of a band of
-    128 ranks, the band predicted from L1's seed-hit count) by default; l2_kernel (a rank code per streamed entry, MM_L2_V1=1) is the same
-    algorithm in its first form.  Reads of 1-60 kb on a repeat-rich reference (duplicate hashes inside windows, DP/DN flags): the default, the zone
+    128 ranks, the band predicted from L1's seed-hit count) by default; the base is l2_kernel, one wave per candidate (MM_L2_V1=1: every streamed
+    entry ranked in the sketch), an independent implementation of the same skip-ahead.  Reads of 1-60 kb on a repeat-rich reference (duplicate hashes inside windows, DP/DN flags): the default, the zone
     kernel without the predicted band (MM_L2_NO_FUSE: the band's masks from a second pass), the zone kernel for the 10 kb class only
     (MM_L2_V1_LONG), the zone kernel searching its index ranges itself (MM_L2_NO_RANGES; by default l2_ranges_kernel makes them for all candidates at once), all with a lowered saturation of the duplicate distances (MM_DUP_SAT: the scan fall-back), and l2_kernel must give
     identical records; the L2 tuples of every candidate are compared as well."""

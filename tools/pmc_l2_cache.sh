@@ -1,5 +1,5 @@
 #!/bin/bash
-# K5 (l2_kernel): where do its re-reads go?  L2 (TCC) requests, hits and misses, and the requests the L2 sends on to the fabric (EA), for one
+# K5 (the zone kernels of the 10 kb class): where do its re-reads go?  L2 (TCC) requests, hits and misses, and the requests the L2 sends on to the fabric (EA), for one
 # bench step.  FETCH_SIZE (profiles/r03_pmc_hbm_traffic.txt) counts what leaves the L2; whether such a request is then served by the
 # memory-side Infinity Cache or by HBM is not visible in the TCC counters.
 cd /tmp && export TMPDIR=/tmp
@@ -13,7 +13,7 @@ done
 python - $out <<'PY' | tee $out/summary.txt
 import csv, glob, sys, collections
 acc = collections.defaultdict(float)
-names = {"l2_kernel<true, unsigned char, 4, 2>": "K5 l2_kernel<true,u8,4,2>", "l2_kernel<true, unsigned char, 2, 2>": "K5 l2_kernel<true,u8,2,2>", "seed_filter_stream_kernel": "K3 seed_filter_stream_kernel", "minimizer_kernel<2>": "K1 minimizer_kernel<2>"}
+names = {"l2z_kernel<4, 2": "K5 l2z_kernel<4,2>", "l2z_kernel<2, 2": "K5 l2z_kernel<2,2>", "seed_filter_stream_kernel": "K3 seed_filter_stream_kernel", "minimizer_kernel<2>": "K1 minimizer_kernel<2>"}
 for f in glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True):
     for row in csv.DictReader(open(f)):
         for kn in names:

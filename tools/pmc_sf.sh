@@ -10,7 +10,7 @@ done
 python - $out <<'PY' | tee $out/summary.txt
 import csv, glob, sys, collections
 acc = collections.defaultdict(float)
-names = {"seed_filter_stream_kernel": "K3 seed_filter_stream_kernel", "l2_kernel<true, unsigned char, 4, 2>": "K5 l2_kernel<true,u8,4,2>", "minimizer_kernel<2>": "K1 minimizer_kernel<2>"}
+names = {"seed_filter_stream_kernel": "K3 seed_filter_stream_kernel", "l2z_kernel<4, 2": "K5 l2z_kernel<4,2>", "minimizer_kernel<2>": "K1 minimizer_kernel<2>"}
 for f in glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True):
     for row in csv.DictReader(open(f)):
         for kn in names:

@@ -10,7 +10,7 @@ done
 python - $out <<'PY'
 import csv, glob, sys, collections
 out = sys.argv[1]
-for tag, pat in (("ubench st<8> (18.68 GB requested per launch)", "st<8>"), ("l2_kernel 4-wave MM_L2_STOP=2", "l2_kernel<true, unsigned char, 4")):
+for tag, pat in (("ubench st<8> (18.68 GB requested per launch)", "st<8>"), ("l2z_kernel 4-wave (10 kb class) MM_L2_STOP=2", "l2z_kernel<4, 2")):
     acc = collections.defaultdict(list)
     for f in glob.glob(f"{out}/{'u' if 'ubench' in tag else 'k'}_*/**/*counter_collection.csv", recursive=True):
         for row in csv.DictReader(open(f)):

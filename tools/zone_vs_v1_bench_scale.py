@@ -1,4 +1,6 @@
 """The zone kernel against l2_kernel (MM_L2_V1=1) on bench batches at full size (10^5 x 10 kb reads vs the 26.8 Gbp community): records must be byte-identical.
+   The v1 leg is l2_kernel's wide form, one wave per workgroup and candidate: built for the few long candidates of a batch, it is slow at this size
+   (its K5 time is no A/B of the zone kernel any more, only its records count).
    python tools/zone_vs_v1_bench_scale.py [BATCH ...]   (defaults 0 10)"""
 import os, sys
 import numpy as np
