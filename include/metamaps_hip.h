@@ -32,7 +32,7 @@ extern "C" {
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
                             *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances,
-                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_*, mm_pileup_*, mm_vcf_*, mm_consensus* (additions to 6) */
+                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_*, mm_pileup_*, mm_vcf_*, mm_consensus*, mm_seqset_*_mods, mm_mod_* (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -109,6 +109,24 @@ int mm_seqset_add_nt16(mm_seqset* s, const uint8_t* nt16, int64_t n_bases, int r
 int mm_seqset_add_qual(mm_seqset* s, const uint8_t* qual, int64_t len, int offset);
 int mm_seqset_has_qual(const mm_seqset* s);
 int mm_seqset_fetch_qual(mm_seqset* s, int64_t i, uint8_t* out, int64_t cap);
+
+/* Base modifications (the MM/ML tags of a read; SAM tags specification, "Base modifications"), two bytes per base beside the packed bases (DESIGN.md
+ * section 1, "Base modifications"; the definition: csrc/mm_mods_core.hpp).  mm_seqset_add_mods attaches n_groups groups, in MM's order and one code
+ * each, to the sequence added last (by mm_seqset_add, _add_view or _add_nt16): base[g] is one of 'A' 'C' 'G' 'T', code[g] the index 0..3 of the
+ * group's code among the codes the caller asks for or -1 for any other code, mode[g] is '.', '?' or 0 for absent, and the group's skips and ML bytes
+ * are skips[off[g] .. off[g + 1]) and ml[off[g] .. off[g + 1]).  Positions are those of the read as the set holds it (an nt16 record added with
+ * reverse != 0 is turned back by the set, so MM needs no turning).  The arrays are copied.  MM_ERR_ARG: no sequence yet, a second call for one
+ * sequence, a set that is uploaded, n_groups outside [0, 255], a base outside ACGT, a code outside [-1, 3], a mode other than the three, offsets
+ * that start below 0 or fall, a null array.  mm_seqset_upload writes the plane with one wavefront per read: who (0 no call, 1 canonical, 2 another
+ * code, 3 + code) and prob per base.  A group that names more occurrences of its base than the sequence has is MM_ERR_DATA, mm_last_error names the
+ * lowest such sequence and its lowest such group.  A set without any mm_seqset_add_mods call allocates and launches nothing for modifications.
+ * mm_seqset_has_mods: 1 if any sequence of the set got a call.  mm_seqset_fetch_mods: who and prob of sequence i in read order (cap >= its length),
+ * zeros for a sequence without groups.  mm_seqset_slice and mm_seqset_concat carry the plane (a part without one gives zeros); mm_seqset_save / _load
+ * and mm_seqset_hpc do not. */
+int mm_seqset_add_mods(mm_seqset* s, int32_t n_groups, const uint8_t* base, const int8_t* code /* -1..3 */, const uint8_t* mode,
+                       const int64_t* off /* [n_groups + 1] */, const uint32_t* skips, const uint8_t* ml);
+int mm_seqset_has_mods(const mm_seqset* s);
+int mm_seqset_fetch_mods(mm_seqset* s, int64_t i, uint8_t* who_out, uint8_t* prob_out, int64_t cap);
 /* Inflate n BGZF blocks (whole gzip members with the BC field: header + deflate + CRC32 + ISIZE) on the context's device, from host memory
  * into host memory.  Block i is comp[comp_off[i], comp_off[i] + comp_len[i]) (comp_bytes bytes in `comp`); its ISIZE inflated bytes go to
  * out[out_off[i], out_off[i] + ISIZE) (out_cap bytes in `out`); no other byte of `out` is written, nor the bytes of a block that fails.
@@ -579,6 +597,35 @@ int mm_pileup_result_sizes(const mm_pileup_result* result, int64_t* n_sites, int
 int mm_pileup_result_fetch_sites(const mm_pileup_result* result, uint64_t* key /* [n_sites] */, uint32_t* count, uint32_t* depth, uint8_t* ref_byte);
 int mm_pileup_result_fetch_contigs(const mm_pileup_result* result, int64_t* alignments /* [n_contigs] */, int64_t* covered, int64_t* sum_depth);
 void mm_pileup_result_destroy(mm_pileup_result* result);
+
+/* The modification calls of aligned jobs per reference position and strand ("Base modifications"; the definition:
+ * csrc/mm_mods_core.hpp).  A job contributes where use[i] != 0 and dist[i] >= 0, as in mm_pileup_events.  Walking its runs from r = first, i = 0:
+ * column t of an = run reads the stored base s = i + t (strand +1) or m - 1 - (i + t) (strand -1) of its read of m bases; where who[s] != 0 it gives
+ * one event (contig, r + t, strand, class) with class 1 (fail) if prob[s] < min_ml, else 0 for canonical, 2 for another code, 3 + code.  X, I and D
+ * runs give none; a read without groups and a set without a plane give none.  key = contig << 36 | pos << 4 | (strand < 0) << 3 | class; more than
+ * 2^28 contigs is MM_ERR_ARG, and so is min_ml outside [0, 255].  mm_mod_events returns one call's events as (key, count) pairs with unique keys in
+ * ascending order and applies mm_bam_encode's rules 1, 2 (the strand), 4, 5 and 6 to the jobs it uses: MM_ERR_ARG with "mm_mod_events: job <index>:
+ * rule <number>: ..." for the lowest offender.  mm_mod_merge takes any multiset of pairs and returns the table with equal keys summed; a sum above
+ * 2^32 - 1 is MM_ERR_ARG.  mm_mod_finish takes a merged table (keys ascending and unique, every key a position of `reference` and a class below
+ * 3 + n_codes: MM_ERR_ARG otherwise), the base letter of each of the 1..4 asked codes and min_coverage >= 1.  At (contig, pos, strand), with b the
+ * reference's byte, upper-cased, complemented for strand -1 (a b outside ACGT gives no row), every code k whose base is b gives, in the codes' order,
+ * a row with N_mod = the count of class 3 + k, N_canonical = class 0, N_other = class 2 plus the other asked codes, N_fail = class 1; it is kept iff
+ * N_mod + N_canonical + N_other >= min_coverage.  Rows come in the order contig, pos, + before -, code; site = key with k in the place of the class.
+ * The tables and results are host memory. */
+typedef struct mm_mod mm_mod;                 /* a table of (key, count) modification events, unique keys ascending */
+typedef struct mm_mod_result mm_mod_result;   /* the rows of a run's modification table */
+int mm_mod_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs,
+                  const int32_t* read, const int32_t* strand, const int32_t* contig, const int32_t* dist, const int64_t* first,
+                  const int64_t* op_off /* [n_jobs + 1] */, const uint32_t* ops, const uint8_t* use /* [n_jobs] */, int32_t min_ml, mm_mod** out);
+int mm_mod_merge(mm_ctx* ctx, int64_t n, const uint64_t* keys, const uint32_t* counts, mm_mod** out);
+int mm_mod_sizes(const mm_mod* table, int64_t* n_pairs);
+int mm_mod_fetch(const mm_mod* table, uint64_t* keys /* [n_pairs] */, uint32_t* counts);
+void mm_mod_destroy(mm_mod* table);
+int mm_mod_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* keys, const uint32_t* counts,
+                  int32_t n_codes, const uint8_t* code_base /* [n_codes] */, int64_t min_coverage, mm_mod_result** out);
+int mm_mod_result_sizes(const mm_mod_result* result, int64_t* n_rows);
+int mm_mod_result_fetch(const mm_mod_result* result, uint64_t* site /* [n_rows] */, uint64_t* n_mod, uint64_t* n_canonical, uint64_t* n_other, uint64_t* n_fail);
+void mm_mod_result_destroy(mm_mod_result* result);
 
 /* The alleles of aligned jobs: SNVs, deletions and insertions that are canonical across reads, left-aligned and counted on the context's device (DESIGN.md
  * section 1, "VCF"; the definition: csrc/mm_vcf_core.hpp).  A job contributes where use[i] != 0 and dist[i] >= 0.  Walking its runs from r = first, i = 0

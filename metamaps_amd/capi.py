@@ -118,6 +118,9 @@ def lib() -> C.CDLL:
             "mm_seqset_add_qual": (C.c_int, [vp, C.c_char_p, i64, C.c_int]),
             "mm_seqset_has_qual": (C.c_int, [vp]),
             "mm_seqset_fetch_qual": (C.c_int, [vp, i64, vp, i64]),
+            "mm_seqset_add_mods": (C.c_int, [vp, C.c_int32, vp, vp, vp, vp, vp, vp]),
+            "mm_seqset_has_mods": (C.c_int, [vp]),
+            "mm_seqset_fetch_mods": (C.c_int, [vp, i64, vp, vp, i64]),
             "mm_bgzf_inflate": (C.c_int, [vp, C.c_char_p, i64, vp, vp, C.c_int32, vp, i64, vp, vp]),
             "mm_bgzf_deflate_bound": (i64, [i64]),
             "mm_bgzf_deflate": (C.c_int, [vp, C.c_char_p, i64, vp, i64, P(i64), P(C.c_int32)]),
@@ -218,6 +221,15 @@ def lib() -> C.CDLL:
             "mm_pileup_result_fetch_sites": (C.c_int, [vp, vp, vp, vp, vp]),
             "mm_pileup_result_fetch_contigs": (C.c_int, [vp, vp, vp, vp]),
             "mm_pileup_result_destroy": (None, [vp]),
+            "mm_mod_events": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp]),
+            "mm_mod_merge": (C.c_int, [vp, i64, vp, vp, vp]),
+            "mm_mod_sizes": (C.c_int, [vp, vp]),
+            "mm_mod_fetch": (C.c_int, [vp, vp, vp]),
+            "mm_mod_destroy": (None, [vp]),
+            "mm_mod_finish": (C.c_int, [vp, vp, i64, vp, vp, C.c_int32, vp, i64, vp]),
+            "mm_mod_result_sizes": (C.c_int, [vp, vp]),
+            "mm_mod_result_fetch": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+            "mm_mod_result_destroy": (None, [vp]),
             "mm_vcf_events": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
             "mm_vcf_events_q": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp]),
             "mm_vcf_merge": (C.c_int, [vp, i64, vp, vp, vp, vp]),
@@ -294,8 +306,21 @@ class Context:
             raise
         return s
 
-    def seqset(self, seqs, quals=None, qual_offset=33) -> "SeqSet":
-        """an uploaded set of ASCII sequences; quals: per sequence its quality bytes (mm_seqset_add_qual with qual_offset) or None"""
+    def add_mods(self, h, groups, **over):
+        """mm_seqset_add_mods for the sequence added last to the set h: groups are dicts with base ("A" "C" "G" "T"), code (-1..3), mode ("." "?" "") and
+        skips and ml of equal lengths, in MM's order; over: arrays in the place of the ones made from the groups (the refusal tests)"""
+        off = np.zeros(len(groups) + 1, dtype=np.int64)
+        np.cumsum([len(g["skips"]) for g in groups], out=off[1:])
+        a = dict(base=np.array([ord(g["base"]) for g in groups], dtype=np.uint8), code=np.array([g["code"] for g in groups], dtype=np.int8),
+                 mode=np.array([ord(g["mode"]) if g["mode"] else 0 for g in groups], dtype=np.uint8), off=off,
+                 skips=np.array([x for g in groups for x in g["skips"]], dtype=np.uint32), ml=np.array([x for g in groups for x in g["ml"]], dtype=np.uint8))
+        a.update(over)
+        assert all(len(g["skips"]) == len(g["ml"]) for g in groups)
+        self.check(lib().mm_seqset_add_mods(h, int(over.get("n_groups", len(groups))), _ptr(a["base"]), _ptr(a["code"]), _ptr(a["mode"]), _ptr(a["off"]), _ptr(a["skips"]), _ptr(a["ml"])))
+
+    def seqset(self, seqs, quals=None, qual_offset=33, mods=None) -> "SeqSet":
+        """an uploaded set of ASCII sequences; quals: per sequence its quality bytes (mm_seqset_add_qual with qual_offset) or None; mods: per sequence
+        its modification groups (add_mods) or None"""
         h = C.c_void_p()
         self.check(lib().mm_seqset_create(self.h, C.byref(h)))
         s = SeqSet(self, h)
@@ -307,11 +332,14 @@ class Context:
             self.check(lib().mm_seqset_add(h, q, len(q)))
             if i < len(keep) and keep[i] is not None:
                 self.check(lib().mm_seqset_add_qual(h, keep[i], len(keep[i]), qual_offset))
+            if mods is not None and i < len(mods) and mods[i] is not None:
+                self.add_mods(h, mods[i])
         return self._upload(s)
 
-    def seqset_nt16(self, records, quals=None, qual_offset=0) -> "SeqSet":
+    def seqset_nt16(self, records, quals=None, qual_offset=0, mods=None) -> "SeqSet":
         """a set of BAM-packed reads: records are (4-bit code bytes, bases, reverse) as a BAM record stores them; quals: per record its quality
-        bytes in the record's order (mm_seqset_add_qual with qual_offset) or None"""
+        bytes in the record's order (mm_seqset_add_qual with qual_offset) or None; mods: per record its modification groups (add_mods), which
+        speak of the read as sequenced, or None"""
         h = C.c_void_p()
         self.check(lib().mm_seqset_create(self.h, C.byref(h)))
         s = SeqSet(self, h)
@@ -321,6 +349,8 @@ class Context:
             self.check(lib().mm_seqset_add_nt16(h, b, n, 1 if rev else 0))
             if i < len(keepq) and keepq[i] is not None:
                 self.check(lib().mm_seqset_add_qual(h, keepq[i], len(keepq[i]), qual_offset))
+            if mods is not None and i < len(mods) and mods[i] is not None:
+                self.add_mods(h, mods[i])
         return self._upload(s)
 
     def bgzf_inflate(self, blocks, out_off=None, out_cap=None):
@@ -683,6 +713,57 @@ class Context:
             if h.value:
                 lib().mm_pileup_result_destroy(h)
 
+    def _mod_table(self, status, handle):
+        """(keys, counts) of an mm_mod, which is destroyed; `handle` is NULL after an error"""
+        try:
+            self.check(status)
+            n = C.c_int64()
+            assert lib().mm_mod_sizes(handle, C.byref(n)) == 0
+            keys, counts = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint32)
+            assert lib().mm_mod_fetch(handle, _ptr(keys), _ptr(counts)) == 0
+            return keys, counts
+        finally:
+            self.last_mod_handle = handle.value                     # (what the call left in *out: None after a refusal)
+            if handle:
+                lib().mm_mod_destroy(handle)
+
+    def mod_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use, min_ml=204):
+        """the modification events of the jobs with use != 0 and dist >= 0 (mm_mod_events): (keys, counts), keys contig << 36 | pos << 4 |
+        (strand < 0) << 3 | class unique and ascending, class 0 canonical, 1 fail (prob < min_ml), 2 another code, 3 + code"""
+        n = len(read)
+        rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
+        fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
+        op, us = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(use, dtype=np.uint8)
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_mod_events(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), int(min_ml), C.byref(h))
+        return self._mod_table(st, h)
+
+    def mod_merge(self, keys, counts):
+        """any (key, count) pairs, unsorted, keys may repeat -> the table with equal keys summed (mm_mod_merge)"""
+        ks, cs = np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(counts, dtype=np.uint32)
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_mod_merge(self.h, len(ks), _ptr(ks), _ptr(cs), C.byref(h))
+        return self._mod_table(st, h)
+
+    def mod_finish(self, reference: "SeqSet", keys, counts, code_base, min_coverage=1):
+        """the rows of a merged table (mm_mod_finish); code_base: the base letters of the asked codes, e.g. "CCA".  A dict of arrays: site (the
+        key with the code's index in the place of the class), n_mod, n_canonical, n_other, n_fail"""
+        ks, cs = np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(counts, dtype=np.uint32)
+        cb = np.frombuffer(code_base.encode() if isinstance(code_base, str) else bytes(code_base), dtype=np.uint8).copy()
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_mod_finish(self.h, reference.h, len(ks), _ptr(ks), _ptr(cs), len(cb), _ptr(cb), int(min_coverage), C.byref(h))
+        try:
+            self.check(st)
+            n = C.c_int64()
+            assert lib().mm_mod_result_sizes(h, C.byref(n)) == 0
+            out = {k: np.zeros(n.value, dtype=np.uint64) for k in ("site", "n_mod", "n_canonical", "n_other", "n_fail")}
+            assert lib().mm_mod_result_fetch(h, *[_ptr(out[k]) for k in ("site", "n_mod", "n_canonical", "n_other", "n_fail")]) == 0
+            return out
+        finally:
+            self.last_mod_handle = h.value
+            if h:
+                lib().mm_mod_result_destroy(h)
+
     def _vcf_table(self, status, handle):
         """(w0, w1, counts) of an mm_vcf, which is destroyed; `handle` is NULL after an error"""
         try:
@@ -850,6 +931,16 @@ class SeqSet:
         buf = np.zeros(max(length, 1), dtype=np.uint8)
         self.ctx.check(lib().mm_seqset_fetch_qual(self.h, i, _ptr(buf), length))
         return buf[:length].tobytes()
+
+    @property
+    def has_mods(self) -> bool:
+        return bool(lib().mm_seqset_has_mods(self.h))
+
+    def fetch_mods(self, i: int, length: int):
+        """(who, prob) of sequence i in read order (mm_seqset_fetch_mods): who 0 no call, 1 canonical, 2 another code, 3 + code"""
+        who, prob = np.zeros(max(length, 1), dtype=np.uint8), np.zeros(max(length, 1), dtype=np.uint8)
+        self.ctx.check(lib().mm_seqset_fetch_mods(self.h, i, _ptr(who), _ptr(prob), length))
+        return who[:length].tobytes(), prob[:length].tobytes()
 
     def fetch_range(self, first: int, count: int):
         """(ASCII of sequences [first, first + count) back to back as a uint8 array, their lengths)"""

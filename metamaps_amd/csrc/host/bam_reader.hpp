@@ -5,7 +5,8 @@
 // What a record becomes is what `samtools fastq -n` writes for it: secondary (0x100) and supplementary (0x800) records are skipped, a record
 // with 0x10 is the reverse complement of the read as sequenced (the complement of a 4-bit code is its bit reversal: A<->T, C<->G, M<->K, R<->Y,
 // V<->B, H<->D; S, W, N and '=' stay), the name is read_name without its NUL, the qualities are handed on as they lie (Record::qual: in the
-// record's order, so reversed where 0x10 is set), tags are ignored, and paired-end flags (0x1, 0x40, 0x80) are NOT interpreted: no /1 or /2 is
+// record's order, so reversed where 0x10 is set), tags are ignored unless the reader is asked for the base-modification tags (want_tags: the aux fields
+// are walked and views of MM, ML and MN handed on), and paired-end flags (0x1, 0x40, 0x80) are NOT interpreted: no /1 or /2 is
 // appended.  The bases stay in BAM's packed 4-bit form (two per byte, high nibble first): the
 // library packs them on the device (mm_seqset_add_nt16).
 #pragma once
@@ -102,6 +103,42 @@ inline bool is_bam_file(const std::string& path) {
   return memcmp(out.data(), "BAM\1", 4) == 0;
 }
 
+// One aux field: its type (A c C s S i I f Z H B), for B the element type and count, and its value's bytes inside the record (Z, H: without the NUL)
+struct AuxField { char tag[2]; char type, sub; const uint8_t* p; size_t bytes, count; };
+inline size_t aux_elem_bytes(char t) { return t == 'A' || t == 'c' || t == 'C' ? 1 : t == 's' || t == 'S' ? 2 : t == 'i' || t == 'I' || t == 'f' ? 4 : 0; }
+// the aux fields in [p, end), each handed to fn; false where a field has an unknown type or runs over the end
+template <class Fn> bool aux_walk(const uint8_t* p, const uint8_t* end, Fn&& fn) {
+  while (p < end) {
+    if (end - p < 3) return false;
+    AuxField f{{(char)p[0], (char)p[1]}, (char)p[2], 0, p + 3, 0, 1};
+    p += 3;
+    if (const size_t w = aux_elem_bytes(f.type)) { if ((size_t)(end - p) < w) return false; f.bytes = w; }
+    else if (f.type == 'Z' || f.type == 'H') {
+      const void* nul = memchr(p, 0, (size_t)(end - p));
+      if (!nul) return false;
+      f.bytes = (size_t)((const uint8_t*)nul - p); f.count = f.bytes;
+      fn(f); p += f.bytes + 1;
+      continue;
+    } else if (f.type == 'B') {
+      if (end - p < 5) return false;
+      f.sub = (char)p[0];
+      const size_t w = aux_elem_bytes(f.sub), n = rd32(p + 1);
+      if (!w || f.sub == 'A' || n > (size_t)(end - p - 5) / w) return false;
+      f.p = p + 5; f.count = n; f.bytes = n * w;
+      fn(f); p += 5 + f.bytes;
+      continue;
+    } else return false;
+    fn(f); p += f.bytes;
+  }
+  return true;
+}
+inline int64_t aux_int(const AuxField& f) {                       // of an integer field (c C s S i I)
+  switch (f.type) {
+    case 'c': return (int8_t)f.p[0]; case 'C': return f.p[0]; case 's': return (int16_t)rd16(f.p); case 'S': return rd16(f.p);
+    case 'i': return (int32_t)rd32(f.p); default: return rd32(f.p);
+  }
+}
+
 struct Record {
   std::string name;
   const uint8_t* seq = nullptr;   // (l_seq + 1) / 2 bytes of 4-bit codes, valid until the next call of Reader::next
@@ -109,6 +146,8 @@ struct Record {
   const uint8_t* qual = nullptr;  // l_seq raw Phred bytes in the record's order, valid as long as seq; nullptr: the record has none (its first quality byte is 0xFF)
   uint16_t flag = 0;
   bool reverse() const { return flag & 0x10; }
+  // under want_tags: the record's MM, ML and MN fields as they lie (type 0: the record has none), valid as long as seq
+  AuxField mm{}, ml{}, mn{};
 };
 
 // One block of a segment to inflate: bs bytes at file offset `off`, its isize inflated bytes go to dst + out.
@@ -200,8 +239,8 @@ class BgzfStream {
 class Reader {
  public:
   static constexpr size_t SEG_BLOCKS = BgzfStream::SEG_BLOCKS;
-  Reader(const std::string& path, unsigned threads, int64_t max_len, bool skip_filtered = true, SegmentInflater inflater = nullptr)
-      : path_(path), max_len_(max_len), skip_filtered_(skip_filtered), z_(path, threads, std::move(inflater)) {
+  Reader(const std::string& path, unsigned threads, int64_t max_len, bool skip_filtered = true, SegmentInflater inflater = nullptr, bool want_tags = false)
+      : path_(path), max_len_(max_len), skip_filtered_(skip_filtered), want_tags_(want_tags), z_(path, threads, std::move(inflater)) {
     read_header();
   }
   Reader(const Reader&) = delete;
@@ -234,6 +273,14 @@ class Reader {
       r.l_seq = l_seq;
       r.qual = l_seq > 0 && r.seq[seq_bytes] != 0xFF ? r.seq + seq_bytes : nullptr;
       r.flag = flag;
+      r.mm = r.ml = r.mn = AuxField{};
+      if (want_tags_) {
+        const auto keep = [&](const AuxField& f) {
+          if (f.tag[0] != 'M') return;
+          if (f.tag[1] == 'M') r.mm = f; else if (f.tag[1] == 'L') r.ml = f; else if (f.tag[1] == 'N') r.mn = f;
+        };
+        if (!aux_walk(r.seq + seq_bytes + (size_t)l_seq, h + bsz, keep)) throw Error(path_ + ": corrupt BAM record (aux fields) of read " + r.name);
+      }
       return true;
     }
   }
@@ -272,7 +319,7 @@ class Reader {
 
   std::string path_;
   int64_t max_len_;
-  bool skip_filtered_;
+  bool skip_filtered_, want_tags_;
   BgzfStream z_;
   std::vector<uint8_t> buf_; size_t pos_ = 0, end_ = 0;          // inflated bytes [pos_, end_) of buf_ not parsed yet
 };

@@ -43,6 +43,7 @@ struct CliSwitches {
   const bool format_trace = on(getenv("MM_CLI_FORMAT_TRACE"));
   const size_t pileup_merge_pairs = (size_t)u64(getenv("MM_PILEUP_MERGE_PAIRS"), (uint64_t)64 << 20);   // --pileup: pairs above which a file's accumulator is merged (tests: small)
   const size_t vcf_merge_pairs = (size_t)u64(getenv("MM_VCF_MERGE_PAIRS"), (uint64_t)64 << 20);   // --vcf: the same for its (w0, w1, count) triples
+  const size_t mods_merge_pairs = (size_t)u64(getenv("MM_MODS_MERGE_PAIRS"), (uint64_t)64 << 20);   // --mods: the same for its (key, count) pairs
   const int64_t cons_group_bases = (int64_t)std::clamp<uint64_t>(u64(getenv("MM_CONS_GROUP_BASES"), (uint64_t)1 << 28), 1, (uint64_t)1 << 40);   // --consensus: bases per call
   const bool classify_from_file = on(getenv("MM_CLI_CLASSIFY_FROM_FILE"));      // --then-classify reads the mappings file back instead of taking the kept lines
   // classify

@@ -1,12 +1,14 @@
 // The side outputs of a batch of mapDirectly (the rows of side_files.hpp: PREFIX.editDistances, .paf, .bam) and the device calls they need, and the run's
-// pileup (PREFIX.pileup, .pileup.contigs), alleles (PREFIX.vcf) and consensus (PREFIX.consensus.fa, .consensus.tsv), which every batch adds to.  The text and
-// byte rules are in edit_dist.hpp, paf_out.hpp, bam_out.hpp, pileup_out.hpp, vcf_out.hpp and consensus_out.hpp, which call nothing; everything of a batch runs
-// on the context that mapped it, the last merge and the finish of the pileup, of the alleles and of the consensus on the first device.
+// pileup (PREFIX.pileup, .pileup.contigs), alleles (PREFIX.vcf), consensus (PREFIX.consensus.fa, .consensus.tsv) and modification counts (PREFIX.bedmethyl),
+// which every batch adds to.  The text and byte rules are in edit_dist.hpp, paf_out.hpp, bam_out.hpp, pileup_out.hpp, vcf_out.hpp, consensus_out.hpp and
+// mods_out.hpp, which call nothing; everything of a batch runs on the context that mapped it, the last merge and the finish of the pileup, of the alleles, of
+// the consensus and of the modification counts on the first device.
 #pragma once
 #include "bam_out.hpp"
 #include "cli_device.hpp"
 #include "consensus_out.hpp"
 #include "edit_dist.hpp"
+#include "mods_out.hpp"
 #include "paf_out.hpp"
 #include "pileup_out.hpp"
 #include "side_files.hpp"
@@ -57,6 +59,17 @@ struct VcfCalls {
     mm_vcf_sizes(t, &n); v.resize((size_t)n, true); mm_vcf_fetch(t, v.w0.data(), v.w1.data(), v.counts.data()); mm_vcf_destroy(t);
   }
 };
+// --mods in the same shape: one-word keys; the int32 behind `use` is the ML threshold where the other two take the base-quality floor
+struct ModCalls {
+  using Table = mm_mod;
+  static constexpr const char* events_what = "modification events"; static constexpr const char* merge_what = "modification merge";
+  static constexpr auto events = mm_mod_events;
+  static int merge(mm_ctx* ctx, const VariantRows& v, Table** t) { return mm_mod_merge(ctx, (int64_t)v.w0.size(), v.w0.data(), v.counts.data(), t); }
+  static void fetch(Table* t, VariantRows& v) {
+    int64_t n = 0;
+    mm_mod_sizes(t, &n); v.resize((size_t)n, false); mm_mod_fetch(t, v.w0.data(), v.counts.data()); mm_mod_destroy(t);
+  }
+};
 // rows and their sums through the output's merge, which leaves them unique and ascending
 template <class C> void merge_rows(mm_ctx* ctx, VariantRows& v) {
   typename C::Table* t = nullptr;
@@ -98,6 +111,18 @@ void pileup_write(mm_ctx* ctx, const mm_seqset* reference, VariantRows& v, const
   if (n_contigs != (int64_t)cname.size()) die("internal error: the pileup's contigs and the reference's differ in number");
   write_or_die(prefix + ".pileup", pileup_text(key, count, depth, ref_byte, cname));
   write_or_die(prefix + ".pileup.contigs", pileup_contigs_text(alignments, covered, sum_depth, cname, clen));
+}
+// --mods, after the last batch of a query file: one merge, one mm_mod_finish against the reference of `ctx`, and the file
+void mods_write(mm_ctx* ctx, const mm_seqset* reference, VariantRows& v, const ModsOpts& mo, const std::string& prefix, const std::vector<std::string>& cname) {
+  merge_rows<ModCalls>(ctx, v);
+  mm_mod_result* r = nullptr;
+  ck(ctx, mm_mod_finish(ctx, reference, (int64_t)v.w0.size(), v.w0.data(), v.counts.data(), mo.n_codes, mo.code_base, mo.min_coverage, &r), "modification rows");
+  int64_t n = 0;
+  mm_mod_result_sizes(r, &n);
+  std::vector<uint64_t> site((size_t)n), n_mod((size_t)n), n_canonical((size_t)n), n_other((size_t)n), n_fail((size_t)n);
+  mm_mod_result_fetch(r, site.data(), n_mod.data(), n_canonical.data(), n_other.data(), n_fail.data());
+  mm_mod_result_destroy(r);
+  write_or_die(prefix + ".bedmethyl", bedmethyl_text(mo, site, n_mod, n_canonical, n_other, n_fail, cname));
 }
 // --vcf, after the last batch of a query file and the merge of its rows: one mm_vcf_finish against the reference of `ctx` over the file's intervals, and the file
 void vcf_write(mm_ctx* ctx, const mm_seqset* reference, const VariantRows& v, const Intervals& iv, const VcfOpts& vo, int min_base_quality, const std::string& prefix,
@@ -153,19 +178,21 @@ void consensus_write(mm_ctx* ctx, const mm_seqset* reference, const VariantRows&
 // the run's accumulators, one set per query file, and what is written from them after the last batch (every pileup before the first VCF).  The alleles are
 // accumulated (vcf_on) for --vcf and for --consensus, merged once, and written as PREFIX.vcf under --vcf alone
 struct RunVariants {
-  struct File { Intervals iv; VariantAcc pile, vcf; };
-  bool pileup_on = false, vcf_on = false, vcf_file = false, cons_on = false;
+  struct File { Intervals iv; VariantAcc pile, vcf, mods; };
+  bool pileup_on = false, vcf_on = false, vcf_file = false, cons_on = false, mods_on = false;
   std::deque<File> files;
-  void resize(bool pileup, bool vcf, bool cons, size_t n_files) {
-    pileup_on = pileup; vcf_on = vcf || cons; vcf_file = vcf; cons_on = cons;
-    if (pileup_on || vcf_on) files.resize(n_files);
+  void resize(bool pileup, bool vcf, bool cons, bool mods, size_t n_files) {
+    pileup_on = pileup; vcf_on = vcf || cons; vcf_file = vcf; cons_on = cons; mods_on = mods;
+    if (pileup_on || vcf_on || mods_on) files.resize(n_files);
   }
   VariantAcc* pile(size_t f) { return pileup_on ? &files[f].pile : nullptr; }
   VariantAcc* vcf(size_t f) { return vcf_on ? &files[f].vcf : nullptr; }
+  VariantAcc* mods(size_t f) { return mods_on ? &files[f].mods : nullptr; }
   Intervals* intervals(size_t f) { return files.empty() ? nullptr : &files[f].iv; }
-  void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const ConsOpts& co, int min_base_quality, int64_t cons_group_bases,
-             const std::vector<std::string>& prefixes, const std::vector<std::string>& cname, const std::vector<int>& clen) {
+  void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const ConsOpts& co, const ModsOpts& mo, int min_base_quality,
+             int64_t cons_group_bases, const std::vector<std::string>& prefixes, const std::vector<std::string>& cname, const std::vector<int>& clen) {
     for (size_t fi = 0; pileup_on && fi < files.size(); ++fi) pileup_write(ctx, reference, files[fi].pile.rows, files[fi].iv, po, prefixes[fi], cname, clen);
+    for (size_t fi = 0; mods_on && fi < files.size(); ++fi) mods_write(ctx, reference, files[fi].mods.rows, mo, prefixes[fi], cname);
     for (size_t fi = 0; vcf_on && fi < files.size(); ++fi) {
       merge_rows<VcfCalls>(ctx, files[fi].vcf.rows);
       if (vcf_file) vcf_write(ctx, reference, files[fi].vcf.rows, files[fi].iv, vo, min_base_quality, prefixes[fi], cname, clen);
@@ -185,15 +212,19 @@ struct BatchSideOutputs {
   size_t vcf_merge_pairs = 0;
   Intervals* iv = nullptr;                                       // --pileup, --vcf, --consensus: the contributing alignments of the batch's query file
   int32_t min_base_quality = 0;                                  // --min-base-quality: the floor of the pileup's events and of the alleles
+  VariantAcc* mods = nullptr;                                    // --mods: the accumulator of the batch's query file (the base-quality floor does not touch its counts)
+  size_t mods_merge_pairs = 0;
+  int32_t min_ml = 0;                                            // --mod-min-ml: the ML byte below which a call counts as failed
 
   // while the mapping lives: d, first, last (and the runs, where .paf or .bam want them) fetched once -> the lines of .editDistances and .paf.
-  // The reads go here unless .bam needs them for SEQ or the pileup or the VCF for their mismatched and inserted bases.  Nothing happens without reads (no side file was asked for).
+  // The reads go here unless .bam needs them for SEQ, the pileup or the VCF for their mismatched and inserted bases, or --mods for their calls.
+  // Nothing happens without reads (no side file was asked for).
   void from_mapping(mm_ctx* ctx, const mm_mapping* m, ReadsPtr& reads, const mm_seqset* reference, float pi, const std::vector<mm_map_record>& rec,
                     const std::vector<std::string>& names, const std::vector<int>& lens, const std::vector<int64_t>& off, const std::vector<std::string>& cname,
                     const std::vector<int>& clen, SideBytes& out) {
     if (!reads) return;
     const size_t n = rec.size();
-    if (on[SIDE_PAF] || on[SIDE_BAM] || pile || vcf) {
+    if (on[SIDE_PAF] || on[SIDE_BAM] || pile || vcf || mods) {
       mm_alignment* a = nullptr;
       ck(ctx, mm_mapping_align(ctx, m, reads.get(), reference, pi, &a), "alignments");
       int64_t n_jobs = 0, n_ops = 0;
@@ -208,7 +239,7 @@ struct BatchSideOutputs {
     }
     edit_distance_text(al.dist.data(), al.first.data(), al.last.data(), names, off, rec, cname, out[SIDE_EDIT]);
     if (on[SIDE_PAF]) paf_text(al, names, lens, off, rec, cname, clen, out[SIDE_PAF]);
-    if (!on[SIDE_BAM] && !pile && !vcf) reads.reset();
+    if (!on[SIDE_BAM] && !pile && !vcf && !mods) reads.reset();
   }
 
   // once the lines are formatted: the batch's BAM records as BGZF members, encoded and deflated on the device, and its pileup events and alleles (all go by
@@ -220,9 +251,10 @@ struct BatchSideOutputs {
     members.clear();
     if (!rec.empty()) {
       const BamFields F = bam_fields(al.dist, rec, names, off, text);
-      if (pile || vcf) {
+      if (pile || vcf || mods) {
         const std::vector<uint8_t> use = pileup_use(F.flag, al.dist);
-        iv->add_intervals(use, F.contig, al.first, al.last);
+        if (mods) add_batch<ModCalls>(ctx, reads.get(), reference, F, al, use, min_ml, mods_merge_pairs, *mods);
+        if (pile || vcf) iv->add_intervals(use, F.contig, al.first, al.last);
         if (pile) add_batch<PileupCalls>(ctx, reads.get(), reference, F, al, use, min_base_quality, pile_merge_pairs, *pile);
         if (vcf) add_batch<VcfCalls>(ctx, reads.get(), reference, F, al, use, min_base_quality, vcf_merge_pairs, *vcf);
       }

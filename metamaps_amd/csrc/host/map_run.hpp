@@ -61,6 +61,7 @@ struct MapRun {
   const VcfOpts vcf = vcf_options(o);                            // --vcf (implies --edit-distance): the same (vcf_out.hpp)
   const ConsOpts cons = consensus_options(o);                    // --consensus (implies --edit-distance): --vcf's accumulator (consensus_out.hpp)
   const QualOpts qual = qual_options(o);                         // --base-qualities, --min-base-quality: the batches carry the reads' qualities to the device
+  const ModsOpts mods = mods_options(o);                         // --mods (implies --edit-distance): a BAM query's MM/ML groups go to the device with its reads (mods_out.hpp)
   RunVariants var;
   std::string bgzf_head;                                         // what a BGZF side file starts with: the header of every PREFIX.bam as BGZF members (the contigs are the run's)
   std::vector<int> clen_raw; std::vector<mm_hpc_map*> hpc_map;
@@ -188,7 +189,7 @@ struct MapRun {
 
   // (started as soon as the reference has been parsed: the first batches are ready when the index is)
   void start_reader() { if (reader.th.joinable() || reader.started) return; reader.started = true; 
-    reader.th = std::thread([this]() { QueryReader(reader, queries, BATCH_READS, BATCH_BASES, devs[0].phys, pc, mapped, sw, qual.keep).run(); }); }
+    reader.th = std::thread([this]() { QueryReader(reader, queries, BATCH_READS, BATCH_BASES, devs[0].phys, pc, mapped, sw, qual.keep, mods.on ? &mods : nullptr).run(); }); }
   void start_prewarm() {
     if (prewarm.joinable() || sw.no_prewarm) return;
     int64_t query_bytes = 0; for (auto& q : queries) query_bytes += (int64_t)file_size(q);
@@ -358,7 +359,7 @@ struct MapRun {
     }
     if (place != Place::Replicated && NC == 1 && !from_index && !maxMem) die("--stream-chunks / --shard-index need --maxmemory (the chunk rule of the reference, winSketch.hpp:274-329)");
     if (edit && place != Place::Replicated)
-      die(std::string(cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : side[SIDE_PAF] ? "--paf" : "--edit-distance")
+      die(std::string(mods.on ? "--mods" : cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : side[SIDE_PAF] ? "--paf" : "--edit-distance")
           + " needs the whole reference resident on every device, and this index does not fit one: run without it");
     for (auto& d : devs) d.idx.assign(NC, nullptr);
     thr_of.assign(NC, INT_MAX);
@@ -419,6 +420,7 @@ struct MapRun {
       if (bt.nt16) ck(ctx, mm_seqset_add_nt16(reads, (const uint8_t*)bt.seq_of(r), (int64_t)bt.lens[r], bt.rev[r]), "add read");
       else ck(ctx, mm_seqset_add_view(reads, bt.seq_of(r), (int64_t)bt.lens[r]), "add read");
       if (const char* q = bt.qual_of(r)) ck(ctx, mm_seqset_add_qual(reads, (const uint8_t*)q, (int64_t)bt.lens[r], bt.qual_offset), "add qualities");   // (--base-qualities)
+      ck(ctx, bt.add_mods_to(reads, r), "add modifications");    // (--mods: nothing for a read without tags)
     }
     ck(ctx, mm_seqset_upload(reads), "upload reads");
     if (hpc) {                                                     // compressed on the context that maps the batch, between upload and K1
@@ -459,7 +461,8 @@ struct MapRun {
     const auto f1 = std::chrono::steady_clock::now();
     std::vector<mm_map_record> rec((size_t)dn->off.back());
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), rec.data(), (int64_t)rec.size()), "fetch");
-    BatchSideOutputs so{side, {}, var.pile(file), sw.pileup_merge_pairs, var.vcf(file), sw.vcf_merge_pairs, var.intervals(file), qual.min_base_quality};   // one alignment for all of them
+    BatchSideOutputs so{side, {}, var.pile(file), sw.pileup_merge_pairs, var.vcf(file), sw.vcf_merge_pairs, var.intervals(file), qual.min_base_quality,
+                        var.mods(file), sw.mods_merge_pairs, mods.min_ml};   // one alignment for all of them
     so.from_mapping(ctx, m, reads, refset[dev], pi, rec, dn->names, dn->lens, dn->off, cname, clen, dn->side);
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
@@ -772,14 +775,14 @@ struct MapRun {
     build_resident_indexes();
     mp = mm_map_params{k, w, pi, minLen};
     for (auto& ch : chunks) chunk_base.push_back(ch.first);
-    var.resize(pileup.on, vcf.on, cons.on, prefixes.size());
+    var.resize(pileup.on, vcf.on, cons.on, mods.on, prefixes.size());
     if (side[SIDE_BAM]) bgzf_head = bam_header_members(ctx0, cname, clen);   // (before the workers take the first device's context)
     start_reader();
     if (prewarm.joinable()) prewarm.join();
     if (place != Place::Replicated) for (auto*& c : wctx) if (c) { mm_ctx_destroy(c); c = nullptr; }   // (the other modes drive one context per device)
     if (place == Place::Replicated) run_replicated(); else run_chunk_major();
     pc.lap("8 write");
-    var.write(ctx0, refset[0], pileup, vcf, cons, qual.min_base_quality, sw.cons_group_bases, prefixes, cname, clen);
+    var.write(ctx0, refset[0], pileup, vcf, cons, mods, qual.min_base_quality, sw.cons_group_bases, prefixes, cname, clen);
     then_classify();
     if (!sw.full_teardown) { if (reader.th.joinable()) reader.th.join(); pc.report(); finish_fast(); }
     drop_refsets();

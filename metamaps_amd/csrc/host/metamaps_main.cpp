@@ -6,7 +6,7 @@
 // reference too: argument parsing, FASTA/FASTQ(.gz) reading, text formatting, taxonomy bookkeeping.
 //
 //   metamaps mapDirectly [--all] [--compress-output] [--edit-distance] [--paf] [--bam] [--pileup [--pileup-min-count N] [--pileup-min-frac F]] [--vcf [--vcf-min-count N] [--vcf-min-frac F]]
-//                       [--consensus [--consensus-min-depth D] [--consensus-min-frac F] [--consensus-min-called C]]
+//                       [--consensus [--consensus-min-depth D] [--consensus-min-frac F] [--consensus-min-called C]] [--mods LIST [--mod-min-ml T] [--mod-min-coverage N]]
 //                        -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
 //   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]] [--lca T] [--genes] [--min-identity T [--refit]]
@@ -85,6 +85,17 @@
 // merged on the device whenever they pass MM_VCF_MERGE_PAIRS; the first device finishes (mm_vcf_finish).  No genotypes, FORMAT columns, qualities or
 // multi-allelic records.  Plain text; an empty run writes the header.  Every other file of the run is the file of the same run without the flag.  Refused
 // wherever --edit-distance is; the two thresholds are refused without --vcf (host/vcf_out.hpp).
+//
+// --mods LIST [--mod-min-ml T] [--mod-min-coverage N] (mapDirectly; not in the reference; implies --edit-distance; may be combined with --paf, --bam, --pileup,
+// --vcf, --consensus and --base-qualities): also PREFIX.bedmethyl, what `modkit pileup` gives over the PRIMARY records of the run: modkit's 18 tab-separated
+// columns without a header, one row per reference position, strand and code of LIST with the primary alignments whose matched (=) base there carries a call.
+// LIST is 1 to 4 items B+code (C+m,C+h,A+a,C+21839).  The calls come from the MM/ML tags of an unaligned BAM query (SAM tags specification, "Base
+// modifications"; host/mods_out.hpp); a FASTA/FASTQ query and a BAM without the tags give an empty file and an INFO line.  The tags' skip lists become a
+// (who, prob) plane beside the read's bases on the device (mm_seqset_add_mods), mm_mod_events walks the batch's one alignment call, the run's pairs are merged
+// whenever they pass MM_MODS_MERGE_PAIRS and the first device finishes (mm_mod_finish).  A call whose probability byte is below T (0..255, default 204) counts
+// as failed; a row is kept with N (default 1) or more valid calls.  Calls in mismatched or inserted bases count nowhere; N_delete, N_diff and N_nocall are
+// written 0; --min-base-quality does not touch the counts.  Every other file of the run is the file of the same run without the flag.  Refused wherever
+// --edit-distance is; the two thresholds are refused without --mods.
 //
 // --base-qualities, --min-base-quality Q (mapDirectly; not in the reference; samtools mpileup's -Q): the run keeps the base qualities of its queries (the quality
 // line of a FASTQ record in any of the text forms, the qual field of a BAM record; a FASTA record and a BAM record without have none) and uploads them beside
@@ -180,6 +191,10 @@ Options parse(int argc, char** argv) {
                    "         PREFIX.bam carries them in QUAL (0xFF for a read without); not with --hpc, --shard-index, --stream-chunks\n"
                    "  --min-base-quality Q  (mapDirectly, with --pileup, --vcf or --consensus) Q in [0, 93], implies --base-qualities: a mismatch counts only where its\n"
                    "         base has quality >= Q, a deletion where the read's bases on both sides of it have, an insertion where all its bases have; DP and depth stay raw\n"
+                   "  --mods LIST [--mod-min-ml T] [--mod-min-coverage N]  (mapDirectly, BAM queries with MM/ML tags) implies --edit-distance and also writes PREFIX.bedmethyl\n"
+                   "         (modkit's 18 columns, no header): per reference position and strand the primary alignments whose matched base carries a modified, canonical,\n"
+                   "         other or failed call of each code of LIST (1 to 4 items like C+m,C+h,A+a,C+21839), counted on the device; a call fails below the ML byte T\n"
+                   "         (default 204), a row needs N (default 1) valid calls; may be combined with the other outputs; not with --hpc, --shard-index, --stream-chunks\n"
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
                    "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
                    "  --genes  (classify, mapDirectly --then-classify) gene-level analysis against DB_annotations.txt and DB_proteins.faa.annotated of the DB:\n"
@@ -277,6 +292,7 @@ int main(int argc, char** argv) {
   const PileupOpts pileup_opts = pileup_options(o);             // (validated before any work; MapRun reads them again)
   const VcfOpts vcf_opts = vcf_options(o);                      // (the same)
   const ConsOpts cons_opts = consensus_options(o);              // (the same)
+  const ModsOpts mods_opts = mods_options(o);                   // (the same)
   if (o.v.count("base-qualities") || o.v.count("min-base-quality")) {   // (refused under the flag's own name wherever --edit-distance is, before any device work)
     const std::string flag = o.v.count("min-base-quality") ? "--min-base-quality" : "--base-qualities";
     (void)qual_options(o);                                       // (the value and what uses it; MapRun reads them again)
@@ -284,9 +300,10 @@ int main(int argc, char** argv) {
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: a homopolymer-compressed read has no per-base qualities");
     if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");
   }
-  if (o.v.count("paf") || o.v.count("bam") || pileup_opts.on || vcf_opts.on || cons_opts.on) o.v["edit-distance"] = "1";   // (all five imply it, and inherit its refusals under their own names)
+  if (o.v.count("paf") || o.v.count("bam") || pileup_opts.on || vcf_opts.on || cons_opts.on || mods_opts.on) o.v["edit-distance"] = "1";   // (all six imply it and inherit its refusals)
   if (o.v.count("edit-distance")) {                              // (refused before any device work)
-    const std::string flag = cons_opts.on ? "--consensus" : vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup" : o.v.count("bam") ? "--bam" : o.v.count("paf") ? "--paf" : "--edit-distance";
+    const std::string flag = mods_opts.on ? "--mods" : cons_opts.on ? "--consensus" : vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup" : o.v.count("bam") ? "--bam"
+                             : o.v.count("paf") ? "--paf" : "--edit-distance";
     if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reference does not stay on the device");
     if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");

@@ -6,6 +6,7 @@
 #include "bam_reader.hpp"
 #include "cli_common.hpp"
 #include "cli_switches.hpp"
+#include "mods_out.hpp"
 #include "seq_reader.hpp"
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -70,6 +71,25 @@ struct Batch {
   static constexpr size_t NO_QUAL = (size_t)-1;
   bool keep_q = false; int qual_offset = 33;
   std::vector<const char*> qview; std::vector<size_t> qoff;
+  // --mods (keep_m: the batch was read from a BAM under the flag; the vectors stay empty otherwise): the parsed MM/ML groups of the reads one behind the
+  // other, read r's are [mod_goff[r], mod_goff[r + 1]), with mod_has[r] == 0 for a read without tags
+  bool keep_m = false;
+  std::vector<uint8_t> mod_has; std::vector<size_t> mod_goff{0}; ModGroups mod;
+  void put_mods(const ModGroups* g) {                            // the read added last (g == nullptr: it has no groups)
+    keep_m = true; mod_has.push_back(g ? 1 : 0);
+    if (g) {
+      const int64_t k0 = mod.off.back();
+      mod.base.insert(mod.base.end(), g->base.begin(), g->base.end()); mod.code.insert(mod.code.end(), g->code.begin(), g->code.end()); mod.mode.insert(mod.mode.end(), g->mode.begin(), g->mode.end());
+      for (size_t i = 1; i < g->off.size(); ++i) mod.off.push_back(k0 + g->off[i]);
+      mod.skips.insert(mod.skips.end(), g->skips.begin(), g->skips.end()); mod.ml.insert(mod.ml.end(), g->ml.begin(), g->ml.end());
+    }
+    mod_goff.push_back(mod.base.size());
+  }
+  int add_mods_to(mm_seqset* s, size_t r) const {                 // mm_seqset_add_mods for read r, which was added to s last (MM_OK where it has no groups)
+    if (!keep_m || !mod_has[r]) return MM_OK;
+    const size_t g0 = mod_goff[r];
+    return mm_seqset_add_mods(s, (int32_t)(mod_goff[r + 1] - g0), mod.base.data() + g0, mod.code.data() + g0, mod.mode.data() + g0, mod.off.data() + g0, mod.skips.data(), mod.ml.data());
+  }
   char* arena = nullptr; size_t cap = 0, used = 0;
   size_t seq = 0, file = 0;
   ~Batch() { free(arena); }
@@ -112,7 +132,10 @@ struct Batch {
     names.push_back(r.name); lens.push_back((int)r.l_seq); off.push_back(used); view.push_back(nullptr); used += nb;
     if (keep) { keep_q = true; qual_offset = 0; put_qual((const char*)r.qual, (size_t)r.l_seq, !nt16 && r.reverse()); }
   }
-  void reset() { names.clear(); lens.clear(); off.clear(); view.clear(); rev.clear(); qview.clear(); qoff.clear(); nt16 = false; keep_q = false; qual_offset = 33; used = 0; }
+  void reset() {
+    names.clear(); lens.clear(); off.clear(); view.clear(); rev.clear(); qview.clear(); qoff.clear(); nt16 = false; keep_q = false; qual_offset = 33; used = 0;
+    keep_m = false; mod_has.clear(); mod_goff.assign(1, 0); mod.clear();
+  }
   int64_t bases() const { int64_t b = 0; for (int L : lens) b += L; return b; }
   void absorb(Batch& o) {                                        // o's reads behind this batch's (the block parser's small batches joined up to the batch limits)
     const size_t base = used;
@@ -147,6 +170,8 @@ struct Reader {
 struct QueryReader {
   Reader& reader; const std::vector<std::string>& queries; const int64_t BATCH_READS, BATCH_BASES; const int dev0; PhaseClock& pc; std::deque<MappedFile>& mapped; const CliSwitches& sw;
   const bool keep_qual;                                          // --base-qualities: the batches carry the reads' qualities
+  const ModsOpts* const mods;                                    // --mods (null without): the batches of a BAM file carry the reads' parsed MM/ML groups
+  ModGroups mod_groups; ModCounters mod_n;                       // the record at hand; the counters of the current query file
   size_t q_reads = 0, q_with = 0;                                // under the flag: the reads of the current query file, and those of them with qualities
   using Emit = std::function<void(std::unique_ptr<Batch>)>;
   size_t seq = 0;
@@ -159,8 +184,8 @@ struct QueryReader {
   bam::SegmentInflater device_inflate;
 
   QueryReader(Reader& reader_, const std::vector<std::string>& queries_, int64_t batch_reads, int64_t batch_bases, int dev0_, PhaseClock& pc_, std::deque<MappedFile>& mapped_, const CliSwitches& sw_,
-              bool keep_qual_ = false)
-      : reader(reader_), queries(queries_), BATCH_READS(batch_reads), BATCH_BASES(batch_bases), dev0(dev0_), pc(pc_), mapped(mapped_), sw(sw_), keep_qual(keep_qual_) {
+              bool keep_qual_ = false, const ModsOpts* mods_ = nullptr)
+      : reader(reader_), queries(queries_), BATCH_READS(batch_reads), BATCH_BASES(batch_bases), dev0(dev0_), pc(pc_), mapped(mapped_), sw(sw_), keep_qual(keep_qual_), mods(mods_) {
     if (!sw.bgzf_host_inflate) device_inflate = [this](const uint8_t* file, const bam::SegBlock* b, size_t n, uint8_t* dst) { inflate_segment(file, b, n, dst); };
   }
   ~QueryReader() { if (zctx) mm_ctx_destroy(zctx); }
@@ -228,10 +253,21 @@ struct QueryReader {
   void read_bam(size_t fi) {                                     // records -> batches of 4-bit codes, packed on the device
     const unsigned P = (unsigned)std::max<unsigned>(1, std::min<unsigned>(32, mm::cpu_budget() / 2));
     try {
-      bam::Reader br(queries[fi], P, (1LL << 29) - 1, true, sw.bam_device_inflate ? device_inflate : nullptr);
+      bam::Reader br(queries[fi], P, (1LL << 29) - 1, true, sw.bam_device_inflate ? device_inflate : nullptr, mods != nullptr);
       bam::Record r;
+      auto put_mods = [&](Batch& b) {                              // --mods: the record's MM/ML groups, which speak of the read as sequenced, behind its bases
+        try {
+          const bool has = mods_parse(*mods, r.mm, r.ml, r.mn, r.l_seq, mod_groups, mod_n);
+          ++mod_n.reads; mod_n.with_tags += has;
+          b.put_mods(has ? &mod_groups : nullptr);
+        } catch (const ModTagError& e) { die("Error reading BAM: " + queries[fi] + ": read " + r.name + ": " + e.what()); }
+      };
       fill_batches([&] { return br.next(r); }, [&] { return (int64_t)r.l_seq; },
-                   [&](Batch& b) { if (b.names.empty()) { b.nt16 = !sw.bam_host_decode; b.reserve(first_reserve((int64_t)r.l_seq)); } b.put_nt16(r, keep_qual); },
+                   [&](Batch& b) {
+                     if (b.names.empty()) { b.nt16 = !sw.bam_host_decode; b.reserve(first_reserve((int64_t)r.l_seq)); }
+                     b.put_nt16(r, keep_qual);
+                     if (mods) put_mods(b);
+                   },
                    [&](std::unique_ptr<Batch> b) { enqueue(std::move(b), fi); });
     } catch (const bam::Error& e) { die(std::string("Error reading BAM: ") + e.what()); }
   }
@@ -326,6 +362,13 @@ struct QueryReader {
     }
   }
 
+  void mods_info(const std::string& q, bool is_bam) {            // --mods: one line per query file, with the reason where its bedMethyl file will be empty
+    if (!is_bam) std::cout << "INFO, --mods: " << q << " is not a BAM file and carries no MM/ML tags: its bedMethyl file is empty\n";
+    else
+      std::cout << "INFO, --mods: " << q << ": " << mod_n.reads << " reads, " << mod_n.with_tags << " with MM/ML tags" << (mod_n.with_tags ? "" : ": its bedMethyl file is empty") << "; dropped: "
+                << mod_n.minus_groups << " groups of strand -, " << mod_n.n_groups << " groups of base N, " << mod_n.mn_mismatch << " reads whose MN differs from their length\n";
+    mod_n = ModCounters{};
+  }
   // every query file in turn, by the kind its content shows; the lap of the kinds that have one, and the end of the file for the writer
   void run() {
     const auto r_t0 = std::chrono::steady_clock::now();
@@ -346,6 +389,7 @@ struct QueryReader {
       if (lap) pc.add(lap, std::chrono::duration<double>(std::chrono::steady_clock::now() - f_t0).count());
       if (keep_qual && q_reads && !q_with) std::cout << "INFO, --base-qualities: " << q << " carries no qualities: every base of its reads is without one (0xFF in PREFIX.bam)\n";
       q_reads = q_with = 0;
+      if (mods) mods_info(q, is_bam);
       std::lock_guard<std::mutex> lk(reader.m); reader.file_end.push_back(seq); reader.cv.notify_all();
     }
     { const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - r_t0).count();

@@ -14,6 +14,7 @@
 #include "mm_bam.hpp"
 #include "mm_pileup.hpp"
 #include "mm_vcf.hpp"
+#include "mm_mods.hpp"
 #include "mm_cons.hpp"
 #include "mm_cons_core.hpp"
 #include "mm_seq.hpp"
@@ -242,6 +243,18 @@ int mm_seqset_has_qual(const mm_seqset* s) {
 int mm_seqset_fetch_qual(mm_seqset* s, int64_t i, uint8_t* out, int64_t cap) {
   if (!s || (!out && cap > 0)) return MM_ERR_ARG;
   return guarded(s->ctx, [&] { mm::seqset_fetch_qual(s, i, out, cap); });
+}
+int mm_seqset_add_mods(mm_seqset* s, int32_t n_groups, const uint8_t* base, const int8_t* code, const uint8_t* mode, const int64_t* off, const uint32_t* skips, const uint8_t* ml) {
+  if (!s) return MM_ERR_ARG;
+  return guarded(s->ctx, [&] { mm::seqset_add_mods(s, n_groups, base, code, mode, off, skips, ml); });
+}
+int mm_seqset_has_mods(const mm_seqset* s) {
+  if (!s) return 0;
+  return s->frozen ? (s->has_mods ? 1 : 0) : (s->staged_mods.seq.empty() ? 0 : 1);
+}
+int mm_seqset_fetch_mods(mm_seqset* s, int64_t i, uint8_t* who_out, uint8_t* prob_out, int64_t cap) {
+  if (!s || ((!who_out || !prob_out) && cap > 0)) return MM_ERR_ARG;
+  return guarded(s->ctx, [&] { mm::seqset_fetch_mods(s, i, who_out, prob_out, cap); });
 }
 int mm_bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const int64_t* comp_off, const int32_t* comp_len, int32_t n,
                     uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status) {
@@ -842,6 +855,55 @@ int mm_pileup_result_fetch_contigs(const mm_pileup_result* r, int64_t* alignment
   return MM_OK;
 }
 void mm_pileup_result_destroy(mm_pileup_result* r) { delete r; }
+
+struct mm_mod { mm::KeyTable t; };                                 // (host memory only, as mm_pileup; one-word keys)
+struct mm_mod_result { mm::ModResult r; };
+int mm_mod_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
+                  const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, int32_t min_ml, mm_mod** out) {
+  if (!ctx || !reads || !reference || !out) return refused(out);
+  return created(ctx, out, [&](mm_mod& t) {
+    require_jobs("mm_mod_events", n_jobs, read && strand && contig && dist && first && op_off && use);
+    mm::mod_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, min_ml, &t.t);
+  });
+}
+int mm_mod_merge(mm_ctx* ctx, int64_t n, const uint64_t* keys, const uint32_t* counts, mm_mod** out) {
+  if (!ctx || !out) return refused(out);
+  return created(ctx, out, [&](mm_mod& t) {
+    require_rows("mm_mod_merge", "pairs", n, keys && counts);
+    mm::merge_run(ctx, n, keys, nullptr, counts, "mm_mod_merge", "MM_MODS_TIMING", &t.t);
+  });
+}
+int mm_mod_sizes(const mm_mod* t, int64_t* n_pairs) {
+  if (!t || !n_pairs) return MM_ERR_ARG;
+  *n_pairs = (int64_t)t->t.w0.size();
+  return MM_OK;
+}
+int mm_mod_fetch(const mm_mod* t, uint64_t* keys, uint32_t* counts) { return t ? table_fetch(t->t, keys, nullptr, counts) : MM_ERR_ARG; }
+void mm_mod_destroy(mm_mod* t) { delete t; }
+int mm_mod_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* keys, const uint32_t* counts, int32_t n_codes, const uint8_t* code_base, int64_t min_coverage,
+                  mm_mod_result** out) {
+  if (!ctx || !reference || !out) return refused(out);
+  return created(ctx, out, [&](mm_mod_result& r) {
+    require_rows("mm_mod_finish", "entries", n, keys && counts);
+    mm::mod_finish_run(ctx, reference, n, keys, counts, n_codes, code_base, min_coverage, &r.r);
+  });
+}
+int mm_mod_result_sizes(const mm_mod_result* r, int64_t* n_rows) {
+  if (!r || !n_rows) return MM_ERR_ARG;
+  *n_rows = (int64_t)r->r.site.size();
+  return MM_OK;
+}
+int mm_mod_result_fetch(const mm_mod_result* r, uint64_t* site, uint64_t* n_mod, uint64_t* n_canonical, uint64_t* n_other, uint64_t* n_fail) {
+  if (!r) return MM_ERR_ARG;
+  const size_t k = r->r.site.size();
+  if (k && (!site || !n_mod || !n_canonical || !n_other || !n_fail)) return MM_ERR_ARG;
+  if (k) {
+    memcpy(site, r->r.site.data(), k * 8); memcpy(n_mod, r->r.n_mod.data(), k * 8); memcpy(n_canonical, r->r.n_canonical.data(), k * 8);
+    memcpy(n_other, r->r.n_other.data(), k * 8); memcpy(n_fail, r->r.n_fail.data(), k * 8);
+  }
+  return MM_OK;
+}
+void mm_mod_result_destroy(mm_mod_result* r) { delete r; }
 
 struct mm_vcf { mm::KeyTable t; };                                 // (host memory only, as mm_pileup; two-word keys)
 struct mm_vcf_result { mm::VcfResult r; };

@@ -184,6 +184,10 @@ struct mm_seqset {
   int staged_kind = 0;                                          // 0 nothing staged yet, 1 ASCII, 2 nt16: one set holds one kind
   struct StagedQual { const uint8_t* p = nullptr; int offset = 0; bool set = false; };
   std::vector<StagedQual> staged_qual;                          // mm_seqset_add_qual: the viewed quality bytes of staged[i] (shorter than `staged`: the rest have none)
+  struct StagedMods {                                           // mm_seqset_add_mods: copies of the groups of the sequences `seq` (ascending) that got a call
+    std::vector<int32_t> seq; std::vector<int64_t> goff{0}, soff{0};   // groups [goff[r], goff[r + 1]) of seq[r]; skips and ML bytes [soff[g], soff[g + 1]) of group g
+    std::vector<uint8_t> base, mode, ml; std::vector<int8_t> code; std::vector<uint32_t> skips;
+  } staged_mods;
   // host-side metadata (always valid after upload / synthesis)
   std::vector<int32_t> len;            // per sequence
   std::vector<uint64_t> base;          // [n+1] first base of sequence i in the packed stream (multiple of 16)
@@ -201,5 +205,10 @@ struct mm_seqset {
   bool has_qual = false;
   mm::DBuf<uint8_t> qual;              // [base[n]]
   const uint8_t* qual_ptr() const { return has_qual ? qual.p : nullptr; }
+  // the modification plane (mm_seqset_add_mods; absent unless has_mods): word base[i] + p is who | prob << 8 of base p of sequence i (mm_mods_core.hpp),
+  // 0 for "no call" (a sequence added without groups, and the padding)
+  bool has_mods = false;
+  mm::DBuf<uint16_t> mods;             // [base[n]]
+  const uint16_t* mods_ptr() const { return has_mods ? mods.p : nullptr; }
   int64_t count() const { return (int64_t)len.size(); }
 };

@@ -110,6 +110,8 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_PILEUP_MERGE_PAIRS", "64 * 2^20", "test", "mapDirectly --pileup: (key, count) pairs a query file's accumulator may hold before it is replaced by its mm_pileup_merge (small values: several merges on small runs; no result depends on it)"},
     {"MM_VCF_TIMING", "unset", "debug", "device times of mm_vcf_events' upload, count, scan, emit, sort and reduce stages (events; reduce includes the table's copy to the host) with its jobs, runs, events, indels, pairs and fetched bytes, and of the stages of mm_vcf_merge and mm_vcf_finish, on stderr (tools/edit_kernel_stats.py --vcf)"},
     {"MM_VCF_MERGE_PAIRS", "64 * 2^20", "test", "mapDirectly --vcf: (w0, w1, count) triples a query file's accumulator may hold before it is replaced by its mm_vcf_merge (small values: several merges on small runs; no result depends on it)"},
+    {"MM_MODS_TIMING", "unset", "debug", "device times of the modification plane's upload and kernel in mm_seqset_upload with its groups, calls and staged bytes, of mm_mod_events' upload, count, scan, emit, sort and reduce stages (events; reduce includes the table's copy to the host) with its jobs, runs, events, pairs and fetched bytes, and of the stages of mm_mod_merge and mm_mod_finish, on stderr"},
+    {"MM_MODS_MERGE_PAIRS", "64 * 2^20", "test", "mapDirectly --mods: (key, count) pairs a query file's accumulator may hold before it is replaced by its mm_mod_merge (small values: several merges on small runs; no result depends on it)"},
     {"MM_CONS_TIMING", "unset", "debug", "device times of mm_consensus' intervals, candidates, select, positions, offsets and emit stages (emit includes the text's copy to the host) with the group's contig range, bases, entries, intervals, kept rows, written contigs and text bytes, on stderr (tools/edit_kernel_stats.py --consensus)"},
     {"MM_CONS_GROUP_BASES", "2^28", "test", "mapDirectly --consensus: reference bases one mm_consensus call may cover; consecutive contigs are grouped up to it and a longer contig is a group alone (small values: one call per contig on small runs; no result depends on it)"},
     {"MM_CLI_FORMAT_PART", "10000", "test", "mapping records per formatter thread of a batch (the text of a batch is formatted in up to eight parts and joined)"},

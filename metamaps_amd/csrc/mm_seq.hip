@@ -193,6 +193,7 @@ void seqset_upload(mm_seqset* s) {
   }
   MM_HIP(mm::stream_sync(st));
   seqset_upload_qual(s);
+  seqset_upload_mods(s);
   s->staged.clear(); s->staged.shrink_to_fit(); s->owned.clear(); s->owned.shrink_to_fit();
   s->frozen = true;
 }
@@ -355,6 +356,7 @@ void seqset_upload_nt16(mm_seqset* s) {
   }
   MM_HIP(mm::stream_sync(st));
   seqset_upload_qual(s);
+  seqset_upload_mods(s);
   s->staged.clear(); s->staged.shrink_to_fit(); s->staged_rev.clear(); s->staged_rev.shrink_to_fit();
   s->frozen = true;
 }
@@ -589,6 +591,10 @@ void seqset_slice(const mm_seqset* s, int64_t first, int64_t count, mm_seqset* o
     o->has_qual = true; o->qual.alloc((size_t)(b1 - b0));
     if (b1 > b0) MM_HIP(hipMemcpyAsync(o->qual.p, s->qual.p + b0, (size_t)(b1 - b0), hipMemcpyDeviceToDevice, st));
   }
+  if (s->has_mods) {                                             // the modification plane: the same range, two bytes per base
+    o->has_mods = true; o->mods.alloc((size_t)(b1 - b0));
+    if (b1 > b0) MM_HIP(hipMemcpyAsync(o->mods.p, s->mods.p + b0, (size_t)(b1 - b0) * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
+  }
   std::vector<uint64_t> es, oes; std::vector<uint32_t> el, oel; std::vector<uint8_t> eb, oeb;
   exc_to_host(s, es, el, eb);
   const size_t lo = (size_t)(std::lower_bound(es.begin(), es.end(), b0) - es.begin()), hi = (size_t)(std::lower_bound(es.begin(), es.end(), b1) - es.begin());
@@ -608,6 +614,8 @@ void seqset_concat(const mm_seqset* const* parts, int n_parts, mm_seqset* o) {
   o->packed.alloc((size_t)(bases >> 4) + 1);
   for (int p = 0; p < n_parts; ++p) o->has_qual = o->has_qual || parts[p]->has_qual;
   if (o->has_qual) o->qual.alloc((size_t)bases);                 // (a part without a plane gives rows of 0xFF)
+  for (int p = 0; p < n_parts; ++p) o->has_mods = o->has_mods || parts[p]->has_mods;
+  if (o->has_mods) o->mods.alloc((size_t)bases);                 // (a part without a plane gives zeros: no call)
   std::vector<uint64_t> oes; std::vector<uint32_t> oel; std::vector<uint8_t> oeb;
   uint64_t b0 = 0;
   for (int p = 0; p < n_parts; ++p) {
@@ -617,6 +625,10 @@ void seqset_concat(const mm_seqset* const* parts, int n_parts, mm_seqset* o) {
     if (o->has_qual && nw) {
       if (s->has_qual) MM_HIP(hipMemcpyAsync(o->qual.p + b0, s->qual.p, nw << 4, hipMemcpyDeviceToDevice, st));
       else MM_HIP(hipMemsetAsync(o->qual.p + b0, 0xFF, nw << 4, st));
+    }
+    if (o->has_mods && nw) {
+      if (s->has_mods) MM_HIP(hipMemcpyAsync(o->mods.p + b0, s->mods.p, (nw << 4) * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
+      else MM_HIP(hipMemsetAsync(o->mods.p + b0, 0, (nw << 4) * sizeof(uint16_t), st));
     }
     for (size_t i = 0; i < s->len.size(); ++i) { o->len.push_back(s->len[i]); o->base.push_back(b0 + s->base[i]); }
     o->total_bases += s->total_bases;

@@ -9,6 +9,11 @@ Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes pr
        python tools/edit_kernel_stats.py --vcf [n_reads]              (writes profiles/vcf_stats.txt)
        python tools/edit_kernel_stats.py --consensus [n_reads]        (writes profiles/consensus_stats.txt)
        python tools/edit_kernel_stats.py --qualities [n_reads] [--min-base-quality Q]   (writes profiles/qual_stats.txt)
+       python tools/edit_kernel_stats.py --mods [n_reads]   (writes profiles/mods_stats.txt)
+--mods: the batch fetched to the host and uploaded again without and with seeded modification groups (C+m? and A+a. on every C and A, ML uniform in 0 .. 255,
+independent of the bases): the upload's wall time both ways with the staged bytes (the MM_MODS_TIMING plane line), then in the same process mm_pileup_events
+and mm_mod_events twice each on the same alignments (the MM_PILEUP_TIMING and MM_MODS_TIMING stage lines), mm_mod_merge and mm_mod_finish with the table's
+size.  Synthetic tags say nothing about real methylation.  One run is one run.
 --qualities: the batch fetched to the host and uploaded again as a parser would hand it over, without and with seeded qualities (uniform in 2 .. 40 per base,
 independent of the bases): the upload's wall time both ways, then in the same process mm_bam_encode on the set without and with the plane, and
 mm_pileup_events_q and mm_vcf_events_q at floor 0 and at Q (default 20) with the rows of both tables at each floor.  Synthetic qualities do not correlate with
@@ -314,7 +319,97 @@ def child_qual(n_reads, floor):
     M.close(); idx.close(); reads.close(); plain.close(); ref.close(); ctx.close()
 
 
+def child_mods(n_reads):
+    import ctypes as C
+    from metamaps_amd import capi
+    ctx = capi.Context(0)
+    L = capi.lib()
+    ref = ctx.synth_reference(seed=20260928, n_species=25, strains_per_species=4, genome_len=2_200_000, strain_divergence=0.02, genus_divergence=0.2)
+    w = L.mm_recommended_window(1e-3, K, PI, 1000, ref.total_bases)
+    idx = ctx.index(ref, K, w)
+    synth, _ = ctx.synth_reads(ref, seed=1000, n_reads=n_reads, read_len=READ_LEN, read_len_min=0, sub_rate=0.04, ins_rate=0.03, del_rate=0.05, frac_random=0.05, n_abundant=100)
+    buf, ln = synth.fetch_range(0, synth.count)                     # the batch as a parser would hand it over: ASCII on the host, and seeded tags beside it
+    synth.close()
+    at = np.concatenate([[0], np.cumsum(ln, dtype=np.int64)])
+    rng = np.random.default_rng(8)
+    # C+m? and A+a. on EVERY C and A (all skips 0), ML bytes uniform in 0 .. 255: seeded, independent of the bases and of the synthetic errors
+    base, code, mode = np.frombuffer(b"CA", dtype=np.uint8).copy(), np.array([0, 1], dtype=np.int8), np.frombuffer(b"?.", dtype=np.uint8).copy()
+    n_c = np.add.reduceat((buf == 67).astype(np.int64), at[:-1]) * (ln > 0)
+    n_a = np.add.reduceat((buf == 65).astype(np.int64), at[:-1]) * (ln > 0)
+    calls = int(n_c.sum() + n_a.sum())
+    ml = rng.integers(0, 256, size=calls, dtype=np.uint8)
+    skips = np.zeros(int((n_c + n_a).max()), dtype=np.uint32)
+    print(f"tags: C+m? and A+a. on every C and A, {calls} calls on {int(ln.sum())} bases, ML uniform in 0 .. 255, seeded; min_ml 204", flush=True)
+    sets = {}
+    for rep in range(2):
+        for name in ("without", "with"):
+            if name in sets:
+                sets[name].close()
+            t0 = time.perf_counter()
+            h = C.c_void_p()
+            ctx.check(L.mm_seqset_create(ctx.h, C.byref(h)))
+            S = capi.SeqSet(ctx, h)
+            m0 = 0
+            for i in range(len(ln)):
+                ctx.check(L.mm_seqset_add_view(h, buf[at[i]:].ctypes.data_as(C.c_char_p), int(ln[i])))
+                if name == "with":
+                    off = np.array([0, n_c[i], n_c[i] + n_a[i]], dtype=np.int64)
+                    ctx.check(L.mm_seqset_add_mods(h, 2, capi._ptr(base), capi._ptr(code), capi._ptr(mode), capi._ptr(off), capi._ptr(skips), capi._ptr(ml[m0:])))
+                    m0 += int(off[2])
+            ctx.check(L.mm_seqset_upload(h))
+            sets[name] = S
+            dt = time.perf_counter() - t0
+            print(f"upload {name} the modification groups, call {rep}: {1e3 * dt:.1f} ms wall (the Python wrapper's adds included), {int(ln.sum()) / 4e6:.1f} MB of packed bases"
+                  + (f" + {5 * calls / 1e6:.1f} MB of skips (4 B) and ML bytes (1 B) host to device, a plane of {2 * int(ln.sum()) / 1e6:.1f} MB on the device" if name == "with" else ""), flush=True)
+    plain, reads = sets["without"], sets["with"]
+    M = ctx.map_batch(idx, reads, K, w, pi=PI)
+    M.keep_best(K)
+    off, rec = M.fetch()
+    n = len(rec)
+    print(f"{n_reads} reads of {READ_LEN} bases against {ref.total_bases} reference bases (k {K}, w {w}, pi {PI}): {n} best mappings", flush=True)
+    dist, first, last, op_off, ops = ctx.mapping_align(M, reads, ref, PI)
+    ev = dict(read=rec["read"], strand=rec["strand"].astype(np.int32), contig=rec["ref_contig"], dist=dist, first=first, op_off=op_off, ops=ops, use=np.ones(n, dtype=np.uint8))
+    for rep in range(2):
+        t0 = time.perf_counter()
+        keys, counts = ctx.pileup_events(reads, ref, **ev)
+        dt = time.perf_counter() - t0
+        print(f"mm_pileup_events call {rep}: {1e3 * dt:.1f} ms wall with the copies, {len(keys)} pairs of {int(counts.sum())} events", flush=True)
+        del keys, counts
+        t0 = time.perf_counter()
+        keys, counts = ctx.mod_events(reads, ref, **ev)
+        dt = time.perf_counter() - t0
+        print(f"mm_mod_events call {rep}: {1e3 * dt:.1f} ms wall with the copies, {len(keys)} pairs of {int(counts.sum())} events ({12 * len(keys) / 1e6:.1f} MB fetched), "
+              f"classes {np.bincount((keys & 7).astype(np.int64), minlength=7).tolist()}", flush=True)
+    assert len(ctx.mod_events(plain, ref, **ev)[0]) == 0            # (a set without a plane: the jobs are checked, nothing is counted)
+    half = len(keys) // 2
+    t0 = time.perf_counter()
+    mk, mc = ctx.mod_merge(np.concatenate([keys[half:], keys]), np.concatenate([counts[half:], counts]))
+    dt = time.perf_counter() - t0
+    assert np.array_equal(mk, keys) and np.array_equal(mc[:half], counts[:half]) and np.array_equal(mc[half:], 2 * counts[half:])
+    print(f"mm_mod_merge of the table with its upper half: {1e3 * dt:.1f} ms wall with the copies, {len(keys) + len(keys) - half} pairs in, {len(mk)} out", flush=True)
+    del mk, mc
+    t0 = time.perf_counter()
+    rows = ctx.mod_finish(ref, keys, counts, "CA", 1)
+    dt = time.perf_counter() - t0
+    print(f"mm_mod_finish (codes C+m, A+a; min_coverage 1): {1e3 * dt:.1f} ms wall with the copies, {len(rows['site'])} rows of {len(keys)} entries, "
+          f"{int(rows['n_mod'].sum())} modified, {int(rows['n_canonical'].sum())} canonical, {int(rows['n_fail'].sum())} failed calls", flush=True)
+    M.close(); idx.close(); reads.close(); plain.close(); ref.close(); ctx.close()
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--child-mods":
+        return child_mods(int(sys.argv[2]))
+    if len(sys.argv) > 1 and sys.argv[1] == "--mods":
+        n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-mods", str(n_reads)], env=dict(os.environ, MM_PILEUP_TIMING="1", MM_MODS_TIMING="1"), stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, timeout=1100)
+        text = f"tools/edit_kernel_stats.py --mods {n_reads}: one batch of {n_reads} reads, best mappings only; one run\n" + p.stdout.decode()
+        print(text)
+        if p.returncode != 0:
+            sys.exit(p.returncode)
+        with open(os.path.join(ROOT, "profiles", "mods_stats.txt"), "w") as f:
+            f.write(text)
+        return None
     if len(sys.argv) > 1 and sys.argv[1] == "--child-qual":
         return child_qual(int(sys.argv[2]), int(sys.argv[3]))
     if len(sys.argv) > 1 and sys.argv[1] == "--qualities":
