@@ -32,7 +32,8 @@ extern "C" {
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
                             *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances,
-                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_*, mm_pileup_*, mm_vcf_*, mm_consensus*, mm_seqset_*_mods, mm_mod_* (additions to 6) */
+                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_*, mm_pileup_*, mm_vcf_*, mm_consensus*, mm_seqset_*_mods, mm_mod_*,
+                            *    mm_depth_* (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -693,6 +694,35 @@ int mm_consensus_fetch_contigs(const struct mm_consensus* result, int32_t* conti
 /* the written contigs, ascending; the text of contig[j] is text[text_off[j], text_off[j + 1]) */
 int mm_consensus_fetch_text(const struct mm_consensus* result, int32_t* contig /* [n_written] */, int64_t* text_off /* [n_written + 1] */, uint8_t* text /* [text_bytes] */);
 void mm_consensus_destroy(struct mm_consensus* result);
+
+/* The depth profile of n_iv intervals (contig, first, last) over contigs of the given LENGTHS, computed on the context's device ("Depth";
+ * the definition: csrc/mm_depth_core.hpp).  The call reads no base and keeps no array indexed by a reference position: depth changes only at the 2 n_iv interval
+ * ends, so device and host memory are O(n_iv + listed contigs + windows) whatever the contigs' lengths.  depth(c, p) is the number of intervals that hold p
+ * (mm_pileup_finish's depth); nothing depends on the order of the intervals.
+ *   runs     the maximal [start, end) of equal depth >= 1 inside one contig, ordered by contig, then start; neighbouring pieces of equal depth are one run
+ *            ([0,4] and [5,9] at depth 1 give [0,10)), a run never crosses a contig's end, and zero depth is not listed.
+ *   contigs  for every contig with an interval, ascending, MM_DEPTH_STATS counters: alignments, covered, sumDepth (the three of mm_pileup_finish), medianDepth
+ *            (the depth at rank (len - 1) / 2, 0-based, of the contig's len depths sorted ascending, zeros included), maxDepth; then n_thresholds counters ge[t],
+ *            the positions with depth >= thresholds[t].
+ *   windows  for every such contig all windows [k * window, min((k + 1) * window, len)), k < ceil(len / window), each with the sum of its depths and its covered
+ *            positions; win_off[j] is the first window of the j-th listed contig, win_off[n_contigs] their number.
+ * All sums are 64-bit, a depth is 32-bit.  MM_ERR_ARG: a length outside [1, 2^29), more than 2^29 contigs, an interval off its contig or with first > last (the
+ * message names the lowest one), window < 1, more than 8 thresholds, a threshold < 1, thresholds that are not strictly ascending, more than 2^31 - 1 windows
+ * (the message names the window).  MM_ERR_LIMIT: 2^31 intervals or more.  All of this is checked on the host before anything is launched; n_iv == 0 gives an
+ * empty result and launches nothing.  All arrays are the caller's; the result lives in host memory until destroyed; an error leaves *out NULL.
+ * MM_DEPTH_TIMING=1 prints the stages' device times. */
+#define MM_DEPTH_STATS 5   /* alignments, covered, sumDepth, medianDepth, maxDepth; then n_thresholds ge counters */
+typedef struct mm_depth mm_depth;
+int mm_depth_profile(mm_ctx* ctx, int64_t n_contigs, const int64_t* contig_len,
+                     int64_t n_iv, const int32_t* iv_contig, const int64_t* iv_first, const int64_t* iv_last,
+                     int64_t window, int32_t n_thresholds, const int64_t* thresholds, mm_depth** out);
+/* n_contigs: the contigs with an interval */
+int mm_depth_sizes(const mm_depth* result, int64_t* n_runs, int64_t* n_contigs, int64_t* n_windows);
+int mm_depth_fetch_runs(const mm_depth* result, int32_t* contig /* [n_runs] */, int64_t* start, int64_t* end, uint32_t* depth);
+int mm_depth_fetch_contigs(const mm_depth* result, int32_t* contig /* [n_contigs] */, int64_t* win_off /* [n_contigs + 1] */,
+                           int64_t* stats /* [(MM_DEPTH_STATS + n_thresholds) * n_contigs] */);
+int mm_depth_fetch_windows(const mm_depth* result, int64_t* sum /* [n_windows] */, int64_t* covered /* [n_windows] */);
+void mm_depth_destroy(mm_depth* result);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------------------------- */
 #define MM_COMM_ID_BYTES 128

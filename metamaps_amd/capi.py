@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmetamaps_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "metamaps_hip.h")
 
 COMM_ID_BYTES = 128
+DEPTH_STATS = 5                                                     # counters per contig of mm_depth_profile before its thresholds' (the header's counter constant)
 CONS_STATS = 10                                                     # counters per contig of mm_consensus (the header's counter constant)
 VCF_WINDOW = 25                                                     # reference bytes a kept allele of mm_vcf_finish carries (the header's window constant)
 MM_ERR_ARG = -1
@@ -245,6 +246,12 @@ def lib() -> C.CDLL:
             "mm_consensus_fetch_contigs": (C.c_int, [vp, vp, vp]),
             "mm_consensus_fetch_text": (C.c_int, [vp, vp, vp, vp]),
             "mm_consensus_destroy": (None, [vp]),
+            "mm_depth_profile": (C.c_int, [vp, i64, vp, i64, vp, vp, vp, i64, C.c_int32, vp, vp]),
+            "mm_depth_sizes": (C.c_int, [vp, vp, vp, vp]),
+            "mm_depth_fetch_runs": (C.c_int, [vp, vp, vp, vp, vp]),
+            "mm_depth_fetch_contigs": (C.c_int, [vp, vp, vp, vp]),
+            "mm_depth_fetch_windows": (C.c_int, [vp, vp, vp]),
+            "mm_depth_destroy": (None, [vp]),
             "mm_comm_unique_id": (C.c_int, [C.c_char_p]),
             "mm_comm_init": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
             "mm_comm_allreduce_f64": (C.c_int, [vp, vp, i64]),
@@ -849,6 +856,33 @@ class Context:
             self.last_cons_handle = h.value                         # (what the call left in *out: None after a refusal)
             if h.value:
                 lib().mm_consensus_destroy(h)
+
+    def depth_profile(self, contig_len, iv_contig, iv_first, iv_last, window=1000, thresholds=(1, 5, 10, 30)):
+        """the depth profile of the intervals over contigs of the given lengths (mm_depth_profile): a dict with the runs (run_contig, run_start, run_end,
+        run_depth), the contigs with an interval (contig, win_off, stats with DEPTH_STATS + len(thresholds) counters each) and their windows (win_sum, win_covered)"""
+        cl, th = np.ascontiguousarray(contig_len, dtype=np.int64), np.ascontiguousarray(thresholds, dtype=np.int64)
+        ic = np.ascontiguousarray(iv_contig, dtype=np.int32)
+        i0, i1 = np.ascontiguousarray(iv_first, dtype=np.int64), np.ascontiguousarray(iv_last, dtype=np.int64)
+        assert len(ic) == len(i0) == len(i1)
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_depth_profile(self.h, len(cl), _ptr(cl), len(ic), _ptr(ic), _ptr(i0), _ptr(i1), int(window), len(th), _ptr(th), C.byref(h))
+        try:
+            self.check(st)
+            nr, nc, nw = C.c_int64(-1), C.c_int64(-1), C.c_int64(-1)
+            assert lib().mm_depth_sizes(h, C.byref(nr), C.byref(nc), C.byref(nw)) == 0
+            rc, rs, re_, rd = (np.full(nr.value, -1, dtype=np.int32), np.full(nr.value, -1, dtype=np.int64), np.full(nr.value, -1, dtype=np.int64),
+                               np.zeros(nr.value, dtype=np.uint32))
+            contig, off, stats = np.full(nc.value, -1, dtype=np.int32), np.full(nc.value + 1, -1, dtype=np.int64), np.full((nc.value, DEPTH_STATS + len(th)), -1, dtype=np.int64)
+            wsum, wcov = np.full(nw.value, -1, dtype=np.int64), np.full(nw.value, -1, dtype=np.int64)
+            assert lib().mm_depth_fetch_runs(h, _ptr(rc), _ptr(rs), _ptr(re_), _ptr(rd)) == 0
+            assert lib().mm_depth_fetch_contigs(h, _ptr(contig), _ptr(off), _ptr(stats)) == 0
+            assert lib().mm_depth_fetch_windows(h, _ptr(wsum), _ptr(wcov)) == 0
+            assert off[0] == 0 and off[-1] == nw.value
+            return dict(run_contig=rc, run_start=rs, run_end=re_, run_depth=rd, contig=contig, win_off=off, stats=stats, win_sum=wsum, win_covered=wcov)
+        finally:
+            self.last_depth_handle = h.value                        # (what the call left in *out: None after a refusal)
+            if h.value:
+                lib().mm_depth_destroy(h)
 
     # ---- communicator
     @staticmethod

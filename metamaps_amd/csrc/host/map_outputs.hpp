@@ -1,12 +1,14 @@
 // The side outputs of a batch of mapDirectly (the rows of side_files.hpp: PREFIX.editDistances, .paf, .bam) and the device calls they need, and the run's
-// pileup (PREFIX.pileup, .pileup.contigs), alleles (PREFIX.vcf), consensus (PREFIX.consensus.fa, .consensus.tsv) and modification counts (PREFIX.bedmethyl),
-// which every batch adds to.  The text and byte rules are in edit_dist.hpp, paf_out.hpp, bam_out.hpp, pileup_out.hpp, vcf_out.hpp, consensus_out.hpp and
-// mods_out.hpp, which call nothing; everything of a batch runs on the context that mapped it, the last merge and the finish of the pileup, of the alleles, of
-// the consensus and of the modification counts on the first device.
+// pileup (PREFIX.pileup, .pileup.contigs), alleles (PREFIX.vcf), consensus (PREFIX.consensus.fa, .consensus.tsv), modification counts (PREFIX.bedmethyl) and
+// depth profile (PREFIX.depth.bedgraph, .depth.windows, .depth.contigs), which every batch adds to.  The text and byte rules are in edit_dist.hpp, paf_out.hpp,
+// bam_out.hpp, pileup_out.hpp, vcf_out.hpp, consensus_out.hpp, mods_out.hpp and depth_out.hpp, which call nothing; everything of a batch runs on the context
+// that mapped it, the last merge and the finish of the pileup, of the alleles, of the consensus and of the modification counts and the depth profile on the
+// first device.
 #pragma once
 #include "bam_out.hpp"
 #include "cli_device.hpp"
 #include "consensus_out.hpp"
+#include "depth_out.hpp"
 #include "edit_dist.hpp"
 #include "mods_out.hpp"
 #include "paf_out.hpp"
@@ -175,23 +177,42 @@ void consensus_write(mm_ctx* ctx, const mm_seqset* reference, const VariantRows&
   }
   if (fclose(fa) != 0 || fclose(tsv) != 0) die("Error writing " + prefix + ".consensus.fa / .consensus.tsv");
 }
+// --depth, after the last batch of a query file: one mm_depth_profile on `ctx` over the file's intervals and the contigs' lengths, and the three files
+void depth_write(mm_ctx* ctx, const Intervals& iv, const DepthOpts& dp, const std::string& prefix, const std::vector<std::string>& cname, const std::vector<int>& clen) {
+  const std::vector<int64_t> len(clen.begin(), clen.end());
+  mm_depth* r = nullptr;
+  ck(ctx, mm_depth_profile(ctx, (int64_t)len.size(), len.data(), (int64_t)iv.contig.size(), iv.contig.data(), iv.first.data(), iv.last.data(), dp.window, dp.n_thresholds,
+                           dp.thresholds, &r), "depth profile");
+  int64_t n_runs = 0, n_contigs = 0, n_windows = 0;
+  mm_depth_sizes(r, &n_runs, &n_contigs, &n_windows);
+  std::vector<int32_t> run_contig((size_t)n_runs), contig((size_t)n_contigs); std::vector<int64_t> start((size_t)n_runs), end((size_t)n_runs); std::vector<uint32_t> depth((size_t)n_runs);
+  std::vector<int64_t> win_off((size_t)n_contigs + 1), stats((size_t)n_contigs * (size_t)(MM_DEPTH_STATS + dp.n_thresholds)), sum((size_t)n_windows), covered((size_t)n_windows);
+  mm_depth_fetch_runs(r, run_contig.data(), start.data(), end.data(), depth.data());
+  mm_depth_fetch_contigs(r, contig.data(), win_off.data(), stats.data());
+  mm_depth_fetch_windows(r, sum.data(), covered.data());
+  mm_depth_destroy(r);
+  write_or_die(prefix + ".depth.bedgraph", depth_bedgraph_text(run_contig, start, end, depth, cname));
+  write_or_die(prefix + ".depth.windows", depth_windows_text(contig, win_off, sum, covered, dp.window, cname, clen));
+  write_or_die(prefix + ".depth.contigs", depth_contigs_text(dp, contig, stats, cname, clen));
+}
 // the run's accumulators, one set per query file, and what is written from them after the last batch (every pileup before the first VCF).  The alleles are
 // accumulated (vcf_on) for --vcf and for --consensus, merged once, and written as PREFIX.vcf under --vcf alone
 struct RunVariants {
   struct File { Intervals iv; VariantAcc pile, vcf, mods; };
-  bool pileup_on = false, vcf_on = false, vcf_file = false, cons_on = false, mods_on = false;
+  bool pileup_on = false, vcf_on = false, vcf_file = false, cons_on = false, mods_on = false, depth_on = false;
   std::deque<File> files;
-  void resize(bool pileup, bool vcf, bool cons, bool mods, size_t n_files) {
-    pileup_on = pileup; vcf_on = vcf || cons; vcf_file = vcf; cons_on = cons; mods_on = mods;
-    if (pileup_on || vcf_on || mods_on) files.resize(n_files);
+  void resize(bool pileup, bool vcf, bool cons, bool mods, bool depth, size_t n_files) {
+    pileup_on = pileup; vcf_on = vcf || cons; vcf_file = vcf; cons_on = cons; mods_on = mods; depth_on = depth;
+    if (pileup_on || vcf_on || mods_on || depth_on) files.resize(n_files);
   }
   VariantAcc* pile(size_t f) { return pileup_on ? &files[f].pile : nullptr; }
   VariantAcc* vcf(size_t f) { return vcf_on ? &files[f].vcf : nullptr; }
   VariantAcc* mods(size_t f) { return mods_on ? &files[f].mods : nullptr; }
   Intervals* intervals(size_t f) { return files.empty() ? nullptr : &files[f].iv; }
-  void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const ConsOpts& co, const ModsOpts& mo, int min_base_quality,
+  void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const ConsOpts& co, const ModsOpts& mo, const DepthOpts& dp, int min_base_quality,
              int64_t cons_group_bases, const std::vector<std::string>& prefixes, const std::vector<std::string>& cname, const std::vector<int>& clen) {
     for (size_t fi = 0; pileup_on && fi < files.size(); ++fi) pileup_write(ctx, reference, files[fi].pile.rows, files[fi].iv, po, prefixes[fi], cname, clen);
+    for (size_t fi = 0; depth_on && fi < files.size(); ++fi) depth_write(ctx, files[fi].iv, dp, prefixes[fi], cname, clen);
     for (size_t fi = 0; mods_on && fi < files.size(); ++fi) mods_write(ctx, reference, files[fi].mods.rows, mo, prefixes[fi], cname);
     for (size_t fi = 0; vcf_on && fi < files.size(); ++fi) {
       merge_rows<VcfCalls>(ctx, files[fi].vcf.rows);
@@ -210,14 +231,16 @@ struct BatchSideOutputs {
   size_t pile_merge_pairs = 0;
   VariantAcc* vcf = nullptr;                                     // --vcf, --consensus: the accumulator of the batch's query file
   size_t vcf_merge_pairs = 0;
-  Intervals* iv = nullptr;                                       // --pileup, --vcf, --consensus: the contributing alignments of the batch's query file
+  Intervals* iv = nullptr;                                       // --pileup, --vcf, --consensus, --depth: the contributing alignments of the batch's query file
   int32_t min_base_quality = 0;                                  // --min-base-quality: the floor of the pileup's events and of the alleles
   VariantAcc* mods = nullptr;                                    // --mods: the accumulator of the batch's query file (the base-quality floor does not touch its counts)
   size_t mods_merge_pairs = 0;
   int32_t min_ml = 0;                                            // --mod-min-ml: the ML byte below which a call counts as failed
+  bool depth = false;                                            // --depth: the intervals alone (no accumulator, no traceback: first and last come with the distances)
 
   // while the mapping lives: d, first, last (and the runs, where .paf or .bam want them) fetched once -> the lines of .editDistances and .paf.
-  // The reads go here unless .bam needs them for SEQ, the pileup or the VCF for their mismatched and inserted bases, or --mods for their calls.
+  // The reads go here unless .bam needs them for SEQ, the pileup or the VCF for their mismatched and inserted bases, or --mods for their calls; --depth reads
+  // none of them but keeps them until from_text, which does nothing without them.
   // Nothing happens without reads (no side file was asked for).
   void from_mapping(mm_ctx* ctx, const mm_mapping* m, ReadsPtr& reads, const mm_seqset* reference, float pi, const std::vector<mm_map_record>& rec,
                     const std::vector<std::string>& names, const std::vector<int>& lens, const std::vector<int64_t>& off, const std::vector<std::string>& cname,
@@ -239,7 +262,7 @@ struct BatchSideOutputs {
     }
     edit_distance_text(al.dist.data(), al.first.data(), al.last.data(), names, off, rec, cname, out[SIDE_EDIT]);
     if (on[SIDE_PAF]) paf_text(al, names, lens, off, rec, cname, clen, out[SIDE_PAF]);
-    if (!on[SIDE_BAM] && !pile && !vcf && !mods) reads.reset();
+    if (!on[SIDE_BAM] && !pile && !vcf && !mods && !depth) reads.reset();
   }
 
   // once the lines are formatted: the batch's BAM records as BGZF members, encoded and deflated on the device, and its pileup events and alleles (all go by
@@ -251,10 +274,10 @@ struct BatchSideOutputs {
     members.clear();
     if (!rec.empty()) {
       const BamFields F = bam_fields(al.dist, rec, names, off, text);
-      if (pile || vcf || mods) {
+      if (pile || vcf || mods || depth) {
         const std::vector<uint8_t> use = pileup_use(F.flag, al.dist);
         if (mods) add_batch<ModCalls>(ctx, reads.get(), reference, F, al, use, min_ml, mods_merge_pairs, *mods);
-        if (pile || vcf) iv->add_intervals(use, F.contig, al.first, al.last);
+        if (pile || vcf || depth) iv->add_intervals(use, F.contig, al.first, al.last);
         if (pile) add_batch<PileupCalls>(ctx, reads.get(), reference, F, al, use, min_base_quality, pile_merge_pairs, *pile);
         if (vcf) add_batch<VcfCalls>(ctx, reads.get(), reference, F, al, use, min_base_quality, vcf_merge_pairs, *vcf);
       }

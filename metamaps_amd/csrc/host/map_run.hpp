@@ -61,6 +61,7 @@ struct MapRun {
   const VcfOpts vcf = vcf_options(o);                            // --vcf (implies --edit-distance): the same (vcf_out.hpp)
   const ConsOpts cons = consensus_options(o);                    // --consensus (implies --edit-distance): --vcf's accumulator (consensus_out.hpp)
   const QualOpts qual = qual_options(o);                         // --base-qualities, --min-base-quality: the batches carry the reads' qualities to the device
+  const DepthOpts depth = depth_options(o);                      // --depth (implies --edit-distance): the intervals --pileup keeps, one profile per query file (depth_out.hpp)
   const ModsOpts mods = mods_options(o);                         // --mods (implies --edit-distance): a BAM query's MM/ML groups go to the device with its reads (mods_out.hpp)
   RunVariants var;
   std::string bgzf_head;                                         // what a BGZF side file starts with: the header of every PREFIX.bam as BGZF members (the contigs are the run's)
@@ -359,8 +360,8 @@ struct MapRun {
     }
     if (place != Place::Replicated && NC == 1 && !from_index && !maxMem) die("--stream-chunks / --shard-index need --maxmemory (the chunk rule of the reference, winSketch.hpp:274-329)");
     if (edit && place != Place::Replicated)
-      die(std::string(mods.on ? "--mods" : cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : side[SIDE_PAF] ? "--paf" : "--edit-distance")
-          + " needs the whole reference resident on every device, and this index does not fit one: run without it");
+      die(std::string(depth.on ? "--depth" : mods.on ? "--mods" : cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : side[SIDE_PAF] ? "--paf"
+                      : "--edit-distance") + " needs the whole reference resident on every device, and this index does not fit one: run without it");
     for (auto& d : devs) d.idx.assign(NC, nullptr);
     thr_of.assign(NC, INT_MAX);
   }
@@ -462,7 +463,7 @@ struct MapRun {
     std::vector<mm_map_record> rec((size_t)dn->off.back());
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), rec.data(), (int64_t)rec.size()), "fetch");
     BatchSideOutputs so{side, {}, var.pile(file), sw.pileup_merge_pairs, var.vcf(file), sw.vcf_merge_pairs, var.intervals(file), qual.min_base_quality,
-                        var.mods(file), sw.mods_merge_pairs, mods.min_ml};   // one alignment for all of them
+                        var.mods(file), sw.mods_merge_pairs, mods.min_ml, depth.on};   // one alignment for all of them
     so.from_mapping(ctx, m, reads, refset[dev], pi, rec, dn->names, dn->lens, dn->off, cname, clen, dn->side);
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
@@ -775,14 +776,14 @@ struct MapRun {
     build_resident_indexes();
     mp = mm_map_params{k, w, pi, minLen};
     for (auto& ch : chunks) chunk_base.push_back(ch.first);
-    var.resize(pileup.on, vcf.on, cons.on, mods.on, prefixes.size());
+    var.resize(pileup.on, vcf.on, cons.on, mods.on, depth.on, prefixes.size());
     if (side[SIDE_BAM]) bgzf_head = bam_header_members(ctx0, cname, clen);   // (before the workers take the first device's context)
     start_reader();
     if (prewarm.joinable()) prewarm.join();
     if (place != Place::Replicated) for (auto*& c : wctx) if (c) { mm_ctx_destroy(c); c = nullptr; }   // (the other modes drive one context per device)
     if (place == Place::Replicated) run_replicated(); else run_chunk_major();
     pc.lap("8 write");
-    var.write(ctx0, refset[0], pileup, vcf, cons, mods, qual.min_base_quality, sw.cons_group_bases, prefixes, cname, clen);
+    var.write(ctx0, refset[0], pileup, vcf, cons, mods, depth, qual.min_base_quality, sw.cons_group_bases, prefixes, cname, clen);
     then_classify();
     if (!sw.full_teardown) { if (reader.th.joinable()) reader.th.join(); pc.report(); finish_fast(); }
     drop_refsets();

@@ -7,6 +7,7 @@
 //
 //   metamaps mapDirectly [--all] [--compress-output] [--edit-distance] [--paf] [--bam] [--pileup [--pileup-min-count N] [--pileup-min-frac F]] [--vcf [--vcf-min-count N] [--vcf-min-frac F]]
 //                       [--consensus [--consensus-min-depth D] [--consensus-min-frac F] [--consensus-min-called C]] [--mods LIST [--mod-min-ml T] [--mod-min-coverage N]]
+//                       [--depth [--depth-window W] [--depth-thresholds T1,T2,...]]
 //                        -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
 //   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]] [--lca T] [--genes] [--min-identity T [--refit]]
@@ -97,6 +98,19 @@
 // written 0; --min-base-quality does not touch the counts.  Every other file of the run is the file of the same run without the flag.  Refused wherever
 // --edit-distance is; the two thresholds are refused without --mods.
 //
+// --depth [--depth-window W] [--depth-thresholds T1,T2,...] (mapDirectly; not in the reference; implies --edit-distance; may be combined with every other side
+// output): also PREFIX.depth.bedgraph, PREFIX.depth.windows and PREFIX.depth.contigs, what `samtools sort` and `mosdepth` give over the PRIMARY records of
+// PREFIX.bam: the maximal runs of equal depth >= 1 (contigID start end depth, no track line), every window of W bases (default 1000, the window of
+// .EM.contigCoverage) of every contig with a primary alignment (contigID start end sumDepth covered meanDepth), and per such contig a line contigID length
+// alignments covered sumDepth meanDepth medianDepth maxDepth breadth expectedBreadth ge<T1> ... behind a # header (breadth = covered / length; expectedBreadth =
+// 1 - exp(-sumDepth / length), what a uniform spread of that depth would cover; ge<T> the positions of depth >= T, 1 to 8 ascending integers, default
+// 1,5,10,30).  Depth changes only at the alignments' ends: one mm_depth_profile call per query file on the first device, after the last batch, sorts the ends
+// and works in memory proportional to the alignments, never to the reference (csrc/mm_depth_core.hpp, DESIGN.md section 1, "Depth").  It shares the one
+// alignment call per batch and the intervals --pileup keeps.  Plain text whatever --compress-output says; an empty run writes the first two files empty and the
+// header of the third alone.  Every other file of the run is the file of the same run without the flag.  Refused wherever --edit-distance is; the two
+// options are refused without --depth (host/depth_out.hpp).  Not provided: zero-depth runs, per-strand depth, a mapping-quality filter, a quality-aware
+// depth, bigWig, depth from secondary mappings, the flag outside mapDirectly.
+//
 // --base-qualities, --min-base-quality Q (mapDirectly; not in the reference; samtools mpileup's -Q): the run keeps the base qualities of its queries (the quality
 // line of a FASTQ record in any of the text forms, the qual field of a BAM record; a FASTA record and a BAM record without have none) and uploads them beside
 // the bases, one byte per base (mm_seqset_add_qual; a quality character outside '!'..'~' ends the run).  --bam then writes every record's QUAL (reversed for
@@ -162,7 +176,7 @@ Options parse(int argc, char** argv) {
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
     if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" ||
-        a == "--bam" || a == "--pileup" || a == "--vcf" || a == "--consensus" || a == "--genes" || a == "--refit" || a == "--base-qualities") { o.v[a.substr(2)] = "1"; continue; }
+        a == "--bam" || a == "--pileup" || a == "--vcf" || a == "--consensus" || a == "--depth" || a == "--genes" || a == "--refit" || a == "--base-qualities") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
@@ -195,6 +209,11 @@ Options parse(int argc, char** argv) {
                    "         (modkit's 18 columns, no header): per reference position and strand the primary alignments whose matched base carries a modified, canonical,\n"
                    "         other or failed call of each code of LIST (1 to 4 items like C+m,C+h,A+a,C+21839), counted on the device; a call fails below the ML byte T\n"
                    "         (default 204), a row needs N (default 1) valid calls; may be combined with the other outputs; not with --hpc, --shard-index, --stream-chunks\n"
+                   "  --depth [--depth-window W] [--depth-thresholds T1,T2,...]  (mapDirectly) implies --edit-distance and also writes PREFIX.depth.bedgraph (contigID start end\n"
+                   "         depth: the runs of equal depth >= 1 of the primary alignments), PREFIX.depth.windows (contigID start end sumDepth covered meanDepth per window of W,\n"
+                   "         default 1000) and PREFIX.depth.contigs (per contig mean, median and maximal depth, breadth, the breadth a uniform spread would give and the\n"
+                   "         positions of depth >= T, default 1,5,10,30), computed on the device from the alignments' ends alone; may be combined with the other outputs;\n"
+                   "         not with --hpc, --shard-index, --stream-chunks\n"
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
                    "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
                    "  --genes  (classify, mapDirectly --then-classify) gene-level analysis against DB_annotations.txt and DB_proteins.faa.annotated of the DB:\n"
@@ -293,6 +312,7 @@ int main(int argc, char** argv) {
   const VcfOpts vcf_opts = vcf_options(o);                      // (the same)
   const ConsOpts cons_opts = consensus_options(o);              // (the same)
   const ModsOpts mods_opts = mods_options(o);                   // (the same)
+  const DepthOpts depth_opts = depth_options(o);                // (the same)
   if (o.v.count("base-qualities") || o.v.count("min-base-quality")) {   // (refused under the flag's own name wherever --edit-distance is, before any device work)
     const std::string flag = o.v.count("min-base-quality") ? "--min-base-quality" : "--base-qualities";
     (void)qual_options(o);                                       // (the value and what uses it; MapRun reads them again)
@@ -300,9 +320,10 @@ int main(int argc, char** argv) {
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: a homopolymer-compressed read has no per-base qualities");
     if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");
   }
-  if (o.v.count("paf") || o.v.count("bam") || pileup_opts.on || vcf_opts.on || cons_opts.on || mods_opts.on) o.v["edit-distance"] = "1";   // (all six imply it and inherit its refusals)
+  if (o.v.count("paf") || o.v.count("bam") || pileup_opts.on || vcf_opts.on || cons_opts.on || mods_opts.on || depth_opts.on)
+    o.v["edit-distance"] = "1";                                  // (all seven imply it and inherit its refusals)
   if (o.v.count("edit-distance")) {                              // (refused before any device work)
-    const std::string flag = mods_opts.on ? "--mods" : cons_opts.on ? "--consensus" : vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup" : o.v.count("bam") ? "--bam"
+    const std::string flag = depth_opts.on ? "--depth" : mods_opts.on ? "--mods" : cons_opts.on ? "--consensus" : vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup" : o.v.count("bam") ? "--bam"
                              : o.v.count("paf") ? "--paf" : "--edit-distance";
     if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reference does not stay on the device");

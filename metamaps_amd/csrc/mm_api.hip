@@ -17,6 +17,8 @@
 #include "mm_mods.hpp"
 #include "mm_cons.hpp"
 #include "mm_cons_core.hpp"
+#include "mm_depth.hpp"
+#include "mm_depth_core.hpp"
 #include "mm_seq.hpp"
 #include "mm_codec.hpp"
 #include <chrono>
@@ -986,6 +988,41 @@ int mm_consensus_fetch_text(const struct mm_consensus* r, int32_t* contig, int64
   return MM_OK;
 }
 void mm_consensus_destroy(struct mm_consensus* r) { delete r; }
+
+struct mm_depth { mm::DepthResult r; };                            // (host memory only: runs, counters and windows)
+static_assert(MM_DEPTH_STATS == mmdp::STATS, "the header's counters are the definition's");
+int mm_depth_profile(mm_ctx* ctx, int64_t n_contigs, const int64_t* contig_len, int64_t n_iv, const int32_t* iv_contig, const int64_t* iv_first, const int64_t* iv_last, int64_t window,
+                     int32_t n_thresholds, const int64_t* thresholds, mm_depth** out) {
+  if (!ctx || !out) return refused(out);
+  return created(ctx, out, [&](mm_depth& r) {
+    mm::depth_profile_run(ctx, mm::DepthIn{n_contigs, contig_len, n_iv, iv_contig, iv_first, iv_last, window, n_thresholds, thresholds}, &r.r);
+  });
+}
+int mm_depth_sizes(const mm_depth* r, int64_t* n_runs, int64_t* n_contigs, int64_t* n_windows) {
+  if (!r || !n_runs || !n_contigs || !n_windows) return MM_ERR_ARG;
+  *n_runs = (int64_t)r->r.run_contig.size(); *n_contigs = (int64_t)r->r.contig.size(); *n_windows = (int64_t)r->r.win_sum.size();
+  return MM_OK;
+}
+int mm_depth_fetch_runs(const mm_depth* r, int32_t* contig, int64_t* start, int64_t* end, uint32_t* depth) {
+  if (!r || (!r->r.run_contig.empty() && (!contig || !start || !end || !depth))) return MM_ERR_ARG;
+  const size_t k = r->r.run_contig.size();
+  if (k) { memcpy(contig, r->r.run_contig.data(), k * 4); memcpy(start, r->r.run_start.data(), k * 8); memcpy(end, r->r.run_end.data(), k * 8); memcpy(depth, r->r.run_depth.data(), k * 4); }
+  return MM_OK;
+}
+int mm_depth_fetch_contigs(const mm_depth* r, int32_t* contig, int64_t* win_off, int64_t* stats) {
+  if (!r || !win_off || (!r->r.contig.empty() && (!contig || !stats))) return MM_ERR_ARG;
+  const size_t k = r->r.contig.size();
+  memcpy(win_off, r->r.win_off.data(), (k + 1) * 8);
+  if (k) { memcpy(contig, r->r.contig.data(), k * 4); memcpy(stats, r->r.stats.data(), r->r.stats.size() * 8); }
+  return MM_OK;
+}
+int mm_depth_fetch_windows(const mm_depth* r, int64_t* sum, int64_t* covered) {
+  if (!r || (!r->r.win_sum.empty() && (!sum || !covered))) return MM_ERR_ARG;
+  const size_t k = r->r.win_sum.size();
+  if (k) { memcpy(sum, r->r.win_sum.data(), k * 8); memcpy(covered, r->r.win_covered.data(), k * 8); }
+  return MM_OK;
+}
+void mm_depth_destroy(mm_depth* r) { delete r; }
 
 // ---- communicator -------------------------------------------------------------------------------------
 int mm_comm_unique_id(char id[MM_COMM_ID_BYTES]) {

@@ -129,7 +129,6 @@ void merge_run(mm_ctx* ctx, int64_t n, const uint64_t* w0, const uint64_t* w1, c
 
 int contig_bits(int64_t n_contigs) { return bits_for((uint64_t)std::max<int64_t>(n_contigs - 1, 0)); }
 
-namespace {
 // The interval keys of n > 0 alignments (host arrays) on the device: starts ascending with end_of[i] the end that belongs to starts[i], ends ascending.
 void sorted_interval_keys(DBuf<uint8_t>& tmp, const FinishIn& in, int bits, hipStream_t st, SortedIntervals& iv) {
   const size_t v = (size_t)in.n_iv;
@@ -140,7 +139,6 @@ void sorted_interval_keys(DBuf<uint8_t>& tmp, const FinishIn& in, int bits, hipS
   sort_keys(tmp, d_ekey.p, iv.ends.p, v, 0, bits, st);
   MM_HIP(mm::stream_sync(st));                                     // (the buffers of this scope)
 }
-}  // namespace
 
 bool finish_kept(mm_ctx* ctx, const mm_seqset* ref, const FinishIn& in, const char* who, const std::function<void()>& check_keys, const std::function<void(const KeptDev&)>& compact,
                  StageClock<3>& clk, SortedIntervals* iv, KeptRows* out) {

@@ -33,6 +33,9 @@ int contig_bits(int64_t n_contigs);                               // the bits th
 // The interval keys (mmp::interval_key) of n > 0 alignments given in host arrays: starts ascending with end_of[i] the end that belongs to starts[i], ends
 // ascending; each buffer holds n words.  bits: 32 + contig_bits of the reference.
 struct SortedIntervals { DBuf<uint64_t> starts, end_of, ends; };
+struct FinishIn;
+// in.n_iv > 0 intervals, already checked against their contigs, uploaded and sorted into iv, whose buffers the caller has allocated (mm_depth.hip shares it)
+void sorted_interval_keys(DBuf<uint8_t>& tmp, const FinishIn& in, int bits, hipStream_t st, SortedIntervals& iv);
 
 // a merged table, the intervals of the contributing alignments and the two thresholds, as mm_pileup_finish and mm_vcf_finish take them (w1 null: one-word keys)
 struct FinishIn {

@@ -10,10 +10,15 @@ Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes pr
        python tools/edit_kernel_stats.py --consensus [n_reads]        (writes profiles/consensus_stats.txt)
        python tools/edit_kernel_stats.py --qualities [n_reads] [--min-base-quality Q]   (writes profiles/qual_stats.txt)
        python tools/edit_kernel_stats.py --mods [n_reads]   (writes profiles/mods_stats.txt)
+       python tools/edit_kernel_stats.py --depth [n_reads]  (writes profiles/depth_stats.txt)
 --mods: the batch fetched to the host and uploaded again without and with seeded modification groups (C+m? and A+a. on every C and A, ML uniform in 0 .. 255,
 independent of the bases): the upload's wall time both ways with the staged bytes (the MM_MODS_TIMING plane line), then in the same process mm_pileup_events
 and mm_mod_events twice each on the same alignments (the MM_PILEUP_TIMING and MM_MODS_TIMING stage lines), mm_mod_merge and mm_mod_finish with the table's
 size.  Synthetic tags say nothing about real methylation.  One run is one run.
+--depth: the batch through mm_mapping_edit_distances (the intervals need no traceback), then twice through mm_depth_profile (mm_depth_core.hpp, mm_depth.hip)
+at the default window and thresholds and once at W = 1 000 000: the MM_DEPTH_TIMING stage lines, the wall time of each call with its copies, the runs, listed
+contigs and windows, beside mm_pileup_finish over an empty table and the same intervals (the MM_PILEUP_TIMING finish line), whose three per-contig sums the
+profile must repeat.  One run is one run.
 --qualities: the batch fetched to the host and uploaded again as a parser would hand it over, without and with seeded qualities (uniform in 2 .. 40 per base,
 independent of the bases): the upload's wall time both ways, then in the same process mm_bam_encode on the set without and with the plane, and
 mm_pileup_events_q and mm_vcf_events_q at floor 0 and at Q (default 20) with the rows of both tables at each floor.  Synthetic qualities do not correlate with
@@ -259,6 +264,39 @@ def child_pileup(n_reads, vcf=False, cons=False):
     M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
 
 
+def child_depth(n_reads):
+    from metamaps_amd import capi
+    ctx = capi.Context(0)
+    ref = ctx.synth_reference(seed=20260928, n_species=25, strains_per_species=4, genome_len=2_200_000, strain_divergence=0.02, genus_divergence=0.2)
+    w = capi.lib().mm_recommended_window(1e-3, K, PI, 1000, ref.total_bases)
+    idx = ctx.index(ref, K, w)
+    reads, _ = ctx.synth_reads(ref, seed=1000, n_reads=n_reads, read_len=READ_LEN, read_len_min=0, sub_rate=0.04, ins_rate=0.03, del_rate=0.05, frac_random=0.05, n_abundant=100)
+    M = ctx.map_batch(idx, reads, K, w, pi=PI)
+    M.keep_best(K)
+    off, rec = M.fetch()
+    n = len(rec)
+    print(f"{n_reads} reads of {READ_LEN} bases against {ref.total_bases} reference bases (k {K}, w {w}, pi {PI}): {n} best mappings", flush=True)
+    dist, first, last = ctx.mapping_edit_distances(M, reads, ref, PI, n)
+    al = dist >= 0
+    ic, i0, i1, clen = rec["ref_contig"][al], first[al], last[al], ref.lengths()
+    print(f"{int(al.sum())} intervals on {len(np.unique(ic))} of {len(clen)} contigs, {int((i1 - i0 + 1).sum())} aligned reference bases", flush=True)
+    t0 = time.perf_counter()
+    fin = ctx.pileup_finish(ref, np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint32), ic, i0, i1)
+    dt = time.perf_counter() - t0
+    print(f"mm_pileup_finish over no entries and these intervals: {1e3 * dt:.1f} ms wall with the copies", flush=True)
+    for rep, window in enumerate((1000, 1000, 1_000_000)):
+        t0 = time.perf_counter()
+        got = ctx.depth_profile(clen, ic, i0, i1, window=window)
+        dt = time.perf_counter() - t0
+        listed = got["contig"]
+        assert np.array_equal(got["stats"][:, 0], fin["alignments"][listed]) and np.array_equal(got["stats"][:, 1], fin["covered"][listed]) and np.array_equal(got["stats"][:, 2], fin["sum_depth"][listed])
+        assert int(got["win_sum"].sum()) == int(fin["sum_depth"].sum()) and int(got["win_covered"].sum()) == int(fin["covered"].sum())
+        print(f"mm_depth_profile call {rep} (window {window}, thresholds 1,5,10,30): {1e3 * dt:.1f} ms wall with the copies and the Python wrapper, {len(got['run_contig'])} runs, "
+              f"{len(listed)} contigs, {len(got['win_sum'])} windows, maximal depth {int(got['run_depth'].max())}, {int(got['stats'][:, 1].sum())} positions covered, "
+              f"summed depth {int(got['stats'][:, 2].sum())}; alignments, covered and sumDepth equal mm_pileup_finish's", flush=True)
+    M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
+
+
 def child_qual(n_reads, floor):
     from metamaps_amd import capi
     ctx = capi.Context(0)
@@ -408,6 +446,19 @@ def main():
         if p.returncode != 0:
             sys.exit(p.returncode)
         with open(os.path.join(ROOT, "profiles", "mods_stats.txt"), "w") as f:
+            f.write(text)
+        return None
+    if len(sys.argv) > 1 and sys.argv[1] == "--child-depth":
+        return child_depth(int(sys.argv[2]))
+    if len(sys.argv) > 1 and sys.argv[1] == "--depth":
+        n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-depth", str(n_reads)], env=dict(os.environ, MM_PILEUP_TIMING="1", MM_DEPTH_TIMING="1"), stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, timeout=1100)
+        text = f"tools/edit_kernel_stats.py --depth {n_reads}: one batch of {n_reads} reads, best mappings only; one run\n" + p.stdout.decode()
+        print(text)
+        if p.returncode != 0:
+            sys.exit(p.returncode)
+        with open(os.path.join(ROOT, "profiles", "depth_stats.txt"), "w") as f:
             f.write(text)
         return None
     if len(sys.argv) > 1 and sys.argv[1] == "--child-qual":
