@@ -32,7 +32,7 @@ extern "C" {
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
                             *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances,
-                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_*, mm_pileup_*, mm_vcf_*, mm_consensus*, mm_seqset_*_mods, mm_mod_*,
+                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_* (mm_bam_encode_sorted, mm_bam_fetch_records, mm_bam_sorter_*), mm_pileup_*, mm_vcf_*, mm_consensus*, mm_seqset_*_mods, mm_mod_*,
                             *    mm_depth_* (additions to 6) */
 
 typedef enum {
@@ -55,6 +55,7 @@ typedef struct mm_em mm_em;            /* EM state (mappings x taxa) resident in
 typedef struct mm_gzip mm_gzip;        /* a plain gzip stream being inflated on a context's device */
 typedef struct mm_alignment mm_alignment;  /* base-level alignments (CIGAR runs) of a batch of jobs, in host memory */
 typedef struct mm_bam mm_bam;          /* BGZF members holding BAM records of a batch of jobs, in host memory */
+typedef struct mm_bam_sorter mm_bam_sorter;  /* sorted runs of BAM records being merged into one coordinate-sorted stream on a context's device */
 typedef struct mm_pileup mm_pileup;    /* a table of (key, count) pileup events, unique keys ascending, in host memory */
 typedef struct mm_pileup_result mm_pileup_result;  /* the kept sites and the per-contig coverage of a run's pileup, in host memory */
 typedef struct mm_vcf mm_vcf;          /* a table of (w0, w1, count) alleles, unique keys ascending, in host memory */
@@ -560,7 +561,48 @@ int mm_bam_encode(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* referenc
                   int64_t group_bytes, mm_bam** out);
 int mm_bam_sizes(const mm_bam* bam, int64_t* n_records, int64_t* raw_bytes, int64_t* bgzf_bytes);
 int mm_bam_fetch(const mm_bam* bam, uint8_t* bgzf /* [bgzf_bytes] */);
+/* mm_bam_encode with the records of the call in ascending (contig, first, job index): a sorted run of a coordinate sort (DESIGN.md section 1,
+ * "Sorted runs").  The same arguments, rules and refusals (the messages start with "mm_bam_encode_sorted"); every record is byte for byte the one
+ * mm_bam_encode writes for its job.  The order is a stable radix sort of (contig << 32 | first, job) on the device; groups are cut along that order. */
+int mm_bam_encode_sorted(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs,
+                         const int32_t* read, const int32_t* strand, const int32_t* contig,
+                         const int32_t* dist, const int64_t* first,
+                         const int64_t* op_off /* [n_jobs + 1] */, const uint32_t* ops,
+                         const uint16_t* flag, const uint8_t* mapq,
+                         const int64_t* name_off /* [n_jobs + 1] */, const char* names,
+                         int64_t group_bytes, mm_bam** out);
+/* The records of either encoder in the order of the inflated stream: record i belongs to job job[i] and lies at [raw_off[i], raw_off[i + 1]) of the
+ * inflated bytes; raw_off[0] = 0 and raw_off[n_records] = raw_bytes. */
+int mm_bam_fetch_records(const mm_bam* bam, int64_t* job /* [n_records] */, int64_t* raw_off /* [n_records + 1] */);
 void mm_bam_destroy(mm_bam* bam);
+
+/* The coordinate sort of BAM records: sorted runs (mm_bam_encode_sorted's members, one run per call) merged on the context's device into one stream of
+ * BGZF members, and its BAI index ("Sorted BAM"; the definitions: csrc/mm_bam_sort_core.hpp).  The sorter never looks inside a
+ * record: a record is raw_off[i + 1] - raw_off[i] bytes with the key (ref_id, pos) and the interval [pos, end), end = pos + max(1, reference span).
+ *   create   ref_len: the contigs' lengths, each below 2^29 (BAI holds no coordinate beyond: MM_ERR_ARG).  window_bytes: the bytes of output made at
+ *            a time, a multiple of 65280 up to 255 MiB; 0 is 255 MiB.  Device memory: two windows and two members per run, 40 bytes per record.
+ *   add_run  the run's members back to back; they stay the caller's and must live until destroy.  raw_off: the records' offsets in the run's inflated
+ *            bytes.  MM_ERR_ARG naming the run and the record: raw_off that does not start at 0, does not rise or does not end at the members' ISIZE sum;
+ *            ref_id outside [0, n_ref); pos < 0; end not behind pos or past the contig's end; a run that is not ascending by (ref_id, pos).
+ *            MM_ERR_DATA: a BSIZE chain that breaks.
+ *   plan     after the last run: the number of windows and the stream's bytes.  The order is ascending (ref_id, pos), then run, then index in the run.
+ *   window   w = 0, 1, ... in order (MM_ERR_STATE otherwise): the members of output bytes [w W, (w + 1) W), each of 65280 inflated bytes but the
+ *            stream's last, fetched with mm_bam_sorter_fetch.  The members of all windows back to back do not depend on window_bytes.
+ *            MM_ERR_DATA naming the run and the member: a member that does not inflate.
+ *   index    after the last window: the bytes of the .bai for a file that holds header_bytes bytes of header members, the windows' members and the
+ *            end-of-file block (the byte after the stream's last lies in that block at offset 0); fetched with mm_bam_sorter_fetch.  Per
+ *            reference: the bins ascending, a bin's chunks the maximal runs of records that are neighbours in the file and share the bin, [vs of the
+ *            first, ve of the last]; pseudo-bin 37450 with (vs of the reference's first record, ve of its last) and (its records, 0); the linear
+ *            index of 1 + ((largest end - 1) >> 14) windows, window w holding the vs of the first record with pos < (w + 1) 2^14 and end > w 2^14,
+ *            or else the next window's value; a reference without records has n_bin = n_intv = 0.  n_no_coor = 0 ends the file. */
+int mm_bam_sorter_create(mm_ctx* ctx, int32_t n_ref, const int32_t* ref_len, int64_t window_bytes, mm_bam_sorter** out);
+int mm_bam_sorter_add_run(mm_bam_sorter* s, const uint8_t* bgzf, int64_t bgzf_bytes, int64_t n_records, const int64_t* raw_off /* [n_records + 1] */,
+                          const int32_t* ref_id, const int32_t* pos, const int32_t* end);
+int mm_bam_sorter_plan(mm_bam_sorter* s, int64_t* n_windows, int64_t* stream_bytes);
+int mm_bam_sorter_window(mm_bam_sorter* s, int64_t w, int64_t* bgzf_bytes);
+int mm_bam_sorter_index(mm_bam_sorter* s, int64_t header_bytes, int64_t* bai_bytes);
+int mm_bam_sorter_fetch(const mm_bam_sorter* s, uint8_t* out /* the bytes of the last window or index */);
+void mm_bam_sorter_destroy(mm_bam_sorter* s);
 
 /* The pileup of aligned jobs: what differs from the reference, counted per column on the context's device ("Pileup"; the
  * definition: csrc/mm_pileup_core.hpp).  A job contributes where use[i] != 0 and dist[i] >= 0.  Walking its runs from r = first, i = 0 in the oriented

@@ -208,6 +208,15 @@ def lib() -> C.CDLL:
             "mm_alignment_fetch": (C.c_int, [vp, vp, vp, vp, vp, vp]),
             "mm_alignment_destroy": (None, [vp]),
             "mm_bam_encode": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+            "mm_bam_encode_sorted": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+            "mm_bam_fetch_records": (C.c_int, [vp, vp, vp]),
+            "mm_bam_sorter_create": (C.c_int, [vp, C.c_int32, vp, i64, vp]),
+            "mm_bam_sorter_add_run": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp]),
+            "mm_bam_sorter_plan": (C.c_int, [vp, vp, vp]),
+            "mm_bam_sorter_window": (C.c_int, [vp, i64, vp]),
+            "mm_bam_sorter_index": (C.c_int, [vp, i64, vp]),
+            "mm_bam_sorter_fetch": (C.c_int, [vp, vp]),
+            "mm_bam_sorter_destroy": (None, [vp]),
             "mm_bam_sizes": (C.c_int, [vp, vp, vp, vp]),
             "mm_bam_fetch": (C.c_int, [vp, vp]),
             "mm_bam_destroy": (None, [vp]),
@@ -635,6 +644,20 @@ class Context:
     def bam_encode(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, flag, mapq, names, group_bytes=0):
         """BAM records of aligned jobs as BGZF members (mm_bam_encode).  names: one bytes object per job.  Returns (members back to back as bytes,
         number of records, raw bytes of the records)."""
+        return self._bam_encode(lib().mm_bam_encode, reads, reference, read, strand, contig, dist, first, op_off, ops, flag, mapq, names, group_bytes)[:3]
+
+    def bam_encode_sorted(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, flag, mapq, names, group_bytes=0):
+        """bam_encode with the records in ascending (contig, first, job) (mm_bam_encode_sorted): the same triple"""
+        return self._bam_encode(lib().mm_bam_encode_sorted, reads, reference, read, strand, contig, dist, first, op_off, ops, flag, mapq, names, group_bytes)[:3]
+
+    def bam_records(self, reads: "SeqSet", reference: "SeqSet", sorted=False, **arrays):
+        """bam_encode (sorted: bam_encode_sorted) of the arrays with the records' places (mm_bam_fetch_records): (members, job of every record in stream
+        order, the records' offsets in the inflated stream, one more than records)"""
+        data, _, _, job, raw_off = self._bam_encode(lib().mm_bam_encode_sorted if sorted else lib().mm_bam_encode, reads, reference, **arrays)
+        return data, job, raw_off
+
+    def _bam_encode(self, entry, reads, reference, read, strand, contig, dist, first, op_off, ops, flag, mapq, names, group_bytes=0):
+        """one of the two encoders: (members, records, raw bytes, job per record, offset per record and the end)"""
         rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
         fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
         op, fl, mq = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(flag, dtype=np.uint16), np.ascontiguousarray(mapq, dtype=np.uint8)
@@ -644,15 +667,17 @@ class Context:
         np.cumsum([len(x) for x in names], out=no[1:])
         text = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8).copy()
         h = C.c_void_p(0xDEAD)                                      # (the call sets it, to NULL on an error)
-        st = lib().mm_bam_encode(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(fl), _ptr(mq), _ptr(no),
-                                 _ptr(text), int(group_bytes), C.byref(h))
+        st = entry(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(fl), _ptr(mq), _ptr(no),
+                   _ptr(text), int(group_bytes), C.byref(h))
         try:
             self.check(st)
             nr, raw, nb = C.c_int64(-1), C.c_int64(-1), C.c_int64(-1)
             assert lib().mm_bam_sizes(h, C.byref(nr), C.byref(raw), C.byref(nb)) == 0
             out = np.zeros(max(nb.value, 1), dtype=np.uint8)
             assert lib().mm_bam_fetch(h, _ptr(out)) == 0
-            return out[:nb.value].tobytes(), nr.value, raw.value
+            job, raw_off = np.full(max(nr.value, 1), -1, dtype=np.int64), np.full(nr.value + 1, -1, dtype=np.int64)
+            assert lib().mm_bam_fetch_records(h, _ptr(job), _ptr(raw_off)) == 0
+            return out[:nb.value].tobytes(), nr.value, raw.value, job[:nr.value], raw_off
         finally:
             self.last_bam_handle = h.value                          # (what the call left in *out: None after a refusal)
             if h.value:
@@ -1018,6 +1043,55 @@ class HpcMap:
         if self.h:
             lib().mm_hpc_map_destroy(self.h)
             self.h = None
+
+
+class BamSorter:
+    """sorted runs of BAM records merged into one coordinate-sorted stream of BGZF members, and its BAI (mm_bam_sorter_*)"""
+    def __init__(self, ctx: Context, ref_len, window_bytes: int = 0):
+        self.ctx, self.keep = ctx, []
+        rl = np.ascontiguousarray(ref_len, dtype=np.int32)
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_bam_sorter_create(ctx.h, len(rl), _ptr(rl), int(window_bytes), C.byref(h))
+        self.h = h if st == 0 else None
+        ctx.check(st)
+
+    def add_run(self, bgzf: bytes, raw_off, ref_id, pos, end):
+        """a run's members (bytes, an mmap or any buffer: not copied, kept alive here until close) and its records' offsets and keys"""
+        buf = np.frombuffer(bgzf, dtype=np.uint8) if len(bgzf) else np.zeros(1, dtype=np.uint8)
+        ro = np.ascontiguousarray(raw_off, dtype=np.int64)
+        rf, ps, en = (np.ascontiguousarray(x, dtype=np.int32) for x in (ref_id, pos, end))
+        assert len(ro) == len(rf) + 1 and len(rf) == len(ps) == len(en)
+        self.keep.append(buf)
+        self.ctx.check(lib().mm_bam_sorter_add_run(self.h, _ptr(buf), len(bgzf), len(rf), _ptr(ro), _ptr(rf), _ptr(ps), _ptr(en)))
+
+    def plan(self):
+        """(number of windows, bytes of the sorted stream)"""
+        nw, nb = C.c_int64(-1), C.c_int64(-1)
+        self.ctx.check(lib().mm_bam_sorter_plan(self.h, C.byref(nw), C.byref(nb)))
+        return nw.value, nb.value
+
+    def _product(self, n: int) -> bytes:
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        self.ctx.check(lib().mm_bam_sorter_fetch(self.h, _ptr(out)))
+        return out[:n].tobytes()
+
+    def window(self, w: int) -> bytes:
+        """the members of window w"""
+        n = C.c_int64(-1)
+        self.ctx.check(lib().mm_bam_sorter_window(self.h, int(w), C.byref(n)))
+        return self._product(n.value)
+
+    def index(self, header_bytes: int) -> bytes:
+        """the .bai of header members of header_bytes bytes + the windows' members + the end-of-file block"""
+        n = C.c_int64(-1)
+        self.ctx.check(lib().mm_bam_sorter_index(self.h, int(header_bytes), C.byref(n)))
+        return self._product(n.value)
+
+    def close(self):
+        if self.h:
+            lib().mm_bam_sorter_destroy(self.h)
+            self.h = None
+        self.keep = []
 
 
 class Index:

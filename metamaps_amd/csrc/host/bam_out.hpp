@@ -1,7 +1,8 @@
 // mapDirectly --bam (implies --edit-distance; not in the reference): PREFIX.bam, one BAM record (SAM/BAM specification v1.6) per ALIGNED line of PREFIX in
 // that order: the lines that have a PAF line under --paf.  The file is BGZF throughout: the header's members, then every batch's, then the 28-byte
 // end-of-file block (side_files.hpp).
-//   header    BAM\1, "@HD VN:1.6 SO:unsorted GO:query" (a read's records are consecutive), one @SQ per contig in the reference's order with the contig ID
+//   header    BAM\1, "@HD VN:1.6 SO:unsorted GO:query" (a read's records are consecutive;
+//             "@HD VN:1.6 SO:coordinate" for PREFIX.sorted.bam: bam_sort_out.hpp), one @SQ per contig in the reference's order with the contig ID
 //             as field 6 of PREFIX has it, "@PG ID:metamaps PN:metamaps" (no command line: the file is a function of the inputs), the binary reference
 //             list in the same order.  Built here, deflated by mm_bgzf_deflate on the first device (map_outputs.hpp).
 //   records   encoded and deflated on the device that mapped the batch, from the alignment the PAF path fetched (mm_bam_encode, csrc/mm_bam_core.hpp;
@@ -22,8 +23,8 @@ namespace {
 void bam_put32(std::string& s, int32_t v) { for (int k = 0; k < 4; ++k) s += (char)((uint32_t)v >> (8 * k)); }
 
 // the inflated header of PREFIX.bam
-std::string bam_header(const std::vector<std::string>& cname, const std::vector<int>& clen) {
-  std::string text = "@HD\tVN:1.6\tSO:unsorted\tGO:query\n";
+std::string bam_header(const std::vector<std::string>& cname, const std::vector<int>& clen, bool sorted = false) {   // sorted: PREFIX.sorted.bam's first line
+  std::string text = sorted ? "@HD\tVN:1.6\tSO:coordinate\n" : "@HD\tVN:1.6\tSO:unsorted\tGO:query\n";
   for (size_t c = 0; c < cname.size(); ++c) { text += "@SQ\tSN:"; text += cname[c]; text += "\tLN:"; append_int(text, clen[c]); text += '\n'; }
   text += "@PG\tID:metamaps\tPN:metamaps\n";
   std::string h("BAM\1", 4);

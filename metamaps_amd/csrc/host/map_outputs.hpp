@@ -6,6 +6,7 @@
 // first device.
 #pragma once
 #include "bam_out.hpp"
+#include "bam_sort_out.hpp"
 #include "cli_device.hpp"
 #include "consensus_out.hpp"
 #include "depth_out.hpp"
@@ -201,8 +202,11 @@ struct RunVariants {
   struct File { Intervals iv; VariantAcc pile, vcf, mods; };
   bool pileup_on = false, vcf_on = false, vcf_file = false, cons_on = false, mods_on = false, depth_on = false;
   std::deque<File> files;
-  void resize(bool pileup, bool vcf, bool cons, bool mods, bool depth, size_t n_files) {
+  SortedBams sorted;                                             // --bam-sorted: the runs of every query file (bam_sort_out.hpp)
+  void resize(bool pileup, bool vcf, bool cons, bool mods, bool depth, bool bam_sorted, size_t n_files) {
     pileup_on = pileup; vcf_on = vcf || cons; vcf_file = vcf; cons_on = cons; mods_on = mods; depth_on = depth;
+    sorted.on = bam_sorted;
+    if (bam_sorted) sorted.files.resize(n_files);
     if (pileup_on || vcf_on || mods_on || depth_on) files.resize(n_files);
   }
   VariantAcc* pile(size_t f) { return pileup_on ? &files[f].pile : nullptr; }
@@ -210,7 +214,7 @@ struct RunVariants {
   VariantAcc* mods(size_t f) { return mods_on ? &files[f].mods : nullptr; }
   Intervals* intervals(size_t f) { return files.empty() ? nullptr : &files[f].iv; }
   void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const ConsOpts& co, const ModsOpts& mo, const DepthOpts& dp, int min_base_quality,
-             int64_t cons_group_bases, const std::vector<std::string>& prefixes, const std::vector<std::string>& cname, const std::vector<int>& clen) {
+             int64_t cons_group_bases, int64_t bam_sort_window, const std::vector<std::string>& prefixes, const std::vector<std::string>& cname, const std::vector<int>& clen) {
     for (size_t fi = 0; pileup_on && fi < files.size(); ++fi) pileup_write(ctx, reference, files[fi].pile.rows, files[fi].iv, po, prefixes[fi], cname, clen);
     for (size_t fi = 0; depth_on && fi < files.size(); ++fi) depth_write(ctx, files[fi].iv, dp, prefixes[fi], cname, clen);
     for (size_t fi = 0; mods_on && fi < files.size(); ++fi) mods_write(ctx, reference, files[fi].mods.rows, mo, prefixes[fi], cname);
@@ -218,6 +222,11 @@ struct RunVariants {
       merge_rows<VcfCalls>(ctx, files[fi].vcf.rows);
       if (vcf_file) vcf_write(ctx, reference, files[fi].vcf.rows, files[fi].iv, vo, min_base_quality, prefixes[fi], cname, clen);
       if (cons_on) consensus_write(ctx, reference, files[fi].vcf.rows, files[fi].iv, co, cons_group_bases, prefixes[fi], cname, clen);
+    }
+    if (sorted.on) {
+      std::string head;
+      bgzf_members(ctx, bam_header(cname, clen, true), head, "deflate the sorted BAM header");
+      for (size_t fi = 0; fi < sorted.files.size(); ++fi) sorted_bam_write(ctx, sorted.files[fi], prefixes[fi], head, clen, bam_sort_window);
     }
   }
 };
@@ -237,6 +246,7 @@ struct BatchSideOutputs {
   size_t mods_merge_pairs = 0;
   int32_t min_ml = 0;                                            // --mod-min-ml: the ML byte below which a call counts as failed
   bool depth = false;                                            // --depth: the intervals alone (no accumulator, no traceback: first and last come with the distances)
+  SortedRun* sorted = nullptr;                                   // --bam-sorted: the batch's sorted run (bam_sort_out.hpp)
 
   // while the mapping lives: d, first, last (and the runs, where .paf or .bam want them) fetched once -> the lines of .editDistances and .paf.
   // The reads go here unless .bam needs them for SEQ, the pileup or the VCF for their mismatched and inserted bases, or --mods for their calls; --depth reads
@@ -247,7 +257,7 @@ struct BatchSideOutputs {
                     const std::vector<int>& clen, SideBytes& out) {
     if (!reads) return;
     const size_t n = rec.size();
-    if (on[SIDE_PAF] || on[SIDE_BAM] || pile || vcf || mods) {
+    if (on[SIDE_PAF] || on[SIDE_BAM] || sorted || pile || vcf || mods) {
       mm_alignment* a = nullptr;
       ck(ctx, mm_mapping_align(ctx, m, reads.get(), reference, pi, &a), "alignments");
       int64_t n_jobs = 0, n_ops = 0;
@@ -262,7 +272,7 @@ struct BatchSideOutputs {
     }
     edit_distance_text(al.dist.data(), al.first.data(), al.last.data(), names, off, rec, cname, out[SIDE_EDIT]);
     if (on[SIDE_PAF]) paf_text(al, names, lens, off, rec, cname, clen, out[SIDE_PAF]);
-    if (!on[SIDE_BAM] && !pile && !vcf && !mods && !depth) reads.reset();
+    if (!on[SIDE_BAM] && !sorted && !pile && !vcf && !mods && !depth) reads.reset();
   }
 
   // once the lines are formatted: the batch's BAM records as BGZF members, encoded and deflated on the device, and its pileup events and alleles (all go by
@@ -281,6 +291,7 @@ struct BatchSideOutputs {
         if (pile) add_batch<PileupCalls>(ctx, reads.get(), reference, F, al, use, min_base_quality, pile_merge_pairs, *pile);
         if (vcf) add_batch<VcfCalls>(ctx, reads.get(), reference, F, al, use, min_base_quality, vcf_merge_pairs, *vcf);
       }
+      if (sorted) sorted_run_encode(ctx, reads.get(), reference, F, al, (int64_t)rec.size(), *sorted);
       if (!on[SIDE_BAM]) { reads.reset(); return; }
       mm_bam* b = nullptr;
       ck(ctx, mm_bam_encode(ctx, reads.get(), reference, (int64_t)rec.size(), F.read.data(), F.strand.data(), F.contig.data(), al.dist.data(), al.first.data(),

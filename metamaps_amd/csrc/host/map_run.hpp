@@ -93,6 +93,7 @@ struct MapRun {
     std::string text;
     std::string gz;                                                // --compress-output: the text as BGZF members
     SideBytes side;                                                // what the batch adds to every side file (side_files.hpp): lines, or BGZF members
+    SortedRun sorted;                                              // --bam-sorted: the batch's sorted run
     std::vector<LineMeta> meta;
     double t_mapq = 0, t_fetch = 0, t_format = 0;
   };
@@ -360,8 +361,8 @@ struct MapRun {
     }
     if (place != Place::Replicated && NC == 1 && !from_index && !maxMem) die("--stream-chunks / --shard-index need --maxmemory (the chunk rule of the reference, winSketch.hpp:274-329)");
     if (edit && place != Place::Replicated)
-      die(std::string(depth.on ? "--depth" : mods.on ? "--mods" : cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : side[SIDE_PAF] ? "--paf"
-                      : "--edit-distance") + " needs the whole reference resident on every device, and this index does not fit one: run without it");
+      die(std::string(depth.on ? "--depth" : mods.on ? "--mods" : cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : bam_sorted_of(o) ? "--bam-sorted"
+                      : side[SIDE_PAF] ? "--paf" : "--edit-distance") + " needs the whole reference resident on every device, and this index does not fit one: run without it");
     for (auto& d : devs) d.idx.assign(NC, nullptr);
     thr_of.assign(NC, INT_MAX);
   }
@@ -463,7 +464,7 @@ struct MapRun {
     std::vector<mm_map_record> rec((size_t)dn->off.back());
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), rec.data(), (int64_t)rec.size()), "fetch");
     BatchSideOutputs so{side, {}, var.pile(file), sw.pileup_merge_pairs, var.vcf(file), sw.vcf_merge_pairs, var.intervals(file), qual.min_base_quality,
-                        var.mods(file), sw.mods_merge_pairs, mods.min_ml, depth.on};   // one alignment for all of them
+                        var.mods(file), sw.mods_merge_pairs, mods.min_ml, depth.on, var.sorted.on ? &dn->sorted : nullptr};   // one alignment for all of them
     so.from_mapping(ctx, m, reads, refset[dev], pi, rec, dn->names, dn->lens, dn->off, cname, clen, dn->side);
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
@@ -525,6 +526,7 @@ struct MapRun {
           std::string().swap(d->side[s]);
         }
         std::string().swap(d->gz);
+        if (var.sorted.on) var.sorted.files[fi].append(prefix, d->sorted);
         if (keep_lines) { if (kept.size() <= fi) kept.resize(fi + 1); d->names.clear(); d->names.shrink_to_fit(); kept[fi].push_back(std::move(d)); }
       }
       if (keep_lines && kept.size() <= fi) kept.resize(fi + 1);
@@ -769,6 +771,7 @@ struct MapRun {
     open_devices();
     if (!from_index) {
       load_reference();
+      if (bam_sorted_of(o)) sorted_bam_check_contigs(cname, clen);   // (said before anything is indexed or mapped)
       plan_chunks();
       if (only_index) return write_index_files();
     } else read_index_files(ipre, cname, clen, ref_bases, chunks);   // `metamaps mapAgainstIndex` (mapWrap.h:443-554)
@@ -776,14 +779,14 @@ struct MapRun {
     build_resident_indexes();
     mp = mm_map_params{k, w, pi, minLen};
     for (auto& ch : chunks) chunk_base.push_back(ch.first);
-    var.resize(pileup.on, vcf.on, cons.on, mods.on, depth.on, prefixes.size());
+    var.resize(pileup.on, vcf.on, cons.on, mods.on, depth.on, bam_sorted_of(o), prefixes.size());
     if (side[SIDE_BAM]) bgzf_head = bam_header_members(ctx0, cname, clen);   // (before the workers take the first device's context)
     start_reader();
     if (prewarm.joinable()) prewarm.join();
     if (place != Place::Replicated) for (auto*& c : wctx) if (c) { mm_ctx_destroy(c); c = nullptr; }   // (the other modes drive one context per device)
     if (place == Place::Replicated) run_replicated(); else run_chunk_major();
     pc.lap("8 write");
-    var.write(ctx0, refset[0], pileup, vcf, cons, mods, depth, qual.min_base_quality, sw.cons_group_bases, prefixes, cname, clen);
+    var.write(ctx0, refset[0], pileup, vcf, cons, mods, depth, qual.min_base_quality, sw.cons_group_bases, sw.bam_sort_window, prefixes, cname, clen);
     then_classify();
     if (!sw.full_teardown) { if (reader.th.joinable()) reader.th.join(); pc.report(); finish_fast(); }
     drop_refsets();

@@ -5,7 +5,8 @@
 // exclusively through the C ABI in include/metamaps_hip.h.  Host work here is what stays host work in the
 // reference too: argument parsing, FASTA/FASTQ(.gz) reading, text formatting, taxonomy bookkeeping.
 //
-//   metamaps mapDirectly [--all] [--compress-output] [--edit-distance] [--paf] [--bam] [--pileup [--pileup-min-count N] [--pileup-min-frac F]] [--vcf [--vcf-min-count N] [--vcf-min-frac F]]
+//   metamaps mapDirectly [--all] [--compress-output] [--edit-distance] [--paf] [--bam] [--bam-sorted] [--pileup [--pileup-min-count N] [--pileup-min-frac F]]
+//                       [--vcf [--vcf-min-count N] [--vcf-min-frac F]]
 //                       [--consensus [--consensus-min-depth D] [--consensus-min-frac F] [--consensus-min-called C]] [--mods LIST [--mod-min-ml T] [--mod-min-coverage N]]
 //                       [--depth [--depth-window W] [--depth-thresholds T1,T2,...]]
 //                        -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
@@ -66,6 +67,10 @@
 // with the largest field 14 (host/bam_out.hpp).  The device that mapped a batch encodes its records from the alignment the .editDistances and .paf lines
 // come from and deflates them where they lie (mm_bam_encode); the file is BGZF whatever --compress-output says and ends with the end-of-file block.
 // Every other file of the run is the file of the same run without the flag.  Refused wherever --edit-distance is.
+//
+// --bam-sorted (mapDirectly; not in the reference; implies --edit-distance; with or without --bam and every other side output): also PREFIX.sorted.bam, the
+// records of PREFIX.bam in ascending (refID, pos, place in PREFIX.bam) in BGZF members of 65 280 bytes, and PREFIX.sorted.bam.bai (bam_sort_out.hpp); refused
+// wherever --edit-distance is and with a contig of 2^29 bases or more.
 //
 // --pileup [--pileup-min-count N] [--pileup-min-frac F] (mapDirectly; not in the reference; implies --edit-distance; may be combined with --paf and --bam): also
 // PREFIX.pileup and PREFIX.pileup.contigs, what a column-by-column count over the PRIMARY records of PREFIX.bam gives (a read's aligned record with the largest
@@ -176,7 +181,8 @@ Options parse(int argc, char** argv) {
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
     if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" ||
-        a == "--bam" || a == "--pileup" || a == "--vcf" || a == "--consensus" || a == "--depth" || a == "--genes" || a == "--refit" || a == "--base-qualities") { o.v[a.substr(2)] = "1"; continue; }
+        a == "--bam" || a == "--bam-sorted" ||
+        a == "--pileup" || a == "--vcf" || a == "--consensus" || a == "--depth" || a == "--genes" || a == "--refit" || a == "--base-qualities") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
@@ -188,6 +194,9 @@ Options parse(int argc, char** argv) {
                    "         line of PREFIX, the alignment traced on the device; not with --hpc, --shard-index, --stream-chunks\n"
                    "  --bam  (mapDirectly) implies --edit-distance and also writes PREFIX.bam (BGZF): one BAM record with the CIGAR, NM and MD for every aligned line of\n"
                    "         PREFIX, encoded and deflated on the device; may be combined with --paf; not with --hpc, --shard-index, --stream-chunks\n"
+                   "  --bam-sorted  (mapDirectly) implies --edit-distance and also writes PREFIX.sorted.bam, the records of PREFIX.bam in ascending (contig, position, place in\n"
+                   "         PREFIX.bam), merged on the device into members of 65 280 bytes, and PREFIX.sorted.bam.bai; with or without --bam; contigs below 2^29 bases;\n"
+                   "         not with --hpc, --shard-index, --stream-chunks\n"
                    "  --pileup [--pileup-min-count N] [--pileup-min-frac F]  (mapDirectly) implies --edit-distance and also writes PREFIX.pileup (contigID pos ref alt count depth for\n"
                    "         every difference from the reference that at least N (default 3) primary alignments and F (default 0.2) of the depth support; alt - is a deleted\n"
                    "         base, + an insertion behind the base) and PREFIX.pileup.contigs (contigID length alignments covered sumDepth), counted on the device; may be\n"
@@ -320,11 +329,11 @@ int main(int argc, char** argv) {
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: a homopolymer-compressed read has no per-base qualities");
     if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");
   }
-  if (o.v.count("paf") || o.v.count("bam") || pileup_opts.on || vcf_opts.on || cons_opts.on || mods_opts.on || depth_opts.on)
-    o.v["edit-distance"] = "1";                                  // (all seven imply it and inherit its refusals)
+  if (o.v.count("paf") || o.v.count("bam") || o.v.count("bam-sorted") || pileup_opts.on || vcf_opts.on || cons_opts.on || mods_opts.on || depth_opts.on)
+    o.v["edit-distance"] = "1";                                  // (all eight imply it and inherit its refusals)
   if (o.v.count("edit-distance")) {                              // (refused before any device work)
     const std::string flag = depth_opts.on ? "--depth" : mods_opts.on ? "--mods" : cons_opts.on ? "--consensus" : vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup" : o.v.count("bam") ? "--bam"
-                             : o.v.count("paf") ? "--paf" : "--edit-distance";
+                             : o.v.count("bam-sorted") ? "--bam-sorted" : o.v.count("paf") ? "--paf" : "--edit-distance";
     if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reference does not stay on the device");
     if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");

@@ -19,10 +19,13 @@ constexpr SideFile kSideFiles[N_SIDE] = {
 using SideSet = std::array<bool, N_SIDE>;
 
 // the rows a command line asks for: --paf and --bam imply --edit-distance (their alignment is the one whose distances that file lists)
+// --bam-sorted (bam_sort_out.hpp) is no row: its two files are written after the run's last batch; it implies --edit-distance too
+inline bool bam_sorted_of(const Options& o) { return o.v.count("bam-sorted") != 0; }
 inline SideSet side_files_of(const Options& o) {
   SideSet on{};
   for (int s = 0; s < N_SIDE; ++s) on[(size_t)s] = o.v.count(kSideFiles[s].flag) != 0;
   for (int s = 0; s < N_SIDE; ++s) if (on[(size_t)s]) on[SIDE_EDIT] = true;
+  if (bam_sorted_of(o)) on[SIDE_EDIT] = true;
   return on;
 }
 

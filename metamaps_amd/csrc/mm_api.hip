@@ -12,6 +12,7 @@
 #include "mm_ident.hpp"
 #include "mm_edit.hpp"
 #include "mm_bam.hpp"
+#include "mm_bam_sort.hpp"
 #include "mm_pileup.hpp"
 #include "mm_vcf.hpp"
 #include "mm_mods.hpp"
@@ -788,8 +789,23 @@ int mm_bam_encode(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* referenc
   if (!ctx || !reads || !reference || !out) return refused(out);
   return created(ctx, out, [&](mm_bam& b) {
     require_jobs("mm_bam_encode", n_jobs, read && strand && contig && dist && first && op_off && flag && mapq && name_off);
-    mm::bam_encode_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, mm::BamColumns{flag, mapq, name_off, names}, group_bytes, &b.b);
+    mm::bam_encode_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, mm::BamColumns{flag, mapq, name_off, names}, group_bytes, false, &b.b);
   });
+}
+int mm_bam_encode_sorted(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
+                         const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint16_t* flag, const uint8_t* mapq,
+                         const int64_t* name_off, const char* names, int64_t group_bytes, mm_bam** out) {
+  if (!ctx || !reads || !reference || !out) return refused(out);
+  return created(ctx, out, [&](mm_bam& b) {
+    require_jobs("mm_bam_encode_sorted", n_jobs, read && strand && contig && dist && first && op_off && flag && mapq && name_off);
+    mm::bam_encode_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, mm::BamColumns{flag, mapq, name_off, names}, group_bytes, true, &b.b);
+  });
+}
+int mm_bam_fetch_records(const mm_bam* b, int64_t* job, int64_t* raw_off) {
+  if (!b || !raw_off || (!b->b.rec_job.empty() && !job)) return MM_ERR_ARG;
+  if (!b->b.rec_job.empty()) memcpy(job, b->b.rec_job.data(), b->b.rec_job.size() * sizeof(int64_t));
+  memcpy(raw_off, b->b.rec_off.data(), b->b.rec_off.size() * sizeof(int64_t));
+  return MM_OK;
 }
 int mm_bam_sizes(const mm_bam* b, int64_t* n_records, int64_t* raw_bytes, int64_t* bgzf_bytes) {
   if (!b || !n_records || !raw_bytes || !bgzf_bytes) return MM_ERR_ARG;
@@ -802,6 +818,35 @@ int mm_bam_fetch(const mm_bam* b, uint8_t* bgzf) {
   return MM_OK;
 }
 void mm_bam_destroy(mm_bam* b) { delete b; }
+
+struct mm_bam_sorter { mm_ctx* ctx = nullptr; mm::BamSorter s; };
+int mm_bam_sorter_create(mm_ctx* ctx, int32_t n_ref, const int32_t* ref_len, int64_t window_bytes, mm_bam_sorter** out) {
+  if (!ctx || !out) return refused(out);
+  return created(ctx, out, [&](mm_bam_sorter& h) { mm::bam_sorter_init(h.s, n_ref, ref_len, window_bytes); });
+}
+void mm_bam_sorter_destroy(mm_bam_sorter* h) { if (h) { bind(h->ctx); delete h; } }
+int mm_bam_sorter_add_run(mm_bam_sorter* h, const uint8_t* bgzf, int64_t bgzf_bytes, int64_t n_records, const int64_t* raw_off, const int32_t* ref_id, const int32_t* pos,
+                          const int32_t* end) {
+  if (!h) return MM_ERR_ARG;
+  return guarded(h->ctx, [&] { mm::bam_sorter_add_run(h->s, bgzf, bgzf_bytes, n_records, raw_off, ref_id, pos, end); });
+}
+int mm_bam_sorter_plan(mm_bam_sorter* h, int64_t* n_windows, int64_t* stream_bytes) {
+  if (!h || !n_windows || !stream_bytes) return MM_ERR_ARG;
+  return guarded(h->ctx, [&] { mm::bam_sorter_plan(h->ctx, h->s); *n_windows = mm::bam_sorter_windows(h->s); *stream_bytes = h->s.stream_bytes; });
+}
+int mm_bam_sorter_window(mm_bam_sorter* h, int64_t w, int64_t* bgzf_bytes) {
+  if (!h || !bgzf_bytes) return MM_ERR_ARG;
+  return guarded(h->ctx, [&] { mm::bam_sorter_window(h->ctx, h->s, w); *bgzf_bytes = (int64_t)h->s.product.size(); });
+}
+int mm_bam_sorter_index(mm_bam_sorter* h, int64_t header_bytes, int64_t* bai_bytes) {
+  if (!h || !bai_bytes) return MM_ERR_ARG;
+  return guarded(h->ctx, [&] { mm::bam_sorter_index(h->ctx, h->s, header_bytes); *bai_bytes = (int64_t)h->s.product.size(); });
+}
+int mm_bam_sorter_fetch(const mm_bam_sorter* h, uint8_t* out) {
+  if (!h || (!h->s.product.empty() && !out)) return MM_ERR_ARG;
+  if (!h->s.product.empty()) memcpy(out, h->s.product.data(), h->s.product.size());
+  return MM_OK;
+}
 
 struct mm_pileup { mm::KeyTable t; };                              // (host memory only, as mm_alignment; one-word keys: t.w1 stays empty)
 struct mm_pileup_result { mm::PileupResult r; };

@@ -10,6 +10,9 @@
 //            store of the wavefront.
 //   deflate  the group's records are the input of bgzf_deflate_kernel where they lie (mm_deflate.hip: bgzf_deflate_resident); only the members come
 //            to the host.  One buffer of the largest group's size serves every group.
+//   sorted   mm_bam_encode_sorted: between size and offsets, bam_key_kernel gives every job the key contig << 32 | first (a job without a record: the
+//            key above every contig's), a stable radix sort of (key, job) gives slot -> job, bam_slot_size_kernel gathers the sizes in that order, and
+//            the scan, the groups and the write kernel go by slot.  mm_bam_encode has no slot table: slot and job are the same number.
 // No kernel here has an atomic other than the error word's, a barrier between workgroups or a loop that waits for another workgroup.
 // The runs are the caller's (mm_alignment is a host object) and are uploaded whole: 4 bytes per run against the 27 KB of a 10 kb read's record.
 // The jobs' arrays, their checks, the launch loop and the error word are mm_jobs_dev.hpp's, shared with mm_pileup.hip and mm_vcf.hip; flag, mapq and the
@@ -45,12 +48,26 @@ __global__ void __launch_bounds__(64) bam_size_kernel(const int32_t* __restrict_
   }
 }
 
-// the records of the jobs [job0, job1) of a group to raw + (off[job] - off0); a job of size 0 has none
+// (sorted alone) the order's key of every job, and the sizes in the order of the slots
+__global__ void __launch_bounds__(256) bam_key_kernel(AlignedJobs J, const int64_t* __restrict__ sizes, uint64_t no_record, uint64_t* __restrict__ key) {
+  const int64_t job = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (job >= J.n) return;
+  key[job] = sizes[job] > 0 ? (uint64_t)J.contig[job] << 32 | (uint64_t)J.first[job] : no_record;   // (a record's first is in [0, 2^31): rule 6)
+}
+__global__ void __launch_bounds__(256) bam_slot_size_kernel(const int64_t* __restrict__ slot_job, const int64_t* __restrict__ sizes, int64_t n, int64_t* __restrict__ out) {
+  const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (slot < n) out[slot] = sizes[slot_job[slot]];
+}
+
+// the records of the slots [slot0, slot1) of a group to raw + (off[slot] - off0); a slot of size 0 has none.  slot_job: the job of every slot, null
+// where the slot is the job
 __global__ void __launch_bounds__(64) bam_write_kernel(EditSeq Q, const uint64_t* __restrict__ q_base, const int32_t* __restrict__ q_len, EditSeq R,
-                                                       const uint64_t* __restrict__ r_base, const int32_t* __restrict__ r_len, AlignedJobs J, BamColumns C, int64_t job0,
-                                                       int64_t job1, const int64_t* __restrict__ off, int64_t off0, const uint8_t* __restrict__ q_qual, uint8_t* __restrict__ raw) {
-  const int64_t job = job0 + (int64_t)blockIdx.x;
-  if (job >= job1 || off[job + 1] == off[job]) return;
+                                                       const uint64_t* __restrict__ r_base, const int32_t* __restrict__ r_len, AlignedJobs J, BamColumns C, int64_t slot0,
+                                                       int64_t slot1, const int64_t* __restrict__ slot_job, const int64_t* __restrict__ off, int64_t off0,
+                                                       const uint8_t* __restrict__ q_qual, uint8_t* __restrict__ raw) {
+  const int64_t slot = slot0 + (int64_t)blockIdx.x;
+  if (slot >= slot1 || off[slot + 1] == off[slot]) return;
+  const int64_t job = slot_job ? slot_job[slot] : slot;
   WaveLanes p;
   const int32_t read = J.read[job], contig = J.contig[job];
   const uint64_t qg = q_base[read], rg = r_base[contig];
@@ -58,18 +75,19 @@ __global__ void __launch_bounds__(64) bam_write_kernel(EditSeq Q, const uint64_t
   j.ops = J.ops + J.op_off[job]; j.n_ops = J.op_off[job + 1] - J.op_off[job];
   j.name = C.names + C.name_off[job]; j.l_name = (int32_t)(C.name_off[job + 1] - C.name_off[job]);
   j.first = J.first[job]; j.m = q_len[read]; j.refid = contig; j.strand = J.strand[job]; j.dist = J.dist[job]; j.flag = C.flag[job]; j.mapq = C.mapq[job];
-  mmb::write_record_q(p, j, SeqBytes{Q.narrowed(qg, qg + (uint64_t)j.m), (int64_t)qg, q_qual}, SeqBytes{R.narrowed(rg, rg + (uint64_t)r_len[contig]), (int64_t)rg}, raw + (off[job] - off0));
+  mmb::write_record_q(p, j, SeqBytes{Q.narrowed(qg, qg + (uint64_t)j.m), (int64_t)qg, q_qual}, SeqBytes{R.narrowed(rg, rg + (uint64_t)r_len[contig]), (int64_t)rg}, raw + (off[slot] - off0));
 }
 
-void bam_encode_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& jobs_in, const BamColumns& in, int64_t group_bytes, BamMembers* out) {
-  AlignedJobsDev jobs(ctx, reads, ref, jobs_in, "mm_bam_encode");
-  MM_REQUIRE(group_bytes >= 0, MM_ERR_ARG, "mm_bam_encode: a negative group_bytes");
-  out->bgzf.clear(); out->n_records = 0; out->raw_bytes = 0;
+void bam_encode_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& jobs_in, const BamColumns& in, int64_t group_bytes, bool sorted, BamMembers* out) {
+  const char* const who = sorted ? "mm_bam_encode_sorted" : "mm_bam_encode";
+  AlignedJobsDev jobs(ctx, reads, ref, jobs_in, who);
+  MM_REQUIRE(group_bytes >= 0, MM_ERR_ARG, std::string(who) + ": a negative group_bytes");
+  out->bgzf.clear(); out->rec_job.clear(); out->rec_off.assign(1, 0); out->n_records = 0; out->raw_bytes = 0;
   const int64_t n = jobs_in.n_jobs;
   if (n == 0) return;
-  offsets_check(in.name_off, n, "mm_bam_encode", "name_off");
+  offsets_check(in.name_off, n, who, "name_off");
   const size_t k = (size_t)n, n_ops = jobs.n_ops, n_name = (size_t)in.name_off[n];
-  MM_REQUIRE(n_name == 0 || in.names, MM_ERR_ARG, "mm_bam_encode: a null array");
+  MM_REQUIRE(n_name == 0 || in.names, MM_ERR_ARG, std::string(who) + ": a null array");
   hipStream_t st = ctx->stream;
   StageClock<5> clk(getenv("MM_BAM_TIMING") != nullptr, st);       // upload, size, scan, write, deflate (with the members' way to the host)
 
@@ -91,13 +109,32 @@ void bam_encode_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, c
 
   clk.start();
   DBuf<uint8_t> tmp;
-  exclusive_scan(tmp, d_sizes.p, d_off.p, k + 1, st);
+  DBuf<int64_t> d_slot_job;                                        // sorted alone: the job of every slot
+  std::vector<int64_t> slot_job;
+  if (sorted) {
+    const uint64_t n_contigs = (uint64_t)ref->count();
+    DBuf<uint64_t> d_key(k), d_key_sorted(k); DBuf<int64_t> d_job(k), d_slot_sizes(k + 1);
+    d_slot_job.alloc(k);
+    bam_key_kernel<<<dim3(flat_grid(n)), dim3(256), 0, st>>>(J, d_sizes.p, n_contigs << 32, d_key.p);
+    MM_KERNEL_CHECK();
+    fill_iota(d_job.p, n, st);
+    sort_pairs(tmp, d_key.p, d_key_sorted.p, d_job.p, d_slot_job.p, k, 0, 32 + bits_for(n_contigs), st);   // (stable: equal keys stay in job order)
+    d_slot_sizes.zero(st);
+    bam_slot_size_kernel<<<dim3(flat_grid(n)), dim3(256), 0, st>>>(d_slot_job.p, d_sizes.p, n, d_slot_sizes.p);
+    MM_KERNEL_CHECK();
+    exclusive_scan(tmp, d_slot_sizes.p, d_off.p, k + 1, st);
+    slot_job = d_slot_job.to_host(st);
+  } else {
+    exclusive_scan(tmp, d_sizes.p, d_off.p, k + 1, st);
+  }
   const std::vector<int64_t> off = d_off.to_host(st);
   clk.stop(2);
   out->raw_bytes = off[k];
-  for (size_t i = 0; i < k; ++i) out->n_records += off[i + 1] > off[i];
+  for (size_t i = 0; i < k; ++i)
+    if (off[i + 1] > off[i]) { out->rec_job.push_back(sorted ? slot_job[i] : (int64_t)i); out->rec_off.push_back(off[i + 1]); }
+  out->n_records = (int64_t)out->rec_job.size();
 
-  // groups of consecutive jobs whose records stay within gb; a record above gb is a group of its own
+  // groups of consecutive slots whose records stay within gb; a record above gb is a group of its own
   const int64_t gb = group_bytes ? group_bytes : BAM_GROUP_BYTES;
   std::vector<int64_t> cut(1, 0);
   int64_t largest = 0;
@@ -115,8 +152,8 @@ void bam_encode_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, c
     if (bytes == 0) continue;
     clk.start();
     for_job_grids(j0, j1, [&](int64_t a, dim3 grid) {
-      bam_write_kernel<<<grid, dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, edit_seq(ref), ref->d_base.p, ref->d_len.p, J, C, a, j1, d_off.p, off[(size_t)j0],
-                                                  reads->qual_ptr(), d_raw.p);
+      bam_write_kernel<<<grid, dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, edit_seq(ref), ref->d_base.p, ref->d_len.p, J, C, a, j1, d_slot_job.p, d_off.p,
+                                                  off[(size_t)j0], reads->qual_ptr(), d_raw.p);
     });
     clk.stop(3);
     clk.start();
@@ -127,7 +164,7 @@ void bam_encode_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, c
       sizes.assign((size_t)nblk, 0);
       bgzf_deflate_resident(ctx, d_raw.p + b0 * mmd::BLOCK_IN, cbytes, nblk, down, sizes.data());
       for (int64_t b = 0; b < nblk; ++b) {
-        MM_REQUIRE(sizes[(size_t)b] >= 26 && sizes[(size_t)b] <= (int32_t)mmd::BLOCK_IN + 31, MM_ERR_DEVICE, "mm_bam_encode: a member's size is out of range");
+        MM_REQUIRE(sizes[(size_t)b] >= 26 && sizes[(size_t)b] <= (int32_t)mmd::BLOCK_IN + 31, MM_ERR_DEVICE, std::string(who) + ": a member's size is out of range");
         out->bgzf.insert(out->bgzf.end(), down + b * mmd::MEMBER_MAX, down + b * mmd::MEMBER_MAX + sizes[(size_t)b]);
       }
     }

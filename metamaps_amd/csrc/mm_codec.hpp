@@ -6,6 +6,9 @@
 namespace mm {
 int64_t bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const int64_t* comp_off, const int32_t* comp_len, int32_t n,
                      uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status);
+// BGZF blocks of the host's inflated into a buffer of the device's, where they stay
+int64_t bgzf_inflate_resident(mm_ctx* ctx, const uint8_t* const* block, const int32_t* comp_len, int32_t n, uint8_t* d_out, int64_t out_cap, const int64_t* out_off,
+                              int32_t* status);
 void bgzf_deflate(mm_ctx* ctx, const uint8_t* in, int64_t in_bytes, uint8_t* out, int64_t out_cap, int64_t* out_bytes, int32_t* n_blocks);
 int64_t bgzf_deflate_bound(int64_t in_bytes);
 // BGZF members of input that lies on the device

@@ -106,6 +106,7 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_EDIT_TIMING", "unset", "debug", "device times of the job and alignment stages of mm_mapping_edit_distances / mm_edit_infix, and of the trace stage of mm_mapping_align / mm_edit_infix_align with its scratch budget and launches (events) on stderr (tools/edit_kernel_stats.py)"},
     {"MM_EDIT_TRACE_MB", "an eighth of the device's free memory at the call", "tuning", "scratch of one launch of the alignment trace (mm_mapping_align, mm_edit_infix_align) in MiB: the jobs are cut into launches that fit it, one job at least per launch; no result depends on it"},
     {"MM_BAM_TIMING", "unset", "debug", "device times of the upload, size, scan, write and deflate stages of mm_bam_encode (events; deflate includes the members' copy to the host) with its jobs, records, runs, groups, raw and BGZF bytes on stderr (tools/edit_kernel_stats.py --bam)"},
+    {"MM_BAM_SORT_TIMING", "unset", "debug", "device times of every window of mm_bam_sorter_window: inflate (with the members' upload), gather, deflate (with the members' copy to the host), with the members inflated and the bytes, on stderr (tools/edit_kernel_stats.py --bam-sort)"},
     {"MM_PILEUP_TIMING", "unset", "debug", "device times of mm_pileup_events' upload, count, scan, emit, sort and reduce stages (events; reduce includes the table's copy to the host) with its jobs, runs, events, pairs and fetched bytes, and of the stages of mm_pileup_merge and mm_pileup_finish, on stderr (tools/edit_kernel_stats.py --pileup)"},
     {"MM_PILEUP_MERGE_PAIRS", "64 * 2^20", "test", "mapDirectly --pileup: (key, count) pairs a query file's accumulator may hold before it is replaced by its mm_pileup_merge (small values: several merges on small runs; no result depends on it)"},
     {"MM_VCF_TIMING", "unset", "debug", "device times of mm_vcf_events' upload, count, scan, emit, sort and reduce stages (events; reduce includes the table's copy to the host) with its jobs, runs, events, indels, pairs and fetched bytes, and of the stages of mm_vcf_merge and mm_vcf_finish, on stderr (tools/edit_kernel_stats.py --vcf)"},
@@ -114,6 +115,7 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_MODS_MERGE_PAIRS", "64 * 2^20", "test", "mapDirectly --mods: (key, count) pairs a query file's accumulator may hold before it is replaced by its mm_mod_merge (small values: several merges on small runs; no result depends on it)"},
     {"MM_CONS_TIMING", "unset", "debug", "device times of mm_consensus' intervals, candidates, select, positions, offsets and emit stages (emit includes the text's copy to the host) with the group's contig range, bases, entries, intervals, kept rows, written contigs and text bytes, on stderr (tools/edit_kernel_stats.py --consensus)"},
     {"MM_DEPTH_TIMING", "unset", "debug", "device times of mm_depth_profile's intervals, breakpoints, runs, contigs and windows stages (each includes its results' copy to the host) with its intervals, unique breakpoints, runs, listed contigs and windows, on stderr (tools/edit_kernel_stats.py --depth)"},
+    {"MM_BAM_SORT_WINDOW_MB", "255", "tuning", "mapDirectly --bam-sorted: MiB of sorted records the merge makes at a time (mm_bam_sorter_create's window_bytes), rounded down to whole members of 65 280 bytes, one member at least (0), 255 MiB at most; device memory of the merge is two windows; no file depends on it"},
     {"MM_CONS_GROUP_BASES", "2^28", "test", "mapDirectly --consensus: reference bases one mm_consensus call may cover; consecutive contigs are grouped up to it and a longer contig is a group alone (small values: one call per contig on small runs; no result depends on it)"},
     {"MM_CLI_FORMAT_PART", "10000", "test", "mapping records per formatter thread of a batch (the text of a batch is formatted in up to eight parts and joined)"},
     {"MM_CLI_CLASSIFY_FROM_FILE", "unset", "test", "mapDirectly --then-classify reads PREFIX back and tokenises it (as `classify` does) instead of taking the lines it has just formatted from memory"},

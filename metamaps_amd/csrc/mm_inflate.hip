@@ -56,6 +56,33 @@ __global__ __launch_bounds__(64) void bgzf_inflate_kernel(const uint8_t* __restr
 
 namespace mm {
 
+// Blocks whose inflated bytes stay on the device: the host's block[i] (comp_len[i] bytes) goes to d_out + out_off[i]; the caller has checked that every block's
+// ISIZE bytes lie inside d_out[0, out_cap) (the kernel checks it again and never writes outside).  status[i] as mm_bgzf_inflate's; returns the
+// number of blocks that are not ok, when the bytes are there.
+int64_t bgzf_inflate_resident(mm_ctx* ctx, const uint8_t* const* block, const int32_t* comp_len, int32_t n, uint8_t* d_out, int64_t out_cap, const int64_t* out_off,
+                              int32_t* status) {
+  if (n == 0) return 0;
+  hipStream_t st = ctx->stream;
+  std::vector<int64_t> rel((size_t)n);
+  int64_t cbytes = 0;
+  for (int32_t i = 0; i < n; ++i) { rel[(size_t)i] = cbytes; cbytes += comp_len[i]; }
+  uint8_t* const up = (uint8_t*)ctx->pinned_up_at_least(std::max<size_t>((size_t)cbytes, 1));
+  for (int32_t i = 0; i < n; ++i) memcpy(up + rel[(size_t)i], block[i], (size_t)comp_len[i]);
+  DBuf<uint8_t> d_comp(std::max<size_t>((size_t)cbytes, 1));
+  d_comp.upload(up, (size_t)cbytes, st);
+  DBuf<int64_t> d_off((size_t)n), d_oo((size_t)n);
+  DBuf<int32_t> d_len((size_t)n), d_st((size_t)n);
+  d_off.upload(rel.data(), (size_t)n, st); d_len.upload(comp_len, (size_t)n, st); d_oo.upload(out_off, (size_t)n, st);
+  const unsigned grid = (unsigned)std::min<int64_t>(n, (int64_t)std::max(1, ctx->cus) * 2);
+  bgzf_inflate_kernel<<<dim3(grid), dim3(64), 0, st>>>(d_comp.p, d_off.p, d_len.p, n, d_out, out_cap, d_oo.p, d_st.p);
+  MM_KERNEL_CHECK();
+  d_st.download(status, (size_t)n, st);
+  MM_HIP(mm::stream_sync(st));
+  int64_t bad = 0;
+  for (int32_t i = 0; i < n; ++i) bad += status[i] != mmi::OK;
+  return bad;
+}
+
 // mm_bgzf_inflate's body: the number of blocks whose status is not ok.  Argument errors throw MM_ERR_ARG.
 int64_t bgzf_inflate(mm_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, const int64_t* comp_off, const int32_t* comp_len, int32_t n,
                      uint8_t* out, int64_t out_cap, const int64_t* out_off, int32_t* status) {

@@ -1,5 +1,5 @@
 // The device primitives that the library's sort, scan and per-read code share (included by the .hip files only).
-//   host    with_scratch: the two-call protocol of rocprim, once; sort_keys / sort_pairs / exclusive_scan on top of it; bits_for, flat_grid,
+//   host    with_scratch: the two-call protocol of rocprim, once; sort_keys / sort_pairs / exclusive_scan / inclusive_scan_max on top of it; bits_for, flat_grid,
 //           fill_iota, rank_by_bits; StageClock, the event-pair clock behind MM_GENE_TIMING and MM_IDENT_TIMING
 //   device  Lanes<W>, the butterflies of W consecutive lanes; for_each_read_tile, the loop of the per-read kernels (mm_lca.hip, mm_ident.hip)
 // with_scratch alone compiles without the HIP runtime (tests/test_with_scratch.cpp via g++, with a stub in place of DBuf).
@@ -38,6 +38,9 @@ template <class K, class V> void sort_pairs(DBuf<uint8_t>& tmp, K* kin, K* kout,
 }
 template <class In, class Out> void exclusive_scan(DBuf<uint8_t>& tmp, const In* src, Out* dst, size_t n, hipStream_t st) {   // sums in Out, from 0
   with_scratch(tmp, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, src, dst, (Out)0, n, rocprim::plus<Out>(), st); });
+}
+template <class T> void inclusive_scan_max(DBuf<uint8_t>& tmp, const T* src, T* dst, size_t n, hipStream_t st) {   // dst[i]: the largest of src[0 .. i]
+  with_scratch(tmp, [&](void* t, size_t& b) { return rocprim::inclusive_scan(t, b, src, dst, n, rocprim::maximum<T>(), st); });
 }
 
 inline int bits_for(uint64_t n) { int b = 1; while (b < 64 && (n >> b)) ++b; return b; }   // bits that hold 0 .. n

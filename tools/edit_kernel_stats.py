@@ -5,6 +5,7 @@ tools/_tmp/), which also holds the device's answers against the host's.
 Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes profiles/edit_kernel_stats.txt)
        python tools/edit_kernel_stats.py --align [n_reads]            (writes profiles/edit_trace_stats.txt)
        python tools/edit_kernel_stats.py --bam [n_reads]              (writes profiles/bam_encode_stats.txt)
+       python tools/edit_kernel_stats.py --bam-sort [n_reads]         (writes profiles/bam_sort_stats.txt)
        python tools/edit_kernel_stats.py --pileup [n_reads]           (writes profiles/pileup_stats.txt)
        python tools/edit_kernel_stats.py --vcf [n_reads]              (writes profiles/vcf_stats.txt)
        python tools/edit_kernel_stats.py --consensus [n_reads]        (writes profiles/consensus_stats.txt)
@@ -32,6 +33,10 @@ mm_pileup_events, which is the comparison.  One run is one run.
 --pileup: the same batch through mm_mapping_align and mm_bam_encode once each, then twice through mm_pileup_events (every aligned best mapping contributes:
 mm_pileup_core.hpp, mm_pileup.hip) and once through mm_pileup_merge and mm_pileup_finish at the default thresholds: the stage times (the MM_PILEUP_TIMING
 lines), the wall time of each call with its copies, the pairs of the batch and the bytes fetched, beside that run's align and encode times.  One run is one run.
+--bam-sort: the same batch through mm_mapping_align once, twice through mm_bam_encode and twice through mm_bam_encode_sorted (wall times, beside each other), then
+as four sorted runs and again as one sorted run through mm_bam_sorter_* (mm_bam_sort.hip): the wall times of the runs' encode, of add_run, plan, every window and
+the index, and the bytes; the two splits must give byte-identical members and index.  The MM_BAM_SORT_TIMING lines have every window's inflate, gather and deflate times.  One
+run is one run.
 --bam: the same batch through mm_mapping_align once and then twice through mm_bam_encode (the BAM records of these alignments, encoded and deflated on the
 device: mm_bam_core.hpp, mm_bam.hip): the upload / size / scan / write / deflate stage times (the MM_BAM_TIMING line), the wall time of the call with its
 copies, raw and BGZF bytes, beside the same run's mm_mapping_align time (the MM_EDIT_TIMING line) and the size PREFIX.paf would have.  The members are
@@ -179,6 +184,65 @@ def child_bam(n_reads):
             got += len(piece)
     assert got == raw and n_rec == int((dist >= 0).sum()), (got, raw, n_rec)
     print(f"the members inflate to {got} bytes on the host: the raw bytes", flush=True)
+    M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
+
+
+def child_bam_sort(n_reads):
+    from metamaps_amd import capi
+    ctx = capi.Context(0)
+    ref = ctx.synth_reference(seed=20260928, n_species=25, strains_per_species=4, genome_len=2_200_000, strain_divergence=0.02, genus_divergence=0.2)
+    w = capi.lib().mm_recommended_window(1e-3, K, PI, 1000, ref.total_bases)
+    idx = ctx.index(ref, K, w)
+    reads, _ = ctx.synth_reads(ref, seed=1000, n_reads=n_reads, read_len=READ_LEN, read_len_min=0, sub_rate=0.04, ins_rate=0.03, del_rate=0.05, frac_random=0.05, n_abundant=100)
+    M = ctx.map_batch(idx, reads, K, w, pi=PI)
+    M.keep_best(K)
+    off, rec = M.fetch()
+    n = len(rec)
+    print(f"{n_reads} reads of {READ_LEN} bases against {ref.total_bases} reference bases (k {K}, w {w}, pi {PI}): {n} best mappings", flush=True)
+    dist, first, last, op_off, ops = ctx.mapping_align(M, reads, ref, PI)
+    strand = rec["strand"].astype(np.int32)
+    contig = rec["ref_contig"].astype(np.int32)
+
+    def args(a, b):
+        return dict(read=rec["read"][a:b], strand=strand[a:b], contig=contig[a:b], dist=dist[a:b], first=first[a:b], op_off=op_off[a:b + 1] - op_off[a], ops=ops[op_off[a]:op_off[b]],
+                    flag=np.where(strand[a:b] < 0, 0x10, 0), mapq=np.full(b - a, 60), names=[b"read%d" % r for r in rec["read"][a:b]])
+    for name, entry in (("mm_bam_encode", ctx.bam_encode), ("mm_bam_encode_sorted", ctx.bam_encode_sorted)):
+        for rep in range(2):
+            t0 = time.perf_counter()
+            data, n_rec, raw = entry(reads, ref, **args(0, n))
+            print(f"{name} call {rep}: {1e3 * (time.perf_counter() - t0):.1f} ms wall with the copies (the Python wrapper's own included), {n_rec} records, {raw / 1e6:.1f} MB raw, "
+                  f"{len(data) / 1e6:.1f} MB BGZF", flush=True)
+    whole = None
+    for n_runs in (4, 1):
+        cuts = [n * r // n_runs for r in range(n_runs + 1)]
+        t0 = time.perf_counter()
+        runs = [(a, ctx.bam_records(reads, ref, sorted=True, **args(a, b))) for a, b in zip(cuts, cuts[1:])]
+        t_encode = time.perf_counter() - t0
+        S = capi.BamSorter(ctx, ref.lengths())
+        t0 = time.perf_counter()
+        for a, (data, job, raw_off) in runs:
+            pos = first[a + job]
+            S.add_run(data, raw_off, contig[a + job], pos, np.maximum(pos + 1, last[a + job] + 1))
+        t_add = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        n_windows, stream = S.plan()
+        t_plan = time.perf_counter() - t0
+        t_win, out = [], []
+        for k in range(n_windows):
+            t0 = time.perf_counter()
+            out.append(S.window(k))
+            t_win.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        bai = S.index(0)
+        t_index = time.perf_counter() - t0
+        S.close()
+        body = b"".join(out)
+        assert whole is None or whole == (body, bai)
+        whole = (body, bai)
+        print(f"{n_runs} run(s): sorted encode {1e3 * t_encode:.1f} ms, add_run {1e3 * t_add:.1f} ms (host: the member chains and the keys' checks), "
+              f"plan {1e3 * t_plan:.1f} ms, {n_windows} windows of 255 MiB {1e3 * sum(t_win):.1f} ms ({', '.join(f'{1e3 * t:.0f}' for t in t_win)}; the MM_BAM_SORT_TIMING lines have each window's inflate, gather and deflate), index {1e3 * t_index:.1f} ms; {stream / 1e6:.1f} MB of records -> {len(body) / 1e6:.1f} MB BGZF, "
+              f".bai {len(bai)} bytes; wall times with the copies, one run", flush=True)
+    print("the files of the two splits are byte-identical", flush=True)
     M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
 
 
@@ -519,6 +583,19 @@ def main():
         if p.returncode != 0:
             sys.exit(p.returncode)
         with open(os.path.join(ROOT, "profiles", "pileup_stats.txt"), "w") as f:
+            f.write(text)
+        return None
+    if len(sys.argv) > 1 and sys.argv[1] == "--child-bam-sort":
+        return child_bam_sort(int(sys.argv[2]))
+    if len(sys.argv) > 1 and sys.argv[1] == "--bam-sort":
+        n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-bam-sort", str(n_reads)], env=dict(os.environ, MM_BAM_TIMING="1", MM_BAM_SORT_TIMING="1"),
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1100)
+        text = f"tools/edit_kernel_stats.py --bam-sort {n_reads}: one batch of {n_reads} reads, best mappings only; one run\n" + p.stdout.decode()
+        print(text)
+        if p.returncode != 0:
+            sys.exit(p.returncode)
+        with open(os.path.join(ROOT, "profiles", "bam_sort_stats.txt"), "w") as f:
             f.write(text)
         return None
     if len(sys.argv) > 1 and sys.argv[1] == "--child-bam":
