@@ -33,7 +33,7 @@ extern "C" {
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
                             *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances,
                             *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_* (mm_bam_encode_sorted, mm_bam_fetch_records, mm_bam_sorter_*), mm_pileup_*, mm_vcf_*, mm_consensus*, mm_seqset_*_mods, mm_mod_*,
-                            *    mm_depth_* (additions to 6) */
+                            *    mm_depth_*, mm_errprof_* (additions to 6) */
 
 typedef enum {
   MM_OK = 0,
@@ -765,6 +765,41 @@ int mm_depth_fetch_contigs(const mm_depth* result, int32_t* contig /* [n_contigs
                            int64_t* stats /* [(MM_DEPTH_STATS + n_thresholds) * n_contigs] */);
 int mm_depth_fetch_windows(const mm_depth* result, int64_t* sum /* [n_windows] */, int64_t* covered /* [n_windows] */);
 void mm_depth_destroy(mm_depth* result);
+
+/* The error profile of aligned jobs ("Error profile"; the definition: csrc/mm_errprof_core.hpp): what the jobs with use != 0 and
+ * dist >= 0 say about the reads, walked on the context's device.  The jobs are mm_pileup_events' (the runs of mm_alignment_fetch, len << 4 | op) and so are
+ * the rules, mm_bam_encode's 1, 2 (the strand), 4, 5 and 6.  The walk runs from r = first, i = 0 over the oriented read Q (the reverse complement for strand -1)
+ * with q(i) its quality (0xFF: none) and code A 0 C 1 G 2 T 3, else N 4:
+ *   = or X column at (r, i)  counted in the read's orientation, as the sequencer saw it: truth a = code(R[r]) (its complement for strand -1), observed b = the
+ *                            code of the stored read byte; SUB[a * 5 + b] += 1 and QUAL[cls][row(q(i))] += 1, cls 0 for =, 1 for X; row(q) = q for 0..93, 94 for none.
+ *   I run of n at (r, i)     QUAL[2][row(q(i + t))] += 1 for each base; INDEL[0][hp][min(n, 64) - 1] += 1, hp = 1 iff the n oriented bases are one letter b of
+ *                            A C G T and R[r - 1] == b (r >= 1) or R[r] == b (r < the contig's length).
+ *   D run of n at r          INDEL[1][hp][min(n, 64) - 1] += 1, hp = 1 iff R[r .. r + n) is one letter b of A C G T and R[r - 1] == b (r >= 1) or R[r + n] == b
+ *                            (r + n < the contig's length).
+ * counters: MM_ERRPROF_COUNTERS 64-bit sums in the order SUB[25], INDEL[kind][hp][64], QUAL[cls][95], overwritten.  cols: per job eq, x, insRuns, insBases,
+ * delRuns, delBases (zeros for a job that is not used).  ident_key: per job contig << 32 | ppm with ppm = floor(10^6 * eq / (eq + x + insBases + delBases)) in
+ * 64-bit integers (0 for an empty read), ~0 for a job that is not used.  All results are integers that add across calls, so nothing depends on batches,
+ * devices or order.  MM_ERR_ARG "mm_errprof_events: job <index>: rule <n>: ..." names the lowest job that breaks a rule; the outputs are then unspecified.
+ * n_jobs == 0 gives zero counters and launches nothing.  All arrays are the caller's.  The walk runs in MM_ERRPROF_GROUPS workgroups (default: 16 per CU), each
+ * with its counters in LDS and one row of partial sums; MM_ERRPROF_TIMING=1 prints the stages' device times. */
+#define MM_ERRPROF_COUNTERS 566   /* 25 + 2 * 2 * 64 + 3 * 95 */
+#define MM_ERRPROF_COLS 6         /* eq, x, insRuns, insBases, delRuns, delBases */
+int mm_errprof_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand,
+                      const int32_t* contig, const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use,
+                      uint64_t* counters /* [MM_ERRPROF_COUNTERS], overwritten */, int32_t* cols /* [n_jobs][MM_ERRPROF_COLS] */, uint64_t* ident_key /* [n_jobs] */);
+/* The per-contig rows of a query file's error profile from the (ident_key, cols) of all its contributing alignments, in any order; entries whose key is ~0 are
+ * skipped.  On the device: one sort of (key, index), the segment of every contig by binary searches, and per contig with at least one alignment
+ * MM_ERRPROF_STATS values: alignments, the six column sums, and of its ppm values v[0 .. n) sorted ascending min = v[0], q1 = v[(n - 1) / 4],
+ * median = v[(n - 1) / 2], q3 = v[3 (n - 1) / 4] (integer divisions), max = v[n - 1].  One more row holds the same over all alignments together (zeros
+ * without any).  MM_ERR_ARG: a key whose contig is >= n_contigs (the message names the lowest entry), a negative count, a null array; checked before anything is
+ * launched; an error leaves *out NULL; n == 0 launches nothing.  The result lives in host memory until destroyed. */
+#define MM_ERRPROF_STATS 12   /* alignments, eq, x, insRuns, insBases, delRuns, delBases, min, q1, median, q3, max (ppm) */
+typedef struct mm_errprof mm_errprof;
+int mm_errprof_finish(mm_ctx* ctx, int64_t n_contigs, int64_t n, const uint64_t* ident_key /* [n] */, const int32_t* cols /* [n][MM_ERRPROF_COLS] */, mm_errprof** out);
+/* n_contigs: the contigs with an alignment */
+int mm_errprof_sizes(const mm_errprof* result, int64_t* n_contigs);
+int mm_errprof_fetch(const mm_errprof* result, int32_t* contig /* [n_contigs], ascending */, int64_t* stats /* [(n_contigs + 1) * MM_ERRPROF_STATS]: the last row is all alignments' */);
+void mm_errprof_destroy(mm_errprof* result);
 
 /* ---- communicator (RCCL over xGMI; one process per GPU) --------------------------------------- */
 #define MM_COMM_ID_BYTES 128

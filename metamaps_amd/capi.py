@@ -17,7 +17,8 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmetamaps_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "metamaps_hip.h")
 
 COMM_ID_BYTES = 128
-DEPTH_STATS = 5                                                     # counters per contig of mm_depth_profile before its thresholds' (the header's counter constant)
+ERRPROF_COUNTERS, ERRPROF_COLS, ERRPROF_STATS = 566, 6, 12          # the sizes of mm_errprof_events' counters and columns and of a row of mm_errprof_finish (the header's constants)
+DEPTH_STATS = 5                                                    # counters per contig of mm_depth_profile before its thresholds' (the header's counter constant)
 CONS_STATS = 10                                                     # counters per contig of mm_consensus (the header's counter constant)
 VCF_WINDOW = 25                                                     # reference bytes a kept allele of mm_vcf_finish carries (the header's window constant)
 MM_ERR_ARG = -1
@@ -261,6 +262,11 @@ def lib() -> C.CDLL:
             "mm_depth_fetch_contigs": (C.c_int, [vp, vp, vp, vp]),
             "mm_depth_fetch_windows": (C.c_int, [vp, vp, vp]),
             "mm_depth_destroy": (None, [vp]),
+            "mm_errprof_events": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "mm_errprof_finish": (C.c_int, [vp, i64, i64, vp, vp, vp]),
+            "mm_errprof_sizes": (C.c_int, [vp, vp]),
+            "mm_errprof_fetch": (C.c_int, [vp, vp, vp]),
+            "mm_errprof_destroy": (None, [vp]),
             "mm_comm_unique_id": (C.c_int, [C.c_char_p]),
             "mm_comm_init": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
             "mm_comm_allreduce_f64": (C.c_int, [vp, vp, i64]),
@@ -908,6 +914,38 @@ class Context:
             self.last_depth_handle = h.value                        # (what the call left in *out: None after a refusal)
             if h.value:
                 lib().mm_depth_destroy(h)
+
+    def errprof_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use):
+        """the error profile of the jobs with use != 0 and dist >= 0 (mm_errprof_events): (counters, cols, ident_key) with ERRPROF_COUNTERS sums in the order
+        SUB[25], INDEL[kind][hp][64], QUAL[cls][95], per job eq, x, insRuns, insBases, delRuns, delBases and contig << 32 | ppm (~0 for a job that is not used)"""
+        rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
+        fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
+        op, us = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(use, dtype=np.uint8)
+        n = len(rd)
+        assert all(len(x) == n for x in (sd, cg, ds, fs, us)) and len(oo) == n + 1
+        counters, cols, keys = np.full(ERRPROF_COUNTERS, 0xDEAD, dtype=np.uint64), np.full((n, ERRPROF_COLS), -1, dtype=np.int32), np.full(n, 0xDEAD, dtype=np.uint64)
+        self.check(lib().mm_errprof_events(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), _ptr(counters),
+                                           _ptr(cols), _ptr(keys)))
+        return counters, cols, keys
+
+    def errprof_finish(self, n_contigs, ident_key, cols):
+        """the per-contig rows of the (ident_key, cols) of a query file's alignments (mm_errprof_finish): (contig, stats) with the contigs that have an alignment,
+        ascending, and ERRPROF_STATS values per listed contig, the last row over all alignments together"""
+        ks, cs = np.ascontiguousarray(ident_key, dtype=np.uint64), np.ascontiguousarray(cols, dtype=np.int32).reshape(-1, ERRPROF_COLS)
+        assert len(ks) == len(cs)
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_errprof_finish(self.h, int(n_contigs), len(ks), _ptr(ks), _ptr(cs), C.byref(h))
+        try:
+            self.check(st)
+            nc = C.c_int64(-1)
+            assert lib().mm_errprof_sizes(h, C.byref(nc)) == 0
+            contig, stats = np.full(nc.value, -1, dtype=np.int32), np.full((nc.value + 1, ERRPROF_STATS), -1, dtype=np.int64)
+            assert lib().mm_errprof_fetch(h, _ptr(contig), _ptr(stats)) == 0
+            return contig, stats
+        finally:
+            self.last_errprof_handle = h.value                      # (what the call left in *out: None after a refusal)
+            if h.value:
+                lib().mm_errprof_destroy(h)
 
     # ---- communicator
     @staticmethod

@@ -1,9 +1,9 @@
 // The side outputs of a batch of mapDirectly (the rows of side_files.hpp: PREFIX.editDistances, .paf, .bam) and the device calls they need, and the run's
 // pileup (PREFIX.pileup, .pileup.contigs), alleles (PREFIX.vcf), consensus (PREFIX.consensus.fa, .consensus.tsv), modification counts (PREFIX.bedmethyl) and
-// depth profile (PREFIX.depth.bedgraph, .depth.windows, .depth.contigs), which every batch adds to.  The text and byte rules are in edit_dist.hpp, paf_out.hpp,
-// bam_out.hpp, pileup_out.hpp, vcf_out.hpp, consensus_out.hpp, mods_out.hpp and depth_out.hpp, which call nothing; everything of a batch runs on the context
-// that mapped it, the last merge and the finish of the pileup, of the alleles, of the consensus and of the modification counts and the depth profile on the
-// first device.
+// depth profile (PREFIX.depth.bedgraph, .depth.windows, .depth.contigs) and error profile (PREFIX.errorProfile.*), which every batch adds to.  The text and
+// byte rules are in edit_dist.hpp, paf_out.hpp, bam_out.hpp, pileup_out.hpp, vcf_out.hpp, consensus_out.hpp, mods_out.hpp, depth_out.hpp and errprof_out.hpp,
+// which call nothing; everything of a batch runs on the context that mapped it, the last merge and the finish of the pileup, of the alleles, of the consensus
+// and of the modification counts, the depth profile and the error profile's rows on the first device.
 #pragma once
 #include "bam_out.hpp"
 #include "bam_sort_out.hpp"
@@ -11,6 +11,7 @@
 #include "consensus_out.hpp"
 #include "depth_out.hpp"
 #include "edit_dist.hpp"
+#include "errprof_out.hpp"
 #include "mods_out.hpp"
 #include "paf_out.hpp"
 #include "pileup_out.hpp"
@@ -196,27 +197,53 @@ void depth_write(mm_ctx* ctx, const Intervals& iv, const DepthOpts& dp, const st
   write_or_die(prefix + ".depth.windows", depth_windows_text(contig, win_off, sum, covered, dp.window, cname, clen));
   write_or_die(prefix + ".depth.contigs", depth_contigs_text(dp, contig, stats, cname, clen));
 }
+// --error-profile, per batch: the counters, columns and identity keys of the primary aligned records (use) walked on the context that mapped the batch
+void errprof_add_batch(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, const BamFields& F, const BatchAlignment& al, const std::vector<uint8_t>& use, ErrprofAcc& acc) {
+  uint64_t counters[MM_ERRPROF_COUNTERS];
+  std::vector<int32_t> cols(use.size() * MM_ERRPROF_COLS); std::vector<uint64_t> key(use.size());
+  ck(ctx, mm_errprof_events(ctx, reads, reference, (int64_t)use.size(), F.read.data(), F.strand.data(), F.contig.data(), al.dist.data(), al.first.data(), al.op_off.data(), al.ops.data(),
+                            use.data(), counters, cols.data(), key.data()), "error profile");
+  acc.add(counters, key, cols);
+}
+// --error-profile, after the last batch of a query file: one mm_errprof_finish on `ctx` over the file's keys and columns, and the four files
+void errprof_write(mm_ctx* ctx, const ErrprofAcc& acc, const std::string& prefix, const std::vector<std::string>& cname, const std::vector<int>& clen) {
+  mm_errprof* r = nullptr;
+  ck(ctx, mm_errprof_finish(ctx, (int64_t)cname.size(), (int64_t)acc.key.size(), acc.key.data(), acc.cols.data(), &r), "error profile rows");
+  int64_t n = 0;
+  mm_errprof_sizes(r, &n);
+  std::vector<int32_t> contig((size_t)n); std::vector<int64_t> stats((size_t)(n + 1) * MM_ERRPROF_STATS);
+  mm_errprof_fetch(r, contig.data(), stats.data());
+  mm_errprof_destroy(r);
+  if (!acc.key.empty() && !errprof_any_quality(acc.counters))
+    std::cout << "INFO, --error-profile: no read of " << prefix << " carried a base quality: " << prefix << ".errorProfile.qualities has the row `none` alone (--base-qualities keeps them)\n";
+  write_or_die(prefix + ".errorProfile.substitutions", errprof_substitutions_text(acc.counters));
+  write_or_die(prefix + ".errorProfile.indels", errprof_indels_text(acc.counters));
+  write_or_die(prefix + ".errorProfile.qualities", errprof_qualities_text(acc.counters));
+  write_or_die(prefix + ".errorProfile.contigs", errprof_contigs_text(contig, stats, cname, clen));
+}
 // the run's accumulators, one set per query file, and what is written from them after the last batch (every pileup before the first VCF).  The alleles are
 // accumulated (vcf_on) for --vcf and for --consensus, merged once, and written as PREFIX.vcf under --vcf alone
 struct RunVariants {
-  struct File { Intervals iv; VariantAcc pile, vcf, mods; };
-  bool pileup_on = false, vcf_on = false, vcf_file = false, cons_on = false, mods_on = false, depth_on = false;
+  struct File { Intervals iv; VariantAcc pile, vcf, mods; ErrprofAcc errprof; };
+  bool pileup_on = false, vcf_on = false, vcf_file = false, cons_on = false, mods_on = false, depth_on = false, errprof_on = false;
   std::deque<File> files;
   SortedBams sorted;                                             // --bam-sorted: the runs of every query file (bam_sort_out.hpp)
-  void resize(bool pileup, bool vcf, bool cons, bool mods, bool depth, bool bam_sorted, size_t n_files) {
-    pileup_on = pileup; vcf_on = vcf || cons; vcf_file = vcf; cons_on = cons; mods_on = mods; depth_on = depth;
+  void resize(bool pileup, bool vcf, bool cons, bool mods, bool depth, bool bam_sorted, bool errprof, size_t n_files) {
+    pileup_on = pileup; vcf_on = vcf || cons; vcf_file = vcf; cons_on = cons; mods_on = mods; depth_on = depth; errprof_on = errprof;
     sorted.on = bam_sorted;
     if (bam_sorted) sorted.files.resize(n_files);
-    if (pileup_on || vcf_on || mods_on || depth_on) files.resize(n_files);
+    if (pileup_on || vcf_on || mods_on || depth_on || errprof_on) files.resize(n_files);
   }
   VariantAcc* pile(size_t f) { return pileup_on ? &files[f].pile : nullptr; }
   VariantAcc* vcf(size_t f) { return vcf_on ? &files[f].vcf : nullptr; }
   VariantAcc* mods(size_t f) { return mods_on ? &files[f].mods : nullptr; }
+  ErrprofAcc* errprof(size_t f) { return errprof_on ? &files[f].errprof : nullptr; }
   Intervals* intervals(size_t f) { return files.empty() ? nullptr : &files[f].iv; }
   void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const ConsOpts& co, const ModsOpts& mo, const DepthOpts& dp, int min_base_quality,
              int64_t cons_group_bases, int64_t bam_sort_window, const std::vector<std::string>& prefixes, const std::vector<std::string>& cname, const std::vector<int>& clen) {
     for (size_t fi = 0; pileup_on && fi < files.size(); ++fi) pileup_write(ctx, reference, files[fi].pile.rows, files[fi].iv, po, prefixes[fi], cname, clen);
     for (size_t fi = 0; depth_on && fi < files.size(); ++fi) depth_write(ctx, files[fi].iv, dp, prefixes[fi], cname, clen);
+    for (size_t fi = 0; errprof_on && fi < files.size(); ++fi) errprof_write(ctx, files[fi].errprof, prefixes[fi], cname, clen);
     for (size_t fi = 0; mods_on && fi < files.size(); ++fi) mods_write(ctx, reference, files[fi].mods.rows, mo, prefixes[fi], cname);
     for (size_t fi = 0; vcf_on && fi < files.size(); ++fi) {
       merge_rows<VcfCalls>(ctx, files[fi].vcf.rows);
@@ -247,6 +274,7 @@ struct BatchSideOutputs {
   int32_t min_ml = 0;                                            // --mod-min-ml: the ML byte below which a call counts as failed
   bool depth = false;                                            // --depth: the intervals alone (no accumulator, no traceback: first and last come with the distances)
   SortedRun* sorted = nullptr;                                   // --bam-sorted: the batch's sorted run (bam_sort_out.hpp)
+  ErrprofAcc* errprof = nullptr;                                 // --error-profile: the accumulator of the batch's query file (a third user of the reads' qualities)
 
   // while the mapping lives: d, first, last (and the runs, where .paf or .bam want them) fetched once -> the lines of .editDistances and .paf.
   // The reads go here unless .bam needs them for SEQ, the pileup or the VCF for their mismatched and inserted bases, or --mods for their calls; --depth reads
@@ -257,7 +285,7 @@ struct BatchSideOutputs {
                     const std::vector<int>& clen, SideBytes& out) {
     if (!reads) return;
     const size_t n = rec.size();
-    if (on[SIDE_PAF] || on[SIDE_BAM] || sorted || pile || vcf || mods) {
+    if (on[SIDE_PAF] || on[SIDE_BAM] || sorted || pile || vcf || mods || errprof) {
       mm_alignment* a = nullptr;
       ck(ctx, mm_mapping_align(ctx, m, reads.get(), reference, pi, &a), "alignments");
       int64_t n_jobs = 0, n_ops = 0;
@@ -272,7 +300,7 @@ struct BatchSideOutputs {
     }
     edit_distance_text(al.dist.data(), al.first.data(), al.last.data(), names, off, rec, cname, out[SIDE_EDIT]);
     if (on[SIDE_PAF]) paf_text(al, names, lens, off, rec, cname, clen, out[SIDE_PAF]);
-    if (!on[SIDE_BAM] && !sorted && !pile && !vcf && !mods && !depth) reads.reset();
+    if (!on[SIDE_BAM] && !sorted && !pile && !vcf && !mods && !depth && !errprof) reads.reset();
   }
 
   // once the lines are formatted: the batch's BAM records as BGZF members, encoded and deflated on the device, and its pileup events and alleles (all go by
@@ -284,8 +312,9 @@ struct BatchSideOutputs {
     members.clear();
     if (!rec.empty()) {
       const BamFields F = bam_fields(al.dist, rec, names, off, text);
-      if (pile || vcf || mods || depth) {
+      if (pile || vcf || mods || depth || errprof) {
         const std::vector<uint8_t> use = pileup_use(F.flag, al.dist);
+        if (errprof) errprof_add_batch(ctx, reads.get(), reference, F, al, use, *errprof);
         if (mods) add_batch<ModCalls>(ctx, reads.get(), reference, F, al, use, min_ml, mods_merge_pairs, *mods);
         if (pile || vcf || depth) iv->add_intervals(use, F.contig, al.first, al.last);
         if (pile) add_batch<PileupCalls>(ctx, reads.get(), reference, F, al, use, min_base_quality, pile_merge_pairs, *pile);

@@ -361,7 +361,7 @@ struct MapRun {
     }
     if (place != Place::Replicated && NC == 1 && !from_index && !maxMem) die("--stream-chunks / --shard-index need --maxmemory (the chunk rule of the reference, winSketch.hpp:274-329)");
     if (edit && place != Place::Replicated)
-      die(std::string(depth.on ? "--depth" : mods.on ? "--mods" : cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : bam_sorted_of(o) ? "--bam-sorted"
+      die(errprof_or(o, depth.on ? "--depth" : mods.on ? "--mods" : cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : bam_sorted_of(o) ? "--bam-sorted"
                       : side[SIDE_PAF] ? "--paf" : "--edit-distance") + " needs the whole reference resident on every device, and this index does not fit one: run without it");
     for (auto& d : devs) d.idx.assign(NC, nullptr);
     thr_of.assign(NC, INT_MAX);
@@ -464,7 +464,7 @@ struct MapRun {
     std::vector<mm_map_record> rec((size_t)dn->off.back());
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), rec.data(), (int64_t)rec.size()), "fetch");
     BatchSideOutputs so{side, {}, var.pile(file), sw.pileup_merge_pairs, var.vcf(file), sw.vcf_merge_pairs, var.intervals(file), qual.min_base_quality,
-                        var.mods(file), sw.mods_merge_pairs, mods.min_ml, depth.on, var.sorted.on ? &dn->sorted : nullptr};   // one alignment for all of them
+                        var.mods(file), sw.mods_merge_pairs, mods.min_ml, depth.on, var.sorted.on ? &dn->sorted : nullptr, var.errprof(file)};   // one alignment for all of them
     so.from_mapping(ctx, m, reads, refset[dev], pi, rec, dn->names, dn->lens, dn->off, cname, clen, dn->side);
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
@@ -779,7 +779,7 @@ struct MapRun {
     build_resident_indexes();
     mp = mm_map_params{k, w, pi, minLen};
     for (auto& ch : chunks) chunk_base.push_back(ch.first);
-    var.resize(pileup.on, vcf.on, cons.on, mods.on, depth.on, bam_sorted_of(o), prefixes.size());
+    var.resize(pileup.on, vcf.on, cons.on, mods.on, depth.on, bam_sorted_of(o), errprof_of(o), prefixes.size());
     if (side[SIDE_BAM]) bgzf_head = bam_header_members(ctx0, cname, clen);   // (before the workers take the first device's context)
     start_reader();
     if (prewarm.joinable()) prewarm.join();

@@ -8,7 +8,7 @@
 //   metamaps mapDirectly [--all] [--compress-output] [--edit-distance] [--paf] [--bam] [--bam-sorted] [--pileup [--pileup-min-count N] [--pileup-min-frac F]]
 //                       [--vcf [--vcf-min-count N] [--vcf-min-frac F]]
 //                       [--consensus [--consensus-min-depth D] [--consensus-min-frac F] [--consensus-min-called C]] [--mods LIST [--mod-min-ml T] [--mod-min-coverage N]]
-//                       [--depth [--depth-window W] [--depth-thresholds T1,T2,...]]
+//                       [--depth [--depth-window W] [--depth-thresholds T1,T2,...]] [--error-profile]
 //                        -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
 //   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]] [--lca T] [--genes] [--min-identity T [--refit]]
@@ -116,6 +116,17 @@
 // options are refused without --depth (host/depth_out.hpp).  Not provided: zero-depth runs, per-strand depth, a mapping-quality filter, a quality-aware
 // depth, bigWig, depth from secondary mappings, the flag outside mapDirectly.
 //
+// --error-profile (mapDirectly; not in the reference; implies --edit-distance; may be combined with every other side output): also
+// PREFIX.errorProfile.substitutions, .indels, .qualities and .contigs from the PRIMARY alignments: which base the sequencer wrote for which base of the reference
+// (counted in the read's orientation), insertions and deletions by length with those that only stretch or shrink a homopolymer apart, matches, mismatches and
+// inserted bases per reported base quality with the empirical error rate (the qualities come with --base-qualities; without it every base is in the row `none`),
+// and per contig the exact identity summed over its alignments, the gap-compressed identity and minimum, quartiles and maximum of the per-read identities, with a
+// last row * over all alignments.  The device that mapped a batch walks its alignments once (mm_errprof_events, csrc/mm_errprof_core.hpp, DESIGN.md section 1,
+// "Error profile"); the run keeps 566 sums and 32 bytes per primary alignment per query file, and the first device sorts them into the rows
+// (mm_errprof_finish).  Plain text whatever --compress-output says; an empty run writes the headers alone.  Every other file of the run is the file of the same
+// run without the flag.  Refused wherever --edit-distance is (host/errprof_out.hpp).  Not provided: a confusion table by the reference's homopolymer length, the
+// error rate along the read, per-read rows, secondary mappings, the flag outside mapDirectly.
+//
 // --base-qualities, --min-base-quality Q (mapDirectly; not in the reference; samtools mpileup's -Q): the run keeps the base qualities of its queries (the quality
 // line of a FASTQ record in any of the text forms, the qual field of a BAM record; a FASTA record and a BAM record without have none) and uploads them beside
 // the bases, one byte per base (mm_seqset_add_qual; a quality character outside '!'..'~' ends the run).  --bam then writes every record's QUAL (reversed for
@@ -123,7 +134,8 @@
 // --pileup, --vcf and --consensus: a mismatched base counts iff its quality is >= Q, a deletion iff the read's bases on either side of the gap have it, an
 // insertion iff all its bases have it; a read without qualities passes every floor (mm_pileup_events_q, mm_vcf_events_q).  The alignments' intervals are
 // untouched: depth, DP and PREFIX.pileup.contigs stay raw, so count / depth errs low under a floor.  With Q > 0 the VCF header gains "##minBaseQuality=Q".
-// --base-qualities needs --bam or --min-base-quality, --min-base-quality one of --pileup, --vcf, --consensus; both are refused wherever --edit-distance is.
+// --base-qualities needs --bam, --min-base-quality or --error-profile (which counts the columns per reported quality), --min-base-quality one of --pileup,
+// --vcf, --consensus; both are refused wherever --edit-distance is.
 // Without the two flags every output is what it was.
 //
 // --hpc (mapDirectly; not in the reference; minimap2's -H): homopolymer-compressed mapping.  Every maximal run of equal bytes of the reference and
@@ -181,7 +193,7 @@ Options parse(int argc, char** argv) {
     if (a == "--shard-index") { o.shard = true; continue; }
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
     if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" ||
-        a == "--bam" || a == "--bam-sorted" ||
+        a == "--bam" || a == "--bam-sorted" || a == "--error-profile" ||
         a == "--pileup" || a == "--vcf" || a == "--consensus" || a == "--depth" || a == "--genes" || a == "--refit" || a == "--base-qualities") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
@@ -210,7 +222,7 @@ Options parse(int argc, char** argv) {
                    "         least D (default 3) primary alignments span a position and F (default 0.5) of them carry the allele, N below D; contigs with at least C (default 0)\n"
                    "         of their length spanned), and PREFIX.consensus.tsv (per-contig counters); may be combined with --vcf, --paf, --bam and --pileup; not with --hpc,\n"
                    "         --shard-index, --stream-chunks\n"
-                   "  --base-qualities  (mapDirectly, with --bam or --min-base-quality) the queries' base qualities (FASTQ, BAM) go to the device beside the bases;\n"
+                   "  --base-qualities  (mapDirectly, with --bam, --min-base-quality or --error-profile) the queries' base qualities (FASTQ, BAM) go to the device beside the bases;\n"
                    "         PREFIX.bam carries them in QUAL (0xFF for a read without); not with --hpc, --shard-index, --stream-chunks\n"
                    "  --min-base-quality Q  (mapDirectly, with --pileup, --vcf or --consensus) Q in [0, 93], implies --base-qualities: a mismatch counts only where its\n"
                    "         base has quality >= Q, a deletion where the read's bases on both sides of it have, an insertion where all its bases have; DP and depth stay raw\n"
@@ -223,6 +235,11 @@ Options parse(int argc, char** argv) {
                    "         default 1000) and PREFIX.depth.contigs (per contig mean, median and maximal depth, breadth, the breadth a uniform spread would give and the\n"
                    "         positions of depth >= T, default 1,5,10,30), computed on the device from the alignments' ends alone; may be combined with the other outputs;\n"
                    "         not with --hpc, --shard-index, --stream-chunks\n"
+                   "  --error-profile  (mapDirectly) implies --edit-distance and also writes PREFIX.errorProfile.substitutions (truth by observed base, in the read's orientation),\n"
+                   "         .indels (insertions and deletions by length, those that only stretch or shrink a homopolymer apart), .qualities (matches, mismatches and inserted\n"
+                   "         bases per reported base quality with the empirical error rate; needs --base-qualities, else the row `none` alone) and .contigs (per contig the\n"
+                   "         exact identity of its primary alignments, gap-compressed identity and the spread across reads), counted on the device; may be combined with the\n"
+                   "         other outputs; not with --hpc, --shard-index, --stream-chunks\n"
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
                    "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
                    "  --genes  (classify, mapDirectly --then-classify) gene-level analysis against DB_annotations.txt and DB_proteins.faa.annotated of the DB:\n"
@@ -329,11 +346,11 @@ int main(int argc, char** argv) {
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: a homopolymer-compressed read has no per-base qualities");
     if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");
   }
-  if (o.v.count("paf") || o.v.count("bam") || o.v.count("bam-sorted") || pileup_opts.on || vcf_opts.on || cons_opts.on || mods_opts.on || depth_opts.on)
-    o.v["edit-distance"] = "1";                                  // (all eight imply it and inherit its refusals)
+  if (o.v.count("paf") || o.v.count("bam") || o.v.count("bam-sorted") || pileup_opts.on || vcf_opts.on || cons_opts.on || mods_opts.on || depth_opts.on || errprof_of(o))
+    o.v["edit-distance"] = "1";                                  // (all nine imply it and inherit its refusals)
   if (o.v.count("edit-distance")) {                              // (refused before any device work)
-    const std::string flag = depth_opts.on ? "--depth" : mods_opts.on ? "--mods" : cons_opts.on ? "--consensus" : vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup" : o.v.count("bam") ? "--bam"
-                             : o.v.count("bam-sorted") ? "--bam-sorted" : o.v.count("paf") ? "--paf" : "--edit-distance";
+    const std::string flag = errprof_or(o, depth_opts.on ? "--depth" : mods_opts.on ? "--mods" : cons_opts.on ? "--consensus" : vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup"
+                                           : o.v.count("bam") ? "--bam" : o.v.count("bam-sorted") ? "--bam-sorted" : o.v.count("paf") ? "--paf" : "--edit-distance");
     if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reference does not stay on the device");
     if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");

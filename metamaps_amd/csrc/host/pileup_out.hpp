@@ -21,7 +21,7 @@ namespace {
 
 // --pileup-min-count N, --pileup-min-frac F: validated before any work; refused without --pileup
 // --base-qualities, --min-base-quality Q (QualOpts, cli_common.hpp): Q an integer 0..93, which implies --base-qualities and needs an output that counts evidence;
-// --base-qualities alone needs one that uses the qualities.  (The refusals by sub-command and by --hpc are main's, under the flag's own name.)
+// --base-qualities alone needs one that uses the qualities (--bam, --error-profile).  (The refusals by sub-command and by --hpc are main's, under the flag's own name.)
 QualOpts qual_options(const Options& o) {
   QualOpts q;
   q.keep = o.v.count("base-qualities") != 0;
@@ -30,7 +30,7 @@ QualOpts qual_options(const Options& o) {
     if (v.empty() || v.size() > 2 || v.find_first_not_of("0123456789") != std::string::npos || std::stoi(v) > 93) die("--min-base-quality takes an integer from 0 to 93, not '" + v + "'");
     if (!o.v.count("pileup") && !o.v.count("vcf") && !o.v.count("consensus")) die("--min-base-quality needs --pileup, --vcf or --consensus: nothing else counts a base's evidence");
     q.min_base_quality = std::stoi(v); q.keep = true;
-  } else if (q.keep && !o.v.count("bam")) die("--base-qualities needs --bam or --min-base-quality: nothing else would use the qualities");
+  } else if (q.keep && !o.v.count("bam") && !o.v.count("error-profile")) die("--base-qualities needs --bam or --min-base-quality (or --error-profile): nothing else would use the qualities");
   return q;
 }
 struct PileupOpts { bool on = false; long long min_count = 3; double min_frac = 0.2; };

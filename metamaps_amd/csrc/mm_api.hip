@@ -20,6 +20,8 @@
 #include "mm_cons_core.hpp"
 #include "mm_depth.hpp"
 #include "mm_depth_core.hpp"
+#include "mm_errprof.hpp"
+#include "mm_errprof_core.hpp"
 #include "mm_seq.hpp"
 #include "mm_codec.hpp"
 #include <chrono>
@@ -1068,6 +1070,37 @@ int mm_depth_fetch_windows(const mm_depth* r, int64_t* sum, int64_t* covered) {
   return MM_OK;
 }
 void mm_depth_destroy(mm_depth* r) { delete r; }
+
+struct mm_errprof { mm::ErrprofResult r; };                        // (host memory only: the listed contigs and their rows)
+static_assert(MM_ERRPROF_COUNTERS == mmep::COUNTERS && MM_ERRPROF_COLS == mmep::COLS && MM_ERRPROF_STATS == mmep::STATS, "the header's constants are the definition's");
+int mm_errprof_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
+                      const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, uint64_t* counters, int32_t* cols, uint64_t* ident_key) {
+  if (!ctx || !reads || !reference) return MM_ERR_ARG;
+  return guarded(ctx, [&] {
+    require_jobs("mm_errprof_events", n_jobs, read && strand && contig && dist && first && op_off && use && cols && ident_key);
+    MM_REQUIRE(counters, MM_ERR_ARG, "mm_errprof_events: a null array");
+    mm::errprof_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, counters, cols, ident_key);
+  });
+}
+int mm_errprof_finish(mm_ctx* ctx, int64_t n_contigs, int64_t n, const uint64_t* ident_key, const int32_t* cols, mm_errprof** out) {
+  if (!ctx || !out) return refused(out);
+  return created(ctx, out, [&](mm_errprof& r) {
+    require_rows("mm_errprof_finish", "entries", n, ident_key && cols);
+    mm::errprof_finish_run(ctx, n_contigs, n, ident_key, cols, &r.r);
+  });
+}
+int mm_errprof_sizes(const mm_errprof* r, int64_t* n_contigs) {
+  if (!r || !n_contigs) return MM_ERR_ARG;
+  *n_contigs = (int64_t)r->r.contig.size();
+  return MM_OK;
+}
+int mm_errprof_fetch(const mm_errprof* r, int32_t* contig, int64_t* stats) {
+  if (!r || !stats || (!r->r.contig.empty() && !contig)) return MM_ERR_ARG;
+  if (!r->r.contig.empty()) memcpy(contig, r->r.contig.data(), r->r.contig.size() * 4);
+  memcpy(stats, r->r.stats.data(), r->r.stats.size() * 8);
+  return MM_OK;
+}
+void mm_errprof_destroy(mm_errprof* r) { delete r; }
 
 // ---- communicator -------------------------------------------------------------------------------------
 int mm_comm_unique_id(char id[MM_COMM_ID_BYTES]) {

@@ -12,6 +12,11 @@ Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes pr
        python tools/edit_kernel_stats.py --qualities [n_reads] [--min-base-quality Q]   (writes profiles/qual_stats.txt)
        python tools/edit_kernel_stats.py --mods [n_reads]   (writes profiles/mods_stats.txt)
        python tools/edit_kernel_stats.py --depth [n_reads]  (writes profiles/depth_stats.txt)
+       python tools/edit_kernel_stats.py --error-profile [n_reads]   (writes profiles/errprof_stats.txt)
+--error-profile: the batch through mm_mapping_align, twice through mm_pileup_events (the MM_PILEUP_TIMING stage lines: the comparison) and in the same process
+through mm_errprof_events (mm_errprof_core.hpp, mm_errprof.hip) twice at the default number of workgroups and once each at G = 1, 2, 4, 8, 16 and 32 per CU
+(MM_ERRPROF_GROUPS; the MM_ERRPROF_TIMING lines have the upload, check, walk and sum stages), every result held equal to the first, then twice through
+mm_errprof_finish.  One run is one run.
 --mods: the batch fetched to the host and uploaded again without and with seeded modification groups (C+m? and A+a. on every C and A, ML uniform in 0 .. 255,
 independent of the bases): the upload's wall time both ways with the staged bytes (the MM_MODS_TIMING plane line), then in the same process mm_pileup_events
 and mm_mod_events twice each on the same alignments (the MM_PILEUP_TIMING and MM_MODS_TIMING stage lines), mm_mod_merge and mm_mod_finish with the table's
@@ -361,6 +366,60 @@ def child_depth(n_reads):
     M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
 
 
+def child_errprof(n_reads):
+    from metamaps_amd import capi
+    ctx = capi.Context(0)
+    cus = ctx.device_info()["cus"]
+    ref = ctx.synth_reference(seed=20260928, n_species=25, strains_per_species=4, genome_len=2_200_000, strain_divergence=0.02, genus_divergence=0.2)
+    w = capi.lib().mm_recommended_window(1e-3, K, PI, 1000, ref.total_bases)
+    idx = ctx.index(ref, K, w)
+    reads, _ = ctx.synth_reads(ref, seed=1000, n_reads=n_reads, read_len=READ_LEN, read_len_min=0, sub_rate=0.04, ins_rate=0.03, del_rate=0.05, frac_random=0.05, n_abundant=100)
+    M = ctx.map_batch(idx, reads, K, w, pi=PI)
+    M.keep_best(K)
+    off, rec = M.fetch()
+    n = len(rec)
+    print(f"{n_reads} reads of {READ_LEN} bases against {ref.total_bases} reference bases (k {K}, w {w}, pi {PI}): {n} best mappings; {cus} CUs", flush=True)
+    dist, first, last, op_off, ops = ctx.mapping_align(M, reads, ref, PI)
+    print(f"mm_mapping_align: {int((dist >= 0).sum())} of {n} aligned, {len(ops)} runs ({4 * len(ops) / 1e6:.1f} MB)", flush=True)
+    args = dict(read=rec["read"], strand=rec["strand"].astype(np.int32), contig=rec["ref_contig"], dist=dist, first=first, op_off=op_off, ops=ops, use=np.ones(n, dtype=np.uint8))
+    for rep in range(2):
+        t0 = time.perf_counter()
+        keys, counts = ctx.pileup_events(reads, ref, **args)
+        dt = time.perf_counter() - t0
+        print(f"mm_pileup_events call {rep}: {1e3 * dt:.1f} ms wall with the copies, {len(keys)} pairs of {int(counts.sum())} events", flush=True)
+    del keys, counts
+    want = None
+    for per_cu in (None, None, 1, 2, 4, 8, 16, 32):                # the default twice (the first call loads the kernels), then G = per_cu * CUs
+        if per_cu is None:
+            os.environ.pop("MM_ERRPROF_GROUPS", None)
+        else:
+            os.environ["MM_ERRPROF_GROUPS"] = str(per_cu * cus)
+        t0 = time.perf_counter()
+        got = ctx.errprof_events(reads, ref, **args)
+        dt = time.perf_counter() - t0
+        want = got if want is None else want
+        assert all(np.array_equal(a, b) for a, b in zip(got, want))   # no result depends on G
+        print(f"mm_errprof_events call at {'the default G' if per_cu is None else f'G = {per_cu} x {cus}'}: {1e3 * dt:.1f} ms wall with the copies", flush=True)
+    os.environ.pop("MM_ERRPROF_GROUPS", None)
+    counters, cols, ident = want
+    used = ident != np.uint64(0xFFFFFFFFFFFFFFFF)
+    sub = counters[:25].reshape(5, 5)
+    assert int(used.sum()) == int((dist >= 0).sum()) and int(sub.sum()) == int(cols[:, 0].sum() + cols[:, 1].sum()) and int(counters[281:281 + 95].sum()) == int(cols[:, 0].sum())
+    assert int(counters[281 + 190:].sum()) == int(cols[:, 3].sum()) and int(counters[25:25 + 128].sum()) == int(cols[:, 2].sum()) and int(counters[25 + 128:281].sum()) == int(cols[:, 4].sum())
+    tot = cols.sum(axis=0)
+    print(f"{int(used.sum())} alignments: {int(tot[0])} matches, {int(tot[1])} mismatches, {int(tot[2])} insertions of {int(tot[3])} bases, {int(tot[4])} deletions of {int(tot[5])} bases; "
+          f"{int(np.trace(sub))} columns on the diagonal; homopolymer insertions {int(counters[25 + 64:25 + 128].sum())}, deletions {int(counters[25 + 192:281].sum())}", flush=True)
+    for rep in range(2):
+        t0 = time.perf_counter()
+        contig, stats = ctx.errprof_finish(len(ref.lengths()), ident, cols)
+        dt = time.perf_counter() - t0
+        assert int(stats[:-1, 0].sum()) == int(stats[-1, 0]) == int(used.sum()) and np.array_equal(stats[:-1, 1:7].sum(axis=0), stats[-1, 1:7])
+        print(f"mm_errprof_finish call {rep}: {1e3 * dt:.1f} ms wall with the copies and the host's pass over the keys, {len(contig)} contigs listed; identity of all alignments "
+              f"{stats[-1, 1] / max(int(stats[-1, 1] + stats[-1, 2] + stats[-1, 4] + stats[-1, 6]), 1):.6f}, per-alignment min {stats[-1, 7] / 1e6:.6f} median {stats[-1, 9] / 1e6:.6f} "
+              f"max {stats[-1, 11] / 1e6:.6f}", flush=True)
+    M.close(); idx.close(); reads.close(); ref.close(); ctx.close()
+
+
 def child_qual(n_reads, floor):
     from metamaps_amd import capi
     ctx = capi.Context(0)
@@ -510,6 +569,19 @@ def main():
         if p.returncode != 0:
             sys.exit(p.returncode)
         with open(os.path.join(ROOT, "profiles", "mods_stats.txt"), "w") as f:
+            f.write(text)
+        return None
+    if len(sys.argv) > 1 and sys.argv[1] == "--child-error-profile":
+        return child_errprof(int(sys.argv[2]))
+    if len(sys.argv) > 1 and sys.argv[1] == "--error-profile":
+        n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-error-profile", str(n_reads)], env=dict(os.environ, MM_PILEUP_TIMING="1", MM_ERRPROF_TIMING="1"),
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1100)
+        text = f"tools/edit_kernel_stats.py --error-profile {n_reads}: one batch of {n_reads} reads, best mappings only; one run\n" + p.stdout.decode()
+        print(text)
+        if p.returncode != 0:
+            sys.exit(p.returncode)
+        with open(os.path.join(ROOT, "profiles", "errprof_stats.txt"), "w") as f:
             f.write(text)
         return None
     if len(sys.argv) > 1 and sys.argv[1] == "--child-depth":
