@@ -285,6 +285,24 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _aligned_jobs(read, strand, contig, dist, first, op_off, ops, use=None):
+    """(n, the contiguous arrays in the order of the C arguments) of a batch's aligned jobs, with `use` behind them where the call takes it"""
+    cols = [np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist)]
+    cols += [np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64), np.ascontiguousarray(ops, dtype=np.uint32)]
+    if use is not None:
+        cols.append(np.ascontiguousarray(use, dtype=np.uint8))
+    n = len(cols[0])
+    assert all(len(x) == n for x in cols[1:5] + cols[7:]) and len(cols[5]) == n + 1
+    return n, cols
+
+
+def _table_rows(*words_and_counts):
+    """(n, the contiguous arrays) of the rows of a key table: one or two columns of key words and the counts"""
+    cols = [np.ascontiguousarray(x, dtype=np.uint64) for x in words_and_counts[:-1]] + [np.ascontiguousarray(words_and_counts[-1], dtype=np.uint32)]
+    assert all(len(x) == len(cols[0]) for x in cols)
+    return len(cols[0]), cols
+
+
 class Context:
     def __init__(self, device: int = 0):
         self.h = C.c_void_p()
@@ -664,17 +682,14 @@ class Context:
 
     def _bam_encode(self, entry, reads, reference, read, strand, contig, dist, first, op_off, ops, flag, mapq, names, group_bytes=0):
         """one of the two encoders: (members, records, raw bytes, job per record, offset per record and the end)"""
-        rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
-        fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
-        op, fl, mq = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(flag, dtype=np.uint16), np.ascontiguousarray(mapq, dtype=np.uint8)
-        n = len(rd)
-        assert all(len(x) == n for x in (sd, cg, ds, fs, fl, mq, names)) and len(oo) == n + 1
+        n, jobs = _aligned_jobs(read, strand, contig, dist, first, op_off, ops)
+        fl, mq = np.ascontiguousarray(flag, dtype=np.uint16), np.ascontiguousarray(mapq, dtype=np.uint8)
+        assert all(len(x) == n for x in (fl, mq, names))
         no = np.zeros(n + 1, dtype=np.int64)
         np.cumsum([len(x) for x in names], out=no[1:])
         text = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8).copy()
         h = C.c_void_p(0xDEAD)                                      # (the call sets it, to NULL on an error)
-        st = entry(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(fl), _ptr(mq), _ptr(no),
-                   _ptr(text), int(group_bytes), C.byref(h))
+        st = entry(self.h, reads.h, reference.h, n, *map(_ptr, jobs), _ptr(fl), _ptr(mq), _ptr(no), _ptr(text), int(group_bytes), C.byref(h))
         try:
             self.check(st)
             nr, raw, nb = C.c_int64(-1), C.c_int64(-1), C.c_int64(-1)
@@ -689,43 +704,39 @@ class Context:
             if h.value:
                 lib().mm_bam_destroy(h)
 
-    def _pileup_table(self, status, handle):
-        """(keys, counts) of an mm_pileup, which is destroyed; `handle` is NULL after an error"""
+    def _key_table(self, kind, status, handle):
+        """(keys, counts) of an mm_pileup or an mm_mod, (w0, w1, counts) of an mm_vcf, which is destroyed (kind: "pileup", "mod", "vcf"); `handle` is NULL after
+        an error"""
         try:
             self.check(status)
             n = C.c_int64(-1)
-            assert lib().mm_pileup_sizes(handle, C.byref(n)) == 0
-            keys, counts = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint32)
-            assert lib().mm_pileup_fetch(handle, _ptr(keys), _ptr(counts)) == 0
-            return keys, counts
+            assert getattr(lib(), f"mm_{kind}_sizes")(handle, C.byref(n)) == 0
+            words = [np.zeros(n.value, dtype=np.uint64) for _ in range(2 if kind == "vcf" else 1)]
+            counts = np.zeros(n.value, dtype=np.uint32)
+            assert getattr(lib(), f"mm_{kind}_fetch")(handle, *map(_ptr, words), _ptr(counts)) == 0
+            return (*words, counts)
         finally:
-            self.last_pileup_handle = handle.value                  # (what the call left in *out: None after a refusal)
+            setattr(self, f"last_{kind}_handle", handle.value)      # (what the call left in *out: None after a refusal)
             if handle.value:
-                lib().mm_pileup_destroy(handle)
+                getattr(lib(), f"mm_{kind}_destroy")(handle)
 
     def pileup_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use, min_base_quality=None):
         """the pileup events of the jobs with use != 0 and dist >= 0 (mm_pileup_events): (keys, counts), keys contig << 35 | pos << 3 | code unique
         and ascending, code A 0 C 1 G 2 T 3 N 4, a deleted base 5, an insertion behind the base 6.  min_base_quality: mm_pileup_events_q's floor"""
-        rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
-        fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
-        op, us = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(use, dtype=np.uint8)
-        n = len(rd)
-        assert all(len(x) == n for x in (sd, cg, ds, fs, us)) and len(oo) == n + 1
+        n, jobs = _aligned_jobs(read, strand, contig, dist, first, op_off, ops, use)
         h = C.c_void_p(0xDEAD)                                      # (the call sets it, to NULL on an error)
         if min_base_quality is None:
-            st = lib().mm_pileup_events(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), C.byref(h))
+            st = lib().mm_pileup_events(self.h, reads.h, reference.h, n, *map(_ptr, jobs), C.byref(h))
         else:
-            st = lib().mm_pileup_events_q(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), int(min_base_quality),
-                                          C.byref(h))
-        return self._pileup_table(st, h)
+            st = lib().mm_pileup_events_q(self.h, reads.h, reference.h, n, *map(_ptr, jobs), int(min_base_quality), C.byref(h))
+        return self._key_table("pileup", st, h)
 
     def pileup_merge(self, keys, counts):
         """any (key, count) pairs, unsorted, keys may repeat -> the table with equal keys summed (mm_pileup_merge)"""
-        ks, cs = np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(counts, dtype=np.uint32)
-        assert len(ks) == len(cs)
+        n, rows = _table_rows(keys, counts)
         h = C.c_void_p(0xDEAD)
-        st = lib().mm_pileup_merge(self.h, len(ks), _ptr(ks), _ptr(cs), C.byref(h))
-        return self._pileup_table(st, h)
+        st = lib().mm_pileup_merge(self.h, n, *map(_ptr, rows), C.byref(h))
+        return self._key_table("pileup", st, h)
 
     def pileup_finish(self, reference: "SeqSet", keys, counts, iv_contig, iv_first, iv_last, min_count=3, min_frac=0.2):
         """the kept sites of a merged table and every contig's coverage from the intervals of all contributing alignments (mm_pileup_finish): a dict with
@@ -751,37 +762,20 @@ class Context:
             if h.value:
                 lib().mm_pileup_result_destroy(h)
 
-    def _mod_table(self, status, handle):
-        """(keys, counts) of an mm_mod, which is destroyed; `handle` is NULL after an error"""
-        try:
-            self.check(status)
-            n = C.c_int64()
-            assert lib().mm_mod_sizes(handle, C.byref(n)) == 0
-            keys, counts = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint32)
-            assert lib().mm_mod_fetch(handle, _ptr(keys), _ptr(counts)) == 0
-            return keys, counts
-        finally:
-            self.last_mod_handle = handle.value                     # (what the call left in *out: None after a refusal)
-            if handle:
-                lib().mm_mod_destroy(handle)
-
     def mod_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use, min_ml=204):
         """the modification events of the jobs with use != 0 and dist >= 0 (mm_mod_events): (keys, counts), keys contig << 36 | pos << 4 |
         (strand < 0) << 3 | class unique and ascending, class 0 canonical, 1 fail (prob < min_ml), 2 another code, 3 + code"""
-        n = len(read)
-        rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
-        fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
-        op, us = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(use, dtype=np.uint8)
+        n, jobs = _aligned_jobs(read, strand, contig, dist, first, op_off, ops, use)
         h = C.c_void_p(0xDEAD)
-        st = lib().mm_mod_events(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), int(min_ml), C.byref(h))
-        return self._mod_table(st, h)
+        st = lib().mm_mod_events(self.h, reads.h, reference.h, n, *map(_ptr, jobs), int(min_ml), C.byref(h))
+        return self._key_table("mod", st, h)
 
     def mod_merge(self, keys, counts):
         """any (key, count) pairs, unsorted, keys may repeat -> the table with equal keys summed (mm_mod_merge)"""
-        ks, cs = np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(counts, dtype=np.uint32)
+        n, rows = _table_rows(keys, counts)
         h = C.c_void_p(0xDEAD)
-        st = lib().mm_mod_merge(self.h, len(ks), _ptr(ks), _ptr(cs), C.byref(h))
-        return self._mod_table(st, h)
+        st = lib().mm_mod_merge(self.h, n, *map(_ptr, rows), C.byref(h))
+        return self._key_table("mod", st, h)
 
     def mod_finish(self, reference: "SeqSet", keys, counts, code_base, min_coverage=1):
         """the rows of a merged table (mm_mod_finish); code_base: the base letters of the asked codes, e.g. "CCA".  A dict of arrays: site (the
@@ -802,44 +796,24 @@ class Context:
             if h:
                 lib().mm_mod_result_destroy(h)
 
-    def _vcf_table(self, status, handle):
-        """(w0, w1, counts) of an mm_vcf, which is destroyed; `handle` is NULL after an error"""
-        try:
-            self.check(status)
-            n = C.c_int64(-1)
-            assert lib().mm_vcf_sizes(handle, C.byref(n)) == 0
-            w0, w1, counts = np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint32)
-            assert lib().mm_vcf_fetch(handle, _ptr(w0), _ptr(w1), _ptr(counts)) == 0
-            return w0, w1, counts
-        finally:
-            self.last_vcf_handle = handle.value                     # (what the call left in *out: None after a refusal)
-            if handle.value:
-                lib().mm_vcf_destroy(handle)
-
     def vcf_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use, min_base_quality=None):
         """the left-aligned alleles of the jobs with use != 0 and dist >= 0 (mm_vcf_events): (w0, w1, counts), keys unique and ascending by (w0, w1);
         w0 = contig << 35 | pos << 3 | code (the alt's 0-3, a deletion 5, an insertion 6), w1 = 0, the deletion's length, or the insertion's length << 48
         | its bases (2 bits each, up to 24).  min_base_quality: mm_vcf_events_q's floor"""
-        rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
-        fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
-        op, us = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(use, dtype=np.uint8)
-        n = len(rd)
-        assert all(len(x) == n for x in (sd, cg, ds, fs, us)) and len(oo) == n + 1
+        n, jobs = _aligned_jobs(read, strand, contig, dist, first, op_off, ops, use)
         h = C.c_void_p(0xDEAD)                                      # (the call sets it, to NULL on an error)
         if min_base_quality is None:
-            st = lib().mm_vcf_events(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), C.byref(h))
+            st = lib().mm_vcf_events(self.h, reads.h, reference.h, n, *map(_ptr, jobs), C.byref(h))
         else:
-            st = lib().mm_vcf_events_q(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), int(min_base_quality),
-                                       C.byref(h))
-        return self._vcf_table(st, h)
+            st = lib().mm_vcf_events_q(self.h, reads.h, reference.h, n, *map(_ptr, jobs), int(min_base_quality), C.byref(h))
+        return self._key_table("vcf", st, h)
 
     def vcf_merge(self, w0, w1, counts):
         """any (w0, w1, count) triples, unsorted, keys may repeat -> the table with equal keys summed (mm_vcf_merge)"""
-        a, b, cs = np.ascontiguousarray(w0, dtype=np.uint64), np.ascontiguousarray(w1, dtype=np.uint64), np.ascontiguousarray(counts, dtype=np.uint32)
-        assert len(a) == len(b) == len(cs)
+        n, rows = _table_rows(w0, w1, counts)
         h = C.c_void_p(0xDEAD)
-        st = lib().mm_vcf_merge(self.h, len(a), _ptr(a), _ptr(b), _ptr(cs), C.byref(h))
-        return self._vcf_table(st, h)
+        st = lib().mm_vcf_merge(self.h, n, *map(_ptr, rows), C.byref(h))
+        return self._key_table("vcf", st, h)
 
     def vcf_finish(self, reference: "SeqSet", w0, w1, counts, iv_contig, iv_first, iv_last, min_count=3, min_frac=0.2):
         """the kept alleles of a merged table, their depths from the intervals of all contributing alignments and their reference windows (mm_vcf_finish):
@@ -918,14 +892,9 @@ class Context:
     def errprof_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use):
         """the error profile of the jobs with use != 0 and dist >= 0 (mm_errprof_events): (counters, cols, ident_key) with ERRPROF_COUNTERS sums in the order
         SUB[25], INDEL[kind][hp][64], QUAL[cls][95], per job eq, x, insRuns, insBases, delRuns, delBases and contig << 32 | ppm (~0 for a job that is not used)"""
-        rd, sd, cg, ds = (np.ascontiguousarray(x, dtype=np.int32) for x in (read, strand, contig, dist))
-        fs, oo = np.ascontiguousarray(first, dtype=np.int64), np.ascontiguousarray(op_off, dtype=np.int64)
-        op, us = np.ascontiguousarray(ops, dtype=np.uint32), np.ascontiguousarray(use, dtype=np.uint8)
-        n = len(rd)
-        assert all(len(x) == n for x in (sd, cg, ds, fs, us)) and len(oo) == n + 1
+        n, jobs = _aligned_jobs(read, strand, contig, dist, first, op_off, ops, use)
         counters, cols, keys = np.full(ERRPROF_COUNTERS, 0xDEAD, dtype=np.uint64), np.full((n, ERRPROF_COLS), -1, dtype=np.int32), np.full(n, 0xDEAD, dtype=np.uint64)
-        self.check(lib().mm_errprof_events(self.h, reads.h, reference.h, n, _ptr(rd), _ptr(sd), _ptr(cg), _ptr(ds), _ptr(fs), _ptr(oo), _ptr(op), _ptr(us), _ptr(counters),
-                                           _ptr(cols), _ptr(keys)))
+        self.check(lib().mm_errprof_events(self.h, reads.h, reference.h, n, *map(_ptr, jobs), _ptr(counters), _ptr(cols), _ptr(keys)))
         return counters, cols, keys
 
     def errprof_finish(self, n_contigs, ident_key, cols):

@@ -82,8 +82,34 @@ void require_finish(const char* who, int64_t n, int64_t n_iv, bool rows, bool in
              std::string(who) + ": a negative number of entries or intervals, or 2^32 or more");
   MM_REQUIRE((n == 0 || rows) && (n_iv == 0 || intervals), MM_ERR_ARG, std::string(who) + ": a null array");
 }
-// the rows of a key table (mm_pileup, mm_vcf) into the caller's arrays; w1: null for a table of one-word keys
-int table_fetch(const mm::KeyTable& t, uint64_t* w0, uint64_t* w1, uint32_t* counts) {
+// The handles of the three key tables (host memory only, as mm_alignment) and the entry points they share; mm_pileup, mm_mod and mm_vcf below are this and
+// nothing else.  One-word keys: t.w1 stays empty, and w1 is null in every call.
+template <bool TwoWords> struct key_table { static constexpr bool two_words = TwoWords; mm::KeyTable t; };
+using EventsRun = void (*)(mm_ctx*, const mm_seqset*, const mm_seqset*, const mm::AlignedJobsIn&, const uint8_t*, int32_t, mm::KeyTable*);
+template <typename H>
+int table_events(const char* who, EventsRun run, mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, const mm::AlignedJobsIn& in, const uint8_t* use, int32_t param, H** out) {
+  if (!ctx || !reads || !reference || !out) return refused(out);
+  return created(ctx, out, [&](H& h) {
+    require_jobs(who, in.n_jobs, in.read && in.strand && in.contig && in.dist && in.first && in.op_off && use);
+    run(ctx, reads, reference, in, use, param, &h.t);
+  });
+}
+template <typename H>
+int table_merge(const char* who, const char* rows, const char* timing_env, mm_ctx* ctx, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, H** out) {
+  if (!ctx || !out) return refused(out);
+  return created(ctx, out, [&](H& h) {
+    require_rows(who, rows, n, w0 && counts && (w1 || !H::two_words));
+    mm::merge_run(ctx, n, w0, w1, counts, who, timing_env, &h.t);
+  });
+}
+template <typename H> int table_sizes(const H* h, int64_t* n_rows) {
+  if (!h || !n_rows) return MM_ERR_ARG;
+  *n_rows = (int64_t)h->t.w0.size();
+  return MM_OK;
+}
+template <typename H> int table_fetch(const H* h, uint64_t* w0, uint64_t* w1, uint32_t* counts) {
+  if (!h) return MM_ERR_ARG;
+  const mm::KeyTable& t = h->t;
   const size_t k = t.w0.size();
   if (k && (!w0 || !counts || (!t.w1.empty() && !w1))) return MM_ERR_ARG;
   if (k) { memcpy(w0, t.w0.data(), k * 8); memcpy(counts, t.counts.data(), k * 4); }
@@ -850,33 +876,21 @@ int mm_bam_sorter_fetch(const mm_bam_sorter* h, uint8_t* out) {
   return MM_OK;
 }
 
-struct mm_pileup { mm::KeyTable t; };                              // (host memory only, as mm_alignment; one-word keys: t.w1 stays empty)
+struct mm_pileup : key_table<false> {};
 struct mm_pileup_result { mm::PileupResult r; };
 int mm_pileup_events_q(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
                        const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, int32_t min_base_quality, mm_pileup** out) {
-  if (!ctx || !reads || !reference || !out) return refused(out);
-  return created(ctx, out, [&](mm_pileup& t) {
-    require_jobs("mm_pileup_events", n_jobs, read && strand && contig && dist && first && op_off && use);
-    mm::pileup_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, min_base_quality, &t.t);
-  });
+  return table_events("mm_pileup_events", mm::pileup_events_run, ctx, reads, reference, {n_jobs, read, strand, contig, dist, first, op_off, ops}, use, min_base_quality, out);
 }
 int mm_pileup_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
                      const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, mm_pileup** out) {
   return mm_pileup_events_q(ctx, reads, reference, n_jobs, read, strand, contig, dist, first, op_off, ops, use, 0, out);
 }
 int mm_pileup_merge(mm_ctx* ctx, int64_t n, const uint64_t* keys, const uint32_t* counts, mm_pileup** out) {
-  if (!ctx || !out) return refused(out);
-  return created(ctx, out, [&](mm_pileup& t) {
-    require_rows("mm_pileup_merge", "pairs", n, keys && counts);
-    mm::merge_run(ctx, n, keys, nullptr, counts, "mm_pileup_merge", "MM_PILEUP_TIMING", &t.t);
-  });
+  return table_merge("mm_pileup_merge", "pairs", "MM_PILEUP_TIMING", ctx, n, keys, nullptr, counts, out);
 }
-int mm_pileup_sizes(const mm_pileup* t, int64_t* n_pairs) {
-  if (!t || !n_pairs) return MM_ERR_ARG;
-  *n_pairs = (int64_t)t->t.w0.size();
-  return MM_OK;
-}
-int mm_pileup_fetch(const mm_pileup* t, uint64_t* keys, uint32_t* counts) { return t ? table_fetch(t->t, keys, nullptr, counts) : MM_ERR_ARG; }
+int mm_pileup_sizes(const mm_pileup* t, int64_t* n_pairs) { return table_sizes(t, n_pairs); }
+int mm_pileup_fetch(const mm_pileup* t, uint64_t* keys, uint32_t* counts) { return table_fetch(t, keys, nullptr, counts); }
 void mm_pileup_destroy(mm_pileup* t) { delete t; }
 int mm_pileup_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* keys, const uint32_t* counts, int64_t n_iv, const int32_t* iv_contig,
                      const int64_t* iv_first, const int64_t* iv_last, int64_t min_count, double min_frac, mm_pileup_result** out) {
@@ -905,29 +919,17 @@ int mm_pileup_result_fetch_contigs(const mm_pileup_result* r, int64_t* alignment
 }
 void mm_pileup_result_destroy(mm_pileup_result* r) { delete r; }
 
-struct mm_mod { mm::KeyTable t; };                                 // (host memory only, as mm_pileup; one-word keys)
+struct mm_mod : key_table<false> {};
 struct mm_mod_result { mm::ModResult r; };
 int mm_mod_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
                   const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, int32_t min_ml, mm_mod** out) {
-  if (!ctx || !reads || !reference || !out) return refused(out);
-  return created(ctx, out, [&](mm_mod& t) {
-    require_jobs("mm_mod_events", n_jobs, read && strand && contig && dist && first && op_off && use);
-    mm::mod_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, min_ml, &t.t);
-  });
+  return table_events("mm_mod_events", mm::mod_events_run, ctx, reads, reference, {n_jobs, read, strand, contig, dist, first, op_off, ops}, use, min_ml, out);
 }
 int mm_mod_merge(mm_ctx* ctx, int64_t n, const uint64_t* keys, const uint32_t* counts, mm_mod** out) {
-  if (!ctx || !out) return refused(out);
-  return created(ctx, out, [&](mm_mod& t) {
-    require_rows("mm_mod_merge", "pairs", n, keys && counts);
-    mm::merge_run(ctx, n, keys, nullptr, counts, "mm_mod_merge", "MM_MODS_TIMING", &t.t);
-  });
+  return table_merge("mm_mod_merge", "pairs", "MM_MODS_TIMING", ctx, n, keys, nullptr, counts, out);
 }
-int mm_mod_sizes(const mm_mod* t, int64_t* n_pairs) {
-  if (!t || !n_pairs) return MM_ERR_ARG;
-  *n_pairs = (int64_t)t->t.w0.size();
-  return MM_OK;
-}
-int mm_mod_fetch(const mm_mod* t, uint64_t* keys, uint32_t* counts) { return t ? table_fetch(t->t, keys, nullptr, counts) : MM_ERR_ARG; }
+int mm_mod_sizes(const mm_mod* t, int64_t* n_pairs) { return table_sizes(t, n_pairs); }
+int mm_mod_fetch(const mm_mod* t, uint64_t* keys, uint32_t* counts) { return table_fetch(t, keys, nullptr, counts); }
 void mm_mod_destroy(mm_mod* t) { delete t; }
 int mm_mod_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* keys, const uint32_t* counts, int32_t n_codes, const uint8_t* code_base, int64_t min_coverage,
                   mm_mod_result** out) {
@@ -954,33 +956,21 @@ int mm_mod_result_fetch(const mm_mod_result* r, uint64_t* site, uint64_t* n_mod,
 }
 void mm_mod_result_destroy(mm_mod_result* r) { delete r; }
 
-struct mm_vcf { mm::KeyTable t; };                                 // (host memory only, as mm_pileup; two-word keys)
+struct mm_vcf : key_table<true> {};
 struct mm_vcf_result { mm::VcfResult r; };
 int mm_vcf_events_q(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
                     const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, int32_t min_base_quality, mm_vcf** out) {
-  if (!ctx || !reads || !reference || !out) return refused(out);
-  return created(ctx, out, [&](mm_vcf& t) {
-    require_jobs("mm_vcf_events", n_jobs, read && strand && contig && dist && first && op_off && use);
-    mm::vcf_events_run(ctx, reads, reference, mm::AlignedJobsIn{n_jobs, read, strand, contig, dist, first, op_off, ops}, use, min_base_quality, &t.t);
-  });
+  return table_events("mm_vcf_events", mm::vcf_events_run, ctx, reads, reference, {n_jobs, read, strand, contig, dist, first, op_off, ops}, use, min_base_quality, out);
 }
 int mm_vcf_events(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, int64_t n_jobs, const int32_t* read, const int32_t* strand, const int32_t* contig,
                   const int32_t* dist, const int64_t* first, const int64_t* op_off, const uint32_t* ops, const uint8_t* use, mm_vcf** out) {
   return mm_vcf_events_q(ctx, reads, reference, n_jobs, read, strand, contig, dist, first, op_off, ops, use, 0, out);
 }
 int mm_vcf_merge(mm_ctx* ctx, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, mm_vcf** out) {
-  if (!ctx || !out) return refused(out);
-  return created(ctx, out, [&](mm_vcf& t) {
-    require_rows("mm_vcf_merge", "triples", n, w0 && w1 && counts);
-    mm::merge_run(ctx, n, w0, w1, counts, "mm_vcf_merge", "MM_VCF_TIMING", &t.t);
-  });
+  return table_merge("mm_vcf_merge", "triples", "MM_VCF_TIMING", ctx, n, w0, w1, counts, out);
 }
-int mm_vcf_sizes(const mm_vcf* t, int64_t* n_triples) {
-  if (!t || !n_triples) return MM_ERR_ARG;
-  *n_triples = (int64_t)t->t.w0.size();
-  return MM_OK;
-}
-int mm_vcf_fetch(const mm_vcf* t, uint64_t* w0, uint64_t* w1, uint32_t* counts) { return t ? table_fetch(t->t, w0, w1, counts) : MM_ERR_ARG; }
+int mm_vcf_sizes(const mm_vcf* t, int64_t* n_triples) { return table_sizes(t, n_triples); }
+int mm_vcf_fetch(const mm_vcf* t, uint64_t* w0, uint64_t* w1, uint32_t* counts) { return table_fetch(t, w0, w1, counts); }
 void mm_vcf_destroy(mm_vcf* t) { delete t; }
 int mm_vcf_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, int64_t n_iv, const int32_t* iv_contig,
                   const int64_t* iv_first, const int64_t* iv_last, int64_t min_count, double min_frac, mm_vcf_result** out) {

@@ -106,13 +106,12 @@ void errprof_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* re
 
   clk.start();
   const AlignedJobs J = jobs.upload(st);
-  DBuf<uint8_t> d_use(k);
-  d_use.upload(use, k, st);
+  const uint8_t* const d_use = jobs.upload_use(use, st);
   clk.stop(0);
 
   clk.start();
   for_job_grids(0, n, [&](int64_t a, dim3 grid) {
-    errprof_check_kernel<<<grid, dim3(64), 0, st>>>(reads->d_len.p, reads->count(), ref->d_len.p, ref->count(), J, d_use.p, a, jobs.err.p);
+    errprof_check_kernel<<<grid, dim3(64), 0, st>>>(reads->d_len.p, reads->count(), ref->d_len.p, ref->count(), J, d_use, a, jobs.err.p);
   });
   jobs.require_no_error(st, mmp::rule_text);
   clk.stop(1);
@@ -122,7 +121,7 @@ void errprof_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* re
   DBuf<unsigned long long> d_part((size_t)groups * mmep::COUNTERS), d_counters(mmep::COUNTERS);
   DBuf<int32_t> d_cols(k * mmep::COLS); DBuf<uint64_t> d_keys(k);
   d_part.zero(st);
-  errprof_walk_kernel<<<dim3((unsigned)groups), dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, reads->qual_ptr(), edit_seq(ref), ref->d_base.p, ref->d_len.p, J, d_use.p,
+  errprof_walk_kernel<<<dim3((unsigned)groups), dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, reads->qual_ptr(), edit_seq(ref), ref->d_base.p, ref->d_len.p, J, d_use,
                                                                    d_part.p, d_cols.p, d_keys.p); MM_KERNEL_CHECK();
   clk.stop(2);
 

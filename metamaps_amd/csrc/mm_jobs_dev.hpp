@@ -1,6 +1,7 @@
-// A batch's aligned jobs on the device, once for every output that walks them (mm_bam.hip, mm_pileup.hip, mm_vcf.hip; DESIGN.md section 1, "Aligned jobs"):
-// the lane policy of their one-wavefront-per-job kernels, the byte view of a sequence, the jobs' common arrays with their checks and uploads, the launch loop
-// and the error word.  A column that one output alone reads (use; flag, mapq and the names) stays with that output, in a struct of its own beside AlignedJobs.
+// A batch's aligned jobs on the device, once for every output that walks them (mm_bam.hip, mm_pileup.hip, mm_vcf.hip, mm_mods.hip, mm_errprof.hip; DESIGN.md
+// section 1, "Aligned jobs"): the lane policy of their one-wavefront-per-job kernels, the byte view of a sequence, the jobs' common arrays with their checks and
+// uploads, the launch loop and the error word.  `use`, one byte per job that every output but BAM reads, is an optional column of AlignedJobsDev and a plain
+// pointer beside AlignedJobs in a kernel's arguments; the columns that BAM alone reads (flag, mapq and the names) stay with it, in a struct of its own.
 #pragma once
 #include "mm_common.hpp"
 #include "mm_edit_seq.hpp"
@@ -39,7 +40,7 @@ struct SeqBytes {                                                 // read (or co
 constexpr unsigned long long JOB_NO_ERROR = ~0ull;
 constexpr int64_t JOB_GRID_MAX = (int64_t)1 << 30;                // workgroups per launch
 
-// the caller's arrays, as mm_bam_encode, mm_pileup_events and mm_vcf_events take them
+// the caller's arrays, as mm_bam_encode and the *_events entry points take them
 struct AlignedJobsIn {
   int64_t n_jobs; const int32_t* read; const int32_t* strand; const int32_t* contig; const int32_t* dist; const int64_t* first;
   const int64_t* op_off; const uint32_t* ops;
@@ -65,7 +66,7 @@ template <class Launch> void for_job_grids(int64_t job0, int64_t job1, Launch&& 
 // The owner of a call's jobs on the device.  who: the entry point's name, which every message starts with.
 struct AlignedJobsDev {
   const AlignedJobsIn in; const char* const who; size_t n_ops = 0;
-  DBuf<int32_t> read, strand, contig, dist; DBuf<int64_t> first, op_off; DBuf<uint32_t> ops;
+  DBuf<int32_t> read, strand, contig, dist; DBuf<int64_t> first, op_off; DBuf<uint32_t> ops; DBuf<uint8_t> use;
   DBuf<unsigned long long> err;                                  // the kernels' error word: the smallest (job << 4 | rule) of the jobs that break a rule
 
   // what is asked of the sets and of the arrays before anything is launched
@@ -84,6 +85,11 @@ struct AlignedJobsDev {
     op_off.upload(in.op_off, k + 1, st); ops.upload(in.ops, n_ops, st);
     MM_HIP(hipMemsetAsync(err.p, 0xFF, sizeof(unsigned long long), st));
     return AlignedJobs{in.n_jobs, read.p, strand.p, contig.p, dist.p, first.p, op_off.p, ops.p};
+  }
+  const uint8_t* upload_use(const uint8_t* u, hipStream_t st) {   // n_jobs > 0; the optional column, one byte per job: its place on the device
+    use.alloc((size_t)in.n_jobs);
+    use.upload(u, (size_t)in.n_jobs, st);
+    return use.p;
   }
   // The host reads the error word before anything else is launched: the kernels behind the first one trust what it checked.
   void require_no_error(hipStream_t st, const char* (*rule_text)(int)) const {

@@ -1,4 +1,5 @@
-// The key tables of the pileup and of the VCF on the device (mm_keytable.hpp; DESIGN.md section 1, "Key tables").
+// The key tables of the pileup, of the VCF and of the base modifications on the device (mm_keytable.hpp; DESIGN.md section 1, "Key tables"; the stages that
+// lead from a batch's jobs to sort and reduce: mm_events.hpp).
 //   sort     one-word keys: one radix sort of the keys over the bits in use (sort_pairs where counts ride along).  Two-word keys: two stable radix passes
 //            over an index, by w1 and then by w0, and the words (and counts) gathered behind the index.
 //   reduce   head flags, a scan and a scatter of (key, first index): mm_ident.hip's compaction.  A segment's count is its length, or the difference of one

@@ -1,6 +1,7 @@
-// A table of (key, count) rows whose key is one or two 64-bit words: the pileup's (key, count) pairs and the VCF's (w0, w1, count) triples, sorted, reduced,
-// merged and finished by one pipeline (mm_keytable.hip; DESIGN.md section 1, "Key tables").  Both key formats hold the contig and the position in w0
-// (mm_pileup_core.hpp: key_contig, key_pos), which is all the pipeline reads of a key; what a key means stays with mm_pileup.hip and mm_vcf.hip.
+// A table of (key, count) rows whose key is one or two 64-bit words: the pileup's and the modifications' (key, count) pairs and the VCF's (w0, w1, count)
+// triples, sorted, reduced, merged and finished by one pipeline (mm_keytable.hip; DESIGN.md section 1, "Key tables"; the events that fill a table:
+// mm_events.hpp).  The pipeline reads no field of a key but, in the finish, the contig and the position that the pileup's and the VCF's formats hold in w0
+// (mm_pileup_core.hpp: key_contig, key_pos); what a key means stays with mm_pileup.hip, mm_vcf.hip and mm_mods.hip.
 #pragma once
 #include "mm_common.hpp"
 #include "mm_edit_seq.hpp"
@@ -25,7 +26,7 @@ void sort_table(DBuf<uint8_t>& tmp, uint64_t* w0, uint64_t* w1, uint32_t* counts
 // The segments of equal keys of a sorted table of n > 0 rows into host memory: their keys, and their counts — the segments' lengths, or with s.counts the sums
 // of their counts.  Returns false where a sum passes 2^32 - 1.
 bool reduce_sorted(DBuf<uint8_t>& tmp, const SortedTable& s, int64_t n, hipStream_t st, KeyTable* out);
-// mm_pileup_merge and mm_vcf_merge (w1 null: one-word keys): the rows summed by key.  who: the entry point's name; timing_env: the variable that asks for
+// mm_pileup_merge, mm_mod_merge and mm_vcf_merge (w1 null: one-word keys): the rows summed by key.  who: the entry point's name; timing_env: the variable that asks for
 // the stage times, and the word its line starts with.
 void merge_run(mm_ctx* ctx, int64_t n, const uint64_t* w0, const uint64_t* w1, const uint32_t* counts, const char* who, const char* timing_env, KeyTable* out);
 

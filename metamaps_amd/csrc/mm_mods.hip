@@ -6,14 +6,15 @@
 //            base is named and gives its ML byte; the lane stores who | prob << 8.  Every trip count is an array length that the host has checked; an
 //            ordinal is compared and never used as an index.  A group that names an occurrence beyond the read's count of its base puts
 //            (sequence << 8 | group) into the error word with an atomic minimum; the host reads the word and drops the plane.
-//   events   mod_count_kernel: one wavefront per job applies the pileup's rules (mmp::count_job) and counts the calls under the job's = runs — a lane
-//            takes a run, all lanes a run of more than 64 columns; a scan places the jobs; mod_emit_kernel writes the keys: memory grows with the calls,
-//            a base without a call takes no slot.  Then one radix sort over the bits in use and the segments of equal keys (mm_keytable.hip).
+//   events   mm_events.hpp's pipeline (count, scan, emit, sort, reduce) over one-word keys with ModEvents.  mod_count_kernel: one wavefront per job applies
+//            the pileup's rules (mmp::count_job) and counts the calls under the job's = runs — a lane takes a run, all lanes a run of more than 64
+//            columns; mod_emit_kernel writes the keys: memory grows with the calls, a base without a call takes no slot.
 //   merge    mm_keytable.hip's merge_run over one-word keys (it reads no field of a key).
 //   finish   mod_rows_kernel twice: the head of every (contig, position, strand) segment counts its rows from its at most 7 entries and the packed
 //            reference's byte, a scan places them, the second launch writes them.
 // No kernel here waits for another workgroup; the only atomic is the error words' minimum.
 #include "mm_mods.hpp"
+#include "mm_events.hpp"
 #include "mm_prims.hpp"
 
 namespace mm {
@@ -175,59 +176,32 @@ void seqset_fetch_mods(mm_seqset* s, int64_t i, uint8_t* who, uint8_t* prob, int
   for (int64_t j = 0; j < L; ++j) { who[j] = (uint8_t)(v[(size_t)j] & 255u); prob[j] = (uint8_t)(v[(size_t)j] >> 8); }
 }
 
-void mod_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& in, const uint8_t* use, int32_t min_ml, KeyTable* out) {
-  AlignedJobsDev jobs(ctx, reads, ref, in, "mm_mod_events");
-  MM_REQUIRE(min_ml >= 0 && min_ml <= 255, MM_ERR_ARG, "mm_mod_events: min_ml is not in [0, 255]");
-  MM_REQUIRE(ref->count() <= mmd::MAX_CONTIGS, MM_ERR_ARG, "mm_mod_events: more than 2^28 contigs");
-  out->clear();
-  const int64_t n = in.n_jobs;
-  if (n == 0) return;
-  const size_t k = (size_t)n;
-  hipStream_t st = ctx->stream;
-  StageClock<6> clk(getenv("MM_MODS_TIMING") != nullptr, st);      // upload, count, scan, emit, sort, reduce (with the table's way to the host)
-
-  clk.start();
-  const AlignedJobs J = jobs.upload(st);
-  DBuf<int64_t> d_counts(k + 1), d_off(k + 1);
-  DBuf<uint8_t> d_use(k);
-  d_use.upload(use, k, st);
-  d_counts.zero(st);
-  clk.stop(0);
-
-  clk.start();
-  for_job_grids(0, n, [&](int64_t a, dim3 grid) {
-    mod_count_kernel<<<grid, dim3(64), 0, st>>>(reads->d_base.p, reads->d_len.p, reads->count(), ref->d_len.p, ref->count(), J, d_use.p, reads->mods_ptr(), min_ml, a, d_counts.p,
-                                                jobs.err.p);
-  });
-  jobs.require_no_error(st, mmp::rule_text);
-  clk.stop(1);
-
-  clk.start();
-  DBuf<uint8_t> tmp;
-  exclusive_scan(tmp, d_counts.p, d_off.p, k + 1, st);
-  int64_t total = 0;
-  d_off.download(&total, 1, st, k);
-  MM_HIP(mm::stream_sync(st));
-  clk.stop(2);
-  MM_REQUIRE(total < ((int64_t)1 << 32), MM_ERR_LIMIT, "mm_mod_events: 2^32 events or more in one call");
-  if (total > 0) {
-    clk.start();
-    DBuf<uint64_t> d_keys((size_t)total);
-    for_job_grids(0, n, [&](int64_t a, dim3 grid) {
-      mod_emit_kernel<<<grid, dim3(64), 0, st>>>(reads->d_base.p, reads->d_len.p, J, reads->mods_ptr(), min_ml, a, d_off.p, d_keys.p);
-    });
-    clk.stop(3);
-    clk.start();
-    SortedTable sorted;
-    sort_table(tmp, d_keys.p, nullptr, nullptr, total, mmd::CONTIG_SHIFT + contig_bits(ref->count()), 0, st, &sorted);
-    clk.stop(4);
-    clk.start();
-    reduce_sorted(tmp, sorted, total, st, out);
-    clk.stop(5);
+namespace {
+struct ModEvents {                                               // what mm_events.hpp's pipeline asks of a format
+  static constexpr const char* who = "mm_mod_events";
+  static constexpr const char* timing = "MM_MODS_TIMING";
+  static constexpr int32_t param_max = 255;
+  static constexpr const char* param_text = "mm_mod_events: min_ml is not in [0, 255]";
+  static constexpr int64_t max_contigs = mmd::MAX_CONTIGS;
+  static constexpr const char* contigs_text = "mm_mod_events: more than 2^28 contigs";
+  static constexpr int key_shift = mmd::CONTIG_SHIFT;
+  static constexpr bool two_words = false;
+  static constexpr const char* second = nullptr;
+  static constexpr uint64_t sentinel = 0;                          // (none: a base without a call takes no slot)
+  static bool cuts_sentinel(int32_t) { return false; }
+  static int32_t value(const mm_seqset*, int32_t min_ml) { return min_ml; }
+  static const char* rule_text(int rule) { return mmp::rule_text(rule); }
+  static void count(const EventsLaunch& L, int64_t a, dim3 grid) {
+    mod_count_kernel<<<grid, dim3(64), 0, L.st>>>(L.reads->d_base.p, L.reads->d_len.p, L.reads->count(), L.ref->d_len.p, L.ref->count(), L.J, L.use, L.reads->mods_ptr(), L.value, a, L.counts,
+                                                  L.err);
   }
-  if (clk.on)
-    fprintf(stderr, "MM_MODS_TIMING events: upload %.3f count %.3f scan %.3f emit %.3f sort %.3f reduce %.3f ms; %lld jobs, %lld runs, %lld events, %zu pairs, %zu B fetched\n", clk.ms[0],
-            clk.ms[1], clk.ms[2], clk.ms[3], clk.ms[4], clk.ms[5], (long long)n, (long long)jobs.n_ops, (long long)total, out->w0.size(), out->w0.size() * 12);
+  static void emit(const EventsLaunch& L, int64_t a, dim3 grid) {
+    mod_emit_kernel<<<grid, dim3(64), 0, L.st>>>(L.reads->d_base.p, L.reads->d_len.p, L.J, L.reads->mods_ptr(), L.value, a, L.off, L.w0);
+  }
+};
+}  // namespace
+void mod_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& in, const uint8_t* use, int32_t min_ml, KeyTable* out) {
+  key_events_run<ModEvents>(ctx, reads, ref, in, use, min_ml, out);
 }
 
 void mod_finish_run(mm_ctx* ctx, const mm_seqset* ref, int64_t n, const uint64_t* keys, const uint32_t* counts, int32_t n_codes, const uint8_t* code_base, int64_t min_coverage,

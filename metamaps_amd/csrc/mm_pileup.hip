@@ -1,21 +1,20 @@
 // The pileup of a run's alignments on the device (mm_pileup_events / _merge / _finish; mapDirectly --pileup; DESIGN.md section 1, "Pileup"; the
 // definition: mm_pileup_core.hpp, the text the host test runs).
-//   events   count    pile_count_kernel: one wavefront (a 64-thread workgroup) per job; the lanes stride over the runs, sum the job's events and apply the
-//                     rules.  A job that breaks one puts (job << 4 | rule) into the error word with an atomic minimum; the host reads the word before
-//                     anything else is launched.
-//            scan     an exclusive scan of the counts (mm_prims.hpp) places every job's events.
+//   events   mm_events.hpp's pipeline (count, scan, emit, sort, reduce) over one-word keys with PileupEvents:
+//            count    pile_count_kernel: one wavefront (a 64-thread workgroup) per job; the lanes stride over the runs, sum the job's events and apply the
+//                     rules.  A job that breaks one puts (job << 4 | rule) into the error word with an atomic minimum.
 //            emit     pile_emit_kernel: one wavefront per job over tiles of 64 runs; a wave scan of the run lengths gives each run its contig position,
 //                     its read index and its place; a lane expands its own short run, the wavefront a run of more than 64 events.  Read bases come
 //                     through EditSeq::byte on a set narrowed to the read.  Keys are stored as 8-byte words, nothing else is written.
-//            reduce   one radix sort of the keys over the bits in use, then the segments of equal keys with their lengths (mm_keytable.hip).
 //            floor    mm_pileup_events_q: the emit kernel reads the reads' quality plane beside the bases and writes mmp::DROPPED in the place of an event
-//                     under the floor; every bit of it in use is set, so it sorts last, and its segment is cut off the table.  Floor 0: nothing differs.
+//                     under the floor; its segment, the last, is cut off the table.  Floor 0: nothing differs.
 //   merge    mm_keytable.hip's merge_run over one-word keys: sort_pairs of (key, count) and the sums of the segments.
 //   finish   mm_keytable.hip's finish_kept with the reference's byte as a kept site's payload; per contig the alignments, the summed lengths and the
 //            union's length (each interval adds what lies beyond the running maximum of the ends before it, an inclusive max-scan) with 64-bit vector atomics.
 // No kernel here waits for another workgroup; the only atomics are the error word's minimum and the per-contig sums.
-// The jobs' arrays, their checks and the launch loop are mm_jobs_dev.hpp's, shared with mm_bam.hip and mm_vcf.hip.
+// The jobs' arrays, their checks and the launch loop are mm_jobs_dev.hpp's, shared with every output that walks the jobs.
 #include "mm_pileup.hpp"
+#include "mm_events.hpp"
 #include "mm_pileup_core.hpp"
 #include "mm_prims.hpp"
 
@@ -66,60 +65,29 @@ __global__ void __launch_bounds__(256) pile_coverage_kernel(const uint64_t* __re
   if (gain) atomicAdd(&covered[c], gain);
 }
 
-void pileup_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& in, const uint8_t* use, int32_t min_base_quality, KeyTable* out) {
-  AlignedJobsDev jobs(ctx, reads, ref, in, "mm_pileup_events");
-  MM_REQUIRE(min_base_quality >= 0 && min_base_quality <= 93, MM_ERR_ARG, "mm_pileup_events_q: min_base_quality is not in [0, 93]");
-  const int32_t qmin = reads->has_qual ? min_base_quality : 0;     // (reads without qualities pass every floor)
-  MM_REQUIRE(ref->count() <= mmp::MAX_CONTIGS, MM_ERR_ARG, "mm_pileup_events: more than 2^29 contigs");
-  out->clear();
-  const int64_t n = in.n_jobs;
-  if (n == 0) return;
-  const size_t k = (size_t)n;
-  hipStream_t st = ctx->stream;
-  StageClock<6> clk(getenv("MM_PILEUP_TIMING") != nullptr, st);    // upload, count, scan, emit, sort, reduce (with the table's way to the host)
-
-  clk.start();
-  const AlignedJobs J = jobs.upload(st);
-  DBuf<int64_t> d_counts(k + 1), d_off(k + 1);
-  DBuf<uint8_t> d_use(k);
-  d_use.upload(use, k, st);
-  d_counts.zero(st);
-  clk.stop(0);
-
-  clk.start();
-  for_job_grids(0, n, [&](int64_t a, dim3 grid) {
-    pile_count_kernel<<<grid, dim3(64), 0, st>>>(reads->d_len.p, reads->count(), ref->d_len.p, ref->count(), J, d_use.p, a, d_counts.p, jobs.err.p);
-  });
-  jobs.require_no_error(st, mmp::rule_text);
-  clk.stop(1);
-
-  clk.start();
-  DBuf<uint8_t> tmp;
-  exclusive_scan(tmp, d_counts.p, d_off.p, k + 1, st);
-  int64_t total = 0;
-  d_off.download(&total, 1, st, k);
-  MM_HIP(mm::stream_sync(st));
-  clk.stop(2);
-  MM_REQUIRE(total < ((int64_t)1 << 32), MM_ERR_LIMIT, "mm_pileup_events: 2^32 events or more in one call");
-  if (total > 0) {
-    clk.start();
-    DBuf<uint64_t> d_keys((size_t)total);
-    for_job_grids(0, n, [&](int64_t a, dim3 grid) {
-      pile_emit_kernel<<<grid, dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, J, a, d_off.p, reads->qual_ptr(), qmin, d_keys.p);
-    });
-    clk.stop(3);
-    clk.start();
-    SortedTable sorted;
-    sort_table(tmp, d_keys.p, nullptr, nullptr, total, mmp::CONTIG_SHIFT + contig_bits(ref->count()), 0, st, &sorted);
-    clk.stop(4);
-    clk.start();
-    reduce_sorted(tmp, sorted, total, st, out);
-    if (qmin > 0 && !out->w0.empty() && out->w0.back() == mmp::DROPPED) { out->w0.pop_back(); out->counts.pop_back(); }   // the events under the floor: the last segment
-    clk.stop(5);
+struct PileupEvents {                                            // what mm_events.hpp's pipeline asks of a format
+  static constexpr const char* who = "mm_pileup_events";
+  static constexpr const char* timing = "MM_PILEUP_TIMING";
+  static constexpr int32_t param_max = 93;
+  static constexpr const char* param_text = "mm_pileup_events_q: min_base_quality is not in [0, 93]";
+  static constexpr int64_t max_contigs = mmp::MAX_CONTIGS;
+  static constexpr const char* contigs_text = "mm_pileup_events: more than 2^29 contigs";
+  static constexpr int key_shift = mmp::CONTIG_SHIFT;
+  static constexpr bool two_words = false;
+  static constexpr const char* second = nullptr;
+  static constexpr uint64_t sentinel = mmp::DROPPED;               // an event under the floor; every bit of it in use is set, so it sorts last
+  static bool cuts_sentinel(int32_t qmin) { return qmin > 0; }
+  static int32_t value(const mm_seqset* reads, int32_t min_base_quality) { return reads->has_qual ? min_base_quality : 0; }   // (reads without qualities pass every floor)
+  static const char* rule_text(int rule) { return mmp::rule_text(rule); }
+  static void count(const EventsLaunch& L, int64_t a, dim3 grid) {
+    pile_count_kernel<<<grid, dim3(64), 0, L.st>>>(L.reads->d_len.p, L.reads->count(), L.ref->d_len.p, L.ref->count(), L.J, L.use, a, L.counts, L.err);
   }
-  if (clk.on)
-    fprintf(stderr, "MM_PILEUP_TIMING events: upload %.3f count %.3f scan %.3f emit %.3f sort %.3f reduce %.3f ms; %lld jobs, %lld runs, %lld events, %zu pairs, %zu B fetched\n", clk.ms[0],
-            clk.ms[1], clk.ms[2], clk.ms[3], clk.ms[4], clk.ms[5], (long long)n, (long long)jobs.n_ops, (long long)total, out->w0.size(), out->w0.size() * 12);
+  static void emit(const EventsLaunch& L, int64_t a, dim3 grid) {
+    pile_emit_kernel<<<grid, dim3(64), 0, L.st>>>(edit_seq(L.reads), L.reads->d_base.p, L.reads->d_len.p, L.J, a, L.off, L.reads->qual_ptr(), L.value, L.w0);
+  }
+};
+void pileup_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& in, const uint8_t* use, int32_t min_base_quality, KeyTable* out) {
+  key_events_run<PileupEvents>(ctx, reads, ref, in, use, min_base_quality, out);
 }
 
 struct PileRefByte {                                              // a kept site's payload: the reference's byte at its position

@@ -9,7 +9,7 @@ struct PileupResult : KeptRows {
   std::vector<uint8_t> ref_byte;
   std::vector<int64_t> alignments, covered, sum_depth;
 };
-// use: the column that the pileup and the VCF read beside the aligned jobs, one byte per job
+// use: one byte per job beside the aligned jobs (mm_jobs_dev.hpp); the events are mm_events.hpp's pipeline with the format's kernels
 void pileup_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* reference, const AlignedJobsIn& jobs, const uint8_t* use, int32_t min_base_quality, KeyTable* out);
 void pileup_finish_run(mm_ctx* ctx, const mm_seqset* reference, const FinishIn& in, PileupResult* out);
 }

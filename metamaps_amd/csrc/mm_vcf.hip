@@ -1,20 +1,20 @@
 // The alleles of a run's alignments on the device (mm_vcf_events / _merge / _finish; mapDirectly --vcf; DESIGN.md section 1, "VCF"; the definition:
 // mm_vcf_core.hpp, the text the host test runs).
-//   events   count    vcf_count_kernel: one wavefront (a 64-thread workgroup) per job; the lanes stride over the runs, apply the rules and sum the job's bound of
-//                     alleles (X bases + the I and D runs between other runs) and its indel runs.  A job that breaks a rule puts (job << 4 | rule) into the
-//                     error word with an atomic minimum; the host reads the word before anything else is launched.
-//            scan     exclusive scans of the two counts (mm_prims.hpp): every job's place, and whether the call has an indel at all.
+//   events   mm_events.hpp's pipeline (count, scan, emit, sort, reduce) over two-word keys with VcfEvents:
+//            count    vcf_count_kernel: one wavefront (a 64-thread workgroup) per job; the lanes stride over the runs, apply the rules and sum the job's bound of
+//                     alleles (X bases + the I and D runs between other runs) and its indel runs, the second count: whether the call has an indel at all.
+//                     A job that breaks a rule puts (job << 4 | rule) into the error word with an atomic minimum.
 //            emit     vcf_emit_kernel: one wavefront per job over tiles of 64 runs; wave scans give each run its contig position, its read index and its
 //                     place; a lane writes its own short run and left-aligns its own indel (a loop of at most NORM_MAX steps over EditSeq::byte on the
 //                     job's contig, no shuffle inside), the wavefront expands an X run of more than 64 bases.  A skipped event is the all-ones pair.
-//            sort     mm_keytable.hip's two-word order: by w1, then by the bits of w0 in use.  A call without an indel sorts w0 alone: every w1 is 0 or
-//                     all ones.  The all-ones pairs sort last and are cut off the table.
-//            reduce   mm_keytable.hip's segments over two-word keys.
+//            sort     by w1, then by the bits of w0 in use.  A call without an indel sorts w0 alone: every w1 is 0 or all ones.  The all-ones pairs sort
+//                     last and are cut off the table.
 //   merge    mm_keytable.hip's merge_run over two-word keys.
 //   finish   mm_keytable.hip's finish_kept with w1 and the reference window as a kept allele's payload.
 // No kernel here waits for another workgroup; the only atomic is the error word's minimum.
-// The jobs' arrays, their checks and the launch loop are mm_jobs_dev.hpp's, shared with mm_bam.hip and mm_pileup.hip.
+// The jobs' arrays, their checks and the launch loop are mm_jobs_dev.hpp's, shared with every output that walks the jobs.
 #include "mm_vcf.hpp"
+#include "mm_events.hpp"
 #include "mm_vcf_core.hpp"
 #include "mm_prims.hpp"
 
@@ -50,70 +50,30 @@ __global__ void __launch_bounds__(64) vcf_emit_kernel(EditSeq Q, const uint64_t*
                   J.ops + J.op_off[job], J.op_off[job + 1] - J.op_off[job], qmin, w0 + off[job], w1 + off[job]);
 }
 
-namespace {
-void cut_skipped(KeyTable* t) {                                   // the all-ones pair, the last segment where there is one, is no allele
-  if (!t->w0.empty() && t->w0.back() == mmv::SKIP) { t->w0.pop_back(); t->w1.pop_back(); t->counts.pop_back(); }
-}
-}  // namespace
-
-void vcf_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& in, const uint8_t* use, int32_t min_base_quality, KeyTable* out) {
-  AlignedJobsDev jobs(ctx, reads, ref, in, "mm_vcf_events");
-  MM_REQUIRE(min_base_quality >= 0 && min_base_quality <= 93, MM_ERR_ARG, "mm_vcf_events_q: min_base_quality is not in [0, 93]");
-  const int32_t qmin = reads->has_qual ? min_base_quality : 0;     // (reads without qualities pass every floor)
-  MM_REQUIRE(ref->count() <= mmp::MAX_CONTIGS, MM_ERR_ARG, "mm_vcf_events: more than 2^29 contigs");
-  out->clear();
-  const int64_t n = in.n_jobs;
-  if (n == 0) return;
-  const size_t k = (size_t)n;
-  hipStream_t st = ctx->stream;
-  StageClock<6> clk(getenv("MM_VCF_TIMING") != nullptr, st);       // upload, count, scan, emit, sort, reduce (with the table's way to the host)
-
-  clk.start();
-  const AlignedJobs J = jobs.upload(st);
-  DBuf<int64_t> d_counts(k + 1), d_indels(k + 1), d_off(k + 1), d_ioff(k + 1);
-  DBuf<uint8_t> d_use(k);
-  d_use.upload(use, k, st);
-  d_counts.zero(st); d_indels.zero(st);
-  clk.stop(0);
-
-  clk.start();
-  for_job_grids(0, n, [&](int64_t a, dim3 grid) {
-    vcf_count_kernel<<<grid, dim3(64), 0, st>>>(reads->d_len.p, reads->count(), ref->d_len.p, ref->count(), J, d_use.p, a, d_counts.p, d_indels.p, jobs.err.p);
-  });
-  jobs.require_no_error(st, mmv::rule_text);
-  clk.stop(1);
-
-  clk.start();
-  DBuf<uint8_t> tmp;
-  exclusive_scan(tmp, d_counts.p, d_off.p, k + 1, st);
-  exclusive_scan(tmp, d_indels.p, d_ioff.p, k + 1, st);
-  int64_t total = 0, indels = 0;
-  d_off.download(&total, 1, st, k);
-  d_ioff.download(&indels, 1, st, k);
-  MM_HIP(mm::stream_sync(st));
-  clk.stop(2);
-  MM_REQUIRE(total < ((int64_t)1 << 32), MM_ERR_LIMIT, "mm_vcf_events: 2^32 events or more in one call");
-  if (total > 0) {
-    clk.start();
-    DBuf<uint64_t> d_w0((size_t)total), d_w1((size_t)total);
-    for_job_grids(0, n, [&](int64_t a, dim3 grid) {
-      vcf_emit_kernel<<<grid, dim3(64), 0, st>>>(edit_seq(reads), reads->d_base.p, reads->d_len.p, edit_seq(ref), ref->d_base.p, J, a, d_off.p, reads->qual_ptr(), qmin, d_w0.p, d_w1.p);
-    });
-    clk.stop(3);
-    clk.start();
-    SortedTable sorted;                                            // without an indel every w1 is 0, or all ones beside an all-ones w0: w0 alone decides
-    sort_table(tmp, d_w0.p, indels ? d_w1.p : nullptr, nullptr, total, mmp::CONTIG_SHIFT + contig_bits(ref->count()), 64, st, &sorted);
-    if (indels) { MM_HIP(mm::stream_sync(st)); sorted.perm.release(); sorted.i1.release(); }   // (the two index buffers go once the sort is through: the reduction takes their blocks)
-    clk.stop(4);
-    clk.start();
-    reduce_sorted(tmp, sorted, total, st, out);
-    if (!indels) out->w1.assign(out->w0.size(), 0);
-    cut_skipped(out);
-    clk.stop(5);
+struct VcfEvents {                                               // what mm_events.hpp's pipeline asks of a format
+  static constexpr const char* who = "mm_vcf_events";
+  static constexpr const char* timing = "MM_VCF_TIMING";
+  static constexpr int32_t param_max = 93;
+  static constexpr const char* param_text = "mm_vcf_events_q: min_base_quality is not in [0, 93]";
+  static constexpr int64_t max_contigs = mmp::MAX_CONTIGS;
+  static constexpr const char* contigs_text = "mm_vcf_events: more than 2^29 contigs";
+  static constexpr int key_shift = mmp::CONTIG_SHIFT;
+  static constexpr bool two_words = true;
+  static constexpr const char* second = "indels";                 // without an indel every w1 is 0, or all ones beside an all-ones w0: w0 alone decides
+  static constexpr uint64_t sentinel = mmv::SKIP;                  // the all-ones pair, the last segment where there is one, is no allele
+  static bool cuts_sentinel(int32_t) { return true; }
+  static int32_t value(const mm_seqset* reads, int32_t min_base_quality) { return reads->has_qual ? min_base_quality : 0; }   // (reads without qualities pass every floor)
+  static const char* rule_text(int rule) { return mmv::rule_text(rule); }
+  static void count(const EventsLaunch& L, int64_t a, dim3 grid) {
+    vcf_count_kernel<<<grid, dim3(64), 0, L.st>>>(L.reads->d_len.p, L.reads->count(), L.ref->d_len.p, L.ref->count(), L.J, L.use, a, L.counts, L.counts2, L.err);
   }
-  if (clk.on)
-    fprintf(stderr, "MM_VCF_TIMING events: upload %.3f count %.3f scan %.3f emit %.3f sort %.3f reduce %.3f ms; %lld jobs, %lld runs, %lld events (%lld indels), %zu pairs, %zu B fetched\n",
-            clk.ms[0], clk.ms[1], clk.ms[2], clk.ms[3], clk.ms[4], clk.ms[5], (long long)n, (long long)jobs.n_ops, (long long)total, (long long)indels, out->w0.size(), out->w0.size() * 20);
+  static void emit(const EventsLaunch& L, int64_t a, dim3 grid) {
+    vcf_emit_kernel<<<grid, dim3(64), 0, L.st>>>(edit_seq(L.reads), L.reads->d_base.p, L.reads->d_len.p, edit_seq(L.ref), L.ref->d_base.p, L.J, a, L.off, L.reads->qual_ptr(), L.value, L.w0,
+                                                 L.w1);
+  }
+};
+void vcf_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, const AlignedJobsIn& in, const uint8_t* use, int32_t min_base_quality, KeyTable* out) {
+  key_events_run<VcfEvents>(ctx, reads, ref, in, use, min_base_quality, out);
 }
 
 struct VcfWindow {                                                // a kept allele's payload: its w1, and the reference's bytes from its position on (zero beyond the contig's end)
