@@ -32,7 +32,7 @@ extern "C" {
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
                             *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances,
-                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_* (mm_bam_encode_sorted, mm_bam_fetch_records, mm_bam_sorter_*), mm_pileup_*, mm_vcf_*, mm_consensus*, mm_seqset_*_mods, mm_mod_*,
+                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_* (mm_bam_encode_sorted, mm_bam_fetch_records, mm_bam_sorter_*), mm_pileup_*, mm_vcf_*, mm_consensus*, mm_seqset_*_mods, mm_mod_* (mm_mod_motifs, mm_motif_result_*),
                             *    mm_depth_*, mm_errprof_* (additions to 6) */
 
 typedef enum {
@@ -669,6 +669,30 @@ int mm_mod_finish(mm_ctx* ctx, const mm_seqset* reference, int64_t n, const uint
 int mm_mod_result_sizes(const mm_mod_result* result, int64_t* n_rows);
 int mm_mod_result_fetch(const mm_mod_result* result, uint64_t* site /* [n_rows] */, uint64_t* n_mod, uint64_t* n_canonical, uint64_t* n_other, uint64_t* n_fail);
 void mm_mod_result_destroy(mm_mod_result* result);
+
+/* Methylation per sequence motif over the contigs [contig_lo, contig_hi) ("Modification motifs"; the definition:
+ * csrc/mm_motif_core.hpp).  The table, the codes and min_coverage are mm_mod_finish's, with the same checks; only the keys of the group's contigs
+ * contribute.  Motif j has the letters motif_mask[motif_off[j], motif_off[j + 1]) as 4-bit sets (A 1, C 2, G 4, T 8, IUPAC letters their unions) and its
+ * modified base at motif_pos[j]: a length outside 1..32, a mask outside 1..15, a modified base that is not a one-bit mask inside the motif, n_motifs outside
+ * 1..8 and, under combine_strands, a motif that is not its own reverse complement are MM_ERR_ARG with "mm_mod_motifs: motif <index>: ...".  A reference byte
+ * outside A C G T fits no letter; no occurrence crosses a contig's end.  An occurrence with modified position q on a strand takes, for every code whose base
+ * is the motif's modified base, mm_mod_finish's counts at (contig, q, strand), zero without an entry; it is covered iff N_mod + N_canonical + N_other >=
+ * min_coverage and modified iff covered and N_mod >= min_frac (0..1) of that sum.  Under combine_strands the + and - occurrence of one window are one unit at
+ * the + site with the sums of both.  Rows: the covered (occurrence, code) in the order contig, position, + before -, motif, code; site = contig << 36 |
+ * pos << 4 | (strand < 0) << 3 (a unit: strand bit 0).  Summary: one entry per (contig with an entry in the table, motif, applicable code) in that order
+ * with MM_MOTIF_SUMS sums: sites (all occurrences, or units), covered, modified, N_valid_cov and N_mod over the covered ones.  The rows and summaries of
+ * successive groups, one behind the other, are those of one call over all contigs.  The result is host memory. */
+#define MM_MOTIF_SUMS 5
+typedef struct mm_motif_result mm_motif_result;
+int mm_mod_motifs(mm_ctx* ctx, const mm_seqset* reference, int32_t contig_lo, int32_t contig_hi, int64_t n, const uint64_t* keys, const uint32_t* counts,
+                  int32_t n_codes, const uint8_t* code_base /* [n_codes] */, int32_t n_motifs, const int32_t* motif_off /* [n_motifs + 1] */,
+                  const uint8_t* motif_mask, const int32_t* motif_pos /* [n_motifs] */, int64_t min_coverage, double min_frac, int32_t combine_strands,
+                  mm_motif_result** out);
+int mm_motif_result_sizes(const mm_motif_result* result, int64_t* n_rows, int64_t* n_summary);
+int mm_motif_result_fetch_rows(const mm_motif_result* result, uint64_t* site /* [n_rows] */, int32_t* motif, int32_t* code, uint64_t* n_mod, uint64_t* n_canonical,
+                               uint64_t* n_other, uint64_t* n_fail);
+int mm_motif_result_fetch_summary(const mm_motif_result* result, int32_t* contig /* [n_summary] */, int32_t* motif, int32_t* code, int64_t* sums /* [MM_MOTIF_SUMS * n_summary] */);
+void mm_motif_result_destroy(mm_motif_result* result);
 
 /* The alleles of aligned jobs: SNVs, deletions and insertions that are canonical across reads, left-aligned and counted on the context's device (DESIGN.md
  * section 1, "VCF"; the definition: csrc/mm_vcf_core.hpp).  A job contributes where use[i] != 0 and dist[i] >= 0.  Walking its runs from r = first, i = 0

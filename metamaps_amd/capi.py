@@ -19,6 +19,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "metamaps_hip.h")
 COMM_ID_BYTES = 128
 ERRPROF_COUNTERS, ERRPROF_COLS, ERRPROF_STATS = 566, 6, 12          # the sizes of mm_errprof_events' counters and columns and of a row of mm_errprof_finish (the header's constants)
 DEPTH_STATS = 5                                                    # counters per contig of mm_depth_profile before its thresholds' (the header's counter constant)
+MOTIF_SUMS = 5                                                      # sums per summary entry of mm_mod_motifs (the header's constant)
+IUPAC_MASK = dict(A=1, C=2, G=4, T=8, R=5, Y=10, S=6, W=9, K=12, M=3, B=14, D=13, H=11, V=7, N=15)   # A 1, C 2, G 4, T 8 and their unions
 CONS_STATS = 10                                                     # counters per contig of mm_consensus (the header's counter constant)
 VCF_WINDOW = 25                                                     # reference bytes a kept allele of mm_vcf_finish carries (the header's window constant)
 MM_ERR_ARG = -1
@@ -241,6 +243,11 @@ def lib() -> C.CDLL:
             "mm_mod_result_sizes": (C.c_int, [vp, vp]),
             "mm_mod_result_fetch": (C.c_int, [vp, vp, vp, vp, vp, vp]),
             "mm_mod_result_destroy": (None, [vp]),
+            "mm_mod_motifs": (C.c_int, [vp, vp, C.c_int32, C.c_int32, i64, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, i64, f64, C.c_int32, vp]),
+            "mm_motif_result_sizes": (C.c_int, [vp, vp, vp]),
+            "mm_motif_result_fetch_rows": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+            "mm_motif_result_fetch_summary": (C.c_int, [vp, vp, vp, vp, vp]),
+            "mm_motif_result_destroy": (None, [vp]),
             "mm_vcf_events": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
             "mm_vcf_events_q": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp]),
             "mm_vcf_merge": (C.c_int, [vp, i64, vp, vp, vp, vp]),
@@ -795,6 +802,35 @@ class Context:
             self.last_mod_handle = h.value
             if h:
                 lib().mm_mod_result_destroy(h)
+
+    def mod_motifs(self, reference: "SeqSet", contig_lo, contig_hi, keys, counts, code_base, motifs, min_coverage=1, min_frac=0.5, combine_strands=False):
+        """methylation per motif over the contigs [contig_lo, contig_hi) of a merged table (mm_mod_motifs); motifs: [(letters, offset)] with IUPAC letters, or
+        [(masks, offset)] with the 4-bit letter sets themselves.  A dict of arrays: the covered rows (site, motif, code, n_mod, n_canonical, n_other, n_fail)
+        and the summary (s_contig, s_motif, s_code, sums with MOTIF_SUMS columns: sites, covered, modified, N_valid_cov, N_mod)"""
+        ks, cs = np.ascontiguousarray(keys, dtype=np.uint64), np.ascontiguousarray(counts, dtype=np.uint32)
+        cb = np.frombuffer(code_base.encode() if isinstance(code_base, str) else bytes(code_base), dtype=np.uint8).copy()
+        masks = [[IUPAC_MASK.get(x, 0) for x in m] if isinstance(m, str) else [int(x) for x in m] for m, _ in motifs]
+        off = np.cumsum([0] + [len(m) for m in masks]).astype(np.int32)
+        mask = np.array([x for m in masks for x in m] + [0], dtype=np.uint8)
+        pos = np.array([int(o) for _, o in motifs] + [0], dtype=np.int32)
+        h = C.c_void_p(0xDEAD)
+        st = lib().mm_mod_motifs(self.h, reference.h, int(contig_lo), int(contig_hi), len(ks), _ptr(ks), _ptr(cs), len(cb), _ptr(cb), len(motifs), _ptr(off), _ptr(mask), _ptr(pos),
+                                 int(min_coverage), float(min_frac), int(bool(combine_strands)), C.byref(h))
+        try:
+            self.check(st)
+            n, ns = C.c_int64(-1), C.c_int64(-1)
+            assert lib().mm_motif_result_sizes(h, C.byref(n), C.byref(ns)) == 0
+            out = {k: np.zeros(n.value, dtype=np.uint64) for k in ("site", "n_mod", "n_canonical", "n_other", "n_fail")}
+            out.update({k: np.zeros(n.value, dtype=np.int32) for k in ("motif", "code")})
+            out.update({k: np.zeros(ns.value, dtype=np.int32) for k in ("s_contig", "s_motif", "s_code")})
+            out["sums"] = np.zeros((ns.value, MOTIF_SUMS), dtype=np.int64)
+            assert lib().mm_motif_result_fetch_rows(h, *[_ptr(out[k]) for k in ("site", "motif", "code", "n_mod", "n_canonical", "n_other", "n_fail")]) == 0
+            assert lib().mm_motif_result_fetch_summary(h, *[_ptr(out[k]) for k in ("s_contig", "s_motif", "s_code", "sums")]) == 0
+            return out
+        finally:
+            self.last_motif_handle = h.value
+            if h.value:
+                lib().mm_motif_result_destroy(h)
 
     def vcf_events(self, reads: "SeqSet", reference: "SeqSet", read, strand, contig, dist, first, op_off, ops, use, min_base_quality=None):
         """the left-aligned alleles of the jobs with use != 0 and dist >= 0 (mm_vcf_events): (w0, w1, counts), keys unique and ascending by (w0, w1);

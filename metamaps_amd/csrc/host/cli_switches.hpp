@@ -45,6 +45,7 @@ struct CliSwitches {
   const size_t vcf_merge_pairs = (size_t)u64(getenv("MM_VCF_MERGE_PAIRS"), (uint64_t)64 << 20);   // --vcf: the same for its (w0, w1, count) triples
   const size_t mods_merge_pairs = (size_t)u64(getenv("MM_MODS_MERGE_PAIRS"), (uint64_t)64 << 20);   // --mods: the same for its (key, count) pairs
   const int64_t cons_group_bases = (int64_t)std::clamp<uint64_t>(u64(getenv("MM_CONS_GROUP_BASES"), (uint64_t)1 << 28), 1, (uint64_t)1 << 40);   // --consensus: bases per call
+  const int64_t motif_group_bases = (int64_t)std::clamp<uint64_t>(u64(getenv("MM_MOTIF_GROUP_BASES"), (uint64_t)1 << 28), 1, (uint64_t)1 << 40);   // --mod-motifs: the same
   // --bam-sorted: output bytes the merge makes at a time, whole members of 65 280 bytes (unset: 0, the library's 255 MiB; 0 MB: one member)
   const int64_t bam_sort_window = !getenv("MM_BAM_SORT_WINDOW_MB") ? 0 : (int64_t)std::clamp<uint64_t>((u64(getenv("MM_BAM_SORT_WINDOW_MB"), 0) << 20) / 65280, 1, 4096) * 65280;
   const bool classify_from_file = on(getenv("MM_CLI_CLASSIFY_FROM_FILE"));      // --then-classify reads the mappings file back instead of taking the kept lines

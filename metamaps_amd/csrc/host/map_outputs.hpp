@@ -1,18 +1,20 @@
 // The side outputs of a batch of mapDirectly (the rows of side_files.hpp: PREFIX.editDistances, .paf, .bam) and the device calls they need, and the run's
-// pileup (PREFIX.pileup, .pileup.contigs), alleles (PREFIX.vcf), consensus (PREFIX.consensus.fa, .consensus.tsv), modification counts (PREFIX.bedmethyl) and
+// pileup (PREFIX.pileup, .pileup.contigs), alleles (PREFIX.vcf), consensus (PREFIX.consensus.fa, .consensus.tsv), modification counts (PREFIX.bedmethyl, .motifs.*) and
 // depth profile (PREFIX.depth.bedgraph, .depth.windows, .depth.contigs) and error profile (PREFIX.errorProfile.*), which every batch adds to.  The text and
-// byte rules are in edit_dist.hpp, paf_out.hpp, bam_out.hpp, pileup_out.hpp, vcf_out.hpp, consensus_out.hpp, mods_out.hpp, depth_out.hpp and errprof_out.hpp,
+// byte rules are in edit_dist.hpp, paf_out.hpp, bam_out.hpp, pileup_out.hpp, vcf_out.hpp, consensus_out.hpp, mods_out.hpp, motif_out.hpp, depth_out.hpp and errprof_out.hpp,
 // which call nothing; everything of a batch runs on the context that mapped it, the last merge and the finish of the pileup, of the alleles, of the consensus
 // and of the modification counts, the depth profile and the error profile's rows on the first device.
 #pragma once
 #include "bam_out.hpp"
 #include "bam_sort_out.hpp"
+#include "classify_run.hpp"
 #include "cli_device.hpp"
 #include "consensus_out.hpp"
 #include "depth_out.hpp"
 #include "edit_dist.hpp"
 #include "errprof_out.hpp"
 #include "mods_out.hpp"
+#include "motif_out.hpp"
 #include "paf_out.hpp"
 #include "pileup_out.hpp"
 #include "side_files.hpp"
@@ -128,6 +130,41 @@ void mods_write(mm_ctx* ctx, const mm_seqset* reference, VariantRows& v, const M
   mm_mod_result_destroy(r);
   write_or_die(prefix + ".bedmethyl", bedmethyl_text(mo, site, n_mod, n_canonical, n_other, n_fail, cname));
 }
+// --mod-motifs, behind mods_write (which has merged the table): the groups of consensus_out.hpp over the contigs with an entry, the entries of a group cut out by
+// key, one mm_mod_motifs per group on `ctx`, and the two files
+void motifs_write(mm_ctx* ctx, const mm_seqset* reference, const VariantRows& v, const ModsOpts& mo, const MotifOpts& mt, int64_t group_bases, const std::string& prefix,
+                  const std::vector<std::string>& cname, const std::vector<int>& clen) {
+  std::vector<int32_t> listed;
+  for (uint64_t key : v.w0) if (listed.empty() || listed.back() != (int32_t)mmd::key_contig(key)) listed.push_back((int32_t)mmd::key_contig(key));
+  FILE* fb = fopen((prefix + ".motifs.bedmethyl").c_str(), "wb");
+  FILE* ft = fopen((prefix + ".motifs.tsv").c_str(), "wb");
+  if (!fb || !ft) die("Error writing " + prefix + ".motifs.bedmethyl / .motifs.tsv");
+  auto put = [&](FILE* f, std::string& t) { if (fwrite(t.data(), 1, t.size(), f) != t.size()) die("Error writing " + prefix + ".motifs.bedmethyl / .motifs.tsv"); t.clear(); };
+  std::string bed, tsv = motif_tsv_header();                      // (appended to as the groups come)
+  std::vector<int64_t> total;
+  std::vector<uint64_t> site, n_mod, n_canonical, n_other, n_fail; std::vector<int32_t> motif, code, s_contig, s_motif, s_code; std::vector<int64_t> sums;
+  for (const ConsGroupRange& g : cons_groups(clen, listed, group_bases)) {
+    const size_t r0 = (size_t)(std::lower_bound(v.w0.begin(), v.w0.end(), mmd::make_key(g.lo, 0, 1, 0)) - v.w0.begin());
+    const size_t r1 = (size_t)g.hi < clen.size() ? (size_t)(std::lower_bound(v.w0.begin(), v.w0.end(), mmd::make_key(g.hi, 0, 1, 0)) - v.w0.begin())
+                                                 : v.w0.size();    // (a key of contig 2^28 would wrap to 0)
+    mm_motif_result* r = nullptr;
+    ck(ctx, mm_mod_motifs(ctx, reference, g.lo, g.hi, (int64_t)(r1 - r0), v.w0.data() + r0, v.counts.data() + r0, mo.n_codes, mo.code_base, mt.n, mt.off.data(), mt.mask.data(),
+                          mt.pos.data(), mo.min_coverage, mt.min_frac, mt.combine ? 1 : 0, &r), "modification motifs");
+    int64_t n = 0, ns = 0;
+    mm_motif_result_sizes(r, &n, &ns);
+    for (auto* x : {&site, &n_mod, &n_canonical, &n_other, &n_fail}) x->resize((size_t)n);
+    motif.resize((size_t)n); code.resize((size_t)n); s_contig.resize((size_t)ns); s_motif.resize((size_t)ns); s_code.resize((size_t)ns); sums.resize((size_t)ns * MM_MOTIF_SUMS);
+    mm_motif_result_fetch_rows(r, site.data(), motif.data(), code.data(), n_mod.data(), n_canonical.data(), n_other.data(), n_fail.data());
+    mm_motif_result_fetch_summary(r, s_contig.data(), s_motif.data(), s_code.data(), sums.data());
+    mm_motif_result_destroy(r);
+    motif_bedmethyl_text(mo, mt, site, motif, code, n_mod, n_canonical, n_other, n_fail, cname, bed);
+    motif_tsv_text(mo, mt, s_contig, s_motif, s_code, sums, cname, total, tsv);
+    put(fb, bed); put(ft, tsv);
+  }
+  motif_tsv_totals(mo, mt, total, tsv);
+  put(ft, tsv);
+  if (fclose(fb) != 0 || fclose(ft) != 0) die("Error writing " + prefix + ".motifs.bedmethyl / .motifs.tsv");
+}
 // --vcf, after the last batch of a query file and the merge of its rows: one mm_vcf_finish against the reference of `ctx` over the file's intervals, and the file
 void vcf_write(mm_ctx* ctx, const mm_seqset* reference, const VariantRows& v, const Intervals& iv, const VcfOpts& vo, int min_base_quality, const std::string& prefix,
                const std::vector<std::string>& cname, const std::vector<int>& clen) {
@@ -239,12 +276,16 @@ struct RunVariants {
   VariantAcc* mods(size_t f) { return mods_on ? &files[f].mods : nullptr; }
   ErrprofAcc* errprof(size_t f) { return errprof_on ? &files[f].errprof : nullptr; }
   Intervals* intervals(size_t f) { return files.empty() ? nullptr : &files[f].iv; }
-  void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const ConsOpts& co, const ModsOpts& mo, const DepthOpts& dp, int min_base_quality,
-             int64_t cons_group_bases, int64_t bam_sort_window, const std::vector<std::string>& prefixes, const std::vector<std::string>& cname, const std::vector<int>& clen) {
+  void write(mm_ctx* ctx, const mm_seqset* reference, const PileupOpts& po, const VcfOpts& vo, const ConsOpts& co, const ModsOpts& mo, const MotifOpts& mt, const DepthOpts& dp,
+             int min_base_quality, int64_t cons_group_bases, int64_t motif_group_bases, int64_t bam_sort_window, const std::vector<std::string>& prefixes,
+             const std::vector<std::string>& cname, const std::vector<int>& clen) {
     for (size_t fi = 0; pileup_on && fi < files.size(); ++fi) pileup_write(ctx, reference, files[fi].pile.rows, files[fi].iv, po, prefixes[fi], cname, clen);
     for (size_t fi = 0; depth_on && fi < files.size(); ++fi) depth_write(ctx, files[fi].iv, dp, prefixes[fi], cname, clen);
     for (size_t fi = 0; errprof_on && fi < files.size(); ++fi) errprof_write(ctx, files[fi].errprof, prefixes[fi], cname, clen);
-    for (size_t fi = 0; mods_on && fi < files.size(); ++fi) mods_write(ctx, reference, files[fi].mods.rows, mo, prefixes[fi], cname);
+    for (size_t fi = 0; mods_on && fi < files.size(); ++fi) {
+      mods_write(ctx, reference, files[fi].mods.rows, mo, prefixes[fi], cname);
+      if (mt.on) motifs_write(ctx, reference, files[fi].mods.rows, mo, mt, motif_group_bases, prefixes[fi], cname, clen);
+    }
     for (size_t fi = 0; vcf_on && fi < files.size(); ++fi) {
       merge_rows<VcfCalls>(ctx, files[fi].vcf.rows);
       if (vcf_file) vcf_write(ctx, reference, files[fi].vcf.rows, files[fi].iv, vo, min_base_quality, prefixes[fi], cname, clen);
@@ -333,6 +374,21 @@ struct BatchSideOutputs {
     }
     reads.reset();
   }
+};
+
+// what a worker of MapRun hands to its writer: the finished text of one batch and what the batch adds to every side file
+struct BatchDone {
+  size_t file = 0;
+  std::vector<std::string> names;
+  std::vector<int> lens;
+  std::vector<int> clens;                                          // --hpc: the compressed lengths (lens stay raw)
+  std::vector<int64_t> off;
+  std::string text;
+  std::string gz;                                                  // --compress-output: the text as BGZF members
+  SideBytes side;                                                  // what the batch adds to every side file (side_files.hpp): lines, or BGZF members
+  SortedRun sorted;                                                // --bam-sorted: the batch's sorted run
+  std::vector<LineMeta> meta;
+  double t_mapq = 0, t_fetch = 0, t_format = 0;
 };
 
 }  // namespace

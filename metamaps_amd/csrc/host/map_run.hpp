@@ -63,6 +63,7 @@ struct MapRun {
   const QualOpts qual = qual_options(o);                         // --base-qualities, --min-base-quality: the batches carry the reads' qualities to the device
   const DepthOpts depth = depth_options(o);                      // --depth (implies --edit-distance): the intervals --pileup keeps, one profile per query file (depth_out.hpp)
   const ModsOpts mods = mods_options(o);                         // --mods (implies --edit-distance): a BAM query's MM/ML groups go to the device with its reads (mods_out.hpp)
+  const MotifOpts motifs = motif_options(o, mods);               // --mod-motifs: the two motif files behind PREFIX.bedmethyl (motif_out.hpp)
   RunVariants var;
   std::string bgzf_head;                                         // what a BGZF side file starts with: the header of every PREFIX.bam as BGZF members (the contigs are the run's)
   std::vector<int> clen_raw; std::vector<mm_hpc_map*> hpc_map;
@@ -83,20 +84,7 @@ struct MapRun {
   std::map<int64_t, int64_t> thr_acc; int thr = INT_MAX;          // occurrence histogram accumulated over the chunks, never cleared (winSketch.hpp:452-494)
   mm_map_params mp{};
   std::vector<int32_t> chunk_base;
-  // what a worker hands to the writer: the finished text of one batch
-  struct Done {
-    size_t file = 0;
-    std::vector<std::string> names;
-    std::vector<int> lens;
-    std::vector<int> clens;                                        // --hpc: the compressed lengths (lens stay raw)
-    std::vector<int64_t> off;
-    std::string text;
-    std::string gz;                                                // --compress-output: the text as BGZF members
-    SideBytes side;                                                // what the batch adds to every side file (side_files.hpp): lines, or BGZF members
-    SortedRun sorted;                                              // --bam-sorted: the batch's sorted run
-    std::vector<LineMeta> meta;
-    double t_mapq = 0, t_fetch = 0, t_format = 0;
-  };
+  using Done = BatchDone;                                        // what a worker hands to the writer (map_outputs.hpp)
   // --then-classify: the batches of every query file as they were written, in order (text + the parsed fields of every line): what classify takes
   // instead of the file
   const bool keep_lines = o.v.count("then-classify") && !sw.classify_from_file;
@@ -361,7 +349,7 @@ struct MapRun {
     }
     if (place != Place::Replicated && NC == 1 && !from_index && !maxMem) die("--stream-chunks / --shard-index need --maxmemory (the chunk rule of the reference, winSketch.hpp:274-329)");
     if (edit && place != Place::Replicated)
-      die(errprof_or(o, depth.on ? "--depth" : mods.on ? "--mods" : cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : bam_sorted_of(o) ? "--bam-sorted"
+      die(errprof_or(o, depth.on ? "--depth" : mods.on ? modflag(o) : cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : bam_sorted_of(o) ? "--bam-sorted"
                       : side[SIDE_PAF] ? "--paf" : "--edit-distance") + " needs the whole reference resident on every device, and this index does not fit one: run without it");
     for (auto& d : devs) d.idx.assign(NC, nullptr);
     thr_of.assign(NC, INT_MAX);
@@ -786,7 +774,7 @@ struct MapRun {
     if (place != Place::Replicated) for (auto*& c : wctx) if (c) { mm_ctx_destroy(c); c = nullptr; }   // (the other modes drive one context per device)
     if (place == Place::Replicated) run_replicated(); else run_chunk_major();
     pc.lap("8 write");
-    var.write(ctx0, refset[0], pileup, vcf, cons, mods, depth, qual.min_base_quality, sw.cons_group_bases, sw.bam_sort_window, prefixes, cname, clen);
+    var.write(ctx0, refset[0], pileup, vcf, cons, mods, motifs, depth, qual.min_base_quality, sw.cons_group_bases, sw.motif_group_bases, sw.bam_sort_window, prefixes, cname, clen);
     then_classify();
     if (!sw.full_teardown) { if (reader.th.joinable()) reader.th.join(); pc.report(); finish_fast(); }
     drop_refsets();

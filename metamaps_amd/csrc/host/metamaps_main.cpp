@@ -7,7 +7,7 @@
 //
 //   metamaps mapDirectly [--all] [--compress-output] [--edit-distance] [--paf] [--bam] [--bam-sorted] [--pileup [--pileup-min-count N] [--pileup-min-frac F]]
 //                       [--vcf [--vcf-min-count N] [--vcf-min-frac F]]
-//                       [--consensus [--consensus-min-depth D] [--consensus-min-frac F] [--consensus-min-called C]] [--mods LIST [--mod-min-ml T] [--mod-min-coverage N]]
+//                       [--consensus [--consensus-min-depth D] [--consensus-min-frac F] [--consensus-min-called C]] [--mods LIST [--mod-min-ml T] [--mod-min-coverage N] [--mod-motifs M1,M2,...]]
 //                       [--depth [--depth-window W] [--depth-thresholds T1,T2,...]] [--error-profile]
 //                        -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
@@ -103,6 +103,18 @@
 // written 0; --min-base-quality does not touch the counts.  Every other file of the run is the file of the same run without the flag.  Refused wherever
 // --edit-distance is; the two thresholds are refused without --mods.
 //
+// --mod-motifs M1,M2,... [--mod-motif-min-frac F] [--mod-motif-combine-strands] (mapDirectly with --mods; not in the reference): also PREFIX.motifs.bedmethyl and
+// PREFIX.motifs.tsv, what `modkit pileup --motif` and a per-contig tally of it give: which sequence motifs of which contig are methylated, and at what fraction
+// of their occurrences.  An item is MOTIF:OFFSET, 1 to 32 IUPAC letters and the 0-based place of the modified base (GATC:1, CCWGG:1, CG:0), 1 to 8 of them.
+// After the last batch of a query file the first device scans the packed reference for the motifs' occurrences on both strands (mm_mod_motifs: a streaming
+// scan over one-hot nibbles, csrc/mm_motif.hip) and joins the merged table of --mods to them: the first file has one bedMethyl row per covered occurrence and
+// code with code,MOTIF,OFFSET in column 4, the second per contig with a call, motif and code the occurrences, how many are covered (--mod-min-coverage) and
+// modified (N_mod >= F of the valid calls, default 0.5), their calls and the fraction, and a last row * per motif and code.  --mod-motif-combine-strands sums the
+// two strands of an occurrence (CpG-style; only motifs that are their own reverse complement).  Plain text; an empty run writes the first file empty and the
+// header of the second.  Every other file of the run, PREFIX.bedmethyl included, is the file of the same run without the flag.  Refused wherever --mods is, under
+// its own name; all three are refused without --mods (host/motif_out.hpp).  Not provided: motif discovery, motifs longer than 32, a modified base that is an
+// ambiguity letter, several offsets per item, partial motifs at contig ends, the flag outside mapDirectly.
+//
 // --depth [--depth-window W] [--depth-thresholds T1,T2,...] (mapDirectly; not in the reference; implies --edit-distance; may be combined with every other side
 // output): also PREFIX.depth.bedgraph, PREFIX.depth.windows and PREFIX.depth.contigs, what `samtools sort` and `mosdepth` give over the PRIMARY records of
 // PREFIX.bam: the maximal runs of equal depth >= 1 (contigID start end depth, no track line), every window of W bases (default 1000, the window of
@@ -194,7 +206,8 @@ Options parse(int argc, char** argv) {
     if (a == "--em-host-reduce") { o.em_host = true; continue; }
     if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" ||
         a == "--bam" || a == "--bam-sorted" || a == "--error-profile" ||
-        a == "--pileup" || a == "--vcf" || a == "--consensus" || a == "--depth" || a == "--genes" || a == "--refit" || a == "--base-qualities") { o.v[a.substr(2)] = "1"; continue; }
+        a == "--pileup" || a == "--vcf" || a == "--consensus" || a == "--depth" || a == "--genes" || a == "--refit" || a == "--base-qualities" ||
+        a == "--mod-motif-combine-strands") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
@@ -230,6 +243,9 @@ Options parse(int argc, char** argv) {
                    "         (modkit's 18 columns, no header): per reference position and strand the primary alignments whose matched base carries a modified, canonical,\n"
                    "         other or failed call of each code of LIST (1 to 4 items like C+m,C+h,A+a,C+21839), counted on the device; a call fails below the ML byte T\n"
                    "         (default 204), a row needs N (default 1) valid calls; may be combined with the other outputs; not with --hpc, --shard-index, --stream-chunks\n"
+                   "  --mod-motifs M1,M2,... [--mod-motif-min-frac F] [--mod-motif-combine-strands]  (mapDirectly, with --mods) also writes PREFIX.motifs.bedmethyl (a bedMethyl row\n"
+                   "         per covered occurrence of a motif and code, code,MOTIF,OFFSET in column 4) and PREFIX.motifs.tsv (per contig, motif and code: occurrences, covered,\n"
+                   "         modified where N_mod >= F (default 0.5) of the valid calls, and the fraction); items MOTIF:OFFSET like GATC:1,CCWGG:1,CG:0, scanned on the device\n"
                    "  --depth [--depth-window W] [--depth-thresholds T1,T2,...]  (mapDirectly) implies --edit-distance and also writes PREFIX.depth.bedgraph (contigID start end\n"
                    "         depth: the runs of equal depth >= 1 of the primary alignments), PREFIX.depth.windows (contigID start end sumDepth covered meanDepth per window of W,\n"
                    "         default 1000) and PREFIX.depth.contigs (per contig mean, median and maximal depth, breadth, the breadth a uniform spread would give and the\n"
@@ -338,6 +354,7 @@ int main(int argc, char** argv) {
   const VcfOpts vcf_opts = vcf_options(o);                      // (the same)
   const ConsOpts cons_opts = consensus_options(o);              // (the same)
   const ModsOpts mods_opts = mods_options(o);                   // (the same)
+  (void)motif_options(o, mods_opts);                            // (the same)
   const DepthOpts depth_opts = depth_options(o);                // (the same)
   if (o.v.count("base-qualities") || o.v.count("min-base-quality")) {   // (refused under the flag's own name wherever --edit-distance is, before any device work)
     const std::string flag = o.v.count("min-base-quality") ? "--min-base-quality" : "--base-qualities";
@@ -349,7 +366,7 @@ int main(int argc, char** argv) {
   if (o.v.count("paf") || o.v.count("bam") || o.v.count("bam-sorted") || pileup_opts.on || vcf_opts.on || cons_opts.on || mods_opts.on || depth_opts.on || errprof_of(o))
     o.v["edit-distance"] = "1";                                  // (all nine imply it and inherit its refusals)
   if (o.v.count("edit-distance")) {                              // (refused before any device work)
-    const std::string flag = errprof_or(o, depth_opts.on ? "--depth" : mods_opts.on ? "--mods" : cons_opts.on ? "--consensus" : vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup"
+    const std::string flag = errprof_or(o, depth_opts.on ? "--depth" : mods_opts.on ? modflag(o) : cons_opts.on ? "--consensus" : vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup"
                                            : o.v.count("bam") ? "--bam" : o.v.count("bam-sorted") ? "--bam-sorted" : o.v.count("paf") ? "--paf" : "--edit-distance");
     if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reference does not stay on the device");

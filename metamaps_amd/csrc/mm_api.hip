@@ -16,6 +16,7 @@
 #include "mm_pileup.hpp"
 #include "mm_vcf.hpp"
 #include "mm_mods.hpp"
+#include "mm_motif.hpp"
 #include "mm_cons.hpp"
 #include "mm_cons_core.hpp"
 #include "mm_depth.hpp"
@@ -955,6 +956,42 @@ int mm_mod_result_fetch(const mm_mod_result* r, uint64_t* site, uint64_t* n_mod,
   return MM_OK;
 }
 void mm_mod_result_destroy(mm_mod_result* r) { delete r; }
+
+struct mm_motif_result { mm::MotifResult r; };                     // (host memory only: one group's rows and sums)
+static_assert(MM_MOTIF_SUMS == mmt::SUMS, "the header's sums are the definition's");
+int mm_mod_motifs(mm_ctx* ctx, const mm_seqset* reference, int32_t contig_lo, int32_t contig_hi, int64_t n, const uint64_t* keys, const uint32_t* counts, int32_t n_codes,
+                  const uint8_t* code_base, int32_t n_motifs, const int32_t* motif_off, const uint8_t* motif_mask, const int32_t* motif_pos, int64_t min_coverage, double min_frac,
+                  int32_t combine_strands, mm_motif_result** out) {
+  if (!ctx || !reference || !out) return refused(out);
+  return created(ctx, out, [&](mm_motif_result& r) {
+    require_rows("mm_mod_motifs", "entries", n, keys && counts);
+    mm::mod_motifs_run(ctx, reference, mm::MotifIn{contig_lo, contig_hi, n, keys, counts, n_codes, code_base, n_motifs, motif_off, motif_mask, motif_pos, min_coverage, min_frac,
+                                                   combine_strands}, &r.r);
+  });
+}
+int mm_motif_result_sizes(const mm_motif_result* r, int64_t* n_rows, int64_t* n_summary) {
+  if (!r || !n_rows || !n_summary) return MM_ERR_ARG;
+  *n_rows = (int64_t)r->r.site.size(); *n_summary = (int64_t)r->r.s_contig.size();
+  return MM_OK;
+}
+int mm_motif_result_fetch_rows(const mm_motif_result* r, uint64_t* site, int32_t* motif, int32_t* code, uint64_t* n_mod, uint64_t* n_canonical, uint64_t* n_other, uint64_t* n_fail) {
+  if (!r) return MM_ERR_ARG;
+  const size_t k = r->r.site.size();
+  if (k && (!site || !motif || !code || !n_mod || !n_canonical || !n_other || !n_fail)) return MM_ERR_ARG;
+  if (k) {
+    memcpy(site, r->r.site.data(), k * 8); memcpy(motif, r->r.motif.data(), k * 4); memcpy(code, r->r.code.data(), k * 4); memcpy(n_mod, r->r.n_mod.data(), k * 8);
+    memcpy(n_canonical, r->r.n_canonical.data(), k * 8); memcpy(n_other, r->r.n_other.data(), k * 8); memcpy(n_fail, r->r.n_fail.data(), k * 8);
+  }
+  return MM_OK;
+}
+int mm_motif_result_fetch_summary(const mm_motif_result* r, int32_t* contig, int32_t* motif, int32_t* code, int64_t* sums) {
+  if (!r) return MM_ERR_ARG;
+  const size_t k = r->r.s_contig.size();
+  if (k && (!contig || !motif || !code || !sums)) return MM_ERR_ARG;
+  if (k) { memcpy(contig, r->r.s_contig.data(), k * 4); memcpy(motif, r->r.s_motif.data(), k * 4); memcpy(code, r->r.s_code.data(), k * 4); memcpy(sums, r->r.sums.data(), k * MM_MOTIF_SUMS * 8); }
+  return MM_OK;
+}
+void mm_motif_result_destroy(mm_motif_result* r) { delete r; }
 
 struct mm_vcf : key_table<true> {};
 struct mm_vcf_result { mm::VcfResult r; };

@@ -111,7 +111,7 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_PILEUP_MERGE_PAIRS", "64 * 2^20", "test", "mapDirectly --pileup: (key, count) pairs a query file's accumulator may hold before it is replaced by its mm_pileup_merge (small values: several merges on small runs; no result depends on it)"},
     {"MM_VCF_TIMING", "unset", "debug", "device times of mm_vcf_events' upload, count, scan, emit, sort and reduce stages (events; reduce includes the table's copy to the host) with its jobs, runs, events, indels, pairs and fetched bytes, and of the stages of mm_vcf_merge and mm_vcf_finish, on stderr (tools/edit_kernel_stats.py --vcf)"},
     {"MM_VCF_MERGE_PAIRS", "64 * 2^20", "test", "mapDirectly --vcf: (w0, w1, count) triples a query file's accumulator may hold before it is replaced by its mm_vcf_merge (small values: several merges on small runs; no result depends on it)"},
-    {"MM_MODS_TIMING", "unset", "debug", "device times of the modification plane's upload and kernel in mm_seqset_upload with its groups, calls and staged bytes, of mm_mod_events' upload, count, scan, emit, sort and reduce stages (events; reduce includes the table's copy to the host) with its jobs, runs, events, pairs and fetched bytes, and of the stages of mm_mod_merge and mm_mod_finish, on stderr"},
+    {"MM_MODS_TIMING", "unset", "debug", "device times of the modification plane's upload and kernel in mm_seqset_upload with its groups, calls and staged bytes, of mm_mod_events' upload, count, scan, emit, sort and reduce stages (events; reduce includes the table's copy to the host) with its jobs, runs, events, pairs and fetched bytes, and of the stages of mm_mod_merge and mm_mod_finish, and of mm_mod_motifs' scan, sites and order stages with the group's contig range, tiles, entries, listed contigs, motifs and rows, on stderr"},
     {"MM_MODS_MERGE_PAIRS", "64 * 2^20", "test", "mapDirectly --mods: (key, count) pairs a query file's accumulator may hold before it is replaced by its mm_mod_merge (small values: several merges on small runs; no result depends on it)"},
     {"MM_CONS_TIMING", "unset", "debug", "device times of mm_consensus' intervals, candidates, select, positions, offsets and emit stages (emit includes the text's copy to the host) with the group's contig range, bases, entries, intervals, kept rows, written contigs and text bytes, on stderr (tools/edit_kernel_stats.py --consensus)"},
     {"MM_DEPTH_TIMING", "unset", "debug", "device times of mm_depth_profile's intervals, breakpoints, runs, contigs and windows stages (each includes its results' copy to the host) with its intervals, unique breakpoints, runs, listed contigs and windows, on stderr (tools/edit_kernel_stats.py --depth)"},
@@ -119,6 +119,7 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_ERRPROF_TIMING", "unset", "debug", "device times of mm_errprof_events' upload, check, walk and sum stages (sum includes the results' copy to the host) with its jobs, runs and workgroups, and of mm_errprof_finish's sort and rows stages with its entries and listed contigs, on stderr (tools/edit_kernel_stats.py --error-profile)"},
     {"MM_ERRPROF_GROUPS", "16 per CU", "test", "mm_errprof_events: workgroups of the walk, each with its counters in LDS and one row of partial sums, grid-stride over the jobs (never more than the jobs or 65536; 1 or 3: a workgroup walks many jobs on small inputs; no result depends on it)"},
     {"MM_CONS_GROUP_BASES", "2^28", "test", "mapDirectly --consensus: reference bases one mm_consensus call may cover; consecutive contigs are grouped up to it and a longer contig is a group alone (small values: one call per contig on small runs; no result depends on it)"},
+    {"MM_MOTIF_GROUP_BASES", "2^28", "test", "mapDirectly --mod-motifs: reference bases one mm_mod_motifs call may cover; consecutive contigs are grouped up to it and a longer contig is a group alone (small values: one call per contig on small runs; no result depends on it)"},
     {"MM_CLI_FORMAT_PART", "10000", "test", "mapping records per formatter thread of a batch (the text of a batch is formatted in up to eight parts and joined)"},
     {"MM_CLI_CLASSIFY_FROM_FILE", "unset", "test", "mapDirectly --then-classify reads PREFIX back and tokenises it (as `classify` does) instead of taking the lines it has just formatted from memory"},
     {"MM_GATHER_SELF_SEND", "unset", "test", "mm_mapping_gather sends the owner's own parts through ncclSend / ncclRecv too (one-GPU test of the exchange)"},

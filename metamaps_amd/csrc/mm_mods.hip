@@ -204,9 +204,8 @@ void mod_events_run(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* ref, c
   key_events_run<ModEvents>(ctx, reads, ref, in, use, min_ml, out);
 }
 
-void mod_finish_run(mm_ctx* ctx, const mm_seqset* ref, int64_t n, const uint64_t* keys, const uint32_t* counts, int32_t n_codes, const uint8_t* code_base, int64_t min_coverage,
-                    ModResult* out) {
-  const std::string w = "mm_mod_finish: ";
+mmd::CodeBases mod_table_checks(const std::string& w, mm_ctx* ctx, const mm_seqset* ref, int64_t n, const uint64_t* keys, int32_t n_codes, const uint8_t* code_base,
+                                int64_t min_coverage) {
   MM_REQUIRE(ref->frozen, MM_ERR_STATE, w + "the reference is not uploaded");
   MM_REQUIRE(ref->ctx->device == ctx->device, MM_ERR_ARG, w + "the reference lives on another device");
   MM_REQUIRE(ref->count() <= mmd::MAX_CONTIGS, MM_ERR_ARG, w + "more than 2^28 contigs");
@@ -224,6 +223,12 @@ void mod_finish_run(mm_ctx* ctx, const mm_seqset* ref, int64_t n, const uint64_t
     MM_REQUIRE(mmd::key_contig(key) < ref->count() && mmd::key_pos(key) < ref->len[(size_t)mmd::key_contig(key)] && mmd::key_class(key) < mmd::CLASS_CODE0 + (uint32_t)n_codes, MM_ERR_ARG,
                w + "entry " + std::to_string(i) + " names no position of the reference, or no class of the asked codes");
   }
+  return cb;
+}
+
+void mod_finish_run(mm_ctx* ctx, const mm_seqset* ref, int64_t n, const uint64_t* keys, const uint32_t* counts, int32_t n_codes, const uint8_t* code_base, int64_t min_coverage,
+                    ModResult* out) {
+  const mmd::CodeBases cb = mod_table_checks("mm_mod_finish: ", ctx, ref, n, keys, n_codes, code_base, min_coverage);
   out->site.clear(); out->n_mod.clear(); out->n_canonical.clear(); out->n_other.clear(); out->n_fail.clear();
   if (n == 0) return;
   hipStream_t st = ctx->stream;

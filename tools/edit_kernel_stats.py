@@ -21,6 +21,9 @@ mm_errprof_finish.  One run is one run.
 independent of the bases): the upload's wall time both ways with the staged bytes (the MM_MODS_TIMING plane line), then in the same process mm_pileup_events
 and mm_mod_events twice each on the same alignments (the MM_PILEUP_TIMING and MM_MODS_TIMING stage lines), mm_mod_merge and mm_mod_finish with the table's
 size.  Synthetic tags say nothing about real methylation.  One run is one run.
+--motifs: the run of --mods, and behind its mm_mod_finish in the same process mm_mod_motifs (mm_motif_core.hpp, mm_motif.hip) over the same table with the motifs
+GATC:1, CCWGG:1 and CG:0, twice without and twice with combined strands, one call per group of at most 2^28 reference bases: the MM_MODS_TIMING motifs lines (scan,
+sites, order and copies), the wall time, rows and sums, beside that run's mm_mod_finish.  Written to profiles/motif_stats.txt.  One run is one run.
 --depth: the batch through mm_mapping_edit_distances (the intervals need no traceback), then twice through mm_depth_profile (mm_depth_core.hpp, mm_depth.hip)
 at the default window and thresholds and once at W = 1 000 000: the MM_DEPTH_TIMING stage lines, the wall time of each call with its copies, the runs, listed
 contigs and windows, beside mm_pileup_finish over an empty table and the same intervals (the MM_PILEUP_TIMING finish line), whose three per-contig sums the
@@ -480,7 +483,10 @@ def child_qual(n_reads, floor):
     M.close(); idx.close(); reads.close(); plain.close(); ref.close(); ctx.close()
 
 
-def child_mods(n_reads):
+MOTIFS = [("GATC", 1), ("CCWGG", 1), ("CG", 0)]                  # --motifs: Dam, Dcm and CpG
+
+
+def child_mods(n_reads, motifs=False):
     import ctypes as C
     from metamaps_amd import capi
     ctx = capi.Context(0)
@@ -554,12 +560,39 @@ def child_mods(n_reads):
     dt = time.perf_counter() - t0
     print(f"mm_mod_finish (codes C+m, A+a; min_coverage 1): {1e3 * dt:.1f} ms wall with the copies, {len(rows['site'])} rows of {len(keys)} entries, "
           f"{int(rows['n_mod'].sum())} modified, {int(rows['n_canonical'].sum())} canonical, {int(rows['n_fail'].sum())} failed calls", flush=True)
+    if motifs:                                                     # the groups the CLI would make: consecutive contigs up to 2^28 bases
+        lens, groups, lo, bases = ref.lengths(), [], 0, 0
+        for c, n_c in enumerate(lens.tolist()):
+            if c > lo and bases + n_c > (1 << 28):
+                groups.append((lo, c)); lo, bases = c, 0
+            bases += n_c
+        groups.append((lo, len(lens)))
+        for combine in (False, True):
+            for rep in range(2):
+                t0 = time.perf_counter()
+                got = [ctx.mod_motifs(ref, a, b, keys, counts, "CA", MOTIFS, 1, 0.5, combine) for a, b in groups]
+                dt = time.perf_counter() - t0
+                sums = np.concatenate([g["sums"] for g in got]).sum(axis=0).tolist()
+                print(f"mm_mod_motifs ({', '.join('%s:%d' % m for m in MOTIFS)}; codes C+m, A+a; min_coverage 1, min_frac 0.5, combine_strands {int(combine)}) call {rep}: {1e3 * dt:.1f} ms wall "
+                      f"with the copies (every call checks the whole table on the host; only the group's slice of it goes to the device), {len(groups)} group(s) over {int(lens.sum())} reference bases, {sum(len(g['site']) for g in got)} rows, "
+                      f"sums over contigs, motifs and codes: sites {sums[0]}, covered {sums[1]}, modified {sums[2]}, N_valid_cov {sums[3]}, N_mod {sums[4]}", flush=True)
     M.close(); idx.close(); reads.close(); plain.close(); ref.close(); ctx.close()
 
 
 def main():
-    if len(sys.argv) > 1 and sys.argv[1] == "--child-mods":
-        return child_mods(int(sys.argv[2]))
+    if len(sys.argv) > 1 and sys.argv[1] in ("--child-mods", "--child-motifs"):
+        return child_mods(int(sys.argv[2]), sys.argv[1] == "--child-motifs")
+    if len(sys.argv) > 1 and sys.argv[1] == "--motifs":
+        n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-motifs", str(n_reads)], env=dict(os.environ, MM_MODS_TIMING="1"), stdout=subprocess.PIPE,
+                           stderr=subprocess.STDOUT, timeout=1100)
+        text = f"tools/edit_kernel_stats.py --motifs {n_reads}: one batch of {n_reads} reads, best mappings only; one run\n" + p.stdout.decode()
+        print(text)
+        if p.returncode != 0:
+            sys.exit(p.returncode)
+        with open(os.path.join(ROOT, "profiles", "motif_stats.txt"), "w") as f:
+            f.write(text)
+        return None
     if len(sys.argv) > 1 and sys.argv[1] == "--mods":
         n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-mods", str(n_reads)], env=dict(os.environ, MM_PILEUP_TIMING="1", MM_MODS_TIMING="1"), stdout=subprocess.PIPE,
