@@ -32,7 +32,7 @@ extern "C" {
                             * 5: mm_mapping_gather, mm_comm_info, mm_seqset_fetch_range;
                             * 6: mm_index_save, mm_index_load; mm_em_bootstrap, mm_gzip_*, mm_seqset_hpc + mm_hpc_map_* + mm_mapping_to_raw,
                             *    mm_em_lca, mm_gene_overlap, mm_ident_filter, mm_edit_infix + mm_mapping_edit_distances,
-                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_* (mm_bam_encode_sorted, mm_bam_fetch_records, mm_bam_sorter_*), mm_pileup_*, mm_vcf_*, mm_consensus*, mm_seqset_*_mods, mm_mod_* (mm_mod_motifs, mm_motif_result_*),
+                            *    mm_edit_infix_align + mm_mapping_align + mm_alignment_*, mm_bam_* (mm_bam_encode_sorted, mm_bam_fetch_records, mm_bam_sorter_*), mm_pileup_*, mm_vcf_*, mm_consensus*, mm_seqset_*_mods, mm_mod_* (mm_mod_motifs, mm_motif_result_*), mm_reads_encode + mm_reads_text_*,
                             *    mm_depth_*, mm_errprof_* (additions to 6) */
 
 typedef enum {
@@ -54,6 +54,7 @@ typedef struct mm_mapping mm_mapping;  /* mapping results of one read batch, res
 typedef struct mm_em mm_em;            /* EM state (mappings x taxa) resident in HBM              */
 typedef struct mm_gzip mm_gzip;        /* a plain gzip stream being inflated on a context's device */
 typedef struct mm_alignment mm_alignment;  /* base-level alignments (CIGAR runs) of a batch of jobs, in host memory */
+typedef struct mm_reads_text mm_reads_text;   /* BGZF members holding FASTQ / FASTA records of selected reads, in host memory */
 typedef struct mm_bam mm_bam;          /* BGZF members holding BAM records of a batch of jobs, in host memory */
 typedef struct mm_bam_sorter mm_bam_sorter;  /* sorted runs of BAM records being merged into one coordinate-sorted stream on a context's device */
 typedef struct mm_pileup mm_pileup;    /* a table of (key, count) pileup events, unique keys ascending, in host memory */
@@ -575,6 +576,27 @@ int mm_bam_encode_sorted(mm_ctx* ctx, const mm_seqset* reads, const mm_seqset* r
  * inflated bytes; raw_off[0] = 0 and raw_off[n_records] = raw_bytes. */
 int mm_bam_fetch_records(const mm_bam* bam, int64_t* job /* [n_records] */, int64_t* raw_off /* [n_records + 1] */);
 void mm_bam_destroy(mm_bam* bam);
+
+/* FASTQ / FASTA records of selected reads of an uploaded set, written and deflated on the context's device (mapDirectly --extract-*; DESIGN.md
+ * section 1, "Read extraction"; the record: csrc/mm_reads_out_core.hpp).  Record i is read read[i] of the set under the name names[name_off[i],
+ * name_off[i + 1]); the indices come in any order and may repeat.  with_qual 1: "@name\nBASES\n+\nQUAL\n", QUAL the stored Phred values + 33 and '!'
+ * on every base without a quality (a read added without qualities; a set without a quality plane, which is valid); with_qual 0: ">name\nBASES\n",
+ * unwrapped.  BASES are the bytes the set holds, in the read's own orientation: upper-cased, bytes other than A C G T verbatim, nt16 codes as their
+ * letters; an empty read gives empty lines.  The records of consecutive indices go into groups of at most group_bytes raw bytes (0: 255 MiB; a larger
+ * record is a group of its own); each group is deflated where it was written and only its BGZF members come to the host, back to back.  The inflated
+ * stream does not depend on group_bytes.  The 28-byte end-of-file block is the caller's to write.
+ * MM_ERR_ARG with "mm_reads_encode: record <index>: rule <number>: ..." in mm_last_error, *out NULL and nothing written, for the lowest record that
+ * breaks a rule (and its lowest rule):  1 a read outside the set;  2 a name of 0 or more than 254 bytes;  3 a name byte outside 0x21..0x7E.
+ * MM_ERR_STATE for a set that is not uploaded and for a result of mm_seqset_hpc, which does not hold the reads' own bases. */
+int mm_reads_encode(mm_ctx* ctx, const mm_seqset* reads, int64_t n_sel,
+                    const int32_t* read,                                      /* indices into the set, any order, repeats allowed */
+                    const int64_t* name_off /* [n_sel + 1] */, const char* names,
+                    int with_qual,                                            /* 0: FASTA records, 1: FASTQ records */
+                    int64_t group_bytes,                                      /* 0: 255 MiB */
+                    mm_reads_text** out);
+int mm_reads_text_sizes(const mm_reads_text* text, int64_t* n_records, int64_t* raw_bytes, int64_t* bgzf_bytes);
+int mm_reads_text_fetch(const mm_reads_text* text, uint8_t* bgzf /* [bgzf_bytes] */);
+void mm_reads_text_destroy(mm_reads_text* text);
 
 /* The coordinate sort of BAM records: sorted runs (mm_bam_encode_sorted's members, one run per call) merged on the context's device into one stream of
  * BGZF members, and its BAI index ("Sorted BAM"; the definitions: csrc/mm_bam_sort_core.hpp).  The sorter never looks inside a

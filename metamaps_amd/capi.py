@@ -211,6 +211,10 @@ def lib() -> C.CDLL:
             "mm_alignment_fetch": (C.c_int, [vp, vp, vp, vp, vp, vp]),
             "mm_alignment_destroy": (None, [vp]),
             "mm_bam_encode": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+            "mm_reads_encode": (C.c_int, [vp, vp, i64, vp, vp, vp, C.c_int, i64, vp]),
+            "mm_reads_text_sizes": (C.c_int, [vp, vp, vp, vp]),
+            "mm_reads_text_fetch": (C.c_int, [vp, vp]),
+            "mm_reads_text_destroy": (None, [vp]),
             "mm_bam_encode_sorted": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
             "mm_bam_fetch_records": (C.c_int, [vp, vp, vp]),
             "mm_bam_sorter_create": (C.c_int, [vp, C.c_int32, vp, i64, vp]),
@@ -710,6 +714,29 @@ class Context:
             self.last_bam_handle = h.value                          # (what the call left in *out: None after a refusal)
             if h.value:
                 lib().mm_bam_destroy(h)
+
+    def reads_encode(self, reads: "SeqSet", read, names, with_qual, group_bytes=0):
+        """FASTQ (with_qual 1) or FASTA (0) records of the reads `read` of the set under `names`, one bytes object each, as BGZF members (mm_reads_encode).
+        Returns (members back to back as bytes, number of records, raw bytes of the records)."""
+        rd = np.ascontiguousarray(read, dtype=np.int32)
+        n = len(rd)
+        assert len(names) == n
+        no = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in names], out=no[1:])
+        text = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8).copy()
+        h = C.c_void_p(0xDEAD)                                      # (the call sets it, to NULL on an error)
+        st = lib().mm_reads_encode(self.h, reads.h, n, _ptr(rd), _ptr(no), _ptr(text), int(with_qual), int(group_bytes), C.byref(h))
+        try:
+            self.check(st)
+            nr, raw, nb = C.c_int64(-1), C.c_int64(-1), C.c_int64(-1)
+            assert lib().mm_reads_text_sizes(h, C.byref(nr), C.byref(raw), C.byref(nb)) == 0
+            out = np.zeros(max(nb.value, 1), dtype=np.uint8)
+            assert lib().mm_reads_text_fetch(h, _ptr(out)) == 0
+            return out[:nb.value].tobytes(), nr.value, raw.value
+        finally:
+            self.last_reads_text_handle = h.value                   # (what the call left in *out: None after a refusal)
+            if h.value:
+                lib().mm_reads_text_destroy(h)
 
     def _key_table(self, kind, status, handle):
         """(keys, counts) of an mm_pileup or an mm_mod, (w0, w1, counts) of an mm_vcf, which is destroyed (kind: "pileup", "mod", "vcf"); `handle` is NULL after

@@ -1,4 +1,4 @@
-// The side outputs of a batch of mapDirectly (the rows of side_files.hpp: PREFIX.editDistances, .paf, .bam) and the device calls they need, and the run's
+// The side outputs of a batch of mapDirectly (the rows of side_files.hpp: PREFIX.editDistances, .paf, .bam and the four read files of reads_out.hpp) and the device calls they need, and the run's
 // pileup (PREFIX.pileup, .pileup.contigs), alleles (PREFIX.vcf), consensus (PREFIX.consensus.fa, .consensus.tsv), modification counts (PREFIX.bedmethyl, .motifs.*) and
 // depth profile (PREFIX.depth.bedgraph, .depth.windows, .depth.contigs) and error profile (PREFIX.errorProfile.*), which every batch adds to.  The text and
 // byte rules are in edit_dist.hpp, paf_out.hpp, bam_out.hpp, pileup_out.hpp, vcf_out.hpp, consensus_out.hpp, mods_out.hpp, motif_out.hpp, depth_out.hpp and errprof_out.hpp,
@@ -17,6 +17,7 @@
 #include "motif_out.hpp"
 #include "paf_out.hpp"
 #include "pileup_out.hpp"
+#include "reads_out.hpp"
 #include "side_files.hpp"
 #include "vcf_out.hpp"
 #include <memory>
@@ -299,6 +300,33 @@ struct RunVariants {
   }
 };
 
+// --extract-*, --deplete-taxa: what a batch's read files need beside the batch itself
+struct ReadsOut { ReadsOutOpts opts; ContigHits hits; };
+// ... per batch: the reads each file takes (reads_out.hpp) written as FASTQ / FASTA records and deflated on the context that holds the batch's reads
+// (mm_reads_encode); only the members come back.  A batch without a selected read adds nothing to the file.
+void extract_batch(mm_ctx* ctx, const mm_seqset* reads, const ReadsOut& ro, const std::vector<mm_map_record>& rec, const std::vector<std::string>& names,
+                   const std::vector<int64_t>& off, const std::string& text, SideBytes& out) {
+  std::vector<int32_t> contig(rec.size());
+  for (size_t i = 0; i < rec.size(); ++i) contig[i] = rec[i].ref_contig;
+  const std::vector<int32_t> primary = primary_contigs(off, contig, bam_line_q(text, rec.size()));
+  for (int f = 0; f < N_EXTRACT; ++f) {
+    if (!ro.opts.on[(size_t)f]) continue;
+    std::string& members = out[(size_t)kExtract[f].side];
+    members.clear();
+    const std::vector<int32_t> sel = extract_selection(f, primary, ro.hits);
+    if (sel.empty()) continue;
+    std::vector<int64_t> name_off(sel.size() + 1, 0); std::string all;
+    for (size_t i = 0; i < sel.size(); ++i) { all += names[(size_t)sel[i]]; name_off[i + 1] = (int64_t)all.size(); }
+    mm_reads_text* t = nullptr;
+    ck(ctx, mm_reads_encode(ctx, reads, (int64_t)sel.size(), sel.data(), name_off.data(), all.data(), ro.opts.with_qual ? 1 : 0, 0, &t), (std::string("--") + kExtract[f].flag).c_str());
+    int64_t n_records = 0, raw = 0, bytes = 0;
+    mm_reads_text_sizes(t, &n_records, &raw, &bytes);
+    members.resize((size_t)bytes);
+    if (bytes) mm_reads_text_fetch(t, (uint8_t*)&members[0]);
+    mm_reads_text_destroy(t);
+  }
+}
+
 // The side outputs of one batch, in the two steps the order of a batch's device calls leaves: the alignment needs the mapping, which goes before the
 // lines are formatted; the BAM records need the formatted lines (their mapping qualities are read from the text).  One alignment serves all three files.
 struct BatchSideOutputs {
@@ -316,15 +344,16 @@ struct BatchSideOutputs {
   bool depth = false;                                            // --depth: the intervals alone (no accumulator, no traceback: first and last come with the distances)
   SortedRun* sorted = nullptr;                                   // --bam-sorted: the batch's sorted run (bam_sort_out.hpp)
   ErrprofAcc* errprof = nullptr;                                 // --error-profile: the accumulator of the batch's query file (a third user of the reads' qualities)
+  const ReadsOut* extract = nullptr;                             // --extract-*, --deplete-taxa: the read files (they keep the reads until from_text, and need no alignment)
 
   // while the mapping lives: d, first, last (and the runs, where .paf or .bam want them) fetched once -> the lines of .editDistances and .paf.
   // The reads go here unless .bam needs them for SEQ, the pileup or the VCF for their mismatched and inserted bases, or --mods for their calls; --depth reads
   // none of them but keeps them until from_text, which does nothing without them.
-  // Nothing happens without reads (no side file was asked for).
+  // Nothing happens without reads (no side file was asked for), and nothing here for the read files alone: they need no alignment, and their reads wait.
   void from_mapping(mm_ctx* ctx, const mm_mapping* m, ReadsPtr& reads, const mm_seqset* reference, float pi, const std::vector<mm_map_record>& rec,
                     const std::vector<std::string>& names, const std::vector<int>& lens, const std::vector<int64_t>& off, const std::vector<std::string>& cname,
                     const std::vector<int>& clen, SideBytes& out) {
-    if (!reads) return;
+    if (!reads || !on[SIDE_EDIT]) return;
     const size_t n = rec.size();
     if (on[SIDE_PAF] || on[SIDE_BAM] || sorted || pile || vcf || mods || errprof) {
       mm_alignment* a = nullptr;
@@ -341,7 +370,7 @@ struct BatchSideOutputs {
     }
     edit_distance_text(al.dist.data(), al.first.data(), al.last.data(), names, off, rec, cname, out[SIDE_EDIT]);
     if (on[SIDE_PAF]) paf_text(al, names, lens, off, rec, cname, clen, out[SIDE_PAF]);
-    if (!on[SIDE_BAM] && !sorted && !pile && !vcf && !mods && !depth && !errprof) reads.reset();
+    if (!on[SIDE_BAM] && !sorted && !pile && !vcf && !mods && !depth && !errprof && !extract) reads.reset();
   }
 
   // once the lines are formatted: the batch's BAM records as BGZF members, encoded and deflated on the device, and its pileup events and alleles (all go by
@@ -349,9 +378,10 @@ struct BatchSideOutputs {
   void from_text(mm_ctx* ctx, ReadsPtr& reads, const mm_seqset* reference, const std::vector<mm_map_record>& rec, const std::vector<std::string>& names,
                  const std::vector<int64_t>& off, const std::string& text, SideBytes& out) {
     if (!reads) return;
+    if (extract) extract_batch(ctx, reads.get(), *extract, rec, names, off, text, out);   // (every read of the batch: one without a line is `unmapped`)
     std::string& members = out[SIDE_BAM];
     members.clear();
-    if (!rec.empty()) {
+    if (on[SIDE_EDIT] && !rec.empty()) {
       const BamFields F = bam_fields(al.dist, rec, names, off, text);
       if (pile || vcf || mods || depth || errprof) {
         const std::vector<uint8_t> use = pileup_use(F.flag, al.dist);

@@ -64,6 +64,10 @@ struct MapRun {
   const DepthOpts depth = depth_options(o);                      // --depth (implies --edit-distance): the intervals --pileup keeps, one profile per query file (depth_out.hpp)
   const ModsOpts mods = mods_options(o);                         // --mods (implies --edit-distance): a BAM query's MM/ML groups go to the device with its reads (mods_out.hpp)
   const MotifOpts motifs = motif_options(o, mods);               // --mod-motifs: the two motif files behind PREFIX.bedmethyl (motif_out.hpp)
+  // --extract-unmapped, --extract-mapped, --extract-taxa, --deplete-taxa: the read files (reads_out.hpp).  They need no alignment and no resident reference: a
+  // batch's reads live until its lines are formatted, and the packed reference goes as it does without them
+  ReadsOut extract{reads_out_options(o), {}};
+  const bool keep_reads = edit || extract.opts.any();            // a batch's reads outlive its mapping
   RunVariants var;
   std::string bgzf_head;                                         // what a BGZF side file starts with: the header of every PREFIX.bam as BGZF members (the contigs are the run's)
   std::vector<int> clen_raw; std::vector<mm_hpc_map*> hpc_map;
@@ -209,6 +213,7 @@ struct MapRun {
     loader.load(ref, refset);
     pc.lap("1 reference parse + pack + upload");
     pc.add("2 reference pack+upload (inside 1)", loader.t_pack);
+    if (extract.opts.any()) extract.hits = contig_hits(extract.opts, cname);   // (a contig without a taxon ends the run here, before anything is indexed or mapped)
     if (hpc) compress_reference();
     if (!only_index) { if (!sw.late_reader) start_reader(); start_prewarm(); }   // (MM_CLI_LATE_READER: measurement aid — the reader starts when the index is built)
     // the packed reference now lives on the device (0.25 B per base, for as long as chunks are cut out of it): what is left is what the indexes get
@@ -348,6 +353,8 @@ struct MapRun {
                 << (place == Place::Sharded ? "the chunk indexes are spread over the devices" : "chunk indexes are built and mapped one after the other") << "\n";
     }
     if (place != Place::Replicated && NC == 1 && !from_index && !maxMem) die("--stream-chunks / --shard-index need --maxmemory (the chunk rule of the reference, winSketch.hpp:274-329)");
+    if (extract.opts.any() && place != Place::Replicated)
+      die(std::string("--") + extract.opts.first_flag() + " needs every chunk index resident on every device, and this index does not fit one: a batch's reads stay on the device only then");
     if (edit && place != Place::Replicated)
       die(errprof_or(o, depth.on ? "--depth" : mods.on ? modflag(o) : cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : bam_sorted_of(o) ? "--bam-sorted"
                       : side[SIDE_PAF] ? "--paf" : "--edit-distance") + " needs the whole reference resident on every device, and this index does not fit one: run without it");
@@ -452,7 +459,8 @@ struct MapRun {
     std::vector<mm_map_record> rec((size_t)dn->off.back());
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), rec.data(), (int64_t)rec.size()), "fetch");
     BatchSideOutputs so{side, {}, var.pile(file), sw.pileup_merge_pairs, var.vcf(file), sw.vcf_merge_pairs, var.intervals(file), qual.min_base_quality,
-                        var.mods(file), sw.mods_merge_pairs, mods.min_ml, depth.on, var.sorted.on ? &dn->sorted : nullptr, var.errprof(file)};   // one alignment for all of them
+                        var.mods(file), sw.mods_merge_pairs, mods.min_ml, depth.on, var.sorted.on ? &dn->sorted : nullptr, var.errprof(file),
+                        extract.opts.any() ? &extract : nullptr};   // one alignment for all of them
     so.from_mapping(ctx, m, reads, refset[dev], pi, rec, dn->names, dn->lens, dn->off, cname, clen, dn->side);
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
@@ -488,9 +496,9 @@ struct MapRun {
       if (!out.is_open()) die("Cannot open output file " + out_name);
       std::array<std::ofstream, N_SIDE> sf;
       for (size_t s = 0; s < N_SIDE; ++s) if (side[s]) {
-        sf[s].open(prefix + kSideFiles[s].suffix, std::ios::binary);
-        if (!sf[s].is_open()) die("Cannot open output file " + prefix + kSideFiles[s].suffix);
-        if (kSideFiles[s].bgzf) sf[s].write(bgzf_head.data(), (std::streamsize)bgzf_head.size());
+        sf[s].open(prefix + side_suffix((int)s, extract.opts.with_qual), std::ios::binary);
+        if (!sf[s].is_open()) die("Cannot open output file " + prefix + side_suffix((int)s, extract.opts.with_qual));
+        if (kSideFiles[s].head) sf[s].write(bgzf_head.data(), (std::streamsize)bgzf_head.size());
       }
       size_t total = 0, tooShort = 0, mapped = 0, notMapped = 0; IdSet seen;   // (id_set.hpp: a std::set of 10^6 IDs bounded the mapping phase)
       for (;;) {
@@ -524,7 +532,7 @@ struct MapRun {
       for (size_t s = 0; s < N_SIDE; ++s) if (side[s]) {
         if (kSideFiles[s].bgzf) sf[s].write((const char*)kBgzfEof, sizeof kBgzfEof);
         sf[s].close();
-        if (!sf[s]) die("Error writing " + prefix + kSideFiles[s].suffix);
+        if (!sf[s]) die("Error writing " + prefix + side_suffix((int)s, extract.opts.with_qual));
       }
       std::ofstream meta(prefix + ".meta");                      // mapWrap.h:178-184
       meta << "TotalReads " << total << "\nReadsTooShort " << tooShort << "\nReadsMapped " << mapped << "\nReadsNotMapped " << notMapped << "\n";
@@ -573,7 +581,7 @@ struct MapRun {
           ck(ctx, mm_mapping_concat(ctx, parts.data(), chunk_base.data(), (int)parts.size(), &m), "merge chunks");
           for (auto* pm : parts) mm_mapping_destroy(pm);
         }
-        if (!edit) reads.reset();                                  // no side output needs them
+        if (!keep_reads) reads.reset();                            // no side output needs them
         const auto t2 = std::chrono::steady_clock::now();
         const size_t seq = bt->seq;
         auto dn = finish_mapping(ctx, d, m, std::move(bt->names), std::move(bt->lens), std::move(clens), bt->file, std::move(reads));

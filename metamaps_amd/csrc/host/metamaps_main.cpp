@@ -9,6 +9,7 @@
 //                       [--vcf [--vcf-min-count N] [--vcf-min-frac F]]
 //                       [--consensus [--consensus-min-depth D] [--consensus-min-frac F] [--consensus-min-called C]] [--mods LIST [--mod-min-ml T] [--mod-min-coverage N] [--mod-motifs M1,M2,...]]
 //                       [--depth [--depth-window W] [--depth-thresholds T1,T2,...]] [--error-profile]
+//                       [--extract-unmapped] [--extract-mapped] [--extract-taxa ID[,ID...]] [--deplete-taxa ID[,ID...]]
 //                        -r DB.fa -q reads.{fq,fa,fq.gz,bam} -o PREFIX [-k 16] [-w W] [-m 1000] [--pi 80] [-p 1e-3] [-t N] [--mm G] [--gpus N]
 //   metamaps index -r DB.fa -i IDX [same reference options]          metamaps mapAgainstIndex [--all] -i IDX -q reads.fq -o PREFIX [--gpus N]
 //   metamaps classify --DB DBDIR --mappings PREFIX [--minreads N] [-t N] [--gpus N] [--bootstrap B [--bootstrap-seed S]] [--lca T] [--genes] [--min-identity T [--refit]]
@@ -139,6 +140,21 @@
 // run without the flag.  Refused wherever --edit-distance is (host/errprof_out.hpp).  Not provided: a confusion table by the reference's homopolymer length, the
 // error rate along the read, per-read rows, secondary mappings, the flag outside mapDirectly.
 //
+// --extract-unmapped, --extract-mapped, --extract-taxa ID[,ID...], --deplete-taxa ID[,ID...] (mapDirectly; not in the reference, whose util/extractReads.pl re-reads the
+// FASTQ on the host; Kraken 2's --unclassified-out / --classified-out; may be combined with each other and with every other side output; none implies
+// --edit-distance): the reads themselves, one BGZF file per flag and query file beside PREFIX, in query order: PREFIX.unmapped.fq.gz (every read without a line in
+// PREFIX: the reads .meta counts as too short and as not mapped), PREFIX.mapped.fq.gz (every read with a line), PREFIX.taxa.fq.gz (the mapped reads whose PRIMARY
+// line, the largest printed field 14 and the first of equals, lies on a contig whose kraken:taxid is in the list) and PREFIX.depleted.fq.gz (every read the same
+// list would not take, unmapped ones included: host depletion).  A list is 1 to 64 distinct IDs x?[0-9]+, exact IDs only; under either taxon flag the reference's
+// header lines are scanned first and a contig without a kraken:taxid ends the run before any device work.  With --base-qualities (accepted with these flags; implied by --min-base-quality) a record is
+// "@ID\nBASES\n+\nQUAL\n" with '!' on every base of a read without qualities; without it the files are FASTA, "PREFIX.*.fa.gz", ">ID\nBASES\n" unwrapped.  ID is the
+// read's ID as PREFIX prints it (1 to 254 bytes), BASES the bytes the device holds: upper-cased, IUPAC letters kept, never reverse-complemented.  The context that
+// mapped a batch writes and deflates the records from the batch's packed reads (mm_reads_encode, csrc/mm_reads_out_core.hpp; host/reads_out.hpp); only the IDs go up
+// and only BGZF members come back.  The inflated files do not depend on batches, devices or groups; a file without a read is the 28-byte end-of-file block.  Every
+// other file of the run is the file of the same run without the flags; the packed reference is dropped as ever.  Refused, under the flag's own name: outside
+// mapDirectly, --hpc, --shard-index / --stream-chunks or an index that is not resident on every device, a malformed, repeated or empty list.  Not provided: selection
+// by the final EM assignment, subtree expansion of an ID, header comments and MM/ML, the original letter case, uncompressed output.
+//
 // --base-qualities, --min-base-quality Q (mapDirectly; not in the reference; samtools mpileup's -Q): the run keeps the base qualities of its queries (the quality
 // line of a FASTQ record in any of the text forms, the qual field of a BAM record; a FASTA record and a BAM record without have none) and uploads them beside
 // the bases, one byte per base (mm_seqset_add_qual; a quality character outside '!'..'~' ends the run).  --bam then writes every record's QUAL (reversed for
@@ -146,8 +162,8 @@
 // --pileup, --vcf and --consensus: a mismatched base counts iff its quality is >= Q, a deletion iff the read's bases on either side of the gap have it, an
 // insertion iff all its bases have it; a read without qualities passes every floor (mm_pileup_events_q, mm_vcf_events_q).  The alignments' intervals are
 // untouched: depth, DP and PREFIX.pileup.contigs stay raw, so count / depth errs low under a floor.  With Q > 0 the VCF header gains "##minBaseQuality=Q".
-// --base-qualities needs --bam, --min-base-quality or --error-profile (which counts the columns per reported quality), --min-base-quality one of --pileup,
-// --vcf, --consensus; both are refused wherever --edit-distance is.
+// --base-qualities needs --bam, --min-base-quality, --error-profile (which counts the columns per reported quality) or one of the --extract-* / --deplete-taxa
+// flags, --min-base-quality one of --pileup, --vcf, --consensus; both are refused wherever --edit-distance is.
 // Without the two flags every output is what it was.
 //
 // --hpc (mapDirectly; not in the reference; minimap2's -H): homopolymer-compressed mapping.  Every maximal run of equal bytes of the reference and
@@ -207,7 +223,7 @@ Options parse(int argc, char** argv) {
     if (a == "--host-gather" || a == "--peer-gather" || a == "--full-index" || a == "--compress-output" || a == "--hpc" || a == "--edit-distance" || a == "--paf" ||
         a == "--bam" || a == "--bam-sorted" || a == "--error-profile" ||
         a == "--pileup" || a == "--vcf" || a == "--consensus" || a == "--depth" || a == "--genes" || a == "--refit" || a == "--base-qualities" ||
-        a == "--mod-motif-combine-strands") { o.v[a.substr(2)] = "1"; continue; }
+        a == "--mod-motif-combine-strands" || a == "--extract-unmapped" || a == "--extract-mapped") { o.v[a.substr(2)] = "1"; continue; }
     if (a == "-h" || a == "--help") {
       std::cout << "see the header of metamaps_main.cpp / the reference's README\n"
                    "  --hpc  (mapDirectly) homopolymer-compressed mapping: runs of equal bases of the reference and the reads are collapsed on the device before\n"
@@ -256,6 +272,10 @@ Options parse(int argc, char** argv) {
                    "         bases per reported base quality with the empirical error rate; needs --base-qualities, else the row `none` alone) and .contigs (per contig the\n"
                    "         exact identity of its primary alignments, gap-compressed identity and the spread across reads), counted on the device; may be combined with the\n"
                    "         other outputs; not with --hpc, --shard-index, --stream-chunks\n"
+                   "  --extract-unmapped, --extract-mapped, --extract-taxa ID[,ID...], --deplete-taxa ID[,ID...]  (mapDirectly) also write the reads themselves as BGZF, in query\n"
+                   "         order: PREFIX.unmapped.fq.gz (no line in PREFIX), .mapped.fq.gz (a line), .taxa.fq.gz (the primary line lies on a contig of a listed kraken:taxid) and\n"
+                   "         .depleted.fq.gz (every read the list would not take); FASTQ with --base-qualities, else FASTA (.fa.gz); written and deflated on the device from the\n"
+                   "         batch's packed reads; lists of 1 to 64 exact IDs; no --edit-distance implied; not with --hpc, --shard-index, --stream-chunks\n"
                    "  --lca T  (classify, mapDirectly --then-classify) T in [0.51, 1]: also assign every read to the deepest taxon that holds T of its posterior mass;\n"
                    "         adds PREFIX.EM.reads2Taxon.lca and the Kraken-style report PREFIX.EM.kreport\n"
                    "  --genes  (classify, mapDirectly --then-classify) gene-level analysis against DB_annotations.txt and DB_proteins.faa.annotated of the DB:\n"
@@ -362,6 +382,14 @@ int main(int argc, char** argv) {
     if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it carries the qualities of a run's reads to the device that aligns them");
     if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: a homopolymer-compressed read has no per-base qualities");
     if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");
+  }
+  const ReadsOutOpts extract_opts = reads_out_options(o);       // (the lists; MapRun reads them again)
+  if (extract_opts.any()) {                                      // (refused under the flag's own name, before any device work)
+    const std::string flag = std::string("--") + extract_opts.first_flag();
+    if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it writes a run's reads from the batches that run holds on the device");
+    if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reads do not stay on the device");
+    if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: a batch's reads stay on the device only when every chunk index is resident");
+    if (o.v.count("reference")) check_reference_taxa(extract_opts, o.v.at("reference"));   // (a contig without a taxon: said before any device work)
   }
   if (o.v.count("paf") || o.v.count("bam") || o.v.count("bam-sorted") || pileup_opts.on || vcf_opts.on || cons_opts.on || mods_opts.on || depth_opts.on || errprof_of(o))
     o.v["edit-distance"] = "1";                                  // (all nine imply it and inherit its refusals)

@@ -13,6 +13,7 @@
 #pragma once
 #include "../mm_pileup_core.hpp"
 #include "cli_common.hpp"
+#include "side_files.hpp"
 #include "fast_format.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -30,7 +31,8 @@ QualOpts qual_options(const Options& o) {
     if (v.empty() || v.size() > 2 || v.find_first_not_of("0123456789") != std::string::npos || std::stoi(v) > 93) die("--min-base-quality takes an integer from 0 to 93, not '" + v + "'");
     if (!o.v.count("pileup") && !o.v.count("vcf") && !o.v.count("consensus")) die("--min-base-quality needs --pileup, --vcf or --consensus: nothing else counts a base's evidence");
     q.min_base_quality = std::stoi(v); q.keep = true;
-  } else if (q.keep && !o.v.count("bam") && !o.v.count("error-profile")) die("--base-qualities needs --bam or --min-base-quality (or --error-profile): nothing else would use the qualities");
+  } else if (q.keep && !o.v.count("bam") && !o.v.count("error-profile") && !reads_out_asked(o))
+    die("--base-qualities needs --bam or --min-base-quality (or --error-profile, --extract-unmapped, --extract-mapped, --extract-taxa, --deplete-taxa): nothing else would use the qualities");
   return q;
 }
 struct PileupOpts { bool on = false; long long min_count = 3; double min_frac = 0.2; };

@@ -8,23 +8,32 @@ namespace {
 struct SideFile {
   const char* flag;                                              // the option that asks for it, as Options::v names it
   const char* suffix;                                            // PREFIX + suffix
-  bool bgzf;                                                     // BGZF members: a head at open (the BAM header), kBgzfEof at close; else plain text
+  bool bgzf;                                                     // BGZF members, kBgzfEof at close; else plain text
+  bool head;                                                     // the BAM header (as BGZF members) at open; else an empty head
+  bool aligned;                                                  // made from the batch's alignment: implies --edit-distance
+  const char* suffix_no_qual;                                    // the suffix without --base-qualities where that differs (the read files: FASTA), else null
 };
-enum { SIDE_EDIT, SIDE_PAF, SIDE_BAM, N_SIDE };
+enum { SIDE_EDIT, SIDE_PAF, SIDE_BAM, SIDE_X_UNMAPPED, SIDE_X_MAPPED, SIDE_X_TAXA, SIDE_X_DEPLETED, N_SIDE };
 constexpr SideFile kSideFiles[N_SIDE] = {
-  {"edit-distance", ".editDistances", false},
-  {"paf", ".paf", false},
-  {"bam", ".bam", true},
+  {"edit-distance", ".editDistances", false, false, true, nullptr},
+  {"paf", ".paf", false, false, true, nullptr},
+  {"bam", ".bam", true, true, true, nullptr},
+  {"extract-unmapped", ".unmapped.fq.gz", true, false, false, ".unmapped.fa.gz"},   // the four read files (reads_out.hpp)
+  {"extract-mapped", ".mapped.fq.gz", true, false, false, ".mapped.fa.gz"},
+  {"extract-taxa", ".taxa.fq.gz", true, false, false, ".taxa.fa.gz"},
+  {"deplete-taxa", ".depleted.fq.gz", true, false, false, ".depleted.fa.gz"},
 };
+inline std::string side_suffix(int s, bool with_qual) { return !with_qual && kSideFiles[s].suffix_no_qual ? kSideFiles[s].suffix_no_qual : kSideFiles[s].suffix; }
 using SideSet = std::array<bool, N_SIDE>;
 
+inline bool reads_out_asked(const Options& o) { for (int s = 0; s < N_SIDE; ++s) if (!kSideFiles[s].aligned && o.v.count(kSideFiles[s].flag)) return true; return false; }
 // the rows a command line asks for: --paf and --bam imply --edit-distance (their alignment is the one whose distances that file lists)
 // --bam-sorted (bam_sort_out.hpp) is no row: its two files are written after the run's last batch; it implies --edit-distance too
 inline bool bam_sorted_of(const Options& o) { return o.v.count("bam-sorted") != 0; }
 inline SideSet side_files_of(const Options& o) {
   SideSet on{};
   for (int s = 0; s < N_SIDE; ++s) on[(size_t)s] = o.v.count(kSideFiles[s].flag) != 0;
-  for (int s = 0; s < N_SIDE; ++s) if (on[(size_t)s]) on[SIDE_EDIT] = true;
+  for (int s = 0; s < N_SIDE; ++s) if (on[(size_t)s] && kSideFiles[s].aligned) on[SIDE_EDIT] = true;   // (the read files need no alignment)
   if (bam_sorted_of(o)) on[SIDE_EDIT] = true;
   return on;
 }

@@ -13,6 +13,7 @@
 #include "mm_edit.hpp"
 #include "mm_bam.hpp"
 #include "mm_bam_sort.hpp"
+#include "mm_reads_out.hpp"
 #include "mm_pileup.hpp"
 #include "mm_vcf.hpp"
 #include "mm_mods.hpp"
@@ -847,6 +848,29 @@ int mm_bam_fetch(const mm_bam* b, uint8_t* bgzf) {
   return MM_OK;
 }
 void mm_bam_destroy(mm_bam* b) { delete b; }
+
+struct mm_reads_text { mm::ReadsText t; };                         // (host memory only, as mm_bam)
+int mm_reads_encode(mm_ctx* ctx, const mm_seqset* reads, int64_t n_sel, const int32_t* read, const int64_t* name_off, const char* names, int with_qual, int64_t group_bytes,
+                    mm_reads_text** out) {
+  if (!ctx || !reads || !out) return refused(out);
+  return created(ctx, out, [&](mm_reads_text& t) {
+    MM_REQUIRE(n_sel >= 0 && n_sel < ((int64_t)1 << 31), n_sel < 0 ? MM_ERR_ARG : MM_ERR_LIMIT, "mm_reads_encode: a negative number of records, or 2^31 or more");
+    MM_REQUIRE(n_sel == 0 || (read && name_off), MM_ERR_ARG, "mm_reads_encode: a null array");
+    MM_REQUIRE(with_qual == 0 || with_qual == 1, MM_ERR_ARG, "mm_reads_encode: with_qual is neither 0 nor 1");
+    mm::reads_encode_run(ctx, reads, mm::ReadsSelection{n_sel, read, name_off, names}, with_qual != 0, group_bytes, &t.t);
+  });
+}
+int mm_reads_text_sizes(const mm_reads_text* t, int64_t* n_records, int64_t* raw_bytes, int64_t* bgzf_bytes) {
+  if (!t || !n_records || !raw_bytes || !bgzf_bytes) return MM_ERR_ARG;
+  *n_records = t->t.n_records; *raw_bytes = t->t.raw_bytes; *bgzf_bytes = (int64_t)t->t.bgzf.size();
+  return MM_OK;
+}
+int mm_reads_text_fetch(const mm_reads_text* t, uint8_t* bgzf) {
+  if (!t || (!t->t.bgzf.empty() && !bgzf)) return MM_ERR_ARG;
+  if (!t->t.bgzf.empty()) memcpy(bgzf, t->t.bgzf.data(), t->t.bgzf.size());
+  return MM_OK;
+}
+void mm_reads_text_destroy(mm_reads_text* t) { delete t; }
 
 struct mm_bam_sorter { mm_ctx* ctx = nullptr; mm::BamSorter s; };
 int mm_bam_sorter_create(mm_ctx* ctx, int32_t n_ref, const int32_t* ref_len, int64_t window_bytes, mm_bam_sorter** out) {

@@ -176,6 +176,7 @@ struct mm_ctx {
 struct mm_seqset {
   mm_ctx* ctx = nullptr;
   bool frozen = false;
+  bool hpc = false;                                             // a result of mm_seqset_hpc: the bases are not the sequences' own (mm_reads_encode refuses it)
   // host staging (until upload)
   std::deque<std::string> owned;                                // copies made by mm_seqset_add (stable addresses)
   std::vector<std::pair<const char*, size_t>> staged;           // what upload packs: views into `owned` or into caller memory (mm_seqset_add_view)
@@ -203,7 +204,8 @@ struct mm_seqset {
   // the quality plane (mm_seqset_add_qual; absent unless has_qual): byte base[i] + p is the Phred value 0..93 of base p of sequence i, 0xFF for "no
   // quality" (a sequence added without qualities, and the padding)
   bool has_qual = false;
-  mm::DBuf<uint8_t> qual;              // [base[n]]
+  mm::DBuf<uint8_t> qual;              // [base[n]]: every base[i] is a multiple of 16 and the buffer starts on a 4-byte boundary, so the aligned 4-byte word that
+                                       // holds any byte of sequence i lies inside [base[i], base[i + 1]) (mm_reads_out.hip reads the plane by such words)
   const uint8_t* qual_ptr() const { return has_qual ? qual.p : nullptr; }
   // the modification plane (mm_seqset_add_mods; absent unless has_mods): word base[i] + p is who | prob << 8 of base p of sequence i (mm_mods_core.hpp),
   // 0 for "no call" (a sequence added without groups, and the padding)

@@ -24,6 +24,18 @@ struct EditSeq {                                                  // the bases o
     if (n_exc) { const int64_t r = lower((uint64_t)g); if (r < n_exc && exc_start[r] <= (uint64_t)g) return exc_byte[r]; }
     return ascii_of_code((packed[g >> 4] >> (2 * (g & 15))) & 3u);
   }
+  // the bytes of g .. g + 3, all four inside one sequence, as one little-endian word: eight bits cut out of one or two packed words, or byte by byte
+  // where a run touches them
+  __device__ uint32_t bytes4(int64_t g) const {
+    if (n_exc) {
+      const int64_t r = lower((uint64_t)g);
+      if (r < n_exc && exc_start[r] < (uint64_t)g + 4) return (uint32_t)byte(g) | (uint32_t)byte(g + 1) << 8 | (uint32_t)byte(g + 2) << 16 | (uint32_t)byte(g + 3) << 24;
+    }
+    const uint32_t sh = 2 * (uint32_t)(g & 15);
+    uint32_t c = packed[g >> 4] >> sh;
+    if (sh > 24) c |= packed[(g >> 4) + 1] << (32 - sh);
+    return (uint32_t)ascii_of_code(c & 3u) | (uint32_t)ascii_of_code((c >> 2) & 3u) << 8 | (uint32_t)ascii_of_code((c >> 4) & 3u) << 16 | (uint32_t)ascii_of_code((c >> 6) & 3u) << 24;
+  }
   __device__ EditSeq narrowed(uint64_t g0, uint64_t g1) const {   // the runs that touch [g0, g1)
     EditSeq s = *this;
     if (!n_exc) return s;

@@ -116,6 +116,7 @@ inline const EnvSwitch* env_table(size_t* n) {
     {"MM_CONS_TIMING", "unset", "debug", "device times of mm_consensus' intervals, candidates, select, positions, offsets and emit stages (emit includes the text's copy to the host) with the group's contig range, bases, entries, intervals, kept rows, written contigs and text bytes, on stderr (tools/edit_kernel_stats.py --consensus)"},
     {"MM_DEPTH_TIMING", "unset", "debug", "device times of mm_depth_profile's intervals, breakpoints, runs, contigs and windows stages (each includes its results' copy to the host) with its intervals, unique breakpoints, runs, listed contigs and windows, on stderr (tools/edit_kernel_stats.py --depth)"},
     {"MM_BAM_SORT_WINDOW_MB", "255", "tuning", "mapDirectly --bam-sorted: MiB of sorted records the merge makes at a time (mm_bam_sorter_create's window_bytes), rounded down to whole members of 65 280 bytes, one member at least (0), 255 MiB at most; device memory of the merge is two windows; no file depends on it"},
+    {"MM_READS_OUT_TIMING", "unset", "debug", "device times of the upload, size, scan, write and deflate stages of mm_reads_encode (events; deflate includes the members' copy to the host) with its records, record kind, groups, raw and BGZF bytes on stderr (tools/edit_kernel_stats.py --reads-out)"},
     {"MM_ERRPROF_TIMING", "unset", "debug", "device times of mm_errprof_events' upload, check, walk and sum stages (sum includes the results' copy to the host) with its jobs, runs and workgroups, and of mm_errprof_finish's sort and rows stages with its entries and listed contigs, on stderr (tools/edit_kernel_stats.py --error-profile)"},
     {"MM_ERRPROF_GROUPS", "16 per CU", "test", "mm_errprof_events: workgroups of the walk, each with its counters in LDS and one row of partial sums, grid-stride over the jobs (never more than the jobs or 65536; 1 or 3: a workgroup walks many jobs on small inputs; no result depends on it)"},
     {"MM_CONS_GROUP_BASES", "2^28", "test", "mapDirectly --consensus: reference bases one mm_consensus call may cover; consecutive contigs are grouped up to it and a longer contig is a group alone (small values: one call per contig on small runs; no result depends on it)"},

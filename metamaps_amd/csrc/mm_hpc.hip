@@ -262,7 +262,7 @@ void seqset_hpc(mm_ctx* ctx, const mm_seqset* raw, mm_seqset* out, mm_hpc_map* m
     map->bitmap = std::move(bitmap);
   }
   MM_HIP(mm::stream_sync(st));
-  out->frozen = true;
+  out->frozen = true; out->hpc = true;
 }
 
 void hpc_map_to_raw(mm_hpc_map* map, const int32_t* seq, const int64_t* pos, int64_t n, int64_t* first_out, int64_t* last_out) {

@@ -5,6 +5,7 @@ tools/_tmp/), which also holds the device's answers against the host's.
 Usage: python tools/edit_kernel_stats.py [n_reads] [host sample]      (writes profiles/edit_kernel_stats.txt)
        python tools/edit_kernel_stats.py --align [n_reads]            (writes profiles/edit_trace_stats.txt)
        python tools/edit_kernel_stats.py --bam [n_reads]              (writes profiles/bam_encode_stats.txt)
+       python tools/edit_kernel_stats.py --reads-out [n_reads]        (writes profiles/reads_out_stats.txt)
        python tools/edit_kernel_stats.py --bam-sort [n_reads]         (writes profiles/bam_sort_stats.txt)
        python tools/edit_kernel_stats.py --pileup [n_reads]           (writes profiles/pileup_stats.txt)
        python tools/edit_kernel_stats.py --vcf [n_reads]              (writes profiles/vcf_stats.txt)
@@ -45,6 +46,10 @@ lines), the wall time of each call with its copies, the pairs of the batch and t
 as four sorted runs and again as one sorted run through mm_bam_sorter_* (mm_bam_sort.hip): the wall times of the runs' encode, of add_run, plan, every window and
 the index, and the bytes; the two splits must give byte-identical members and index.  The MM_BAM_SORT_TIMING lines have every window's inflate, gather and deflate times.  One
 run is one run.
+--reads-out: the same batch's reads, given seeded qualities, through mm_reads_encode (FASTA and FASTQ records of every read, written and deflated on the device:
+mm_reads_out_core.hpp, mm_reads_out.hip) twice each: the upload / size / scan / write / deflate stage times (the MM_READS_OUT_TIMING line) and the wall time of the call,
+and in the same process the alternative that needs no new kernel: the same text formatted by one host thread from the batch's arena and handed to mm_bgzf_deflate.
+
 --bam: the same batch through mm_mapping_align once and then twice through mm_bam_encode (the BAM records of these alignments, encoded and deflated on the
 device: mm_bam_core.hpp, mm_bam.hip): the upload / size / scan / write / deflate stage times (the MM_BAM_TIMING line), the wall time of the call with its
 copies, raw and BGZF bytes, beside the same run's mm_mapping_align time (the MM_EDIT_TIMING line) and the size PREFIX.paf would have.  The members are
@@ -100,6 +105,60 @@ def child(n_reads, n_sample):
     os.makedirs(os.path.dirname(exe), exist_ok=True)
     subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tools", "edit_host_align.cpp")], check=True)
     subprocess.run([exe], input=("\n".join(lines) + "\n").encode(), check=True)
+
+
+def child_reads_out(n_reads):
+    """--reads-out: the batch's reads (re-uploaded as ASCII with seeded qualities, which synthetic reads lack) through mm_reads_encode as FASTA and as FASTQ, twice
+    each, and the same text formatted by one host thread from the batch's arena and handed to mm_bgzf_deflate, in the same process"""
+    import ctypes as C
+    from metamaps_amd import capi
+    ctx = capi.Context(0)
+    ref = ctx.synth_reference(seed=20260928, n_species=25, strains_per_species=4, genome_len=2_200_000, strain_divergence=0.02, genus_divergence=0.2)
+    synth, _ = ctx.synth_reads(ref, seed=1000, n_reads=n_reads, read_len=READ_LEN, read_len_min=0, sub_rate=0.04, ins_rate=0.03, del_rate=0.05, frac_random=0.05, n_abundant=100)
+    arena, ln = synth.fetch_range(0, synth.count)
+    synth.close(); ref.close()
+    off = np.zeros(len(ln) + 1, dtype=np.int64); np.cumsum(ln, out=off[1:])
+    qual = np.random.default_rng(7).integers(2, 41, size=len(arena), dtype=np.uint8)   # seeded Phred 2..40, independent of the bases
+    seqs = [arena[off[i]:off[i + 1]].tobytes() for i in range(len(ln))]
+    t0 = time.perf_counter()
+    reads = ctx.seqset(seqs, quals=[(qual[off[i]:off[i + 1]] + 33).tobytes() for i in range(len(ln))], qual_offset=33)
+    print(f"{len(ln)} reads, {len(arena)} bases with qualities uploaded in {time.perf_counter() - t0:.2f} s (the Python wrapper's loop included)", flush=True)
+    names = [b"read%d" % i for i in range(len(ln))]
+    sel = np.arange(len(ln), dtype=np.int32)
+    got = {}
+    for wq in (0, 1):
+        for rep in range(2):
+            t0 = time.perf_counter()
+            data, n_rec, raw = ctx.reads_encode(reads, sel, names, wq)
+            dt = time.perf_counter() - t0
+            print(f"mm_reads_encode {'FASTQ' if wq else 'FASTA'} call {rep}: {1e3 * dt:.1f} ms wall with the copies (the Python wrapper's own included), {n_rec} records, "
+                  f"{raw / 1e6:.1f} MB raw, {len(data) / 1e6:.1f} MB BGZF", flush=True)
+        got[wq] = data
+    L = capi.lib()
+    for wq in (0, 1):
+        for rep in range(2):
+            t0 = time.perf_counter()
+            qc = qual + 33 if wq else None
+            parts = []
+            for i in range(len(ln)):
+                a, b = off[i], off[i + 1]
+                if wq:
+                    parts += [b"@", names[i], b"\n", arena[a:b].data, b"\n+\n", qc[a:b].data, b"\n"]
+                else:
+                    parts += [b">", names[i], b"\n", arena[a:b].data, b"\n"]
+            text = b"".join(parts)
+            t1 = time.perf_counter()
+            cap = L.mm_bgzf_deflate_bound(len(text))
+            out = np.empty(cap, dtype=np.uint8)
+            nbytes, nblocks = C.c_int64(-1), C.c_int32(-1)
+            ctx.check(L.mm_bgzf_deflate(ctx.h, text, len(text), out.ctypes.data_as(C.c_void_p), cap, C.byref(nbytes), C.byref(nblocks)))
+            t2 = time.perf_counter()
+            print(f"host alternative {'FASTQ' if wq else 'FASTA'} call {rep}: format on one host thread {1e3 * (t1 - t0):.1f} ms + mm_bgzf_deflate {1e3 * (t2 - t1):.1f} ms = "
+                  f"{1e3 * (t2 - t0):.1f} ms wall, {len(text) / 1e6:.1f} MB raw, {nbytes.value / 1e6:.1f} MB BGZF", flush=True)
+        import gzip
+        same = gzip.decompress(got[wq]) == text if len(text) < (1 << 28) else None
+        print(f"the device's inflated stream equals the host's text: {same if same is not None else 'not compared at this size'}", flush=True)
+    reads.close(); ctx.close()
 
 
 def paf_bytes(dist, first, last, op_off, ops, read, read_len, contig, contig_len):
@@ -688,6 +747,19 @@ def main():
         if p.returncode != 0:
             sys.exit(p.returncode)
         with open(os.path.join(ROOT, "profiles", "pileup_stats.txt"), "w") as f:
+            f.write(text)
+        return None
+    if len(sys.argv) > 1 and sys.argv[1] == "--child-reads-out":
+        return child_reads_out(int(sys.argv[2]))
+    if len(sys.argv) > 1 and sys.argv[1] == "--reads-out":
+        n_reads = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-reads-out", str(n_reads)], env=dict(os.environ, MM_READS_OUT_TIMING="1"),
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1100)
+        text = f"tools/edit_kernel_stats.py --reads-out {n_reads}: one batch of {n_reads} reads of {READ_LEN} bases, every read selected; one run\n" + p.stdout.decode()
+        print(text)
+        if p.returncode != 0:
+            sys.exit(p.returncode)
+        with open(os.path.join(ROOT, "profiles", "reads_out_stats.txt"), "w") as f:
             f.write(text)
         return None
     if len(sys.argv) > 1 and sys.argv[1] == "--child-bam-sort":
