@@ -4,9 +4,9 @@
 //   header    BAM\1, "@HD VN:1.6 SO:unsorted GO:query" (a read's records are consecutive;
 //             "@HD VN:1.6 SO:coordinate" for PREFIX.sorted.bam: bam_sort_out.hpp), one @SQ per contig in the reference's order with the contig ID
 //             as field 6 of PREFIX has it, "@PG ID:metamaps PN:metamaps" (no command line: the file is a function of the inputs), the binary reference
-//             list in the same order.  Built here, deflated by mm_bgzf_deflate on the first device (map_outputs.hpp).
+//             list in the same order.  Built here, deflated by mm_bgzf_deflate on the first device (run_outputs.hpp).
 //   records   encoded and deflated on the device that mapped the batch, from the alignment the PAF path fetched (mm_bam_encode, csrc/mm_bam_core.hpp;
-//             called from map_outputs.hpp): only the members come back.  This file supplies what the device cannot know: the name, the flag and the
+//             called from batch_outputs.hpp): only the members come back.  This file supplies what the device cannot know: the name, the flag and the
 //             mapping quality (bam_fields).
 //   mapq      from the TEXT of field 14 of the record's own line of PREFIX, q: 0 if q <= 0, 60 if 1 - q <= 1e-6, else min(60, floor(-10 log10(1 - q) + 0.5)).
 //   flag      0x10 for strand -; 0x100 on every record of a read but its primary, the aligned record with the largest q, the first of equals.

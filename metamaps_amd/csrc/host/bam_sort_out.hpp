@@ -65,7 +65,6 @@ struct SortedFile {
   void close() { if (f && fclose(f) != 0) die("Error writing " + tmp); f = nullptr; }
 };
 
-struct SortedBams { bool on = false; std::deque<SortedFile> files; };   // the run's: one per query file
 // BAI holds coordinates below 2^29
 void sorted_bam_check_contigs(const std::vector<std::string>& cname, const std::vector<int>& clen) {
   for (size_t c = 0; c < clen.size(); ++c)

@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <iostream>
 #include <map>
 #include <mutex>
@@ -53,6 +54,20 @@ uint64_t file_size(const std::string& f) {                       // commonFunc.h
 
 // the command line as parse() of metamaps_main.cpp leaves it: option values by their long names, the plain flags
 struct Options { std::map<std::string, std::string> v; bool all = false, stream = false, shard = false, em_host = false; };
+// The two shapes an option's number takes, for every *_options parser: whether the value is well-formed, and the value.  The ranges and the messages are the callers'.
+// Digits alone, 1 to max_digits of them (strtoull: past 64 bits it saturates and sets errno to ERANGE, which only --bootstrap-seed's 20 digits can reach).
+struct IntegerValue { bool ok; unsigned long long value; };
+inline IntegerValue integer_value(const std::string& v, size_t max_digits) {
+  const bool digits = !v.empty() && v.size() <= max_digits && v.find_first_not_of("0123456789") == std::string::npos;
+  return {digits, digits ? strtoull(v.c_str(), nullptr, 10) : 0};
+}
+// Digits with at most one point and at least one digit (1, 0.25, .5, 1.), 32 bytes at most: no sign, no exponent
+struct DecimalValue { bool ok; double value; };
+inline DecimalValue decimal_value(const std::string& v) {
+  const bool decimal = !v.empty() && v.size() <= 32 && v.find_first_not_of("0123456789.") == std::string::npos && v.find_first_of("0123456789") != std::string::npos &&
+                       v.find('.') == v.rfind('.');
+  return {decimal, decimal ? strtod(v.c_str(), nullptr) : 0};
+}
 // --bootstrap B [--bootstrap-seed S] (classify, mapDirectly --then-classify; not in the reference): B read-level Poisson bootstrap replicates of
 // the EM after the point estimate, PREFIX.EM.WIMP.bootstrap beside the WIMP.  B = 0: off (nothing changes, no file appears).
 struct BootOpts { int B = 0; uint64_t seed = 1; };

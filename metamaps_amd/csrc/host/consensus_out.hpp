@@ -29,18 +29,16 @@ ConsOpts consensus_options(const Options& o) {
     if (!o.v.count(name)) return;
     const std::string& v = o.v.at(name);
     if (!p.on) die(std::string("--") + name + " needs --consensus");
-    const bool decimal = !v.empty() && v.size() <= 32 && v.find_first_not_of("0123456789.") == std::string::npos && v.find_first_of("0123456789") != std::string::npos &&
-                         std::count(v.begin(), v.end(), '.') <= 1;
-    const double x = decimal ? strtod(v.c_str(), nullptr) : -1;
-    if (!decimal || !(x >= lo && x <= 1.0)) die(std::string("--consensus: --") + name + " takes a decimal from " + range + " to 1, not '" + v + "'");
-    *out = x;
+    const DecimalValue x = decimal_value(v);
+    if (!x.ok || !(x.value >= lo && x.value <= 1.0)) die(std::string("--consensus: --") + name + " takes a decimal from " + range + " to 1, not '" + v + "'");
+    *out = x.value;
   };
   if (o.v.count("consensus-min-depth")) {
     const std::string& v = o.v.at("consensus-min-depth");
     if (!p.on) die("--consensus-min-depth needs --consensus");
-    if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos || std::stoll(v) < 1)
-      die("--consensus: --consensus-min-depth takes an integer from 1 to 999999999, not '" + v + "'");
-    p.min_depth = std::stoll(v);
+    const IntegerValue x = integer_value(v, 9);
+    if (!x.ok || x.value < 1) die("--consensus: --consensus-min-depth takes an integer from 1 to 999999999, not '" + v + "'");
+    p.min_depth = (long long)x.value;
   }
   decimal_of("consensus-min-frac", 0.5, "0.5", &p.min_frac);
   decimal_of("consensus-min-called", 0.0, "0", &p.min_called);

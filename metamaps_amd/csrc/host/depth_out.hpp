@@ -23,7 +23,8 @@ DepthOpts depth_options(const Options& o) {
   DepthOpts p;
   p.on = o.v.count("depth") != 0;
   auto integer_of = [](const std::string& v) -> long long {       // 1 to 999999999999, or -1
-    return v.empty() || v.size() > 12 || v.find_first_not_of("0123456789") != std::string::npos ? -1 : std::stoll(v);
+    const IntegerValue x = integer_value(v, 12);
+    return x.ok ? (long long)x.value : -1;
   };
   if (o.v.count("depth-window")) {
     const std::string& v = o.v.at("depth-window");

@@ -2,7 +2,7 @@
 //   readID contigID strand d first last        (strand + / -; first, last: 0-based inclusive contig coordinates; "NA NA NA": not aligned)
 // d, first and last come from the device (mm_mapping_edit_distances: Myers' bit-vector alignment of every record inside the window around its
 // mapped position, within floor(1.5 L (100 - pi) / 100) edits).  The context that mapped a batch aligns it, against its device's packed reference,
-// before the batch's reads and mapping are destroyed (map_outputs.hpp).  Text only: nothing here calls the device.
+// before the batch's reads and mapping are destroyed (batch_outputs.hpp).  Text only: nothing here calls the device.
 #pragma once
 #include "../../../include/metamaps_hip.h"
 #include "cli_common.hpp"

@@ -13,7 +13,7 @@
 //                                      medianIdentity q3Identity maxIdentity, and a last row * over all alignments with the listed contigs' summed length;
 //                                      identity = matches / (matches + mismatches + insertedBases + deletedBases), the gap-compressed one counts an indel run
 //                                      once; the five order statistics are per-alignment identities (ppm / 10^6); all seven %.6f
-// Text, arrays and the flag only: nothing here calls the device.
+// Text and arrays only (the flag itself is OutputPlan's, output_plan.hpp): nothing here calls the device.
 #pragma once
 #include "../mm_errprof_core.hpp"
 #include "cli_common.hpp"
@@ -23,10 +23,6 @@
 #include <mutex>
 
 namespace {
-
-bool errprof_of(const Options& o) { return o.v.count("error-profile") != 0; }
-// the flag a refusal names: this one where it is given, else the other side output's
-std::string errprof_or(const Options& o, const char* other) { return errprof_of(o) ? "--error-profile" : other; }
 
 // what the batches of one query file leave behind: the counters' sums and (key, six columns) of every contributing alignment
 struct ErrprofAcc {

@@ -1,5 +1,5 @@
 // One run of mapDirectly / index / mapAgainstIndex (MapRun).  What it stands on: the reference loader (ref_loader.hpp), the formatter of the
-// mapping lines (map_format.hpp) and a batch's side outputs (map_outputs.hpp, the files of side_files.hpp).
+// mapping lines (map_format.hpp) and the run's outputs beside PREFIX (output_plan.hpp says which; run_outputs.hpp and batch_outputs.hpp make them).
 #pragma once
 #include "classify_run.hpp"
 #include "cli_device.hpp"
@@ -7,12 +7,13 @@
 #include "id_set.hpp"
 #include "index_files.hpp"
 #include "map_format.hpp"
-#include "map_outputs.hpp"
 #include "query_reader.hpp"
 #include "ref_loader.hpp"
+#include "run_outputs.hpp"
 #include <climits>
 #include <cmath>
 #include <fstream>
+#include <optional>
 #include <sstream>
 
 namespace {
@@ -43,6 +44,10 @@ namespace {
 // records (sharded / streamed) -> writers -> optionally classify in-process.  (Until round 5 this was one 800-line function.)
 struct MapRun {
   const Options& o; const CliSwitches& sw; const std::string mode;
+  // what the command line asks for beside PREFIX (output_plan.hpp).  With an aligned output (plan.edit()) the packed reference stays on every device; a batch's
+  // reads live as long as the plan says (keep_reads(), reads_until_text()).  The read files need no alignment and no resident reference.
+  const OutputPlan& plan;
+  std::optional<RunOutputs> outs;                                // what the outputs keep between the batches (run_outputs.hpp): made once the number of query files is known
   const bool from_index, only_index;
   std::string ref; uint64_t refSize = 0, maxMem = 0; int k = 16, w = 0, minLen = 1000; double pval = 1e-3; float pi = 80;
   std::string ipre;
@@ -53,23 +58,6 @@ struct MapRun {
   // --hpc: the sequences are homopolymer-compressed on the device (mm_seqset_hpc) and everything from the chunk plan to the mapping qualities sees the
   // compressed ones: clen holds the compressed contig lengths, clen_raw what is printed; hpc_map[d] translates the records' coordinates on device d
   const bool hpc = o.v.count("hpc") != 0;
-  // --edit-distance, --paf, --bam (the last two imply the first): the side files of the run (side_files.hpp).  With any of them the packed reference
-  // stays on every device and a batch's reads live until its alignment is fetched, under --bam until its records are encoded (map_outputs.hpp)
-  const SideSet side = side_files_of(o);
-  const bool edit = side[SIDE_EDIT];
-  const PileupOpts pileup = pileup_options(o);                   // --pileup (implies --edit-distance): one accumulator per query file (pileup_out.hpp)
-  const VcfOpts vcf = vcf_options(o);                            // --vcf (implies --edit-distance): the same (vcf_out.hpp)
-  const ConsOpts cons = consensus_options(o);                    // --consensus (implies --edit-distance): --vcf's accumulator (consensus_out.hpp)
-  const QualOpts qual = qual_options(o);                         // --base-qualities, --min-base-quality: the batches carry the reads' qualities to the device
-  const DepthOpts depth = depth_options(o);                      // --depth (implies --edit-distance): the intervals --pileup keeps, one profile per query file (depth_out.hpp)
-  const ModsOpts mods = mods_options(o);                         // --mods (implies --edit-distance): a BAM query's MM/ML groups go to the device with its reads (mods_out.hpp)
-  const MotifOpts motifs = motif_options(o, mods);               // --mod-motifs: the two motif files behind PREFIX.bedmethyl (motif_out.hpp)
-  // --extract-unmapped, --extract-mapped, --extract-taxa, --deplete-taxa: the read files (reads_out.hpp).  They need no alignment and no resident reference: a
-  // batch's reads live until its lines are formatted, and the packed reference goes as it does without them
-  ReadsOut extract{reads_out_options(o), {}};
-  const bool keep_reads = edit || extract.opts.any();            // a batch's reads outlive its mapping
-  RunVariants var;
-  std::string bgzf_head;                                         // what a BGZF side file starts with: the header of every PREFIX.bam as BGZF members (the contigs are the run's)
   std::vector<int> clen_raw; std::vector<mm_hpc_map*> hpc_map;
   using Chunk = IndexChunk;                                      // (index_files.hpp)
   std::vector<Chunk> chunks;
@@ -88,7 +76,7 @@ struct MapRun {
   std::map<int64_t, int64_t> thr_acc; int thr = INT_MAX;          // occurrence histogram accumulated over the chunks, never cleared (winSketch.hpp:452-494)
   mm_map_params mp{};
   std::vector<int32_t> chunk_base;
-  using Done = BatchDone;                                        // what a worker hands to the writer (map_outputs.hpp)
+  using Done = BatchDone;                                        // what a worker hands to the writer (batch_outputs.hpp)
   // --then-classify: the batches of every query file as they were written, in order (text + the parsed fields of every line): what classify takes
   // instead of the file
   const bool keep_lines = o.v.count("then-classify") && !sw.classify_from_file;
@@ -104,7 +92,8 @@ struct MapRun {
   std::deque<MappedFile> mapped;                                 // query files whose sequences the batches point into: alive until the end
   std::thread prewarm;                                           // (declared last: joined first)
 
-  MapRun(const Options& o_, const std::string& mode_, const CliSwitches& sw_) : o(o_), sw(sw_), mode(mode_), from_index(mode_ == "mapAgainstIndex"), only_index(mode_ == "index") {}
+  MapRun(const Options& o_, const std::string& mode_, const CliSwitches& sw_, const OutputPlan& plan_)
+      : o(o_), sw(sw_), mode(mode_), plan(plan_), from_index(mode_ == "mapAgainstIndex"), only_index(mode_ == "index") {}
   ~MapRun() { if (prewarm.joinable()) prewarm.join(); }
 
   void read_parameters() {
@@ -183,7 +172,7 @@ struct MapRun {
 
   // (started as soon as the reference has been parsed: the first batches are ready when the index is)
   void start_reader() { if (reader.th.joinable() || reader.started) return; reader.started = true; 
-    reader.th = std::thread([this]() { QueryReader(reader, queries, BATCH_READS, BATCH_BASES, devs[0].phys, pc, mapped, sw, qual.keep, mods.on ? &mods : nullptr).run(); }); }
+    reader.th = std::thread([this]() { QueryReader(reader, queries, BATCH_READS, BATCH_BASES, devs[0].phys, pc, mapped, sw, plan.qual.keep, plan.mods.on ? &plan.mods : nullptr).run(); }); }
   void start_prewarm() {
     if (prewarm.joinable() || sw.no_prewarm) return;
     int64_t query_bytes = 0; for (auto& q : queries) query_bytes += (int64_t)file_size(q);
@@ -213,7 +202,7 @@ struct MapRun {
     loader.load(ref, refset);
     pc.lap("1 reference parse + pack + upload");
     pc.add("2 reference pack+upload (inside 1)", loader.t_pack);
-    if (extract.opts.any()) extract.hits = contig_hits(extract.opts, cname);   // (a contig without a taxon ends the run here, before anything is indexed or mapped)
+    outs->check_contigs(cname, clen);                            // (before anything is indexed or mapped)
     if (hpc) compress_reference();
     if (!only_index) { if (!sw.late_reader) start_reader(); start_prewarm(); }   // (MM_CLI_LATE_READER: measurement aid — the reader starts when the index is built)
     // the packed reference now lives on the device (0.25 B per base, for as long as chunks are cut out of it): what is left is what the indexes get
@@ -353,11 +342,10 @@ struct MapRun {
                 << (place == Place::Sharded ? "the chunk indexes are spread over the devices" : "chunk indexes are built and mapped one after the other") << "\n";
     }
     if (place != Place::Replicated && NC == 1 && !from_index && !maxMem) die("--stream-chunks / --shard-index need --maxmemory (the chunk rule of the reference, winSketch.hpp:274-329)");
-    if (extract.opts.any() && place != Place::Replicated)
-      die(std::string("--") + extract.opts.first_flag() + " needs every chunk index resident on every device, and this index does not fit one: a batch's reads stay on the device only then");
-    if (edit && place != Place::Replicated)
-      die(errprof_or(o, depth.on ? "--depth" : mods.on ? modflag(o) : cons.on ? "--consensus" : vcf.on ? "--vcf" : pileup.on ? "--pileup" : side[SIDE_BAM] ? "--bam" : bam_sorted_of(o) ? "--bam-sorted"
-                      : side[SIDE_PAF] ? "--paf" : "--edit-distance") + " needs the whole reference resident on every device, and this index does not fit one: run without it");
+    if (plan.reads.any() && place != Place::Replicated)
+      die(std::string("--") + plan.reads.first_flag() + " needs every chunk index resident on every device, and this index does not fit one: a batch's reads stay on the device only then");
+    if (plan.edit() && place != Place::Replicated)
+      die(std::string(plan.flag_name()) + " needs the whole reference resident on every device, and this index does not fit one: run without it");
     for (auto& d : devs) d.idx.assign(NC, nullptr);
     thr_of.assign(NC, INT_MAX);
   }
@@ -406,7 +394,7 @@ struct MapRun {
     if (place == Place::Replicated) {
       on_each(G, [&](size_t d) { for (size_t c = 0; c < NC; ++c) build_chunk(devs[d], c); });
       for (size_t c = 0; c < NC; ++c) settle_threshold(c);
-      if (!edit) drop_refsets();
+      if (!plan.edit()) drop_refsets();
       pc.lap("3 index build");
     }
   }
@@ -458,9 +446,7 @@ struct MapRun {
     const auto f1 = std::chrono::steady_clock::now();
     std::vector<mm_map_record> rec((size_t)dn->off.back());
     ck(ctx, mm_mapping_fetch(m, dn->off.data(), rec.data(), (int64_t)rec.size()), "fetch");
-    BatchSideOutputs so{side, {}, var.pile(file), sw.pileup_merge_pairs, var.vcf(file), sw.vcf_merge_pairs, var.intervals(file), qual.min_base_quality,
-                        var.mods(file), sw.mods_merge_pairs, mods.min_ml, depth.on, var.sorted.on ? &dn->sorted : nullptr, var.errprof(file),
-                        extract.opts.any() ? &extract : nullptr};   // one alignment for all of them
+    BatchSideOutputs so = outs->batch(file, *dn);
     so.from_mapping(ctx, m, reads, refset[dev], pi, rec, dn->names, dn->lens, dn->off, cname, clen, dn->side);
     mm_mapping_destroy(m);
     const auto f2 = std::chrono::steady_clock::now();
@@ -477,7 +463,7 @@ struct MapRun {
     dn->t_format = std::chrono::duration<double>(f3 - f2).count();
     return dn;
   }
-  // the text of a batch as BGZF members (map_outputs.hpp: the batches' members concatenate in output order); the text itself is kept only
+  // the text of a batch as BGZF members (batch_outputs.hpp: the batches' members concatenate in output order); the text itself is kept only
   // where --then-classify takes its lines from memory
   void deflate_text(mm_ctx* ctx, Done& dn) {
     const auto z0 = std::chrono::steady_clock::now();
@@ -495,10 +481,10 @@ struct MapRun {
       std::ofstream out(out_name, std::ios::binary), unm(prefix + ".meta.unmappedReadsLengths");
       if (!out.is_open()) die("Cannot open output file " + out_name);
       std::array<std::ofstream, N_SIDE> sf;
-      for (size_t s = 0; s < N_SIDE; ++s) if (side[s]) {
-        sf[s].open(prefix + side_suffix((int)s, extract.opts.with_qual), std::ios::binary);
-        if (!sf[s].is_open()) die("Cannot open output file " + prefix + side_suffix((int)s, extract.opts.with_qual));
-        if (kSideFiles[s].head) sf[s].write(bgzf_head.data(), (std::streamsize)bgzf_head.size());
+      for (size_t s = 0; s < N_SIDE; ++s) if (plan.side[s]) {
+        sf[s].open(prefix + side_suffix((int)s, plan.reads.with_qual), std::ios::binary);
+        if (!sf[s].is_open()) die("Cannot open output file " + prefix + side_suffix((int)s, plan.reads.with_qual));
+        if (kSideFiles[s].head) sf[s].write(outs->bam_head.data(), (std::streamsize)outs->bam_head.size());
       }
       size_t total = 0, tooShort = 0, mapped = 0, notMapped = 0; IdSet seen;   // (id_set.hpp: a std::set of 10^6 IDs bounded the mapping phase)
       for (;;) {
@@ -517,22 +503,22 @@ struct MapRun {
           ++mapped;
         }
         if (compress) out.write(d->gz.data(), (std::streamsize)d->gz.size()); else out << d->text;
-        for (size_t s = 0; s < N_SIDE; ++s) if (side[s]) {
+        for (size_t s = 0; s < N_SIDE; ++s) if (plan.side[s]) {
           sf[s].write(d->side[s].data(), (std::streamsize)d->side[s].size());
           std::string().swap(d->side[s]);
         }
         std::string().swap(d->gz);
-        if (var.sorted.on) var.sorted.files[fi].append(prefix, d->sorted);
+        outs->append_sorted(fi, prefix, *d);
         if (keep_lines) { if (kept.size() <= fi) kept.resize(fi + 1); d->names.clear(); d->names.shrink_to_fit(); kept[fi].push_back(std::move(d)); }
       }
       if (keep_lines && kept.size() <= fi) kept.resize(fi + 1);
       if (compress) out.write((const char*)kBgzfEof, sizeof kBgzfEof);
       out.close();
       if (!out) die("Error writing " + out_name);
-      for (size_t s = 0; s < N_SIDE; ++s) if (side[s]) {
+      for (size_t s = 0; s < N_SIDE; ++s) if (plan.side[s]) {
         if (kSideFiles[s].bgzf) sf[s].write((const char*)kBgzfEof, sizeof kBgzfEof);
         sf[s].close();
-        if (!sf[s]) die("Error writing " + prefix + side_suffix((int)s, extract.opts.with_qual));
+        if (!sf[s]) die("Error writing " + prefix + side_suffix((int)s, plan.reads.with_qual));
       }
       std::ofstream meta(prefix + ".meta");                      // mapWrap.h:178-184
       meta << "TotalReads " << total << "\nReadsTooShort " << tooShort << "\nReadsMapped " << mapped << "\nReadsNotMapped " << notMapped << "\n";
@@ -581,7 +567,7 @@ struct MapRun {
           ck(ctx, mm_mapping_concat(ctx, parts.data(), chunk_base.data(), (int)parts.size(), &m), "merge chunks");
           for (auto* pm : parts) mm_mapping_destroy(pm);
         }
-        if (!keep_reads) reads.reset();                            // no side output needs them
+        if (!plan.keep_reads()) reads.reset();                     // no side output needs them
         const auto t2 = std::chrono::steady_clock::now();
         const size_t seq = bt->seq;
         auto dn = finish_mapping(ctx, d, m, std::move(bt->names), std::move(bt->lens), std::move(clens), bt->file, std::move(reads));
@@ -764,10 +750,10 @@ struct MapRun {
 
   int run() {
     read_parameters();
+    outs.emplace(plan, sw, prefixes.size());
     open_devices();
     if (!from_index) {
       load_reference();
-      if (bam_sorted_of(o)) sorted_bam_check_contigs(cname, clen);   // (said before anything is indexed or mapped)
       plan_chunks();
       if (only_index) return write_index_files();
     } else read_index_files(ipre, cname, clen, ref_bases, chunks);   // `metamaps mapAgainstIndex` (mapWrap.h:443-554)
@@ -775,14 +761,13 @@ struct MapRun {
     build_resident_indexes();
     mp = mm_map_params{k, w, pi, minLen};
     for (auto& ch : chunks) chunk_base.push_back(ch.first);
-    var.resize(pileup.on, vcf.on, cons.on, mods.on, depth.on, bam_sorted_of(o), errprof_of(o), prefixes.size());
-    if (side[SIDE_BAM]) bgzf_head = bam_header_members(ctx0, cname, clen);   // (before the workers take the first device's context)
+    outs->deflate_bam_header(ctx0, cname, clen);                 // (before the workers take the first device's context)
     start_reader();
     if (prewarm.joinable()) prewarm.join();
     if (place != Place::Replicated) for (auto*& c : wctx) if (c) { mm_ctx_destroy(c); c = nullptr; }   // (the other modes drive one context per device)
     if (place == Place::Replicated) run_replicated(); else run_chunk_major();
     pc.lap("8 write");
-    var.write(ctx0, refset[0], pileup, vcf, cons, mods, motifs, depth, qual.min_base_quality, sw.cons_group_bases, sw.motif_group_bases, sw.bam_sort_window, prefixes, cname, clen);
+    outs->write(ctx0, refset[0], prefixes, cname, clen);
     then_classify();
     if (!sw.full_teardown) { if (reader.th.joinable()) reader.th.join(); pc.report(); finish_fast(); }
     drop_refsets();
@@ -791,6 +776,6 @@ struct MapRun {
   }
 };
 
-int map_mode(const Options& o, const std::string& mode, const CliSwitches& sw) { MapRun run(o, mode, sw); return run.run(); }
+int map_mode(const Options& o, const std::string& mode, const CliSwitches& sw, const OutputPlan& plan) { MapRun run(o, mode, sw, plan); return run.run(); }
 
 }  // namespace

@@ -52,14 +52,14 @@
 // "readID contigID strand d first last": the exact unit-cost edit distance of the whole read (its reverse complement for strand -) to the best
 // substring of the window contig[ref_start - pad, ref_start + L + pad), pad = 64 + L / 16, and that substring's 0-based inclusive coordinates;
 // "NA NA NA" where the distance is above floor(1.5 L (100 - pi) / 100) or the read is longer than 65 536 bases.  Aligned on the device that mapped
-// the batch (mm_mapping_edit_distances, host/map_outputs.hpp); every device keeps its packed reference (0.25 bytes per base) and a batch's reads live
+// the batch (mm_mapping_edit_distances, host/batch_outputs.hpp); every device keeps its packed reference (0.25 bytes per base) and a batch's reads live
 // until its distances are fetched.  PREFIX, .meta* and .parameters are the bytes of a run without the flag.  Refused: --hpc, index, mapAgainstIndex,
 // classify, and any run whose chunk indexes are sharded or streamed (--shard-index, --stream-chunks, or an index that does not fit one device).
 //
 // --paf (mapDirectly; not in the reference; implies --edit-distance): also PREFIX.paf, one PAF line per ALIGNED line of PREFIX in the same order,
 // "readID L 0 L strand contigID contigLen first last+1 matches alignmentLength 255 NM:i:d cg:Z:CIGAR" with = X I D runs: the base-level alignment
 // behind d, first and last (the definition: csrc/mm_edit_core.hpp; for strand - the reverse-complemented read along the forward contig).  The context
-// that mapped a batch traces it on the device in the one call that also gives the .editDistances lines (mm_mapping_align, host/map_outputs.hpp).  A mapping
+// that mapped a batch traces it on the device in the one call that also gives the .editDistances lines (mm_mapping_align, host/batch_outputs.hpp).  A mapping
 // that is not aligned has no PAF line.  PREFIX.paf is plain text even under --compress-output.  Refused wherever --edit-distance is.
 //
 // --bam (mapDirectly; not in the reference; implies --edit-distance; may be combined with --paf): also PREFIX.bam, one BAM record (SAM/BAM specification
@@ -295,19 +295,19 @@ Options parse(int argc, char** argv) {
 // --bootstrap B [--bootstrap-seed S]: validated here (BootOpts, cli_common.hpp)
 BootOpts boot_options(const Options& o) {
   BootOpts b;
-  auto digits = [](const std::string& v) { return !v.empty() && v.size() <= 20 && v.find_first_not_of("0123456789") == std::string::npos; };
   if (o.v.count("bootstrap")) {
     const std::string& v = o.v.at("bootstrap");
-    if (!digits(v) || v.size() > 6 || std::stoul(v) < 2 || std::stoul(v) > 100000) die("--bootstrap takes an integer from 2 to 100000, not '" + v + "'");
-    b.B = (int)std::stoul(v);
+    const IntegerValue x = integer_value(v, 6);
+    if (!x.ok || x.value < 2 || x.value > 100000) die("--bootstrap takes an integer from 2 to 100000, not '" + v + "'");
+    b.B = (int)x.value;
   }
   if (o.v.count("bootstrap-seed")) {
     const std::string& v = o.v.at("bootstrap-seed");
     errno = 0;
-    const unsigned long long x = digits(v) ? strtoull(v.c_str(), nullptr, 10) : 0;
-    if (!digits(v) || errno == ERANGE) die("--bootstrap-seed takes an unsigned 64-bit integer, not '" + v + "'");
+    const IntegerValue x = integer_value(v, 20);                 // (twenty digits may pass 2^64: ERANGE)
+    if (!x.ok || errno == ERANGE) die("--bootstrap-seed takes an unsigned 64-bit integer, not '" + v + "'");
     if (!b.B) die("--bootstrap-seed needs --bootstrap B");
-    b.seed = (uint64_t)x;
+    b.seed = (uint64_t)x.value;
   }
   return b;
 }
@@ -317,11 +317,9 @@ LcaOpts lca_options(const Options& o) {
   LcaOpts l;
   if (!o.v.count("lca")) return l;
   const std::string& v = o.v.at("lca");
-  const bool decimal = !v.empty() && v.size() <= 32 && v.find_first_not_of("0123456789.") == std::string::npos && v.find_first_of("0123456789") != std::string::npos &&
-                       std::count(v.begin(), v.end(), '.') <= 1;
-  const double x = decimal ? strtod(v.c_str(), nullptr) : 0;
-  if (!decimal || !(x >= 0.51 && x <= 1.0)) die("--lca takes a decimal threshold from 0.51 to 1, not '" + v + "'");
-  l.on = true; l.tau = x;
+  const DecimalValue x = decimal_value(v);
+  if (!x.ok || !(x.value >= 0.51 && x.value <= 1.0)) die("--lca takes a decimal threshold from 0.51 to 1, not '" + v + "'");
+  l.on = true; l.tau = x.value;
   return l;
 }
 
@@ -334,11 +332,9 @@ IdentOpts ident_options(const Options& o) {
   f.refit = o.v.count("refit") > 0;
   if (!o.v.count("min-identity")) { if (f.refit) die("--refit needs --min-identity T"); return f; }
   const std::string& v = o.v.at("min-identity");
-  const bool decimal = !v.empty() && v.size() <= 32 && v.find_first_not_of("0123456789.") == std::string::npos && v.find_first_of("0123456789") != std::string::npos &&
-                       std::count(v.begin(), v.end(), '.') <= 1;
-  const double x = decimal ? strtod(v.c_str(), nullptr) : -1;
-  if (!decimal || !(x >= 0.0 && x <= 1.0)) die("--min-identity takes a decimal threshold from 0 to 1, not '" + v + "'");
-  f.on = true; f.T = x;
+  const DecimalValue x = decimal_value(v);
+  if (!x.ok || !(x.value >= 0.0 && x.value <= 1.0)) die("--min-identity takes a decimal threshold from 0 to 1, not '" + v + "'");
+  f.on = true; f.T = x.value;
   return f;
 }
 
@@ -353,7 +349,7 @@ int main(int argc, char** argv) {
   const std::string mode = argv[1];
   if (mm::env_strict()) { const std::string bad = mm::env_unknown(); if (!bad.empty()) die("unknown MM_* environment switch(es): " + bad + " (MM_STRICT_ENV is set; see INTEGRATION.md)"); }
   const CliSwitches sw;                                           // the environment, read once (cli_switches.hpp)
-  Options o = parse(argc, argv);
+  const Options o = parse(argc, argv);
   const BootOpts boot = boot_options(o);                          // (validated before any work)
   if (boot.B && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--bootstrap needs classify or mapDirectly --then-classify");
   const LcaOpts lca = lca_options(o);
@@ -370,37 +366,10 @@ int main(int argc, char** argv) {
   if ((identf_opts.on || identf_opts.refit) && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify")))
     die("--min-identity and --refit need classify or mapDirectly --then-classify");
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
-  const PileupOpts pileup_opts = pileup_options(o);             // (validated before any work; MapRun reads them again)
-  const VcfOpts vcf_opts = vcf_options(o);                      // (the same)
-  const ConsOpts cons_opts = consensus_options(o);              // (the same)
-  const ModsOpts mods_opts = mods_options(o);                   // (the same)
-  (void)motif_options(o, mods_opts);                            // (the same)
-  const DepthOpts depth_opts = depth_options(o);                // (the same)
-  if (o.v.count("base-qualities") || o.v.count("min-base-quality")) {   // (refused under the flag's own name wherever --edit-distance is, before any device work)
-    const std::string flag = o.v.count("min-base-quality") ? "--min-base-quality" : "--base-qualities";
-    (void)qual_options(o);                                       // (the value and what uses it; MapRun reads them again)
-    if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it carries the qualities of a run's reads to the device that aligns them");
-    if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: a homopolymer-compressed read has no per-base qualities");
-    if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");
-  }
-  const ReadsOutOpts extract_opts = reads_out_options(o);       // (the lists; MapRun reads them again)
-  if (extract_opts.any()) {                                      // (refused under the flag's own name, before any device work)
-    const std::string flag = std::string("--") + extract_opts.first_flag();
-    if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it writes a run's reads from the batches that run holds on the device");
-    if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reads do not stay on the device");
-    if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: a batch's reads stay on the device only when every chunk index is resident");
-    if (o.v.count("reference")) check_reference_taxa(extract_opts, o.v.at("reference"));   // (a contig without a taxon: said before any device work)
-  }
-  if (o.v.count("paf") || o.v.count("bam") || o.v.count("bam-sorted") || pileup_opts.on || vcf_opts.on || cons_opts.on || mods_opts.on || depth_opts.on || errprof_of(o))
-    o.v["edit-distance"] = "1";                                  // (all nine imply it and inherit its refusals)
-  if (o.v.count("edit-distance")) {                              // (refused before any device work)
-    const std::string flag = errprof_or(o, depth_opts.on ? "--depth" : mods_opts.on ? modflag(o) : cons_opts.on ? "--consensus" : vcf_opts.on ? "--vcf" : pileup_opts.on ? "--pileup"
-                                           : o.v.count("bam") ? "--bam" : o.v.count("bam-sorted") ? "--bam-sorted" : o.v.count("paf") ? "--paf" : "--edit-distance");
-    if (mode != "mapDirectly") die(flag + " belongs to mapDirectly: it aligns a run's reads to the reference that run has packed on the device");
-    if (o.v.count("hpc")) die(flag + " cannot be combined with --hpc: the raw reference does not stay on the device");
-    if (o.stream || o.shard) die(flag + " cannot be combined with --shard-index or --stream-chunks: the whole reference must be resident where the reads are");
-  }
-  if (mode == "mapDirectly" || mode == "index" || mode == "mapAgainstIndex") return map_mode(o, mode, sw);
+  // every output of mapDirectly: parsed once, and refused under its own flag's name outside mapDirectly, with --hpc and with a sharded or streamed index (output_plan.hpp)
+  const OutputPlan plan = output_plan(o, mode);
+  if (plan.reads.any() && o.v.count("reference")) check_reference_taxa(plan.reads, o.v.at("reference"));   // (a contig without a taxon: said before any device work)
+  if (mode == "mapDirectly" || mode == "index" || mode == "mapAgainstIndex") return map_mode(o, mode, sw, plan);
   if (mode == "classify") {
     if (o.v.count("hpc")) die("--hpc belongs to mapDirectly: classify reads the raw coordinates a --hpc mapping reports and takes no such flag");
     if (!o.v.count("DB")) die("Provide path to DB.");

@@ -31,7 +31,6 @@ struct ModsOpts {
 ModsOpts mods_options(const Options& o) {
   ModsOpts m;
   m.on = o.v.count("mods") != 0;
-  auto digits = [](const std::string& v, size_t max) { return !v.empty() && v.size() <= max && v.find_first_not_of("0123456789") == std::string::npos; };
   if (m.on) {
     const std::string& list = o.v.at("mods");
     for (size_t a = 0; a <= list.size();) {
@@ -39,7 +38,7 @@ ModsOpts mods_options(const Options& o) {
       const std::string it = list.substr(a, e - a);
       const std::string code = it.size() > 2 ? it.substr(2) : "";
       const bool letters = !code.empty() && code.find_first_not_of("abcdefghijklmnopqrstuvwxyz") == std::string::npos;
-      if (it.size() < 3 || !strchr("ACGT", it[0]) || it[1] != '+' || !(letters || digits(code, 9)) || m.n_codes == mmd::MAX_CODES)
+      if (it.size() < 3 || !strchr("ACGT", it[0]) || it[1] != '+' || !(letters || integer_value(code, 9).ok) || m.n_codes == mmd::MAX_CODES)
         die("--mods takes 1 to 4 comma-separated items like C+m, C+h, A+a or C+21839 (a base of A C G T, '+', lower-case letters or a ChEBI number), not '" + list + "'");
       for (int k = 0; k < m.n_codes; ++k) if (m.code_base[k] == (uint8_t)it[0] && m.code_name[k] == code) die("--mods: the item " + it + " is given twice");
       m.code_base[m.n_codes] = (uint8_t)it[0]; m.code_name[m.n_codes++] = code;
@@ -49,14 +48,16 @@ ModsOpts mods_options(const Options& o) {
   if (o.v.count("mod-min-ml")) {
     const std::string& v = o.v.at("mod-min-ml");
     if (!m.on) die("--mod-min-ml needs --mods");
-    if (!digits(v, 3) || std::stoi(v) > 255) die("--mods: --mod-min-ml takes an integer from 0 to 255, not '" + v + "'");
-    m.min_ml = std::stoi(v);
+    const IntegerValue x = integer_value(v, 3);
+    if (!x.ok || x.value > 255) die("--mods: --mod-min-ml takes an integer from 0 to 255, not '" + v + "'");
+    m.min_ml = (int)x.value;
   }
   if (o.v.count("mod-min-coverage")) {
     const std::string& v = o.v.at("mod-min-coverage");
     if (!m.on) die("--mod-min-coverage needs --mods");
-    if (!digits(v, 9) || std::stoll(v) < 1) die("--mods: --mod-min-coverage takes an integer from 1 to 999999999, not '" + v + "'");
-    m.min_coverage = std::stoll(v);
+    const IntegerValue x = integer_value(v, 9);
+    if (!x.ok || x.value < 1) die("--mods: --mod-min-coverage takes an integer from 1 to 999999999, not '" + v + "'");
+    m.min_coverage = (long long)x.value;
   }
   return m;
 }

@@ -22,8 +22,6 @@ struct MotifOpts {
   std::string text[mmt::MAX_MOTIFS];                               // the letters as given
   std::vector<int32_t> off{0}, pos; std::vector<uint8_t> mask;     // as mm_mod_motifs takes them
 };
-// the flag under whose name a run with --mods is refused
-const char* modflag(const Options& o) { return o.v.count("mod-motifs") ? "--mod-motifs" : "--mods"; }
 // own reverse complement as a sequence of letter sets (whatever the offset)
 bool motif_own_reverse_complement(const std::string& letters) {
   for (size_t i = 0; i < letters.size(); ++i)
@@ -43,11 +41,11 @@ MotifOpts motif_options(const Options& o, const ModsOpts& mo) {
     const std::string it = list.substr(a, e - a);
     const size_t colon = it.find(':');
     const std::string letters = it.substr(0, colon), num = colon == std::string::npos ? "" : it.substr(colon + 1);
-    if (letters.empty() || letters.size() > (size_t)mmt::MAX_LEN || letters.find_first_not_of("ACGTRYSWKMBDHVN") != std::string::npos || num.empty() || num.size() > 2 ||
-        num.find_first_not_of("0123456789") != std::string::npos || m.n == mmt::MAX_MOTIFS)
+    if (letters.empty() || letters.size() > (size_t)mmt::MAX_LEN || letters.find_first_not_of("ACGTRYSWKMBDHVN") != std::string::npos ||
+        !integer_value(num, 2).ok || m.n == mmt::MAX_MOTIFS)
       die("--mod-motifs takes 1 to 8 comma-separated items MOTIF:OFFSET (1 to 32 IUPAC letters of ACGTRYSWKMBDHVN, ':', the 0-based place of the modified base), not '" + it + "' in '" +
           list + "'");
-    const int pos = std::stoi(num);
+    const int pos = (int)integer_value(num, 2).value;
     if (pos >= (int)letters.size()) die("--mod-motifs: the item " + it + ": the offset " + num + " is not inside the motif's " + std::to_string(letters.size()) + " letters");
     if (!strchr("ACGT", letters[(size_t)pos])) die("--mod-motifs: the item " + it + ": the modified base " + std::string(1, letters[(size_t)pos]) + " is not one of A C G T");
     if (std::find(mo.code_base, mo.code_base + mo.n_codes, (uint8_t)letters[(size_t)pos]) == mo.code_base + mo.n_codes)
@@ -60,11 +58,9 @@ MotifOpts motif_options(const Options& o, const ModsOpts& mo) {
   }
   if (o.v.count("mod-motif-min-frac")) {
     const std::string& v = o.v.at("mod-motif-min-frac");
-    const bool decimal = !v.empty() && v.size() <= 32 && v.find_first_not_of("0123456789.") == std::string::npos && v.find_first_of("0123456789") != std::string::npos &&
-                         std::count(v.begin(), v.end(), '.') <= 1;
-    const double x = decimal ? strtod(v.c_str(), nullptr) : -1;
-    if (!decimal || !(x >= 0.0 && x <= 1.0)) die("--mod-motifs: --mod-motif-min-frac takes a decimal from 0 to 1, not '" + v + "'");
-    m.min_frac = x;
+    const DecimalValue x = decimal_value(v);
+    if (!x.ok || !(x.value >= 0.0 && x.value <= 1.0)) die("--mod-motifs: --mod-motif-min-frac takes a decimal from 0 to 1, not '" + v + "'");
+    m.min_frac = x.value;
   }
   if (o.v.count("mod-motif-combine-strands")) {
     for (int k = 0; k < m.n; ++k)

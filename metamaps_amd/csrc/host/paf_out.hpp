@@ -2,7 +2,7 @@
 //   readID  L  0  L  +|-  contigID  contigLen  first  last+1  n_eq  n_eq+n_X+n_I+n_D  255  NM:i:d  cg:Z:<runs with = X I D>
 // The read is aligned whole (query start 0, end L); first / last+1 are the alignment's 0-based half-open contig coordinates; for strand - the CIGAR is that
 // of the reverse-complemented read along the forward contig, as PAF has it.  A mapping that is not aligned (NA NA NA in .editDistances) has no line.
-// One call (mm_mapping_align, map_outputs.hpp) on the context that mapped the batch gives d, first, last and the runs, fetched once (BatchAlignment):
+// One call (mm_mapping_align, batch_outputs.hpp) on the context that mapped the batch gives d, first, last and the runs, fetched once (BatchAlignment):
 // the lines of PREFIX.editDistances (edit_dist.hpp: the bytes of a run with --edit-distance alone), the lines of PREFIX.paf and the records of
 // PREFIX.bam (bam_out.hpp) come from the same answer, nothing is aligned twice.  Text only: nothing here calls the device.
 #pragma once

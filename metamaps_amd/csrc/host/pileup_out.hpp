@@ -8,7 +8,7 @@
 //   PREFIX.pileup.contigs  one line per contig with a contributing alignment, in the reference's order: contigID  length  alignments  covered  sumDepth
 //   primary                a read's aligned record without 0x100 in bam_fields' flags (bam_out.hpp): under --all a read counts once.
 //   accumulator            a batch's (key, count) pairs and the (contig, first, last) of its contributing alignments are appended under a mutex; above
-//                          MM_PILEUP_MERGE_PAIRS pairs (64 * 2^20) the pairs are replaced by their mm_pileup_merge (map_outputs.hpp).
+//                          MM_PILEUP_MERGE_PAIRS pairs (64 * 2^20) the pairs are replaced by their mm_pileup_merge (batch_outputs.hpp).
 // Text, arrays and the option values only (the key's fields: mm_pileup_core.hpp, plain host code here): nothing here calls the device.
 #pragma once
 #include "../mm_pileup_core.hpp"
@@ -22,15 +22,16 @@ namespace {
 
 // --pileup-min-count N, --pileup-min-frac F: validated before any work; refused without --pileup
 // --base-qualities, --min-base-quality Q (QualOpts, cli_common.hpp): Q an integer 0..93, which implies --base-qualities and needs an output that counts evidence;
-// --base-qualities alone needs one that uses the qualities (--bam, --error-profile).  (The refusals by sub-command and by --hpc are main's, under the flag's own name.)
+// --base-qualities alone needs one that uses the qualities (--bam, --error-profile).  (The refusals by sub-command and by --hpc are output_plan's, under the flag's own name.)
 QualOpts qual_options(const Options& o) {
   QualOpts q;
   q.keep = o.v.count("base-qualities") != 0;
   if (o.v.count("min-base-quality")) {
     const std::string& v = o.v.at("min-base-quality");
-    if (v.empty() || v.size() > 2 || v.find_first_not_of("0123456789") != std::string::npos || std::stoi(v) > 93) die("--min-base-quality takes an integer from 0 to 93, not '" + v + "'");
+    const IntegerValue x = integer_value(v, 2);
+    if (!x.ok || x.value > 93) die("--min-base-quality takes an integer from 0 to 93, not '" + v + "'");
     if (!o.v.count("pileup") && !o.v.count("vcf") && !o.v.count("consensus")) die("--min-base-quality needs --pileup, --vcf or --consensus: nothing else counts a base's evidence");
-    q.min_base_quality = std::stoi(v); q.keep = true;
+    q.min_base_quality = (int)x.value; q.keep = true;
   } else if (q.keep && !o.v.count("bam") && !o.v.count("error-profile") && !reads_out_asked(o))
     die("--base-qualities needs --bam or --min-base-quality (or --error-profile, --extract-unmapped, --extract-mapped, --extract-taxa, --deplete-taxa): nothing else would use the qualities");
   return q;
@@ -42,18 +43,16 @@ PileupOpts pileup_options(const Options& o) {
   if (o.v.count("pileup-min-count")) {
     const std::string& v = o.v.at("pileup-min-count");
     if (!p.on) die("--pileup-min-count needs --pileup");
-    if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos || std::stoll(v) < 1)
-      die("--pileup: --pileup-min-count takes an integer from 1 to 999999999, not '" + v + "'");
-    p.min_count = std::stoll(v);
+    const IntegerValue x = integer_value(v, 9);
+    if (!x.ok || x.value < 1) die("--pileup: --pileup-min-count takes an integer from 1 to 999999999, not '" + v + "'");
+    p.min_count = (long long)x.value;
   }
   if (o.v.count("pileup-min-frac")) {
     const std::string& v = o.v.at("pileup-min-frac");
     if (!p.on) die("--pileup-min-frac needs --pileup");
-    const bool decimal = !v.empty() && v.size() <= 32 && v.find_first_not_of("0123456789.") == std::string::npos && v.find_first_of("0123456789") != std::string::npos &&
-                         std::count(v.begin(), v.end(), '.') <= 1;
-    const double x = decimal ? strtod(v.c_str(), nullptr) : -1;
-    if (!decimal || !(x >= 0.0 && x <= 1.0)) die("--pileup: --pileup-min-frac takes a decimal from 0 to 1, not '" + v + "'");
-    p.min_frac = x;
+    const DecimalValue x = decimal_value(v);
+    if (!x.ok || !(x.value >= 0.0 && x.value <= 1.0)) die("--pileup: --pileup-min-frac takes a decimal from 0 to 1, not '" + v + "'");
+    p.min_frac = x.value;
   }
   return p;
 }

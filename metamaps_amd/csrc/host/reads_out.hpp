@@ -1,6 +1,6 @@
 // mapDirectly --extract-unmapped, --extract-mapped, --extract-taxa LIST, --deplete-taxa LIST (not in the reference, whose util/extractReads.pl re-reads the
 // FASTQ on the host): selected reads of every query file as BGZF FASTQ (under --base-qualities) or FASTA beside PREFIX, written on the device from the
-// batch's packed reads (mm_reads_encode, csrc/mm_reads_out_core.hpp; the call sits in map_outputs.hpp).  Here: the options, the table of labels and
+// batch's packed reads (mm_reads_encode, csrc/mm_reads_out_core.hpp; the call sits in batch_outputs.hpp).  Here: the options, the table of labels and
 // suffixes, and which reads of a batch each file takes.  No device call.
 //   unmapped   every read without a line in PREFIX: the reads .meta counts as ReadsTooShort and as ReadsNotMapped
 //   mapped     every read with at least one line

@@ -1,4 +1,4 @@
-// The files mapDirectly writes beside PREFIX when asked to: one table that MapRun's workers (map_outputs.hpp) and writer go by.  No device call.
+// The files mapDirectly writes beside PREFIX when asked to: one table that MapRun's workers (batch_outputs.hpp) and writer go by.  No device call.
 #pragma once
 #include "cli_common.hpp"
 #include <array>
@@ -28,13 +28,13 @@ using SideSet = std::array<bool, N_SIDE>;
 
 inline bool reads_out_asked(const Options& o) { for (int s = 0; s < N_SIDE; ++s) if (!kSideFiles[s].aligned && o.v.count(kSideFiles[s].flag)) return true; return false; }
 // the rows a command line asks for: --paf and --bam imply --edit-distance (their alignment is the one whose distances that file lists)
-// --bam-sorted (bam_sort_out.hpp) is no row: its two files are written after the run's last batch; it implies --edit-distance too
-inline bool bam_sorted_of(const Options& o) { return o.v.count("bam-sorted") != 0; }
+// --bam-sorted (bam_sort_out.hpp) is no row: its two files are written after the run's last batch; it implies --edit-distance too.  (So do the outputs that
+// keep a table per query file, which have no row either: OutputPlan, output_plan.hpp, adds them.)
 inline SideSet side_files_of(const Options& o) {
   SideSet on{};
   for (int s = 0; s < N_SIDE; ++s) on[(size_t)s] = o.v.count(kSideFiles[s].flag) != 0;
   for (int s = 0; s < N_SIDE; ++s) if (on[(size_t)s] && kSideFiles[s].aligned) on[SIDE_EDIT] = true;   // (the read files need no alignment)
-  if (bam_sorted_of(o)) on[SIDE_EDIT] = true;
+  if (o.v.count("bam-sorted")) on[SIDE_EDIT] = true;
   return on;
 }
 

@@ -12,7 +12,7 @@
 //              Kept: count >= N (default 3) and count >= F * depth (default 0.2); mm_vcf_finish decides, on the first device, and hands back the
 //              reference bytes ref[pos .. pos + 25) that REF is printed from.
 //   accumulator  a batch's (w0, w1, count) triples are appended under a mutex, 20 bytes each; above MM_VCF_MERGE_PAIRS triples (64 * 2^20) they are replaced by
-//              their mm_vcf_merge (map_outputs.hpp).  The accumulator and the intervals of the contributing alignments are pileup_out.hpp's: one copy of the intervals serves both.
+//              their mm_vcf_merge (batch_outputs.hpp).  The accumulator and the intervals of the contributing alignments are pileup_out.hpp's: one copy of the intervals serves both.
 // Text, arrays and the option values only (the key's fields: mm_vcf_core.hpp, plain host code here): nothing here calls the device.
 #pragma once
 #include "../mm_vcf_core.hpp"
@@ -28,18 +28,16 @@ VcfOpts vcf_options(const Options& o) {
   if (o.v.count("vcf-min-count")) {
     const std::string& v = o.v.at("vcf-min-count");
     if (!p.on) die("--vcf-min-count needs --vcf");
-    if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos || std::stoll(v) < 1)
-      die("--vcf: --vcf-min-count takes an integer from 1 to 999999999, not '" + v + "'");
-    p.min_count = std::stoll(v);
+    const IntegerValue x = integer_value(v, 9);
+    if (!x.ok || x.value < 1) die("--vcf: --vcf-min-count takes an integer from 1 to 999999999, not '" + v + "'");
+    p.min_count = (long long)x.value;
   }
   if (o.v.count("vcf-min-frac")) {
     const std::string& v = o.v.at("vcf-min-frac");
     if (!p.on) die("--vcf-min-frac needs --vcf");
-    const bool decimal = !v.empty() && v.size() <= 32 && v.find_first_not_of("0123456789.") == std::string::npos && v.find_first_of("0123456789") != std::string::npos &&
-                         std::count(v.begin(), v.end(), '.') <= 1;
-    const double x = decimal ? strtod(v.c_str(), nullptr) : -1;
-    if (!decimal || !(x >= 0.0 && x <= 1.0)) die("--vcf: --vcf-min-frac takes a decimal from 0 to 1, not '" + v + "'");
-    p.min_frac = x;
+    const DecimalValue x = decimal_value(v);
+    if (!x.ok || !(x.value >= 0.0 && x.value <= 1.0)) die("--vcf: --vcf-min-frac takes a decimal from 0 to 1, not '" + v + "'");
+    p.min_frac = x.value;
   }
   return p;
 }

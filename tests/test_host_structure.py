@@ -2,6 +2,7 @@
 one 797-line function, classify_one 280; round 6: map_batch 997), and none of the device allocator (mm_alloc.hpp and the two headers beside it) above 60; no file of
 metamaps_amd/csrc/host/ above 800 lines (the CLI was one file of 2 488; map_run.hpp later stood at 999 by squeezing its lines) and no line of them above 200 characters.  CPU."""
 import os
+import re
 import subprocess
 import sys
 
@@ -25,6 +26,30 @@ def test_no_function_above_200_lines_in_the_host_program():
     assert not any("load_reference" in ln for ln in out.split("\n")[:12]), out     # (once the longest host function of the CLI, 137 lines: now ref_loader.hpp's pieces)
     parsed = out.strip().split("\n")[-4].split()                   # "library files: NAME.hip ..."
     assert parsed[:2] == ["library", "files:"] and "mm_merge.hip" in parsed and "mm_api.hip" in parsed, out   # (the chunk merge is library host code under the 200-line rule)
+
+
+HOST = os.path.join(ROOT, "metamaps_amd", "csrc", "host")
+
+
+def host_sources():
+    return {n: open(os.path.join(HOST, n)).read() for n in sorted(os.listdir(HOST)) if n.endswith((".hpp", ".cpp"))}
+
+
+def test_the_run_outputs_are_declared_once():
+    """What the command line asks mapDirectly to write is parsed and combined in output_plan.hpp alone: main and MapRun name no output's option struct and no flag
+    helper, nobody writes an implied --edit-distance back into the options, the precedence of the flag a refusal names and the decimal validator stand in one
+    file each, and map_run.hpp is shorter than the 796 lines it had when every new output took a line of it."""
+    src = host_sources()
+    for name in ("map_run.hpp", "metamaps_main.cpp"):
+        code = re.sub(r"//[^\n]*", "", src[name])
+        for ident in ("PileupOpts", "VcfOpts", "ConsOpts", "ModsOpts", "MotifOpts", "DepthOpts", "errprof_of", "errprof_or", "modflag", "bam_sorted_of"):
+            assert not re.search(r"\b" + ident + r"\b", code), (name, ident)
+    assert not [n for n, s in src.items() if 'o.v["edit-distance"] =' in s]
+    assert [n for n, s in src.items() if '"--consensus" :' in s] == ["output_plan.hpp"]
+    assert [n for n, s in src.items() if "const bool decimal" in s] == ["cli_common.hpp"]
+    assert 200 < src["map_run.hpp"].count("\n") < 796
+    plan = src["output_plan.hpp"]                                  # device-free: none of the headers that name a call of the C ABI, directly
+    assert not re.search(r'#include "(bam_sort_out|batch_outputs|run_outputs|cli_device|bam_out|paf_out|edit_dist)\.hpp"', plan) and "metamaps_hip.h" not in plan
 
 
 def test_the_c_surface_holds_no_kernels_no_rccl_and_no_stand_in_declarations():
