@@ -2,7 +2,7 @@
 #pragma once
 #include "bam_out.hpp"
 #include "bam_sort_out.hpp"
-#include "classify_run.hpp"
+#include "mapping_lines.hpp"
 #include "cli_device.hpp"
 #include "cli_switches.hpp"
 #include "edit_dist.hpp"

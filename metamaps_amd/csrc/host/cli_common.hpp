@@ -47,6 +47,14 @@ template <typename F> void on_each(size_t n, F&& fn) {           // fn(i) for i 
   for (auto& t : th) t.join();
 }
 
+// the same with fn(0) on the calling thread, which goes on with whatever fn(0) does behind its share while the others run
+template <typename F> void on_each_caller_first(size_t n, F&& fn) {
+  std::vector<std::thread> th;
+  for (size_t i = 1; i < n; ++i) th.emplace_back([&fn, i] { fn(i); });
+  fn(0);
+  for (auto& t : th) t.join();
+}
+
 uint64_t file_size(const std::string& f) {                       // commonFunc.hpp:211-231
   struct stat st; if (stat(f.c_str(), &st) != 0) die("Cannot open " + f + " for size determination.");
   return (uint64_t)st.st_size;
@@ -85,9 +93,9 @@ struct QualOpts { bool keep = false; int min_base_quality = 0; };
 // a median identity below T (a decimal in [0, 1], the script's --identityThreshold) are removed and their reads set to unclassified in PREFIX.EM-filtered*;
 // --refit (not in the reference) also runs the EM again without the removed genomes' mappings.  Off without the flag: nothing changes and no file appears.
 struct IdentOpts { bool on = false, refit = false; double T = 0; };
-BootOpts boot_options(const Options& o);                         // (metamaps_main.cpp: they end the program on a malformed value)
-LcaOpts lca_options(const Options& o);
-GeneOpts gene_options(const Options& o);
-IdentOpts ident_options(const Options& o);
+// What `classify` and `mapDirectly --then-classify` take from the command line beside the files; --minreads N: the reads a taxon needs to serve as the
+// reference distribution of PREFIX.EM.evidenceUnknownSpecies (parseCmdArgs.hpp:462-471)
+struct ClassifyOpts { BootOpts boot; LcaOpts lca; GeneOpts genes; IdentOpts ident; size_t minReadsU = 10000; };
+ClassifyOpts classify_options(const Options& o, const std::string& mode);   // (metamaps_main.cpp: it ends the program on a malformed value or a flag outside its sub-commands)
 
 }  // namespace

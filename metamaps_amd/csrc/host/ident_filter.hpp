@@ -1,7 +1,7 @@
 // classify --min-identity T [--refit] (the reference's util/filterLowIdentityEntities.pl; DESIGN.md section 4, "Identity filter"): the host side of the
 // identity filter.  The arithmetic — every read's largest identity, the genomes' median best identities, which genomes go, the EM problem that is
 // left — runs on the first device (mm_ident_filter); here are the identity field of a mapping line, the text of PREFIX.extractedIdentities placed by
-// the device's order, and the filtered WIMP.  ClassifyRun (classify_run.hpp) owns the lines and calls these.  No device call in here.
+// the device's order, and the filtered WIMP.  ClassifyRun (classify_run.hpp) owns the lines; its writers (classify_outputs.hpp) call these.  No device call in here.
 #pragma once
 #include "taxonomy.hpp"
 #include <cstring>

@@ -2,7 +2,7 @@
 #pragma once
 #include "../cpu_budget.hpp"
 #include "../task_pool.hpp"
-#include "classify_run.hpp"
+#include "mapping_lines.hpp"
 #include "cli_switches.hpp"
 #include "fast_format.hpp"
 #include <cmath>

@@ -731,7 +731,7 @@ struct MapRun {
     if (!o.v.count("then-classify") || only_index) return;
     if (reader.th.joinable()) reader.th.join();
     const EmReduce reduce = o.em_host ? EmReduce::Host : ((devs.size() > 1 || o.v.count("gpus") || o.v.count("devices")) ? EmReduce::Rccl : EmReduce::None);
-    const size_t minReadsU = o.v.count("minreads") ? std::stoull(o.v.at("minreads")) : 10000;   // parseCmdArgs.hpp:462-471
+    const ClassifyOpts copts = classify_options(o, mode);         // (main has refused what is malformed)
     // the last prefix ends the process from inside classify_one, as the last file of `classify` does: everything is written and closed, the
     // gigabyte of line tables and text is not taken apart first (MM_CLI_FULL_TEARDOWN=1: the orderly way)
     const std::function<void()> leave = [&] { pc.lap("9 classify"); pc.report(); };
@@ -740,8 +740,7 @@ struct MapRun {
       KeptLines kl; kl.cname = &cname;
       if (keep_lines && fi < kept.size())
         for (const auto& d : kept[fi]) kl.parts.push_back(KeptLines::Part{d->text.data(), d->meta.data(), d->meta.size(), d->off.data(), d->lens.size()});
-      classify_one(devs, reduce, prefixes[fi], o.v.at("then-classify"), minReadsU, last ? leave : std::function<void()>(), nullptr, keep_lines ? &kl : nullptr,
-                   boot_options(o), lca_options(o), gene_options(o), ident_options(o), sw);
+      classify_one(devs, reduce, prefixes[fi], o.v.at("then-classify"), copts, ClassifyHooks{last ? leave : std::function<void()>(), nullptr}, keep_lines ? &kl : nullptr, sw);
       if (keep_lines && fi < kept.size()) kept[fi].clear();
       for (auto& d : devs) mm_comm_destroy(d.ctx);
       pc.lap("9 classify");

@@ -338,6 +338,29 @@ IdentOpts ident_options(const Options& o) {
   return f;
 }
 
+// Everything classify and mapDirectly --then-classify take beside their files (ClassifyOpts, cli_common.hpp), each flag refused outside those two
+// in the order of the flags here; both callers of classify_one parse through this
+ClassifyOpts classify_options(const Options& o, const std::string& mode) {
+  const bool classifies = mode == "classify" || (mode == "mapDirectly" && o.v.count("then-classify"));
+  ClassifyOpts c;
+  c.boot = boot_options(o);
+  if (c.boot.B && !classifies) die("--bootstrap needs classify or mapDirectly --then-classify");
+  c.lca = lca_options(o);
+  if (c.lca.on && !classifies) die("--lca needs classify or mapDirectly --then-classify");
+  c.genes = gene_options(o);
+  if (c.genes.on && !classifies) die("--genes needs classify or mapDirectly --then-classify");
+  if (c.genes.on && (mode == "mapDirectly" || o.v.count("DB"))) {  // (a database without gene annotations: said before any work)
+    const std::string& db = mode == "classify" ? o.v.at("DB") : o.v.at("then-classify");
+    struct stat probe;
+    if (stat(gene::annotations_path(db).c_str(), &probe) != 0) die("--genes: please supply a gene-annotated database (file " + gene::annotations_path(db) + " not found).");
+    if (stat(gene::proteins_path(db).c_str(), &probe) != 0) die("--genes: please supply a protein annotation file (file " + gene::proteins_path(db) + " not found).");
+  }
+  c.ident = ident_options(o);
+  if ((c.ident.on || c.ident.refit) && !classifies) die("--min-identity and --refit need classify or mapDirectly --then-classify");
+  if ((mode == "classify" || o.v.count("then-classify")) && o.v.count("minreads")) c.minReadsU = std::stoull(o.v.at("minreads"));
+  return c;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -350,21 +373,7 @@ int main(int argc, char** argv) {
   if (mm::env_strict()) { const std::string bad = mm::env_unknown(); if (!bad.empty()) die("unknown MM_* environment switch(es): " + bad + " (MM_STRICT_ENV is set; see INTEGRATION.md)"); }
   const CliSwitches sw;                                           // the environment, read once (cli_switches.hpp)
   const Options o = parse(argc, argv);
-  const BootOpts boot = boot_options(o);                          // (validated before any work)
-  if (boot.B && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--bootstrap needs classify or mapDirectly --then-classify");
-  const LcaOpts lca = lca_options(o);
-  if (lca.on && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--lca needs classify or mapDirectly --then-classify");
-  const GeneOpts genes = gene_options(o);
-  if (genes.on && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify"))) die("--genes needs classify or mapDirectly --then-classify");
-  if (genes.on && (mode == "mapDirectly" || o.v.count("DB"))) {  // (a database without gene annotations: said before any work)
-    const std::string& db = mode == "classify" ? o.v.at("DB") : o.v.at("then-classify");
-    struct stat probe;
-    if (stat(gene::annotations_path(db).c_str(), &probe) != 0) die("--genes: please supply a gene-annotated database (file " + gene::annotations_path(db) + " not found).");
-    if (stat(gene::proteins_path(db).c_str(), &probe) != 0) die("--genes: please supply a protein annotation file (file " + gene::proteins_path(db) + " not found).");
-  }
-  const IdentOpts identf_opts = ident_options(o);
-  if ((identf_opts.on || identf_opts.refit) && mode != "classify" && !(mode == "mapDirectly" && o.v.count("then-classify")))
-    die("--min-identity and --refit need classify or mapDirectly --then-classify");
+  const ClassifyOpts copts = classify_options(o, mode);           // (validated before any work)
   if (o.v.count("compress-output") && mode != "mapDirectly" && mode != "mapAgainstIndex") die("--compress-output belongs to mapDirectly and mapAgainstIndex");
   // every output of mapDirectly: parsed once, and refused under its own flag's name outside mapDirectly, with --hpc and with a sharded or streamed index (output_plan.hpp)
   const OutputPlan plan = output_plan(o, mode);
@@ -395,11 +404,11 @@ int main(int argc, char** argv) {
     };
     // an explicit --gpus 1 also goes through RCCL (one rank); --em-host-reduce: the ranks' sums are added on the host (test hook: ranks may share a device)
     const EmReduce reduce = o.em_host ? EmReduce::Host : ((devs.size() > 1 || o.v.count("gpus") || o.v.count("devices")) ? EmReduce::Rccl : EmReduce::None);
-    const size_t minReadsU = o.v.count("minreads") ? std::stoull(o.v.at("minreads")) : 10000;   // parseCmdArgs.hpp:462-471
     const std::vector<std::string> files = split(o.v.at("mappings"), ",");
     for (size_t fi = 0; fi < files.size(); ++fi) {
-      if (fi + 1 == files.size()) classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, [&] { since("mappings file done"); }, need_devices, nullptr, boot, lca, genes, identf_opts, sw);
-      else classify_one(devs, reduce, files[fi], o.v.at("DB"), minReadsU, nullptr, need_devices, nullptr, boot, lca, genes, identf_opts, sw);
+      ClassifyHooks hooks{nullptr, need_devices};
+      if (fi + 1 == files.size()) hooks.leave_now = [&] { since("mappings file done"); };
+      classify_one(devs, reduce, files[fi], o.v.at("DB"), copts, hooks, nullptr, sw);
       need_devices();
       for (auto& d : devs) mm_comm_destroy(d.ctx);
       since("mappings file done");

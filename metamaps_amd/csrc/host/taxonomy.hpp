@@ -119,7 +119,15 @@ std::map<std::string, WimpLevel> wimp_em_frequencies(const Taxonomy& T, const st
   return W;
 }
 
-void write_wimp(const std::string& fn, const Taxonomy& T, const std::map<std::string, double>& freq, const std::map<std::string, size_t>& reads,
+// cleanF (fEM.h:1135-1163): taxa whose frequency lies below 0.9 of one read's share of the n_mapped reads and that no read has as its best mapping are
+// dropped, the rest made to sum to 1 (added in the map's order)
+void clean_frequencies(std::map<std::string, double>& f, const std::map<std::string, size_t>& readsPer, size_t n_mapped) {
+  const double minF = 0.9 * (1.0 / (double)n_mapped);
+  for (auto it = f.begin(); it != f.end();) if (it->second < minF && !readsPer.count(it->first)) it = f.erase(it); else ++it;
+  double s = 0; for (auto& e : f) s += e.second; for (auto& e : f) e.second /= s;
+}
+
+void write_wimp(const std::string& fn,const Taxonomy& T, const std::map<std::string, double>& freq, const std::map<std::string, size_t>& reads,
                 size_t nTotal, size_t nUnmapped, size_t nTooShort) {   // fEM.h:52-215
   const std::set<std::string> levels{"species", "genus", "family", "order", "phylum", "superkingdom"};
   std::map<std::string, WimpLevel> W = wimp_em_frequencies(T, freq, reads);

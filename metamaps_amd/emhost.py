@@ -6,7 +6,7 @@ csrc/host has the same logic).  Mirrors meta::doEM's data preparation and loop c
   getMappingLocations           fEM.h:234    per (read, taxon): number of possible mapping locations
   doEM loop                     fEM.h:501    f <- normalised sums; stop when ll gain <= 1 and relative < 1e-4
 
-TEST-SIDE code: the product (libmetamaps_hip.so, the `metamaps` CLI) never imports this module; its `classify` is C++ (csrc/host/classify_run.hpp, ClassifyRun).
+TEST-SIDE code: the product (libmetamaps_hip.so, the `metamaps` CLI) never imports this module; its `classify` is C++ (csrc/host/classify_run.hpp, ClassifyRun; the data preparation: csrc/host/classify_tables.hpp, held against load_problem by tests/test_mapping_lines.py).
 """
 from __future__ import annotations
 

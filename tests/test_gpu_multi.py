@@ -302,7 +302,7 @@ def test_records_gathered_from_parts_equal_device_concat(oracle_lib, monkeypatch
 
 # ---- the multi-rank classify bookkeeping (shard ranges, shard-local offsets, best-mapping rebasing, final f), everything around the
 # collective: `--em-host-reduce` adds the ranks' partial sums on the host in rank order (what the all-reduce delivers), so several
-# ranks may share the one GPU of the test box (run_em_sharded, csrc/host/classify_run.hpp; fEM.h:583-600, :1229)
+# ranks may share the one GPU of the test box (run_em_sharded, csrc/host/em_sharded.hpp; fEM.h:583-600, :1229)
 def _classify(prefix, db, extra, env=None):
     p = subprocess.run([CLI, "classify", "--DB", db, "--mappings", prefix, "--minreads", "3"] + extra, capture_output=True, timeout=900,
                        env=dict(os.environ, **(env or {})))

@@ -52,6 +52,27 @@ def test_the_run_outputs_are_declared_once():
     assert not re.search(r'#include "(bam_sort_out|batch_outputs|run_outputs|cli_device|bam_out|paf_out|edit_dist)\.hpp"', plan) and "metamaps_hip.h" not in plan
 
 
+def test_classify_is_split_by_stage_and_its_first_half_is_device_free():
+    """classify_run.hpp (788 lines, one struct of 35 members, when this was written) keeps the run and its device calls; the lines, the tables, the EM driver and
+    the writers have a header each, the first two without the C ABI (tests/test_mapping_lines.cpp compiles them alone); the formatter of the mapping lines and a
+    batch's outputs take LineMeta and KeptLines without the rest of classify; cleanF stands once, and so does the length of a line's read ID."""
+    src = host_sources()
+    new = ("mapping_lines.hpp", "classify_tables.hpp", "em_sharded.hpp", "classify_outputs.hpp")
+    assert 100 < src["classify_run.hpp"].count("\n") <= 450
+    for name in new:
+        assert 20 < src[name].count("\n") <= 400, name
+    for name in ("mapping_lines.hpp", "classify_tables.hpp"):
+        assert "metamaps_hip.h" not in src[name] and not re.search(r'#include "(cli_device|em_sharded|classify_run)\.hpp"', src[name]), name
+    assert re.findall(r'#include "([^"]+)"', src["mapping_lines.hpp"]) == ["cli_common.hpp"]
+    for name in ("map_format.hpp", "batch_outputs.hpp"):
+        assert '#include "classify_run.hpp"' not in src[name] and '#include "mapping_lines.hpp"' in src[name], name
+    assert [n for n, s in src.items() if "const double minF" in s] == ["taxonomy.hpp"]
+    assert not [n for n, s in src.items() if "memchr(B.p, ' '" in s or "memchr(A.p, ' '" in s]
+    assert [n for n, s in src.items() if "struct ClassifyOpts" in s] == ["cli_common.hpp"]
+    assert [n for n, s in src.items() if re.search(r"\bClassifyOpts classify_options\(.*\) \{", s)] == ["metamaps_main.cpp"]
+    assert [n for n, s in src.items() if 'o.v.at("minreads")' in s] == ["metamaps_main.cpp"] and src["metamaps_main.cpp"].count('o.v.at("minreads")') == 1
+
+
 def test_the_c_surface_holds_no_kernels_no_rccl_and_no_stand_in_declarations():
     """mm_api.hip turns exceptions into status codes and owns handle lifetimes: device code and collectives live in the units it calls, and what
     it calls is declared in their headers, where the compiler checks the declarations against the definitions."""
